@@ -250,6 +250,42 @@ def parity_in_run(gpr, ctx, w, theta, Xs, timed_model, O, ref):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+KINV_SAMPLE = 1 << 20  # K^-1 entries kept by --dump-outputs (8 MB in f64; the full matrix is 128 MB at n = 4096)
+
+
+def model_outputs(fk):
+    """What a caller of FittedKernel.new receives, as float64 arrays: theta, lml, alpha and K^-1.  K^-1 is cut to a fixed
+    sample of KINV_SAMPLE entries (row-major flat indices from a seeded generator, sorted) when it is larger than that; the
+    indices are written beside it."""
+    import numpy as np
+
+    alpha, kinv = fk.arrays()
+    out = {"theta": np.asarray(fk.theta, np.float64), "lml": np.array([fk.lml], np.float64), "alpha": alpha.astype(np.float64)}
+    flat = kinv.astype(np.float64).ravel()
+    if flat.size > KINV_SAMPLE:
+        idx = np.sort(np.random.default_rng(20240917).choice(flat.size, KINV_SAMPLE, replace=False))
+        out["kinv_sample"], out["kinv_sample_index"] = flat[idx], idx.astype(np.float64)
+    else:
+        out["kinv"] = kinv.astype(np.float64)
+    return out
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, float32 / float64 only, at most DUMP_LIMIT_BYTES in all."""
+    import numpy as np
+
+    arrays = {k: np.ascontiguousarray(v) for k, v in arrays.items()}
+    for k, v in arrays.items():
+        assert v.dtype in (np.float32, np.float64), (k, v.dtype)
+    total = sum(v.nbytes for v in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit"
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, f"{k}.npy"), v)
+    log(f"wrote {len(arrays)} arrays ({total / 1e6:.1f} MB) to {path}")
+
+
 def self_launch(args):
     """`--gpus N` without a torchrun environment: start the N ranks ourselves (nothing in this process has touched a GPU),
     relay their output, return their exit code."""
@@ -383,18 +419,26 @@ def run_c3(args):
     starts = synth.restart_points("C3", w["lo"], w["hi"], 7)
     ctx = gpr.Context(device_ids=list(range(G)))
 
-    def step():
+    kept = []
+
+    def step(keep=False):
         fk = gpr.FittedKernel.new(X, y, w["theta0"], w["lo"], w["hi"], starts, nu=2.5, ctx=ctx, maxeval=EVALS_PER_RUN, fixed_work=True)
         out = (fk.lml, fk.n_evals, fk.n_not_pd)
-        fk.release()
+        if keep:
+            kept.append(fk)  # --dump-outputs: the last timed fit is read back and released after the timed region
+        else:
+            fk.release()
         return out
 
     for _ in range(args.warmup):
         step()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        lml, n_evals, n_not_pd = step()
+    for i in range(args.steps):
+        lml, n_evals, n_not_pd = step(keep=bool(args.dump_outputs) and i == args.steps - 1)
     elapsed = time.perf_counter() - t0
+    if kept:
+        dump_outputs(args.dump_outputs, model_outputs(kept[0]))
+        kept[0].release()
     n, d = X.shape
     out = {
         "metric": "GP fits/sec (C3: rastrigin d=16, n=4096, f64, 8 optimiser runs sharded over the GPUs of one process)",
@@ -434,7 +478,12 @@ def main():
     ap.add_argument("--no-side-lines", action="store_true",
                     help="skip the f32 / small-n / converged-fit side lines (profiling runs: the kernel statistics then hold the headline workload only)")
     ap.add_argument("--dry", action="store_true", help="launcher/harness rehearsal on CPU (gloo, no GPU work): prints the line with value 0")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (the fitted model and its predictions; "
+                         "a fixed sample of K^-1) as DIR/<name>.npy, float64; rank 0 only")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.workload == "C3" and not args.dry:
         return run_c3(args)
@@ -484,13 +533,16 @@ def main():
     ctx = gpr.Context(device_ids=[local_rank])
     fit_stats = {}
 
-    def step():
+    def step(keep=False):
         fk = gpr.FittedKernel.new(X, y, w["theta0"], w["lo"], w["hi"], starts, nu=2.5, ctx=ctx, maxeval=EVALS_PER_RUN,
                                   fixed_work=True)
         fit_stats["n_evals"], fit_stats["n_not_pd"] = fk.n_evals, fk.n_not_pd
         mean, var, _ = fk.predict(Xs)
         fit_stats["model"] = {"theta": fk.theta.copy(), "lml": fk.lml, "mean": mean, "var": var}  # what the parity leg checks afterwards
-        fk.release()
+        if keep:
+            fit_stats["kept"] = fk  # --dump-outputs: the last timed model is read back and released after the timed region
+        else:
+            fk.release()
         return mean, var
 
     log(f"{args.warmup} warm-up + {args.steps} timed fit+predict steps")
@@ -498,11 +550,16 @@ def main():
         step()
     D.barrier(dist)
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
+    for i in range(args.steps):
+        step(keep=bool(args.dump_outputs) and rank == 0 and i == args.steps - 1)
     D.barrier(dist)
     elapsed = D.max_over_ranks(dist, time.perf_counter() - t0)
     log(f"timed region done: {elapsed / args.steps * 1e3:.1f} ms per step")
+    if "kept" in fit_stats:
+        fk = fit_stats.pop("kept")
+        tm = fit_stats["model"]
+        dump_outputs(args.dump_outputs, dict(model_outputs(fk), mean=tm["mean"].astype(np.float64), var=tm["var"].astype(np.float64)))
+        fk.release()
 
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
@@ -637,18 +694,16 @@ def main():
             out["small_n_side_line"] = {"error": str(e)}
         if world == 1 and not args.no_side_lines:
             # replicas on ONE GPU: k independent fits side by side, one host thread each, in a child
-            # process of its own so that GPU_MAX_HW_QUEUES (HIP's hardware queues per device: streams that share one run one after
-            # the other) can be raised there without touching this process
+            # process of its own, with the runtime's hardware-queue settings as this process has them
             try:
                 conc = {}
                 for nn_, ks_ in ((128, "1 4 16"), (1024, "1 4")):
-                    env = dict(os.environ, GPU_MAX_HW_QUEUES="16")
                     cp = subprocess.run([sys.executable, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools", "concurrent_fits.py"), str(nn_)] + ks_.split(),
-                                        env=env, capture_output=True, text=True, timeout=300)
+                                        capture_output=True, text=True, timeout=300)
                     last = [l for l in cp.stdout.splitlines() if l.startswith("{")]
                     conc[f"n={nn_}"] = json.loads(last[-1]) if last else {"error": (cp.stderr or cp.stdout)[-300:]}
                 out["concurrent_fits_side_line"] = dict(conc, note="aggregate fixed-work fits/s of k host threads fitting on one context / one GPU (config M "
-                                                        "data cut to n rows, 3 runs x 150 evaluations each), GPU_MAX_HW_QUEUES=16; every concurrent fit is "
+                                                        "data cut to n rows, 3 runs x 150 evaluations each), hardware queues as the bench process has them; every concurrent fit is "
                                                         "compared bit for bit with the same fit alone")
             except Exception as e:
                 out["concurrent_fits_side_line"] = {"error": str(e)}

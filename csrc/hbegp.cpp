@@ -232,7 +232,7 @@ struct HostPool {
   }
 };
 static HostPool g_host_pool;
-// HIP maps its streams onto a few hardware queues per device (GPU_MAX_HW_QUEUES, default 4) in the order the streams are
+// HIP maps its streams onto a few hardware queues per device (4 by default) in the order the streams are
 // created, and two streams that share a queue run one after the other.  So the pool is keyed by what a stream is FOR: the
 // evaluation slots of a fit always get the same streams back (created first, on distinct queues), whatever a model's or the
 // block pool's stream does in between -- with ONE free list a fit's three slots got, every other fit, two streams of one queue

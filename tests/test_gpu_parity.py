@@ -430,8 +430,7 @@ def test_fresh_pool_blocks_are_cleared_before_their_first_writer(dtype, monkeypa
     devs = run()
     assert max(devs) <= tol, devs
     env = dict(os.environ, HBEGP_POOL_OLD_CLEAR="1")
-    for k in ("HBEGP_NO_GRAPH", "GPU_MAX_HW_QUEUES"):  # (tools/gpu_matrix.sh: the demonstration is about the shipped configuration)
-        env.pop(k, None)
+    env.pop("HBEGP_NO_GRAPH", None)  # (tools/gpu_matrix.sh: the demonstration is about the shipped configuration)
     cp = subprocess.run([sys.executable, os.path.join(os.path.dirname(os.path.abspath(__file__)), "pool_clear_scenario.py"), np.dtype(dtype).name],
                         env=env, capture_output=True, text=True, timeout=300)
     lines = [l for l in cp.stdout.splitlines() if l.startswith("{")]

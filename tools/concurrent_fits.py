@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """k independent fixed-work fits side by side on ONE GPU, one host thread each, one context (replicas).
 Usage: concurrent_fits.py n k [k ...]   -> aggregate fits/s per k, and whether every concurrent fit reproduced the solo fit's bits;
-the last line is the same as JSON.  HIP maps streams onto GPU_MAX_HW_QUEUES hardware queues (default 4) and streams that share a
-queue run one after the other: set GPU_MAX_HW_QUEUES >= 3 x fits (one stream per optimiser run; up to 128 rows one per fit)."""
+the last line is the same as JSON.  HIP maps streams onto a few hardware queues per device (4 by default) and streams that share
+a queue run one after the other (one stream per optimiser run; up to 128 rows one per fit)."""
 import json
 import os
 import sys
@@ -40,7 +40,7 @@ def fit():
 
 
 solo = fit()
-summary = {"n": n, "dtype": np.dtype(dtype).name, "gpu_max_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES", "default (4)"), "fits_per_s": {}, "bitwise_equal_to_solo": True}
+summary = {"n": n, "dtype": np.dtype(dtype).name, "fits_per_s": {}, "bitwise_equal_to_solo": True}
 for k in ks:
     reps = max(8, 24 // k) if n <= 256 else max(2, 8 // k)  # (small fits: rounds of several threads need a few rounds to fall into step)
     results = [[] for _ in range(k)]
