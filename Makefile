@@ -22,7 +22,7 @@ $(LIB): build/kernels.o build/hbegp.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -lpthread
 
 # experimental builds of the kernels (diagnostics only; loaded with HBEGP_LIB=build/var/libhbegp_<NAME>.so):
-#   make variant NAME=noinline DEFS="-DDAG_LEAF_NOINLINE=1"
+#   make variant NAME=stamp DEFS="-DDAG_STAMP_INNER"
 variant: build/hbegp.o
 	@mkdir -p build/var
 	$(HIPCC) $(CXXFLAGS) $(DEFS) -c csrc/kernels.hip -o build/var/kernels_$(NAME).o

@@ -16,7 +16,7 @@
 //     ONE agent-scope acquire (buffer_inv sc1: drops this CU's L1 lines), waits for it, and the workgroup meets at a
 //     barrier before any wave loads operands with plain loads.
 //   * Every wait is bounded (DagLaunch::wait_ticks of the constant 100 MHz clock; the host sets max(2 s, 200 x the plan's
-//     simulated makespan), HBEGP_DAG_WAIT_S overrides -- the clock keeps running while a queue is preempted): on expiry the task index is recorded, info becomes
+//     simulated makespan) -- the clock keeps running while a queue is preempted): on expiry the task index is recorded, info becomes
 //     DAG_INFO_TIMEOUT and every workgroup drains out -- a scheduling bug ends in an error code, not in a hung GPU.
 //   * Not positive definite (info > 0, set by a diagonal block): later tasks skip their work but still bump their
 //     counters, so the queue drains at once.
@@ -24,35 +24,15 @@
 // Arithmetic per output element is the same sequence of MFMA accumulations as in gemm_kernel (k ascending in steps of
 // four, operands identical), so results are bitwise equal to the launch-per-product path.
 
-// Contraction depth of one pipeline stage of the task-queue tiles, in units of Cfg<T>::BK (128 bytes of k).  Experiment (round
-// 3): f64 with 2 -> 32 elements per stage, as f32 has -- twice the MFMAs between two stage barriers (32 per wave), half as many
-// barrier bubbles per flop; the old values of a beta = 1 tile then live in registers for both tile shapes (the 128x64 stash no
-// longer fits the LDS).  Measured SLOWER: 2048-deep 128x64 tile 127.3 vs 123.3 us, fit+predict/s 1.625 vs 1.665 (same box,
-// 0 spills either way): the barrier bubble is not what costs the 9 % between the stage loop and the MFMA rate.  Stays 1.
-#ifndef DAG_F64_KMUL
-#define DAG_F64_KMUL 1
-#endif
-// Stage-loop form per tile shape (dag_gemm_tile): 0 = the shipped loop (a stage's fragments in registers, reads / loads / stores in
-// clumps); 1 = one k-step's fragments double-buffered, every non-MFMA instruction in the shadow of an MFMA.  Form 1 is round 5's
-// experiment: bitwise equal, +1.6 % on the tile alone, -0.5 % in the fit -- NOT in the product build (these
-// defaults), kept as a compile-time form for tools/tile_ubench.hip, which also switches parts of it off (PIPE = 1 + 16 * ABL) to
-// price the loop's data path.  Two more forms were built on it, measured and removed (commit 392ba09 has them): three register
-// sets with loads three stages ahead (88.3 % of the MFMA rate alone, -4 % in the fit) and an LDS-DMA ring (global_load_lds into
-// unpadded, source-swizzled stage images: 80-83 %).
-#ifndef DAG_PIPE_128x128
-#define DAG_PIPE_128x128 0
-#endif
-#ifndef DAG_PIPE_128x64
-#define DAG_PIPE_128x64 0
-#endif
-#ifndef DAG_PIPE_64x64
-#define DAG_PIPE_64x64 0
-#endif
+// Contraction depth of one pipeline stage of the task-queue tiles: Cfg<T>::BK (128 bytes of k).  Twice that for f64 was measured
+// slower (round 3: 2048-deep 128x64 tile 127.3 vs 123.3 us, fit+predict/s 1.625 vs 1.665).  Other stage-loop forms were measured
+// and removed (round 5): k-step fragments double-buffered with every non-MFMA instruction in an MFMA's shadow
+// (+1.6 % on the tile alone, -0.5 % in the fit), three register sets (-4 % in the fit), an LDS-DMA ring (80-83 % of the MFMA rate).
 template <typename T, int TA, int TB>
 struct DagGeom {
   using C = Cfg<T>;
   static constexpr int NT = 512;
-  static constexpr int BK = sizeof(T) == 8 ? DAG_F64_KMUL * C::BK : C::BK;
+  static constexpr int BK = C::BK;
   static constexpr int SK = BK + 2;                    // LDS row stride, operand stored [outer][k]
   static constexpr int SMA = TA + 16, SMB = TB + 16;   // LDS row stride, operand stored [k][outer]
   static constexpr int LDSA = (TA * SK > BK * SMA) ? TA * SK : BK * SMA;
@@ -73,7 +53,7 @@ static_assert(DAG_LDS_BYTES <= 163840, "the diagonal block and the control words
 // free (claiming it a whole task earlier parks the chain's tasks behind bulk tiles: measured 2.05 -> 3.06 ms per evaluation).
 // -DDAG_STAMP_INNER (diagnostic build, tools/trace_inner.py): two more time stamps per tile task -- first stage in the LDS (the
 // first MFMA can start) and last MFMA issued -- packed into the trace's CU-id word (low 32 bits of the 100 MHz clock each).
-template <typename T, int TA, int TB, int PIPE, typename PullFn, typename FetchFn>
+template <typename T, int TA, int TB, typename PullFn, typename FetchFn>
 __device__ __forceinline__ void dag_gemm_tile(int flags, int row0, int col0, int kbeg, int kend, T* __restrict__ W1,
                                               T* __restrict__ W2, T* __restrict__ W3, T* __restrict__ Kinv, int ld, char* smem_raw,
                                               PullFn pull, FetchFn fetch, unsigned long long* inner = nullptr) {
@@ -84,9 +64,6 @@ __device__ __forceinline__ void dag_gemm_tile(int flags, int row0, int col0, int
   constexpr int VEC = C::VEC, BK = G::BK, SK = G::SK, SMA = G::SMA, SMB = G::SMB, NCHA = G::NCHA, NCHB = G::NCHB;
   constexpr int TMA = G::TMA, TMB = G::TMB, NT = G::NT;
 
-#ifdef DAG_HEAD_DELAY  /* diagnostic build: every tile task starts DAG_HEAD_DELAY x 64 cycles late -- does the fit rate follow the per-task fixed cost? */
-  for (int q = 0; q < DAG_HEAD_DELAY; ++q) __builtin_amdgcn_s_sleep(1);
-#endif
   const int akm = (flags & DAGF_AKM) ? 1 : 0, bkm = (flags & DAGF_BKM) ? 1 : 0;
   const T* Ag = (flags & DAGF_A3) ? W3 : ((flags & DAGF_ABUF) ? W2 : W1);
   const T* Bg = (flags & DAGF_B3) ? W3 : ((flags & DAGF_BBUF) ? W2 : W1);
@@ -143,7 +120,7 @@ __device__ __forceinline__ void dag_gemm_tile(int flags, int row0, int col0, int
   constexpr bool NOACC = TB == 128;
   const bool accum = (flags & DAGF_ACC) != 0;
   const bool cinit = !NOACC && sizeof(T) == 8 && (flags & DAGF_CINIT) != 0;  // the old values start the accumulation (engine.hpp)
-  constexpr bool PREFETCH_C = TA == 64 || (sizeof(T) == 8 && DAG_F64_KMUL > 1);
+  constexpr bool PREFETCH_C = TA == 64;
   constexpr int STASH_OFF = 2 * (G::LDSA + G::LDSB);  // in elements of T, behind [A buf0 | A buf1 | B buf0 | B buf1]
   static_assert(NOACC || PREFETCH_C || (size_t)(STASH_OFF + TA * TB) * sizeof(T) <= (size_t)DAG_LDS_CTL_OFF, "the stash must fit in front of the control words");
   static_assert((size_t)STASH_OFF * sizeof(T) <= (size_t)DAG_LDS_CTL_OFF, "the stage buffers must fit in front of the control words");
@@ -204,278 +181,126 @@ __device__ __forceinline__ void dag_gemm_tile(int flags, int row0, int col0, int
   const int fb0 = 2 * G::LDSA + (wn * (TB / G::WN) + (lane & 15)) * soB + (lane >> 4) * skB;
 
   constexpr int NK = BK / 4;
-  if constexpr (PIPE == 0) {
-    // Same software pipeline as gemm_kernel's 64-tile: global loads two stages ahead in two register sets, LDS double
-    // buffer, the fragments of a whole stage in registers, the next stage's first fragments read under the MFMAs of the
-    // last k-step.
-    T fa[NK][TMA], fb[NK][TMB];
-    auto read_frags = [&](int buf, int k4) {
-      const int ia = buf * G::LDSA + fa0 + k4 * 4 * skA, ib = buf * G::LDSB + fb0 + k4 * 4 * skB;
+  // Same software pipeline as gemm_kernel's 64-tile: global loads two stages ahead in two register sets, LDS double
+  // buffer, the fragments of a whole stage in registers, the next stage's first fragments read under the MFMAs of the
+  // last k-step.
+  T fa[NK][TMA], fb[NK][TMB];
+  auto read_frags = [&](int buf, int k4) {
+    const int ia = buf * G::LDSA + fa0 + k4 * 4 * skA, ib = buf * G::LDSB + fb0 + k4 * 4 * skB;
 #pragma unroll
-      for (int a = 0; a < TMA; ++a) fa[k4][a] = lds[ia + a * 16 * soA];
+    for (int a = 0; a < TMA; ++a) fa[k4][a] = lds[ia + a * 16 * soA];
 #pragma unroll
-      for (int b2 = 0; b2 < TMB; ++b2) fb[k4][b2] = lds[ib + b2 * 16 * soB];
-    };
-    auto mfma_step = [&](int k4) {
+    for (int b2 = 0; b2 < TMB; ++b2) fb[k4][b2] = lds[ib + b2 * 16 * soB];
+  };
+  auto mfma_step = [&](int k4) {
 #pragma unroll
-      for (int a = 0; a < TMA; ++a)
+    for (int a = 0; a < TMA; ++a)
 #pragma unroll
-        for (int b2 = 0; b2 < TMB; ++b2) acc[a][b2] = C::mfma(fa[k4][a], fb[k4][b2], acc[a][b2]);
-    };
-    auto stage = [&](int cur, bool do_load, vec_t (&la)[NCHA], vec_t (&lb)[NCHB], bool do_store, vec_t (&sa)[NCHA],
-                     vec_t (&sb)[NCHB], bool has_next) {
-      if (do_load) load_stage(la, lb);
-      // f32 128x128 (NK = 8: 48 fragment registers beside 64 fp64 chunk totals): the fragments of a stage are read in two
-      // halves, the second under the first half's MFMAs -- with all of them up front the kernel spilled (round 4: 4 VGPRs)
-      constexpr bool SPLIT_READS = NK >= 8 && TA * TB >= 128 * 128;
-      constexpr int KH = SPLIT_READS ? NK / 2 : NK - 1;  // last k-step read up front
+      for (int b2 = 0; b2 < TMB; ++b2) acc[a][b2] = C::mfma(fa[k4][a], fb[k4][b2], acc[a][b2]);
+  };
+  auto stage = [&](int cur, bool do_load, vec_t (&la)[NCHA], vec_t (&lb)[NCHB], bool do_store, vec_t (&sa)[NCHA],
+                   vec_t (&sb)[NCHB], bool has_next) {
+    if (do_load) load_stage(la, lb);
+    // f32 128x128 (NK = 8: 48 fragment registers beside 64 fp64 chunk totals): the fragments of a stage are read in two
+    // halves, the second under the first half's MFMAs -- with all of them up front the kernel spilled (round 4: 4 VGPRs)
+    constexpr bool SPLIT_READS = NK >= 8 && TA * TB >= 128 * 128;
+    constexpr int KH = SPLIT_READS ? NK / 2 : NK - 1;  // last k-step read up front
 #pragma unroll
-      for (int k4 = 1; k4 <= KH; ++k4) read_frags(cur, k4);
-      if constexpr (SPLIT_READS) {
+    for (int k4 = 1; k4 <= KH; ++k4) read_frags(cur, k4);
+    if constexpr (SPLIT_READS) {
 #pragma unroll
-        for (int k4 = 0; k4 + 1 < KH; ++k4) mfma_step(k4);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int k4 = KH + 1; k4 < NK; ++k4) read_frags(cur, k4);
-#pragma unroll
-        for (int k4 = KH - 1; k4 + 2 < NK; ++k4) mfma_step(k4);
-      } else {
-#pragma unroll
-        for (int k4 = 0; k4 + 2 < NK; ++k4) mfma_step(k4);
-      }
+      for (int k4 = 0; k4 + 1 < KH; ++k4) mfma_step(k4);
       __builtin_amdgcn_sched_barrier(0);
-      if (do_store) store_stage(cur ^ 1, sa, sb);
-      if (NK >= 2) mfma_step(NK - 2);
-      __builtin_amdgcn_sched_barrier(0);
-      __syncthreads();
-      __builtin_amdgcn_sched_barrier(0);
-      if (has_next) read_frags(cur ^ 1, 0);
-      mfma_step(NK - 1);
-      __builtin_amdgcn_sched_group_barrier(0x100, TMA + TMB, 0);  // reads first: their latency hides under the MFMAs
-      __builtin_amdgcn_sched_group_barrier(0x008, TMA * TMB, 0);
-      __builtin_amdgcn_sched_barrier(0);
-      kabs += BK;
-      if (CHUNKED && kabs % F32_CHUNK == 0) flush();
-    };
-    if (nstages > 0) {
-      load_stage(ra0, rb0);
-      if (nstages > 1) load_stage(ra1, rb1);
-      if constexpr (!PREFETCH_C && !NOACC) {
-        if (accum) {  // old values of the output tile -> LDS stash (each thread its own 16 slots, lane-contiguous)
-          T cst[TMA][TMB][4];
-          const int er0p = row0 + wm * (TA / G::WM), ec0p = col0 + wn * (TB / G::WN) + (lane & 15);
 #pragma unroll
-          for (int a = 0; a < TMA; ++a)
+      for (int k4 = KH + 1; k4 < NK; ++k4) read_frags(cur, k4);
 #pragma unroll
-            for (int b = 0; b < TMB; ++b)
+      for (int k4 = KH - 1; k4 + 2 < NK; ++k4) mfma_step(k4);
+    } else {
 #pragma unroll
-              for (int r = 0; r < 4; ++r) cst[a][b][r] = Cg[(size_t)(er0p + a * 16 + C::crow(lane, r)) * ld + ec0p + b * 16];
-          store_stage(0, ra0, rb0);
-          bool stash = true;
-          if constexpr (sizeof(T) == 8) {
-            if (cinit) {
-              stash = false;
+      for (int k4 = 0; k4 + 2 < NK; ++k4) mfma_step(k4);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    if (do_store) store_stage(cur ^ 1, sa, sb);
+    if (NK >= 2) mfma_step(NK - 2);
+    __builtin_amdgcn_sched_barrier(0);
+    __syncthreads();
+    __builtin_amdgcn_sched_barrier(0);
+    if (has_next) read_frags(cur ^ 1, 0);
+    mfma_step(NK - 1);
+    __builtin_amdgcn_sched_group_barrier(0x100, TMA + TMB, 0);  // reads first: their latency hides under the MFMAs
+    __builtin_amdgcn_sched_group_barrier(0x008, TMA * TMB, 0);
+    __builtin_amdgcn_sched_barrier(0);
+    kabs += BK;
+    if (CHUNKED && kabs % F32_CHUNK == 0) flush();
+  };
+  if (nstages > 0) {
+    load_stage(ra0, rb0);
+    if (nstages > 1) load_stage(ra1, rb1);
+    if constexpr (!PREFETCH_C && !NOACC) {
+      if (accum) {  // old values of the output tile -> LDS stash (each thread its own 16 slots, lane-contiguous)
+        T cst[TMA][TMB][4];
+        const int er0p = row0 + wm * (TA / G::WM), ec0p = col0 + wn * (TB / G::WN) + (lane & 15);
 #pragma unroll
-              for (int a = 0; a < TMA; ++a)
+        for (int a = 0; a < TMA; ++a)
 #pragma unroll
-                for (int b = 0; b < TMB; ++b)
+          for (int b = 0; b < TMB; ++b)
 #pragma unroll
-                  for (int r = 0; r < 4; ++r) acc[a][b][r] = cst[a][b][r];
-            }
-          }
-          if (stash) {
+            for (int r = 0; r < 4; ++r) cst[a][b][r] = Cg[(size_t)(er0p + a * 16 + C::crow(lane, r)) * ld + ec0p + b * 16];
+        store_stage(0, ra0, rb0);
+        bool stash = true;
+        if constexpr (sizeof(T) == 8) {
+          if (cinit) {
+            stash = false;
 #pragma unroll
             for (int a = 0; a < TMA; ++a)
 #pragma unroll
               for (int b = 0; b < TMB; ++b)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) lds[STASH_OFF + ((a * TMB + b) * 4 + r) * NT + t] = cst[a][b][r];
+                for (int r = 0; r < 4; ++r) acc[a][b][r] = cst[a][b][r];
           }
-        } else {
-          store_stage(0, ra0, rb0);
+        }
+        if (stash) {
+#pragma unroll
+          for (int a = 0; a < TMA; ++a)
+#pragma unroll
+            for (int b = 0; b < TMB; ++b)
+#pragma unroll
+              for (int r = 0; r < 4; ++r) lds[STASH_OFF + ((a * TMB + b) * 4 + r) * NT + t] = cst[a][b][r];
         }
       } else {
         store_stage(0, ra0, rb0);
       }
-      __syncthreads();
-      read_frags(0, 0);
-  #ifdef DAG_STAMP_INNER
-      unsigned long long st1 = 0;
-      if (inner && t == 0) st1 = __builtin_amdgcn_s_memrealtime();
-  #endif
-      int s = 0;
-      for (; s + 3 < nstages; s += 2) {
-        stage(0, true, ra0, rb0, true, ra1, rb1, true);
-        stage(1, true, ra1, rb1, true, ra0, rb0, true);
-      }
-      const int left = nstages - s;  // 1..3
-      if (left <= 2) pull();
-      if (left == 1) fetch();
-      stage(0, left > 2, ra0, rb0, left > 1, ra1, rb1, left > 1);
-      if (left > 2) pull();
-      if (left == 2) fetch();
-      if (left > 1) stage(1, false, ra1, rb1, left > 2, ra0, rb0, left > 2);
-      if (left > 2) {
-        fetch();
-        stage(0, false, ra0, rb0, false, ra1, rb1, false);
-      }
-  #ifdef DAG_STAMP_INNER
-      if (inner && t == 0) *inner = ((st1 & 0xffffffffull) << 32) | (__builtin_amdgcn_s_memrealtime() & 0xffffffffull);
-  #endif
     } else {
-      pull();
-      fetch();
+      store_stage(0, ra0, rb0);
     }
+    __syncthreads();
+    read_frags(0, 0);
+#ifdef DAG_STAMP_INNER
+    unsigned long long st1 = 0;
+    if (inner && t == 0) st1 = __builtin_amdgcn_s_memrealtime();
+#endif
+    int s = 0;
+    for (; s + 3 < nstages; s += 2) {
+      stage(0, true, ra0, rb0, true, ra1, rb1, true);
+      stage(1, true, ra1, rb1, true, ra0, rb0, true);
+    }
+    const int left = nstages - s;  // 1..3
+    if (left <= 2) pull();
+    if (left == 1) fetch();
+    stage(0, left > 2, ra0, rb0, left > 1, ra1, rb1, left > 1);
+    if (left > 2) pull();
+    if (left == 2) fetch();
+    if (left > 1) stage(1, false, ra1, rb1, left > 2, ra0, rb0, left > 2);
+    if (left > 2) {
+      fetch();
+      stage(0, false, ra0, rb0, false, ra1, rb1, false);
+    }
+#ifdef DAG_STAMP_INNER
+    if (inner && t == 0) *inner = ((st1 & 0xffffffffull) << 32) | (__builtin_amdgcn_s_memrealtime() & 0xffffffffull);
+#endif
   } else {
-    // PIPE 1 (round 5): the stage loop with every wave's LDS reads, global loads and LDS stores dealt one by one into the
-    // shadows of its own MFMAs.  Why: the two waves of a SIMD share one fp64 MFMA pipe and the pipe serves the older wave
-    // first, so the older wave runs ahead to the stage barrier and the younger one then runs most of its stage ALONE -- and
-    // whenever a lone wave issues a clump of non-MFMA instructions (PIPE 0: 18 fragment reads + 4 global loads at the head of a
-    // stage, 4 LDS stores in the middle) the pipe idles: the stage loop ran at 92 % of the MFMA rate.  Here the fragments of
-    // ONE k-step are double-buffered (k-step k lives in set k & 1: 2 x (TMA + TMB) values instead of NK x), each MFMA is
-    // followed by at most one fragment read of the NEXT k-step and one load or store, and sched_group_barrier pins that
-    // order, so a wave alone keeps the pipe busy.  Same k-ascending chain of MFMA accumulations per element: same bits.
-    // An interval = what lies between two stage barriers: MFMAs of the last k-step of stage s-1 (fragments already in
-    // registers), then k-steps 0 .. NK-2 of stage s; the loads of stage s+2 sit in the first group, the LDS stores of stage s+1
-    // in the group before the last one.
-    static_assert(NK % 2 == 0 && NK >= 2, "k-step k lives in fragment set k & 1 across stage boundaries");
-    // tools/tile_ubench only (wrong results, timing only): PIPE = 1 + 16 * ABL switches parts of the loop off -- 1: no global
-    // loads, 2: no LDS stores, 4: no stage barrier, 8: no fragment reads (what is each worth beside the MFMAs?)
-    constexpr int ABL = PIPE >> 4;
-    constexpr int NF = TMA + TMB, NM = TMA * TMB;
-    constexpr int RPM = (NF + NM - 1) / NM;  // fragment reads dealt behind one MFMA
-    T fr[2][NF];
-    auto read_frag = [&](int set, int buf, int k4, int i) {
-      if (i < TMA) fr[set][i] = lds[buf * G::LDSA + fa0 + k4 * 4 * skA + i * 16 * soA];
-      else fr[set][i] = lds[buf * G::LDSB + fb0 + k4 * 4 * skB + (i - TMA) * 16 * soB];
-    };
-    // the MFMAs of one k-step (fragments in set ms) with the reads of k-step rk of buffer rbuf (into set ms ^ 1) in their shadows
-    auto group = [&](int ms, bool rd, int rbuf, int rk) {
-#pragma unroll
-      for (int i = 0; i < NM; ++i) {
-        acc[i / TMB][i % TMB] = C::mfma(fr[ms][i / TMB], fr[ms][TMA + i % TMB], acc[i / TMB][i % TMB]);
-        if (rd) {
-#pragma unroll
-          for (int q = 0; q < RPM; ++q)
-            if (i * RPM + q < NF) read_frag(ms ^ 1, rbuf, rk, i * RPM + q);
-        }
-      }
-    };
-    // pins the issue order of one group: MFMA, its fragment reads, then (first NV MFMAs) one global load / (first NW) one LDS store
-    auto pin = [&](bool rd, int nv, int nw) {
-#pragma unroll
-      for (int i = 0; i < NM; ++i) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        if (rd && i * RPM < NF) __builtin_amdgcn_sched_group_barrier(0x100, RPM, 0);
-        if (i < nv) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-        if (i < nw) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
-      }
-    };
-    constexpr int KST = NK >= 4 ? NK - 3 : 0;  // the k-step group that carries the LDS stores of the next stage
-    auto interval = [&](int cur, bool g0, bool do_load, vec_t (&la)[NCHA], vec_t (&lb)[NCHB], bool do_store, vec_t (&sa)[NCHA],
-                        vec_t (&sb)[NCHB]) {
-      __builtin_amdgcn_sched_barrier(0);
-      if (g0) {
-        if (do_load && !(ABL & 1)) load_stage(la, lb);
-        group((NK - 1) & 1, !(ABL & 8), cur, 0);
-        pin(true, NCHA + NCHB, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        kabs += BK;
-        if (CHUNKED && kabs % F32_CHUNK == 0) flush();
-      } else {
-        if (do_load && !(ABL & 1)) load_stage(la, lb);
-#pragma unroll
-        for (int i = 0; i < NF; ++i) read_frag(0, cur, 0, i);
-        if constexpr ((ABL & 8) != 0) {
-#pragma unroll
-          for (int i = 0; i < NF; ++i) read_frag(1, cur, 1, i);
-        }
-      }
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int k4 = 0; k4 + 1 < NK; ++k4) {
-        const bool st = do_store && k4 == KST && !(ABL & 2);
-        if (st) store_stage(cur ^ 1, sa, sb);
-        group(k4 & 1, !(ABL & 8), cur, k4 + 1);
-        pin(true, 0, k4 == KST ? NCHA + NCHB : 0);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      if constexpr (!(ABL & 4)) __syncthreads();
-      __builtin_amdgcn_sched_barrier(0);
-    };
-    if (nstages > 0) {
-      load_stage(ra0, rb0);
-      if (nstages > 1) load_stage(ra1, rb1);
-      if constexpr (!PREFETCH_C && !NOACC) {
-        if (accum) {  // old values of the output tile -> LDS stash (as PIPE 0)
-          T cst[TMA][TMB][4];
-          const int er0p = row0 + wm * (TA / G::WM), ec0p = col0 + wn * (TB / G::WN) + (lane & 15);
-#pragma unroll
-          for (int a = 0; a < TMA; ++a)
-#pragma unroll
-            for (int b = 0; b < TMB; ++b)
-#pragma unroll
-              for (int r = 0; r < 4; ++r) cst[a][b][r] = Cg[(size_t)(er0p + a * 16 + C::crow(lane, r)) * ld + ec0p + b * 16];
-          store_stage(0, ra0, rb0);
-          bool stash = true;
-          if constexpr (sizeof(T) == 8) {
-            if (cinit) {
-              stash = false;
-#pragma unroll
-              for (int a = 0; a < TMA; ++a)
-#pragma unroll
-                for (int b = 0; b < TMB; ++b)
-#pragma unroll
-                  for (int r = 0; r < 4; ++r) acc[a][b][r] = cst[a][b][r];
-            }
-          }
-          if (stash) {
-#pragma unroll
-            for (int a = 0; a < TMA; ++a)
-#pragma unroll
-              for (int b = 0; b < TMB; ++b)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) lds[STASH_OFF + ((a * TMB + b) * 4 + r) * NT + t] = cst[a][b][r];
-          }
-        } else {
-          store_stage(0, ra0, rb0);
-        }
-      } else {
-        store_stage(0, ra0, rb0);
-      }
-      __syncthreads();
-#ifdef DAG_STAMP_INNER
-      unsigned long long st1 = 0;
-      if (inner && t == 0) st1 = __builtin_amdgcn_s_memrealtime();
-#endif
-      int s = 0;
-      bool g0 = false;
-        for (; s + 3 < nstages; s += 2) {
-          interval(0, g0, true, ra0, rb0, true, ra1, rb1);
-          g0 = true;
-          interval(1, true, true, ra1, rb1, true, ra0, rb0);
-        }
-        const int left = nstages - s;  // 1..3
-        if (left <= 2) pull();
-        if (left == 1) fetch();
-        interval(0, g0, left > 2, ra0, rb0, left > 1, ra1, rb1);
-        if (left > 2) pull();
-        if (left == 2) fetch();
-        if (left > 1) interval(1, true, false, ra1, rb1, left > 2, ra0, rb0);
-        if (left > 2) {
-          fetch();
-          interval(0, true, false, ra0, rb0, false, ra1, rb1);
-        }
-      // the last k-step of the last stage
-      group((NK - 1) & 1, false, 0, 0);
-      kabs += BK;
-#ifdef DAG_STAMP_INNER
-      if (inner && t == 0) *inner = ((st1 & 0xffffffffull) << 32) | (__builtin_amdgcn_s_memrealtime() & 0xffffffffull);
-#endif
-    } else {
-      pull();
-      fetch();
-    }
+    pull();
+    fetch();
   }
 
   flush();  // f32: what the last (partial) chunk holds
@@ -598,31 +423,16 @@ __device__ __forceinline__ void dag_gemm_tile_chain(int flags, int row0, int col
   }
 }
 
-// DAG_LEAF_NOINLINE=1 compiles the diagonal block as a function of its own: nothing of it spills in the kernel body then (the
-// callee saves 25 registers on its stack instead).  Round 2 found that build not reproducible run to run and kept it off; the
-// cause (round 3, profiles/r03_leaf_race.txt) was not the call but a race inside leaf_body that every build had -- the helper
-// waves re-read pivot rows that wave 0 overwrites in the same phase -- and the called build merely lost it more often.  With
-// the pivot-row copy (LEAF_DIAG_COPY) the called build is bitwise reproducible too (0 deviations in 39,600 concurrent
-// evaluations, 5 without the copy).  Variant 2 names the workgroup's dynamic LDS itself and keeps ds_ accesses.
-#ifndef DAG_LEAF_NOINLINE
-#define DAG_LEAF_NOINLINE 1  /* round 3: on.  Kernel body 0 spilled VGPRs (inlined: 21 f64 / 53 f32); fit+predict/s 1.690 vs 1.682 */
-#endif
+// The diagonal block is a function of its own: nothing of it spills in the kernel body then (the callee saves 25 registers on
+// its stack instead; inlined, the body spilled 21 f64 / 53 f32 VGPRs; fit+predict/s 1.690 vs 1.682).  Round 2 found the called
+// build not reproducible run to run; the cause (round 3, profiles/r03_leaf_race.txt) was not the call but a race inside leaf_body
+// that every build had -- the helper waves re-read pivot rows that wave 0 overwrites in the same phase -- and the called build
+// merely lost it more often.  With the pivot-row copy in leaf_body it is bitwise reproducible (0 deviations in 39,600
+// concurrent evaluations, 5 without the copy).
 template <typename T>
-#if DAG_LEAF_NOINLINE == 2
-// variant 2: the function names the workgroup's dynamic LDS itself, so the block keeps local-address-space (ds_) accesses
-__device__ __attribute__((noinline)) void dag_leaf_task(T* W1, T* W2, int ld, int blk, T* ldiag, int* info, char*, int dbg) {
-  extern __shared__ __align__(16) char leaf_smem[];
-  leaf_body<double, T, true>(W1, W2, ld, blk, ldiag, info, dbg, leaf_smem);
-}
-#elif DAG_LEAF_NOINLINE
 __device__ __attribute__((noinline)) void dag_leaf_task(T* W1, T* W2, int ld, int blk, T* ldiag, int* info, char* smem_raw, int dbg) {
   leaf_body<double, T, true>(W1, W2, ld, blk, ldiag, info, dbg, smem_raw);
 }
-#else
-__device__ __forceinline__ void dag_leaf_task(T* W1, T* W2, int ld, int blk, T* ldiag, int* info, char* smem_raw, int dbg) {
-  leaf_body<double, T, true>(W1, W2, ld, blk, ldiag, info, dbg, smem_raw);
-}
-#endif
 
 // The task loop.  A workgroup claims its next queue entry and fetches its descriptor under the last MFMA stages of the task it
 // runs (dag_gemm_tile's pull / fetch hooks).  Between two tasks the hand-off then costs only what cannot overlap:
@@ -755,11 +565,11 @@ __global__ void __launch_bounds__(512, 2) dag_kernel(DagLaunch g) {
       } else if ((flags & DAGF_CKINV) && g.Kinv == nullptr) {
         // factorisation-only launch: the K^-1 tiles are not wanted
       } else if (kind == DAG_GEMM_128x64) {
-        dag_gemm_tile<T, 128, 64, DAG_PIPE_128x64>(flags, row0, col0, kbeg, kend, W1, W2, static_cast<T*>(g.W3), static_cast<T*>(g.Kinv), g.ld, smem_raw, pull, fetch, inner_stamp);
+        dag_gemm_tile<T, 128, 64>(flags, row0, col0, kbeg, kend, W1, W2, static_cast<T*>(g.W3), static_cast<T*>(g.Kinv), g.ld, smem_raw, pull, fetch, inner_stamp);
       } else if (kind == DAG_GEMM_64x64) {
-        dag_gemm_tile<T, 64, 64, DAG_PIPE_64x64>(flags, row0, col0, kbeg, kend, W1, W2, static_cast<T*>(g.W3), static_cast<T*>(g.Kinv), g.ld, smem_raw, pull, fetch, inner_stamp);
+        dag_gemm_tile<T, 64, 64>(flags, row0, col0, kbeg, kend, W1, W2, static_cast<T*>(g.W3), static_cast<T*>(g.Kinv), g.ld, smem_raw, pull, fetch, inner_stamp);
       } else if (kind == DAG_GEMM_128x128) {
-        dag_gemm_tile<T, 128, 128, DAG_PIPE_128x128>(flags, row0, col0, kbeg, kend, W1, W2, static_cast<T*>(g.W3), static_cast<T*>(g.Kinv), g.ld, smem_raw, pull, fetch, inner_stamp);
+        dag_gemm_tile<T, 128, 128>(flags, row0, col0, kbeg, kend, W1, W2, static_cast<T*>(g.W3), static_cast<T*>(g.Kinv), g.ld, smem_raw, pull, fetch, inner_stamp);
       } else if (kind == DAG_GEMM_32x64) {
         dag_gemm_tile_chain<T>(flags, row0, col0, kbeg, kend, W1, W2, static_cast<T*>(g.W3), g.ld, smem_raw, pull, fetch);
       }

@@ -27,7 +27,6 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
-#include <cstdlib>
 #include <queue>
 #include <string>
 #include <vector>
@@ -36,22 +35,10 @@
 
 namespace hbegp {
 
-// Where a node [lo, hi) of the recursion is split.  Default: in the middle, as the launch path does (same arithmetic, same
-// bits).  HBEGP_SPLIT_NUM/HBEGP_SPLIT_DEN (experiment, task queue only): nodes wider than HBEGP_SPLIT_MIN blocks put num/den
-// of their blocks into the LEFT part -- a smaller left part shortens the chain-bound head of the factorisation (nothing but
-// the diagonal chain can run until the left part is done) at the price of a longer chain later.  Simulated for n=4096, 85
-// workgroups: 1/2 -> 2932 us, 3/8 -> 2932, 1/3 -> 2887, 1/4 -> 3015, 1/8 -> 3045: nothing to gain, the default stays.
-inline int dag_split_point(int lo, int hi) {
-  static const int num = getenv("HBEGP_SPLIT_NUM") ? atoi(getenv("HBEGP_SPLIT_NUM")) : 1;
-  static const int den = getenv("HBEGP_SPLIT_DEN") ? atoi(getenv("HBEGP_SPLIT_DEN")) : 2;
-  static const int minw = getenv("HBEGP_SPLIT_MIN") ? atoi(getenv("HBEGP_SPLIT_MIN")) : 8;
-  const int w = hi - lo;
-  if (w <= minw || den <= 0 || num <= 0 || num >= den || 2 * num == den) return lo + w / 2;  // default: exactly the launch path's split
-  int left = (w * num) / den;
-  // keep the parts multiples of 4 blocks where possible (small nodes stay balanced binary trees)
-  left = std::max(4, left / 4 * 4);
-  return lo + std::min(left, w - 1);
-}
+// Where a node [lo, hi) of the recursion is split: in the middle, exactly as the launch path does (same arithmetic, same
+// bits).  Uneven splits were simulated for n=4096, 85 workgroups (left part 1/2 -> 2932 us, 3/8 -> 2932, 1/3 -> 2887, 1/4
+// -> 3015, 1/8 -> 3045): nothing to gain.
+inline int dag_split_point(int lo, int hi) { return lo + (hi - lo) / 2; }
 
 struct DagPlan {
   std::vector<DagTask> tasks;
@@ -85,10 +72,8 @@ class DagBuilder {
   // bk: contraction elements per pipeline stage (16 for f64, 32 for f32): ranges are whole stages
   // small_h: nodes whose halves are at most this many 128-blocks wide use 64x64 tiles (latency-bound products)
   // nwg: workgroups the queue is ordered for (0: keep the recursion's order)
-  // crit_rows: in the big nodes, this many block rows next to the diagonal chain (the first rows of T and of the Schur
-  //            update, the last rows of X21) also use 64x64 tiles: they sit on the critical path, where a tile's time counts
-  DagBuilder(int bk, int small_h, int nwg = 0, bool fine = true, int crit_rows = 1)
-      : bk_(bk), small_h_(small_h), nwg_(nwg), fine_(fine), crit_rows_(crit_rows) {}
+  // fine: dependencies per block row (false: on whole subtrees)
+  DagBuilder(int bk, int small_h, int nwg = 0, bool fine = true) : bk_(bk), small_h_(small_h), nwg_(nwg), fine_(fine) {}
 
   // full = true: the kernel-matrix tiles in front of the recursion and the alpha / lml reductions behind it are tasks of the
   // same queue (whole matrix only: blo = 0, bhi = np / 128)
@@ -100,9 +85,7 @@ class DagBuilder {
   }
   // right-looking plan, round 4: the inverse of the factor and K^-1 follow the diagonal chain row by row (rl_progressive)
   // instead of by divide and conquer behind it
-  void set_rl_progressive(bool on, int unear = -1, int knear = -1, bool small_tiles = false) {
-    rl_prog_ = on; prog_unear_ = unear; prog_knear_ = knear; prog_small_ = small_tiles;
-  }
+  void set_rl_progressive(bool on) { rl_prog_ = on; }
   // lauum = true: the tiles of K^-1 = X^T X (lml.rs:62) follow the recursion in the same queue (whole matrix only)
   // rl = true: right-looking tile Cholesky + recursive inverse of the factor (build_rl) instead of the recursion that
   // carries the inverse (whole matrix only; the factor L lives in W3)
@@ -124,16 +107,16 @@ class DagBuilder {
   }
 
  private:
+  // in the big nodes, the block row next to the diagonal chain (the first row of T and of the Schur update, the last row of
+  // X21) also uses 64x64 tiles: it sits on the critical path, where a tile's time counts
+  static constexpr int crit_rows_ = 1;
   int bk_, small_h_, nwg_;
   bool fine_;
-  int crit_rows_ = 1;
   int rl_group_ = 32, rl_near_ = 1;
   bool rl_lauum_split_ = true;
   bool big128_ = false;      // 128x128 tiles for the bulk products (never for a continued sum)
   bool big128_acc_ = false;  // ... also with beta = 1 (the old values fetched in the epilogue)
   bool rl_prog_ = false;     // right-looking plan: row-progressive inverse and K^-1 (rl_progressive)
-  int prog_unear_ = -1, prog_knear_ = -1;  // single rows at the end of the U / K^-1 range lists (-1: rl_near_)
-  bool prog_small_ = false;  // 64x64 tiles for the rows of X and the last U updates before a row (measured: no gain, more tasks)
   bool rl_chain32_ = true;   // right-looking plan: the two products between consecutive diagonal blocks as 32x64 one-shot tiles
   DagPlan plan_;
   DagCosts cost_;
@@ -549,9 +532,8 @@ class DagBuilder {
     const uint16_t cont = bk_ == 16 ? (uint16_t)(DAGF_ACC | DAGF_CINIT) : (uint16_t)DAGF_ACC;
     std::vector<DagGate> rowfin(nb), uprev(nb);
     std::vector<std::vector<std::pair<int, int>>> ugroups(nb);
-    const int UNEAR = prog_unear_ >= 0 ? prog_unear_ : NEAR, KNEAR = prog_knear_ >= 0 ? prog_knear_ : NEAR;
-    for (int i = 1; i < nb; ++i) ugroups[i] = rl_groups(i, GROUP, UNEAR);
-    const std::vector<std::pair<int, int>> kgroups = rl_groups(nb, GROUP, KNEAR);
+    for (int i = 1; i < nb; ++i) ugroups[i] = rl_groups(i, GROUP, NEAR);
+    const std::vector<std::pair<int, int>> kgroups = rl_groups(nb, GROUP, NEAR);
     DagGate kprev;
     const double g0 = plan_.gflop;
     double g_lauum = 0, cu = 0;
@@ -563,7 +545,7 @@ class DagBuilder {
         Op x{};
         x.flags = DAGF_ABUF | DAGF_BKM | DAGF_CBUF | DAGF_NEG;  // A = W2 (X_kk), B = W1 (U, contraction along rows), C = W2
         x.r0 = k; x.r1 = k + 1; x.c0 = 0; x.c1 = k; x.k0 = k; x.k1 = k + 1; x.klim = 3; x.tri_a = true;
-        const std::vector<Tile> xt = tiles_of(x, prog_small_);
+        const std::vector<Tile> xt = tiles_of(x, false);
         const int c = new_counter();
         for (const Tile& tl : xt) {
           const DagTask tk = make(x, tl, &cu);
@@ -577,7 +559,6 @@ class DagBuilder {
         for (const auto& gr : ugroups[i])
           if (gr.second == k + 1) a = gr.first;
         if (a < 0) continue;
-        const bool near = prog_small_ && (k + 1 - a) == 1 && i - k <= NEAR + 1;  // the last rows before row i: latency counts
         const int c = new_counter();
         int cnt = 0;
         const std::vector<DagGate> waits = {lc[i][k], rowfin[k], uprev[i]};
@@ -585,7 +566,7 @@ class DagBuilder {
           Op u{};
           u.flags = (uint16_t)(DAGF_A3 | DAGF_BBUF | DAGF_BKM | cont);  // A = W3 (L), B = W2 (X, contraction along rows), C = W1
           u.r0 = i; u.r1 = i + 1; u.c0 = 0; u.c1 = a; u.k0 = a; u.k1 = k + 1;
-          for (const Tile& tl : tiles_of(u, near)) {
+          for (const Tile& tl : tiles_of(u, false)) {
             const DagTask tk = make(u, tl, &cu);
             push(tk, waits, c, -1, cu);
             ++cnt;
@@ -595,7 +576,7 @@ class DagBuilder {
           Op u{};
           u.flags = DAGF_A3 | DAGF_BBUF | DAGF_BKM;
           u.r0 = i; u.r1 = i + 1; u.c0 = a; u.c1 = k + 1; u.k0 = a; u.k1 = k + 1; u.klim = 2; u.tri_b = true;
-          for (const Tile& tl : tiles_of(u, near)) {
+          for (const Tile& tl : tiles_of(u, false)) {
             const DagTask tk = make(u, tl, &cu);
             push(tk, waits, c, -1, cu);
             ++cnt;
@@ -707,24 +688,6 @@ class DagBuilder {
       for (int w = 0; w < t.nwait; ++w) blc[t.wcnt[w]] = std::max(blc[t.wcnt[w]], bl[i]);
     }
     plan_.crit_us = *std::max_element(bl.begin(), bl.end());
-    if (getenv("HBEGP_DAG_DUMP")) {  // the critical path, task by task (diagnostics)
-      int cur = (int)(std::max_element(bl.begin(), bl.end()) - bl.begin());
-      double acc_leaf = 0, acc_small = 0, acc_big = 0;
-      for (;;) {
-        const DagTask& t = plan_.tasks[cur];
-        fprintf(stderr, "crit: kind=%d row=%d col=%d depth=%d cost=%.1f remaining=%.1f flags=%x\n", t.kind, t.row0, t.col0, t.kend - t.kbeg,
-                t.cost * 0.1, bl[cur], t.flags);
-        (t.kind == DAG_LEAF ? acc_leaf : (t.kind == DAG_GEMM_64x64 ? acc_small : acc_big)) += t.cost * 0.1;
-        int nxt = -1;
-        for (int q = 0; q < DAG_MAXSIG; ++q)
-          if (t.sig[q] != DAG_NOSIG)
-            for (int wtr : waiters[t.sig[q]])
-              if (nxt < 0 || bl[wtr] > bl[nxt]) nxt = wtr;
-        if (nxt < 0) break;
-        cur = nxt;
-      }
-      fprintf(stderr, "crit totals: leaf %.0f us, 64x64 tiles %.0f us, 128x64 tiles %.0f us\n", acc_leaf, acc_small, acc_big);
-    }
     std::vector<int> count(nc, 0), missing(nt, 0);
     typedef std::pair<double, int> Pri;  // (bottom level, -index): highest first, earlier emission breaks ties
     std::priority_queue<Pri> ready;

@@ -14,7 +14,6 @@
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
-#include <array>
 #include <atomic>
 #include <queue>
 #include <cmath>
@@ -253,8 +252,7 @@ struct StreamPool {
     }
     hipStream_t s = nullptr;
     hipError_t e;
-    static const bool batch_prio = env_int("HBEGP_BATCH_STREAM_PRIORITY", 1) != 0;
-    if (kind == STREAM_BATCH && batch_prio) {
+    if (kind == STREAM_BATCH) {
       // the runtime keeps a pool of hardware queues PER PRIORITY: a stream of another priority never shares its queue with the
       // normal-priority streams of the fits -- whose copies and small kernels would otherwise wait for the ~10 ms persistent grid
       // of a small-fit batch whenever they land on its queue
@@ -317,9 +315,10 @@ static std::mutex g_small_host_mu;      // turn-taking of the host-side phases o
 static std::atomic<int> g_small_active{0};  // threads inside a small fit
 // Threads that have just come back from a small fit are the ones most likely to bring the next one: each thread keeps the time of
 // its last return in a slot of this table (0 while it is inside a fit), and the thread that opens a batch also waits for those
-// whose return is younger than HBEGP_SMALL_BATCH_RECENT_US (4 ms) -- without this, threads that finish together drift apart
+// whose return is younger than SMALL_RECENT_NS (4 ms) -- without this, threads that finish together drift apart
 // again (whoever is back first sees nobody on the way and launches alone: measured, 16 threads, 68 of 101 grids carried one fit).
 constexpr int SMALL_RECENT_SLOTS = 64;
+constexpr long long SMALL_RECENT_NS = 4000000;
 static std::atomic<long long> g_small_recent[SMALL_RECENT_SLOTS];
 static std::atomic<int> g_small_recent_next{0};
 static int small_recent_slot() {
@@ -381,17 +380,12 @@ static std::shared_ptr<SmallBatch> small_batch_submit(int dev, int nu2, const st
   arrival.arrived();  // (notifies: a leader waiting for the stragglers looks again)
   if (leader) {
     const auto t_open = std::chrono::steady_clock::now();
-    static const long long recent_ns = 1000ll * env_int("HBEGP_SMALL_BATCH_RECENT_US", 4000);
     if (window_us > 0) {
       // until nobody is on the way and nobody has just come back (their marks expire by themselves: look again every 200 us)
       const auto deadline = t_open + std::chrono::microseconds(window_us);
-      while (std::chrono::steady_clock::now() < deadline && (B.arriving.load() != 0 || small_recent_others(recent_ns) != 0))
+      while (std::chrono::steady_clock::now() < deadline && (B.arriving.load() != 0 || small_recent_others(SMALL_RECENT_NS) != 0))
         B.cv.wait_for(lk, std::chrono::microseconds(200));
     }
-    static const bool log_batches = env_int("HBEGP_SMALL_BATCH_LOG", 0) != 0;
-    if (log_batches)
-      fprintf(stderr, "small-fit batch: %zu runs, waited %.0f us for stragglers (%d still on their way, %d just back)\n", b->fits.size(),
-              std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_open).count(), B.arriving.load(), small_recent_others(recent_ns));
     b->closed = true;
     B.open.erase(key);
     lk.unlock();
@@ -480,12 +474,10 @@ struct PhaseTimer {
 };
 
 static int pick_tile(int tiles128) {
-  static const int forced = env_int("HBEGP_TILE", 0);
-  if (forced == 32 || forced == 64 || forced == 128) return forced;
   // 128-tiles only when a launch has >= 600 of them (n >= 8192): measured n=8192 15.1 -> 13.7 ms/evaluation with them,
   // n=4096 LAUUM (528 tiles) 0.44 ms with 64-tiles vs 0.77 ms with 128-tiles
-  if (tiles128 >= env_int("HBEGP_T128_MIN", 600)) return 128;
-  if (tiles128 >= env_int("HBEGP_T64_MIN", 128)) return 64;  // h=1024 SYRK+U (100 tiles): 58 us with 32-tiles vs 83 us with 64-tiles
+  if (tiles128 >= 600) return 128;
+  if (tiles128 >= 128) return 64;  // h=1024 SYRK+U (100 tiles): 58 us with 32-tiles vs 83 us with 64-tiles
   return 32;
 }
 
@@ -547,18 +539,15 @@ static bool build_sched(const GemmLaunch& g, int tile, std::vector<int>* off, st
   }
   const int ntiles = (int)its.size();
   // resident workgroups per CU the kernel can reach (registers: 206 / 168 VGPRs for the 128- / 64-tile kernels)
-  static const int occ_env = env_int("HBEGP_SCHED_OCC", 0);
-  const int occmax = occ_env > 0 ? occ_env : (tile == 128 ? 2 : 3);  // residency the kernels reach (VGPRs); pinned via the LDS request
+  const int occmax = tile == 128 ? 2 : 3;  // residency the kernels reach (VGPRs); pinned via the LDS request
   // Above ~2 tiles per resident slot the hardware dispatcher (tiles are listed deepest-first) balances better than a
   // static list (measured: LAUUM at n=4096, 2080 tiles: 50 vs 47 TFLOP/s); below it the static list wins (TRSM 29 -> 44).
+  // From 2048 tiles on the dispatcher alone.
   int nwg = 0;
-  static const int sched_max_tiles = env_int("HBEGP_SCHED_MAXTILES", 2048);
-  if (ntiles < sched_max_tiles)
+  if (ntiles < 2048)
     for (int occ = occmax; occ >= 1; --occ)
       if (ntiles >= 2 * 256 * occ) { nwg = 256 * occ; break; }
-  static const int sched_on = env_int("HBEGP_SCHED", 1);
-  static const int sched_t32 = env_int("HBEGP_SCHED_T32", 1);
-  if (!sched_on || nwg == 0 || (tile == 32 && !sched_t32)) return false;
+  if (nwg == 0) return false;
   std::stable_sort(its.begin(), its.end(), [](const It& a, const It& b) { return a.w > b.w; });
   typedef std::pair<double, int> Load;  // (load, wg)
   std::priority_queue<Load, std::vector<Load>, std::greater<Load>> pq;
@@ -588,6 +577,12 @@ constexpr int DAG_MAX_VARIANTS = 4;  // task-queue launches sized for 1..4 busy 
 constexpr int DAG_CROWD_LEVELS = 3;
 constexpr int DAG_CROWD_BUSY[DAG_CROWD_LEVELS] = {6, 12, 24};
 constexpr int MAX_DEVS = 64;
+// What a task-queue plan is built from: Problem::init keeps the plans it builds by this key
+struct DagPlanKey {
+  int blocks, bk, small_h, nwg, lauum, rl, rl_group, rl_near, lauum_split, chain32, prog, big128;
+  auto tie() const { return std::tie(blocks, bk, small_h, nwg, lauum, rl, rl_group, rl_near, lauum_split, chain32, prog, big128); }
+  bool operator<(const DagPlanKey& o) const { return tie() < o.tie(); }
+};
 static std::atomic<int> g_dev_busy[MAX_DEVS];  // optimiser runs in flight per device id, over all fits of the process
 
 template <typename T>
@@ -597,7 +592,7 @@ struct Slot {
   T *Xalt = nullptr, *ldalt = nullptr;  // device-driven small fit: second buffers for L^-1 / diag(L) (they ping-pong with K^-1 / alpha)
   bool x_captured = false;              // ... and after such a fit: (best_idx ? Xalt : W2) IS the captured evaluation's factor
   T *W1 = nullptr, *W2 = nullptr, *Kinv[2] = {nullptr, nullptr}, *alpha[2] = {nullptr, nullptr};
-  T* W3 = nullptr;  // f32 problems only: the Cholesky factor L (lower), kept for the refinement of the panel solves
+  T* W3 = nullptr;  // right-looking task-queue plan only: the Cholesky factor L (lower)
   T *ldiag = nullptr, *wbuf = nullptr;
   double *part_t = nullptr, *part_g = nullptr;
   EvalParams* dP = nullptr;
@@ -667,11 +662,6 @@ struct Problem : ProblemBase {
   unsigned long long dag_wait_ticks_ = 200000000ull;  // bound of one dependency wait (100 MHz ticks), see init()
   size_t dag_ctrl_bytes = 0;
   double dag_gflop = 0;
-  // f32 (--use-32): the panel solve T = A21 L11^-T is a product with the explicit inverse X11, whose residual grows with
-  // cond(L11) * eps -- harmless in f64, but in f32 it makes the lml gradient ~8x less accurate than LAPACK's substitution.
-  // One step of iterative refinement against the factor itself (kept in W3) restores a small residual:
-  //   T = A21 X11^T;  A21 -= T L11^T;  T += A21 X11^T          (three products of the same shape, all fp32 MFMA)
-  bool refine_ = false;
   bool dry_ = false;                        // walk the evaluation without launching (schedule construction)
   bool adhoc_ = false;                      // GEMM launches bypass the per-evaluation schedule table
   bool small_ = false;                      // np = 128, d <= 32: one evaluation = ONE launch (small_eval_kernel), everything in the LDS
@@ -721,15 +711,11 @@ struct Problem : ProblemBase {
     ctx = c; n = n_; d = d_; np = round_up(n_, NB); n_slots = n_slots_;
     nu2 = std::isinf(nu) ? 0 : (int)std::lround(2 * nu);  // 0 = squared exponential (nu = infinity)
     is_f32 = sizeof(T) == 4;
-    // off by default: with the chunked fp64 totals of the f32 tile GEMM (kernels.hip) the plain recursion is already 2-7x
-    // closer to the f64 result than LAPACK's f32 path (n=2048, cond 7e4: gradient 3e-6 vs 2e-5); refinement buys another
-    // 1.3x on alpha / K^-1 for 26 % more time (measured), for kernel matrices beyond cond ~1e5
-    refine_ = is_f32 && env_int("HBEGP_F32_REFINE", 0) != 0;
     leaf_dbg_ = env_int("HBEGP_LEAF_DBG", 0) & 16;  // tests only; the bits that skip work stay with tools/leaf_bench
     // The reference's own regime (minimize.rs:118-120: n stays at 100-200): up to 128 rows the five launches of the general path
     // cost more in launch gaps and HBM round trips than in arithmetic; one workgroup does the whole evaluation in its LDS
     // instead (HBEGP_SMALL=0: the general path, which the tests compare it with).
-    small_ = np == NB && d <= SMALL_EVAL_MAXD && !refine_ && env_int("HBEGP_SMALL", 1) != 0;
+    small_ = np == NB && d <= SMALL_EVAL_MAXD && env_int("HBEGP_SMALL", 1) != 0;
     hostio_ = env_int("HBEGP_HOSTIO", 1) != 0;
     const size_t nn = (size_t)np * np;
     Xd.assign(c->devs.size(), nullptr);
@@ -760,11 +746,6 @@ struct Problem : ProblemBase {
         // once per slot is enough -- also when it is recycled from the pool (it may have held a full symmetric K^-1).
         // W1's strict upper part is only ever multiplied by those zeros or ignored: it just has to be finite.
         HIPCHECK(hipMemsetAsync(s.W2, 0, sizeof(T) * nn, st0));
-        if (refine_) {
-          bool f3 = false;
-          s.W3 = static_cast<T*>(g_pool.get(s.dev, sizeof(T) * nn, &f3));
-          HIPCHECK(hipMemsetAsync(s.W3, 0, sizeof(T) * nn, st0));  // strict upper triangle must be zero, like W2's
-        }
         (void)fresh1; (void)fresh2; (void)fk;  // fresh blocks were cleared by the pool
         // the small per-slot arrays: one pooled block
         {
@@ -816,7 +797,6 @@ struct Problem : ProblemBase {
     // 1536 0.650 / 0.572 -- the queue from 6 blocks on, for fits and for single evaluations alike
     const int dag_min_blocks = env_int("HBEGP_DAG_MIN_BLOCKS", DAG_MIN_BLOCKS_FIT);
     dag_ = (dag_env < 0 ? np / NB >= dag_min_blocks : dag_env != 0) && !adhoc_ && np / NB >= 2;
-    if (refine_) dag_ = false;  // the refined panel solve exists as launches only (the task queue carries the f64 recursion)
     if (dag_) {
       int cus = 1 << 30;  // the launch sizes are shared by the devices of the context: size them for the smallest one
       for (int dev : c->devs) {
@@ -831,7 +811,7 @@ struct Problem : ProblemBase {
       // Measured, 3 slots, n=4096, fit+predict/s: 80 -> 1.58, 85 -> 1.62, 88 -> 1.64, 96 -> 1.68, 104 -> 1.64, 112 -> 1.68,
       // 120 -> 1.54, 128 -> 1.60, 170 -> 1.43, 256 -> 1.14.
       auto share_of = [&](int busy) {
-        const int share = busy <= 1 ? cus : std::max(8, (cus * env_int("HBEGP_DAG_OVERSUB", 112) / 100 / busy + 4) / 8 * 8);  // 3 slots: 96
+        const int share = busy <= 1 ? cus : std::max(8, (cus * 112 / 100 / busy + 4) / 8 * 8);  // 3 slots: 96
         return forced > 0 ? forced : std::max(1, std::min(cus, share));
       };
       // plans depend only on (blocks, stage depth, tiling and ordering knobs): the caller fits one model per generation with
@@ -847,33 +827,30 @@ struct Problem : ProblemBase {
       // 9.9 ms recursion / right-looking, 12288: 31.4 / 32.0, 16384: 72.3 / 75.5).
       dag_rl_ = env_int("HBEGP_DAG_RL", np / NB <= 80 ? 1 : 0) != 0;
       static std::mutex cache_mu;
-      static std::map<std::array<int, 20>, std::shared_ptr<const DagPlan>> cache;
+      static std::map<DagPlanKey, std::shared_ptr<const DagPlan>> cache;
       auto plan_for = [&](int nwg) {
-        std::array<int, 20> key = {np / NB, dag_stage_depth(is_f32), env_int("HBEGP_DAG_SMALLH", dag_rl_ ? 4 : 8), env_int("HBEGP_DAG_ORDER", 1) ? env_int("HBEGP_DAG_ORDER_WG", nwg) : 0,
-                                   env_int("HBEGP_DAG_FINE", 1), env_int("HBEGP_DAG_CRIT", 1), 0, dag_lauum_ ? 1 : 0, dag_rl_ ? 1 : 0,
-                                   env_int("HBEGP_DAG_RL_GROUP", 32), env_int("HBEGP_DAG_RL_NEAR", 1),
-                                   env_int("HBEGP_DAG_LAUUM_SPLIT", n_slots <= 1 ? 1 : 0),
-                                   env_int("HBEGP_DAG_CHAIN32", 1),
-                                   // row-progressive inverse and K^-1 (dag_plan.hpp rl_progressive) up to 20 blocks.  Measured (divide and
-                                   // conquer / progressive; one evaluation alone in ms, three-run fits per s): n=1536 0.65/0.65, 9.0/10.1;
-                                   // 2048 0.88/0.80, 6.4/7.1; 2560 1.12/1.05, 4.5/4.7; 3072 1.41/1.30, 3.37/3.21; 3584 1.75/1.67, 2.38/2.21;
-                                   // 4096 2.08/2.08, 1.67/1.55; C5 (n=2048 f32): 0.85/0.75 ms, 8.9/12.5 fits/s.  Above ~22 blocks the bulk
-                                   // tiles fill every CU and the chain's tasks wait for a free workgroup; a function of n alone, so that
-                                   // `extend` repeats a fit's evaluation bit for bit.
-                                   env_int("HBEGP_DAG_PROG", np / NB <= DAG_PROG_MAX_BLOCKS ? 1 : 0),
-                                   env_int("HBEGP_DAG_PROG_UNEAR", -1), env_int("HBEGP_DAG_PROG_KNEAR", -1), env_int("HBEGP_DAG_PROG_SMALL", 0),
-                                   0, 0,  // (round 4: geometric ranges, chain tasks moved forward in the queue -- measured, no gain, removed)
-                                   // 128x128 tiles for the deep products without beta = 1 when several slots share the chip (throughput: half the
-                                   // tasks, fewer fragment reads per MFMA): three-run fits M f64 1.727 -> 1.740, M f32 2.64 -> 2.77, C4 0.233 ->
-                                   // 0.245; one evaluation alone gets SLOWER (fewer, longer tasks on 256 workgroups: n=4096 2.08 -> 2.22 ms), so
-                                   // single-slot problems keep 128x64.  The bits do not depend on the tile shape (one k-ascending chain of MFMA
-                                   // accumulations per element), so `extend` still repeats a fit's evaluation bit for bit.
-                                   // Below 32 blocks the fits lose (n=1536 10.4 -> 8.5, 2048 7.0 -> 6.4, 3072 3.36 -> 3.13 fits/s: too few deep
-                                   // products, the longer tasks only unbalance the end of the launch).
-                                   // 2: also the tiles with beta = 1 (the trailing updates; the old values are then fetched in the epilogue): M f64
-                                   // 1.711 / 1.737 / 1.739 -> 1.753 / 1.754 / 1.756 (alternating), M f32 2.76 -> 2.80, C4 0.242 -> 0.249 fits/s.
-                                   // One evaluation alone: n=6144 4.58 -> 4.73 ms (worse), n=8192 9.69 -> 9.31 ms: from 64 blocks on there too.
-                                   env_int("HBEGP_DAG_BIG128", ((n_slots >= 2 && np / NB >= 32) || np / NB >= 64) ? 2 : 0)};  // one evaluation alone: 2.21 -> 2.17 ms at n=4096, 1.02 -> 0.97 at 2048; a fit: 1.67 -> 1.66
+        const DagPlanKey key = {np / NB, dag_stage_depth(is_f32), env_int("HBEGP_DAG_SMALLH", dag_rl_ ? 4 : 8), nwg, dag_lauum_, dag_rl_,
+                                env_int("HBEGP_DAG_RL_GROUP", 32), env_int("HBEGP_DAG_RL_NEAR", 1),
+                                env_int("HBEGP_DAG_LAUUM_SPLIT", n_slots <= 1 ? 1 : 0),
+                                env_int("HBEGP_DAG_CHAIN32", 1),
+                                // row-progressive inverse and K^-1 (dag_plan.hpp rl_progressive) up to 20 blocks.  Measured (divide and
+                                // conquer / progressive; one evaluation alone in ms, three-run fits per s): n=1536 0.65/0.65, 9.0/10.1;
+                                // 2048 0.88/0.80, 6.4/7.1; 2560 1.12/1.05, 4.5/4.7; 3072 1.41/1.30, 3.37/3.21; 3584 1.75/1.67, 2.38/2.21;
+                                // 4096 2.08/2.08, 1.67/1.55; C5 (n=2048 f32): 0.85/0.75 ms, 8.9/12.5 fits/s.  Above ~22 blocks the bulk
+                                // tiles fill every CU and the chain's tasks wait for a free workgroup; a function of n alone, so that
+                                // `extend` repeats a fit's evaluation bit for bit.
+                                env_int("HBEGP_DAG_PROG", np / NB <= DAG_PROG_MAX_BLOCKS ? 1 : 0),
+                                // 128x128 tiles for the deep products without beta = 1 when several slots share the chip (throughput: half the
+                                // tasks, fewer fragment reads per MFMA): three-run fits M f64 1.727 -> 1.740, M f32 2.64 -> 2.77, C4 0.233 ->
+                                // 0.245; one evaluation alone gets SLOWER (fewer, longer tasks on 256 workgroups: n=4096 2.08 -> 2.22 ms), so
+                                // single-slot problems keep 128x64.  The bits do not depend on the tile shape (one k-ascending chain of MFMA
+                                // accumulations per element), so `extend` still repeats a fit's evaluation bit for bit.
+                                // Below 32 blocks the fits lose (n=1536 10.4 -> 8.5, 2048 7.0 -> 6.4, 3072 3.36 -> 3.13 fits/s: too few deep
+                                // products, the longer tasks only unbalance the end of the launch).
+                                // 2: also the tiles with beta = 1 (the trailing updates; the old values are then fetched in the epilogue): M f64
+                                // 1.711 / 1.737 / 1.739 -> 1.753 / 1.754 / 1.756 (alternating), M f32 2.76 -> 2.80, C4 0.242 -> 0.249 fits/s.
+                                // One evaluation alone: n=6144 4.58 -> 4.73 ms (worse), n=8192 9.69 -> 9.31 ms: from 64 blocks on there too.
+                                env_int("HBEGP_DAG_BIG128", ((n_slots >= 2 && np / NB >= 32) || np / NB >= 64) ? 2 : 0)};  // one evaluation alone: 2.21 -> 2.17 ms at n=4096, 1.02 -> 0.97 at 2048; a fit: 1.67 -> 1.66
         std::shared_ptr<const DagPlan> cached;
         {
           std::lock_guard<std::mutex> lk(cache_mu);
@@ -881,10 +858,10 @@ struct Problem : ProblemBase {
           if (it != cache.end()) cached = it->second;
         }
         if (!cached) {
-          DagBuilder builder(key[1], key[2], key[3], key[4] != 0, key[5]);
-          builder.set_rl(key[9], key[10], key[11] != 0, key[12] != 0);
-          builder.set_rl_progressive(key[13] != 0, key[14], key[15], key[16] != 0);
-          builder.set_big128(key[19] != 0, key[19] >= 2);
+          DagBuilder builder(key.bk, key.small_h, key.nwg);
+          builder.set_rl(key.rl_group, key.rl_near, key.lauum_split != 0, key.chain32 != 0);
+          builder.set_rl_progressive(key.prog != 0);
+          builder.set_big128(key.big128 != 0, key.big128 >= 2);
           cached = std::make_shared<const DagPlan>(builder.build(0, np / NB, dag_lauum_, dag_rl_));
           std::lock_guard<std::mutex> lk(cache_mu);
           if (cache.size() > 64) cache.clear();
@@ -905,9 +882,6 @@ struct Problem : ProblemBase {
         const std::string why = dag_plan_validate(plan, np / NB);
         if (!why.empty()) throw std::runtime_error("task queue of the factorisation is unsound: " + why);
       }
-      if (dag_ && env_int("HBEGP_DAG_VERBOSE", 0))
-        fprintf(stderr, "dag plan: %zu tasks (%d K^-1 tiles), %zu counters, %d workgroups, critical path %.0f us, simulated %.0f us, %.2f GFLOP (%.2f in K^-1)\n",
-                plan.tasks.size(), plan.n_lauum, plan.totals.size(), dag_nwg, plan.crit_us, plan.sim_us, plan.gflop, plan.gflop_lauum);
       if (dag_) {
         dag_ntasks = (int)plan.tasks.size();
         dag_nwg = std::min(dag_nwg, dag_ntasks);
@@ -917,11 +891,7 @@ struct Problem : ProblemBase {
         // A dependency wait longer than this is reported as a scheduling bug (info = -2).  The clock runs on while the queue is
         // preempted or time-sliced (another process, a profiler serialising dispatches) and single waits grow with the plan, so
         // the bound follows the plan: 200 x its simulated makespan with every slot sharing the chip, at least 2 s.
-        {
-          const double wait_s = std::max(2.0, 200.0 * plan.sim_us * 1e-6 * std::max(1, n_slots));
-          const double forced_s = getenv("HBEGP_DAG_WAIT_S") ? atof(getenv("HBEGP_DAG_WAIT_S")) : 0.0;
-          dag_wait_ticks_ = (unsigned long long)((forced_s > 0 ? forced_s : wait_s) * 1e8);
-        }
+        dag_wait_ticks_ = (unsigned long long)(std::max(2.0, 200.0 * plan.sim_us * 1e-6 * std::max(1, n_slots)) * 1e8);
         busy_slots_.reset(new std::atomic<int>[c->devs.size()]);
         for (size_t di = 0; di < c->devs.size(); ++di) busy_slots_[di].store(0);
         // the variants: [nvar] = the default (every slot busy), [v < nvar] for v busy slots (HBEGP_DAG_ADAPT=0: default only)
@@ -953,7 +923,7 @@ struct Problem : ProblemBase {
         for (size_t di = 0; di < c->devs.size(); ++di) {
           HIPCHECK(hipSetDevice(c->devs[di]));
           for (auto& s : slots[di]) {
-            if (dag_rl_ && !s.W3) {
+            if (dag_rl_) {
               bool f3 = false;
               s.W3 = static_cast<T*>(g_pool.get(s.dev, sizeof(T) * nn, &f3));  // the factor L: every tile read has been written
             }
@@ -1058,7 +1028,7 @@ struct Problem : ProblemBase {
     if (hi - lo == 1) {
       if (dry_) return;
       if (tm) tm->begin(PhaseTimer::LEAF);
-      launch_leaf<T>(s.W1, s.W2, np, lo, s.ldiag, &s.dOut->info, s.stream, leaf_dbg_, refine_ ? s.W3 : nullptr);
+      launch_leaf<T>(s.W1, s.W2, np, lo, s.ldiag, &s.dOut->info, s.stream, leaf_dbg_);
       if (tm) tm->end();
       return;
     }
@@ -1071,35 +1041,17 @@ struct Problem : ProblemBase {
     if (!left_done) chol_inv_rec(s, di, lo, mid, tm);
     GemmOp base{};
     base.lda = base.ldb = base.ldc = np;
-    T* Tbuf = refine_ ? s.W3 : s.W2;  // where T = L21 lives: f32 keeps it (it IS the factor's block), f64 lets X21 overwrite it
     {
-      // T = A21 * X11^T  -> Tbuf[2,1]      (TRSM of potrf as a product with the explicit inverse)
+      // T = A21 * X11^T  -> W2[2,1]      (TRSM of potrf as a product with the explicit inverse; X21 overwrites it later)
       GemmLaunch g{};
       g.nops = 1;
       GemmOp& op = g.op[0];
       op = base;
-      op.A = s.W1; op.B = s.W2; op.C = Tbuf;
+      op.A = s.W1; op.B = s.W2; op.C = s.W2;
       op.a_kmajor = 0; op.b_kmajor = 0;
       op.ci0 = mid; op.mi = hi - mid; op.cj0 = lo; op.nj = mid - lo;
       op.k0 = lo; op.k1 = mid; op.klim = 1; op.maskB = 1;
       gemm(s, di, g, tm, PhaseTimer::GEMM);
-      if (refine_ && !left_done) {
-        // residual in place: A21 -= T * L11^T   (L11 = W3[lo:mid, lo:mid], lower), then the correction T += A21 * X11^T
-        GemmLaunch gr{};
-        gr.nops = 1;
-        GemmOp& r = gr.op[0];
-        r = base;
-        r.A = s.W3; r.B = s.W3; r.C = s.W1;
-        r.ci0 = mid; r.mi = hi - mid; r.cj0 = lo; r.nj = mid - lo;
-        r.k0 = lo; r.k1 = mid; r.klim = 1; r.maskB = 1; r.alpha_neg = 1; r.beta_one = 1;
-        gemm(s, di, gr, tm, PhaseTimer::GEMM);
-        GemmLaunch gc{};
-        gc.nops = 1;
-        GemmOp& cc = gc.op[0];
-        cc = op;
-        cc.beta_one = 1;
-        gemm(s, di, gc, tm, PhaseTimer::GEMM);
-      }
     }
     {
       // A22 -= T T^T (lower)   and   U = T * X11 -> W1[2,1]   (independent: one launch, one static schedule).
@@ -1109,12 +1061,12 @@ struct Problem : ProblemBase {
       g.nops = 2;
       GemmOp& syrk = g.op[0];
       syrk = base;
-      syrk.A = Tbuf; syrk.B = Tbuf; syrk.C = s.W1;
+      syrk.A = s.W2; syrk.B = s.W2; syrk.C = s.W1;
       syrk.ci0 = mid; syrk.cj0 = mid; syrk.mi = hi - mid; syrk.nj = hi - mid; syrk.c_lower = 1;
       syrk.k0 = lo; syrk.k1 = mid; syrk.alpha_neg = 1; syrk.beta_one = 1;
       GemmOp& u = g.op[1];
       u = base;
-      u.A = Tbuf; u.B = s.W2; u.C = s.W1;
+      u.A = s.W2; u.B = s.W2; u.C = s.W1;
       u.a_kmajor = 0; u.b_kmajor = 1;
       u.ci0 = mid; u.mi = hi - mid; u.cj0 = lo; u.nj = mid - lo;
       u.k0 = lo; u.k1 = mid; u.klim = 2; u.maskB = 1;
@@ -1184,16 +1136,13 @@ struct Problem : ProblemBase {
 
   void small_eval(Slot<T>& s, size_t di, int target, int mode) {
     SmallEval g{};
-    g.X = Xd[di]; g.y = yd[di]; g.n = n; g.d = d; g.P = s.dP;
+    g.X = Xd[di]; g.y = yd[di]; g.n = n; g.d = d;
     g.W2 = s.W2; g.ldiag = s.ldiag; g.Kinv = s.Kinv[target]; g.alpha = s.alpha[target]; g.out = s.dOut; g.mode = mode;
     // The kernel reads the parameters from, and writes its few scalar results to, the slot's pinned host blocks itself: the
     // captured graph of an evaluation is ONE node (no parameter copy, no reset kernel, no result copy -- each was ~2-5 us of
-    // a 57 us evaluation).  HBEGP_SMALL_HOSTIO=0: through device memory and copy nodes, as the general path does.
-    static const bool hostio = env_int("HBEGP_SMALL_HOSTIO", 1) != 0;
-    if (hostio) { g.P = s.hP; g.hout = s.hOut; }
-    else { g.hout = s.dOut; HIPCHECK(hipMemcpyAsync(s.dP, s.hP, sizeof(EvalParams), hipMemcpyHostToDevice, s.stream)); }
+    // a 57 us evaluation).
+    g.P = s.hP; g.hout = s.hOut;
     launch_small_eval<T>(g, nu2, s.stream);
-    if (!hostio) HIPCHECK(hipMemcpyAsync(s.hOut, s.dOut, sizeof(EvalOut), hipMemcpyDeviceToHost, s.stream));
   }
 
   void enqueue_eval(Slot<T>& s, size_t di, int target, bool want_grad, PhaseTimer* tm) {
@@ -1277,13 +1226,12 @@ struct Problem : ProblemBase {
   // thread falls back to hipStreamSynchronize, which reports the fault (or simply waits for a very long evaluation).
   // Long evaluations are slept through first: the thread remembers how long this slot's last evaluation took (they are all
   // alike) and, from 1.5 ms on, sleeps until an eighth of it (at least 300 us) before that: a fit at n = 4096 then keeps 1.4 cores busy
-  // instead of 4 (hipStreamSynchronize spins as well: 4 cores with HBEGP_HOSTIO=0 too; tools/cpu_cost_probe.py).  A sleep that ran past the end shortens the next one.  HBEGP_SPIN_ONLY=1: no sleeping.
+  // instead of 4 (hipStreamSynchronize spins as well: 4 cores with HBEGP_HOSTIO=0 too; tools/cpu_cost_probe.py).  A sleep that ran past the end shortens the next one.
   void wait_eval(Slot<T>& s, std::chrono::steady_clock::time_point t_launch) {
     if (s.published) {
       using namespace std::chrono;
-      static const bool spin_only = env_int("HBEGP_SPIN_ONLY", 0) != 0;
       const volatile unsigned long long* q = &s.hOut->seq;
-      if (!spin_only && s.expect_ns > 1500000) {  // below ~1.5 ms a timer's wake-up jitter (50-100 us) costs more than it saves: n=512 fits 29.7 -> 21.6 /s with a 0.4 ms threshold
+      if (s.expect_ns > 1500000) {  // below ~1.5 ms a timer's wake-up jitter (50-100 us) costs more than it saves: n=512 fits 29.7 -> 21.6 /s with a 0.4 ms threshold
         const long long margin = std::max<long long>(300000, s.expect_ns / 8);  // concurrent runs stretch each other by a few per cent, unevenly
         std::this_thread::sleep_until(t_launch + nanoseconds(s.expect_ns - margin));
         if (*q == s.seq) {  // slept too long: the measurement below would include the oversleep
@@ -1551,10 +1499,6 @@ struct Problem : ProblemBase {
           float dt = 0;
           HIPCHECK(hipEventElapsedTime(&dt, rec.a, rec.b));
           const double v = dt / treps;
-          static const bool dump = env_int("HBEGP_TRACE_LAUNCHES", 0) != 0;
-          if (dump && r == treps - 1)
-            fprintf(stderr, "launch kind=%d tile=%d gflop=%.4f ms=%.4f tflops=%.2f\n", rec.kind, rec.tile, rec.gflop, dt,
-                    dt > 0 ? rec.gflop / dt : 0.0);
           if (rec.kind == PhaseTimer::KMAT) phase_ms[0] += v;
           if (rec.kind == PhaseTimer::GEMM) { phase_ms[1] += v; phase_ms[7] += 1.0 / treps; }
           if (rec.kind == PhaseTimer::LEAF) { phase_ms[2] += v; phase_ms[15] += 1.0 / treps; }
@@ -1790,10 +1734,7 @@ template <typename T>
 static int model_predict(hbegp_model* m, const T* Xs, int cnt, T* mean, T* var, int* n_warn) {
   std::lock_guard<std::mutex> lock(m->mu);
   HIPCHECK(hipSetDevice(m->dev));
-  static const bool small_on = env_int("HBEGP_PRED_SMALL", 1) != 0;
-  static const bool kinv_form_small = env_int("HBEGP_PREDVAR_KINV", 0) != 0;
-  static const int small_max = std::min(PRED_SMALL_MAX, std::max(0, env_int("HBEGP_PRED_SMALL_MAX", 8)));
-  if (small_on && cnt <= small_max && !kinv_form_small) {
+  if (cnt <= 8) {
     // a handful of candidates (the caller's scalar predict_* loops): read L^-1 once instead of a padded 128-row tile GEMM
     const size_t out_bytes = sizeof(T) * 2 * PRED_SMALL_MAX + 16;
     if (!m->sm_Xs) {
@@ -1845,7 +1786,9 @@ static int model_predict(hbegp_model* m, const T* Xs, int cnt, T* mean, T* var, 
                   static_cast<T*>(m->Ks), s);
   launch_pred_mean<T>(static_cast<T*>(m->Ks), cnt, m->np, static_cast<T*>(m->alpha), static_cast<T*>(m->mean), s);
   if (var) {
-    static const bool kinv_form = env_int("HBEGP_PREDVAR_KINV", 0) != 0;
+    // The reference's k*^T K^-1 k* (predict.rs:30-37) as |L^-1 k*|^2: Q = Kstar * X^T (X = L^-1 lower: k <= j, half the
+    // flops), then var = c + 1e-5 - rowsum(Q o Q).  A sum of squares has no cancellation inside the quadratic form, so the
+    // result is at least as close to the exact value as the K^-1 form.
     GemmLaunch g{};
     g.nops = 1;
     g.info = &m->dOut->info;
@@ -1853,20 +1796,10 @@ static int model_predict(hbegp_model* m, const T* Xs, int cnt, T* mean, T* var, 
     op.lda = m->np; op.ldb = m->np; op.ldc = m->np;
     op.ci0 = 0; op.cj0 = 0; op.mi = mp / NB; op.nj = m->np / NB;
     op.k0 = 0; op.k1 = m->np / NB;
-    if (kinv_form) {
-      // the reference's literal formula (predict.rs:30-37): Q = Kstar * Kinv, var = c + 1e-5 - rowsum(Q o Kstar)
-      op.A = m->Ks; op.B = m->Kinv; op.C = m->Q;
-      launch_gemm<T>(g, pick_tile(op.mi * op.nj), s);
-      launch_pred_var<T>(static_cast<T*>(m->Ks), static_cast<T*>(m->Q), cnt, m->np, m->dP, static_cast<T*>(m->var), m->dOut, s);
-    } else {
-      // same quantity as k*^T K^-1 k* = |L^-1 k*|^2: Q = Kstar * X^T (X = L^-1 lower: k <= j, half the flops), then
-      // var = c + 1e-5 - rowsum(Q o Q).  A sum of squares has no cancellation inside the quadratic form, so the
-      // result is at least as close to the exact value as the K^-1 form.
-      op.A = m->Ks; op.B = m->Xinv; op.C = m->Q;
-      op.klim = 1; op.maskB = 1;
-      launch_gemm<T>(g, pick_tile(op.mi * op.nj), s);
-      launch_pred_var<T>(static_cast<T*>(m->Q), static_cast<T*>(m->Q), cnt, m->np, m->dP, static_cast<T*>(m->var), m->dOut, s);
-    }
+    op.A = m->Ks; op.B = m->Xinv; op.C = m->Q;
+    op.klim = 1; op.maskB = 1;
+    launch_gemm<T>(g, pick_tile(op.mi * op.nj), s);
+    launch_pred_var<T>(static_cast<T*>(m->Q), static_cast<T*>(m->Q), cnt, m->np, m->dP, static_cast<T*>(m->var), m->dOut, s);
   }
   CHECK_LAUNCHES();
   HIPCHECK(hipMemcpyAsync(mean, m->mean, sizeof(T) * cnt, hipMemcpyDeviceToHost, s));
@@ -1912,8 +1845,7 @@ static int do_fit(hbegp_ctx* ctx, const T* X, const T* y, int n, int d, double n
   // Up to 128 rows an optimiser run is ONE persistent launch on ONE compute unit (small_fit_kernel: evaluation + L-BFGS step +
   // capture on the device): every run gets a slot of its own and all of them run side by side
   constexpr int SMALL_FIT_MAX_RUNS = 64;  // per device
-  bool small_fit = round_up(n, NB) == NB && d <= SMALL_EVAL_MAXD && env_int("HBEGP_SMALL", 1) != 0 && env_int("HBEGP_SMALL_FIT", 1) != 0 &&
-                   !(sizeof(T) == 4 && env_int("HBEGP_F32_REFINE", 0) != 0);
+  bool small_fit = round_up(n, NB) == NB && d <= SMALL_EVAL_MAXD && env_int("HBEGP_SMALL", 1) != 0 && env_int("HBEGP_SMALL_FIT", 1) != 0;
   for (int di = 0; di < ndev; ++di) small_fit = small_fit && runs_on[di] <= SMALL_FIT_MAX_RUNS;
   if (small_fit)
     for (int di = 0; di < ndev; ++di) n_slots = std::max(n_slots, runs_on[di]);
@@ -2021,16 +1953,13 @@ static int do_fit(hbegp_ctx* ctx, const T* X, const T* y, int n, int d, double n
         f.Kinv[0] = s.Kinv[0]; f.Kinv[1] = s.Kinv[1]; f.alpha[0] = s.alpha[0]; f.alpha[1] = s.alpha[1];
         // L^-1 and diag(L) ping-pong too: the captured evaluation's factor survives the run, the model takes it as it is (no
         // factorisation at the captured theta behind the fit: one small launch and a wait less inside the model's turn)
-        static const bool x_pingpong = env_int("HBEGP_SMALL_X_PINGPONG", 1) != 0;
-        if (x_pingpong) {
-          if (!s.Xalt) {
-            s.Xalt = prob.template palloc<T>(s.dev, (size_t)NB * NB);
-            s.ldalt = prob.template palloc<T>(s.dev, NB);
-            HIPCHECK(hipMemsetAsync(s.Xalt, 0, sizeof(T) * NB * NB, st));  // the strict upper triangle must be zero, like W2's
-          }
-          f.Xinv[0] = s.W2; f.Xinv[1] = s.Xalt; f.ldiag[0] = s.ldiag; f.ldiag[1] = s.ldalt;
-          s.x_captured = true;
+        if (!s.Xalt) {
+          s.Xalt = prob.template palloc<T>(s.dev, (size_t)NB * NB);
+          s.ldalt = prob.template palloc<T>(s.dev, NB);
+          HIPCHECK(hipMemsetAsync(s.Xalt, 0, sizeof(T) * NB * NB, st));  // the strict upper triangle must be zero, like W2's
         }
+        f.Xinv[0] = s.W2; f.Xinv[1] = s.Xalt; f.ldiag[0] = s.ldiag; f.ldiag[1] = s.ldalt;
+        s.x_captured = true;
         f.st = w.st; f.x0 = w.x0; f.lo = w.x0 + p; f.hi = w.x0 + 2 * p;
         LbfgsOptions lo_opt;
         f.maxeval = opt.maxeval; f.memory = opt.lbfgs_memory > 0 ? opt.lbfgs_memory : lo_opt.memory; f.fixed_work = opt.fixed_work != 0;
@@ -2280,7 +2209,7 @@ static int do_extend(hbegp_ctx* ctx, const T* X, const T* y, int n, int d, doubl
   // arithmetic does not depend on how the launch is scheduled).
   const int dag_env = env_int("HBEGP_DAG", -1);
   const bool queue_like_fit = (dag_env < 0 ? round_up(n, NB) / NB >= env_int("HBEGP_DAG_MIN_BLOCKS", DAG_MIN_BLOCKS_FIT) : dag_env != 0) && round_up(n, NB) / NB >= 2;
-  Problem<T> prob(&one, X, y, n, d, nu, 1, !queue_like_fit && env_int("HBEGP_EXTEND_SCHED", 0) == 0, true);
+  Problem<T> prob(&one, X, y, n, d, nu, 1, !queue_like_fit, true);
   const int p = d + 2;
   Slot<T>& s = prob.slots[0][0];
   theta_to_params(theta, lo, hi, d, s.hP);
@@ -2390,7 +2319,6 @@ int hbegp_ctx_create(int n_devices, const int* device_ids, hbegp_ctx** out) {
     if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
       return fail(HBEGP_ENODEV, "device %d is %s; this library only carries gfx950 code", id, prop.gcnArchName);
     HIPCHECK(hipSetDevice(id));
-    if (env_int("HBEGP_SPIN", 0)) (void)hipSetDeviceFlags(hipDeviceScheduleSpin);
     init_kernels();
     ctx->devs.push_back(id);
   }
@@ -2693,7 +2621,7 @@ int hbegp_debug_dag_plan(int nblocks, int bk, int small_h, int nwg, int fine, in
   if (nblocks < 1 || (bk != 16 && bk != 32) || small_h < 0 || nwg < 0) return fail(HBEGP_EINVAL, "bad argument");
   GUARD_BEGIN
   DagBuilder builder(bk, small_h, nwg, (fine & 1) != 0);
-  builder.set_rl_progressive((fine & 16) != 0, -1, -1, false);
+  builder.set_rl_progressive((fine & 16) != 0);
   builder.set_big128(getenv("HBEGP_DAG_BIG128") && atoi(getenv("HBEGP_DAG_BIG128")) != 0, getenv("HBEGP_DAG_BIG128") && atoi(getenv("HBEGP_DAG_BIG128")) >= 2);
   // bit 1: unused (rounds 2-4: kernel-matrix tiles and alpha / lml reductions as tasks too); bit 2: the K^-1 = X^T X tiles behind
   // the recursion; bit 3: the right-looking plan; bit 4: its row-progressive inverse and K^-1

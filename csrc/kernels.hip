@@ -74,23 +74,17 @@ __device__ __forceinline__ float readlane(float v, int lane) {
 // =================================================================================================================
 // Tile GEMM
 // =================================================================================================================
-#ifndef HBEGP_F32_CHUNK
-#define HBEGP_F32_CHUNK 32  /* round 4, 64 (make variant DEFS=-DHBEGP_F32_CHUNK=64): C5 f32 fits 8.63 -> 9.70 /s, M f32 2.78 -> 2.79, but alpha at cond(K) = 7e4 leaves the plain 1e-4 bar (8e-5 -> 1.03e-4, tests/test_gpu_fullsize.py): stays 32 */
-#endif
-constexpr int F32_CHUNK = HBEGP_F32_CHUNK;  // contraction elements per f32 accumulation chunk (see gemm_kernel); boundaries at absolute multiples
+// contraction elements per f32 accumulation chunk (see gemm_kernel); boundaries at absolute multiples.  64 was measured (C5 f32
+// fits 8.63 -> 9.70 /s, M f32 2.78 -> 2.79), but alpha at cond(K) = 7e4 then leaves the plain 1e-4 bar (8e-5 -> 1.03e-4,
+// tests/test_gpu_fullsize.py)
+constexpr int F32_CHUNK = 32;
 
 template <typename T, int TILE, int KM = 0>
 struct GemmGeom {
   using C = Cfg<T>;
-  // contraction depth per LDS stage: 128 bytes of k for the big tiles, 512 bytes for the 32-tiles (small, latency-bound
-  // launches: fewer, fatter stages)
-#ifndef HBEGP_KMUL32
-#define HBEGP_KMUL32 2  /* measured in the 3-stream bench: 1 -> 1.104, 2 -> 1.127, 4 -> 1.054 fit+predict/s */
-#endif
-#ifndef HBEGP_KMUL64
-#define HBEGP_KMUL64 1
-#endif
-  static constexpr int BKE = (KM > 0 ? KM : (TILE == 32 ? HBEGP_KMUL32 : (TILE == 64 ? HBEGP_KMUL64 : 1))) * C::BK;
+  // contraction depth per LDS stage: 128 bytes of k for the big tiles, 256 bytes for the 32-tiles (small, latency-bound
+  // launches: fewer, fatter stages; measured in the 3-stream bench, 32-tile depth x1 / x2 / x4: 1.104 / 1.127 / 1.054 fit+predict/s)
+  static constexpr int BKE = (KM > 0 ? KM : (TILE == 32 ? 2 : 1)) * C::BK;
   static constexpr int SK = BKE + 2;          // LDS row stride, operand stored [outer][k]
   static constexpr int SM = TILE + 16;        // LDS row stride, operand stored [k][outer]
   static constexpr int LDSE = (TILE * SK > BKE * SM) ? TILE * SK : BKE * SM;  // elements per operand buffer
@@ -106,12 +100,6 @@ __device__ __forceinline__ int tri_row(int idx) {
   return r;
 }
 
-#ifndef HBEGP_XBAR
-#define HBEGP_XBAR 1  /* 64-tile: 64.7 -> 66.9 TFLOP/s at 3 workgroups per CU, 64.0 -> 66.5 at 2, 55.0 -> 61.5 at 1; 32-tile: 55.0 -> 52.9 */
-#endif
-#ifndef HBEGP_T128_TWOSETS
-#define HBEGP_T128_TWOSETS 0  /* two register sets spill at 128 accumulator registers: 52.9 vs 59.7 TFLOP/s */
-#endif
 template <typename T, int TILE, int KM = 0>
 __global__ void __launch_bounds__(256, 2) gemm_kernel(GemmLaunch g) {
   using C = Cfg<T>;
@@ -300,8 +288,9 @@ __global__ void __launch_bounds__(256, 2) gemm_kernel(GemmLaunch g) {
     kabs += BK;
   };
 
-  if constexpr (TILE == 128 && !HBEGP_T128_TWOSETS) {
-    // one register set (the 128-tile already holds 128 accumulator registers): loads of stage s+1 fly during stage s
+  if constexpr (TILE == 128) {
+    // one register set (the 128-tile already holds 128 accumulator registers; two spill: 52.9 vs 59.7 TFLOP/s): loads of
+    // stage s+1 fly during stage s
     if (nstages > 0) {
       load_stage(ra0, rb0);
       store_stage(0, ra0, rb0);
@@ -320,12 +309,12 @@ __global__ void __launch_bounds__(256, 2) gemm_kernel(GemmLaunch g) {
       compute_stage(s & 1);
       __syncthreads();
     }
-  } else {
-    if constexpr (TILE == 64 && HBEGP_XBAR) {
+  } else if constexpr (TILE == 64) {
     // Software pipelining across the stage barrier: the fragments of a whole stage live in registers, the LDS stores of
     // the next stage are issued before the last-but-one k-step and the first fragments of the next stage are read
     // right after the barrier, under the MFMAs of the last k-step -- so neither the store latency nor the first read
-    // latency sits between a barrier and an MFMA.
+    // latency sits between a barrier and an MFMA.  Measured: 64.7 -> 66.9 TFLOP/s at 3 workgroups per CU, 64.0 -> 66.5
+    // at 2, 55.0 -> 61.5 at 1; the 32-tile loses with it (55.0 -> 52.9).
     constexpr int NK = BK / 4;
     T fa[NK][TM], fb[NK][TM];
     auto read_frags = [&](int buf, int k4) {
@@ -382,7 +371,7 @@ __global__ void __launch_bounds__(256, 2) gemm_kernel(GemmLaunch g) {
       if (left > 2) stage(0, false, ra0, rb0, false, ra1, rb1, false);
       __syncthreads();  // the next tile of this workgroup overwrites LDS
     }
-    } else {
+  } else {
     // prologue: stage 0 -> LDS buffer 0, stage 1 -> register set 1
     if (nstages > 0) {
       load_stage(ra0, rb0);
@@ -431,7 +420,6 @@ __global__ void __launch_bounds__(256, 2) gemm_kernel(GemmLaunch g) {
         }
       }
     }
-    }
   }
 
   // epilogue
@@ -478,8 +466,6 @@ static void launch_gemm_t(const GemmLaunch& gl, hipStream_t s) {
     const size_t share = ((size_t)163840 / (size_t)(g.sched_nwg / 256)) / 4096 * 4096;  // LDS is allocated in coarse granules
     if (share > lds) lds = share;
   }
-  static const size_t lds_min = getenv("HBEGP_GEMM_LDS_MIN") ? (size_t)atol(getenv("HBEGP_GEMM_LDS_MIN")) : 0;  // experiments: cap residency
-  if (lds_min > lds) lds = lds_min;
   hipLaunchKernelGGL((gemm_kernel<T, TILE>), dim3(total), dim3(256), lds, s, g);
 }
 
@@ -521,9 +507,6 @@ struct LeafGeom {
 //   G(i,j):    S[i,j] += L[i,k2] X[k2,j]           {L block (i,k2), X^T block (j,k2) or Yt_k2, S^T block (j,i), 0},  i >= p+1, j <= k2
 //   GU1(j):    S[p,j] += L[p,k2] X[k2,j], j <= k2  (as G)
 //   GU2(j):    S[p,j] += L[p,k] X[k,j],  j <= k    (as G; for j < k it waits for F(j)'s flag)
-#ifndef LEAF_WAVE4_WORKS
-#define LEAF_WAVE4_WORKS 1  /* wave 4 shares a SIMD with wave 0 and slows its elimination by a fifth (2370 -> 2870-3140 cycles), but the MFMA items are what a phase waits for: 25.8 -> 24.7 us per block */
-#endif
 constexpr int LEAF_S = 130;
 constexpr int LEAF_YT0 = 128 * LEAF_S;       // element offset of the image of the transposed 16x16 inverses: Y_q[r][c] at YT0 + c S + 16 q + r
 constexpr int LEAF_MAXITEMS = 26;
@@ -567,8 +550,9 @@ constexpr LeafItemTab leaf_build_items(int xcol_bytes) {
     // Round-robin dealing of the phase's items to its MFMA waves, continuing across the lists: waves 1, 2, 3, 5, 7 while wave 6
     // is the helper (p < 4), then 1, 2, 3, 5, 6, 7; wave 4 (it shares a SIMD with the eliminating wave 0) comes last.  The
     // first item of every wave in every list is tabulated: no division at run time (an integer modulo costs ~30
-    // instructions -- more than half an item).
-    const int nw = (p < 4 ? 5 : 6) + LEAF_WAVE4_WORKS;
+    // instructions -- more than half an item).  Wave 4 slows wave 0's elimination by a fifth (2370 -> 2870-3140 cycles), but
+    // the MFMA items are what a phase waits for: 25.8 -> 24.7 us per block with it.
+    const int nw = p < 4 ? 6 : 7;
     const int starts[4] = {0, leaf_nf(p), leaf_nf(p) + leaf_nu(p), leaf_nf(p) + leaf_nu(p) + leaf_ng(p)};  // GU: its own numbering (j)
     for (int w = 0; w < 8; ++w) {
       const int widx = w <= 3 ? w - 1 : (w == 4 ? nw - 1 : (w == 5 ? 3 : (p < 4 ? 4 : w - 2)));
@@ -701,8 +685,7 @@ __device__ __forceinline__ void gstore(TIO* p, TIO v) {
 // barrier): small_eval_kernel assembles the kernel matrix there and never writes it to HBM.
 template <typename T, typename TIO, bool SC1, bool FROM_LDS = false>
 __device__ __forceinline__ void leaf_body(TIO* __restrict__ W1, TIO* __restrict__ W2, int ld, int blk,
-                                          TIO* __restrict__ ldiag, int* info, int dbg, char* smem_raw,
-                                          TIO* __restrict__ W3 = nullptr) {
+                                          TIO* __restrict__ ldiag, int* info, int dbg, char* smem_raw) {
   static_assert(sizeof(T) == 8, "the diagonal block is factored in fp64");
   using C = Cfg<T>;
   using L = LeafGeom<T>;
@@ -967,7 +950,7 @@ __device__ __forceinline__ void leaf_body(TIO* __restrict__ W1, TIO* __restrict_
         }
         LEAF_STAMP(42 + 3 * p);
       }
-    } else if (p > 0 && (LEAF_WAVE4_WORKS || wave != 4)) {
+    } else if (p > 0) {
       // the other waves meanwhile
       pool_phase(p);
     }
@@ -1017,30 +1000,22 @@ __device__ __forceinline__ void leaf_body(TIO* __restrict__ W1, TIO* __restrict_
       atomicCAS(info, 0, 1 + blk * NB + (first & ~15));  // reported per 16-column panel, as rounds 1-3 did
     }
   }
-  // optional: the factor itself (lower triangle of the block), for the f32 path's refinement of the panel solve
-  if (W3) {
-    TIO* Lblk = W3 + g0;
-    for (int c = t; c < 128 * 128; c += 512) {
-      const int r = c >> 7, j = c & 127;
-      if (j <= r) gstore<SC1>(&Lblk[(size_t)r * ld + j], (TIO)As[r * S + j]);
-    }
-  }
 }
 
 template <typename T, typename TIO>
 __global__ void __launch_bounds__(512, 2) leaf_kernel(TIO* __restrict__ W1, TIO* __restrict__ W2, int ld, int blk,
-                                                   TIO* __restrict__ ldiag, int* info, int dbg, TIO* __restrict__ W3) {
+                                                   TIO* __restrict__ ldiag, int* info, int dbg) {
   if (*info != 0) return;
   extern __shared__ __align__(16) char smem_raw[];
-  leaf_body<T, TIO, false>(W1, W2, ld, blk, ldiag, info, dbg, smem_raw, W3);
+  leaf_body<T, TIO, false>(W1, W2, ld, blk, ldiag, info, dbg, smem_raw);
 }
 
 template <typename T>
-void launch_leaf(T* W1, T* W2, int ld, int blk, T* ldiag, int* info, hipStream_t s, int dbg, T* W3) {
-  hipLaunchKernelGGL((leaf_kernel<double, T>), dim3(1), dim3(512), LeafGeom<double>::LDS_BYTES, s, W1, W2, ld, blk, ldiag, info, dbg, W3);
+void launch_leaf(T* W1, T* W2, int ld, int blk, T* ldiag, int* info, hipStream_t s, int dbg) {
+  hipLaunchKernelGGL((leaf_kernel<double, T>), dim3(1), dim3(512), LeafGeom<double>::LDS_BYTES, s, W1, W2, ld, blk, ldiag, info, dbg);
 }
-template void launch_leaf<double>(double*, double*, int, int, double*, int*, hipStream_t, int, double*);
-template void launch_leaf<float>(float*, float*, int, int, float*, int*, hipStream_t, int, float*);
+template void launch_leaf<double>(double*, double*, int, int, double*, int*, hipStream_t, int);
+template void launch_leaf<float>(float*, float*, int, int, float*, int*, hipStream_t, int);
 
 // =================================================================================================================
 // Kernel-matrix assembly
@@ -2100,7 +2075,7 @@ __device__ __forceinline__ void small_eval_body(const SmallEval& g, char* smem_r
 
   // ---- L and X = L^-1
   TIO* W2 = static_cast<TIO*>(g.W2);
-  leaf_body<T, TIO, false, true>(nullptr, W2, 128, 0, static_cast<TIO*>(g.ldiag), &g.out->info, 0, smem_raw, nullptr);
+  leaf_body<T, TIO, false, true>(nullptr, W2, 128, 0, static_cast<TIO*>(g.ldiag), &g.out->info, 0, smem_raw);
   __syncthreads();
   if (t == 0) g_leaf_stamps[202] = (long long)__builtin_readcyclecounter();
   if (pool[15] != 0) {  // not positive definite: the outputs stay poisoned (lml.rs:47-50)

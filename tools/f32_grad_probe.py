@@ -42,5 +42,3 @@ for name, ki in (("device", kinv.astype(np.float64)), ("lapack32", r32["k_inv"].
     dg = np.diag(R)
     print(name, "trace(R)/n = %.3e" % (dg.sum() / n), " per 128-block mean diag(R):", " ".join("%.1e" % dg[b:b + 128].mean() for b in range(0, n, 128)))
     print(name, " |R|_max = %.2e" % np.abs(R).max())
-if os.environ.get("HBEGP_F32_REFINE", "1") != "0":
-    pass

@@ -2,18 +2,18 @@
 """Where do the loads of the 16 panel entries a[0..15] sit inside the diagonal block's elimination chain?
 
 usage: leaf_isa_window.py <device .s file> [<function substring> ...]
-(make the .s with: hipcc -O3 -std=c++17 --offload-arch=gfx950 --cuda-device-only -S [-DLEAF_DIAG_COPY=0] [-DDAG_LEAF_NOINLINE=1] csrc/kernels.hip)
+(make the .s with: make build/kernels.s)
 
 For every function that contains an elimination (16 consecutive v_rsq_f64, one per pivot) the script prints, per ds_read of
 panel data issued after the first pivot, the index of the last pivot whose v_rsq_f64 precedes it, and the instruction counts
 first pivot -> that load -> first ds_write of the results.  A load that sits behind pivot k of 16 is a load the helper waves
 issue roughly k/16 of the way through THEIR elimination: if wave 0 is ahead by the remaining (16-k)/16 of the chain it has
-already overwritten those pivot rows with L (round 2's non-reproducibility; fixed by LEAF_DIAG_COPY)."""
+already overwritten those pivot rows with L (round 2's non-reproducibility; fixed by the pivot-row copy in leaf_body)."""
 import re
 import sys
 
 path = sys.argv[1]
-want = sys.argv[2:] or ["leaf_kernelIdd", "dag_kernelIdLi0E", "dag_leaf_taskId"]
+want = sys.argv[2:] or ["leaf_kernelIdd", "dag_kernelId", "dag_leaf_taskId"]
 lines = open(path).read().split("\n")
 starts = [(i, l[:-1].split(":")[0]) for i, l in enumerate(lines) if re.match(r"^_Z\w+:", l)]
 for idx, (i0, name) in enumerate(starts):

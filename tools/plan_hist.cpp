@@ -6,7 +6,7 @@
 using namespace hbegp;
 int main(int argc, char** argv) {
   const int nb = argc > 1 ? atoi(argv[1]) : 32, nwg = argc > 2 ? atoi(argv[2]) : 96, bk = argc > 3 ? atoi(argv[3]) : 16;
-  DagBuilder b(bk, 4, nwg, true, 1);
+  DagBuilder b(bk, 4, nwg);
   b.set_rl(32, 1, false);
   DagPlan p = b.build(0, nb, true, true);
   std::map<std::pair<int, int>, std::pair<int, double>> h;

@@ -11,9 +11,9 @@ int main() {
     for (int rl = 0; rl < 2; ++rl)
       for (int bk : {16, 32})
         for (int nwg : {0, 3, 96, 256}) {
-          DagBuilder b(bk, rl ? 4 : 8, nwg, true, 1);
+          DagBuilder b(bk, rl ? 4 : 8, nwg);
           b.set_rl(32, 1, nb % 2 == 0);
-          b.set_rl_progressive(rl != 0 && nb % 3 != 0, -1, -1, nb % 2 == 1);  // two thirds of the right-looking plans: row-progressive inverse
+          b.set_rl_progressive(rl != 0 && nb % 3 != 0);  // two thirds of the right-looking plans: row-progressive inverse
           b.set_big128(nb % 4 < 2);
           DagPlan p = b.build(0, nb, true, rl != 0);
           if (p.tasks.empty()) { if (nb >= 2) ++bad; continue; }

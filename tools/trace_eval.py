@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Write a task trace of one evaluation (HBEGP_DAG_TRACE must name the output file) and analyse it.
-Usage: HBEGP_DAG_TRACE=out.txt [HBEGP_DAG_SPLIT=1 ...] trace_eval.py [n]"""
+Usage: HBEGP_DAG_TRACE=out.txt [HBEGP_DAG_RL=0 ...] trace_eval.py [n]"""
 import os, subprocess, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from hbetune_rs_amd import gpr, synth
