@@ -189,6 +189,16 @@ template <typename T>
 void launch_pred_mean(const T* Ks, int m, int np, const T* alpha, T* mean, hipStream_t s);
 template <typename T>
 void launch_pred_var(const T* Ks, const T* Q, int m, int np, const EvalParams* P, T* var, EvalOut* out, hipStream_t s);
+// posterior gradient w.r.t. the candidates: dmean[m][d] (part: pred_grad_chunks(n) * m * d doubles); G[d][mp][np] = dKstar/dx*_k;
+// dvar[m][d] = -2 rowsum(W_k o Q) with W = G X^T (tile GEMM), 0 where the clamped variance var[i] is 0
+template <typename T>
+void launch_pred_grad(const T* Xs, int m, const T* X, int n, int d, int nu2, const EvalParams* P, const T* alpha, double* part, T* dmean,
+                      hipStream_t s);
+template <typename T>
+void launch_kstar_grad(const T* Xs, int m, int mp, const T* X, int n, int d, int np, int nu2, const EvalParams* P, T* G, hipStream_t s);
+template <typename T>
+void launch_pred_dvar(const T* W, const T* Q, int m, int mp, int np, int d, const T* var, T* dvar, hipStream_t s);
+int pred_grad_chunks(int n);
 
 // predict for m <= PRED_SMALL_MAX candidates without the 128-row padding: reads L^-1 once (row dots against the m
 // cross-kernel vectors).  Ks: [PRED_SMALL_MAX][np] scratch, pmean: [(np+255)/256][PRED_SMALL_MAX], w: [n][PRED_SMALL_MAX].

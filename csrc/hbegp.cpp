@@ -1642,6 +1642,9 @@ struct hbegp_model {
   // predict scratch (grow-only)
   int cap_m = 0;
   void *Xs = nullptr, *Ks = nullptr, *Q = nullptr, *mean = nullptr, *var = nullptr;
+  // gradient scratch (grow-only): G = dKstar/dx*, W = G X^T [d x cap_g x np], the chunk partial sums, dmean / dvar [cap_g x d]
+  int cap_g = 0;
+  void *G = nullptr, *W = nullptr, *gpart = nullptr, *dmean = nullptr, *dvar = nullptr;
   // scratch of the path for a handful of candidates (allocated on first use): device [Xs | Ks | out], partial sums, and
   // pinned host staging so that a single-point predict costs one H2D and one D2H
   void *sm_Xs = nullptr, *sm_Ks = nullptr, *sm_out = nullptr, *sm_hin = nullptr, *sm_hout = nullptr;
@@ -1730,6 +1733,48 @@ static hbegp_model* make_model(Problem<T>& prob, size_t di, int si, const double
   return m.release();
 }
 
+// The batched predict path: scratch for mp (a multiple of NB) candidate rows, grown on demand ...
+template <typename T>
+static void predict_batched_reserve(hbegp_model* m, int mp) {
+  if (mp <= m->cap_m) return;
+  HIPCHECK(hipStreamSynchronize(m->stream));  // nothing of an earlier predict is still using the smaller arrays
+  m->pfree(m->Xs); m->pfree(m->Ks); m->pfree(m->Q); m->pfree(m->mean); m->pfree(m->var);
+  m->Xs = m->Ks = m->Q = m->mean = m->var = nullptr;
+  m->cap_m = 0;
+  m->Xs = m->palloc(sizeof(T) * (size_t)mp * m->d);
+  m->Ks = m->palloc(sizeof(T) * (size_t)mp * m->np);
+  m->Q = m->palloc(sizeof(T) * (size_t)mp * m->np);
+  m->mean = m->palloc(sizeof(T) * mp);
+  m->var = m->palloc(sizeof(T) * mp);
+  m->cap_m = mp;
+}
+// ... and its launches on the model stream, the candidates already in m->Xs: Kstar, the mean and, with want_var, the variance
+template <typename T>
+static void predict_batched_launches(hbegp_model* m, int cnt, int mp, bool want_var) {
+  hipStream_t s = m->stream;
+  HIPCHECK(hipMemsetAsync(m->dOut, 0, sizeof(EvalOut), s));
+  launch_kstar<T>(static_cast<T*>(m->Xs), cnt, mp, static_cast<T*>(m->X), m->n, m->d, m->np, m->nu2, m->dP,
+                  static_cast<T*>(m->Ks), s);
+  launch_pred_mean<T>(static_cast<T*>(m->Ks), cnt, m->np, static_cast<T*>(m->alpha), static_cast<T*>(m->mean), s);
+  if (want_var) {
+    // The reference's k*^T K^-1 k* (predict.rs:30-37) as |L^-1 k*|^2: Q = Kstar * X^T (X = L^-1 lower: k <= j, half the
+    // flops), then var = c + 1e-5 - rowsum(Q o Q).  A sum of squares has no cancellation inside the quadratic form, so the
+    // result is at least as close to the exact value as the K^-1 form.
+    GemmLaunch g{};
+    g.nops = 1;
+    g.info = &m->dOut->info;
+    GemmOp& op = g.op[0];
+    op.lda = m->np; op.ldb = m->np; op.ldc = m->np;
+    op.ci0 = 0; op.cj0 = 0; op.mi = mp / NB; op.nj = m->np / NB;
+    op.k0 = 0; op.k1 = m->np / NB;
+    op.A = m->Ks; op.B = m->Xinv; op.C = m->Q;
+    op.klim = 1; op.maskB = 1;
+    launch_gemm<T>(g, pick_tile(op.mi * op.nj), s);
+    launch_pred_var<T>(static_cast<T*>(m->Q), static_cast<T*>(m->Q), cnt, m->np, m->dP, static_cast<T*>(m->var), m->dOut, s);
+  }
+  CHECK_LAUNCHES();
+}
+
 template <typename T>
 static int model_predict(hbegp_model* m, const T* Xs, int cnt, T* mean, T* var, int* n_warn) {
   std::lock_guard<std::mutex> lock(m->mu);
@@ -1767,47 +1812,160 @@ static int model_predict(hbegp_model* m, const T* Xs, int cnt, T* mean, T* var, 
     return HBEGP_OK;
   }
   const int mp = round_up(std::max(cnt, 1), NB);
-  if (mp > m->cap_m) {
-    HIPCHECK(hipStreamSynchronize(m->stream));  // nothing of an earlier predict is still using the smaller arrays
-    m->pfree(m->Xs); m->pfree(m->Ks); m->pfree(m->Q); m->pfree(m->mean); m->pfree(m->var);
-    m->Xs = m->Ks = m->Q = m->mean = m->var = nullptr;
-    m->cap_m = 0;
-    m->Xs = m->palloc(sizeof(T) * (size_t)mp * m->d);
-    m->Ks = m->palloc(sizeof(T) * (size_t)mp * m->np);
-    m->Q = m->palloc(sizeof(T) * (size_t)mp * m->np);
-    m->mean = m->palloc(sizeof(T) * mp);
-    m->var = m->palloc(sizeof(T) * mp);
-    m->cap_m = mp;
-  }
+  predict_batched_reserve<T>(m, mp);
   hipStream_t s = m->stream;
   HIPCHECK(hipMemcpyAsync(m->Xs, Xs, sizeof(T) * (size_t)cnt * m->d, hipMemcpyHostToDevice, s));
-  HIPCHECK(hipMemsetAsync(m->dOut, 0, sizeof(EvalOut), s));
-  launch_kstar<T>(static_cast<T*>(m->Xs), cnt, mp, static_cast<T*>(m->X), m->n, m->d, m->np, m->nu2, m->dP,
-                  static_cast<T*>(m->Ks), s);
-  launch_pred_mean<T>(static_cast<T*>(m->Ks), cnt, m->np, static_cast<T*>(m->alpha), static_cast<T*>(m->mean), s);
-  if (var) {
-    // The reference's k*^T K^-1 k* (predict.rs:30-37) as |L^-1 k*|^2: Q = Kstar * X^T (X = L^-1 lower: k <= j, half the
-    // flops), then var = c + 1e-5 - rowsum(Q o Q).  A sum of squares has no cancellation inside the quadratic form, so the
-    // result is at least as close to the exact value as the K^-1 form.
-    GemmLaunch g{};
-    g.nops = 1;
-    g.info = &m->dOut->info;
-    GemmOp& op = g.op[0];
-    op.lda = m->np; op.ldb = m->np; op.ldc = m->np;
-    op.ci0 = 0; op.cj0 = 0; op.mi = mp / NB; op.nj = m->np / NB;
-    op.k0 = 0; op.k1 = m->np / NB;
-    op.A = m->Ks; op.B = m->Xinv; op.C = m->Q;
-    op.klim = 1; op.maskB = 1;
-    launch_gemm<T>(g, pick_tile(op.mi * op.nj), s);
-    launch_pred_var<T>(static_cast<T*>(m->Q), static_cast<T*>(m->Q), cnt, m->np, m->dP, static_cast<T*>(m->var), m->dOut, s);
-  }
-  CHECK_LAUNCHES();
+  predict_batched_launches<T>(m, cnt, mp, var != nullptr);
   HIPCHECK(hipMemcpyAsync(mean, m->mean, sizeof(T) * cnt, hipMemcpyDeviceToHost, s));
   if (var) HIPCHECK(hipMemcpyAsync(var, m->var, sizeof(T) * cnt, hipMemcpyDeviceToHost, s));
   EvalOut out;
   HIPCHECK(hipMemcpyAsync(&out, m->dOut, sizeof(EvalOut), hipMemcpyDeviceToHost, s));
   HIPCHECK(hipStreamSynchronize(s));
   if (n_warn) *n_warn = var ? out.n_warn : 0;
+  return HBEGP_OK;
+}
+
+// Posterior mean / variance as the batched predict computes them (for every m, also m <= 8) plus their gradients w.r.t. the
+// candidates (kernels.hip, pred_grad_kernel ..).  dvar = -2 (L^-1 dk*/dx_k) . (L^-1 k*): the d gradient matrices G_k stacked
+// into one [d*mp x np] operand of the same triangular tile GEMM that makes Q = Kstar X^T for the variance, then one fp64 row
+// dot per (k, row) against Q.  (The explicit V = Kstar K^-1 -- one GEMM against the symmetric K^-1, or V = Q X through the
+// triangular options -- costs 2 or 1 m n^2 instead of d m n^2 flops, but V grows with cond(K) and its sum cancels: on the
+// fitted config-M model both V forms were off by the whole scale of the gradient.  DESIGN section 10.)
+template <typename T>
+static int model_predict_grad(hbegp_model* m, const T* Xs, int cnt, T* mean, T* var, T* dmean, T* dvar, int* n_warn) {
+  std::lock_guard<std::mutex> lock(m->mu);
+  HIPCHECK(hipSetDevice(m->dev));
+  const int mp = round_up(cnt, NB);
+  const int nch = pred_grad_chunks(m->n);
+  predict_batched_reserve<T>(m, mp);
+  if (mp > m->cap_g) {
+    HIPCHECK(hipStreamSynchronize(m->stream));
+    m->pfree(m->G); m->pfree(m->W); m->pfree(m->gpart); m->pfree(m->dmean); m->pfree(m->dvar);
+    m->G = m->W = m->gpart = m->dmean = m->dvar = nullptr;
+    m->cap_g = 0;
+    m->G = m->palloc(sizeof(T) * (size_t)m->d * mp * m->np);
+    m->W = m->palloc(sizeof(T) * (size_t)m->d * mp * m->np);
+    m->gpart = m->palloc(sizeof(double) * (size_t)nch * mp * m->d);
+    m->dmean = m->palloc(sizeof(T) * (size_t)mp * m->d);
+    m->dvar = m->palloc(sizeof(T) * (size_t)mp * m->d);
+    m->cap_g = mp;
+  }
+  hipStream_t s = m->stream;
+  const bool want_var = var != nullptr;
+  HIPCHECK(hipMemcpyAsync(m->Xs, Xs, sizeof(T) * (size_t)cnt * m->d, hipMemcpyHostToDevice, s));
+  predict_batched_launches<T>(m, cnt, mp, want_var);
+  launch_pred_grad<T>(static_cast<T*>(m->Xs), cnt, static_cast<T*>(m->X), m->n, m->d, m->nu2, m->dP, static_cast<T*>(m->alpha),
+                      static_cast<double*>(m->gpart), static_cast<T*>(m->dmean), s);
+  if (want_var) {
+    launch_kstar_grad<T>(static_cast<T*>(m->Xs), cnt, mp, static_cast<T*>(m->X), m->n, m->d, m->np, m->nu2, m->dP,
+                         static_cast<T*>(m->G), s);
+    GemmLaunch g{};
+    g.nops = 1;
+    g.info = &m->dOut->info;
+    GemmOp& op = g.op[0];
+    op.lda = m->np; op.ldb = m->np; op.ldc = m->np;
+    op.ci0 = 0; op.cj0 = 0; op.mi = m->d * mp / NB; op.nj = m->np / NB;
+    op.k0 = 0; op.k1 = m->np / NB;
+    op.A = m->G; op.B = m->Xinv; op.C = m->W;
+    op.klim = 1; op.maskB = 1;  // X = L^-1 lower, as for Q
+    launch_gemm<T>(g, pick_tile(op.mi * op.nj), s);
+    launch_pred_dvar<T>(static_cast<T*>(m->W), static_cast<T*>(m->Q), cnt, mp, m->np, m->d, static_cast<T*>(m->var),
+                        static_cast<T*>(m->dvar), s);
+  }
+  CHECK_LAUNCHES();
+  HIPCHECK(hipMemcpyAsync(mean, m->mean, sizeof(T) * cnt, hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipMemcpyAsync(dmean, m->dmean, sizeof(T) * (size_t)cnt * m->d, hipMemcpyDeviceToHost, s));
+  if (want_var) {
+    HIPCHECK(hipMemcpyAsync(var, m->var, sizeof(T) * cnt, hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipMemcpyAsync(dvar, m->dvar, sizeof(T) * (size_t)cnt * m->d, hipMemcpyDeviceToHost, s));
+  }
+  EvalOut out;
+  HIPCHECK(hipMemcpyAsync(&out, m->dOut, sizeof(EvalOut), hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
+  if (n_warn) *n_warn = want_var ? out.n_warn : 0;
+  return HBEGP_OK;
+}
+
+// Expected improvement of acquisition.rs:141-171 (estimator.expected_improvement) at mean mu and variance var, and its gradient
+// from the posterior gradients: dEI = -Phi(z) dmu + phi(z) dsigma, dsigma = dvar / (2 sigma); sigma = 0: -dmu where mu < fmin.
+static double ei_with_gradient(double mu, double var, const double* dmu, const double* dvar, double fmin, int d, double* g) {
+  const double sd = std::sqrt(var);
+  if (sd <= 0.0 || std::fabs(sd) <= std::numeric_limits<double>::epsilon()) {  // ulps_eq!(std, 0.0)
+    for (int k = 0; k < d; ++k) g[k] = mu < fmin ? -dmu[k] : 0.0;
+    return mu < fmin ? -(mu - fmin) : 0.0;
+  }
+  const double z = -(mu - fmin) / sd;
+  const double cdf = 0.5 * std::erfc(-z / std::sqrt(2.0));
+  const double pdf = std::exp(-0.5 * z * z) / std::sqrt(2.0 * M_PI);
+  const double ei = -(mu - fmin) * cdf + sd * pdf;
+  for (int k = 0; k < d; ++k) g[k] = -cdf * dmu[k] + pdf * (dvar[k] / (2.0 * sd));
+  return std::max(ei, 0.0);
+}
+
+// the element of type T nearest to v that lies in [lo, hi] (an f32 run evaluates, and returns, points of the box)
+template <typename T>
+static T to_box(double v, double lo, double hi) {
+  T t = (T)v;
+  if ((double)t > hi) t = std::nextafter(t, -std::numeric_limits<T>::infinity());
+  if ((double)t < lo) t = std::nextafter(t, std::numeric_limits<T>::infinity());
+  return t;
+}
+
+// S bounded L-BFGS runs on -EI (lbfgs_step.hpp, the fit optimiser's constants) in lockstep: every round gathers the point each
+// unfinished run asks for and evaluates them all with ONE model_predict_grad.  Each run returns the best point it evaluated.
+template <typename T>
+static int model_maximize_ei(hbegp_model* m, const T* starts, int S, const double* lo, const double* hi, double fmin, int maxeval,
+                             T* x_out, double* ei_out, int* nevals_out) {
+  const int d = m->d;
+  const LbfgsOptions o;
+  std::vector<LbfgsState> st(S);
+  std::vector<char> running(S, 1);
+  std::vector<double> best(S, -std::numeric_limits<double>::infinity());
+  std::vector<double> x0(d), g(d), gd(d), dmu_d(d), dvar_d(d);
+  for (int r = 0; r < S; ++r) {
+    for (int k = 0; k < d; ++k) x0[k] = (double)starts[(size_t)r * d + k];
+    lbfgs_begin(st[r], x0.data(), lo, hi, d, maxeval, o.memory, o.pgtol, o.ftol, false);
+    for (int k = 0; k < d; ++k) x_out[(size_t)r * d + k] = starts[(size_t)r * d + k];
+  }
+  std::vector<int> act;
+  std::vector<T> xs((size_t)S * d), mu(S), var(S), dmu((size_t)S * d), dvar((size_t)S * d);
+  for (;;) {
+    act.clear();
+    for (int r = 0; r < S; ++r)
+      if (running[r]) act.push_back(r);
+    if (act.empty()) break;
+    const int cnt = (int)act.size();
+    for (int i = 0; i < cnt; ++i) {
+      const double* q = lbfgs_request(st[act[i]]);
+      for (int k = 0; k < d; ++k) xs[(size_t)i * d + k] = to_box<T>(q[k], lo[k], hi[k]);
+    }
+    const int rc = model_predict_grad<T>(m, xs.data(), cnt, mu.data(), var.data(), dmu.data(), dvar.data(), nullptr);
+    if (rc != HBEGP_OK) return rc;
+    for (int i = 0; i < cnt; ++i) {
+      const int r = act[i];
+      for (int k = 0; k < d; ++k) {
+        dmu_d[k] = (double)dmu[(size_t)i * d + k];
+        dvar_d[k] = (double)dvar[(size_t)i * d + k];
+      }
+      const double mu_i = (double)mu[i], var_i = (double)var[i];
+      double f = std::numeric_limits<double>::infinity();  // a NaN prediction is a failed evaluation
+      double ei = -std::numeric_limits<double>::infinity();
+      if (std::isfinite(mu_i) && std::isfinite(var_i)) {
+        ei = ei_with_gradient(mu_i, var_i, dmu_d.data(), dvar_d.data(), fmin, d, gd.data());
+        f = -ei;
+        for (int k = 0; k < d; ++k) g[k] = -gd[k];
+      }
+      if (ei > best[r]) {
+        best[r] = ei;
+        for (int k = 0; k < d; ++k) x_out[(size_t)r * d + k] = xs[(size_t)i * d + k];
+      }
+      running[r] = lbfgs_advance(st[r], f, g.data()) ? 1 : 0;
+    }
+  }
+  for (int r = 0; r < S; ++r) {
+    ei_out[r] = best[r];
+    if (nevals_out) nevals_out[r] = st[r].nevals;
+  }
   return HBEGP_OK;
 }
 
@@ -2551,6 +2709,67 @@ int hbegp_predict_f32(hbegp_model* model, const float* Xs, int m, float* mean, f
   if (m == 0) { if (n_warn) *n_warn = 0; return HBEGP_OK; }
   GUARD_BEGIN
   return model_predict<float>(model, Xs, m, mean, var, n_warn);
+  GUARD_END
+}
+
+}  // extern "C"
+// argument checks of the gradient entry points: everything is refused before any device call
+template <typename T>
+static int check_predict_grad(hbegp_model* model, const T* Xs, int m, T* mean, T* var, T* dmean, T* dvar) {
+  if (m < 0) return fail(HBEGP_EINVAL, "m must be >= 0 (got %d)", m);
+  if (!model) return fail(HBEGP_EINVAL, "NULL model");
+  if (!Xs || !mean || !dmean) return fail(HBEGP_EINVAL, "Xs/mean/dmean is NULL");
+  if ((var == nullptr) != (dvar == nullptr)) return fail(HBEGP_EINVAL, "var and dvar must be given together or both be NULL");
+  if (model->is_f32 != (sizeof(T) == 4)) return fail(HBEGP_EINVAL, "model holds %s data", model->is_f32 ? "f32" : "f64");
+  return HBEGP_OK;
+}
+template <typename T>
+static int check_maximize_ei(hbegp_model* model, const T* starts, int S, const double* lo, const double* hi, double fmin, int maxeval,
+                             T* x_out, double* ei_out) {
+  if (S < 1) return fail(HBEGP_EINVAL, "S must be >= 1 (got %d)", S);
+  if (!model) return fail(HBEGP_EINVAL, "NULL model");
+  if (!starts || !lo || !hi || !x_out || !ei_out) return fail(HBEGP_EINVAL, "starts/lo/hi/x_out/ei_out is NULL");
+  if (model->is_f32 != (sizeof(T) == 4)) return fail(HBEGP_EINVAL, "model holds %s data", model->is_f32 ? "f32" : "f64");
+  if (maxeval < 1) return fail(HBEGP_EINVAL, "maxeval must be >= 1 (got %d)", maxeval);
+  if (!std::isfinite(fmin)) return fail(HBEGP_EINVAL, "fmin_normalized is not finite");
+  const int d = model->d;
+  for (int k = 0; k < d; ++k)
+    if (!(lo[k] <= hi[k])) return fail(HBEGP_EINVAL, "lo[%d] > hi[%d] (%g > %g)", k, k, lo[k], hi[k]);
+  for (int r = 0; r < S; ++r)
+    for (int k = 0; k < d; ++k) {
+      const double v = (double)starts[(size_t)r * d + k];
+      if (!(v >= lo[k] && v <= hi[k])) return fail(HBEGP_EINVAL, "start %d lies outside the box (feature %d: %g)", r, k, v);
+    }
+  return HBEGP_OK;
+}
+extern "C" {
+int hbegp_predict_grad_f64(hbegp_model* model, const double* Xs, int m, double* mean, double* var, double* dmean, double* dvar,
+                           int* n_warn) {
+  if (int rc = check_predict_grad<double>(model, Xs, m, mean, var, dmean, dvar)) return rc;
+  if (m == 0) { if (n_warn) *n_warn = 0; return HBEGP_OK; }
+  GUARD_BEGIN
+  return model_predict_grad<double>(model, Xs, m, mean, var, dmean, dvar, n_warn);
+  GUARD_END
+}
+int hbegp_predict_grad_f32(hbegp_model* model, const float* Xs, int m, float* mean, float* var, float* dmean, float* dvar, int* n_warn) {
+  if (int rc = check_predict_grad<float>(model, Xs, m, mean, var, dmean, dvar)) return rc;
+  if (m == 0) { if (n_warn) *n_warn = 0; return HBEGP_OK; }
+  GUARD_BEGIN
+  return model_predict_grad<float>(model, Xs, m, mean, var, dmean, dvar, n_warn);
+  GUARD_END
+}
+int hbegp_maximize_ei_f64(hbegp_model* model, const double* starts, int S, const double* lo, const double* hi, double fmin_normalized,
+                          int maxeval, double* x_out, double* ei_out, int* nevals_out) {
+  if (int rc = check_maximize_ei<double>(model, starts, S, lo, hi, fmin_normalized, maxeval, x_out, ei_out)) return rc;
+  GUARD_BEGIN
+  return model_maximize_ei<double>(model, starts, S, lo, hi, fmin_normalized, maxeval, x_out, ei_out, nevals_out);
+  GUARD_END
+}
+int hbegp_maximize_ei_f32(hbegp_model* model, const float* starts, int S, const double* lo, const double* hi, double fmin_normalized,
+                          int maxeval, float* x_out, double* ei_out, int* nevals_out) {
+  if (int rc = check_maximize_ei<float>(model, starts, S, lo, hi, fmin_normalized, maxeval, x_out, ei_out)) return rc;
+  GUARD_BEGIN
+  return model_maximize_ei<float>(model, starts, S, lo, hi, fmin_normalized, maxeval, x_out, ei_out, nevals_out);
   GUARD_END
 }
 

@@ -1835,6 +1835,166 @@ template void launch_pred_var<double>(const double*, const double*, int, int, co
 template void launch_pred_var<float>(const float*, const float*, int, int, const EvalParams*, float*, EvalOut*, hipStream_t);
 
 // =================================================================================================================
+// posterior gradient at the candidates: the derivative of predict (predict.rs:7-52) w.r.t. the query point x*
+//   dk_j/dx*_k = c psi(r_j) (x*_k - x_jk) / ell_k^2 = c psi(r_j) (s*_k - s_jk) / ell_k,   s = x / ell,  psi = phi'(r) / r
+//   dmean_k = sum_j dk_j/dx*_k alpha_j
+//   dvar_k  = -2 (dk/dx*_k)^T K^-1 k* = -2 (L^-1 dk/dx*_k) . (L^-1 k*) = -2 rowsum(W_k o Q),   W_k = G_k X^T (tile GEMM)
+// The variance gradient goes through L^-1 like the variance itself (|L^-1 k*|^2): both factors are bounded (|L^-1 k*|^2 <= c),
+// whereas V = K^-1 k* itself grows with cond(K) and the sum over V cancels -- measured on the fitted config-M model
+// (cond(K) = 6.7e11) the V forms were off by 100 % of the gradient's scale.
+// A training point at r = 0 contributes 0 for every order (the limit for nu >= 3/2; a choice for nu = 1/2, where k has a kink).
+//
+// pred_grad_kernel (dmean): grid (ceil(m/4), ceil(n/PG_CHUNK)); wave w of a workgroup is candidate row 4 blockIdx.x + w, lane
+// l takes the training points j0 + l of the chunk, 64 at a time through the LDS (features scaled as in kstar_kernel, r^2
+// accumulated in the same order and type).  psi and the sums are fp64 for both element types; per-lane sums over PG_KB
+// features per pass over the chunk, then one wave_sum each: part[chunk][row][k].  pred_grad_finish_kernel adds the chunks in
+// ascending order.
+// kstar_grad_kernel writes G[k][i][j] = dk_j/dx*_i,k (zero padding, like Kstar); pred_dvar_kernel: one wave per (k, row).
+// No atomics anywhere: the same rows give the same bits.
+// =================================================================================================================
+constexpr int PG_CHUNK = 512;  // training points per workgroup
+constexpr int PG_KB = 16;      // features per pass (16 fp64 accumulators per lane)
+
+// psi(r) = phi'(r) / r of matern_map, from r^2 (> 0)
+__device__ __forceinline__ double matern_psi(double r2, int nu2) {
+#pragma clang fp contract(off)
+  if (nu2 == 0) return -exp_nonpos(-0.5 * r2);
+  const double r = sqrt_nonneg(r2);
+  if (nu2 == 1) return -exp_nonpos(-r) / r;
+  if (nu2 == 3) return -3.0 * exp_nonpos(-1.7320508075688772 * r);
+  const double k = 2.23606797749979 * r;
+  return -(5.0 / 3.0) * (1.0 + k) * exp_nonpos(-k);
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256) pred_grad_kernel(const T* __restrict__ Xs, int m, const T* __restrict__ X, int n, int d, int nu2,
+                                                        const EvalParams* __restrict__ P, const T* __restrict__ alpha,
+                                                        double* __restrict__ part) {
+  extern __shared__ __align__(16) char smem_raw[];
+  T* sx = reinterpret_cast<T*>(smem_raw);  // [d][64] scaled features of 64 training points
+  T* sq = sx + (size_t)d * 64;             // [4][d] scaled features of this workgroup's candidates
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const int row = blockIdx.x * 4 + w;
+  const bool live = row < m;
+  const int jc0 = blockIdx.y * PG_CHUNK, jc1 = min(n, jc0 + PG_CHUNK);
+  const double amp = P->amp;
+  for (int e = t; e < 4 * d; e += 256) {
+    const int q = e / d, k = e - q * d, gi = blockIdx.x * 4 + q;
+    sq[e] = (gi < m) ? Xs[(size_t)gi * d + k] / (T)P->ell[k] : T(0);
+  }
+  const T* xq = sq + w * d;
+  for (int kb = 0; kb < d; kb += PG_KB) {
+    double am[PG_KB];
+#pragma unroll
+    for (int kk = 0; kk < PG_KB; ++kk) am[kk] = 0.0;
+    for (int j0 = jc0; j0 < jc1; j0 += 64) {
+      __syncthreads();  // the previous 64 points are consumed (first time: sq is written)
+      for (int e = t; e < 64 * d; e += 256) {
+        const int jj = e / d, k = e - jj * d, gj = j0 + jj;
+        sx[k * 64 + jj] = (gj < n) ? X[(size_t)gj * d + k] / (T)P->ell[k] : T(0);
+      }
+      __syncthreads();
+      const int j = j0 + lane;
+      if (live && j < jc1) {
+        T r2 = T(0);
+        for (int k = 0; k < d; ++k) {  // kstar_kernel's accumulation (cdist order, matern_kernel.rs:274-278)
+          const T df = xq[k] - sx[k * 64 + lane];
+          r2 += df * df;
+        }
+        const double a = (r2 == T(0)) ? 0.0 : amp * matern_psi((double)r2, nu2) * (double)alpha[j];
+#pragma unroll
+        for (int kk = 0; kk < PG_KB; ++kk)
+          if (kb + kk < d) am[kk] += a * (double)(xq[kb + kk] - sx[(kb + kk) * 64 + lane]);
+      }
+    }
+#pragma unroll
+    for (int kk = 0; kk < PG_KB; ++kk) {
+      if (kb + kk < d) {
+        const double sm = wave_sum(am[kk]);
+        if (live && lane == 0) part[((size_t)blockIdx.y * m + row) * d + kb + kk] = sm;
+      }
+    }
+  }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256) pred_grad_finish_kernel(const double* __restrict__ part, int nch, int m, int d,
+                                                               const EvalParams* __restrict__ P, T* __restrict__ dmean) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= m * d) return;
+  const int k = e % d;
+  double sm = 0.0;
+  for (int c = 0; c < nch; ++c) sm += part[(size_t)c * m * d + e];
+  dmean[e] = (T)(sm / P->ell[k]);
+}
+
+// G[k][i][j] (k < d, i < mp, j < np) = dk(x*_i, x_j) / dx*_i,k; 0 for i >= m or j >= n.  One thread per (i, j), all d features.
+template <typename T>
+__global__ void __launch_bounds__(256) kstar_grad_kernel(const T* __restrict__ Xs, int m, int mp, const T* __restrict__ X, int n, int d,
+                                                         int np, int nu2, const EvalParams* __restrict__ P, T* __restrict__ G) {
+  const int j = blockIdx.x * 256 + threadIdx.x, i = blockIdx.y;
+  if (j >= np) return;
+  const size_t plane = (size_t)mp * np, at = (size_t)i * np + j;
+  if (i >= m || j >= n) {
+    for (int k = 0; k < d; ++k) G[k * plane + at] = T(0);
+    return;
+  }
+  T r2 = T(0);
+  for (int k = 0; k < d; ++k) {
+    const T ell = (T)P->ell[k];
+    const T df = Xs[(size_t)i * d + k] / ell - X[(size_t)j * d + k] / ell;
+    r2 += df * df;
+  }
+  const double g = (r2 == T(0)) ? 0.0 : P->amp * matern_psi((double)r2, nu2);
+  for (int k = 0; k < d; ++k) {
+    const T ell = (T)P->ell[k];
+    const T df = Xs[(size_t)i * d + k] / ell - X[(size_t)j * d + k] / ell;
+    G[k * plane + at] = (T)(g * (double)df / P->ell[k]);
+  }
+}
+
+// dvar[i][k] = -2 sum_j W[k][i][j] Q[i][j]; 0 where the variance was clamped to 0 (a NaN variance keeps its NaN).  One wave per (k, i).
+template <typename T>
+__global__ void __launch_bounds__(256) pred_dvar_kernel(const T* __restrict__ W, const T* __restrict__ Q, int m, int mp, int np, int d,
+                                                        const T* __restrict__ var, T* __restrict__ dvar) {
+  const int lane = threadIdx.x & 63, item = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (item >= m * d) return;
+  const int k = item / m, i = item - k * m;
+  const T* wr = W + ((size_t)k * mp + i) * np;
+  const T* qr = Q + (size_t)i * np;
+  double acc = 0.0;
+  for (int j = lane; j < np; j += 64) acc += (double)wr[j] * (double)qr[j];
+  acc = wave_sum(acc);
+  if (lane == 0) dvar[(size_t)i * d + k] = (var[i] == T(0)) ? T(0) : (T)(-2.0 * acc);
+}
+
+template <typename T>
+void launch_pred_grad(const T* Xs, int m, const T* X, int n, int d, int nu2, const EvalParams* P, const T* alpha, double* part, T* dmean,
+                      hipStream_t s) {
+  const int nch = (n + PG_CHUNK - 1) / PG_CHUNK;
+  const size_t lds = (size_t)(64 + 4) * d * sizeof(T);
+  hipLaunchKernelGGL((pred_grad_kernel<T>), dim3((m + 3) / 4, nch), dim3(256), lds, s, Xs, m, X, n, d, nu2, P, alpha, part);
+  hipLaunchKernelGGL((pred_grad_finish_kernel<T>), dim3((m * d + 255) / 256), dim3(256), 0, s, part, nch, m, d, P, dmean);
+}
+template <typename T>
+void launch_kstar_grad(const T* Xs, int m, int mp, const T* X, int n, int d, int np, int nu2, const EvalParams* P, T* G, hipStream_t s) {
+  hipLaunchKernelGGL((kstar_grad_kernel<T>), dim3((np + 255) / 256, mp), dim3(256), 0, s, Xs, m, mp, X, n, d, np, nu2, P, G);
+}
+template <typename T>
+void launch_pred_dvar(const T* W, const T* Q, int m, int mp, int np, int d, const T* var, T* dvar, hipStream_t s) {
+  hipLaunchKernelGGL((pred_dvar_kernel<T>), dim3((m * d + 3) / 4), dim3(256), 0, s, W, Q, m, mp, np, d, var, dvar);
+}
+template void launch_pred_grad<double>(const double*, int, const double*, int, int, int, const EvalParams*, const double*, double*, double*,
+                                       hipStream_t);
+template void launch_pred_grad<float>(const float*, int, const float*, int, int, int, const EvalParams*, const float*, double*, float*,
+                                      hipStream_t);
+template void launch_kstar_grad<double>(const double*, int, int, const double*, int, int, int, int, const EvalParams*, double*, hipStream_t);
+template void launch_kstar_grad<float>(const float*, int, int, const float*, int, int, int, int, const EvalParams*, float*, hipStream_t);
+template void launch_pred_dvar<double>(const double*, const double*, int, int, int, int, const double*, double*, hipStream_t);
+template void launch_pred_dvar<float>(const float*, const float*, int, int, int, int, const float*, float*, hipStream_t);
+int pred_grad_chunks(int n) { return (n + PG_CHUNK - 1) / PG_CHUNK; }
+
+// =================================================================================================================
 // predict for a handful of candidates (m <= PRED_SMALL_MAX): the caller's acquisition and selection loops issue
 // thousands of single-point predicts per generation (acquisition.rs:46-64, minimize.rs:656-714).  The batched path pads
 // to 128 candidate rows and runs a tile GEMM over all of L^-1 (0.2 ms at n=4096 whatever m is); here L^-1 is read once,

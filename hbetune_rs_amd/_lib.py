@@ -80,6 +80,10 @@ SIGNATURES = {
     "hbegp_extend_from_f32": (C.c_int, [_vp, _vp, _fp, _fp, C.c_int, C.POINTER(_vp), _ip]),
     "hbegp_predict_f64": (C.c_int, [_vp, _dp, C.c_int, _dp, _dp, _ip]),
     "hbegp_predict_f32": (C.c_int, [_vp, _fp, C.c_int, _fp, _fp, _ip]),
+    "hbegp_predict_grad_f64": (C.c_int, [_vp, _dp, C.c_int, _dp, _dp, _dp, _dp, _ip]),
+    "hbegp_predict_grad_f32": (C.c_int, [_vp, _fp, C.c_int, _fp, _fp, _fp, _fp, _ip]),
+    "hbegp_maximize_ei_f64": (C.c_int, [_vp, _dp, C.c_int, _dp, _dp, C.c_double, C.c_int, _dp, _dp, _ip]),
+    "hbegp_maximize_ei_f32": (C.c_int, [_vp, _fp, C.c_int, _dp, _dp, C.c_double, C.c_int, _fp, _dp, _ip]),
     "hbegp_model_info": (C.c_int, [_vp, _ip, _ip, _ip, _dp, _dp]),
     "hbegp_model_get_f64": (C.c_int, [_vp, _dp, _dp, _dp]),
     "hbegp_model_get_f32": (C.c_int, [_vp, _dp, _fp, _fp]),

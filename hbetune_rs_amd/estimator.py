@@ -100,6 +100,19 @@ def _norm_inverse_cdf(p, mu, sigma):
     return mu + sigma * float(ndtri(p))
 
 
+def expected_improvement_with_gradient(mean, var, dmean, dvar, fmin):
+    """EI of `expected_improvement` at (mean, sqrt(var)) and its gradient from those of the mean and the variance:
+    dEI = -Phi(z) dmean + phi(z) dstd with dstd = dvar / (2 std); where std is 0 (the ulps_eq branch) -dmean if mean < fmin,
+    else 0.  The same arithmetic as hbegp_maximize_ei_* (hbegp.cpp, ei_with_gradient)."""
+    std = math.sqrt(var)
+    dmean = np.asarray(dmean, dtype=np.float64)
+    if std <= 0.0 or abs(std) <= np.finfo(float).eps:
+        return expected_improvement(mean, std, fmin), (-dmean if mean < fmin else np.zeros_like(dmean))
+    z = -(mean - fmin) / std
+    cdf, pdf = _norm_cdf(z), _norm_pdf(z)
+    return expected_improvement(mean, std, fmin), -cdf * dmean + pdf * (np.asarray(dvar, dtype=np.float64) / (2.0 * std))
+
+
 def expected_improvement(mean, std, fmin):
     """acquisition.rs:141-171"""
     assert math.isfinite(mean) and math.isfinite(std) and math.isfinite(fmin)
@@ -224,6 +237,41 @@ class SurrogateModelGPR:
         fmin_n = float(self.y_norm.project_into_normalized(np.array([fmin], dtype=self.dtype))[0])
         ei = np.array([expected_improvement(float(mi), float(math.sqrt(vi)), fmin_n) for mi, vi in zip(m, v)], dtype=self.dtype)
         return self.y_norm.project_location_from_normalized(m), ei
+
+    # Gradients w.r.t. the features (opt-in; nothing the estimator suggests by default uses them).
+    def predict_mean_grad_a(self, x):
+        """projected mean and its gradient [m, d] (chain rule through project_location_from_normalized)."""
+        m, _, dm, _, _ = self.fitted.predict_with_gradient(np.asarray(x, dtype=self.dtype), want_variance=False)
+        amp = self.y_norm.amplitude
+        if self.y_norm.projection == "linear":
+            scale = np.full(m.shape, amp, dtype=self.dtype)
+        else:
+            scale = amp * np.exp(m * amp)
+        return self.y_norm.project_location_from_normalized(m), dm * scale[:, None]
+
+    def _fmin_normalized(self, fmin):
+        return float(self.y_norm.project_into_normalized(np.array([fmin], dtype=self.dtype))[0])
+
+    def predict_mean_ei_grad_a(self, x, fmin):
+        """predict_mean_ei_a plus dEI/dx [m, d] (EI in normalised space, as predict_mean_ei_a computes it)."""
+        m, v, dm, dv, n_warn = self.fitted.predict_with_gradient(np.asarray(x, dtype=self.dtype), want_variance=True)
+        if n_warn:
+            import sys
+
+            print("Variances below 0 were predicted and will be corrected", file=sys.stderr)  # predict.rs:39-48
+        fmin_n = self._fmin_normalized(fmin)
+        pairs = [expected_improvement_with_gradient(float(mi), float(vi), dmi, dvi, fmin_n) for mi, vi, dmi, dvi in zip(m, v, dm, dv)]
+        ei = np.array([p[0] for p in pairs], dtype=self.dtype)
+        dei = np.array([p[1] for p in pairs], dtype=self.dtype).reshape(len(m), -1)
+        return self.y_norm.project_location_from_normalized(m), ei, dei
+
+    def maximize_ei(self, starts, bounds, fmin, maxeval=150):
+        """Bounded L-BFGS ascent of EI from every row of `starts` (the box: `bounds` = [(lo, hi)] per feature), all runs in
+        lockstep on the device model.  fmin is projected into normalised space as predict_mean_ei_a does it.
+        Returns (x[S, d], ei[S], nevals[S])."""
+        lo = np.array([b[0] for b in bounds], dtype=np.float64)
+        hi = np.array([b[1] for b in bounds], dtype=np.float64)
+        return self.fitted.maximize_ei(np.asarray(starts, dtype=self.dtype), lo, hi, self._fmin_normalized(fmin), maxeval=maxeval)
 
     # Batched forms of the scalar trait methods (SURVEY.md 8f rank 1: the acquisition loops call these once per generation
     # instead of m single-point predicts, each of which reads all of K^-1).

@@ -287,6 +287,40 @@ class FittedKernel:
         _lib.check(pred(self._h, _lib.aptr(x), m, _lib.aptr(mean), _lib.aptr(var), C.byref(n_warn)))
         return mean, var, n_warn.value
 
+    def predict_with_gradient(self, x, want_variance=True):
+        """predict() plus the gradients w.r.t. the query points (hbegp_predict_grad_*): returns
+        (mean[m], var[m] or None, dmean[m, d], dvar[m, d] or None, n_warn), gradients in the units of the feature space."""
+        lib = _lib.load()
+        x = _lib.as_c(x, self.dtype)
+        assert x.ndim == 2 and x.shape[1] == self.d
+        m = x.shape[0]
+        mean = np.zeros(m, dtype=self.dtype)
+        dmean = np.zeros((m, self.d), dtype=self.dtype)
+        var = np.zeros(m, dtype=self.dtype) if want_variance else None
+        dvar = np.zeros((m, self.d), dtype=self.dtype) if want_variance else None
+        n_warn = C.c_int(0)
+        fn = getattr(lib, f"hbegp_predict_grad_{self._sfx}")
+        _lib.check(fn(self._h, _lib.aptr(x), m, _lib.aptr(mean), _lib.aptr(var), _lib.aptr(dmean), _lib.aptr(dvar), C.byref(n_warn)))
+        return mean, var, dmean, dvar, n_warn.value
+
+    def maximize_ei(self, starts, lo, hi, fmin_normalized, maxeval=150):
+        """S bounded L-BFGS runs maximising EI in the normalised y space (hbegp_maximize_ei_*), one batched gradient predict
+        per round.  starts: [S, d] inside [lo, hi].  Returns (x[S, d], ei[S], nevals[S]): each run's best point."""
+        lib = _lib.load()
+        starts = _lib.as_c(np.atleast_2d(starts), self.dtype)
+        assert starts.shape[1] == self.d
+        S = starts.shape[0]
+        lo = _lib.as_c(lo, np.float64)
+        hi = _lib.as_c(hi, np.float64)
+        assert lo.shape == (self.d,) and hi.shape == (self.d,)
+        x = np.zeros((S, self.d), dtype=self.dtype)
+        ei = np.zeros(S)
+        nevals = np.zeros(S, dtype=np.int32)
+        fn = getattr(lib, f"hbegp_maximize_ei_{self._sfx}")
+        _lib.check(fn(self._h, _lib.aptr(starts), S, _lib.dptr(lo), _lib.dptr(hi), float(fmin_normalized), int(maxeval), _lib.aptr(x),
+                      _lib.dptr(ei), nevals.ctypes.data_as(C.POINTER(C.c_int))))
+        return x, ei, nevals
+
     def release(self):
         if self._h:
             _lib.load().hbegp_model_release(self._h)

@@ -195,6 +195,37 @@ int hbegp_extend_from_f32(hbegp_ctx* ctx, hbegp_model* prior, const float* X, co
 int hbegp_predict_f64(hbegp_model* model, const double* Xs, int m, double* mean, double* var, int* n_warn);
 int hbegp_predict_f32(hbegp_model* model, const float* Xs, int m, float* mean, float* var, int* n_warn);
 
+/* Posterior gradient at m query points.  mean[m], var[m], n_warn as hbegp_predict_* computes them on its batched path (m > 8;
+ * the gradient call takes that path for every m); dmean[m*d], dvar[m*d] row-major: d mean / d x*_k and d var / d x*_k, in the
+ * units of the feature space the model was fitted on (the coordinates of Xs, not the length-scaled ones).  var and dvar may be
+ * NULL together (mean and its gradient only); one of them alone is HBEGP_EINVAL.  m = 0 is a no-op.
+ *   k(x*, x_j) = c phi_nu(r),  r^2 = sum_k ((x*_k - x_jk) / ell_k)^2  (no noise term),  psi = phi'(r) / r:
+ *     nu = 1/2: -exp(-r)/r,  nu = 3/2: -3 exp(-sqrt3 r),  nu = 5/2: -(5/3)(1 + sqrt5 r) exp(-sqrt5 r),  nu = inf: -exp(-r^2/2)
+ *   dk_j/dx*_k = c psi(r) (x*_k - x_jk) / ell_k^2
+ *   dmean_k = sum_j dk_j/dx*_k alpha_j,   dvar_k = -2 (d k* / d x*_k)^T K^-1 k*, evaluated as -2 (L^-1 d k* / d x*_k) . (L^-1 k*)
+ *   like the variance itself (an explicit K^-1 k* loses digits in proportion to cond(K))
+ * A training point at r = 0 (the query point equals it) contributes 0 for every nu: the exact limit for nu >= 3/2; for
+ * nu = 1/2 the kernel has a kink there and has no derivative, and 0 is the chosen value (the mean of the one-sided slopes).
+ * Where the variance was clamped to 0 (predict.rs:39-48) dvar is 0.  A NaN in a query row gives NaN in that row's outputs
+ * only.  Sums are fp64 for both element types, in a fixed order: the same call gives the same bits. */
+int hbegp_predict_grad_f64(hbegp_model* model, const double* Xs, int m, double* mean, double* var, double* dmean, double* dvar,
+                           int* n_warn);
+int hbegp_predict_grad_f32(hbegp_model* model, const float* Xs, int m, float* mean, float* var, float* dmean, float* dvar,
+                           int* n_warn);
+
+/* Maximise the expected improvement EI(x) (acquisition.rs:141-171) in the model's normalised y space over the box
+ * [lo, hi] (d entries each, feature space) with S bounded L-BFGS runs on -EI (the fit optimiser's method and constants,
+ * lbfgs_step.hpp), run s from starts[s*d ..] (inside the box).  The runs advance in lockstep: every round is ONE batched
+ * hbegp_predict_grad over the runs still going.  EI and its gradient are computed on the host in double:
+ *   dEI/dx = -Phi(z) dmean + phi(z) dsigma,  dsigma = dvar / (2 sigma);  sigma = 0: -dmean where mean < fmin, else 0.
+ * x_out[S*d] receives each run's best evaluated point, ei_out[S] its EI (never below the EI at the start),
+ * nevals_out[S] (may be NULL) the evaluations each run used (<= maxeval).  HBEGP_EINVAL for S < 1, maxeval < 1, lo > hi,
+ * a start outside the box, a non-finite fmin_normalized or a model of the other element type; nothing runs on the device then. */
+int hbegp_maximize_ei_f64(hbegp_model* model, const double* starts, int S, const double* lo, const double* hi, double fmin_normalized,
+                          int maxeval, double* x_out, double* ei_out, int* nevals_out);
+int hbegp_maximize_ei_f32(hbegp_model* model, const float* starts, int S, const double* lo, const double* hi, double fmin_normalized,
+                          int maxeval, float* x_out, double* ei_out, int* nevals_out);
+
 int hbegp_model_info(const hbegp_model* model, int* n, int* d, int* is_f32, double* nu, double* lml);
 /* theta[p] (log space, clamped), alpha[n], kinv[n*n] full symmetric; any pointer may be NULL. */
 int hbegp_model_get_f64(hbegp_model* model, double* theta, double* alpha, double* kinv);

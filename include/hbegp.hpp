@@ -51,6 +51,11 @@ template <> struct Abi<double> {
                     const double* hi, hbegp_model** m) { return hbegp_extend_f64(c, x, y, n, d, nu, t, lo, hi, m); }
   static int extend_from(hbegp_ctx* c, hbegp_model* p, const double* x, const double* y, int n, hbegp_model** m, int* inc) { return hbegp_extend_from_f64(c, p, x, y, n, m, inc); }
   static int predict(hbegp_model* m, const double* xs, int k, double* mean, double* var, int* w) { return hbegp_predict_f64(m, xs, k, mean, var, w); }
+  static int predict_grad(hbegp_model* m, const double* xs, int k, double* mean, double* var, double* dm, double* dv, int* w) {
+    return hbegp_predict_grad_f64(m, xs, k, mean, var, dm, dv, w);
+  }
+  static int maximize_ei(hbegp_model* m, const double* st, int s, const double* lo, const double* hi, double fmin, int maxeval, double* x,
+                         double* ei, int* ne) { return hbegp_maximize_ei_f64(m, st, s, lo, hi, fmin, maxeval, x, ei, ne); }
   static int get(hbegp_model* m, double* t, double* a, double* ki) { return hbegp_model_get_f64(m, t, a, ki); }
 };
 template <> struct Abi<float> {
@@ -62,6 +67,11 @@ template <> struct Abi<float> {
                     const double* hi, hbegp_model** m) { return hbegp_extend_f32(c, x, y, n, d, nu, t, lo, hi, m); }
   static int extend_from(hbegp_ctx* c, hbegp_model* p, const float* x, const float* y, int n, hbegp_model** m, int* inc) { return hbegp_extend_from_f32(c, p, x, y, n, m, inc); }
   static int predict(hbegp_model* m, const float* xs, int k, float* mean, float* var, int* w) { return hbegp_predict_f32(m, xs, k, mean, var, w); }
+  static int predict_grad(hbegp_model* m, const float* xs, int k, float* mean, float* var, float* dm, float* dv, int* w) {
+    return hbegp_predict_grad_f32(m, xs, k, mean, var, dm, dv, w);
+  }
+  static int maximize_ei(hbegp_model* m, const float* st, int s, const double* lo, const double* hi, double fmin, int maxeval, float* x,
+                         double* ei, int* ne) { return hbegp_maximize_ei_f32(m, st, s, lo, hi, fmin, maxeval, x, ei, ne); }
   static int get(hbegp_model* m, double* t, float* a, float* ki) { return hbegp_model_get_f32(m, t, a, ki); }
 };
 }  // namespace detail
@@ -121,6 +131,17 @@ class FittedKernel {
     int warn = 0;
     check(detail::Abi<A>::predict(h_, xs, m, mean, var, &warn));
     return warn;
+  }
+  // predict plus d mean / dx* and d var / dx* (dmean[m*d], dvar[m*d] row-major; var and dvar nullptr together)
+  int predict_grad(const A* xs, int m, A* mean, A* var, A* dmean, A* dvar) const {
+    int warn = 0;
+    check(detail::Abi<A>::predict_grad(h_, xs, m, mean, var, dmean, dvar, &warn));
+    return warn;
+  }
+  // S bounded L-BFGS ascents of EI (normalised y space) from starts[S*d] inside [lo, hi]; x_out[S*d], ei_out[S], nevals[S] (may be nullptr)
+  void maximize_ei(const A* starts, int S, const double* lo, const double* hi, double fmin_normalized, int maxeval, A* x_out,
+                   double* ei_out, int* nevals = nullptr) const {
+    check(detail::Abi<A>::maximize_ei(h_, starts, S, lo, hi, fmin_normalized, maxeval, x_out, ei_out, nevals));
   }
   double lml() const { return lml_; }
   double noise() const { return std::exp(theta_[0]); }

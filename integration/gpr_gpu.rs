@@ -105,6 +105,22 @@ extern "C" {
     fn hbegp_predict_f32(
         model: *mut HbegpModel, xs: *const c_float, m: c_int, mean: *mut c_float, var: *mut c_float, n_warn: *mut c_int,
     ) -> c_int;
+    fn hbegp_predict_grad_f64(
+        model: *mut HbegpModel, xs: *const c_double, m: c_int, mean: *mut c_double, var: *mut c_double, dmean: *mut c_double,
+        dvar: *mut c_double, n_warn: *mut c_int,
+    ) -> c_int;
+    fn hbegp_predict_grad_f32(
+        model: *mut HbegpModel, xs: *const c_float, m: c_int, mean: *mut c_float, var: *mut c_float, dmean: *mut c_float,
+        dvar: *mut c_float, n_warn: *mut c_int,
+    ) -> c_int;
+    fn hbegp_maximize_ei_f64(
+        model: *mut HbegpModel, starts: *const c_double, s: c_int, lo: *const c_double, hi: *const c_double,
+        fmin_normalized: c_double, maxeval: c_int, x_out: *mut c_double, ei_out: *mut c_double, nevals_out: *mut c_int,
+    ) -> c_int;
+    fn hbegp_maximize_ei_f32(
+        model: *mut HbegpModel, starts: *const c_float, s: c_int, lo: *const c_double, hi: *const c_double,
+        fmin_normalized: c_double, maxeval: c_int, x_out: *mut c_float, ei_out: *mut c_double, nevals_out: *mut c_int,
+    ) -> c_int;
     fn hbegp_model_info(
         model: *const HbegpModel, n: *mut c_int, d: *mut c_int, is_f32: *mut c_int, nu: *mut c_double, lml: *mut c_double,
     ) -> c_int;
@@ -158,6 +174,16 @@ pub trait GpuScalar: Scalar + sealed::Sealed {
     unsafe fn ffi_predict(
         model: *mut HbegpModel, xs: *const Self, m: c_int, mean: *mut Self, var: *mut Self, n_warn: *mut c_int,
     ) -> c_int;
+    /// `hbegp_predict_grad_*`
+    unsafe fn ffi_predict_grad(
+        model: *mut HbegpModel, xs: *const Self, m: c_int, mean: *mut Self, var: *mut Self, dmean: *mut Self, dvar: *mut Self,
+        n_warn: *mut c_int,
+    ) -> c_int;
+    /// `hbegp_maximize_ei_*`
+    unsafe fn ffi_maximize_ei(
+        model: *mut HbegpModel, starts: *const Self, s: c_int, lo: *const f64, hi: *const f64, fmin_normalized: f64,
+        maxeval: c_int, x_out: *mut Self, ei_out: *mut f64, nevals_out: *mut c_int,
+    ) -> c_int;
 }
 
 impl GpuScalar for f64 {
@@ -185,6 +211,18 @@ impl GpuScalar for f64 {
     ) -> c_int {
         hbegp_predict_f64(model, xs, m, mean, var, n_warn)
     }
+    unsafe fn ffi_predict_grad(
+        model: *mut HbegpModel, xs: *const f64, m: c_int, mean: *mut f64, var: *mut f64, dmean: *mut f64, dvar: *mut f64,
+        n_warn: *mut c_int,
+    ) -> c_int {
+        hbegp_predict_grad_f64(model, xs, m, mean, var, dmean, dvar, n_warn)
+    }
+    unsafe fn ffi_maximize_ei(
+        model: *mut HbegpModel, starts: *const f64, s: c_int, lo: *const f64, hi: *const f64, fmin_normalized: f64,
+        maxeval: c_int, x_out: *mut f64, ei_out: *mut f64, nevals_out: *mut c_int,
+    ) -> c_int {
+        hbegp_maximize_ei_f64(model, starts, s, lo, hi, fmin_normalized, maxeval, x_out, ei_out, nevals_out)
+    }
 }
 
 impl GpuScalar for f32 {
@@ -211,6 +249,18 @@ impl GpuScalar for f32 {
         model: *mut HbegpModel, xs: *const f32, m: c_int, mean: *mut f32, var: *mut f32, n_warn: *mut c_int,
     ) -> c_int {
         hbegp_predict_f32(model, xs, m, mean, var, n_warn)
+    }
+    unsafe fn ffi_predict_grad(
+        model: *mut HbegpModel, xs: *const f32, m: c_int, mean: *mut f32, var: *mut f32, dmean: *mut f32, dvar: *mut f32,
+        n_warn: *mut c_int,
+    ) -> c_int {
+        hbegp_predict_grad_f32(model, xs, m, mean, var, dmean, dvar, n_warn)
+    }
+    unsafe fn ffi_maximize_ei(
+        model: *mut HbegpModel, starts: *const f32, s: c_int, lo: *const f64, hi: *const f64, fmin_normalized: f64,
+        maxeval: c_int, x_out: *mut f32, ei_out: *mut f64, nevals_out: *mut c_int,
+    ) -> c_int {
+        hbegp_maximize_ei_f32(model, starts, s, lo, hi, fmin_normalized, maxeval, x_out, ei_out, nevals_out)
     }
 }
 
@@ -358,6 +408,49 @@ impl<A: GpuScalar> SurrogateModelGpu<A> {
             eprintln!("Variances below 0 were predicted and will be corrected ({} values)", n_warn);
         }
         (mean, var)
+    }
+
+    /// `predict_normalized` plus the gradients w.r.t. the features (`hbegp_predict_grad_*`): mean, variance, d mean / dx
+    /// and d variance / dx ([m, d]), all in the normalised y space.  Opt-in: nothing the estimator suggests uses it.
+    pub fn predict_normalized_with_gradient(&self, x: ArrayView2<A>) -> (Array1<A>, Array1<A>, Array2<A>, Array2<A>) {
+        let (m, d) = x.dim();
+        let x = x.as_standard_layout();
+        let mut mean = Array1::<A>::zeros(m);
+        let mut var = Array1::<A>::zeros(m);
+        let mut dmean = Array2::<A>::zeros((m, d));
+        let mut dvar = Array2::<A>::zeros((m, d));
+        if m == 0 {
+            return (mean, var, dmean, dvar);
+        }
+        let mut n_warn: c_int = 0;
+        let rc = unsafe {
+            A::ffi_predict_grad(self.handle, x.as_ptr(), m as c_int, mean.as_mut_ptr(), var.as_mut_ptr(), dmean.as_mut_ptr(),
+                                dvar.as_mut_ptr(), &mut n_warn)
+        };
+        if rc != HBEGP_OK {
+            panic!("hbegp_predict_grad failed: {}", last_error());
+        }
+        (mean, var, dmean, dvar)
+    }
+
+    /// Bounded L-BFGS ascents of EI in the normalised y space from every row of `starts` inside [lo, hi]
+    /// (`hbegp_maximize_ei_*`, all runs in lockstep on the device model): each run's best point, its EI and its evaluations.
+    pub fn maximize_ei(&self, starts: ArrayView2<A>, lo: &[f64], hi: &[f64], fmin_normalized: f64, maxeval: usize)
+        -> (Array2<A>, Vec<f64>, Vec<c_int>) {
+        let (s, d) = starts.dim();
+        assert!(lo.len() == d && hi.len() == d, "bounds must have one entry per feature");
+        let starts = starts.as_standard_layout();
+        let mut x = Array2::<A>::zeros((s, d));
+        let mut ei = vec![0.0f64; s];
+        let mut nevals: Vec<c_int> = vec![0; s];
+        let rc = unsafe {
+            A::ffi_maximize_ei(self.handle, starts.as_ptr(), s as c_int, lo.as_ptr(), hi.as_ptr(), fmin_normalized,
+                               maxeval as c_int, x.as_mut_ptr(), ei.as_mut_ptr(), nevals.as_mut_ptr())
+        };
+        if rc != HBEGP_OK {
+            panic!("hbegp_maximize_ei failed: {}", last_error());
+        }
+        (x, ei, nevals)
     }
 
     /// Batched `predict_confidence_bound` (gpr.rs:94-112 for every row): one device call instead of one per individual
