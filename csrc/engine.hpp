@@ -199,6 +199,13 @@ void launch_kstar_grad(const T* Xs, int m, int mp, const T* X, int n, int d, int
 template <typename T>
 void launch_pred_dvar(const T* W, const T* Q, int m, int mp, int np, int d, const T* var, T* dvar, hipStream_t s);
 int pred_grad_chunks(int n);
+// joint posterior (hbegp_predict_cov / hbegp_sample_posterior): launch_leaf plus L_kk itself -> W3's block (lower, zeros above
+// the diagonal); then, per draw s (row s of Y [S][ld] = (L z_s)^T): Y[s][i] += mean[i] when `store`, amin[s] = argmin_i, ties
+// to the lowest index.  Both do nothing when *info != 0.
+template <typename T>
+void launch_leaf_keep(T* W1, T* W2, T* W3, int ld, int blk, T* ldiag, int* info, hipStream_t s);
+template <typename T>
+void launch_sample_epilogue(T* Y, int ld, const T* mean, int m, int S, int store, int* amin, const int* info, hipStream_t s);
 
 // predict for m <= PRED_SMALL_MAX candidates without the 128-row padding: reads L^-1 once (row dots against the m
 // cross-kernel vectors).  Ks: [PRED_SMALL_MAX][np] scratch, pmean: [(np+255)/256][PRED_SMALL_MAX], w: [n][PRED_SMALL_MAX].

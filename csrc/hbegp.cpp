@@ -1645,6 +1645,8 @@ struct hbegp_model {
   // gradient scratch (grow-only): G = dKstar/dx*, W = G X^T [d x cap_g x np], the chunk partial sums, dmean / dvar [cap_g x d]
   int cap_g = 0;
   void *G = nullptr, *W = nullptr, *gpart = nullptr, *dmean = nullptr, *dvar = nullptr;
+  // joint posterior: the model's parameters with noise = 1e-5 + jitter (its m_p x m_p work matrices are borrowed per call)
+  EvalParams* dPcov = nullptr;
   // scratch of the path for a handful of candidates (allocated on first use): device [Xs | Ks | out], partial sums, and
   // pinned host staging so that a single-point predict costs one H2D and one D2H
   void *sm_Xs = nullptr, *sm_Ks = nullptr, *sm_out = nullptr, *sm_hin = nullptr, *sm_hout = nullptr;
@@ -1883,6 +1885,203 @@ static int model_predict_grad(hbegp_model* m, const T* Xs, int cnt, T* mean, T* 
   HIPCHECK(hipMemcpyAsync(&out, m->dOut, sizeof(EvalOut), hipMemcpyDeviceToHost, s));
   HIPCHECK(hipStreamSynchronize(s));
   if (n_warn) *n_warn = want_var ? out.n_warn : 0;
+  return HBEGP_OK;
+}
+
+// ---- joint posterior at m candidates (hbegp_predict_cov / hbegp_sample_posterior) ----------------------------------------
+// Work matrices of m_p^2 elements come from the block pool for ONE call and go back at its end (a model that once sampled
+// m = 8192 keeps no gigabyte).  They go back cleared, as the pool hands out fresh blocks: a later owner of the same size (a fit's
+// work matrix) then finds zeros above the diagonal, never Sigma's upper triangle or the NaN of a factor that failed (m = 8192
+// f64: 3 x 512 MiB cleared in ~0.3 ms).
+struct CallScratch {
+  int dev;
+  hipStream_t s;
+  std::vector<std::pair<void*, size_t>> held;
+  void* get(size_t bytes) {
+    bool fresh = false;
+    bytes = std::max<size_t>(16, bytes);
+    void* p = g_pool.get(dev, bytes, &fresh);
+    held.push_back({p, bytes});
+    return p;
+  }
+  ~CallScratch() {
+    for (auto& h : held) (void)hipMemsetAsync(h.first, 0, h.second, s);
+    (void)hipStreamSynchronize(s);  // nothing on the stream still uses them
+    for (auto& h : held) g_pool.put(dev, h.first, h.second);
+  }
+};
+
+// one tile-GEMM launch without a static schedule (the hardware dispatcher), like the batched predict's
+template <typename T>
+static void gemm_launch(GemmLaunch& g, const int* info, hipStream_t s) {
+  g.info = info;
+  int tiles = 0;
+  for (int i = 0; i < g.nops; ++i) tiles += g.op[i].c_lower ? g.op[i].mi * (g.op[i].mi + 1) / 2 : g.op[i].mi * g.op[i].nj;
+  launch_gemm<T>(g, pick_tile(tiles), s);
+}
+
+// Cholesky of the SPD matrix in W1 (lower; blocks [lo, hi) of NB) that KEEPS the factor: L -> W3, X = L^-1 -> W2 where a later
+// step needs it (need_x), diag(L) -> ldiag.  The recursion of the fit (Problem::chol_inv_split) with two changes: its TRSM
+// result L21 = A21 X11^T goes to W3 and stays there (the fit overwrites it with X21), and the diagonal blocks store L_kk
+// (leaf_keep_kernel).  X of a right part is formed only when an enclosing left part needs it: the top node skips X21.
+template <typename T>
+static void chol_keep_rec(T* W1, T* W2, T* W3, T* ldiag, int ld, int lo, int hi, bool need_x, int* info, hipStream_t s) {
+  if (hi - lo == 1) {
+    launch_leaf_keep<T>(W1, W2, W3, ld, lo, ldiag, info, s);
+    return;
+  }
+  const int mid = lo + (hi - lo) / 2;
+  chol_keep_rec<T>(W1, W2, W3, ldiag, ld, lo, mid, true, info, s);
+  GemmOp base{};
+  base.lda = base.ldb = base.ldc = ld;
+  {
+    // L21 = A21 X11^T -> W3[2,1]
+    GemmLaunch g{};
+    g.nops = 1;
+    GemmOp& op = g.op[0];
+    op = base;
+    op.A = W1; op.B = W2; op.C = W3;
+    op.ci0 = mid; op.mi = hi - mid; op.cj0 = lo; op.nj = mid - lo;
+    op.k0 = lo; op.k1 = mid; op.klim = 1; op.maskB = 1;
+    gemm_launch<T>(g, info, s);
+  }
+  {
+    // A22 -= L21 L21^T (lower)   and, where X is needed, U = L21 X11 -> W1[2,1]   (one launch)
+    GemmLaunch g{};
+    g.nops = need_x ? 2 : 1;
+    GemmOp& syrk = g.op[0];
+    syrk = base;
+    syrk.A = W3; syrk.B = W3; syrk.C = W1;
+    syrk.ci0 = mid; syrk.cj0 = mid; syrk.mi = hi - mid; syrk.nj = hi - mid; syrk.c_lower = 1;
+    syrk.k0 = lo; syrk.k1 = mid; syrk.alpha_neg = 1; syrk.beta_one = 1;
+    GemmOp& u = g.op[1];
+    u = base;
+    u.A = W3; u.B = W2; u.C = W1;
+    u.b_kmajor = 1;
+    u.ci0 = mid; u.mi = hi - mid; u.cj0 = lo; u.nj = mid - lo;
+    u.k0 = lo; u.k1 = mid; u.klim = 2; u.maskB = 1;
+    gemm_launch<T>(g, info, s);
+  }
+  chol_keep_rec<T>(W1, W2, W3, ldiag, ld, mid, hi, need_x, info, s);
+  if (need_x) {
+    // X21 = -X22 U -> W2[2,1]
+    GemmLaunch g{};
+    g.nops = 1;
+    GemmOp& op = g.op[0];
+    op = base;
+    op.A = W2; op.B = W1; op.C = W2;
+    op.b_kmajor = 1;
+    op.ci0 = mid; op.mi = hi - mid; op.cj0 = lo; op.nj = mid - lo;
+    op.k0 = mid; op.k1 = hi; op.klim = 3; op.maskA = 1; op.alpha_neg = 1;
+    gemm_launch<T>(g, info, s);
+  }
+}
+
+// phase times of the calling thread's last sampling call (hbegp_debug_posterior_phases): Q, Sigma, factor, draws in ms
+static thread_local bool t_time_posterior = false;
+static thread_local double t_posterior_ms[4] = {0, 0, 0, 0};
+
+// Sigma = K** + (1e-5 + jitter) I - Q Q^T at the candidates (Q = Kstar X^T of the batched predict), then either
+//   cov != nullptr: Sigma mirrored to the full matrix and copied out (hbegp_predict_cov), or
+//   the draws mean + L_S z_s with L_S the Cholesky factor of Sigma: Y = Z L^T (tile GEMM), then the epilogue adds the mean and
+//   finds each draw's argmin (hbegp_sample_posterior).
+// Padding: Kstar's padded rows are zero, so Q's are too, and kmat's identity padding survives the product; L's padding is the
+// identity.  Z's padded rows and columns are zero.
+template <typename T>
+static int model_posterior(hbegp_model* m, const T* Xs, int cnt, double jitter, T* mean, T* cov, const T* z, int S, T* samples,
+                           int* argmin, int* info_out) {
+  std::lock_guard<std::mutex> lock(m->mu);
+  HIPCHECK(hipSetDevice(m->dev));
+  const int mp = round_up(cnt, NB);
+  const int Sp = cov ? 0 : round_up(S, NB);
+  const size_t nn = (size_t)mp * mp;
+  // everything the call borrows, counted before anything is taken: an m far beyond the device is ENOMEM, not an overflow
+  const double need = (double)sizeof(T) * ((cov ? 1.0 : 3.0) * (double)mp * mp + 2.0 * (double)Sp * mp + 2.0 * (double)mp * m->np);
+  if (need > 1e15) return fail(HBEGP_ENOMEM, "the joint posterior of %d points needs %.3g bytes of device memory", cnt, need);
+  predict_batched_reserve<T>(m, mp);
+  if (!m->dPcov) m->dPcov = static_cast<EvalParams*>(m->palloc(sizeof(EvalParams)));
+  hipStream_t s = m->stream;
+  int* info = &m->dOut->info;
+  const double noise = 1e-5 + jitter;  // predict.rs:25-29's min_noise, plus the caller's jitter (copied from here: outlives the stream work)
+  CallScratch ws{m->dev, s, {}};
+  T* W1 = static_cast<T*>(ws.get(sizeof(T) * nn));
+  hipEvent_t ev[5] = {};
+  const bool timed = t_time_posterior && !cov;
+  if (timed)
+    for (auto& e : ev) HIPCHECK(hipEventCreate(&e));
+  if (timed) HIPCHECK(hipEventRecord(ev[0], s));
+  HIPCHECK(hipMemcpyAsync(m->Xs, Xs, sizeof(T) * (size_t)cnt * m->d, hipMemcpyHostToDevice, s));
+  predict_batched_launches<T>(m, cnt, mp, true);  // Kstar, the mean, Q (and the variance, unused here)
+  if (timed) HIPCHECK(hipEventRecord(ev[1], s));
+  HIPCHECK(hipMemcpyAsync(m->dPcov, m->dP, sizeof(EvalParams), hipMemcpyDeviceToDevice, s));
+  HIPCHECK(hipMemcpyAsync(&m->dPcov->noise, &noise, sizeof(double), hipMemcpyHostToDevice, s));
+  launch_kmat<T>(static_cast<T*>(m->Xs), cnt, m->d, mp, m->nu2, m->dPcov, W1, info, s);
+  {
+    // Sigma -= Q Q^T (lower tiles), contraction over the training points
+    GemmLaunch g{};
+    g.nops = 1;
+    GemmOp& op = g.op[0];
+    op.A = m->Q; op.B = m->Q; op.C = W1;
+    op.lda = m->np; op.ldb = m->np; op.ldc = mp;
+    op.mi = mp / NB; op.nj = mp / NB; op.c_lower = 1;
+    op.k0 = 0; op.k1 = m->np / NB;
+    op.alpha_neg = 1; op.beta_one = 1;
+    gemm_launch<T>(g, info, s);
+  }
+  if (cov) {
+    launch_symmetrize<T>(W1, mp, s);
+    CHECK_LAUNCHES();
+    if (mean) HIPCHECK(hipMemcpyAsync(mean, m->mean, sizeof(T) * cnt, hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipMemcpy2DAsync(cov, sizeof(T) * cnt, W1, sizeof(T) * mp, sizeof(T) * cnt, cnt, hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipStreamSynchronize(s));
+    return HBEGP_OK;
+  }
+  if (timed) HIPCHECK(hipEventRecord(ev[2], s));
+  T* W2 = static_cast<T*>(ws.get(sizeof(T) * nn));
+  T* W3 = static_cast<T*>(ws.get(sizeof(T) * nn));
+  T* ld = static_cast<T*>(ws.get(sizeof(T) * mp));
+  // the tile GEMMs read X and L as triangular operands: what the diagonal blocks do not write above the diagonal (the strict
+  // upper 16 x 16 blocks of X's diagonal blocks) must be zero in memory, and a recycled block holds its earlier owner's numbers
+  HIPCHECK(hipMemsetAsync(W2, 0, sizeof(T) * nn, s));
+  HIPCHECK(hipMemsetAsync(W3, 0, sizeof(T) * nn, s));
+  chol_keep_rec<T>(W1, W2, W3, ld, mp, 0, mp / NB, false, info, s);
+  if (timed) HIPCHECK(hipEventRecord(ev[3], s));
+  T* Z = static_cast<T*>(ws.get(sizeof(T) * (size_t)Sp * mp));
+  T* Y = static_cast<T*>(ws.get(sizeof(T) * (size_t)Sp * mp));
+  int* amin = static_cast<int*>(ws.get(sizeof(int) * (size_t)S));
+  HIPCHECK(hipMemsetAsync(Z, 0, sizeof(T) * (size_t)Sp * mp, s));
+  HIPCHECK(hipMemcpy2DAsync(Z, sizeof(T) * mp, z, sizeof(T) * cnt, sizeof(T) * cnt, S, hipMemcpyHostToDevice, s));
+  {
+    // Y = Z L^T: Y[s][i] = sum_{k <= i} z_s[k] L[i][k]  (L lower: k <= j, as for Q = Kstar X^T)
+    GemmLaunch g{};
+    g.nops = 1;
+    GemmOp& op = g.op[0];
+    op.A = Z; op.B = W3; op.C = Y;
+    op.lda = mp; op.ldb = mp; op.ldc = mp;
+    op.mi = Sp / NB; op.nj = mp / NB;
+    op.k0 = 0; op.k1 = mp / NB; op.klim = 1; op.maskB = 1;
+    gemm_launch<T>(g, info, s);
+  }
+  launch_sample_epilogue<T>(Y, mp, static_cast<T*>(m->mean), cnt, S, samples != nullptr, amin, info, s);
+  if (timed) HIPCHECK(hipEventRecord(ev[4], s));
+  CHECK_LAUNCHES();
+  EvalOut out;
+  HIPCHECK(hipMemcpyAsync(&out, m->dOut, sizeof(EvalOut), hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
+  if (timed) {
+    for (int i = 0; i < 4; ++i) {
+      float ms = 0;
+      HIPCHECK(hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
+      t_posterior_ms[i] = ms;
+    }
+    for (auto& e : ev) (void)hipEventDestroy(e);
+  }
+  if (info_out) *info_out = out.info;
+  if (out.info != 0) return fail(HBEGP_NOT_PD, "Sigma is not positive definite (pivot panel at column %d); a larger jitter may help",
+                                 out.info - 1);
+  if (samples) HIPCHECK(hipMemcpy2DAsync(samples, sizeof(T) * cnt, Y, sizeof(T) * mp, sizeof(T) * cnt, S, hipMemcpyDeviceToHost, s));
+  if (argmin) HIPCHECK(hipMemcpyAsync(argmin, amin, sizeof(int) * (size_t)S, hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
   return HBEGP_OK;
 }
 
@@ -2771,6 +2970,72 @@ int hbegp_maximize_ei_f32(hbegp_model* model, const float* starts, int S, const 
   GUARD_BEGIN
   return model_maximize_ei<float>(model, starts, S, lo, hi, fmin_normalized, maxeval, x_out, ei_out, nevals_out);
   GUARD_END
+}
+
+}  // extern "C"
+// argument checks of the joint-posterior entry points: everything is refused before any device call
+template <typename T>
+static int check_posterior(hbegp_model* model, const T* Xs, int m, double jitter) {
+  if (m < 0) return fail(HBEGP_EINVAL, "m must be >= 0 (got %d)", m);
+  if (!(jitter >= 0.0) || !std::isfinite(jitter)) return fail(HBEGP_EINVAL, "jitter must be finite and >= 0 (got %g)", jitter);
+  if (!model) return fail(HBEGP_EINVAL, "NULL model");
+  if (model->is_f32 != (sizeof(T) == 4)) return fail(HBEGP_EINVAL, "model holds %s data", model->is_f32 ? "f32" : "f64");
+  if (m > 0 && !Xs) return fail(HBEGP_EINVAL, "Xs is NULL");
+  const size_t cnt = (size_t)m * model->d;
+  for (size_t i = 0; i < cnt; ++i)
+    if (!std::isfinite((double)Xs[i]))
+      return fail(HBEGP_EINVAL, "query point %d has a non-finite coordinate (feature %d)", (int)(i / model->d), (int)(i % model->d));
+  return HBEGP_OK;
+}
+// the checks that need no model come first, so that each one has its own message whatever else is wrong
+template <typename T>
+static int check_sample(hbegp_model* model, const T* Xs, int m, const T* z, int S, double jitter, T* samples, int* argmin) {
+  if (m < 0) return fail(HBEGP_EINVAL, "m must be >= 0 (got %d)", m);
+  if (S < 1) return fail(HBEGP_EINVAL, "S must be >= 1 (got %d)", S);
+  if (m > 0 && !z) return fail(HBEGP_EINVAL, "z is NULL");
+  if (!samples && !argmin) return fail(HBEGP_EINVAL, "samples and argmin are both NULL");
+  return check_posterior<T>(model, Xs, m, jitter);
+}
+extern "C" {
+int hbegp_predict_cov_f64(hbegp_model* model, const double* Xs, int m, double jitter, double* mean, double* cov) {
+  if (int rc = check_posterior<double>(model, Xs, m, jitter)) return rc;
+  if (m > 0 && !cov) return fail(HBEGP_EINVAL, "cov is NULL");
+  if (m == 0) return HBEGP_OK;
+  GUARD_BEGIN
+  return model_posterior<double>(model, Xs, m, jitter, mean, cov, nullptr, 0, nullptr, nullptr, nullptr);
+  GUARD_END
+}
+int hbegp_predict_cov_f32(hbegp_model* model, const float* Xs, int m, double jitter, float* mean, float* cov) {
+  if (int rc = check_posterior<float>(model, Xs, m, jitter)) return rc;
+  if (m > 0 && !cov) return fail(HBEGP_EINVAL, "cov is NULL");
+  if (m == 0) return HBEGP_OK;
+  GUARD_BEGIN
+  return model_posterior<float>(model, Xs, m, jitter, mean, cov, nullptr, 0, nullptr, nullptr, nullptr);
+  GUARD_END
+}
+int hbegp_sample_posterior_f64(hbegp_model* model, const double* Xs, int m, const double* z, int S, double jitter, double* samples,
+                               int* argmin, int* info) {
+  if (int rc = check_sample<double>(model, Xs, m, z, S, jitter, samples, argmin)) return rc;
+  if (info) *info = 0;
+  if (m == 0) return HBEGP_OK;
+  GUARD_BEGIN
+  return model_posterior<double>(model, Xs, m, jitter, nullptr, nullptr, z, S, samples, argmin, info);
+  GUARD_END
+}
+int hbegp_sample_posterior_f32(hbegp_model* model, const float* Xs, int m, const float* z, int S, double jitter, float* samples,
+                               int* argmin, int* info) {
+  if (int rc = check_sample<float>(model, Xs, m, z, S, jitter, samples, argmin)) return rc;
+  if (info) *info = 0;
+  if (m == 0) return HBEGP_OK;
+  GUARD_BEGIN
+  return model_posterior<float>(model, Xs, m, jitter, nullptr, nullptr, z, S, samples, argmin, info);
+  GUARD_END
+}
+int hbegp_debug_posterior_phases(int enable, double* phase_ms) {
+  if (phase_ms)
+    for (int i = 0; i < 4; ++i) phase_ms[i] = t_posterior_ms[i];
+  t_time_posterior = enable != 0;
+  return HBEGP_OK;
 }
 
 int hbegp_model_info(const hbegp_model* model, int* n, int* d, int* is_f32, double* nu, double* lml) {

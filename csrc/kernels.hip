@@ -1995,6 +1995,74 @@ template void launch_pred_dvar<float>(const float*, const float*, int, int, int,
 int pred_grad_chunks(int n) { return (n + PG_CHUNK - 1) / PG_CHUNK; }
 
 // =================================================================================================================
+// joint posterior at the candidates (hbegp.cpp: model_posterior).  Sigma = K** + (1e-5 + jitter) I - Q Q^T comes from kmat_kernel
+// and one tile GEMM; its factor from the recursion of the fit with the diagonal blocks below, which keep L; the draws
+// Y = Z L^T from one more tile GEMM.  Two kernels of their own:
+//   leaf_keep_kernel:       leaf_kernel's diagonal block, plus L_kk itself -> W3 (lower, explicit zeros above the diagonal:
+//                           the tile GEMM reads W3 as a triangular operand).  leaf_kernel's own code is unchanged.
+//   sample_epilogue_kernel: one workgroup per draw s: v_i = Y[s][i] + mean_i (stored in place when asked), and the index of
+//                           the smallest v, ties to the lowest index -- every thread scans its entries in ascending i, then a
+//                           fixed tree over the threads.  No atomics: the same inputs give the same bits.
+// Both return at once when `info` is set (a failed pivot upstream): nothing spins, nothing reads a factor that failed.
+// =================================================================================================================
+template <typename T, typename TIO>
+__global__ void __launch_bounds__(512, 2) leaf_keep_kernel(TIO* __restrict__ W1, TIO* __restrict__ W2, TIO* __restrict__ W3, int ld,
+                                                        int blk, TIO* __restrict__ ldiag, int* info) {
+  if (*info != 0) return;
+  extern __shared__ __align__(16) char smem_raw[];
+  leaf_body<T, TIO, false>(W1, W2, ld, blk, ldiag, info, 0, smem_raw);
+  __syncthreads();
+  // the lower triangle of the image holds L since the last panel's barrier (what follows it writes X^T above the diagonal)
+  const T* As = reinterpret_cast<const T*>(smem_raw);
+  TIO* Lblk = W3 + (size_t)blk * NB * ld + (size_t)blk * NB;
+  for (int c = threadIdx.x; c < NB * NB; c += 512) {
+    const int r = c >> 7, j = c & (NB - 1);
+    Lblk[(size_t)r * ld + j] = j <= r ? (TIO)As[r * LeafGeom<T>::S + j] : TIO(0);
+  }
+}
+template <typename T>
+void launch_leaf_keep(T* W1, T* W2, T* W3, int ld, int blk, T* ldiag, int* info, hipStream_t s) {
+  hipLaunchKernelGGL((leaf_keep_kernel<double, T>), dim3(1), dim3(512), LeafGeom<double>::LDS_BYTES, s, W1, W2, W3, ld, blk, ldiag, info);
+}
+template void launch_leaf_keep<double>(double*, double*, double*, int, int, double*, int*, hipStream_t);
+template void launch_leaf_keep<float>(float*, float*, float*, int, int, float*, int*, hipStream_t);
+
+template <typename T>
+__global__ void __launch_bounds__(256) sample_epilogue_kernel(T* __restrict__ Y, int ld, const T* __restrict__ mean, int m, int store,
+                                                              int* __restrict__ amin, const int* info) {
+  if (*info != 0) return;
+  __shared__ T sv[256];
+  __shared__ int si[256];
+  const int t = threadIdx.x;
+  T* y = Y + (size_t)blockIdx.x * ld;
+  T best = T(0);
+  int bi = -1;
+  for (int i = t; i < m; i += 256) {
+    const T v = y[i] + mean[i];
+    if (store) y[i] = v;
+    if (bi < 0 || v < best) { best = v; bi = i; }  // ascending i: an equal value keeps the earlier index
+  }
+  sv[t] = best;
+  si[t] = bi;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (t < w) {
+      const T v = sv[t + w];
+      const int i = si[t + w];
+      if (i >= 0 && (si[t] < 0 || v < sv[t] || (v == sv[t] && i < si[t]))) { sv[t] = v; si[t] = i; }
+    }
+    __syncthreads();
+  }
+  if (t == 0) amin[blockIdx.x] = si[0];
+}
+template <typename T>
+void launch_sample_epilogue(T* Y, int ld, const T* mean, int m, int S, int store, int* amin, const int* info, hipStream_t s) {
+  hipLaunchKernelGGL((sample_epilogue_kernel<T>), dim3(S), dim3(256), 0, s, Y, ld, mean, m, store, amin, info);
+}
+template void launch_sample_epilogue<double>(double*, int, const double*, int, int, int, int*, const int*, hipStream_t);
+template void launch_sample_epilogue<float>(float*, int, const float*, int, int, int, int*, const int*, hipStream_t);
+
+// =================================================================================================================
 // predict for a handful of candidates (m <= PRED_SMALL_MAX): the caller's acquisition and selection loops issue
 // thousands of single-point predicts per generation (acquisition.rs:46-64, minimize.rs:656-714).  The batched path pads
 // to 128 candidate rows and runs a tile GEMM over all of L^-1 (0.2 ms at n=4096 whatever m is); here L^-1 is read once,
@@ -2896,6 +2964,8 @@ void init_kernels() {
   init_gemm_attr<float, 128>(); init_gemm_attr<float, 64>(); init_gemm_attr<float, 32>();
   set_lds_attr(reinterpret_cast<const void*>(&leaf_kernel<double, double>), (int)LeafGeom<double>::LDS_BYTES, "leaf_kernel<f64>: dynamic LDS limit");
   set_lds_attr(reinterpret_cast<const void*>(&leaf_kernel<double, float>), (int)LeafGeom<double>::LDS_BYTES, "leaf_kernel<f32>: dynamic LDS limit");
+  set_lds_attr(reinterpret_cast<const void*>(&leaf_keep_kernel<double, double>), (int)LeafGeom<double>::LDS_BYTES, "leaf_keep_kernel<f64>: dynamic LDS limit");
+  set_lds_attr(reinterpret_cast<const void*>(&leaf_keep_kernel<double, float>), (int)LeafGeom<double>::LDS_BYTES, "leaf_keep_kernel<f32>: dynamic LDS limit");
   init_dag_kernels();
   const int lb = 163840;
   // kmat / gradtrace: 2 d 64 elements of dynamic LDS (64 KiB at d = 64 in f64) beside ~21 KiB of static LDS

@@ -84,6 +84,11 @@ SIGNATURES = {
     "hbegp_predict_grad_f32": (C.c_int, [_vp, _fp, C.c_int, _fp, _fp, _fp, _fp, _ip]),
     "hbegp_maximize_ei_f64": (C.c_int, [_vp, _dp, C.c_int, _dp, _dp, C.c_double, C.c_int, _dp, _dp, _ip]),
     "hbegp_maximize_ei_f32": (C.c_int, [_vp, _fp, C.c_int, _dp, _dp, C.c_double, C.c_int, _fp, _dp, _ip]),
+    "hbegp_predict_cov_f64": (C.c_int, [_vp, _dp, C.c_int, C.c_double, _dp, _dp]),
+    "hbegp_predict_cov_f32": (C.c_int, [_vp, _fp, C.c_int, C.c_double, _fp, _fp]),
+    "hbegp_sample_posterior_f64": (C.c_int, [_vp, _dp, C.c_int, _dp, C.c_int, C.c_double, _dp, _ip, _ip]),
+    "hbegp_sample_posterior_f32": (C.c_int, [_vp, _fp, C.c_int, _fp, C.c_int, C.c_double, _fp, _ip, _ip]),
+    "hbegp_debug_posterior_phases": (C.c_int, [C.c_int, _dp]),
     "hbegp_model_info": (C.c_int, [_vp, _ip, _ip, _ip, _dp, _dp]),
     "hbegp_model_get_f64": (C.c_int, [_vp, _dp, _dp, _dp]),
     "hbegp_model_get_f32": (C.c_int, [_vp, _dp, _fp, _fp]),

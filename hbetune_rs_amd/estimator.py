@@ -183,6 +183,21 @@ class RNG:
         self.count += 1
         return lo + (hi - lo) * u
 
+    def standard_normal(self, size):
+        """Deterministic standard normals (Box-Muller over the same SplitMix64 stream as `uniform`), shape `size`.  The first
+        uniform of every pair enters as 1 - u, in (0, 1]: the logarithm never sees 0, so no draw is infinite."""
+        shape = (size,) if np.isscalar(size) else tuple(size)
+        count = int(np.prod(shape, dtype=np.int64))
+        pairs = (count + 1) // 2
+        u = splitmix64_uniform_fast(self.seed + 7919 * self.count, 2 * pairs)
+        self.count += 1
+        r = np.sqrt(-2.0 * np.log(1.0 - u[0::2]))
+        t = 2.0 * math.pi * u[1::2]
+        z = np.empty(2 * pairs)
+        z[0::2] = r * np.cos(t)
+        z[1::2] = r * np.sin(t)
+        return z[:count].reshape(shape)
+
 
 class SurrogateModelGPR:
     """gpr.rs:54-63 + impl SurrogateModel (gpr.rs:71-213)."""
@@ -273,6 +288,15 @@ class SurrogateModelGPR:
         hi = np.array([b[1] for b in bounds], dtype=np.float64)
         return self.fitted.maximize_ei(np.asarray(starts, dtype=self.dtype), lo, hi, self._fmin_normalized(fmin), maxeval=maxeval)
 
+    # Joint posterior draws (opt-in; nothing the estimator suggests by default uses them).
+    def sample_a(self, x, n_samples, rng, jitter=0.0):
+        """n_samples joint draws of the surrogate at the rows of x [m, d], projected like predict_mean_a: [n_samples, m].
+        The normals come from rng.standard_normal; the projection is elementwise and monotone, so it is exact for draws."""
+        x = np.asarray(x, dtype=self.dtype)
+        z = rng.standard_normal((int(n_samples), x.shape[0])).astype(self.dtype)
+        samples, _ = self.fitted.sample_posterior(x, z, jitter=jitter)
+        return self.y_norm.project_location_from_normalized(samples)
+
     # Batched forms of the scalar trait methods (SURVEY.md 8f rank 1: the acquisition loops call these once per generation
     # instead of m single-point predicts, each of which reads all of K^-1).
     def predict_confidence_bound_a(self, x, cb):
@@ -323,6 +347,19 @@ def acquire_by_mutation(candidates, model, fmin):
     idx = _argmax_last(eis)
     rows = np.arange(npar)
     return idx, means[rows, idx], eis[rows, idx]
+
+
+def acquire_by_thompson(candidates, model, k, rng, jitter=0.0):
+    """Batch Thompson sampling over a candidate set [m, n_features]: k joint posterior draws of the surrogate at the candidates
+    (one device call), and for each draw the index of its minimum -- k indices, repeats allowed.  The y projection is monotone
+    increasing, so the argmin of a normalised draw is the argmin of the projected one: only the k indices leave the device.
+    Opt-in: nothing the estimator suggests by default calls it."""
+    c = np.asarray(candidates, dtype=model.dtype)
+    if c.ndim != 2:
+        raise ValueError("candidates must be [m, n_features]")
+    z = rng.standard_normal((int(k), c.shape[0])).astype(model.dtype)
+    _, argmin = model.fitted.sample_posterior(c, z, jitter=jitter, want_samples=False)
+    return np.asarray(argmin, dtype=np.int64)
 
 
 class FitnessOperator:

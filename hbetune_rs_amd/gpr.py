@@ -321,6 +321,37 @@ class FittedKernel:
                       _lib.dptr(ei), nevals.ctypes.data_as(C.POINTER(C.c_int))))
         return x, ei, nevals
 
+    def predict_cov(self, x, jitter=0.0):
+        """Joint posterior at the query points (hbegp_predict_cov_*): returns (mean[m], cov[m, m]) in the normalised y space,
+        cov = K** + (1e-5 + jitter) I - K*^T K^-1 K* (unclamped; its diagonal is predict()'s variance before clamping)."""
+        lib = _lib.load()
+        x = _lib.as_c(np.atleast_2d(x), self.dtype)
+        assert x.ndim == 2 and x.shape[1] == self.d
+        m = x.shape[0]
+        mean = np.zeros(m, dtype=self.dtype)
+        cov = np.zeros((m, m), dtype=self.dtype)
+        fn = getattr(lib, f"hbegp_predict_cov_{self._sfx}")
+        _lib.check(fn(self._h, _lib.aptr(x), m, float(jitter), _lib.aptr(mean), _lib.aptr(cov)))
+        return mean, cov
+
+    def sample_posterior(self, x, z, jitter=0.0, want_samples=True):
+        """S joint draws mean + L z_s from N(mean, cov) of predict_cov (hbegp_sample_posterior_*), z[S, m] the caller's standard
+        normals.  Returns (samples[S, m] or None, argmin[S]): argmin = each draw's smallest entry, ties to the lowest index.
+        Raises HbegpError with code NOT_PD when cov is not positive definite (retry with a larger jitter)."""
+        lib = _lib.load()
+        x = _lib.as_c(np.atleast_2d(x), self.dtype)
+        assert x.ndim == 2 and x.shape[1] == self.d
+        m = x.shape[0]
+        z = _lib.as_c(np.atleast_2d(z), self.dtype)
+        assert z.ndim == 2 and z.shape[1] == m, (z.shape, m)
+        S = z.shape[0]
+        samples = np.zeros((S, m), dtype=self.dtype) if want_samples else None
+        argmin = np.zeros(S, dtype=np.int32)
+        fn = getattr(lib, f"hbegp_sample_posterior_{self._sfx}")
+        _lib.check(fn(self._h, _lib.aptr(x), m, _lib.aptr(z), S, float(jitter), _lib.aptr(samples),
+                      argmin.ctypes.data_as(C.POINTER(C.c_int)), None))
+        return samples, argmin
+
     def release(self):
         if self._h:
             _lib.load().hbegp_model_release(self._h)

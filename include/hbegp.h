@@ -226,6 +226,34 @@ int hbegp_maximize_ei_f64(hbegp_model* model, const double* starts, int S, const
 int hbegp_maximize_ei_f32(hbegp_model* model, const float* starts, int S, const double* lo, const double* hi, double fmin_normalized,
                           int maxeval, float* x_out, double* ei_out, int* nevals_out);
 
+/* Joint posterior of the latent function at m query points (predict.rs:7-52 extended to pairs), in the model's normalised
+ * y space like hbegp_predict_*:
+ *   cov[i*m + j] = c phi_nu(r(x*_i, x*_j)) + (1e-5 + jitter) [i == j] - q_i . q_j,   q_i = L^-1 k*_i
+ * full symmetric m x m, row-major, exactly symmetric (the lower triangle mirrored, not computed twice).  1e-5 is the reference's
+ * min_noise (predict.rs:25-29), so the diagonal is hbegp_predict's variance before clamping; with jitter = 0 it matches it to
+ * rounding.  No clamping: a clamped diagonal would not be a covariance.  mean[m] as hbegp_predict_* (may be NULL).
+ * jitter >= 0 and finite.  m = 0 is a no-op.  A non-finite query coordinate is HBEGP_EINVAL (one NaN row would poison the
+ * factor of every other row in the sampling call), checked on the host before any device work.  Threads may call these on
+ * one model at once (serialised per model, like predict).  Work matrices of m_p^2 elements (m_p = m rounded up to 128) are
+ * borrowed for the call; an m whose work does not fit in device memory is HBEGP_ENOMEM. */
+int hbegp_predict_cov_f64(hbegp_model* model, const double* Xs, int m, double jitter, double* mean, double* cov);
+int hbegp_predict_cov_f32(hbegp_model* model, const float* Xs, int m, double jitter, float* mean, float* cov);
+
+/* S joint draws from N(mean, cov) as above, from the CALLER's standard normals (the RNG stays on the caller side, DESIGN
+ * section 7): z[S*m], draw s = row s.  samples[S*m] (may be NULL): samples[s] = mean + L_S z_s, where L_S is the lower Cholesky
+ * factor of cov (unique, so the result does not depend on how the library factors it).
+ * argmin[S] (may be NULL): the index of the smallest entry of draw s, ties to the lowest index (Thompson sampling for a
+ * minimiser).  samples and argmin must not both be NULL.  *info (may be NULL): 0, or 1 + the first column of the 16-column
+ * panel whose pivot failed (the fit's convention).  Returns HBEGP_NOT_PD when cov is not positive definite in the element
+ * type; nothing is written to samples / argmin then.  The caller can retry with a larger jitter: the library never raises it
+ * by itself.  HBEGP_EINVAL (before any device call) for a NULL model, m < 0, S < 1, a NULL z with m > 0, a jitter < 0 or
+ * not finite, samples and argmin both NULL, a model of the other element type or a non-finite query coordinate.
+ * The same call gives the same bits (fixed-order sums, no atomics). */
+int hbegp_sample_posterior_f64(hbegp_model* model, const double* Xs, int m, const double* z, int S, double jitter,
+                               double* samples, int* argmin, int* info);
+int hbegp_sample_posterior_f32(hbegp_model* model, const float* Xs, int m, const float* z, int S, double jitter,
+                               float* samples, int* argmin, int* info);
+
 int hbegp_model_info(const hbegp_model* model, int* n, int* d, int* is_f32, double* nu, double* lml);
 /* theta[p] (log space, clamped), alpha[n], kinv[n*n] full symmetric; any pointer may be NULL. */
 int hbegp_model_get_f64(hbegp_model* model, double* theta, double* alpha, double* kinv);
@@ -267,6 +295,12 @@ int hbegp_debug_dag_plan(int nblocks, int bk, int small_h, int nwg, int fine, in
  * gradmin.rs:35-60) through it and compare every point. */
 int hbegp_debug_lbfgs_replay(int n, const double* x0, const double* lo, const double* hi, int maxeval, int memory, int fixed_work,
                              int count, const double* f, const double* g, double* requested, int* n_requested);
+
+/* ---- timing hook (tools/posterior_cov_bench.py): phase_ms[4] (may be NULL) receives the device time of the phases of the
+ * calling thread's last timed hbegp_sample_posterior_* call -- Q (Kstar, mean, Q = Kstar L^-T), Sigma, its factor, the draws
+ * (upload of z, Z L^T, epilogue) -- in milliseconds; then enable != 0 makes this thread's later sampling calls timed (events
+ * around the phases on the model stream). */
+int hbegp_debug_posterior_phases(int enable, double* phase_ms);
 
 #ifdef __cplusplus
 }

@@ -56,6 +56,10 @@ template <> struct Abi<double> {
   }
   static int maximize_ei(hbegp_model* m, const double* st, int s, const double* lo, const double* hi, double fmin, int maxeval, double* x,
                          double* ei, int* ne) { return hbegp_maximize_ei_f64(m, st, s, lo, hi, fmin, maxeval, x, ei, ne); }
+  static int predict_cov(hbegp_model* m, const double* xs, int k, double j, double* mean, double* cov) { return hbegp_predict_cov_f64(m, xs, k, j, mean, cov); }
+  static int sample_posterior(hbegp_model* m, const double* xs, int k, const double* z, int s, double j, double* smp, int* amin, int* info) {
+    return hbegp_sample_posterior_f64(m, xs, k, z, s, j, smp, amin, info);
+  }
   static int get(hbegp_model* m, double* t, double* a, double* ki) { return hbegp_model_get_f64(m, t, a, ki); }
 };
 template <> struct Abi<float> {
@@ -72,6 +76,10 @@ template <> struct Abi<float> {
   }
   static int maximize_ei(hbegp_model* m, const float* st, int s, const double* lo, const double* hi, double fmin, int maxeval, float* x,
                          double* ei, int* ne) { return hbegp_maximize_ei_f32(m, st, s, lo, hi, fmin, maxeval, x, ei, ne); }
+  static int predict_cov(hbegp_model* m, const float* xs, int k, double j, float* mean, float* cov) { return hbegp_predict_cov_f32(m, xs, k, j, mean, cov); }
+  static int sample_posterior(hbegp_model* m, const float* xs, int k, const float* z, int s, double j, float* smp, int* amin, int* info) {
+    return hbegp_sample_posterior_f32(m, xs, k, z, s, j, smp, amin, info);
+  }
   static int get(hbegp_model* m, double* t, float* a, float* ki) { return hbegp_model_get_f32(m, t, a, ki); }
 };
 }  // namespace detail
@@ -142,6 +150,15 @@ class FittedKernel {
   void maximize_ei(const A* starts, int S, const double* lo, const double* hi, double fmin_normalized, int maxeval, A* x_out,
                    double* ei_out, int* nevals = nullptr) const {
     check(detail::Abi<A>::maximize_ei(h_, starts, S, lo, hi, fmin_normalized, maxeval, x_out, ei_out, nevals));
+  }
+  // joint posterior at xs[m*d]: mean[m] (may be nullptr), cov[m*m] = K** + (1e-5 + jitter) I - K*^T K^-1 K* (normalised y space)
+  void predict_cov(const A* xs, int m, A* mean, A* cov, double jitter = 0.0) const {
+    check(detail::Abi<A>::predict_cov(h_, xs, m, jitter, mean, cov));
+  }
+  // S joint draws mean + L z_s from the caller's normals z[S*m]: samples[S*m] and / or argmin[S] (either may be nullptr, not both);
+  // throws Error(HBEGP_NOT_PD) when cov does not factor (retry with a larger jitter)
+  void sample_posterior(const A* xs, int m, const A* z, int S, A* samples, int* argmin, double jitter = 0.0) const {
+    check(detail::Abi<A>::sample_posterior(h_, xs, m, z, S, jitter, samples, argmin, nullptr));
   }
   double lml() const { return lml_; }
   double noise() const { return std::exp(theta_[0]); }

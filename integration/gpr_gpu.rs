@@ -121,6 +121,20 @@ extern "C" {
         model: *mut HbegpModel, starts: *const c_float, s: c_int, lo: *const c_double, hi: *const c_double,
         fmin_normalized: c_double, maxeval: c_int, x_out: *mut c_float, ei_out: *mut c_double, nevals_out: *mut c_int,
     ) -> c_int;
+    fn hbegp_predict_cov_f64(
+        model: *mut HbegpModel, xs: *const c_double, m: c_int, jitter: c_double, mean: *mut c_double, cov: *mut c_double,
+    ) -> c_int;
+    fn hbegp_predict_cov_f32(
+        model: *mut HbegpModel, xs: *const c_float, m: c_int, jitter: c_double, mean: *mut c_float, cov: *mut c_float,
+    ) -> c_int;
+    fn hbegp_sample_posterior_f64(
+        model: *mut HbegpModel, xs: *const c_double, m: c_int, z: *const c_double, s: c_int, jitter: c_double,
+        samples: *mut c_double, argmin: *mut c_int, info: *mut c_int,
+    ) -> c_int;
+    fn hbegp_sample_posterior_f32(
+        model: *mut HbegpModel, xs: *const c_float, m: c_int, z: *const c_float, s: c_int, jitter: c_double,
+        samples: *mut c_float, argmin: *mut c_int, info: *mut c_int,
+    ) -> c_int;
     fn hbegp_model_info(
         model: *const HbegpModel, n: *mut c_int, d: *mut c_int, is_f32: *mut c_int, nu: *mut c_double, lml: *mut c_double,
     ) -> c_int;
@@ -184,6 +198,15 @@ pub trait GpuScalar: Scalar + sealed::Sealed {
         model: *mut HbegpModel, starts: *const Self, s: c_int, lo: *const f64, hi: *const f64, fmin_normalized: f64,
         maxeval: c_int, x_out: *mut Self, ei_out: *mut f64, nevals_out: *mut c_int,
     ) -> c_int;
+    /// `hbegp_predict_cov_*`
+    unsafe fn ffi_predict_cov(
+        model: *mut HbegpModel, xs: *const Self, m: c_int, jitter: f64, mean: *mut Self, cov: *mut Self,
+    ) -> c_int;
+    /// `hbegp_sample_posterior_*`
+    unsafe fn ffi_sample_posterior(
+        model: *mut HbegpModel, xs: *const Self, m: c_int, z: *const Self, s: c_int, jitter: f64, samples: *mut Self,
+        argmin: *mut c_int, info: *mut c_int,
+    ) -> c_int;
 }
 
 impl GpuScalar for f64 {
@@ -223,6 +246,17 @@ impl GpuScalar for f64 {
     ) -> c_int {
         hbegp_maximize_ei_f64(model, starts, s, lo, hi, fmin_normalized, maxeval, x_out, ei_out, nevals_out)
     }
+    unsafe fn ffi_predict_cov(
+        model: *mut HbegpModel, xs: *const f64, m: c_int, jitter: f64, mean: *mut f64, cov: *mut f64,
+    ) -> c_int {
+        hbegp_predict_cov_f64(model, xs, m, jitter, mean, cov)
+    }
+    unsafe fn ffi_sample_posterior(
+        model: *mut HbegpModel, xs: *const f64, m: c_int, z: *const f64, s: c_int, jitter: f64, samples: *mut f64,
+        argmin: *mut c_int, info: *mut c_int,
+    ) -> c_int {
+        hbegp_sample_posterior_f64(model, xs, m, z, s, jitter, samples, argmin, info)
+    }
 }
 
 impl GpuScalar for f32 {
@@ -261,6 +295,17 @@ impl GpuScalar for f32 {
         maxeval: c_int, x_out: *mut f32, ei_out: *mut f64, nevals_out: *mut c_int,
     ) -> c_int {
         hbegp_maximize_ei_f32(model, starts, s, lo, hi, fmin_normalized, maxeval, x_out, ei_out, nevals_out)
+    }
+    unsafe fn ffi_predict_cov(
+        model: *mut HbegpModel, xs: *const f32, m: c_int, jitter: f64, mean: *mut f32, cov: *mut f32,
+    ) -> c_int {
+        hbegp_predict_cov_f32(model, xs, m, jitter, mean, cov)
+    }
+    unsafe fn ffi_sample_posterior(
+        model: *mut HbegpModel, xs: *const f32, m: c_int, z: *const f32, s: c_int, jitter: f64, samples: *mut f32,
+        argmin: *mut c_int, info: *mut c_int,
+    ) -> c_int {
+        hbegp_sample_posterior_f32(model, xs, m, z, s, jitter, samples, argmin, info)
     }
 }
 
@@ -451,6 +496,52 @@ impl<A: GpuScalar> SurrogateModelGpu<A> {
             panic!("hbegp_maximize_ei failed: {}", last_error());
         }
         (x, ei, nevals)
+    }
+
+    /// Joint posterior at the rows of `x` (`hbegp_predict_cov_*`): mean [m] and covariance [m, m] in the normalised y space,
+    /// cov = K** + (1e-5 + jitter) I - K*^T K^-1 K* (unclamped, exactly symmetric).  Opt-in, like the gradients.
+    pub fn predict_normalized_cov(&self, x: ArrayView2<A>, jitter: f64) -> (Array1<A>, Array2<A>) {
+        let (m, _d) = x.dim();
+        let x = x.as_standard_layout();
+        let mut mean = Array1::<A>::zeros(m);
+        let mut cov = Array2::<A>::zeros((m, m));
+        if m == 0 {
+            return (mean, cov);
+        }
+        let rc = unsafe { A::ffi_predict_cov(self.handle, x.as_ptr(), m as c_int, jitter, mean.as_mut_ptr(), cov.as_mut_ptr()) };
+        if rc != HBEGP_OK {
+            panic!("hbegp_predict_cov failed: {}", last_error());
+        }
+        (mean, cov)
+    }
+
+    /// Joint draws mean + L z_s (`hbegp_sample_posterior_*`, L = cholesky(cov) of `predict_normalized_cov`) from the caller's
+    /// standard normals `z` [S, m] (the RNG stays with the caller): the draws [S, m] in the normalised y space and each draw's
+    /// argmin (ties to the lowest index: batch Thompson sampling for a minimiser).  Err(info) when cov is not positive definite
+    /// in A (info = 1 + the failing pivot's panel column): the caller may retry with a larger jitter.
+    pub fn sample_normalized(&self, x: ArrayView2<A>, z: ArrayView2<A>, jitter: f64) -> Result<(Array2<A>, Vec<usize>), c_int> {
+        let (m, _d) = x.dim();
+        let (s, mz) = z.dim();
+        assert!(mz == m && s >= 1, "z must be [S, m] with S >= 1");
+        let x = x.as_standard_layout();
+        let z = z.as_standard_layout();
+        let mut samples = Array2::<A>::zeros((s, m));
+        let mut argmin: Vec<c_int> = vec![0; s];
+        if m == 0 {
+            return Ok((samples, Vec::new()));
+        }
+        let mut info: c_int = 0;
+        let rc = unsafe {
+            A::ffi_sample_posterior(self.handle, x.as_ptr(), m as c_int, z.as_ptr(), s as c_int, jitter, samples.as_mut_ptr(),
+                                    argmin.as_mut_ptr(), &mut info)
+        };
+        if rc == HBEGP_NOT_PD {
+            return Err(info);
+        }
+        if rc != HBEGP_OK {
+            panic!("hbegp_sample_posterior failed: {}", last_error());
+        }
+        Ok((samples, argmin.into_iter().map(|i| i as usize).collect()))
     }
 
     /// Batched `predict_confidence_bound` (gpr.rs:94-112 for every row): one device call instead of one per individual
