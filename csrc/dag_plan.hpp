@@ -2,7 +2,7 @@
 // and its dependency counters for the Cholesky + inverse-factor recursion on a range of 128-blocks, and checks it.
 // Plain C++ (no HIP): also compiled into the CPU-only tests through hbegp_debug_dag_plan().
 //
-// Recursion (same as Problem::chol_inv_rec / chol_inv_split, lml.rs:47 + the inverse of the factor lml.rs:62 needs):
+// Recursion (same as chol_inv_rec in hbegp.cpp, lml.rs:47 + the inverse of the factor lml.rs:62 needs):
 //   node N = [lo, hi), mid:   left subtree L;  T = A21 X11^T (W1,W2 -> W2[2,1]);  A22 -= T T^T (W2 -> W1, lower);
 //                             U = T X11 (W2 -> W1[2,1]);  right subtree R;  X21 = -X22 U (W2,W1 -> W2[2,1])
 // Dependencies are per 128-row block, so that the latency-bound chain of diagonal blocks runs ahead of (and beside) the

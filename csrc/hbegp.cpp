@@ -473,12 +473,83 @@ struct PhaseTimer {
   void end() { HIPCHECK(hipEventRecord(recs.back().b, s)); }
 };
 
-static int pick_tile(int tiles128) {
+// tile size of a launch, by its number of 128-tiles
+static int pick_tile(const GemmLaunch& g) {
+  int tiles128 = 0;
+  for (int i = 0; i < g.nops; ++i) tiles128 += g.op[i].c_lower ? g.op[i].mi * (g.op[i].mi + 1) / 2 : g.op[i].mi * g.op[i].nj;
   // 128-tiles only when a launch has >= 600 of them (n >= 8192): measured n=8192 15.1 -> 13.7 ms/evaluation with them,
   // n=4096 LAUUM (528 tiles) 0.44 ms with 64-tiles vs 0.77 ms with 128-tiles
   if (tiles128 >= 600) return 128;
   if (tiles128 >= 128) return 64;  // h=1024 SYRK+U (100 tiles): 58 us with 32-tiles vs 83 us with 64-tiles
   return 32;
+}
+
+// one tile-GEMM launch without a static schedule: the hardware dispatcher places the tiles
+template <typename T>
+static void gemm_adhoc(GemmLaunch& g, const int* info, hipStream_t s) {
+  g.info = info;
+  launch_gemm<T>(g, pick_tile(g), s);
+}
+
+// Cholesky + inverse of the factor of the SPD matrix in W1 (lower) on the diagonal block range [lo, hi) (units of 128), split
+// at mid: X = L^-1 -> W2 (lower), diag(L) -> ldiag (by the diagonal blocks).  The TRSM result L21 = A21 X11^T goes to `L21`:
+// W2 for the fit, where X21 overwrites it later, or a third matrix that keeps L (the joint posterior: its diagonal blocks store
+// L_kk there too).  need_x: form X21 -- always for the fit; a kept factor needs X only where an enclosing left part does, so
+// its top node skips it.  left_done: X (and diag(L)) of [lo, mid) are already in place (incremental extend).
+// gemm(g, kind) issues one launch, leaf(k) runs diagonal block k.
+template <typename T, class Gemm, class Leaf>
+static void chol_inv_rec(T* W1, T* W2, T* L21, int ld, int lo, int mid, int hi, bool left_done, bool need_x, Gemm&& gemm,
+                         Leaf&& leaf) {
+  if (hi - lo == 1) {
+    leaf(lo);
+    return;
+  }
+  if (!left_done) chol_inv_rec<T>(W1, W2, L21, ld, lo, lo + (mid - lo) / 2, mid, false, true, gemm, leaf);
+  GemmOp base{};
+  base.lda = base.ldb = base.ldc = ld;
+  {
+    // L21 = A21 * X11^T   (TRSM of potrf as a product with the explicit inverse)
+    GemmLaunch g{};
+    g.nops = 1;
+    GemmOp& op = g.op[0];
+    op = base;
+    op.A = W1; op.B = W2; op.C = L21;
+    op.ci0 = mid; op.mi = hi - mid; op.cj0 = lo; op.nj = mid - lo;
+    op.k0 = lo; op.k1 = mid; op.klim = 1; op.maskB = 1;
+    gemm(g, PhaseTimer::GEMM);
+  }
+  {
+    // A22 -= L21 L21^T (lower)   and, with need_x, U = L21 * X11 -> W1[2,1]   (independent: one launch, one static schedule).
+    // Measured alternatives at n=4096: two launches 3.71 ms/evaluation, U forked onto a second stream inside the graph
+    // 3.57 ms but 0.76 fit+predict/s in the 3-run bench (multi-branch graphs serialise badly); merged 3.38 ms, 1.10.
+    GemmLaunch g{};
+    g.nops = need_x ? 2 : 1;
+    GemmOp& syrk = g.op[0];
+    syrk = base;
+    syrk.A = L21; syrk.B = L21; syrk.C = W1;
+    syrk.ci0 = mid; syrk.cj0 = mid; syrk.mi = hi - mid; syrk.nj = hi - mid; syrk.c_lower = 1;
+    syrk.k0 = lo; syrk.k1 = mid; syrk.alpha_neg = 1; syrk.beta_one = 1;
+    GemmOp& u = g.op[1];
+    u = base;
+    u.A = L21; u.B = W2; u.C = W1;
+    u.b_kmajor = 1;
+    u.ci0 = mid; u.mi = hi - mid; u.cj0 = lo; u.nj = mid - lo;
+    u.k0 = lo; u.k1 = mid; u.klim = 2; u.maskB = 1;
+    gemm(g, PhaseTimer::GEMM);
+  }
+  chol_inv_rec<T>(W1, W2, L21, ld, mid, mid + (hi - mid) / 2, hi, false, need_x, gemm, leaf);
+  if (need_x) {
+    // X21 = -X22 * U -> W2[2,1]
+    GemmLaunch g{};
+    g.nops = 1;
+    GemmOp& op = g.op[0];
+    op = base;
+    op.A = W2; op.B = W1; op.C = W2;
+    op.b_kmajor = 1;
+    op.ci0 = mid; op.mi = hi - mid; op.cj0 = lo; op.nj = mid - lo;
+    op.k0 = mid; op.k1 = hi; op.klim = 3; op.maskA = 1; op.alpha_neg = 1;
+    gemm(g, PhaseTimer::GEMM);
+  }
 }
 
 // algorithmic flops of one op (in 128-tile units): 2*128^3 per (tile, k-tile) pair, half for pairs that only
@@ -615,8 +686,6 @@ struct Slot {
   std::vector<double> best_params;  // persistent fit kernel only: the clamped linear parameters the device evaluated the captured theta with
   int last_target = 0;  // buffer written by the most recent evaluation
   int dag_variant = 1;  // which ordering / launch size the next task-queue launch uses (Problem::DagVariant)
-  T* dag_kinv = nullptr;  // K^-1 buffer the task-queue launch writes (its X^T X tiles); null: factorisation only
-  int gemm_ord = 0;     // ordinal of the next GEMM launch inside the current evaluation (indexes the static schedules)
   unsigned long long seq = 0;  // serial number of the last evaluation handed to the device (EvalParams::seq)
   bool ctrl_cleared = false;   // the evaluation's first kernel clears dag_ctrl itself (EvalPrologue): no memset node
   bool published = false;      // the evaluation ends with publish_out_kernel: the host may spin on hOut->seq
@@ -662,8 +731,7 @@ struct Problem : ProblemBase {
   unsigned long long dag_wait_ticks_ = 200000000ull;  // bound of one dependency wait (100 MHz ticks), see init()
   size_t dag_ctrl_bytes = 0;
   double dag_gflop = 0;
-  bool dry_ = false;                        // walk the evaluation without launching (schedule construction)
-  bool adhoc_ = false;                      // GEMM launches bypass the per-evaluation schedule table
+  bool adhoc_ = false;                      // single-shot problem: no schedule table, every GEMM launch is ad hoc
   bool small_ = false;                      // np = 128, d <= 32: one evaluation = ONE launch (small_eval_kernel), everything in the LDS
   bool like_fit_ = false;                   // path selection of a fit (task queue from DAG_MIN_BLOCKS_FIT blocks on) although there is one slot
   // HBEGP_HOSTIO (default 1): an evaluation is driven through the slot's pinned blocks -- the first kernel reads the parameters
@@ -938,15 +1006,31 @@ struct Problem : ProblemBase {
         }
       }
     }
-    // build the static GEMM schedules (per device; shared by its slots) by walking one evaluation without launching
+    // the static GEMM schedules (per device; shared by its slots): eval_gemms walked with a dispatcher that records instead of
+    // launching, so that the i-th launch of an evaluation finds its schedule at index i
     scheds.resize(c->devs.size());
-    if (adhoc_) return;
-    dry_ = true;
+    if (adhoc_ || small_) return;
     for (size_t di = 0; di < c->devs.size(); ++di) {
       HIPCHECK(hipSetDevice(c->devs[di]));
-      enqueue_eval(slots[di][0], di, 0, true, nullptr);
+      Slot<T>& s = slots[di][0];
+      auto record = [&](GemmLaunch& g, int) {
+        Sched sc;
+        sc.tile = pick_tile(g);
+        std::vector<int> off;
+        std::vector<unsigned> items;
+        int nwg = 0;
+        if (build_sched(g, sc.tile, &off, &items, &nwg)) {
+          sc.nwg = nwg;
+          sc.d_off = palloc<int>(s.dev, off.size());
+          sc.d_items = palloc<unsigned>(s.dev, items.size());
+          HIPCHECK(hipMemcpyAsync(sc.d_off, off.data(), sizeof(int) * off.size(), hipMemcpyHostToDevice, s.stream));
+          HIPCHECK(hipMemcpyAsync(sc.d_items, items.data(), sizeof(unsigned) * items.size(), hipMemcpyHostToDevice, s.stream));
+          HIPCHECK(hipStreamSynchronize(s.stream));  // off / items are locals
+        }
+        scheds[di].push_back(sc);
+      };
+      eval_gemms(s, s.Kinv[0], record, [](int) {}, [] {});
     }
-    dry_ = false;
   }
   ~Problem() override { release(); }
 
@@ -976,114 +1060,55 @@ struct Problem : ProblemBase {
     yd.clear();
   }
 
-  void gemm(Slot<T>& s, size_t di, GemmLaunch& g, PhaseTimer* tm, int kind) {
-    hipStream_t stream = s.stream;
-    g.info = &s.dOut->info;
-    const int ord = s.gemm_ord++;
-    if (dry_) {
-      int tiles = 0;
-      for (int i = 0; i < g.nops; ++i) {
-        const GemmOp& op = g.op[i];
-        tiles += op.c_lower ? op.mi * (op.mi + 1) / 2 : op.mi * op.nj;
-      }
-      Sched sc;
-      sc.tile = pick_tile(tiles);
-      std::vector<int> off;
-      std::vector<unsigned> items;
-      int nwg = 0;
-      if (build_sched(g, sc.tile, &off, &items, &nwg)) {
-        sc.nwg = nwg;
-        sc.d_off = palloc<int>(s.dev, off.size());
-        sc.d_items = palloc<unsigned>(s.dev, items.size());
-        HIPCHECK(hipMemcpyAsync(sc.d_off, off.data(), sizeof(int) * off.size(), hipMemcpyHostToDevice, stream));
-        HIPCHECK(hipMemcpyAsync(sc.d_items, items.data(), sizeof(unsigned) * items.size(), hipMemcpyHostToDevice, stream));
-        HIPCHECK(hipStreamSynchronize(stream));  // off / items are locals
-      }
-      if ((int)scheds[di].size() <= ord) scheds[di].resize(ord + 1);
-      scheds[di][ord] = sc;
-      return;
-    }
-    if (adhoc_) {  // launch sequences other than the evaluation's (incremental extend): hardware dispatch, no table
-      g.sched_off = nullptr; g.sched_items = nullptr; g.sched_nwg = 0;
-      int tiles = 0;
-      for (int i = 0; i < g.nops; ++i) tiles += g.op[i].c_lower ? g.op[i].mi * (g.op[i].mi + 1) / 2 : g.op[i].mi * g.op[i].nj;
-      launch_gemm<T>(g, pick_tile(tiles), stream);
-      return;
-    }
-    const Sched& sc = scheds[di][ord];
-    g.sched_off = sc.nwg ? sc.d_off : nullptr;
-    g.sched_items = sc.nwg ? sc.d_items : nullptr;
-    g.sched_nwg = sc.nwg;
-    double gf = 0;
-    if (tm)
-      for (int i = 0; i < g.nops; ++i) gf += op_gflop(g.op[i]);
-    if (tm) tm->begin(kind, sc.tile, gf);
-    launch_gemm<T>(g, sc.tile, stream);
-    if (tm) tm->end();
-  }
-
-  // Cholesky + inverse of the factor on the diagonal block range [lo, hi) (units of 128): on return W2 holds
-  // X = L^-1 on that range (lower), ldiag the diagonal of L.
-  void chol_inv_rec(Slot<T>& s, size_t di, int lo, int hi, PhaseTimer* tm) {
-    if (hi - lo == 1) {
-      if (dry_) return;
-      if (tm) tm->begin(PhaseTimer::LEAF);
-      launch_leaf<T>(s.W1, s.W2, np, lo, s.ldiag, &s.dOut->info, s.stream, leaf_dbg_);
+  // The GEMMs of an evaluation of the launch path are issued by this dispatcher: the i-th launch by the i-th static schedule
+  // (init records them by walking eval_gemms); a single-shot problem has no table and issues them ad hoc.
+  auto scheduled(Slot<T>& s, size_t di, PhaseTimer* tm) {
+    return [this, &s, di, tm, ord = 0](GemmLaunch& g, int kind) mutable {
+      if (adhoc_) return gemm_adhoc<T>(g, &s.dOut->info, s.stream);
+      const Sched& sc = scheds[di][ord++];
+      g.info = &s.dOut->info;
+      g.sched_off = sc.nwg ? sc.d_off : nullptr;
+      g.sched_items = sc.nwg ? sc.d_items : nullptr;
+      g.sched_nwg = sc.nwg;
+      double gf = 0;
+      if (tm)
+        for (int i = 0; i < g.nops; ++i) gf += op_gflop(g.op[i]);
+      if (tm) tm->begin(kind, sc.tile, gf);
+      launch_gemm<T>(g, sc.tile, s.stream);
       if (tm) tm->end();
-      return;
-    }
-    chol_inv_split(s, di, lo, lo + (hi - lo) / 2, hi, tm, false);
+    };
   }
 
-  // One node of the recursion with an explicit split point.  left_done: X (and L's diagonal) of [lo, mid) are already in
-  // place (incremental extend), only the border and the right part are computed.
-  void chol_inv_split(Slot<T>& s, size_t di, int lo, int mid, int hi, PhaseTimer* tm, bool left_done) {
-    if (!left_done) chol_inv_rec(s, di, lo, mid, tm);
-    GemmOp base{};
-    base.lda = base.ldb = base.ldc = np;
-    {
-      // T = A21 * X11^T  -> W2[2,1]      (TRSM of potrf as a product with the explicit inverse; X21 overwrites it later)
+  // the diagonal-block step of the fit's chol_inv_rec: X_kk -> W2, diag(L_kk) -> ldiag
+  auto leaf_step(Slot<T>& s, PhaseTimer* tm) {
+    return [this, &s, tm](int k) {
+      if (tm) tm->begin(PhaseTimer::LEAF);
+      launch_leaf<T>(s.W1, s.W2, np, k, s.ldiag, &s.dOut->info, s.stream, leaf_dbg_);
+      if (tm) tm->end();
+    };
+  }
+
+  // The GEMM launches of one evaluation of the launch path in order, and what runs between them: the factorisation
+  // (chol_inv_rec; the task queue, launched before, does it instead), `alpha`, then K^-1 = X^T X.  Walked once with a recording
+  // dispatcher to build the schedule table, then with the scheduled one for every evaluation.
+  // (round 1: a right-looking sweep over 512- / 1024-wide big blocks in front of the recursion -- 3.55 vs 3.43 ms per evaluation at
+  // n = 4096, removed in round 5)
+  template <class Gemm, class Leaf, class Alpha>
+  void eval_gemms(Slot<T>& s, T* Kinv, Gemm&& gemm, Leaf&& leaf, Alpha&& alpha) {
+    const int nb = np / NB;
+    if (!dag_) chol_inv_rec<T>(s.W1, s.W2, s.W2, np, 0, nb / 2, nb, false, true, gemm, leaf);
+    alpha();
+    if (!(dag_ && dag_lauum_)) {
+      // K^-1 = X^T X (lower)  [LAUUM]   (task-queue path: tiles of the same queue, dag_plan.hpp build_lauum)
       GemmLaunch g{};
       g.nops = 1;
       GemmOp& op = g.op[0];
-      op = base;
-      op.A = s.W1; op.B = s.W2; op.C = s.W2;
-      op.a_kmajor = 0; op.b_kmajor = 0;
-      op.ci0 = mid; op.mi = hi - mid; op.cj0 = lo; op.nj = mid - lo;
-      op.k0 = lo; op.k1 = mid; op.klim = 1; op.maskB = 1;
-      gemm(s, di, g, tm, PhaseTimer::GEMM);
-    }
-    {
-      // A22 -= T T^T (lower)   and   U = T * X11 -> W1[2,1]   (independent: one launch, one static schedule).
-      // Measured alternatives at n=4096: two launches 3.71 ms/evaluation, U forked onto a second stream inside the graph
-      // 3.57 ms but 0.76 fit+predict/s in the 3-run bench (multi-branch graphs serialise badly); merged 3.38 ms, 1.10.
-      GemmLaunch g{};
-      g.nops = 2;
-      GemmOp& syrk = g.op[0];
-      syrk = base;
-      syrk.A = s.W2; syrk.B = s.W2; syrk.C = s.W1;
-      syrk.ci0 = mid; syrk.cj0 = mid; syrk.mi = hi - mid; syrk.nj = hi - mid; syrk.c_lower = 1;
-      syrk.k0 = lo; syrk.k1 = mid; syrk.alpha_neg = 1; syrk.beta_one = 1;
-      GemmOp& u = g.op[1];
-      u = base;
-      u.A = s.W2; u.B = s.W2; u.C = s.W1;
-      u.a_kmajor = 0; u.b_kmajor = 1;
-      u.ci0 = mid; u.mi = hi - mid; u.cj0 = lo; u.nj = mid - lo;
-      u.k0 = lo; u.k1 = mid; u.klim = 2; u.maskB = 1;
-      gemm(s, di, g, tm, PhaseTimer::GEMM);
-    }
-    chol_inv_rec(s, di, mid, hi, tm);
-    {
-      // X21 = -X22 * U -> W2[2,1]
-      GemmLaunch g{};
-      g.nops = 1;
-      GemmOp& op = g.op[0];
-      op = base;
-      op.A = s.W2; op.B = s.W1; op.C = s.W2;
-      op.a_kmajor = 0; op.b_kmajor = 1;
-      op.ci0 = mid; op.mi = hi - mid; op.cj0 = lo; op.nj = mid - lo;
-      op.k0 = mid; op.k1 = hi; op.klim = 3; op.maskA = 1; op.alpha_neg = 1;
-      gemm(s, di, g, tm, PhaseTimer::GEMM);
+      op.lda = op.ldb = op.ldc = np;
+      op.A = s.W2; op.B = s.W2; op.C = Kinv;
+      op.a_kmajor = 1; op.b_kmajor = 1;
+      op.ci0 = 0; op.cj0 = 0; op.mi = nb; op.nj = nb; op.c_lower = 1;
+      op.k0 = 0; op.k1 = nb; op.klim = 4; op.maskA = 1; op.maskB = 1;
+      gemm(g, PhaseTimer::LAUUM);
     }
   }
 
@@ -1105,33 +1130,23 @@ struct Problem : ProblemBase {
     (void)hipGetLastError();
   }
 
-  // Top of the factorisation.  Above `big` (in 128-blocks) the binary recursion would issue a chain of mid-size,
-  // poorly filled launches; instead the big blocks are swept right-looking (one TRSM and one SYRK per big block, each
-  // covering everything below / behind it) and the off-diagonal blocks of X = L^-1 are formed afterwards level by level,
-  // all nodes of a level in one launch (they are independent: TRTRI has no dependency along the diagonal).
-  void chol_inv(Slot<T>& s, size_t di, int nb, PhaseTimer* tm) {
-    if (dag_ && !adhoc_) {
-      // the whole recursion in ONE persistent launch: workgroups pull diagonal-block and tile tasks from an ordered queue
-      if (dry_) return;
-      if (!s.ctrl_cleared) HIPCHECK(hipMemsetAsync(s.dag_ctrl, 0, dag_ctrl_bytes, s.stream));
-      s.ctrl_cleared = false;
-      DagLaunch g{};
-      const DagVariant& var = dag_var[s.dag_variant];
-      g.tasks = var.tasks[di]; g.ntasks = dag_ntasks; g.ctrl = s.dag_ctrl;
-      g.W1 = s.W1; g.W2 = s.W2; g.ld = np; g.ldiag = s.ldiag; g.info = &s.dOut->info;
-      g.W3 = s.W3;
-      g.Kinv = dag_lauum_ ? s.dag_kinv : nullptr;
-      g.trace = s.dag_trace;
-      g.wait_ticks = dag_wait_ticks_;
-      g.leaf_dbg = leaf_dbg_;
-      if (tm) tm->begin(PhaseTimer::DAG, 0, g.Kinv ? dag_gflop : dag_gflop - dag_gflop_lauum);
-      launch_dag<T>(g, var.nwg, s.stream);
-      if (tm) tm->end();
-      return;
-    }
-    // (round 1: a right-looking sweep over 512- / 1024-wide big blocks in front of the recursion -- 3.55 vs 3.43 ms per evaluation at
-    // n = 4096, removed in round 5)
-    chol_inv_rec(s, di, 0, nb, tm);
+  // The factorisation as ONE persistent launch of the task queue: workgroups pull diagonal-block and tile tasks from an ordered
+  // queue.  With dag_lauum_ its tiles of K^-1 = X^T X go to Kinv (null: factorisation only).
+  void launch_queue(Slot<T>& s, size_t di, T* Kinv, PhaseTimer* tm) {
+    if (!s.ctrl_cleared) HIPCHECK(hipMemsetAsync(s.dag_ctrl, 0, dag_ctrl_bytes, s.stream));
+    s.ctrl_cleared = false;
+    DagLaunch g{};
+    const DagVariant& var = dag_var[s.dag_variant];
+    g.tasks = var.tasks[di]; g.ntasks = dag_ntasks; g.ctrl = s.dag_ctrl;
+    g.W1 = s.W1; g.W2 = s.W2; g.ld = np; g.ldiag = s.ldiag; g.info = &s.dOut->info;
+    g.W3 = s.W3;
+    g.Kinv = dag_lauum_ ? Kinv : nullptr;
+    g.trace = s.dag_trace;
+    g.wait_ticks = dag_wait_ticks_;
+    g.leaf_dbg = leaf_dbg_;
+    if (tm) tm->begin(PhaseTimer::DAG, 0, g.Kinv ? dag_gflop : dag_gflop - dag_gflop_lauum);
+    launch_dag<T>(g, var.nwg, s.stream);
+    if (tm) tm->end();
   }
 
   void small_eval(Slot<T>& s, size_t di, int target, int mode) {
@@ -1146,11 +1161,8 @@ struct Problem : ProblemBase {
   }
 
   void enqueue_eval(Slot<T>& s, size_t di, int target, bool want_grad, PhaseTimer* tm) {
-    const int nb = np / NB;
-    s.gemm_ord = 0;
     const int* info = &s.dOut->info;
     if (small_) {
-      if (dry_) return;
       if (tm) tm->begin(PhaseTimer::LEAF);
       small_eval(s, di, target, 1 | 2 | (want_grad ? 4 : 0));
       if (tm) tm->end();
@@ -1158,45 +1170,29 @@ struct Problem : ProblemBase {
       return;
     }
     const bool hostio = eval_published();
-    if (!dry_) {
-      if (hostio) {
-        EvalPrologue pro;
-        pro.dP = s.dP; pro.out = s.dOut;
-        if (dag_ && !adhoc_) {
-          pro.ctrl = s.dag_ctrl; pro.ctrl_words = (int)(dag_ctrl_bytes / sizeof(int));
-          s.ctrl_cleared = true;
-        }
-        if (tm) tm->begin(PhaseTimer::KMAT);
-        launch_kmat<T>(Xd[di], n, d, np, nu2, s.hP, s.W1, info, s.stream, &pro);
-        if (tm) tm->end();
-      } else {
-        HIPCHECK(hipMemcpyAsync(s.dP, s.hP, sizeof(EvalParams), hipMemcpyHostToDevice, s.stream));
-        launch_reset_out(s.dOut, s.stream);
-        if (tm) tm->begin(PhaseTimer::KMAT);
-        launch_kmat<T>(Xd[di], n, d, np, nu2, s.dP, s.W1, info, s.stream);
-        if (tm) tm->end();
+    if (hostio) {
+      EvalPrologue pro;
+      pro.dP = s.dP; pro.out = s.dOut;
+      if (dag_) {
+        pro.ctrl = s.dag_ctrl; pro.ctrl_words = (int)(dag_ctrl_bytes / sizeof(int));
+        s.ctrl_cleared = true;
       }
+      if (tm) tm->begin(PhaseTimer::KMAT);
+      launch_kmat<T>(Xd[di], n, d, np, nu2, s.hP, s.W1, info, s.stream, &pro);
+      if (tm) tm->end();
+    } else {
+      HIPCHECK(hipMemcpyAsync(s.dP, s.hP, sizeof(EvalParams), hipMemcpyHostToDevice, s.stream));
+      launch_reset_out(s.dOut, s.stream);
+      if (tm) tm->begin(PhaseTimer::KMAT);
+      launch_kmat<T>(Xd[di], n, d, np, nu2, s.dP, s.W1, info, s.stream);
+      if (tm) tm->end();
     }
-    s.dag_kinv = s.Kinv[target];
-    chol_inv(s, di, nb, tm);
-    if (!dry_) {
+    if (dag_) launch_queue(s, di, s.Kinv[target], tm);
+    eval_gemms(s, s.Kinv[target], scheduled(s, di, tm), leaf_step(s, tm), [&] {
       if (tm) tm->begin(PhaseTimer::ALPHA);
       launch_alpha_lml<T>(s.W2, np, n, yd[di], s.ldiag, s.wbuf, s.part_t, s.alpha[target], s.dOut, info, s.stream, hostio ? s.tickets : nullptr);
       if (tm) tm->end();
-    }
-    if (!(dag_ && dag_lauum_ && !adhoc_)) {
-      // K^-1 = X^T X (lower)  [LAUUM]   (task-queue path: tiles of the same queue, dag_plan.hpp build_lauum)
-      GemmLaunch g{};
-      g.nops = 1;
-      GemmOp& op = g.op[0];
-      op.lda = op.ldb = op.ldc = np;
-      op.A = s.W2; op.B = s.W2; op.C = s.Kinv[target];
-      op.a_kmajor = 1; op.b_kmajor = 1;
-      op.ci0 = 0; op.cj0 = 0; op.mi = nb; op.nj = nb; op.c_lower = 1;
-      op.k0 = 0; op.k1 = nb; op.klim = 4; op.maskA = 1; op.maskB = 1;
-      gemm(s, di, g, tm, PhaseTimer::LAUUM);
-    }
-    if (dry_) return;
+    });
     bool fuse_grad = false;
     if (want_grad) {
       if (tm) tm->begin(PhaseTimer::GRAD);
@@ -1267,11 +1263,9 @@ struct Problem : ProblemBase {
   int factor_only(size_t di, int si) {
     Slot<T>& s = slots[di][si];
     HIPCHECK(hipSetDevice(s.dev));
-    s.gemm_ord = 0;
     s.dag_variant = variant_now(di);
     HIPCHECK(hipMemcpyAsync(s.dP, s.hP, sizeof(EvalParams), hipMemcpyHostToDevice, s.stream));
     launch_reset_out(s.dOut, s.stream);
-    s.dag_kinv = nullptr;  // the captured K^-1 stays as it is
     if (small_) {
       small_eval(s, di, 0, 0);  // factor + inverse factor only: alpha and K^-1 of the captured evaluation stay as they are
       CHECK_LAUNCHES();
@@ -1279,7 +1273,10 @@ struct Problem : ProblemBase {
       return s.hOut->info != 0 ? HBEGP_NOT_PD : HBEGP_OK;
     }
     launch_kmat<T>(Xd[di], n, d, np, nu2, s.dP, s.W1, &s.dOut->info, s.stream);
-    chol_inv(s, di, np / NB, nullptr);
+    // the captured K^-1 stays as it is; the recursion's launches are the first ones of eval_gemms, whose schedules they take
+    const int nb = np / NB;
+    if (dag_) launch_queue(s, di, nullptr, nullptr);
+    else chol_inv_rec<T>(s.W1, s.W2, s.W2, np, 0, nb / 2, nb, false, true, scheduled(s, di, nullptr), leaf_step(s, nullptr));
     CHECK_LAUNCHES();
     HIPCHECK(hipMemcpyAsync(s.hOut, s.dOut, sizeof(EvalOut), hipMemcpyDeviceToHost, s.stream));
     HIPCHECK(hipStreamSynchronize(s.stream));
@@ -1318,42 +1315,36 @@ struct Problem : ProblemBase {
     HIPCHECK(hipMemcpy2DAsync(s.Kinv[0], sizeof(T) * np, pKinv, sizeof(T) * pnp, sizeof(T) * w, w, hipMemcpyDeviceToDevice, s.stream));
     HIPCHECK(hipMemcpyAsync(s.ldiag, pldiag, sizeof(T) * w, hipMemcpyDeviceToDevice, s.stream));
     launch_kmat<T>(Xd[di], n, d, np, nu2, s.dP, s.W1, info, s.stream);
-    const bool was_adhoc = adhoc_;
-    adhoc_ = true;
-    try {
-      chol_inv_split(s, di, 0, q0, nb, nullptr, true);
-      launch_alpha_lml<T>(s.W2, np, n, yd[di], s.ldiag, s.wbuf, s.part_t, s.alpha[0], s.dOut, info, s.stream);
-      if (pnp / NB > q0) {
-        // the prior's K^-1 also holds X^T X contributions of its own trailing (partial) block, which is being replaced:
-        // take them out of the kept block first
-        GemmLaunch gf{};
-        gf.nops = 1;
-        GemmOp& fix = gf.op[0];
-        fix.A = pXinv; fix.B = pXinv; fix.C = s.Kinv[0];
-        fix.lda = fix.ldb = pnp; fix.ldc = np;
-        fix.a_kmajor = 1; fix.b_kmajor = 1;
-        fix.mi = fix.nj = q0; fix.c_lower = 1;
-        fix.k0 = q0; fix.k1 = pnp / NB; fix.alpha_neg = 1; fix.beta_one = 1;
-        gemm(s, di, gf, nullptr, PhaseTimer::LAUUM);
-      }
-      GemmLaunch g{};
-      GemmOp base{};
-      base.lda = base.ldb = base.ldc = np;
-      base.A = s.W2; base.B = s.W2; base.C = s.Kinv[0];
-      base.a_kmajor = 1; base.b_kmajor = 1;
-      base.k0 = q0; base.k1 = nb; base.maskA = 1; base.maskB = 1;
-      GemmOp& keep = g.op[g.nops++];   // kept block: += X21^T X21
-      keep = base; keep.mi = keep.nj = q0; keep.c_lower = 1; keep.beta_one = 1;
-      GemmOp& rect = g.op[g.nops++];   // new rows x kept columns: X22^T X21 (k >= i)
-      rect = base; rect.ci0 = q0; rect.mi = nb - q0; rect.nj = q0; rect.klim = 4;
-      GemmOp& tri = g.op[g.nops++];    // new rows x new columns (lower)
-      tri = base; tri.ci0 = tri.cj0 = q0; tri.mi = tri.nj = nb - q0; tri.c_lower = 1; tri.klim = 4;
-      gemm(s, di, g, nullptr, PhaseTimer::LAUUM);
-    } catch (...) {
-      adhoc_ = was_adhoc;
-      throw;
+    // a launch sequence other than the evaluation's: every GEMM ad hoc
+    chol_inv_rec<T>(s.W1, s.W2, s.W2, np, 0, q0, nb, true, true, [&](GemmLaunch& g, int) { gemm_adhoc<T>(g, info, s.stream); },
+                    leaf_step(s, nullptr));
+    launch_alpha_lml<T>(s.W2, np, n, yd[di], s.ldiag, s.wbuf, s.part_t, s.alpha[0], s.dOut, info, s.stream);
+    if (pnp / NB > q0) {
+      // the prior's K^-1 also holds X^T X contributions of its own trailing (partial) block, which is being replaced:
+      // take them out of the kept block first
+      GemmLaunch gf{};
+      gf.nops = 1;
+      GemmOp& fix = gf.op[0];
+      fix.A = pXinv; fix.B = pXinv; fix.C = s.Kinv[0];
+      fix.lda = fix.ldb = pnp; fix.ldc = np;
+      fix.a_kmajor = 1; fix.b_kmajor = 1;
+      fix.mi = fix.nj = q0; fix.c_lower = 1;
+      fix.k0 = q0; fix.k1 = pnp / NB; fix.alpha_neg = 1; fix.beta_one = 1;
+      gemm_adhoc<T>(gf, info, s.stream);
     }
-    adhoc_ = was_adhoc;
+    GemmLaunch g{};
+    GemmOp base{};
+    base.lda = base.ldb = base.ldc = np;
+    base.A = s.W2; base.B = s.W2; base.C = s.Kinv[0];
+    base.a_kmajor = 1; base.b_kmajor = 1;
+    base.k0 = q0; base.k1 = nb; base.maskA = 1; base.maskB = 1;
+    GemmOp& keep = g.op[g.nops++];   // kept block: += X21^T X21
+    keep = base; keep.mi = keep.nj = q0; keep.c_lower = 1; keep.beta_one = 1;
+    GemmOp& rect = g.op[g.nops++];   // new rows x kept columns: X22^T X21 (k >= i)
+    rect = base; rect.ci0 = q0; rect.mi = nb - q0; rect.nj = q0; rect.klim = 4;
+    GemmOp& tri = g.op[g.nops++];    // new rows x new columns (lower)
+    tri = base; tri.ci0 = tri.cj0 = q0; tri.mi = tri.nj = nb - q0; tri.c_lower = 1; tri.klim = 4;
+    gemm_adhoc<T>(g, info, s.stream);
     CHECK_LAUNCHES();
     HIPCHECK(hipMemcpyAsync(s.hOut, s.dOut, sizeof(EvalOut), hipMemcpyDeviceToHost, s.stream));
     HIPCHECK(hipStreamSynchronize(s.stream));
@@ -1764,14 +1755,13 @@ static void predict_batched_launches(hbegp_model* m, int cnt, int mp, bool want_
     // result is at least as close to the exact value as the K^-1 form.
     GemmLaunch g{};
     g.nops = 1;
-    g.info = &m->dOut->info;
     GemmOp& op = g.op[0];
     op.lda = m->np; op.ldb = m->np; op.ldc = m->np;
     op.ci0 = 0; op.cj0 = 0; op.mi = mp / NB; op.nj = m->np / NB;
     op.k0 = 0; op.k1 = m->np / NB;
     op.A = m->Ks; op.B = m->Xinv; op.C = m->Q;
     op.klim = 1; op.maskB = 1;
-    launch_gemm<T>(g, pick_tile(op.mi * op.nj), s);
+    gemm_adhoc<T>(g, &m->dOut->info, s);
     launch_pred_var<T>(static_cast<T*>(m->Q), static_cast<T*>(m->Q), cnt, m->np, m->dP, static_cast<T*>(m->var), m->dOut, s);
   }
   CHECK_LAUNCHES();
@@ -1863,14 +1853,13 @@ static int model_predict_grad(hbegp_model* m, const T* Xs, int cnt, T* mean, T* 
                          static_cast<T*>(m->G), s);
     GemmLaunch g{};
     g.nops = 1;
-    g.info = &m->dOut->info;
     GemmOp& op = g.op[0];
     op.lda = m->np; op.ldb = m->np; op.ldc = m->np;
     op.ci0 = 0; op.cj0 = 0; op.mi = m->d * mp / NB; op.nj = m->np / NB;
     op.k0 = 0; op.k1 = m->np / NB;
     op.A = m->G; op.B = m->Xinv; op.C = m->W;
     op.klim = 1; op.maskB = 1;  // X = L^-1 lower, as for Q
-    launch_gemm<T>(g, pick_tile(op.mi * op.nj), s);
+    gemm_adhoc<T>(g, &m->dOut->info, s);
     launch_pred_dvar<T>(static_cast<T*>(m->W), static_cast<T*>(m->Q), cnt, mp, m->np, m->d, static_cast<T*>(m->var),
                         static_cast<T*>(m->dvar), s);
   }
@@ -1910,72 +1899,6 @@ struct CallScratch {
     for (auto& h : held) g_pool.put(dev, h.first, h.second);
   }
 };
-
-// one tile-GEMM launch without a static schedule (the hardware dispatcher), like the batched predict's
-template <typename T>
-static void gemm_launch(GemmLaunch& g, const int* info, hipStream_t s) {
-  g.info = info;
-  int tiles = 0;
-  for (int i = 0; i < g.nops; ++i) tiles += g.op[i].c_lower ? g.op[i].mi * (g.op[i].mi + 1) / 2 : g.op[i].mi * g.op[i].nj;
-  launch_gemm<T>(g, pick_tile(tiles), s);
-}
-
-// Cholesky of the SPD matrix in W1 (lower; blocks [lo, hi) of NB) that KEEPS the factor: L -> W3, X = L^-1 -> W2 where a later
-// step needs it (need_x), diag(L) -> ldiag.  The recursion of the fit (Problem::chol_inv_split) with two changes: its TRSM
-// result L21 = A21 X11^T goes to W3 and stays there (the fit overwrites it with X21), and the diagonal blocks store L_kk
-// (leaf_keep_kernel).  X of a right part is formed only when an enclosing left part needs it: the top node skips X21.
-template <typename T>
-static void chol_keep_rec(T* W1, T* W2, T* W3, T* ldiag, int ld, int lo, int hi, bool need_x, int* info, hipStream_t s) {
-  if (hi - lo == 1) {
-    launch_leaf_keep<T>(W1, W2, W3, ld, lo, ldiag, info, s);
-    return;
-  }
-  const int mid = lo + (hi - lo) / 2;
-  chol_keep_rec<T>(W1, W2, W3, ldiag, ld, lo, mid, true, info, s);
-  GemmOp base{};
-  base.lda = base.ldb = base.ldc = ld;
-  {
-    // L21 = A21 X11^T -> W3[2,1]
-    GemmLaunch g{};
-    g.nops = 1;
-    GemmOp& op = g.op[0];
-    op = base;
-    op.A = W1; op.B = W2; op.C = W3;
-    op.ci0 = mid; op.mi = hi - mid; op.cj0 = lo; op.nj = mid - lo;
-    op.k0 = lo; op.k1 = mid; op.klim = 1; op.maskB = 1;
-    gemm_launch<T>(g, info, s);
-  }
-  {
-    // A22 -= L21 L21^T (lower)   and, where X is needed, U = L21 X11 -> W1[2,1]   (one launch)
-    GemmLaunch g{};
-    g.nops = need_x ? 2 : 1;
-    GemmOp& syrk = g.op[0];
-    syrk = base;
-    syrk.A = W3; syrk.B = W3; syrk.C = W1;
-    syrk.ci0 = mid; syrk.cj0 = mid; syrk.mi = hi - mid; syrk.nj = hi - mid; syrk.c_lower = 1;
-    syrk.k0 = lo; syrk.k1 = mid; syrk.alpha_neg = 1; syrk.beta_one = 1;
-    GemmOp& u = g.op[1];
-    u = base;
-    u.A = W3; u.B = W2; u.C = W1;
-    u.b_kmajor = 1;
-    u.ci0 = mid; u.mi = hi - mid; u.cj0 = lo; u.nj = mid - lo;
-    u.k0 = lo; u.k1 = mid; u.klim = 2; u.maskB = 1;
-    gemm_launch<T>(g, info, s);
-  }
-  chol_keep_rec<T>(W1, W2, W3, ldiag, ld, mid, hi, need_x, info, s);
-  if (need_x) {
-    // X21 = -X22 U -> W2[2,1]
-    GemmLaunch g{};
-    g.nops = 1;
-    GemmOp& op = g.op[0];
-    op = base;
-    op.A = W2; op.B = W1; op.C = W2;
-    op.b_kmajor = 1;
-    op.ci0 = mid; op.mi = hi - mid; op.cj0 = lo; op.nj = mid - lo;
-    op.k0 = mid; op.k1 = hi; op.klim = 3; op.maskA = 1; op.alpha_neg = 1;
-    gemm_launch<T>(g, info, s);
-  }
-}
 
 // phase times of the calling thread's last sampling call (hbegp_debug_posterior_phases): Q, Sigma, factor, draws in ms
 static thread_local bool t_time_posterior = false;
@@ -2026,7 +1949,7 @@ static int model_posterior(hbegp_model* m, const T* Xs, int cnt, double jitter, 
     op.mi = mp / NB; op.nj = mp / NB; op.c_lower = 1;
     op.k0 = 0; op.k1 = m->np / NB;
     op.alpha_neg = 1; op.beta_one = 1;
-    gemm_launch<T>(g, info, s);
+    gemm_adhoc<T>(g, info, s);
   }
   if (cov) {
     launch_symmetrize<T>(W1, mp, s);
@@ -2044,7 +1967,10 @@ static int model_posterior(hbegp_model* m, const T* Xs, int cnt, double jitter, 
   // upper 16 x 16 blocks of X's diagonal blocks) must be zero in memory, and a recycled block holds its earlier owner's numbers
   HIPCHECK(hipMemsetAsync(W2, 0, sizeof(T) * nn, s));
   HIPCHECK(hipMemsetAsync(W3, 0, sizeof(T) * nn, s));
-  chol_keep_rec<T>(W1, W2, W3, ld, mp, 0, mp / NB, false, info, s);
+  // the fit's recursion with L kept: L21 -> W3, where the diagonal blocks store L_kk too (leaf_keep_kernel)
+  const int nbm = mp / NB;
+  chol_inv_rec<T>(W1, W2, W3, mp, 0, nbm / 2, nbm, false, false, [&](GemmLaunch& g, int) { gemm_adhoc<T>(g, info, s); },
+                  [&](int k) { launch_leaf_keep<T>(W1, W2, W3, mp, k, ld, info, s); });
   if (timed) HIPCHECK(hipEventRecord(ev[3], s));
   T* Z = static_cast<T*>(ws.get(sizeof(T) * (size_t)Sp * mp));
   T* Y = static_cast<T*>(ws.get(sizeof(T) * (size_t)Sp * mp));
@@ -2060,7 +1986,7 @@ static int model_posterior(hbegp_model* m, const T* Xs, int cnt, double jitter, 
     op.lda = mp; op.ldb = mp; op.ldc = mp;
     op.mi = Sp / NB; op.nj = mp / NB;
     op.k0 = 0; op.k1 = mp / NB; op.klim = 1; op.maskB = 1;
-    gemm_launch<T>(g, info, s);
+    gemm_adhoc<T>(g, info, s);
   }
   launch_sample_epilogue<T>(Y, mp, static_cast<T*>(m->mean), cnt, S, samples != nullptr, amin, info, s);
   if (timed) HIPCHECK(hipEventRecord(ev[4], s));
