@@ -206,6 +206,13 @@ template <typename T>
 void launch_leaf_keep(T* W1, T* W2, T* W3, int ld, int blk, T* ldiag, int* info, hipStream_t s);
 template <typename T>
 void launch_sample_epilogue(T* Y, int ld, const T* mean, int m, int S, int store, int* amin, const int* info, hipStream_t s);
+// greedy batch selection by EI (hbegp_select_batch; batch_select_kernel: one workgroup, the whole k-step loop): Sig the symmetrised
+// Sigma [ld][ld] at jitter 0, mean[m] the posterior mean, P->noise the fantasy observations' noise s2, use_lie ? lie : mu_j the
+// fantasy.  Workspace (fp64): C [k][ld], v [ld], mu [ld]; picked [ld] ints.  Out: idx[k], ei[k], and mean_out / var_out [m] after
+// the k conditionings (var clamped at 0).  1 <= k <= m.
+template <typename T>
+void launch_batch_select(const T* Sig, int ld, const T* mean, int m, int k, const EvalParams* P, double fmin, int use_lie, double lie,
+                         double* C, double* v, double* mu, int* picked, int* idx, double* ei, T* mean_out, T* var_out, hipStream_t s);
 
 // predict for m <= PRED_SMALL_MAX candidates without the 128-row padding: reads L^-1 once (row dots against the m
 // cross-kernel vectors).  Ks: [PRED_SMALL_MAX][np] scratch, pmean: [(np+255)/256][PRED_SMALL_MAX], w: [n][PRED_SMALL_MAX].

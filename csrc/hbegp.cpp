@@ -1904,6 +1904,34 @@ struct CallScratch {
 static thread_local bool t_time_posterior = false;
 static thread_local double t_posterior_ms[4] = {0, 0, 0, 0};
 
+// Sigma = K** + noise I - Q Q^T at the candidates into W (lower tiles; m_p x m_p, kmat's identity padding): the candidates'
+// upload, the batched predict's launches (Kstar, the mean, Q = Kstar X^T; the variance too, unused), then kmat_kernel over
+// the candidates with a parameter block whose noise is *noise and one tile GEMM.  `noise` is copied from the caller's variable:
+// it has to outlive the stream work.  ev_q (may be null) is recorded behind Q.
+template <typename T>
+static void posterior_sigma(hbegp_model* m, const T* Xs, int cnt, int mp, const double* noise, T* W, hipEvent_t ev_q) {
+  hipStream_t s = m->stream;
+  int* info = &m->dOut->info;
+  HIPCHECK(hipMemcpyAsync(m->Xs, Xs, sizeof(T) * (size_t)cnt * m->d, hipMemcpyHostToDevice, s));
+  predict_batched_launches<T>(m, cnt, mp, true);
+  if (ev_q) HIPCHECK(hipEventRecord(ev_q, s));
+  HIPCHECK(hipMemcpyAsync(m->dPcov, m->dP, sizeof(EvalParams), hipMemcpyDeviceToDevice, s));
+  HIPCHECK(hipMemcpyAsync(&m->dPcov->noise, noise, sizeof(double), hipMemcpyHostToDevice, s));
+  launch_kmat<T>(static_cast<T*>(m->Xs), cnt, m->d, mp, m->nu2, m->dPcov, W, info, s);
+  {
+    // Sigma -= Q Q^T (lower tiles), contraction over the training points
+    GemmLaunch g{};
+    g.nops = 1;
+    GemmOp& op = g.op[0];
+    op.A = m->Q; op.B = m->Q; op.C = W;
+    op.lda = m->np; op.ldb = m->np; op.ldc = mp;
+    op.mi = mp / NB; op.nj = mp / NB; op.c_lower = 1;
+    op.k0 = 0; op.k1 = m->np / NB;
+    op.alpha_neg = 1; op.beta_one = 1;
+    gemm_adhoc<T>(g, info, s);
+  }
+}
+
 // Sigma = K** + (1e-5 + jitter) I - Q Q^T at the candidates (Q = Kstar X^T of the batched predict), then either
 //   cov != nullptr: Sigma mirrored to the full matrix and copied out (hbegp_predict_cov), or
 //   the draws mean + L_S z_s with L_S the Cholesky factor of Sigma: Y = Z L^T (tile GEMM), then the epilogue adds the mean and
@@ -1933,24 +1961,7 @@ static int model_posterior(hbegp_model* m, const T* Xs, int cnt, double jitter, 
   if (timed)
     for (auto& e : ev) HIPCHECK(hipEventCreate(&e));
   if (timed) HIPCHECK(hipEventRecord(ev[0], s));
-  HIPCHECK(hipMemcpyAsync(m->Xs, Xs, sizeof(T) * (size_t)cnt * m->d, hipMemcpyHostToDevice, s));
-  predict_batched_launches<T>(m, cnt, mp, true);  // Kstar, the mean, Q (and the variance, unused here)
-  if (timed) HIPCHECK(hipEventRecord(ev[1], s));
-  HIPCHECK(hipMemcpyAsync(m->dPcov, m->dP, sizeof(EvalParams), hipMemcpyDeviceToDevice, s));
-  HIPCHECK(hipMemcpyAsync(&m->dPcov->noise, &noise, sizeof(double), hipMemcpyHostToDevice, s));
-  launch_kmat<T>(static_cast<T*>(m->Xs), cnt, m->d, mp, m->nu2, m->dPcov, W1, info, s);
-  {
-    // Sigma -= Q Q^T (lower tiles), contraction over the training points
-    GemmLaunch g{};
-    g.nops = 1;
-    GemmOp& op = g.op[0];
-    op.A = m->Q; op.B = m->Q; op.C = W1;
-    op.lda = m->np; op.ldb = m->np; op.ldc = mp;
-    op.mi = mp / NB; op.nj = mp / NB; op.c_lower = 1;
-    op.k0 = 0; op.k1 = m->np / NB;
-    op.alpha_neg = 1; op.beta_one = 1;
-    gemm_adhoc<T>(g, info, s);
-  }
+  posterior_sigma<T>(m, Xs, cnt, mp, &noise, W1, timed ? ev[1] : nullptr);
   if (cov) {
     launch_symmetrize<T>(W1, mp, s);
     CHECK_LAUNCHES();
@@ -2008,6 +2019,66 @@ static int model_posterior(hbegp_model* m, const T* Xs, int cnt, double jitter, 
   if (samples) HIPCHECK(hipMemcpy2DAsync(samples, sizeof(T) * cnt, Y, sizeof(T) * mp, sizeof(T) * cnt, S, hipMemcpyDeviceToHost, s));
   if (argmin) HIPCHECK(hipMemcpyAsync(argmin, amin, sizeof(int) * (size_t)S, hipMemcpyDeviceToHost, s));
   HIPCHECK(hipStreamSynchronize(s));
+  return HBEGP_OK;
+}
+
+// phase times of the calling thread's last batch selection (hbegp_debug_batch_select_phases): Sigma, select in ms
+static thread_local bool t_time_select = false;
+static thread_local double t_select_ms[2] = {0, 0};
+
+// Greedy batch selection by EI with fantasised observations (hbegp_select_batch): Sigma at jitter 0 as predict_cov builds it
+// (posterior_sigma, then mirrored), then the whole k-step loop in one launch of batch_select_kernel.  Only idx / ei (k each) and
+// the optional mean / variance after the k conditionings leave the device; the m_p^2 Sigma and the fp64 workspace
+// (C [k][m_p], v, mu; the picked flags, idx, ei and the T outputs) are borrowed for the call and go back cleared.
+template <typename T>
+static int model_select_batch(hbegp_model* m, const T* Xs, int cnt, int k, double fmin, const double* lie, int* idx, double* ei,
+                              T* mean_out, T* var_out) {
+  std::lock_guard<std::mutex> lock(m->mu);
+  HIPCHECK(hipSetDevice(m->dev));
+  const int mp = round_up(cnt, NB);
+  // everything the call borrows, counted before anything is taken: an m far beyond the device is ENOMEM, not an overflow
+  const double need = (double)sizeof(T) * ((double)mp * mp + 2.0 * (double)mp * m->np + 2.0 * mp) +
+                      8.0 * ((double)k * mp + 2.0 * mp + k) + 4.0 * ((double)mp + k);
+  if (need > 1e15) return fail(HBEGP_ENOMEM, "the batch selection over %d points needs %.3g bytes of device memory", cnt, need);
+  predict_batched_reserve<T>(m, mp);
+  if (!m->dPcov) m->dPcov = static_cast<EvalParams*>(m->palloc(sizeof(EvalParams)));
+  hipStream_t s = m->stream;
+  const double noise = 1e-5;  // jitter 0: predict_cov's Sigma, whose diagonal is hbegp_predict's variance before clamping
+  CallScratch ws{m->dev, s, {}};
+  T* W1 = static_cast<T*>(ws.get(sizeof(T) * (size_t)mp * mp));
+  double* Cw = static_cast<double*>(ws.get(sizeof(double) * ((size_t)k * mp + 2 * (size_t)mp + k)));
+  double* v = Cw + (size_t)k * mp;
+  double* mu = v + mp;
+  double* dei = mu + mp;
+  int* picked = static_cast<int*>(ws.get(sizeof(int) * ((size_t)mp + k)));
+  int* didx = picked + mp;
+  T* dmean = static_cast<T*>(ws.get(sizeof(T) * 2 * (size_t)mp));
+  T* dvar = dmean + mp;
+  hipEvent_t ev[3] = {};
+  const bool timed = t_time_select;
+  if (timed)
+    for (auto& e : ev) HIPCHECK(hipEventCreate(&e));
+  if (timed) HIPCHECK(hipEventRecord(ev[0], s));
+  posterior_sigma<T>(m, Xs, cnt, mp, &noise, W1, nullptr);
+  launch_symmetrize<T>(W1, mp, s);  // the kernel reads row j of Sigma
+  if (timed) HIPCHECK(hipEventRecord(ev[1], s));
+  launch_batch_select<T>(W1, mp, static_cast<const T*>(m->mean), cnt, k, m->dP, fmin, lie ? 1 : 0, lie ? *lie : 0.0, Cw, v, mu, picked,
+                         didx, dei, dmean, dvar, s);
+  if (timed) HIPCHECK(hipEventRecord(ev[2], s));
+  CHECK_LAUNCHES();
+  HIPCHECK(hipMemcpyAsync(idx, didx, sizeof(int) * (size_t)k, hipMemcpyDeviceToHost, s));
+  if (ei) HIPCHECK(hipMemcpyAsync(ei, dei, sizeof(double) * (size_t)k, hipMemcpyDeviceToHost, s));
+  if (mean_out) HIPCHECK(hipMemcpyAsync(mean_out, dmean, sizeof(T) * cnt, hipMemcpyDeviceToHost, s));
+  if (var_out) HIPCHECK(hipMemcpyAsync(var_out, dvar, sizeof(T) * cnt, hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
+  if (timed) {
+    for (int i = 0; i < 2; ++i) {
+      float ms = 0;
+      HIPCHECK(hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
+      t_select_ms[i] = ms;
+    }
+    for (auto& e : ev) (void)hipEventDestroy(e);
+  }
   return HBEGP_OK;
 }
 
@@ -2956,6 +3027,41 @@ int hbegp_sample_posterior_f32(hbegp_model* model, const float* Xs, int m, const
   GUARD_BEGIN
   return model_posterior<float>(model, Xs, m, jitter, nullptr, nullptr, z, S, samples, argmin, info);
   GUARD_END
+}
+}  // extern "C"
+// argument checks of hbegp_select_batch_*: everything is refused before any device call, the checks that need no model first
+template <typename T>
+static int check_select(hbegp_model* model, const T* Xs, int m, int k, double fmin, const double* lie, int* idx) {
+  if (m < 0) return fail(HBEGP_EINVAL, "m must be >= 0 (got %d)", m);
+  if (k < 0) return fail(HBEGP_EINVAL, "k must be >= 0 (got %d)", k);
+  if (k > m) return fail(HBEGP_EINVAL, "k must be <= m (got k = %d, m = %d)", k, m);
+  if (k > 0 && !idx) return fail(HBEGP_EINVAL, "idx is NULL");
+  if (!std::isfinite(fmin)) return fail(HBEGP_EINVAL, "fmin must be finite (got %g)", fmin);
+  if (lie && !std::isfinite(*lie)) return fail(HBEGP_EINVAL, "the lie must be finite (got %g)", *lie);
+  return check_posterior<T>(model, Xs, m, 0.0);
+}
+extern "C" {
+int hbegp_select_batch_f64(hbegp_model* model, const double* Xs, int m, int k, double fmin_normalized, const double* lie, int* idx,
+                           double* ei, double* mean_out, double* var_out) {
+  if (int rc = check_select<double>(model, Xs, m, k, fmin_normalized, lie, idx)) return rc;
+  if (k == 0) return HBEGP_OK;
+  GUARD_BEGIN
+  return model_select_batch<double>(model, Xs, m, k, fmin_normalized, lie, idx, ei, mean_out, var_out);
+  GUARD_END
+}
+int hbegp_select_batch_f32(hbegp_model* model, const float* Xs, int m, int k, double fmin_normalized, const double* lie, int* idx,
+                           double* ei, float* mean_out, float* var_out) {
+  if (int rc = check_select<float>(model, Xs, m, k, fmin_normalized, lie, idx)) return rc;
+  if (k == 0) return HBEGP_OK;
+  GUARD_BEGIN
+  return model_select_batch<float>(model, Xs, m, k, fmin_normalized, lie, idx, ei, mean_out, var_out);
+  GUARD_END
+}
+int hbegp_debug_batch_select_phases(int enable, double* phase_ms) {
+  if (phase_ms)
+    for (int i = 0; i < 2; ++i) phase_ms[i] = t_select_ms[i];
+  t_time_select = enable != 0;
+  return HBEGP_OK;
 }
 int hbegp_debug_posterior_phases(int enable, double* phase_ms) {
   if (phase_ms)

@@ -2063,6 +2063,119 @@ template void launch_sample_epilogue<double>(double*, int, const double*, int, i
 template void launch_sample_epilogue<float>(float*, int, const float*, int, int, int, int*, const int*, hipStream_t);
 
 // =================================================================================================================
+// greedy batch selection by expected improvement (hbegp.cpp: model_select_batch).  The whole k-step loop in ONE
+// workgroup: each pick depends on the last, and a grid would need a device-wide seam per pick.  Thread tid owns the rows
+// i = tid (mod BSEL_THREADS).  Per step t:
+//   EI of every row not yet picked (fp64, acquisition.rs:141-171), the LAST index of the maximum (Rust's max_by) through a
+//   fixed LDS tree; then the fantasy f = mu_j (kriging believer) or the lie, and the conditioning on a noisy observation f at
+//   row j: r_i = Sigma[j][i] - sum_{s<t} C[s][i] C[s][j] (ascending s), r_j = v_j - 1e-5 (the latent variance),
+//   c = r / sqrt(max(r_j, 0) + s2) -> C[t], v -= c^2, mu += c (f - mu_j) / sqrt(max(r_j, 0) + s2).
+// Sigma (symmetrised, ld x ld) is read in T, row j contiguously; C [k][ld], v, mu are fp64 global workspace, so every
+// read of C is coalesced across the threads; C[s][j] of the first BSEL_CJ steps is staged in the LDS once per step.  Global
+// values another thread wrote are read only behind a __syncthreads (workgroup-scope fence: one CU, one L1).  No atomics: the
+// same inputs give the same bits, and the first t picks do not depend on k.
+// =================================================================================================================
+constexpr int BSEL_THREADS = 1024;
+constexpr int BSEL_CJ = 4096;
+
+// not inlined: erfc's fp64 coefficients, hoisted out of the row loop, would take more SGPRs than the kernel has (26 spilled)
+__device__ __noinline__ double bsel_ei(double mu, double var, double fmin) {
+  const double sd = sqrt(fmax(var, 0.0));
+  if (sd <= 2.220446049250313e-16) return mu < fmin ? -(mu - fmin) : 0.0;  // ulps_eq!(std, 0.0): |std| <= f64::EPSILON
+  const double z = -(mu - fmin) / sd;
+  const double cdf = 0.5 * erfc(-z / 1.4142135623730951);
+  const double pdf = exp(-0.5 * z * z) / 2.5066282746310002;
+  return fmax(-(mu - fmin) * cdf + sd * pdf, 0.0);
+}
+
+template <typename T>
+__global__ void __launch_bounds__(BSEL_THREADS) batch_select_kernel(const T* __restrict__ Sig, int ld, const T* __restrict__ mean, int m,
+                                                                    int k, const EvalParams* __restrict__ P, double fmin0, int use_lie,
+                                                                    double lie, double* __restrict__ C, double* __restrict__ v,
+                                                                    double* __restrict__ mu, int* __restrict__ picked, int* __restrict__ idx,
+                                                                    double* __restrict__ ei, T* __restrict__ mean_out, T* __restrict__ var_out) {
+  __shared__ double sv[BSEL_THREADS];
+  __shared__ int si[BSEL_THREADS];
+  __shared__ double cj[BSEL_CJ];
+  __shared__ double sh_vj, sh_muj;
+  const int tid = threadIdx.x;
+  for (int i = tid; i < m; i += BSEL_THREADS) {
+    v[i] = (double)Sig[(size_t)i * ld + i];
+    mu[i] = (double)mean[i];
+    picked[i] = 0;
+  }
+  const double s2 = P->noise;
+  double fm = fmin0;
+  for (int t = 0; t < k; ++t) {
+    // every row not yet picked is a candidate whatever its EI: with k <= m the index found is a valid row
+    double best = 0.0;
+    int bi = -1;
+    for (int i = tid; i < m; i += BSEL_THREADS) {
+      if (picked[i]) continue;
+      const double e = bsel_ei(mu[i], v[i], fm);
+      if (bi < 0 || e >= best) { best = e; bi = i; }  // ascending i: an equal value moves to the later index
+    }
+    sv[tid] = best;
+    si[tid] = bi;
+    __syncthreads();
+#pragma unroll 1
+    for (int w = BSEL_THREADS / 2; w > 0; w >>= 1) {
+      if (tid < w) {
+        const double o = sv[tid + w];
+        const int oi = si[tid + w];
+        if (oi >= 0 && (si[tid] < 0 || o > sv[tid] || (o == sv[tid] && oi > si[tid]))) { sv[tid] = o; si[tid] = oi; }
+      }
+      __syncthreads();
+    }
+    const int j = si[0];
+    if (tid == 0) {
+      idx[t] = j;
+      ei[t] = sv[0];
+      sh_vj = v[j];
+      sh_muj = mu[j];
+    }
+    const int tc = t < BSEL_CJ ? t : BSEL_CJ;
+    for (int s = tid; s < tc; s += BSEL_THREADS) cj[s] = C[(size_t)s * ld + j];
+    __syncthreads();
+    const double vj = sh_vj, muj = sh_muj;
+    const double f = use_lie ? lie : muj;
+    const double rj = vj - 1e-5;
+    const double sd = sqrt(fmax(rj, 0.0) + s2);
+    for (int i = tid; i < m; i += BSEL_THREADS) {
+      double r = rj;
+      if (i != j) {
+        r = (double)Sig[(size_t)j * ld + i];
+        for (int s = 0; s < tc; ++s) r -= C[(size_t)s * ld + i] * cj[s];
+        for (int s = tc; s < t; ++s) r -= C[(size_t)s * ld + i] * C[(size_t)s * ld + j];
+      } else {
+        picked[i] = 1;
+      }
+      const double c = r / sd;
+      C[(size_t)t * ld + i] = c;
+      v[i] -= c * c;
+      mu[i] += c * (f - muj) / sd;
+    }
+    fm = fmin(fm, f);
+    // the next step's EI reads only this thread's own rows; its tree writes sv / si, which nobody reads before the barrier
+    // behind them, and cj, which every thread has finished reading when it reaches that step's first barrier
+  }
+  for (int i = tid; i < m; i += BSEL_THREADS) {
+    mean_out[i] = (T)mu[i];
+    var_out[i] = (T)fmax(v[i], 0.0);
+  }
+}
+template <typename T>
+void launch_batch_select(const T* Sig, int ld, const T* mean, int m, int k, const EvalParams* P, double fmin, int use_lie, double lie,
+                         double* C, double* v, double* mu, int* picked, int* idx, double* ei, T* mean_out, T* var_out, hipStream_t s) {
+  hipLaunchKernelGGL((batch_select_kernel<T>), dim3(1), dim3(BSEL_THREADS), 0, s, Sig, ld, mean, m, k, P, fmin, use_lie, lie, C, v, mu,
+                     picked, idx, ei, mean_out, var_out);
+}
+template void launch_batch_select<double>(const double*, int, const double*, int, int, const EvalParams*, double, int, double, double*,
+                                          double*, double*, int*, int*, double*, double*, double*, hipStream_t);
+template void launch_batch_select<float>(const float*, int, const float*, int, int, const EvalParams*, double, int, double, double*,
+                                         double*, double*, int*, int*, double*, float*, float*, hipStream_t);
+
+// =================================================================================================================
 // predict for a handful of candidates (m <= PRED_SMALL_MAX): the caller's acquisition and selection loops issue
 // thousands of single-point predicts per generation (acquisition.rs:46-64, minimize.rs:656-714).  The batched path pads
 // to 128 candidate rows and runs a tile GEMM over all of L^-1 (0.2 ms at n=4096 whatever m is); here L^-1 is read once,

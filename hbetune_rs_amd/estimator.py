@@ -297,6 +297,17 @@ class SurrogateModelGPR:
         samples, _ = self.fitted.sample_posterior(x, z, jitter=jitter)
         return self.y_norm.project_location_from_normalized(samples)
 
+    # Greedy batch selection by EI (opt-in; nothing the estimator suggests by default uses it).
+    def select_batch_a(self, x, k, fmin, lie=None):
+        """k rows of x [m, d] picked greedily by EI with fantasised observations (FittedKernel.select_batch).  fmin and the
+        constant lie are in y units and projected like predict_mean_ei_a projects fmin.  Returns (idx[k], the projected means of
+        the picks under the model before any fantasy, ei[k] in the normalised space)."""
+        x = np.asarray(x, dtype=self.dtype)
+        lie_n = None if lie is None else self._fmin_normalized(lie)
+        idx, ei, _, _ = self.fitted.select_batch(x, k, self._fmin_normalized(fmin), lie=lie_n)
+        means, _, _ = self.fitted.predict(x[idx], want_variance=False) if len(idx) else (np.zeros(0, self.dtype), None, 0)
+        return idx, self.y_norm.project_location_from_normalized(means), ei
+
     # Batched forms of the scalar trait methods (SURVEY.md 8f rank 1: the acquisition loops call these once per generation
     # instead of m single-point predicts, each of which reads all of K^-1).
     def predict_confidence_bound_a(self, x, cb):
@@ -360,6 +371,18 @@ def acquire_by_thompson(candidates, model, k, rng, jitter=0.0):
     z = rng.standard_normal((int(k), c.shape[0])).astype(model.dtype)
     _, argmin = model.fitted.sample_posterior(c, z, jitter=jitter, want_samples=False)
     return np.asarray(argmin, dtype=np.int64)
+
+
+def acquire_by_batch_ei(candidates, model, k, fmin, lie=None):
+    """Deterministic batch acquisition over a candidate set [m, n_features]: k distinct candidates picked greedily by EI, the
+    surrogate conditioned after every pick on a fantasy observation there -- its predicted mean (kriging believer) or the
+    constant `lie` (constant liar, y units) -- so that later picks move away from earlier ones.  One device call; k = 1 is
+    find_best_candidate_by_ei.  Returns (idx[k], projected means of the picks, ei[k]).  Opt-in: the twin of
+    acquire_by_thompson."""
+    c = np.asarray(candidates, dtype=model.dtype)
+    if c.ndim != 2:
+        raise ValueError("candidates must be [m, n_features]")
+    return model.select_batch_a(c, int(k), fmin, lie=lie)
 
 
 class FitnessOperator:

@@ -352,6 +352,25 @@ class FittedKernel:
                       argmin.ctypes.data_as(C.POINTER(C.c_int)), None))
         return samples, argmin
 
+    def select_batch(self, x, k, fmin_normalized, lie=None):
+        """Greedy batch selection by EI with fantasised observations (hbegp_select_batch_*), in the normalised y space: k rows of
+        x picked one after another, each by the largest EI (ties to the last index), the posterior then conditioned on a noisy
+        observation at the pick -- its mean (kriging believer, lie=None) or `lie` (constant liar).  Returns (idx[k] int64, ei[k],
+        mean[m], var[m]): mean / var after the k conditionings, var clamped at 0 like predict()."""
+        lib = _lib.load()
+        x = _lib.as_c(np.atleast_2d(x), self.dtype)
+        assert x.ndim == 2 and x.shape[1] == self.d
+        m, k = x.shape[0], int(k)
+        idx = np.zeros(k, dtype=np.int32)
+        ei = np.zeros(k)
+        mean = np.zeros(m, dtype=self.dtype)
+        var = np.zeros(m, dtype=self.dtype)
+        lie_c = None if lie is None else C.byref(C.c_double(float(lie)))
+        fn = getattr(lib, f"hbegp_select_batch_{self._sfx}")
+        _lib.check(fn(self._h, _lib.aptr(x), m, k, float(fmin_normalized), lie_c, idx.ctypes.data_as(C.POINTER(C.c_int)), _lib.dptr(ei),
+                      _lib.aptr(mean), _lib.aptr(var)))
+        return idx.astype(np.int64), ei, mean, var
+
     def release(self):
         if self._h:
             _lib.load().hbegp_model_release(self._h)

@@ -254,6 +254,26 @@ int hbegp_sample_posterior_f64(hbegp_model* model, const double* Xs, int m, cons
 int hbegp_sample_posterior_f32(hbegp_model* model, const float* Xs, int m, const float* z, int S, double jitter,
                                float* samples, int* argmin, int* info);
 
+/* Greedy batch selection by expected improvement with fantasised observations (kriging believer / constant liar), in the
+ * normalised y space like hbegp_predict_*.  Start: mu = the posterior mean, v = diag Sigma of hbegp_predict_cov at jitter 0
+ * (hbegp_predict's variance before clamping), fmin_0 = fmin_normalized.  For t = 0 .. k-1:
+ *   j_t = argmax over the rows not yet picked of EI(mu_i, sqrt(max(v_i, 0)), fmin_t) (acquisition.rs:141-171, fp64), ties to
+ *         the LAST maximal index as Rust's max_by (k = 1 is find_best_candidate_by_ei); ei[t] = that EI;
+ *   f_t = mu_{j_t} (lie == NULL: kriging believer) or *lie (constant liar); fmin_{t+1} = min(fmin_t, f_t);
+ *   condition on a noisy observation f_t at x_{j_t} with the model's noise s2: r_i = Sigma_{i,j_t} - sum_{s<t} c_s[i] c_s[j_t],
+ *         r_{j_t} = v_{j_t} - 1e-5, c_t = r / sqrt(max(r_{j_t}, 0) + s2), v -= c_t^2, mu += c_t (f_t - mu_{j_t}) / sqrt(..).
+ * After t picks (mu, max(v, 0)) is hbegp_predict of the model extended at the same theta with the rows (x_{j_s}, f_s), s < t.
+ * idx[k] (required for k > 0); ei[k], mean_out[m], var_out[m] (each may be NULL): the state after all k conditionings,
+ * var_out clamped at 0 like hbegp_predict.  k = 0 is a no-op.  HBEGP_EINVAL (before any device call) for a NULL model, m < 0,
+ * k < 0, k > m, a NULL idx with k > 0, a non-finite fmin_normalized or *lie, a model of the other element type or a non-finite
+ * query coordinate.  Serialised per model like predict; the same call gives the same bits, and a call with k = t returns the
+ * first t entries of idx / ei of any call with a larger k.  Sigma (m_p^2 elements) and an fp64 workspace of k m_p are
+ * borrowed for the call; work that does not fit in device memory is HBEGP_ENOMEM. */
+int hbegp_select_batch_f64(hbegp_model* model, const double* Xs, int m, int k, double fmin_normalized, const double* lie, int* idx,
+                           double* ei, double* mean_out, double* var_out);
+int hbegp_select_batch_f32(hbegp_model* model, const float* Xs, int m, int k, double fmin_normalized, const double* lie, int* idx,
+                           double* ei, float* mean_out, float* var_out);
+
 int hbegp_model_info(const hbegp_model* model, int* n, int* d, int* is_f32, double* nu, double* lml);
 /* theta[p] (log space, clamped), alpha[n], kinv[n*n] full symmetric; any pointer may be NULL. */
 int hbegp_model_get_f64(hbegp_model* model, double* theta, double* alpha, double* kinv);
@@ -301,6 +321,10 @@ int hbegp_debug_lbfgs_replay(int n, const double* x0, const double* lo, const do
  * (upload of z, Z L^T, epilogue) -- in milliseconds; then enable != 0 makes this thread's later sampling calls timed (events
  * around the phases on the model stream). */
 int hbegp_debug_posterior_phases(int enable, double* phase_ms);
+/* ---- timing hook (tools/batch_select_bench.py): phase_ms[2] (may be NULL) receives the device time of the phases of the
+ * calling thread's last timed hbegp_select_batch_* call -- Sigma (upload, K*, mean, Q, kmat, Q Q^T, mirror), the selection
+ * kernel -- in milliseconds; then enable != 0 makes this thread's later selection calls timed. */
+int hbegp_debug_batch_select_phases(int enable, double* phase_ms);
 
 #ifdef __cplusplus
 }

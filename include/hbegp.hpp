@@ -60,6 +60,8 @@ template <> struct Abi<double> {
   static int sample_posterior(hbegp_model* m, const double* xs, int k, const double* z, int s, double j, double* smp, int* amin, int* info) {
     return hbegp_sample_posterior_f64(m, xs, k, z, s, j, smp, amin, info);
   }
+  static int select_batch(hbegp_model* m, const double* xs, int n, int k, double fmin, const double* lie, int* idx, double* ei, double* mean,
+                          double* var) { return hbegp_select_batch_f64(m, xs, n, k, fmin, lie, idx, ei, mean, var); }
   static int get(hbegp_model* m, double* t, double* a, double* ki) { return hbegp_model_get_f64(m, t, a, ki); }
 };
 template <> struct Abi<float> {
@@ -80,6 +82,8 @@ template <> struct Abi<float> {
   static int sample_posterior(hbegp_model* m, const float* xs, int k, const float* z, int s, double j, float* smp, int* amin, int* info) {
     return hbegp_sample_posterior_f32(m, xs, k, z, s, j, smp, amin, info);
   }
+  static int select_batch(hbegp_model* m, const float* xs, int n, int k, double fmin, const double* lie, int* idx, double* ei, float* mean,
+                          float* var) { return hbegp_select_batch_f32(m, xs, n, k, fmin, lie, idx, ei, mean, var); }
   static int get(hbegp_model* m, double* t, float* a, float* ki) { return hbegp_model_get_f32(m, t, a, ki); }
 };
 }  // namespace detail
@@ -159,6 +163,12 @@ class FittedKernel {
   // throws Error(HBEGP_NOT_PD) when cov does not factor (retry with a larger jitter)
   void sample_posterior(const A* xs, int m, const A* z, int S, A* samples, int* argmin, double jitter = 0.0) const {
     check(detail::Abi<A>::sample_posterior(h_, xs, m, z, S, jitter, samples, argmin, nullptr));
+  }
+  // k candidates of xs[m*d] picked greedily by EI with fantasised observations (kriging believer, or the constant liar *lie):
+  // idx[k]; ei[k], mean[m], var[m] may be nullptr (normalised y space; mean / var after the k conditionings)
+  void select_batch(const A* xs, int m, int k, double fmin_normalized, int* idx, double* ei = nullptr, A* mean = nullptr,
+                    A* var = nullptr, const double* lie = nullptr) const {
+    check(detail::Abi<A>::select_batch(h_, xs, m, k, fmin_normalized, lie, idx, ei, mean, var));
   }
   double lml() const { return lml_; }
   double noise() const { return std::exp(theta_[0]); }

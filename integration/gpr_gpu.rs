@@ -135,6 +135,14 @@ extern "C" {
         model: *mut HbegpModel, xs: *const c_float, m: c_int, z: *const c_float, s: c_int, jitter: c_double,
         samples: *mut c_float, argmin: *mut c_int, info: *mut c_int,
     ) -> c_int;
+    fn hbegp_select_batch_f64(
+        model: *mut HbegpModel, xs: *const c_double, m: c_int, k: c_int, fmin_normalized: c_double, lie: *const c_double,
+        idx: *mut c_int, ei: *mut c_double, mean_out: *mut c_double, var_out: *mut c_double,
+    ) -> c_int;
+    fn hbegp_select_batch_f32(
+        model: *mut HbegpModel, xs: *const c_float, m: c_int, k: c_int, fmin_normalized: c_double, lie: *const c_double,
+        idx: *mut c_int, ei: *mut c_double, mean_out: *mut c_float, var_out: *mut c_float,
+    ) -> c_int;
     fn hbegp_model_info(
         model: *const HbegpModel, n: *mut c_int, d: *mut c_int, is_f32: *mut c_int, nu: *mut c_double, lml: *mut c_double,
     ) -> c_int;
@@ -207,6 +215,11 @@ pub trait GpuScalar: Scalar + sealed::Sealed {
         model: *mut HbegpModel, xs: *const Self, m: c_int, z: *const Self, s: c_int, jitter: f64, samples: *mut Self,
         argmin: *mut c_int, info: *mut c_int,
     ) -> c_int;
+    /// `hbegp_select_batch_*`
+    unsafe fn ffi_select_batch(
+        model: *mut HbegpModel, xs: *const Self, m: c_int, k: c_int, fmin_normalized: f64, lie: *const f64, idx: *mut c_int,
+        ei: *mut f64, mean_out: *mut Self, var_out: *mut Self,
+    ) -> c_int;
 }
 
 impl GpuScalar for f64 {
@@ -257,6 +270,12 @@ impl GpuScalar for f64 {
     ) -> c_int {
         hbegp_sample_posterior_f64(model, xs, m, z, s, jitter, samples, argmin, info)
     }
+    unsafe fn ffi_select_batch(
+        model: *mut HbegpModel, xs: *const f64, m: c_int, k: c_int, fmin_normalized: f64, lie: *const f64, idx: *mut c_int,
+        ei: *mut f64, mean_out: *mut f64, var_out: *mut f64,
+    ) -> c_int {
+        hbegp_select_batch_f64(model, xs, m, k, fmin_normalized, lie, idx, ei, mean_out, var_out)
+    }
 }
 
 impl GpuScalar for f32 {
@@ -306,6 +325,12 @@ impl GpuScalar for f32 {
         argmin: *mut c_int, info: *mut c_int,
     ) -> c_int {
         hbegp_sample_posterior_f32(model, xs, m, z, s, jitter, samples, argmin, info)
+    }
+    unsafe fn ffi_select_batch(
+        model: *mut HbegpModel, xs: *const f32, m: c_int, k: c_int, fmin_normalized: f64, lie: *const f64, idx: *mut c_int,
+        ei: *mut f64, mean_out: *mut f32, var_out: *mut f32,
+    ) -> c_int {
+        hbegp_select_batch_f32(model, xs, m, k, fmin_normalized, lie, idx, ei, mean_out, var_out)
     }
 }
 
@@ -542,6 +567,30 @@ impl<A: GpuScalar> SurrogateModelGpu<A> {
             panic!("hbegp_sample_posterior failed: {}", last_error());
         }
         Ok((samples, argmin.into_iter().map(|i| i as usize).collect()))
+    }
+
+    /// Greedy batch selection by EI with fantasised observations (`hbegp_select_batch_*`): k distinct rows of `x`, each the
+    /// largest EI (ties to the last index, as `max_by`) after the model was conditioned on a fantasy at every earlier pick --
+    /// its mean (kriging believer, `lie = None`) or `lie` (constant liar).  `fmin_normalized` and `lie` are in the normalised
+    /// y space.  Returns (indices [k], EI of each pick [k]).  k = 1 is `find_best_candidate_by_ei`.  Opt-in.
+    pub fn select_batch_normalized(&self, x: ArrayView2<A>, k: usize, fmin_normalized: f64, lie: Option<f64>) -> (Vec<usize>, Vec<f64>) {
+        let (m, _d) = x.dim();
+        assert!(k <= m, "k must be <= the number of candidates");
+        if k == 0 {
+            return (Vec::new(), Vec::new());
+        }
+        let x = x.as_standard_layout();
+        let mut idx: Vec<c_int> = vec![0; k];
+        let mut ei = vec![0.0f64; k];
+        let lie_ptr = lie.as_ref().map_or(std::ptr::null(), |l| l as *const f64);
+        let rc = unsafe {
+            A::ffi_select_batch(self.handle, x.as_ptr(), m as c_int, k as c_int, fmin_normalized, lie_ptr, idx.as_mut_ptr(),
+                                ei.as_mut_ptr(), std::ptr::null_mut(), std::ptr::null_mut())
+        };
+        if rc != HBEGP_OK {
+            panic!("hbegp_select_batch failed: {}", last_error());
+        }
+        (idx.into_iter().map(|i| i as usize).collect(), ei)
     }
 
     /// Batched `predict_confidence_bound` (gpr.rs:94-112 for every row): one device call instead of one per individual
