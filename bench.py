@@ -17,6 +17,11 @@ own N ranks (`python -m torch.distributed.run ... bench.py`) before anything tou
 gradmin.rs:19-31): ONE process owns `--gpus G` devices through hbegp_ctx_create(G), run r goes to device r mod G, the
 host picks the arg-max ("strong" scaling: the 8 runs are the fixed total work).
 
+A plain run sets up, warms up, times the steps, writes `--dump-outputs` and prints the headline line.  `--full` adds, after
+the timed steps, everything else the bench measures or checks: the roofline (kernel timings in runs of their own), the CPU
+baseline with the in-run parity check against the oracle and the referee, and the side lines (converged fit, f32, the other
+BASELINE configurations, small n, concurrent fits); `--no-cpu-baseline` and `--no-side-lines` trim a `--full` run.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -451,13 +456,14 @@ def run_c3(args):
         "fit_frac_of_peak": n_evals * n ** 3 * 1e-12 / (elapsed / args.steps) / (PEAK_FP64_MFMA_TFLOPS * G),
         "lml": lml,
     }
-    # the kernel the runs spend their time in, on device 0 with the slots one device runs side by side (8 runs over G devices,
-    # at most 3 at once per device)
-    nslots = max(1, min(3, -(-8 // G)))
-    ctx0 = gpr.Context(device_ids=[0])
-    out["roofline"] = roofline_block(gpr, ctx0, X, y, w["theta"], nslots, elapsed / args.steps * 1e3, n_evals, 0.0, pmc_ok=False, n_devices=G)
-    ctx0.close()
-    if not args.no_cpu_baseline:
+    if args.full:
+        # the kernel the runs spend their time in, on device 0 with the slots one device runs side by side (8 runs over G
+        # devices, at most 3 at once per device)
+        nslots = max(1, min(3, -(-8 // G)))
+        ctx0 = gpr.Context(device_ids=[0])
+        out["roofline"] = roofline_block(gpr, ctx0, X, y, w["theta"], nslots, elapsed / args.steps * 1e3, n_evals, 0.0, pmc_ok=False, n_devices=G)
+        ctx0.close()
+    if args.full and not args.no_cpu_baseline:
         cb = cpu_baseline(w, w["theta"], synth.candidates("C3", 8, d), n_evals, reps=3)
         cb["value"] = 1.0 / (n_evals * cb["eval_s"])  # fits/s: no predict in this workload
         cb["unit"] = "fits/s"
@@ -474,9 +480,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default="M", choices=["M", "C3"])
     ap.add_argument("--n", type=int, default=None, help="override n (debug only; invalidates the metric)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything beyond the headline: roofline, CPU baseline "
+                         "and in-run parity, side lines")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the in-run parity check")
     ap.add_argument("--no-side-lines", action="store_true",
-                    help="skip the f32 / small-n / converged-fit side lines (profiling runs: the kernel statistics then hold the headline workload only)")
+                    help="with --full: skip the side lines and the CPU baseline (profiling runs: the kernel statistics then hold "
+                         "the headline workload and the roofline's timings only)")
     ap.add_argument("--dry", action="store_true", help="launcher/harness rehearsal on CPU (gloo, no GPU work): prints the line with value 0")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step computed (the fitted model and its predictions; "
@@ -564,10 +574,6 @@ def main():
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
         value = world * args.steps / elapsed  # whole-job fit+predict per second
-        nslots = 1 + N_RESTARTS
-        log("roofline: kernel times with all slots evaluating at once")
-        roofline = roofline_block(gpr, ctx, X, y, theta, nslots, ms_per_step, fit_stats.get("n_evals", 0), 2.0 * M_CANDIDATES * n * n,
-                                  pmc_ok=args.n is None)
         out = {
             "metric": "GP fit+predict/sec (n=4096,d=8,f64)",
             "value": value,
@@ -590,9 +596,12 @@ def main():
                 "m_candidates": M_CANDIDATES,
                 "parallelism": f"replicas x{world} (independent fits per GPU, no collective)",
             },
-            "roofline": roofline,
         }
-        if args.no_side_lines:
+        if args.full:
+            log("roofline: kernel times with all slots evaluating at once")
+            out["roofline"] = roofline_block(gpr, ctx, X, y, theta, 1 + N_RESTARTS, ms_per_step, fit_stats.get("n_evals", 0),
+                                             2.0 * M_CANDIDATES * n * n, pmc_ok=args.n is None)
+        if not args.full or args.no_side_lines:
             print(json.dumps(out), flush=True)
             if dist is not None:
                 D.barrier(dist)

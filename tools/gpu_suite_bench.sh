@@ -9,7 +9,7 @@ tail -4 $OUT/gputest.txt
 if [ $rc -ne 0 ]; then echo "GPU SUITE rc=$rc"; grep -n "Error\|assert" $OUT/gputest.txt | head -20; exit $rc; fi
 timeout -k 10 600 python3 -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.txt 2>&1 || { tail -5 $OUT/smoke.txt; exit 1; }
 tail -1 $OUT/smoke.txt
-timeout -k 10 900 python3 bench.py ${BENCH_ARGS} > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
+timeout -k 10 900 python3 bench.py --full ${BENCH_ARGS} > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
 python3 - <<PY
 import json
 d=json.load(open("$OUT/bench.json"))

@@ -10,7 +10,7 @@ OUT=$ROOT/gpurun_out/profiles_$TAG
 rm -rf "$OUT"; mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 echo "[1/7] kernel trace of bench.py (3 concurrent optimiser runs, task-queue launches)"
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/bench" -o run -- python3 "$ROOT/bench.py" --no-cpu-baseline --no-side-lines --steps 3 --warmup 1 > "$OUT/bench_trace.log" 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/bench" -o run -- python3 "$ROOT/bench.py" --full --no-cpu-baseline --no-side-lines --steps 3 --warmup 1 > "$OUT/bench_trace.log" 2>&1
 cp "$OUT/bench/run_kernel_stats.csv" "$OUT/${TAG}_bench_3stream_kernel_stats.csv"
 python3 "$ROOT/tools/trace_timeline.py" "$OUT/bench/run_kernel_trace.csv" > "$OUT/${TAG}_bench_3stream_timeline.txt" 2>&1 || true
 rm -rf "$OUT/bench"
@@ -36,7 +36,7 @@ rm -rf "$OUT/sq1" "$OUT/sq0"
 cd "$ROOT"
 echo "[7/7] bench.py (full, with CPU baseline)"
 cp "$OUT/${TAG}_pmc_traffic.json" "$ROOT/profiles/${TAG}_pmc_traffic.json"
-python3 bench.py > "$OUT/${TAG}_bench.json" 2> "$OUT/bench.err"
+python3 bench.py --full > "$OUT/${TAG}_bench.json" 2> "$OUT/bench.err"
 cut -c1-300 "$OUT/${TAG}_bench.json"
 cat "$OUT/pmc_sq_summary.log"
 ls -la "$OUT"

@@ -4,7 +4,7 @@ out=$1; shift
 : > "$out"
 for cfg in "$@"; do
   echo "== $cfg" >> "$out"
-  env $cfg python3 bench.py --steps 4 --warmup 1 --no-cpu-baseline 2>>"$out.err" | python3 -c "
+  env $cfg python3 bench.py --full --steps 4 --warmup 1 --no-cpu-baseline 2>>"$out.err" | python3 -c "
 import sys, json
 for l in sys.stdin:
     l = l.strip()
