@@ -3102,6 +3102,21 @@ int hbegp_model_get_f64(hbegp_model* model, double* theta, double* alpha, double
 int hbegp_model_get_f32(hbegp_model* model, double* theta, float* alpha, float* kinv) {
   return model_get<float>(model, theta, alpha, kinv);
 }
+int hbegp_model_debug_params(hbegp_model* model, double* out) {
+  if (!model) return fail(HBEGP_EINVAL, "NULL model");
+  if (!out) return fail(HBEGP_EINVAL, "NULL out");
+  GUARD_BEGIN
+  std::lock_guard<std::mutex> lock(model->mu);
+  HIPCHECK(hipSetDevice(model->dev));
+  EvalParams P;
+  HIPCHECK(hipMemcpyAsync(&P, model->dP, sizeof(P), hipMemcpyDeviceToHost, model->stream));
+  HIPCHECK(hipStreamSynchronize(model->stream));
+  out[0] = P.noise;
+  out[1] = P.amp;
+  for (int k = 0; k < model->d; ++k) out[2 + k] = P.ell[k];
+  return HBEGP_OK;
+  GUARD_END
+}
 void hbegp_model_retain(hbegp_model* model) {
   if (model) model->refs.fetch_add(1);
 }

@@ -95,6 +95,7 @@ SIGNATURES = {
     "hbegp_model_info": (C.c_int, [_vp, _ip, _ip, _ip, _dp, _dp]),
     "hbegp_model_get_f64": (C.c_int, [_vp, _dp, _dp, _dp]),
     "hbegp_model_get_f32": (C.c_int, [_vp, _dp, _fp, _fp]),
+    "hbegp_model_debug_params": (C.c_int, [_vp, _dp]),
     "hbegp_model_retain": (None, [_vp]),
     "hbegp_model_release": (None, [_vp]),
     "hbegp_debug_lbfgs_replay": (C.c_int, [C.c_int, _dp, _dp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _ip]),

@@ -182,6 +182,13 @@ class FittedKernel:
     def length_scale(self):
         return np.exp(self.theta[2:])
 
+    def device_params(self):
+        """(noise, amplitude, length_scale) as the model's posterior queries use them (hbegp_model_debug_params): for a
+        device-driven fit the captured evaluation's own numbers, which may differ from exp(theta) in the last bit."""
+        out = np.zeros(self.d + 2)
+        _lib.check(_lib.load().hbegp_model_debug_params(self._h, _lib.dptr(out)))
+        return float(out[0]), float(out[1]), out[2:].copy()
+
     def arrays(self, want_kinv=True):
         """(alpha, k_inv) copied from the device; k_inv is the full symmetric matrix (fit.rs:60,168)."""
         alpha = np.zeros(self.n, dtype=self.dtype)

@@ -296,6 +296,11 @@ double hbegp_minimize_by_gradient(hbegp_objective_fn f, void* user, double* x, c
 int hbegp_problem_debug_get_f64(hbegp_problem* prob, int dev, int slot, int which, double* out);
 int hbegp_problem_debug_get_f32(hbegp_problem* prob, int dev, int slot, int which, float* out);
 
+/* ---- test hook: the kernel parameters every posterior query of the model evaluates with (its device copy of noise,
+ * amplitude, ell_1..ell_d), copied into out[d + 2].  For a device-driven fit these are the numbers the captured evaluation ran
+ * with, which can differ from exp(theta) of the reported theta in the last bit.  HBEGP_EINVAL for a NULL model or out. */
+int hbegp_model_debug_params(hbegp_model* model, double* out);
+
 /* ---- test hook (host only, no GPU): build the task queue of the device-scheduled factorisation for `nblocks`
  * 128-blocks (bk = contraction elements per stage: 16 for f64, 32 for f32; nodes up to small_h blocks wide use 64x64
  * tiles; nwg > 0: order the queue by a list schedule simulated for nwg workgroups; fine bit 0: per-row-block dependencies,

@@ -17,6 +17,8 @@ import subprocess
 import numpy as np
 from scipy.linalg import lapack
 
+from oracle import gpr_oracle as O
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB = os.path.join(HERE, "libreferee.so")
 MIN_NOISE = 1e-5  # predict.rs:25
@@ -66,6 +68,30 @@ def nu2_of(nu):
     return 0 if math.isinf(nu) else int(round(2 * nu))
 
 
+def _psi(r, nu):
+    """phi'(r) / r of the Matern correlation phi (0 at r = 0), in float64."""
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        if math.isinf(nu):
+            out = -np.exp(-0.5 * r * r)
+        elif nu == 0.5:
+            out = -np.exp(-r) / r
+        elif nu == 1.5:
+            out = -3.0 * np.exp(-math.sqrt(3.0) * r)
+        elif nu == 2.5:
+            out = -(5.0 / 3.0) * (1.0 + math.sqrt(5.0) * r) * np.exp(-math.sqrt(5.0) * r)
+        else:
+            raise ValueError(nu)
+    return np.where(r == 0.0, 0.0, out)
+
+
+def dkstar(Xs, X, amplitude, length_scale, nu):
+    """dk(x*_q, x_j) / dx*_q,k = c psi(r) (x*_k - x_jk) / ell_k^2 as [m, n, d], in float64."""
+    ell = np.asarray(length_scale, dtype=np.float64)
+    diff = (np.asarray(Xs, np.float64) / ell)[:, None, :] - (np.asarray(X, np.float64) / ell)[None, :, :]
+    r = np.sqrt((diff * diff).sum(axis=2))
+    return (amplitude * _psi(r, nu))[:, :, None] * diff / ell
+
+
 class Referee:
     """Truth for one (X, y, noise, amplitude, length_scale, nu): alpha, predictive mean / variance, selected columns of K^-1."""
 
@@ -76,6 +102,7 @@ class Referee:
         self.n, self.d = self.X.shape
         self.amp, self.noise = float(amplitude), float(noise)
         self.ell = _c(length_scale)
+        self.nu = nu
         self.h = lib.referee_create(_p(self.X), self.n, self.d, self.noise, self.amp, _p(self.ell), nu2_of(nu))
         if not self.h:
             raise MemoryError("referee_create")
@@ -192,3 +219,60 @@ class Referee:
         raw = ((ld(self.amp) + ld(MIN_NOISE)) - ld(qh)) - ld(ql)  # diag + min_noise - k*^T K^-1 k*  (predict.rs:30-37)
         raw = raw.astype(np.float64)
         return mean, np.where(raw < 0, 0.0, raw), raw
+
+    def _kstar(self, Xs):
+        """k* = k(X, Xs) as a double-double pair [n, m], and K^-1 k* likewise."""
+        Xs = _c(Xs)
+        m = Xs.shape[0]
+        kh, kl = np.empty((self.n, m)), np.empty((self.n, m))
+        _load().referee_kstar(self.h, _p(Xs), m, _p(kh), _p(kl))
+        wh, wl = self.solve(kh, kl)
+        return kh, kl, _c(wh).reshape(self.n, m), _c(wl).reshape(self.n, m)
+
+    def predict_grad(self, Xs):
+        """The gradients of predict's mean and variance w.r.t. the query points (include/hbegp.h, hbegp_predict_grad_*):
+        (dmean [m, d], dvar [m, d]), each rounded to f64.  dmean = dk . alpha with the refined alpha, dvar = -2 dk . (K^-1 k*)
+        with K^-1 k* from `solve`, both dot products summed in double-double.  dk itself is formed in f64 (`dkstar`) and taken
+        as exact: its rounding is a relative 1e-16 per entry, the error the refinement removes is cond(K) eps.  dvar is 0 where
+        the true variance clamps at 0 (as predict.rs:39-48 and tests/predict_grad_ref.py do)."""
+        lib = _load()
+        Xs = _c(Xs)
+        m = Xs.shape[0]
+        dk = dkstar(Xs, self.X, self.amp, self.ell, self.nu)  # [m, n, d]
+        kh, kl, wh, wl = self._kstar(Xs)
+        ah, al = self.alpha()
+        Ah, Al = _c(np.repeat(ah[:, None], m, axis=1)), _c(np.repeat(al[:, None], m, axis=1))
+        zero = np.zeros((self.n, m))
+        dmean, dvar = np.empty((m, self.d)), np.empty((m, self.d))
+        qh, ql = np.empty(m), np.empty(m)
+        for k in range(self.d):
+            G = _c(dk[:, :, k].T)
+            lib.referee_coldot(self.n, m, _p(G), _p(zero), _p(Ah), _p(Al), _p(qh), _p(ql))
+            dmean[:, k] = qh + ql
+            lib.referee_coldot(self.n, m, _p(G), _p(zero), _p(wh), _p(wl), _p(qh), _p(ql))
+            dvar[:, k] = -2.0 * (qh + ql)
+        qh2, ql2 = np.empty(m), np.empty(m)
+        lib.referee_coldot(self.n, m, _p(kh), _p(kl), _p(wh), _p(wl), _p(qh2), _p(ql2))
+        ld = np.longdouble
+        raw = (((ld(self.amp) + ld(MIN_NOISE)) - ld(qh2)) - ld(ql2)).astype(np.float64)
+        dvar[raw < 0] = 0.0
+        return dmean, dvar
+
+    def sigma(self, Xs, jitter=0.0):
+        """The joint posterior at the query points (include/hbegp.h, hbegp_predict_cov_*) as [m, m] in f64:
+        K** + (1e-5 + jitter) I - K*^T K^-1 K*, the cross term K*^T (K^-1 K*) summed in double-double (K^-1 K* from `solve`) and
+        symmetrised; K** in f64."""
+        lib = _load()
+        Xs = _c(Xs)
+        m = Xs.shape[0]
+        kh, kl, wh, wl = self._kstar(Xs)
+        cross = np.empty((m, m))
+        qh, ql = np.empty(m), np.empty(m)
+        for i in range(m):
+            Bh, Bl = _c(np.repeat(wh[:, i:i + 1], m, axis=1)), _c(np.repeat(wl[:, i:i + 1], m, axis=1))
+            lib.referee_coldot(self.n, m, _p(kh), _p(kl), _p(Bh), _p(Bl), _p(qh), _p(ql))
+            cross[i] = qh + ql
+        kss = O.product_kernel(Xs, Xs, self.amp, self.ell, self.nu)
+        truth = kss - 0.5 * (cross + cross.T)
+        truth[np.diag_indices(m)] += MIN_NOISE + float(jitter)
+        return truth

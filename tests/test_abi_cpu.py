@@ -99,3 +99,11 @@ def test_minimize_respects_maxeval_and_infinite_values():
     f, x = gpr.minimize_by_gradient(obj, [0.0], [(-1, 1)], maxeval=40)
     assert len(calls) <= 40
     assert x[0] <= 0.5 and f <= -0.4
+
+
+def test_model_debug_params_refuses_a_null_model():
+    lib = _lib.load()
+    out = np.zeros(4)
+    assert lib.hbegp_model_debug_params(None, _lib.dptr(out)) == _lib.EINVAL
+    assert "NULL model" in _lib.last_error()
+    assert lib.hbegp_model_debug_params(None, None) == _lib.EINVAL

@@ -9,6 +9,7 @@ import pytest
 
 from hbetune_rs_amd import gpr, synth
 from oracle import gpr_oracle as O
+from oracle import referee as R
 
 import parity_rules as PR
 
@@ -408,8 +409,28 @@ def test_persistent_fit_kernel_for_the_reference_regime(n, cfg, dtype, fixed_wor
         print("fitted model: " + jm.summary())
         assert dtype == np.float32 or jm.n_nodigits == 0
         rf.close()
-    mean, var, _ = fk.predict(X[:5])
+    # predict of the fitted model at the parameters its kernels use (a device-driven fit's own exp / clamp of the captured theta,
+    # exp(theta) up to the rounding of theta, an ulp of which moves exp(theta) by |theta| eps): against the oracle of the element
+    # type, the referee where the plain bar fails
+    noise, amp, ell = fk.device_params()
+    want = np.exp(fk.theta)
+    assert (np.abs(np.concatenate([[noise, amp], ell]) - want) <= (np.abs(fk.theta) + 2) * np.finfo(float).eps * want).all()
+    Xq = X[:5]
+    mean, var, _ = fk.predict(Xq)
     assert np.all(np.isfinite(mean)) and np.all(var >= 0)
+    try:
+        rp = O.extend(X, y, noise, amp, ell, 2.5)
+    except FloatingPointError:
+        rp = None  # (LAPACK f32 cannot factor K at these parameters: the reference has no digits there)
+    if rp is not None:
+        om, ov, _ = O.predict(Xq, X, rp["alpha"], rp["k_inv"], amp, ell, 2.5)
+        rfp = R.Referee(X64, y64, noise, amp, ell, 2.5)
+        jp = PR.Judge(tol)
+        jp.check("predict mean of the fitted model", mean, om, lambda: rfp.predict(Xq.astype(np.float64))[0])
+        jp.check("predict variance of the fitted model", var, ov, lambda: rfp.predict(Xq.astype(np.float64))[1], scale=amp)
+        print("fitted model, predict: " + jp.summary())
+        assert dtype == np.float32 or jp.n_nodigits == 0
+        rfp.close()
     # (c) the device's optimiser against the host state machine (csrc/lbfgs_step.hpp): every run's recorded evaluations
     # (theta_i, f_i, g_i) are fed to lbfgs_advance on the host, which must ask for the very points the device went on to
     # evaluate -- start point, line-search trials, bound hits, failed evaluations (+inf), and in fixed-work mode the repeats at

@@ -99,22 +99,8 @@ def test_jitter_moves_the_diagonal_only(dtype):
 def _truth_sigma(fk, X, y, Xs):
     """K** + 1e-5 I - K*^T K^-1 K* with the cross term in double-double (referee: iterative refinement in extended precision)."""
     rf = R.Referee(X, y, fk.noise, fk.amplitude, fk.length_scale, fk.nu)
-    lib = R._load()
-    m, n = len(Xs), len(X)
-    Xs = R._c(Xs)
-    kh, kl = np.empty((n, m)), np.empty((n, m))
-    lib.referee_kstar(rf.h, R._p(Xs), m, R._p(kh), R._p(kl))
-    wh, wl = rf.solve(kh, kl)
-    cross = np.empty((m, m))
-    qh, ql = np.empty(m), np.empty(m)
-    for i in range(m):
-        Bh, Bl = R._c(np.repeat(wh[:, i:i + 1], m, axis=1)), R._c(np.repeat(wl[:, i:i + 1], m, axis=1))
-        lib.referee_coldot(n, m, R._p(kh), R._p(kl), R._p(Bh), R._p(Bl), R._p(qh), R._p(ql))
-        cross[i] = qh + ql
+    truth = rf.sigma(Xs)
     rf.close()
-    kss = O.product_kernel(Xs, Xs, fk.amplitude, fk.length_scale, fk.nu)
-    truth = kss - 0.5 * (cross + cross.T)
-    truth[np.diag_indices(m)] += O.MIN_NOISE
     return truth
 
 
