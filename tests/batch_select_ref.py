@@ -67,3 +67,28 @@ def select(mu, sigma, s2, fmin, k, lie=None, picks=None):
     out["mean"] = mu
     out["var"] = np.maximum(v, 0.0)
     return out
+
+
+def bars(dtype):
+    # (pick: EI of the device's pick against the step's maximum, relative to max(1, EI); values: relative to c or max(1, |.|))
+    return (1e-12, 1e-8) if dtype == np.float64 else (1e-5, 1e-4)
+
+
+def replay(fk, Xs, k, fmin, lie, dtype):
+    """The device's k picks (fk.select_batch) replayed through select on the engine's own mean and Sigma (predict_cov at
+    jitter 0), against bars(dtype).  Returns (idx, ei, mean, var, (pick gap, ei, mean, var deviations))."""
+    pick_bar, bar = bars(dtype)
+    c = fk.amplitude
+    idx, ei, mean, var = fk.select_batch(Xs, k, fmin, lie=lie)
+    assert idx.dtype == np.int64 and idx.shape == (k,) and ei.shape == (k,)
+    assert mean.dtype == dtype and var.dtype == dtype and mean.shape == (len(Xs),)
+    assert len(set(idx.tolist())) == k and idx.min() >= 0 and idx.max() < len(Xs)
+    mean0, cov = fk.predict_cov(Xs)
+    r = select(mean0, cov, fk.noise, fmin, k, lie=lie, picks=idx)
+    gap = float(np.max((r["best"] - r["ei"]) / np.maximum(1.0, r["best"])))
+    dei = float(np.abs(ei - r["ei"]).max()) / max(1.0, float(np.abs(r["ei"]).max()))
+    dmean = float(np.abs(mean.astype(np.float64) - r["mean"]).max()) / max(1.0, float(np.abs(r["mean"]).max()))
+    dvar = float(np.abs(var.astype(np.float64) - r["var"]).max()) / c
+    assert gap <= pick_bar, gap
+    assert dei <= bar and dmean <= bar and dvar <= bar, (dei, dmean, dvar)
+    return idx, ei, mean, var, (gap, dei, dmean, dvar)

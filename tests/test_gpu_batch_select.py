@@ -39,32 +39,13 @@ def _candidates(m, seed, dtype, d=D):
     return np.random.default_rng(seed).uniform(-0.1, 1.1, (m, d)).astype(dtype)
 
 
-def _bars(dtype):
-    # (pick: EI of the device's pick against the step's maximum, relative to max(1, EI); values: relative to c or max(1, |.|))
-    return (1e-12, 1e-8) if dtype == np.float64 else (1e-5, 1e-4)
-
-
 def _fmin_lie(y, lie):
     fmin = float(np.min(y))
     return fmin, (None if not lie else float(np.median(y)))
 
 
-def _replay(fk, Xs, k, fmin, lie, dtype):
-    pick_bar, bar = _bars(dtype)
-    c = fk.amplitude
-    idx, ei, mean, var = fk.select_batch(Xs, k, fmin, lie=lie)
-    assert idx.dtype == np.int64 and idx.shape == (k,) and ei.shape == (k,)
-    assert mean.dtype == dtype and var.dtype == dtype and mean.shape == (len(Xs),)
-    assert len(set(idx.tolist())) == k and idx.min() >= 0 and idx.max() < len(Xs)
-    mean0, cov = fk.predict_cov(Xs)
-    r = BS.select(mean0, cov, fk.noise, fmin, k, lie=lie, picks=idx)
-    gap = float(np.max((r["best"] - r["ei"]) / np.maximum(1.0, r["best"])))
-    dei = float(np.abs(ei - r["ei"]).max()) / max(1.0, float(np.abs(r["ei"]).max()))
-    dmean = float(np.abs(mean.astype(np.float64) - r["mean"]).max()) / max(1.0, float(np.abs(r["mean"]).max()))
-    dvar = float(np.abs(var.astype(np.float64) - r["var"]).max()) / c
-    assert gap <= pick_bar, gap
-    assert dei <= bar and dmean <= bar and dvar <= bar, (dei, dmean, dvar)
-    return idx, ei, mean, var, (gap, dei, dmean, dvar)
+_bars = BS.bars
+_replay = BS.replay
 
 
 @pytest.mark.parametrize("lie", [False, True])
