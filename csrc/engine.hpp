@@ -213,6 +213,20 @@ void launch_sample_epilogue(T* Y, int ld, const T* mean, int m, int S, int store
 template <typename T>
 void launch_batch_select(const T* Sig, int ld, const T* mean, int m, int k, const EvalParams* P, double fmin, int use_lie, double lie,
                          double* C, double* v, double* mu, int* picked, int* idx, double* ei, T* mean_out, T* var_out, hipStream_t s);
+// batch expected improvement by Monte Carlo (hbegp_qei; qei_batch_kernel: one workgroup per batch of q points).  Rows b q .. b q + q - 1
+// of Xs [B q][d], Q [mp][np], mean, dmean [mp][d] and W [d][mp][np] (W and dmean are read only with want_grad); z [S][q] shared by
+// the batches; noise = 1e-5 + jitter.  Out: qei[B], grad[B q][d] (want_grad), info[B] (0, or 1 + the column whose pivot failed).
+constexpr int QEI_MAXQ = 64;
+constexpr int QEI_CH = 256;  // draws per chunk
+// dynamic LDS of qei_batch_kernel: fp64 points / ell [q d], Sigma -> L [q q], Lbar -> X [q q], mu, mubar [q], I_s [QEI_CH]; ints
+// j_s [QEI_CH] and the failure flag (padded to 4)
+constexpr size_t qei_lds_bytes(int q, int d) {
+  return sizeof(double) * ((size_t)q * d + 2 * (size_t)q * q + 2 * (size_t)q + QEI_CH) + sizeof(int) * (QEI_CH + 4);
+}
+template <typename T>
+void launch_qei_batch(const T* Xs, int B, int q, int d, const T* Q, const T* W, int mp, int np, const T* mean, const T* dmean,
+                      const EvalParams* P, double noise, int nu2, const T* z, int S, double fmin, int want_grad, double* qei, T* grad,
+                      int* info, hipStream_t s);
 
 // predict for m <= PRED_SMALL_MAX candidates without the 128-row padding: reads L^-1 once (row dots against the m
 // cross-kernel vectors).  Ks: [PRED_SMALL_MAX][np] scratch, pmean: [(np+255)/256][PRED_SMALL_MAX], w: [n][PRED_SMALL_MAX].

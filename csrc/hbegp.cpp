@@ -1817,6 +1817,40 @@ static int model_predict(hbegp_model* m, const T* Xs, int cnt, T* mean, T* var, 
   return HBEGP_OK;
 }
 
+// the gradient scratch for mp (a multiple of NB) rows, grown on demand (predict_batched_reserve's arrays too)
+template <typename T>
+static void predict_grad_reserve(hbegp_model* m, int mp) {
+  predict_batched_reserve<T>(m, mp);
+  if (mp <= m->cap_g) return;
+  HIPCHECK(hipStreamSynchronize(m->stream));
+  m->pfree(m->G); m->pfree(m->W); m->pfree(m->gpart); m->pfree(m->dmean); m->pfree(m->dvar);
+  m->G = m->W = m->gpart = m->dmean = m->dvar = nullptr;
+  m->cap_g = 0;
+  m->G = m->palloc(sizeof(T) * (size_t)m->d * mp * m->np);
+  m->W = m->palloc(sizeof(T) * (size_t)m->d * mp * m->np);
+  m->gpart = m->palloc(sizeof(double) * (size_t)pred_grad_chunks(m->n) * mp * m->d);
+  m->dmean = m->palloc(sizeof(T) * (size_t)mp * m->d);
+  m->dvar = m->palloc(sizeof(T) * (size_t)mp * m->d);
+  m->cap_g = mp;
+}
+// W = G X^T on the model stream, the candidates in m->Xs: G = dKstar/dx* (d matrices [mp x np] stacked into one operand), then the
+// triangular tile GEMM that makes Q = Kstar X^T.  Row k mp + i of W is L^-1 dk*_i / dx*_i,k.
+template <typename T>
+static void predict_grad_w_launches(hbegp_model* m, int cnt, int mp) {
+  hipStream_t s = m->stream;
+  launch_kstar_grad<T>(static_cast<T*>(m->Xs), cnt, mp, static_cast<T*>(m->X), m->n, m->d, m->np, m->nu2, m->dP,
+                       static_cast<T*>(m->G), s);
+  GemmLaunch g{};
+  g.nops = 1;
+  GemmOp& op = g.op[0];
+  op.lda = m->np; op.ldb = m->np; op.ldc = m->np;
+  op.ci0 = 0; op.cj0 = 0; op.mi = m->d * mp / NB; op.nj = m->np / NB;
+  op.k0 = 0; op.k1 = m->np / NB;
+  op.A = m->G; op.B = m->Xinv; op.C = m->W;
+  op.klim = 1; op.maskB = 1;  // X = L^-1 lower, as for Q
+  gemm_adhoc<T>(g, &m->dOut->info, s);
+}
+
 // Posterior mean / variance as the batched predict computes them (for every m, also m <= 8) plus their gradients w.r.t. the
 // candidates (kernels.hip, pred_grad_kernel ..).  dvar = -2 (L^-1 dk*/dx_k) . (L^-1 k*): the d gradient matrices G_k stacked
 // into one [d*mp x np] operand of the same triangular tile GEMM that makes Q = Kstar X^T for the variance, then one fp64 row
@@ -1828,20 +1862,7 @@ static int model_predict_grad(hbegp_model* m, const T* Xs, int cnt, T* mean, T* 
   std::lock_guard<std::mutex> lock(m->mu);
   HIPCHECK(hipSetDevice(m->dev));
   const int mp = round_up(cnt, NB);
-  const int nch = pred_grad_chunks(m->n);
-  predict_batched_reserve<T>(m, mp);
-  if (mp > m->cap_g) {
-    HIPCHECK(hipStreamSynchronize(m->stream));
-    m->pfree(m->G); m->pfree(m->W); m->pfree(m->gpart); m->pfree(m->dmean); m->pfree(m->dvar);
-    m->G = m->W = m->gpart = m->dmean = m->dvar = nullptr;
-    m->cap_g = 0;
-    m->G = m->palloc(sizeof(T) * (size_t)m->d * mp * m->np);
-    m->W = m->palloc(sizeof(T) * (size_t)m->d * mp * m->np);
-    m->gpart = m->palloc(sizeof(double) * (size_t)nch * mp * m->d);
-    m->dmean = m->palloc(sizeof(T) * (size_t)mp * m->d);
-    m->dvar = m->palloc(sizeof(T) * (size_t)mp * m->d);
-    m->cap_g = mp;
-  }
+  predict_grad_reserve<T>(m, mp);
   hipStream_t s = m->stream;
   const bool want_var = var != nullptr;
   HIPCHECK(hipMemcpyAsync(m->Xs, Xs, sizeof(T) * (size_t)cnt * m->d, hipMemcpyHostToDevice, s));
@@ -1849,17 +1870,7 @@ static int model_predict_grad(hbegp_model* m, const T* Xs, int cnt, T* mean, T* 
   launch_pred_grad<T>(static_cast<T*>(m->Xs), cnt, static_cast<T*>(m->X), m->n, m->d, m->nu2, m->dP, static_cast<T*>(m->alpha),
                       static_cast<double*>(m->gpart), static_cast<T*>(m->dmean), s);
   if (want_var) {
-    launch_kstar_grad<T>(static_cast<T*>(m->Xs), cnt, mp, static_cast<T*>(m->X), m->n, m->d, m->np, m->nu2, m->dP,
-                         static_cast<T*>(m->G), s);
-    GemmLaunch g{};
-    g.nops = 1;
-    GemmOp& op = g.op[0];
-    op.lda = m->np; op.ldb = m->np; op.ldc = m->np;
-    op.ci0 = 0; op.cj0 = 0; op.mi = m->d * mp / NB; op.nj = m->np / NB;
-    op.k0 = 0; op.k1 = m->np / NB;
-    op.A = m->G; op.B = m->Xinv; op.C = m->W;
-    op.klim = 1; op.maskB = 1;  // X = L^-1 lower, as for Q
-    gemm_adhoc<T>(g, &m->dOut->info, s);
+    predict_grad_w_launches<T>(m, cnt, mp);
     launch_pred_dvar<T>(static_cast<T*>(m->W), static_cast<T*>(m->Q), cnt, mp, m->np, m->d, static_cast<T*>(m->var),
                         static_cast<T*>(m->dvar), s);
   }
@@ -2162,6 +2173,141 @@ static int model_maximize_ei(hbegp_model* m, const T* starts, int S, const doubl
     ei_out[r] = best[r];
     if (nevals_out) nevals_out[r] = st[r].nevals;
   }
+  return HBEGP_OK;
+}
+
+// phase times of the calling thread's last timed qEI call (hbegp_debug_qei_phases): the shared launches, the qEI kernel in ms
+static thread_local bool t_time_qei = false;
+static thread_local double t_qei_ms[2] = {0, 0};
+
+// Batch expected improvement by Monte Carlo (hbegp_qei) for B batches of q points: the B q points go through the batched predict's
+// launches (Kstar, mean, Q) and, with a gradient, the gradient's (dmean; G and W = G X^T), in the order hbegp_predict_grad issues
+// them; then qei_batch_kernel, one workgroup per batch (kernels.hip).  Only qei[B], info[B] and grad[B q d] leave the device;
+// z and the outputs are borrowed for the call (CallScratch), Q / W / dmean are the model's grow-only arrays.
+template <typename T>
+static int model_qei(hbegp_model* m, const T* Xb, int B, int q, const T* z, int S, double fmin, double jitter, double* qei, T* grad,
+                     int* info_out) {
+  std::lock_guard<std::mutex> lock(m->mu);
+  HIPCHECK(hipSetDevice(m->dev));
+  const bool want_grad = grad != nullptr;
+  const int d = m->d;
+  // everything the call borrows, counted before anything is taken: a B far beyond the device is ENOMEM, not an overflow
+  const double rows = round_up(std::max(1.0, (double)B * q), (double)NB);
+  const double need = (double)sizeof(T) * ((2.0 + (want_grad ? 2.0 * d : 0.0)) * rows * m->np + (double)S * q + rows * (d + 2)) +
+                      8.0 * (want_grad ? (double)pred_grad_chunks(m->n) * rows * d : 0.0) + 12.0 * B;
+  if (need > 1e15 || rows > (double)(1 << 30))
+    return fail(HBEGP_ENOMEM, "qEI of %d batches of %d points needs %.3g bytes of device memory", B, q, need);
+  const int cnt = B * q;
+  const int mp = round_up(cnt, NB);
+  if (want_grad) predict_grad_reserve<T>(m, mp);
+  else predict_batched_reserve<T>(m, mp);
+  hipStream_t s = m->stream;
+  const double noise = 1e-5 + jitter;  // predict_cov's diagonal
+  CallScratch ws{m->dev, s, {}};
+  T* dz = static_cast<T*>(ws.get(sizeof(T) * (size_t)S * q));
+  double* dq = static_cast<double*>(ws.get(sizeof(double) * (size_t)B));
+  int* dinfo = static_cast<int*>(ws.get(sizeof(int) * (size_t)B));
+  T* dg = want_grad ? static_cast<T*>(ws.get(sizeof(T) * (size_t)cnt * d)) : nullptr;
+  hipEvent_t ev[3] = {};
+  const bool timed = t_time_qei;
+  if (timed)
+    for (auto& e : ev) HIPCHECK(hipEventCreate(&e));
+  if (timed) HIPCHECK(hipEventRecord(ev[0], s));
+  HIPCHECK(hipMemcpyAsync(m->Xs, Xb, sizeof(T) * (size_t)cnt * d, hipMemcpyHostToDevice, s));
+  predict_batched_launches<T>(m, cnt, mp, true);
+  if (want_grad) {
+    launch_pred_grad<T>(static_cast<T*>(m->Xs), cnt, static_cast<T*>(m->X), m->n, d, m->nu2, m->dP, static_cast<T*>(m->alpha),
+                        static_cast<double*>(m->gpart), static_cast<T*>(m->dmean), s);
+    predict_grad_w_launches<T>(m, cnt, mp);
+  }
+  HIPCHECK(hipMemcpyAsync(dz, z, sizeof(T) * (size_t)S * q, hipMemcpyHostToDevice, s));
+  if (timed) HIPCHECK(hipEventRecord(ev[1], s));
+  const T* W = want_grad ? static_cast<const T*>(m->W) : static_cast<const T*>(m->Q);         // (not read without a gradient)
+  const T* dmean = want_grad ? static_cast<const T*>(m->dmean) : static_cast<const T*>(m->mean);
+  launch_qei_batch<T>(static_cast<const T*>(m->Xs), B, q, d, static_cast<const T*>(m->Q), W, mp, m->np, static_cast<const T*>(m->mean),
+                      dmean, m->dP, noise, m->nu2, dz, S, fmin, want_grad ? 1 : 0, dq, dg, dinfo, s);
+  if (timed) HIPCHECK(hipEventRecord(ev[2], s));
+  CHECK_LAUNCHES();
+  std::vector<int> hinfo(B);
+  HIPCHECK(hipMemcpyAsync(qei, dq, sizeof(double) * (size_t)B, hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipMemcpyAsync(hinfo.data(), dinfo, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost, s));
+  if (want_grad) HIPCHECK(hipMemcpyAsync(grad, dg, sizeof(T) * (size_t)cnt * d, hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
+  if (timed) {
+    for (int i = 0; i < 2; ++i) {
+      float ms = 0;
+      HIPCHECK(hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
+      t_qei_ms[i] = ms;
+    }
+    for (auto& e : ev) (void)hipEventDestroy(e);
+  }
+  if (info_out) memcpy(info_out, hinfo.data(), sizeof(int) * (size_t)B);
+  for (int b = 0; b < B; ++b)
+    if (hinfo[b] != 0)
+      return fail(HBEGP_NOT_PD, "Sigma of batch %d is not positive definite (pivot at column %d); a larger jitter may help", b,
+                  hinfo[b] - 1);
+  return HBEGP_OK;
+}
+
+// R bounded L-BFGS runs on -qEI over q d coordinates each (lbfgs_step.hpp with the host state sized per run: q d exceeds
+// LbfgsState's LBFGS_MAXN), the box [lo, hi] applied to every point, in lockstep: every round is ONE model_qei over the runs still
+// going, with the same z (a deterministic sample-average objective).  A batch whose factor failed is a failed evaluation.
+template <typename T>
+static int model_maximize_qei(hbegp_model* m, const T* starts, int R, int q, const double* lo, const double* hi, const T* z, int S,
+                              double fmin, double jitter, int maxeval, T* x_out, double* qei_out, int* nevals_out) {
+  const int d = m->d, n = q * d;
+  const LbfgsOptions o;
+  std::vector<double> lof(n), hif(n), x0(n), g(n);
+  for (int e = 0; e < n; ++e) {
+    lof[e] = lo[e % d];
+    hif[e] = hi[e % d];
+  }
+  std::vector<std::unique_ptr<LbfgsStateHost>> st;
+  std::vector<char> running(R, 1);
+  std::vector<double> best(R, -std::numeric_limits<double>::infinity());
+  for (int r = 0; r < R; ++r) {
+    st.emplace_back(new LbfgsStateHost(n));
+    for (int e = 0; e < n; ++e) x0[e] = (double)starts[(size_t)r * n + e];
+    lbfgs_begin(*st[r], x0.data(), lof.data(), hif.data(), n, maxeval, o.memory, o.pgtol, o.ftol, false);
+    for (int e = 0; e < n; ++e) x_out[(size_t)r * n + e] = starts[(size_t)r * n + e];
+  }
+  std::vector<int> act, info(R);
+  std::vector<T> xs((size_t)R * n), gr((size_t)R * n);
+  std::vector<double> qv(R);
+  for (;;) {
+    act.clear();
+    for (int r = 0; r < R; ++r)
+      if (running[r]) act.push_back(r);
+    if (act.empty()) break;
+    const int cnt = (int)act.size();
+    for (int i = 0; i < cnt; ++i) {
+      const double* p = lbfgs_request(*st[act[i]]);
+      for (int e = 0; e < n; ++e) xs[(size_t)i * n + e] = to_box<T>(p[e], lof[e], hif[e]);
+    }
+    const int rc = model_qei<T>(m, xs.data(), cnt, q, z, S, fmin, jitter, qv.data(), gr.data(), info.data());
+    if (rc != HBEGP_OK && rc != HBEGP_NOT_PD) return rc;
+    for (int i = 0; i < cnt; ++i) {
+      const int r = act[i];
+      double f = std::numeric_limits<double>::infinity();  // a failed factor is a failed evaluation
+      double v = -std::numeric_limits<double>::infinity();
+      if (info[i] == 0 && std::isfinite(qv[i])) {
+        v = qv[i];
+        f = -v;
+        for (int e = 0; e < n; ++e) g[e] = -(double)gr[(size_t)i * n + e];
+      }
+      if (v > best[r]) {
+        best[r] = v;
+        for (int e = 0; e < n; ++e) x_out[(size_t)r * n + e] = xs[(size_t)i * n + e];
+      }
+      running[r] = lbfgs_advance(*st[r], f, g.data()) ? 1 : 0;
+    }
+  }
+  // a run whose every evaluation failed (its start batch included) keeps its start with qei_out = -inf, as maximize_ei does
+  for (int r = 0; r < R; ++r) {
+    qei_out[r] = best[r];
+    if (nevals_out) nevals_out[r] = st[r]->nevals;
+  }
+  g_last_error.clear();  // a failed batch inside a round is an evaluation result, not an error of this call
   return HBEGP_OK;
 }
 
@@ -3029,6 +3175,84 @@ int hbegp_sample_posterior_f32(hbegp_model* model, const float* Xs, int m, const
   GUARD_END
 }
 }  // extern "C"
+// argument checks of hbegp_qei_* / hbegp_maximize_qei_*: everything is refused before any device call, the checks that need no
+// model first
+template <typename T>
+static int check_qei(hbegp_model* model, const T* Xb, int B, int q, const T* z, int S, double fmin, double jitter) {
+  if (q < 1 || q > QEI_MAXQ) return fail(HBEGP_EINVAL, "q must be in [1, %d] (got %d)", QEI_MAXQ, q);
+  if (B < 0) return fail(HBEGP_EINVAL, "B must be >= 0 (got %d)", B);
+  if (S < 1) return fail(HBEGP_EINVAL, "S must be >= 1 (got %d)", S);
+  if (!z) return fail(HBEGP_EINVAL, "z is NULL");
+  if (!std::isfinite(fmin)) return fail(HBEGP_EINVAL, "fmin must be finite (got %g)", fmin);
+  if (!(jitter >= 0.0) || !std::isfinite(jitter)) return fail(HBEGP_EINVAL, "jitter must be finite and >= 0 (got %g)", jitter);
+  if (!model) return fail(HBEGP_EINVAL, "NULL model");
+  if (model->is_f32 != (sizeof(T) == 4)) return fail(HBEGP_EINVAL, "model holds %s data", model->is_f32 ? "f32" : "f64");
+  if (B > 0 && !Xb) return fail(HBEGP_EINVAL, "Xb is NULL");
+  const size_t cnt = (size_t)B * q * model->d;
+  for (size_t i = 0; i < cnt; ++i)
+    if (!std::isfinite((double)Xb[i]))
+      return fail(HBEGP_EINVAL, "query point %d has a non-finite coordinate (feature %d)", (int)(i / model->d), (int)(i % model->d));
+  return HBEGP_OK;
+}
+template <typename T>
+static int check_maximize_qei(hbegp_model* model, const T* starts, int R, int q, const double* lo, const double* hi, const T* z, int S,
+                              double fmin, double jitter, int maxeval, T* x_out, double* qei_out) {
+  if (R < 1) return fail(HBEGP_EINVAL, "R must be >= 1 (got %d)", R);
+  if (maxeval < 1) return fail(HBEGP_EINVAL, "maxeval must be >= 1 (got %d)", maxeval);
+  if (!starts || !lo || !hi || !x_out || !qei_out) return fail(HBEGP_EINVAL, "starts/lo/hi/x_out/qei_out is NULL");
+  if (int rc = check_qei<T>(model, starts, R, q, z, S, fmin, jitter)) return rc;
+  const int d = model->d;
+  for (int k = 0; k < d; ++k)
+    if (!(lo[k] <= hi[k])) return fail(HBEGP_EINVAL, "lo[%d] > hi[%d] (%g > %g)", k, k, lo[k], hi[k]);
+  for (int r = 0; r < R; ++r)
+    for (int e = 0; e < q * d; ++e) {
+      const double v = (double)starts[(size_t)r * q * d + e];
+      if (!(v >= lo[e % d] && v <= hi[e % d]))
+        return fail(HBEGP_EINVAL, "start %d lies outside the box (point %d, feature %d: %g)", r, e / d, e % d, v);
+    }
+  return HBEGP_OK;
+}
+extern "C" {
+int hbegp_qei_f64(hbegp_model* model, const double* Xb, int B, int q, const double* z, int S, double fmin_normalized, double jitter,
+                  double* qei, double* grad, int* info) {
+  if (int rc = check_qei<double>(model, Xb, B, q, z, S, fmin_normalized, jitter)) return rc;
+  if (B > 0 && !qei) return fail(HBEGP_EINVAL, "qei is NULL");
+  if (B == 0) return HBEGP_OK;
+  GUARD_BEGIN
+  return model_qei<double>(model, Xb, B, q, z, S, fmin_normalized, jitter, qei, grad, info);
+  GUARD_END
+}
+int hbegp_qei_f32(hbegp_model* model, const float* Xb, int B, int q, const float* z, int S, double fmin_normalized, double jitter,
+                  double* qei, float* grad, int* info) {
+  if (int rc = check_qei<float>(model, Xb, B, q, z, S, fmin_normalized, jitter)) return rc;
+  if (B > 0 && !qei) return fail(HBEGP_EINVAL, "qei is NULL");
+  if (B == 0) return HBEGP_OK;
+  GUARD_BEGIN
+  return model_qei<float>(model, Xb, B, q, z, S, fmin_normalized, jitter, qei, grad, info);
+  GUARD_END
+}
+int hbegp_maximize_qei_f64(hbegp_model* model, const double* starts, int R, int q, const double* lo, const double* hi, const double* z,
+                           int S, double fmin_normalized, double jitter, int maxeval, double* x_out, double* qei_out, int* nevals_out) {
+  if (int rc = check_maximize_qei<double>(model, starts, R, q, lo, hi, z, S, fmin_normalized, jitter, maxeval, x_out, qei_out)) return rc;
+  GUARD_BEGIN
+  return model_maximize_qei<double>(model, starts, R, q, lo, hi, z, S, fmin_normalized, jitter, maxeval, x_out, qei_out, nevals_out);
+  GUARD_END
+}
+int hbegp_maximize_qei_f32(hbegp_model* model, const float* starts, int R, int q, const double* lo, const double* hi, const float* z,
+                           int S, double fmin_normalized, double jitter, int maxeval, float* x_out, double* qei_out, int* nevals_out) {
+  if (int rc = check_maximize_qei<float>(model, starts, R, q, lo, hi, z, S, fmin_normalized, jitter, maxeval, x_out, qei_out)) return rc;
+  GUARD_BEGIN
+  return model_maximize_qei<float>(model, starts, R, q, lo, hi, z, S, fmin_normalized, jitter, maxeval, x_out, qei_out, nevals_out);
+  GUARD_END
+}
+int hbegp_debug_qei_phases(int enable, double* phase_ms) {
+  if (phase_ms)
+    for (int i = 0; i < 2; ++i) phase_ms[i] = t_qei_ms[i];
+  t_time_qei = enable != 0;
+  return HBEGP_OK;
+}
+}  // extern "C"
+
 // argument checks of hbegp_select_batch_*: everything is refused before any device call, the checks that need no model first
 template <typename T>
 static int check_select(hbegp_model* model, const T* Xs, int m, int k, double fmin, const double* lie, int* idx) {

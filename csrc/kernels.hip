@@ -2176,6 +2176,237 @@ template void launch_batch_select<float>(const float*, int, const float*, int, i
                                          double*, double*, int*, int*, double*, float*, float*, hipStream_t);
 
 // =================================================================================================================
+// batch expected improvement by Monte Carlo (hbegp.cpp: model_qei).  One workgroup per batch b of q points
+// (rows b q .. b q + q - 1 of the batched predict's Q [mp][np], mean, dmean [mp][d] and W [d][mp][np]):
+//   Sigma = K** + noise I - Q_b Q_b^T   (fp64: K** from the points, q (q+1) / 2 wave dots over np, ascending lane stride)
+//   L = chol(Sigma) in the LDS, right-looking, one column per step; a pivot that is not > 0 fails the batch (info = 1 + column)
+//   per draw s (one wave, lane a = row a): f_a = sum_{c <= a} L_ac z_sc + mu_a; j_s = argmin (ties to the lowest index, a
+//   fixed xor tree); I_s = max(0, fmin - f_j).  Draws go in chunks of QEI_CH: the waves store j_s (-1: I_s = 0) and I_s in the
+//   LDS, then thread c adds z_sc to Lbar[j_s][c] and counts j_s = c, and thread 64 adds I_s, all in ascending s: no atomics.
+//   reverse (want_grad): Lbar *= -1/S, mubar = -count/S; M = L^T Lbar (thread j owns column j, in place in ascending rows),
+//   Phi(M) (lower, halved diagonal), P = L^-T Phi (column j, in place), X = P L^-1 (row i, in place), Sigmabar = (X + X^T) / 2;
+//   grad[a][k] = mubar_a dmean[a][k] + 2 sum_c Sigmabar_ac (dk(x_a, x_c)/dx_a,k - w_ak . q_c), evaluated as
+//   2 (sum_c Sigmabar_ac dk_ac,k - w_ak . v_a) with v_a = sum_c Sigmabar_ac q_c: one wave per (a, eight k), v_a formed per lane
+//   element in ascending c and dotted with the eight W rows (Q is read d/8 times per point instead of q d times).  psi's
+//   convention at r = 0 makes the c = a term -w_aa . q_a.
+// Everything is fp64 for both element types; the same inputs give the same bits, and a batch reads nothing of another batch.
+// LDS (doubles): scaled points q d, Sigma -> L q^2, Lbar -> X q^2, mu / mubar 2 q, I_s QEI_CH; ints: j_s QEI_CH, the failure flag.
+// =================================================================================================================
+constexpr int QEI_THREADS = 256;
+static_assert(qei_lds_bytes(QEI_MAXQ, MAXD) <= 160 * 1024, "qei_batch_kernel: the largest batch must fit the LDS of one CU");
+
+// not inlined (as bsel_ei): the Matern constants hoisted into the kernel body spilled SGPRs.  r^2 of the scaled points a and c;
+// k(x_a, x_c) + noise [a == c] (kmat_entry in fp64), or c psi(r) (s_a,k - s_c,k) / ell_k (0 at r = 0).
+__device__ __noinline__ double qei_r2(const double* sx, int a, int c, int d) {
+  double r2 = 0.0;
+  for (int k = 0; k < d; ++k) {
+    const double df = sx[a * d + k] - sx[c * d + k];
+    r2 += df * df;
+  }
+  return r2;
+}
+__device__ __noinline__ double qei_kss(double r2, int nu2, double amp, double noise, bool diag) {
+  return kmat_entry<double>(r2, nu2, amp, noise, diag);
+}
+__device__ __noinline__ double qei_dk(double r2, int nu2, double amp, double df, double ell) {
+  return r2 == 0.0 ? 0.0 : amp * matern_psi(r2, nu2) * df / ell;
+}
+
+template <typename T>
+__global__ void __launch_bounds__(QEI_THREADS) qei_batch_kernel(const T* __restrict__ Xs, int q, int d, const T* __restrict__ Q,
+                                                                const T* __restrict__ W, int mp, int np, const T* __restrict__ mean,
+                                                                const T* __restrict__ dmean, const EvalParams* __restrict__ P,
+                                                                double noise, int nu2, const T* __restrict__ z, int S, double fmin,
+                                                                int want_grad, double* __restrict__ qei, T* __restrict__ grad,
+                                                                int* __restrict__ info) {
+  extern __shared__ __align__(16) char smem_raw[];
+  double* sx = reinterpret_cast<double*>(smem_raw);  // [q][d] points / ell
+  double* A = sx + (size_t)q * d;                    // [q][q] Sigma, then L (lower)
+  double* Lb = A + (size_t)q * q;                    // [q][q] Lbar, then M, Phi, P, X
+  double* mu = Lb + (size_t)q * q;                   // [q]
+  double* mub = mu + q;                              // [q]
+  double* Iv = mub + q;                              // [QEI_CH]
+  int* jv = reinterpret_cast<int*>(Iv + QEI_CH);     // [QEI_CH]
+  int* fail = jv + QEI_CH;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = blockIdx.x, r0 = b * q;
+  const double amp = P->amp;
+  for (int e = tid; e < q * d; e += QEI_THREADS) sx[e] = (double)Xs[(size_t)r0 * d + e] / P->ell[e % d];
+  for (int e = tid; e < q * q; e += QEI_THREADS) Lb[e] = 0.0;
+  for (int a = tid; a < q; a += QEI_THREADS) mu[a] = (double)mean[r0 + a];
+  if (tid == 0) *fail = 0;
+  __syncthreads();
+  // Sigma (lower): pair p = (a, c), c <= a, in row order, dealt to the waves round robin
+  {
+    int p = 0;
+    for (int a = 0; a < q; ++a) {
+      for (int c = 0; c <= a; ++c, ++p) {
+        if ((p & 3) != wave) continue;
+        const T* qa = Q + (size_t)(r0 + a) * np;
+        const T* qc = Q + (size_t)(r0 + c) * np;
+        double acc = 0.0;
+        for (int j = lane; j < np; j += 64) acc += (double)qa[j] * (double)qc[j];
+        acc = wave_sum(acc);
+        if (lane == 0) A[a * q + c] = qei_kss(qei_r2(sx, a, c, d), nu2, amp, noise, a == c) - acc;
+      }
+    }
+  }
+  // Cholesky, right-looking
+  for (int j = 0; j < q; ++j) {
+    __syncthreads();
+    if (tid == 0) {
+      const double pv = A[j * q + j];
+      if (pv > 0.0) A[j * q + j] = sqrt(pv);
+      else *fail = j + 1;
+    }
+    __syncthreads();
+    if (*fail) break;
+    const double ljj = A[j * q + j];
+    for (int i = j + 1 + tid; i < q; i += QEI_THREADS) A[i * q + j] /= ljj;
+    __syncthreads();
+    const int w = q - j - 1;
+    for (int e = tid; e < w * w; e += QEI_THREADS) {
+      const int i = j + 1 + e / w, k = j + 1 + e % w;
+      if (k <= i) A[i * q + k] -= A[i * q + j] * A[k * q + j];
+    }
+  }
+  if (*fail) {
+    if (want_grad)
+      for (int e = tid; e < q * d; e += QEI_THREADS) grad[(size_t)r0 * d + e] = T(0);
+    if (tid == 0) {
+      qei[b] = __longlong_as_double(0x7ff8000000000000LL);
+      info[b] = *fail;
+    }
+    return;
+  }
+  // draws
+  double isum = 0.0;
+  int cnt = 0;
+  for (int s0 = 0; s0 < S; s0 += QEI_CH) {
+    const int s1 = min(S, s0 + QEI_CH);
+    for (int s = s0 + wave; s < s1; s += QEI_THREADS / 64) {
+      const double zl = lane < q ? (double)z[(size_t)s * q + lane] : 0.0;
+      double f = 0.0;
+      for (int c = 0; c < q; ++c) {
+        const double zc = __shfl(zl, c, 64);
+        if (c <= lane && lane < q) f += A[lane * q + c] * zc;
+      }
+      double v = lane < q ? f + mu[lane] : __longlong_as_double(0x7ff0000000000000LL);
+      int ix = lane;
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) {
+        const double ov = __shfl_xor(v, off, 64);
+        const int oi = __shfl_xor(ix, off, 64);
+        if (ov < v || (ov == v && oi < ix)) { v = ov; ix = oi; }
+      }
+      if (lane == 0) {
+        const double imp = fmin - v;
+        Iv[s - s0] = imp > 0.0 ? imp : 0.0;
+        jv[s - s0] = imp > 0.0 ? ix : -1;
+      }
+    }
+    __syncthreads();
+    if (tid < q && want_grad) {
+      for (int s = s0; s < s1; ++s) {
+        const int j = jv[s - s0];
+        if (j < 0) continue;
+        if (tid <= j) Lb[j * q + tid] += (double)z[(size_t)s * q + tid];
+        if (j == tid) ++cnt;
+      }
+    }
+    if (tid == 64)
+      for (int s = s0; s < s1; ++s) isum += Iv[s - s0];
+    __syncthreads();
+  }
+  if (tid == 64) {
+    qei[b] = isum / (double)S;
+    info[b] = 0;
+  }
+  if (!want_grad) return;
+  // reverse through the factor
+  if (tid < q) {
+    for (int a = tid; a < q; ++a) Lb[a * q + tid] = -Lb[a * q + tid] / (double)S;
+    mub[tid] = -(double)cnt / (double)S;
+  }
+  __syncthreads();
+  if (tid < q) {  // M = L^T Lbar, column j = tid, rows ascending (row i reads rows k >= i only); Phi: lower, halved diagonal
+    const int j = tid;
+    for (int i = 0; i < q; ++i) {
+      if (i < j) { Lb[i * q + j] = 0.0; continue; }
+      double m = 0.0;
+      for (int k = i; k < q; ++k) m += A[k * q + i] * Lb[k * q + j];
+      Lb[i * q + j] = i == j ? 0.5 * m : m;
+    }
+  }
+  __syncthreads();
+  if (tid < q) {  // P = L^-T Phi, column j = tid, rows descending
+    const int j = tid;
+    for (int i = q - 1; i >= 0; --i) {
+      double p = Lb[i * q + j];
+      for (int k = i + 1; k < q; ++k) p -= A[k * q + i] * Lb[k * q + j];
+      Lb[i * q + j] = p / A[i * q + i];
+    }
+  }
+  __syncthreads();
+  if (tid < q) {  // X = P L^-1, row i = tid, columns descending
+    const int i = tid;
+    for (int j = q - 1; j >= 0; --j) {
+      double x = Lb[i * q + j];
+      for (int k = j + 1; k < q; ++k) x -= Lb[i * q + k] * A[k * q + j];
+      Lb[i * q + j] = x / A[j * q + j];
+    }
+  }
+  __syncthreads();
+  if (tid < q) {  // Sigmabar = (X + X^T) / 2 in place, row i = tid against the rows below it
+    const int i = tid;
+    for (int j = i + 1; j < q; ++j) {
+      const double v = 0.5 * (Lb[i * q + j] + Lb[j * q + i]);
+      Lb[i * q + j] = v;
+      Lb[j * q + i] = v;
+    }
+  }
+  __syncthreads();
+  // gradient: one wave per (a, eight features k0 .. k0 + 7)
+  const int nkc = (d + 7) / 8;
+  for (int item = wave; item < q * nkc; item += QEI_THREADS / 64) {
+    const int a = item / nkc, k0 = (item - a * nkc) * 8;
+    const double* sb = Lb + a * q;  // row a of Sigmabar
+    double acc[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) acc[u] = 0.0;
+    for (int j = lane; j < np; j += 64) {
+      double v = 0.0;  // v_a[j] = sum_c Sigmabar_ac q_c[j]
+      for (int c = 0; c < q; ++c) v += sb[c] * (double)Q[(size_t)(r0 + c) * np + j];
+#pragma unroll
+      for (int u = 0; u < 8; ++u)
+        if (k0 + u < d) acc[u] += (double)W[((size_t)(k0 + u) * mp + r0 + a) * np + j] * v;
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) acc[u] = wave_sum(acc[u]);
+    if (lane == 0) {
+      for (int u = 0; u < 8 && k0 + u < d; ++u) {
+        const int k = k0 + u;
+        const double ell = P->ell[k];
+        double dks = 0.0;
+        for (int c = 0; c < q; ++c) dks += sb[c] * qei_dk(qei_r2(sx, a, c, d), nu2, amp, sx[a * d + k] - sx[c * d + k], ell);
+        grad[(size_t)(r0 + a) * d + k] = (T)(mub[a] * (double)dmean[(size_t)(r0 + a) * d + k] + 2.0 * (dks - acc[u]));
+      }
+    }
+  }
+}
+template <typename T>
+void launch_qei_batch(const T* Xs, int B, int q, int d, const T* Q, const T* W, int mp, int np, const T* mean, const T* dmean,
+                      const EvalParams* P, double noise, int nu2, const T* z, int S, double fmin, int want_grad, double* qei, T* grad,
+                      int* info, hipStream_t s) {
+  hipLaunchKernelGGL((qei_batch_kernel<T>), dim3(B), dim3(QEI_THREADS), qei_lds_bytes(q, d), s, Xs, q, d, Q, W, mp, np, mean, dmean, P,
+                     noise, nu2, z, S, fmin, want_grad, qei, grad, info);
+}
+template void launch_qei_batch<double>(const double*, int, int, int, const double*, const double*, int, int, const double*, const double*,
+                                       const EvalParams*, double, int, const double*, int, double, int, double*, double*, int*, hipStream_t);
+template void launch_qei_batch<float>(const float*, int, int, int, const float*, const float*, int, int, const float*, const float*,
+                                      const EvalParams*, double, int, const float*, int, double, int, double*, float*, int*, hipStream_t);
+
+// =================================================================================================================
 // predict for a handful of candidates (m <= PRED_SMALL_MAX): the caller's acquisition and selection loops issue
 // thousands of single-point predicts per generation (acquisition.rs:46-64, minimize.rs:656-714).  The batched path pads
 // to 128 candidate rows and runs a tile GEMM over all of L^-1 (0.2 ms at n=4096 whatever m is); here L^-1 is read once,
@@ -3079,6 +3310,8 @@ void init_kernels() {
   set_lds_attr(reinterpret_cast<const void*>(&leaf_kernel<double, float>), (int)LeafGeom<double>::LDS_BYTES, "leaf_kernel<f32>: dynamic LDS limit");
   set_lds_attr(reinterpret_cast<const void*>(&leaf_keep_kernel<double, double>), (int)LeafGeom<double>::LDS_BYTES, "leaf_keep_kernel<f64>: dynamic LDS limit");
   set_lds_attr(reinterpret_cast<const void*>(&leaf_keep_kernel<double, float>), (int)LeafGeom<double>::LDS_BYTES, "leaf_keep_kernel<f32>: dynamic LDS limit");
+  set_lds_attr(reinterpret_cast<const void*>(&qei_batch_kernel<double>), (int)qei_lds_bytes(QEI_MAXQ, MAXD), "qei_batch_kernel<f64>: dynamic LDS limit");
+  set_lds_attr(reinterpret_cast<const void*>(&qei_batch_kernel<float>), (int)qei_lds_bytes(QEI_MAXQ, MAXD), "qei_batch_kernel<f32>: dynamic LDS limit");
   init_dag_kernels();
   const int lb = 163840;
   // kmat / gradtrace: 2 d 64 elements of dynamic LDS (64 KiB at d = 64 in f64) beside ~21 KiB of static LDS

@@ -17,6 +17,9 @@
 // on the free variables, projected backtracking (Armijo) line search with safeguarded quadratic interpolation.
 #pragma once
 #include <cmath>
+#if !defined(__HIP_DEVICE_COMPILE__)
+#include <vector>
+#endif
 
 #if defined(__HIPCC__)
 #define LBFGS_HD __host__ __device__
@@ -44,13 +47,24 @@ struct LbfgsState {
   double S[LBFGS_MAXM][LBFGS_MAXN], Y[LBFGS_MAXM][LBFGS_MAXN], rho[LBFGS_MAXM];
 };
 
+// The functions below are templates over the state type St.  LbfgsState (fixed arrays, shared with small_fit_kernel through
+// engine.hpp) keeps its work vectors on the stack; LbfgsStateHost (host only, arrays sized per run) hands out its own, for
+// optimisations over more than LBFGS_MAXN variables (hbegp_maximize_qei: q points of d features).  The arithmetic is the same
+// for both: a host state replays an LbfgsState run bit for bit (tests/cpp/test_lbfgs_host_state.cpp).
+template <class St>
+struct LbfgsWork {
+  static constexpr int N = LBFGS_MAXN;  // stack work vector length
+  LBFGS_HD static double* get(St&, double* stack, int) { return stack; }
+};
+
 namespace lbfgs_detail {
 LBFGS_HD inline double dmin(double a, double b) { return a < b ? a : b; }
 LBFGS_HD inline double dmax(double a, double b) { return a > b ? a : b; }
 LBFGS_HD inline bool finite(double v) { return v - v == 0.0; }
 
 // Proposes the next line-search point xn = clip(x + step d); false: the step no longer changes x.
-LBFGS_HD inline bool propose(LbfgsState& s) {
+template <class St>
+LBFGS_HD inline bool propose(St& s) {
   const int n = s.n;
   double gs = 0, moved = 0;
   for (int i = 0; i < n; ++i) {
@@ -66,11 +80,14 @@ LBFGS_HD inline bool propose(LbfgsState& s) {
 
 // Start of an outer iteration at (x, f, g): convergence test, search direction, first trial point.
 // Returns the next phase: 1 (xn is to be evaluated) or 2 (go on to the burn / finish).
-LBFGS_HD inline int begin_iteration(LbfgsState& s) {
+template <class St>
+LBFGS_HD inline int begin_iteration(St& s) {
   const int n = s.n;
   for (;;) {
     if (s.nevals >= s.maxeval) return 2;
-    double pg[LBFGS_MAXN], q[LBFGS_MAXN], a[LBFGS_MAXM];
+    double pg_stack[LbfgsWork<St>::N], q_stack[LbfgsWork<St>::N], a[LBFGS_MAXM];
+    double* pg = LbfgsWork<St>::get(s, pg_stack, 0);
+    double* q = LbfgsWork<St>::get(s, q_stack, 1);
     double pgnorm = 0;
     for (int i = 0; i < n; ++i) {
       const bool at_lo = s.x[i] <= s.lo[i] && s.g[i] > 0, at_hi = s.x[i] >= s.hi[i] && s.g[i] < 0;
@@ -137,7 +154,8 @@ LBFGS_HD inline int begin_iteration(LbfgsState& s) {
 }  // namespace lbfgs_detail
 
 // Sets the run up at x0 (clipped into the box); the first point to evaluate is st.x.
-LBFGS_HD inline void lbfgs_begin(LbfgsState& s, const double* x0, const double* lo, const double* hi, int n, int maxeval, int memory,
+template <class St>
+LBFGS_HD inline void lbfgs_begin(St& s, const double* x0, const double* lo, const double* hi, int n, int maxeval, int memory,
                                  double pgtol, double ftol, bool fixed_work) {
   s.n = n;
   s.maxeval = maxeval;
@@ -158,11 +176,13 @@ LBFGS_HD inline void lbfgs_begin(LbfgsState& s, const double* x0, const double* 
 }
 
 // The point the caller has to evaluate next (valid while phase != 3).
-LBFGS_HD inline const double* lbfgs_request(const LbfgsState& s) { return s.phase == 1 ? s.xn : s.x; }
+template <class St>
+LBFGS_HD inline const double* lbfgs_request(const St& s) { return s.phase == 1 ? s.xn : s.x; }
 
 // Feeds the evaluation of lbfgs_request(): f (may be +inf / NaN: a failed evaluation, grad then ignored) and grad.
 // Returns true while another evaluation is wanted.
-LBFGS_HD inline bool lbfgs_advance(LbfgsState& s, double fe, const double* ge) {
+template <class St>
+LBFGS_HD inline bool lbfgs_advance(St& s, double fe, const double* ge) {
   using namespace lbfgs_detail;
   const int n = s.n;
   ++s.nevals;
@@ -178,7 +198,9 @@ LBFGS_HD inline bool lbfgs_advance(LbfgsState& s, double fe, const double* ge) {
     if (finite(fn) && fn <= s.f + 1e-4 * s.gs) {
       // accepted: curvature pair, move
       ++s.iterations;
-      double sv[LBFGS_MAXN], yv[LBFGS_MAXN];
+      double sv_stack[LbfgsWork<St>::N], yv_stack[LbfgsWork<St>::N];
+      double* sv = LbfgsWork<St>::get(s, sv_stack, 2);
+      double* yv = LbfgsWork<St>::get(s, yv_stack, 3);
       double sy = 0, ss = 0, yy = 0;
       for (int i = 0; i < n; ++i) {
         sv[i] = s.xn[i] - s.x[i];
@@ -250,5 +272,43 @@ LBFGS_HD inline bool lbfgs_advance(LbfgsState& s, double fe, const double* ge) {
   s.phase = 3;
   return false;
 }
+
+#if !defined(__HIP_DEVICE_COMPILE__)
+// Host-only state of the same machine for any n: LbfgsState's fields, its arrays (and the four work vectors that LbfgsState keeps
+// on the stack) in one heap buffer of (10 + 2 LBFGS_MAXM) n doubles.  Not copyable: the pointers point into its own buffer.
+struct LbfgsStateHost {
+  int n, maxeval, m;
+  double pgtol, ftol;
+  int fixed_work;
+  double *lo, *hi;
+  int phase;
+  int nevals, iterations, converged;
+  int hcount;
+  double f, step, gs;
+  double *x, *g, *xn, *d;
+  double* S[LBFGS_MAXM];
+  double* Y[LBFGS_MAXM];
+  double rho[LBFGS_MAXM];
+  double* work[4];
+  explicit LbfgsStateHost(int nvars) : buf_((size_t)(10 + 2 * LBFGS_MAXM) * (nvars < 1 ? 1 : nvars), 0.0) {
+    const size_t w = (size_t)(nvars < 1 ? 1 : nvars);
+    double* p = buf_.data();
+    auto take = [&]() { double* r = p; p += w; return r; };
+    lo = take(); hi = take(); x = take(); g = take(); xn = take(); d = take();
+    for (auto& v : work) v = take();
+    for (int h = 0; h < LBFGS_MAXM; ++h) { S[h] = take(); Y[h] = take(); }
+  }
+  LbfgsStateHost(const LbfgsStateHost&) = delete;
+  LbfgsStateHost& operator=(const LbfgsStateHost&) = delete;
+
+ private:
+  std::vector<double> buf_;
+};
+template <>
+struct LbfgsWork<LbfgsStateHost> {
+  static constexpr int N = 1;
+  static double* get(LbfgsStateHost& s, double*, int which) { return s.work[which]; }
+};
+#endif
 
 }  // namespace hbegp

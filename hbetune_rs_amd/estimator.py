@@ -308,6 +308,24 @@ class SurrogateModelGPR:
         means, _, _ = self.fitted.predict(x[idx], want_variance=False) if len(idx) else (np.zeros(0, self.dtype), None, 0)
         return idx, self.y_norm.project_location_from_normalized(means), ei
 
+    # Batch expected improvement by Monte Carlo (opt-in; nothing the estimator suggests by default uses it).
+    def qei_a(self, x, fmin, n_samples, rng, jitter=0.0, want_grad=True):
+        """q-EI of batches x [B, q, d] (or [q, d]) in the normalised space (FittedKernel.qei), fmin projected as predict_mean_ei_a
+        projects it, z [n_samples, q] from rng.standard_normal.  Returns (qei[B], grad[B, q, d] or None, info[B])."""
+        x = np.asarray(x, dtype=self.dtype)
+        q = x.shape[-2]
+        z = rng.standard_normal((int(n_samples), q)).astype(self.dtype)
+        return self.fitted.qei(x, z, self._fmin_normalized(fmin), jitter=jitter, want_grad=want_grad)
+
+    def maximize_qei(self, starts, bounds, fmin, n_samples, rng, jitter=0.0, maxeval=150):
+        """Bounded L-BFGS ascents of q-EI from every batch of `starts` [R, q, d] (the box: `bounds` = [(lo, hi)] per feature), all
+        runs in lockstep with one z [n_samples, q] from rng.standard_normal.  Returns (x[R, q, d], qei[R], nevals[R])."""
+        starts = np.asarray(starts, dtype=self.dtype)
+        lo = np.array([b[0] for b in bounds], dtype=np.float64)
+        hi = np.array([b[1] for b in bounds], dtype=np.float64)
+        z = rng.standard_normal((int(n_samples), starts.shape[-2])).astype(self.dtype)
+        return self.fitted.maximize_qei(starts, lo, hi, z, self._fmin_normalized(fmin), jitter=jitter, maxeval=maxeval)
+
     # Batched forms of the scalar trait methods (SURVEY.md 8f rank 1: the acquisition loops call these once per generation
     # instead of m single-point predicts, each of which reads all of K^-1).
     def predict_confidence_bound_a(self, x, cb):
@@ -383,6 +401,28 @@ def acquire_by_batch_ei(candidates, model, k, fmin, lie=None):
     if c.ndim != 2:
         raise ValueError("candidates must be [m, n_features]")
     return model.select_batch_a(c, int(k), fmin, lie=lie)
+
+
+def acquire_by_qei(candidates, model, q, fmin, rng, n_samples=512, n_restarts=8, maxeval=150, jitter=0.0):
+    """Batch acquisition by Monte Carlo q-EI: the q points are optimised jointly in the box the candidates span.  The starts are the
+    greedy kriging-believer batch over the candidates (select_batch_a) and n_restarts - 1 random q-subsets of them; each start is
+    one bounded L-BFGS ascent of q-EI with the same normals z [n_samples, q] (rng.standard_normal).  Returns (x[q, n_features], the
+    batch's q-EI in the normalised space).  Opt-in: nothing the estimator suggests by default calls it."""
+    c = np.asarray(candidates, dtype=model.dtype)
+    if c.ndim != 2:
+        raise ValueError("candidates must be [m, n_features]")
+    q = int(q)
+    if not 1 <= q <= c.shape[0]:
+        raise ValueError("q must lie in [1, number of candidates]")
+    idx, _, _ = model.select_batch_a(c, q, fmin)
+    starts = [c[idx]]
+    for _ in range(max(0, int(n_restarts) - 1)):
+        u = rng.uniform(0.0, 1.0, c.shape[0])
+        starts.append(c[np.argsort(u, kind="stable")[:q]])
+    bounds = list(zip(c.min(axis=0).astype(np.float64), c.max(axis=0).astype(np.float64)))
+    x, qei, _ = model.maximize_qei(np.stack(starts), bounds, fmin, n_samples, rng, jitter=jitter, maxeval=maxeval)
+    best = int(np.argmax(qei))  # ties to the first run: the greedy batch
+    return x[best], float(qei[best])
 
 
 class FitnessOperator:

@@ -378,6 +378,51 @@ class FittedKernel:
                       _lib.aptr(mean), _lib.aptr(var)))
         return idx.astype(np.int64), ei, mean, var
 
+    def qei(self, x, z, fmin_normalized, jitter=0.0, want_grad=True, raise_not_pd=False):
+        """Batch expected improvement by Monte Carlo (hbegp_qei_*) in the normalised y space: x [B, q, d] (or [q, d]: B = 1) batches
+        of q points, z [S, q] the caller's standard normals, shared by every batch.  Returns (qei[B], grad[B, q, d] or None,
+        info[B]): a batch whose Sigma is not positive definite has qei NaN, a zero gradient and info = 1 + the failed column; that
+        raises HbegpError (code NOT_PD) only with raise_not_pd."""
+        lib = _lib.load()
+        x = _lib.as_c(x, self.dtype)
+        if x.ndim == 2:
+            x = x[None]
+        assert x.ndim == 3 and x.shape[2] == self.d, x.shape
+        B, q = x.shape[0], x.shape[1]
+        z = _lib.as_c(np.atleast_2d(z), self.dtype)
+        assert z.ndim == 2 and z.shape[1] == q, (z.shape, q)
+        qei = np.zeros(B)
+        grad = np.zeros((B, q, self.d), dtype=self.dtype) if want_grad else None
+        info = np.zeros(B, dtype=np.int32)
+        fn = getattr(lib, f"hbegp_qei_{self._sfx}")
+        rc = fn(self._h, _lib.aptr(x), B, q, _lib.aptr(z), z.shape[0], float(fmin_normalized), float(jitter), _lib.dptr(qei),
+                _lib.aptr(grad), info.ctypes.data_as(C.POINTER(C.c_int)))
+        _lib.check(rc, allow=() if raise_not_pd else (_lib.NOT_PD,))
+        return qei, grad, info
+
+    def maximize_qei(self, starts, lo, hi, z, fmin_normalized, jitter=0.0, maxeval=150):
+        """R bounded L-BFGS ascents of q-EI (hbegp_maximize_qei_*), each over a whole batch of q points in the box [lo, hi], with
+        the same z [S, q] every round.  starts: [R, q, d] inside the box.  Returns (x[R, q, d], qei[R], nevals[R]): each run's best
+        batch."""
+        lib = _lib.load()
+        starts = _lib.as_c(starts, self.dtype)
+        if starts.ndim == 2:
+            starts = starts[None]
+        assert starts.ndim == 3 and starts.shape[2] == self.d, starts.shape
+        R, q = starts.shape[0], starts.shape[1]
+        lo = _lib.as_c(lo, np.float64)
+        hi = _lib.as_c(hi, np.float64)
+        assert lo.shape == (self.d,) and hi.shape == (self.d,)
+        z = _lib.as_c(np.atleast_2d(z), self.dtype)
+        assert z.ndim == 2 and z.shape[1] == q, (z.shape, q)
+        x = np.zeros_like(starts)
+        qei = np.zeros(R)
+        nevals = np.zeros(R, dtype=np.int32)
+        fn = getattr(lib, f"hbegp_maximize_qei_{self._sfx}")
+        _lib.check(fn(self._h, _lib.aptr(starts), R, q, _lib.dptr(lo), _lib.dptr(hi), _lib.aptr(z), z.shape[0], float(fmin_normalized),
+                      float(jitter), int(maxeval), _lib.aptr(x), _lib.dptr(qei), nevals.ctypes.data_as(C.POINTER(C.c_int))))
+        return x, qei, nevals
+
     def release(self):
         if self._h:
             _lib.load().hbegp_model_release(self._h)

@@ -274,6 +274,46 @@ int hbegp_select_batch_f64(hbegp_model* model, const double* Xs, int m, int k, d
 int hbegp_select_batch_f32(hbegp_model* model, const float* Xs, int m, int k, double fmin_normalized, const double* lie, int* idx,
                            double* ei, float* mean_out, float* var_out);
 
+/* Batch expected improvement by Monte Carlo (q-EI) in the normalised y space like hbegp_predict_*, for B batches of q points:
+ * Xb[B*q*d] (batch b = rows b*q .. b*q + q - 1, feature space), z[S*q] the CALLER's standard normals (draw s = row s), shared by
+ * every batch (common random numbers; the RNG stays on the caller side).  Per batch b:
+ *   mu_a = the batched predict mean;  Sigma = K**(X_b, X_b) + (1e-5 + jitter) I - Q_b^T Q_b, the matrix hbegp_predict_cov returns
+ *   for those q points, to rounding (here formed by fp64 dots);  L = chol(Sigma), lower, factored in fp64 for both element types;
+ *   per draw s: f_s = mu + L z_s,  j_s = argmin_a f_s,a (ties to the lowest index, as hbegp_sample_posterior),
+ *   I_s = max(0, fmin - f_s,j_s);   qei[b] = (1/S) sum_s I_s, summed in fp64 in ascending s.
+ * grad[B*q*d] (may be NULL): the exact gradient of that sample average for the given z (defined almost everywhere: ties and
+ * I_s = 0 are measure-zero kinks), reverse mode in fp64:
+ *   mubar_a = -(1/S) #{s : I_s > 0, j_s = a},   Lbar_ac = -(1/S) sum_{s : I_s > 0, j_s = a} z_s,c  (c <= a),
+ *   X = L^-T Phi(L^T Lbar) L^-1 (Phi: lower triangle, halved diagonal; Murray 2016),  Sigmabar = (X + X^T) / 2,
+ *   dqEI/dx_a,k = mubar_a dmu_a/dx_a,k + 2 sum_c Sigmabar_ac (dk(x_a, x_c)/dx_a,k - w_a,k . q_c),
+ *   w_a,k = L_K^-1 dk*_a / dx_a,k (hbegp_predict_grad's bounded form), q_c = L_K^-1 k*_c; dk with hbegp_predict_grad's psi and its
+ *   convention at r = 0, so the c = a term is -w_a,a . q_a; no derivative of the jitter.  For q = 1 this is
+ *   (1/S) sum_{I_s > 0} (-dmean - z_s dvar / (2 sigma)) with hbegp_predict_grad's dmean / dvar.
+ * info[B] (may be NULL): 0, or 1 + the first column whose pivot failed in that batch's factor; such a batch gets qei NaN and a zero
+ * gradient, the others stay valid, and the call returns HBEGP_NOT_PD after writing every output.  No automatic jitter increase.
+ * 1 <= q <= 64, S >= 1, B >= 0 (B = 0 is a no-op).  HBEGP_EINVAL (before any device call) for a NULL model, q out of range, B < 0,
+ * S < 1, a NULL z, a non-finite fmin, a jitter < 0 or not finite, a non-finite coordinate or a model of the other element type.
+ * Work that does not fit in device memory (Kstar / Q, and with a gradient G and W: d B q n_p elements each) is HBEGP_ENOMEM.
+ * Fixed-order sums, no atomics: the same call gives the same bits, and a batch's outputs do not depend on the other batches of the
+ * call.  Serialised per model like predict: threads may call it on one model at once. */
+int hbegp_qei_f64(hbegp_model* model, const double* Xb, int B, int q, const double* z, int S, double fmin_normalized, double jitter,
+                  double* qei, double* grad, int* info);
+int hbegp_qei_f32(hbegp_model* model, const float* Xb, int B, int q, const float* z, int S, double fmin_normalized, double jitter,
+                  double* qei, float* grad, int* info);
+
+/* Maximise q-EI over batches: R bounded L-BFGS ascents (the fit optimiser's method and constants, lbfgs_step.hpp with a host state
+ * sized per run), each over the q*d coordinates of one batch, [lo, hi] (d entries) applied to every point; run r starts at
+ * starts[r*q*d ..] (inside the box).  The runs advance in lockstep: one hbegp_qei call per round over the runs still going, with
+ * the same z every round (a deterministic sample-average objective).  A batch whose factor fails is a failed evaluation (objective
+ * +inf); f32 points are rounded into the box.  x_out[R*q*d]: the best batch each run evaluated, qei_out[R] its qEI (never below
+ * the qEI at the start; bit for bit hbegp_qei at x_out; a run whose every evaluation failed, its start included, keeps the start
+ * with qei_out = -inf), nevals_out[R] (may be NULL) the evaluations used (<= maxeval).
+ * HBEGP_EINVAL for R < 1, maxeval < 1, lo > hi, a start outside the box, or any hbegp_qei check. */
+int hbegp_maximize_qei_f64(hbegp_model* model, const double* starts, int R, int q, const double* lo, const double* hi, const double* z,
+                           int S, double fmin_normalized, double jitter, int maxeval, double* x_out, double* qei_out, int* nevals_out);
+int hbegp_maximize_qei_f32(hbegp_model* model, const float* starts, int R, int q, const double* lo, const double* hi, const float* z,
+                           int S, double fmin_normalized, double jitter, int maxeval, float* x_out, double* qei_out, int* nevals_out);
+
 int hbegp_model_info(const hbegp_model* model, int* n, int* d, int* is_f32, double* nu, double* lml);
 /* theta[p] (log space, clamped), alpha[n], kinv[n*n] full symmetric; any pointer may be NULL. */
 int hbegp_model_get_f64(hbegp_model* model, double* theta, double* alpha, double* kinv);
@@ -330,6 +370,10 @@ int hbegp_debug_posterior_phases(int enable, double* phase_ms);
  * calling thread's last timed hbegp_select_batch_* call -- Sigma (upload, K*, mean, Q, kmat, Q Q^T, mirror), the selection
  * kernel -- in milliseconds; then enable != 0 makes this thread's later selection calls timed. */
 int hbegp_debug_batch_select_phases(int enable, double* phase_ms);
+/* ---- timing hook (tools/qei_bench.py): phase_ms[2] (may be NULL) receives the device time of the phases of the calling thread's
+ * last timed hbegp_qei_* call -- the shared launches (upload of the points, Kstar, mean, Q; with a gradient dmean, G, W; upload of
+ * z), the qEI kernel -- in milliseconds; then enable != 0 makes this thread's later qEI calls timed. */
+int hbegp_debug_qei_phases(int enable, double* phase_ms);
 
 #ifdef __cplusplus
 }

@@ -62,6 +62,13 @@ template <> struct Abi<double> {
   }
   static int select_batch(hbegp_model* m, const double* xs, int n, int k, double fmin, const double* lie, int* idx, double* ei, double* mean,
                           double* var) { return hbegp_select_batch_f64(m, xs, n, k, fmin, lie, idx, ei, mean, var); }
+  static int qei(hbegp_model* m, const double* xb, int b, int q, const double* z, int s, double fmin, double j, double* v, double* g, int* info) {
+    return hbegp_qei_f64(m, xb, b, q, z, s, fmin, j, v, g, info);
+  }
+  static int maximize_qei(hbegp_model* m, const double* st, int r, int q, const double* lo, const double* hi, const double* z, int s, double fmin,
+                          double j, int maxeval, double* x, double* v, int* ne) {
+    return hbegp_maximize_qei_f64(m, st, r, q, lo, hi, z, s, fmin, j, maxeval, x, v, ne);
+  }
   static int get(hbegp_model* m, double* t, double* a, double* ki) { return hbegp_model_get_f64(m, t, a, ki); }
 };
 template <> struct Abi<float> {
@@ -84,6 +91,13 @@ template <> struct Abi<float> {
   }
   static int select_batch(hbegp_model* m, const float* xs, int n, int k, double fmin, const double* lie, int* idx, double* ei, float* mean,
                           float* var) { return hbegp_select_batch_f32(m, xs, n, k, fmin, lie, idx, ei, mean, var); }
+  static int qei(hbegp_model* m, const float* xb, int b, int q, const float* z, int s, double fmin, double j, double* v, float* g, int* info) {
+    return hbegp_qei_f32(m, xb, b, q, z, s, fmin, j, v, g, info);
+  }
+  static int maximize_qei(hbegp_model* m, const float* st, int r, int q, const double* lo, const double* hi, const float* z, int s, double fmin,
+                          double j, int maxeval, float* x, double* v, int* ne) {
+    return hbegp_maximize_qei_f32(m, st, r, q, lo, hi, z, s, fmin, j, maxeval, x, v, ne);
+  }
   static int get(hbegp_model* m, double* t, float* a, float* ki) { return hbegp_model_get_f32(m, t, a, ki); }
 };
 }  // namespace detail
@@ -169,6 +183,19 @@ class FittedKernel {
   void select_batch(const A* xs, int m, int k, double fmin_normalized, int* idx, double* ei = nullptr, A* mean = nullptr,
                     A* var = nullptr, const double* lie = nullptr) const {
     check(detail::Abi<A>::select_batch(h_, xs, m, k, fmin_normalized, lie, idx, ei, mean, var));
+  }
+  // Monte Carlo q-EI of B batches xb[B*q*d] with the caller's normals z[S*q]: qei[B]; grad[B*q*d] and info[B] may be nullptr.
+  // Returns HBEGP_OK or HBEGP_NOT_PD (some batch's Sigma did not factor: its qei is NaN, info says where); throws otherwise
+  int qei(const A* xb, int B, int q, const A* z, int S, double fmin_normalized, double* qei, A* grad = nullptr, int* info = nullptr,
+          double jitter = 0.0) const {
+    const int rc = detail::Abi<A>::qei(h_, xb, B, q, z, S, fmin_normalized, jitter, qei, grad, info);
+    if (rc != HBEGP_NOT_PD) check(rc);
+    return rc;
+  }
+  // R bounded L-BFGS ascents of q-EI over whole batches from starts[R*q*d] inside [lo, hi]; x_out[R*q*d], qei_out[R], nevals[R]
+  void maximize_qei(const A* starts, int R, int q, const double* lo, const double* hi, const A* z, int S, double fmin_normalized,
+                    int maxeval, A* x_out, double* qei_out, int* nevals = nullptr, double jitter = 0.0) const {
+    check(detail::Abi<A>::maximize_qei(h_, starts, R, q, lo, hi, z, S, fmin_normalized, jitter, maxeval, x_out, qei_out, nevals));
   }
   double lml() const { return lml_; }
   double noise() const { return std::exp(theta_[0]); }

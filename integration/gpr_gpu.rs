@@ -143,6 +143,24 @@ extern "C" {
         model: *mut HbegpModel, xs: *const c_float, m: c_int, k: c_int, fmin_normalized: c_double, lie: *const c_double,
         idx: *mut c_int, ei: *mut c_double, mean_out: *mut c_float, var_out: *mut c_float,
     ) -> c_int;
+    fn hbegp_qei_f64(
+        model: *mut HbegpModel, xb: *const c_double, b: c_int, q: c_int, z: *const c_double, s: c_int, fmin_normalized: c_double,
+        jitter: c_double, qei: *mut c_double, grad: *mut c_double, info: *mut c_int,
+    ) -> c_int;
+    fn hbegp_qei_f32(
+        model: *mut HbegpModel, xb: *const c_float, b: c_int, q: c_int, z: *const c_float, s: c_int, fmin_normalized: c_double,
+        jitter: c_double, qei: *mut c_double, grad: *mut c_float, info: *mut c_int,
+    ) -> c_int;
+    fn hbegp_maximize_qei_f64(
+        model: *mut HbegpModel, starts: *const c_double, r: c_int, q: c_int, lo: *const c_double, hi: *const c_double,
+        z: *const c_double, s: c_int, fmin_normalized: c_double, jitter: c_double, maxeval: c_int, x_out: *mut c_double,
+        qei_out: *mut c_double, nevals_out: *mut c_int,
+    ) -> c_int;
+    fn hbegp_maximize_qei_f32(
+        model: *mut HbegpModel, starts: *const c_float, r: c_int, q: c_int, lo: *const c_double, hi: *const c_double,
+        z: *const c_float, s: c_int, fmin_normalized: c_double, jitter: c_double, maxeval: c_int, x_out: *mut c_float,
+        qei_out: *mut c_double, nevals_out: *mut c_int,
+    ) -> c_int;
     fn hbegp_model_info(
         model: *const HbegpModel, n: *mut c_int, d: *mut c_int, is_f32: *mut c_int, nu: *mut c_double, lml: *mut c_double,
     ) -> c_int;
@@ -220,6 +238,16 @@ pub trait GpuScalar: Scalar + sealed::Sealed {
         model: *mut HbegpModel, xs: *const Self, m: c_int, k: c_int, fmin_normalized: f64, lie: *const f64, idx: *mut c_int,
         ei: *mut f64, mean_out: *mut Self, var_out: *mut Self,
     ) -> c_int;
+    /// `hbegp_qei_*`
+    unsafe fn ffi_qei(
+        model: *mut HbegpModel, xb: *const Self, b: c_int, q: c_int, z: *const Self, s: c_int, fmin_normalized: f64, jitter: f64,
+        qei: *mut f64, grad: *mut Self, info: *mut c_int,
+    ) -> c_int;
+    /// `hbegp_maximize_qei_*`
+    unsafe fn ffi_maximize_qei(
+        model: *mut HbegpModel, starts: *const Self, r: c_int, q: c_int, lo: *const f64, hi: *const f64, z: *const Self, s: c_int,
+        fmin_normalized: f64, jitter: f64, maxeval: c_int, x_out: *mut Self, qei_out: *mut f64, nevals_out: *mut c_int,
+    ) -> c_int;
 }
 
 impl GpuScalar for f64 {
@@ -276,6 +304,18 @@ impl GpuScalar for f64 {
     ) -> c_int {
         hbegp_select_batch_f64(model, xs, m, k, fmin_normalized, lie, idx, ei, mean_out, var_out)
     }
+    unsafe fn ffi_qei(
+        model: *mut HbegpModel, xb: *const f64, b: c_int, q: c_int, z: *const f64, s: c_int, fmin_normalized: f64, jitter: f64,
+        qei: *mut f64, grad: *mut f64, info: *mut c_int,
+    ) -> c_int {
+        hbegp_qei_f64(model, xb, b, q, z, s, fmin_normalized, jitter, qei, grad, info)
+    }
+    unsafe fn ffi_maximize_qei(
+        model: *mut HbegpModel, starts: *const f64, r: c_int, q: c_int, lo: *const f64, hi: *const f64, z: *const f64, s: c_int,
+        fmin_normalized: f64, jitter: f64, maxeval: c_int, x_out: *mut f64, qei_out: *mut f64, nevals_out: *mut c_int,
+    ) -> c_int {
+        hbegp_maximize_qei_f64(model, starts, r, q, lo, hi, z, s, fmin_normalized, jitter, maxeval, x_out, qei_out, nevals_out)
+    }
 }
 
 impl GpuScalar for f32 {
@@ -331,6 +371,18 @@ impl GpuScalar for f32 {
         ei: *mut f64, mean_out: *mut f32, var_out: *mut f32,
     ) -> c_int {
         hbegp_select_batch_f32(model, xs, m, k, fmin_normalized, lie, idx, ei, mean_out, var_out)
+    }
+    unsafe fn ffi_qei(
+        model: *mut HbegpModel, xb: *const f32, b: c_int, q: c_int, z: *const f32, s: c_int, fmin_normalized: f64, jitter: f64,
+        qei: *mut f64, grad: *mut f32, info: *mut c_int,
+    ) -> c_int {
+        hbegp_qei_f32(model, xb, b, q, z, s, fmin_normalized, jitter, qei, grad, info)
+    }
+    unsafe fn ffi_maximize_qei(
+        model: *mut HbegpModel, starts: *const f32, r: c_int, q: c_int, lo: *const f64, hi: *const f64, z: *const f32, s: c_int,
+        fmin_normalized: f64, jitter: f64, maxeval: c_int, x_out: *mut f32, qei_out: *mut f64, nevals_out: *mut c_int,
+    ) -> c_int {
+        hbegp_maximize_qei_f32(model, starts, r, q, lo, hi, z, s, fmin_normalized, jitter, maxeval, x_out, qei_out, nevals_out)
     }
 }
 
@@ -591,6 +643,51 @@ impl<A: GpuScalar> SurrogateModelGpu<A> {
             panic!("hbegp_select_batch failed: {}", last_error());
         }
         (idx.into_iter().map(|i| i as usize).collect(), ei)
+    }
+
+    /// Monte Carlo q-EI (`hbegp_qei_*`) of `b` batches of q points, `xb` [b q, d] (batch i = rows i q .. i q + q - 1), with the
+    /// caller's normals `z` [S, q] shared by the batches, in the normalised y space.  Returns (qei[b], grad[b q, d], info[b]): a
+    /// batch whose Sigma did not factor has qei NaN, a zero gradient and info = 1 + the failed column.  Opt-in.
+    pub fn qei_normalized(&self, xb: ArrayView2<A>, b: usize, z: ArrayView2<A>, fmin_normalized: f64, jitter: f64)
+        -> (Vec<f64>, Array2<A>, Vec<c_int>) {
+        let (rows, d) = xb.dim();
+        let (s, q) = z.dim();
+        assert!(q > 0 && rows == b * q, "xb must hold b batches of q = z.ncols() points");
+        let xb = xb.as_standard_layout();
+        let z = z.as_standard_layout();
+        let mut qei = vec![0.0f64; b];
+        let mut grad = Array2::<A>::zeros((rows, d));
+        let mut info: Vec<c_int> = vec![0; b];
+        let rc = unsafe {
+            A::ffi_qei(self.handle, xb.as_ptr(), b as c_int, q as c_int, z.as_ptr(), s as c_int, fmin_normalized, jitter,
+                       qei.as_mut_ptr(), grad.as_mut_ptr(), info.as_mut_ptr())
+        };
+        if rc != HBEGP_OK && rc != HBEGP_NOT_PD {
+            panic!("hbegp_qei failed: {}", last_error());
+        }
+        (qei, grad, info)
+    }
+
+    /// `hbegp_maximize_qei_*`: `r` bounded L-BFGS ascents of q-EI over whole batches from `starts` [r q, d] inside [lo, hi], with the
+    /// same normals `z` [S, q] every round.  Returns (x[r q, d], qei[r], nevals[r]): each run's best batch.  Opt-in.
+    pub fn maximize_qei_normalized(&self, starts: ArrayView2<A>, r: usize, lo: &[f64], hi: &[f64], z: ArrayView2<A>,
+                                   fmin_normalized: f64, jitter: f64, maxeval: usize) -> (Array2<A>, Vec<f64>, Vec<c_int>) {
+        let (rows, d) = starts.dim();
+        let (s, q) = z.dim();
+        assert!(q > 0 && rows == r * q && lo.len() == d && hi.len() == d, "starts must hold r batches of q = z.ncols() points");
+        let starts = starts.as_standard_layout();
+        let z = z.as_standard_layout();
+        let mut x = Array2::<A>::zeros((rows, d));
+        let mut qei = vec![0.0f64; r];
+        let mut nevals: Vec<c_int> = vec![0; r];
+        let rc = unsafe {
+            A::ffi_maximize_qei(self.handle, starts.as_ptr(), r as c_int, q as c_int, lo.as_ptr(), hi.as_ptr(), z.as_ptr(), s as c_int,
+                                fmin_normalized, jitter, maxeval as c_int, x.as_mut_ptr(), qei.as_mut_ptr(), nevals.as_mut_ptr())
+        };
+        if rc != HBEGP_OK {
+            panic!("hbegp_maximize_qei failed: {}", last_error());
+        }
+        (x, qei, nevals)
     }
 
     /// Batched `predict_confidence_bound` (gpr.rs:94-112 for every row): one device call instead of one per individual
