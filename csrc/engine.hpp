@@ -228,6 +228,25 @@ void launch_qei_batch(const T* Xs, int B, int q, int d, const T* Q, const T* W, 
                       const EvalParams* P, double noise, int nu2, const T* z, int S, double fmin, int want_grad, double* qei, T* grad,
                       int* info, hipStream_t s);
 
+// posterior sample paths (hbegp_paths_*; kernels.hip: paths_project_kernel, paths_eval_kernel).  omT [d][F] = om0^T / ell, phase [F],
+// Wf [S][F] are fp64 for both element types; Vt, Rt [Sp][np] hold one path per row (the tile GEMMs' operand layout).
+//   scale_omega: omT from the caller's unit-length-scale om0 [F][d]
+//   project:     Rt[s][i] = y_i - sqrt(2c/F) sum_j Wf[s][j] cos(om_j . x_i + b_j) - sqrt(sigma^2) eps[s][i] (eps [S][n] or null), zero
+//                padding; part: paths_project_chunks(F, n, S) * S * n doubles
+//   eval:        f [S][m], df [S][m][d] (want_grad) at Xs [m][d] (per_path = 0) or [S][m][d] (per_path = 1);
+//                part: paths_eval_chunks(n, F) * S * m * (d + 1) doubles
+int paths_project_chunks(int F, int n, int S, int* fch_out = nullptr);
+int paths_eval_chunks(int n, int F, int* nchd_out = nullptr);
+template <typename T>
+void launch_paths_scale_omega(const T* om0, int F, int d, const EvalParams* P, double* omT, hipStream_t s);
+template <typename T>
+void launch_paths_project(const T* X, int n, int d, int np, const double* omT, const double* phase, int F, const double* Wf, int S, int Sp,
+                          const T* y, const T* eps, const EvalParams* P, double* part, T* Rt, hipStream_t s);
+template <typename T>
+void launch_paths_eval(const T* Xs, int m, int per_path, int S, const T* X, int n, int d, int np, int nu2, const EvalParams* P, const T* Vt,
+                       const double* omT, const double* phase, const double* Wf, int F, int want_grad, double* part, T* f, T* df,
+                       hipStream_t s);
+
 // predict for m <= PRED_SMALL_MAX candidates without the 128-row padding: reads L^-1 once (row dots against the m
 // cross-kernel vectors).  Ks: [PRED_SMALL_MAX][np] scratch, pmean: [(np+255)/256][PRED_SMALL_MAX], w: [n][PRED_SMALL_MAX].
 constexpr int PRED_SMALL_MAX = 16;

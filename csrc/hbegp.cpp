@@ -1624,6 +1624,7 @@ struct hbegp_model {
   double lml = 0;
   std::vector<double> theta;  // clamped, log space
   void *X = nullptr, *alpha = nullptr, *Kinv = nullptr;  // device
+  void* y = nullptr;     // the (normalised) targets, n entries: the residual of a sample path (hbegp_paths_create) starts from them
   void* Xinv = nullptr;  // L^-1 (lower), for the predictive variance as c + 1e-5 - |L^-1 k*|^2
   void* ldiag = nullptr; // diag(L), np entries (incremental extend needs the log-determinant of the kept part)
   size_t kinv_bytes = 0;
@@ -1688,6 +1689,7 @@ static hbegp_model* make_model(Problem<T>& prob, size_t di, int si, const double
   m->stream = g_stream_pool.get(m->dev, STREAM_MODEL);
   m->X = m->palloc(sizeof(T) * (size_t)prob.n * prob.d);
   m->alpha = m->palloc(sizeof(T) * prob.np);
+  m->y = m->palloc(sizeof(T) * prob.n);
   { bool fr; m->Kinv = g_pool.get(m->dev, sizeof(T) * nn, &fr); m->Xinv = g_pool.get(m->dev, sizeof(T) * nn, &fr); m->kinv_bytes = sizeof(T) * nn; }
   m->dP = static_cast<EvalParams*>(m->palloc(sizeof(EvalParams)));
   m->dOut = static_cast<EvalOut*>(m->palloc(sizeof(EvalOut)));
@@ -1715,6 +1717,7 @@ static hbegp_model* make_model(Problem<T>& prob, size_t di, int si, const double
   HIPCHECK(hipMemcpyAsync(m->Xinv, Xsrc, sizeof(T) * nn, hipMemcpyDeviceToDevice, m->stream));
   HIPCHECK(hipMemcpyAsync(m->X, prob.Xd[di], sizeof(T) * (size_t)prob.n * prob.d, hipMemcpyDeviceToDevice, m->stream));
   HIPCHECK(hipMemcpyAsync(m->alpha, s.alpha[b], sizeof(T) * prob.np, hipMemcpyDeviceToDevice, m->stream));
+  HIPCHECK(hipMemcpyAsync(m->y, prob.yd[di], sizeof(T) * prob.n, hipMemcpyDeviceToDevice, m->stream));
   HIPCHECK(hipMemcpyAsync(m->Kinv, s.Kinv[b], sizeof(T) * nn, hipMemcpyDeviceToDevice, m->stream));
   launch_symmetrize<T>(static_cast<T*>(m->Kinv), prob.np, m->stream);  // invc_into() returns the full matrix (fit.rs:60,168)
   CHECK_LAUNCHES();
@@ -2308,6 +2311,305 @@ static int model_maximize_qei(hbegp_model* m, const T* starts, int R, int q, con
     if (nevals_out) nevals_out[r] = st[r]->nevals;
   }
   g_last_error.clear();  // a failed batch inside a round is an evaluation result, not an error of this call
+  return HBEGP_OK;
+}
+
+// ---- posterior sample paths (hbegp_paths_*) ------------------------------------------------------------
+// The handle keeps, on the model's device: om^T [d][F] = omega0^T / ell, the phases [F] and the weights [S][F] in fp64, and
+// V^T [S_p][n_p] (one path per row: the tile GEMMs' operand layout).  Its calls run on the model's stream under the model's
+// mutex (they read the model's arrays and share its device), so a handle is safe from any number of threads.
+struct hbegp_paths {
+  hbegp_model* model = nullptr;  // retained
+  int F = 0, S = 0, Sp = 0;
+  bool is_f32 = false;
+  double *omT = nullptr, *phase = nullptr, *Wf = nullptr;
+  void* Vt = nullptr;
+  // evaluation scratch (grow-only): points, chunk partial sums, outputs
+  size_t cap_x = 0, cap_part = 0, cap_f = 0, cap_df = 0;
+  void *Xs = nullptr, *part = nullptr, *f = nullptr, *df = nullptr;
+  std::vector<std::pair<void*, size_t>> pooled;
+  void* palloc(size_t bytes) {
+    bool fresh = false;
+    bytes = std::max<size_t>(16, bytes);
+    void* q = g_pool.get(model->dev, bytes, &fresh);
+    pooled.push_back({q, bytes});
+    return q;
+  }
+  // Blocks go back to the pool cleared, as CallScratch's do: a NaN query row leaves NaN in the scratch, a later owner of the same
+  // size (a fit's work matrix) must find zeros.  The caller has synchronised the stream or does so before the block is reused.
+  void pfree(void* q) {
+    for (size_t i = 0; i < pooled.size(); ++i)
+      if (pooled[i].first == q) {
+        (void)hipMemsetAsync(q, 0, pooled[i].second, model->stream);
+        (void)hipStreamSynchronize(model->stream);
+        g_pool.put(model->dev, q, pooled[i].second);
+        pooled.erase(pooled.begin() + (long)i);
+        return;
+      }
+  }
+  void grow(void** q, size_t* cap, size_t bytes) {
+    if (bytes <= *cap) return;
+    HIPCHECK(hipStreamSynchronize(model->stream));  // nothing of an earlier call still uses the smaller array
+    if (*q) pfree(*q);
+    *q = nullptr; *cap = 0;
+    *q = palloc(bytes);
+    *cap = bytes;
+  }
+  ~hbegp_paths() {
+    if (!model) return;
+    (void)hipSetDevice(model->dev);
+    {
+      std::lock_guard<std::mutex> lock(model->mu);
+      for (auto& q : pooled) (void)hipMemsetAsync(q.first, 0, q.second, model->stream);
+      (void)hipStreamSynchronize(model->stream);
+      for (auto& q : pooled) g_pool.put(model->dev, q.first, q.second);
+    }
+    hbegp_model_release(model);
+  }
+};
+
+// phase times of the calling thread's last timed hbegp_paths_create call (hbegp_debug_paths_phases): uploads + frequency scaling,
+// the feature projection, the two triangular products, in ms
+static thread_local bool t_time_paths = false;
+static thread_local double t_paths_ms[3] = {0, 0, 0};
+
+template <typename T>
+static int paths_create(hbegp_model* m, const T* omega0, const T* phase, const T* w, const T* eps, int F, int S, hbegp_paths** out) {
+  std::unique_ptr<hbegp_paths> p(new hbegp_paths());
+  hbegp_model_retain(m);
+  p->model = m; p->F = F; p->S = S; p->Sp = round_up(S, NB); p->is_f32 = m->is_f32;
+  std::lock_guard<std::mutex> lock(m->mu);
+  HIPCHECK(hipSetDevice(m->dev));
+  hipStream_t s = m->stream;
+  const int n = m->n, d = m->d, np = m->np, Sp = p->Sp;
+  p->omT = static_cast<double*>(p->palloc(sizeof(double) * (size_t)F * d));
+  p->phase = static_cast<double*>(p->palloc(sizeof(double) * (size_t)F));
+  p->Wf = static_cast<double*>(p->palloc(sizeof(double) * (size_t)S * F));
+  p->Vt = p->palloc(sizeof(T) * (size_t)Sp * np);
+  // the weights and phases go up as fp64 (every feature sum is fp64 for both element types)
+  std::vector<double> hw((size_t)S * F + F);
+  for (size_t i = 0; i < (size_t)S * F; ++i) hw[i] = (double)w[i];
+  for (int j = 0; j < F; ++j) hw[(size_t)S * F + j] = (double)phase[j];
+  CallScratch ws{m->dev, s, {}};
+  T* om0 = static_cast<T*>(ws.get(sizeof(T) * (size_t)F * d));
+  T* deps = eps ? static_cast<T*>(ws.get(sizeof(T) * (size_t)S * n)) : nullptr;
+  double* part = static_cast<double*>(ws.get(sizeof(double) * (size_t)paths_project_chunks(F, n, S) * S * n));
+  T* Rt = static_cast<T*>(ws.get(sizeof(T) * (size_t)Sp * np));
+  T* T1 = static_cast<T*>(ws.get(sizeof(T) * (size_t)Sp * np));
+  struct Events {  // destroyed on every way out, a throwing HIPCHECK included
+    hipEvent_t e[4] = {};
+    ~Events() {
+      for (auto& x : e)
+        if (x) (void)hipEventDestroy(x);
+    }
+  } evs;
+  hipEvent_t* ev = evs.e;
+  const bool timed = t_time_paths;
+  if (timed)
+    for (auto& e : evs.e) HIPCHECK(hipEventCreate(&e));
+  if (timed) HIPCHECK(hipEventRecord(ev[0], s));
+  HIPCHECK(hipMemcpyAsync(p->Wf, hw.data(), sizeof(double) * (size_t)S * F, hipMemcpyHostToDevice, s));
+  HIPCHECK(hipMemcpyAsync(p->phase, hw.data() + (size_t)S * F, sizeof(double) * (size_t)F, hipMemcpyHostToDevice, s));
+  HIPCHECK(hipMemcpyAsync(om0, omega0, sizeof(T) * (size_t)F * d, hipMemcpyHostToDevice, s));
+  if (eps) HIPCHECK(hipMemcpyAsync(deps, eps, sizeof(T) * (size_t)S * n, hipMemcpyHostToDevice, s));
+  HIPCHECK(hipMemsetAsync(m->dOut, 0, sizeof(EvalOut), s));
+  launch_paths_scale_omega<T>(om0, F, d, m->dP, p->omT, s);
+  if (timed) HIPCHECK(hipEventRecord(ev[1], s));
+  launch_paths_project<T>(static_cast<T*>(m->X), n, d, np, p->omT, p->phase, F, p->Wf, S, Sp, static_cast<T*>(m->y), deps, m->dP, part, Rt, s);
+  if (timed) HIPCHECK(hipEventRecord(ev[2], s));
+  {
+    // v = L^-T (L^-1 r) for all paths, one path per row: T1 = R^T X^T (X = L^-1 lower: k <= j, as Q = Kstar X^T), then
+    // V^T = T1 X (k >= j).  Never through the stored K^-1 (section 10).
+    GemmLaunch g{};
+    g.nops = 1;
+    GemmOp& op = g.op[0];
+    op.lda = np; op.ldb = np; op.ldc = np;
+    op.mi = Sp / NB; op.nj = np / NB; op.k0 = 0; op.k1 = np / NB;
+    op.A = Rt; op.B = m->Xinv; op.C = T1;
+    op.klim = 1; op.maskB = 1;
+    gemm_adhoc<T>(g, &m->dOut->info, s);
+    GemmLaunch g2{};
+    g2.nops = 1;
+    GemmOp& o2 = g2.op[0];
+    o2 = op;
+    o2.A = T1; o2.C = p->Vt;
+    o2.b_kmajor = 1; o2.klim = 2;
+    gemm_adhoc<T>(g2, &m->dOut->info, s);
+  }
+  if (timed) HIPCHECK(hipEventRecord(ev[3], s));
+  CHECK_LAUNCHES();
+  HIPCHECK(hipStreamSynchronize(s));
+  if (timed) {
+    for (int i = 0; i < 3; ++i) {
+      float ms = 0;
+      HIPCHECK(hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
+      t_paths_ms[i] = ms;
+    }
+  }
+  *out = p.release();
+  return HBEGP_OK;
+}
+
+// the points go through the kernels in blocks: at most PATHS_EVAL_ROWS (path, point) pairs and PATHS_EVAL_PART bytes of partial sums
+constexpr size_t PATHS_EVAL_ROWS = 262144;
+constexpr size_t PATHS_EVAL_PART = (size_t)256 << 20;
+
+// the caller holds the model's mutex
+template <typename T>
+static void paths_eval_locked(hbegp_paths* p, const T* Xs, int cnt, int per_path, T* f, T* df) {
+  hbegp_model* m = p->model;
+  hipStream_t s = m->stream;
+  const int d = m->d, S = p->S;
+  const size_t per_point = sizeof(double) * (size_t)paths_eval_chunks(m->n, p->F) * S * (d + 1);
+  const int mb = (int)std::max<size_t>(1, std::min<size_t>({(size_t)cnt, PATHS_EVAL_ROWS / (size_t)S, PATHS_EVAL_PART / per_point}));
+  p->grow(&p->Xs, &p->cap_x, sizeof(T) * (size_t)(per_path ? S : 1) * mb * d);
+  p->grow(&p->part, &p->cap_part, per_point * mb);
+  p->grow(&p->f, &p->cap_f, sizeof(T) * (size_t)S * mb);
+  if (df) p->grow(&p->df, &p->cap_df, sizeof(T) * (size_t)S * mb * d);
+  for (int p0 = 0; p0 < cnt; p0 += mb) {
+    const int c = std::min(mb, cnt - p0);
+    if (per_path)
+      HIPCHECK(hipMemcpy2DAsync(p->Xs, sizeof(T) * (size_t)c * d, Xs + (size_t)p0 * d, sizeof(T) * (size_t)cnt * d, sizeof(T) * (size_t)c * d, S,
+                                hipMemcpyHostToDevice, s));
+    else
+      HIPCHECK(hipMemcpyAsync(p->Xs, Xs + (size_t)p0 * d, sizeof(T) * (size_t)c * d, hipMemcpyHostToDevice, s));
+    launch_paths_eval<T>(static_cast<T*>(p->Xs), c, per_path, S, static_cast<T*>(m->X), m->n, d, m->np, m->nu2, m->dP, static_cast<T*>(p->Vt),
+                         p->omT, p->phase, p->Wf, p->F, df ? 1 : 0, static_cast<double*>(p->part), static_cast<T*>(p->f),
+                         static_cast<T*>(p->df), s);
+    CHECK_LAUNCHES();
+    HIPCHECK(hipMemcpy2DAsync(f + p0, sizeof(T) * (size_t)cnt, p->f, sizeof(T) * (size_t)c, sizeof(T) * (size_t)c, S, hipMemcpyDeviceToHost, s));
+    if (df)
+      HIPCHECK(hipMemcpy2DAsync(df + (size_t)p0 * d, sizeof(T) * (size_t)cnt * d, p->df, sizeof(T) * (size_t)c * d, sizeof(T) * (size_t)c * d, S,
+                                hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipStreamSynchronize(s));  // the next block reuses the scratch; the caller's arrays are pageable
+  }
+}
+
+template <typename T>
+static int paths_eval(hbegp_paths* p, const T* Xs, int cnt, int per_path, T* f, T* df) {
+  std::lock_guard<std::mutex> lock(p->model->mu);
+  HIPCHECK(hipSetDevice(p->model->dev));
+  paths_eval_locked<T>(p, Xs, cnt, per_path, f, df);
+  return HBEGP_OK;
+}
+
+// S R bounded L-BFGS descents (lbfgs_step.hpp, the fit optimiser's constants), R per path, in lockstep: every round gathers the
+// point each unfinished run asks for and evaluates them with ONE per-path evaluation ([S][mr] points, mr the largest number of
+// unfinished runs of any path; a path with fewer repeats its last point).  Each path returns the best point any of its runs
+// evaluated (a NaN value is a failed evaluation; a path without a finite value returns its first start and +inf).
+template <typename T>
+static int paths_minimize(hbegp_paths* p, const T* starts, int R, const double* lo, const double* hi, int maxeval, T* x_best, double* f_best,
+                          int* n_evals) {
+  hbegp_model* m = p->model;
+  std::lock_guard<std::mutex> lock(m->mu);
+  HIPCHECK(hipSetDevice(m->dev));
+  const int d = m->d, S = p->S;
+  const size_t NR = (size_t)S * R;
+  const LbfgsOptions o;
+  std::vector<LbfgsState> st(NR);
+  std::vector<char> running(NR, 1);
+  std::vector<double> best(S, std::numeric_limits<double>::infinity());
+  std::vector<double> x0(d), g(d);
+  for (size_t r = 0; r < NR; ++r) {
+    for (int k = 0; k < d; ++k) x0[k] = (double)starts[r * d + k];
+    lbfgs_begin(st[r], x0.data(), lo, hi, d, maxeval, o.memory, o.pgtol, o.ftol, false);
+  }
+  for (int sp = 0; sp < S; ++sp)
+    for (int k = 0; k < d; ++k) x_best[(size_t)sp * d + k] = starts[(size_t)sp * R * d + k];
+  std::vector<std::vector<int>> act(S);
+  std::vector<T> xs, fv, dfv;
+  for (;;) {
+    int mr = 0;
+    for (int sp = 0; sp < S; ++sp) {
+      act[sp].clear();
+      for (int r = 0; r < R; ++r)
+        if (running[(size_t)sp * R + r]) act[sp].push_back(r);
+      mr = std::max(mr, (int)act[sp].size());
+    }
+    if (mr == 0) break;
+    xs.assign((size_t)S * mr * d, T(0));
+    fv.resize((size_t)S * mr);
+    dfv.resize((size_t)S * mr * d);
+    for (int sp = 0; sp < S; ++sp) {
+      T* row = xs.data() + (size_t)sp * mr * d;
+      const int na = (int)act[sp].size();
+      for (int i = 0; i < mr; ++i) {
+        if (i < na) {
+          const double* q = lbfgs_request(st[(size_t)sp * R + act[sp][i]]);
+          for (int k = 0; k < d; ++k) row[(size_t)i * d + k] = to_box<T>(q[k], lo[k], hi[k]);
+        } else {
+          const T* src = i > 0 ? row + (size_t)(i - 1) * d : x_best + (size_t)sp * d;
+          for (int k = 0; k < d; ++k) row[(size_t)i * d + k] = src[k];
+        }
+      }
+    }
+    paths_eval_locked<T>(p, xs.data(), mr, 1, fv.data(), dfv.data());
+    for (int sp = 0; sp < S; ++sp) {
+      for (int i = 0; i < (int)act[sp].size(); ++i) {
+        const size_t r = (size_t)sp * R + act[sp][i], at = (size_t)sp * mr + i;
+        double fx = (double)fv[at];
+        bool ok = std::isfinite(fx);
+        for (int k = 0; k < d; ++k) {
+          g[k] = (double)dfv[at * d + k];
+          ok = ok && std::isfinite(g[k]);
+        }
+        if (!ok) {
+          fx = std::numeric_limits<double>::infinity();
+          for (int k = 0; k < d; ++k) g[k] = 0.0;
+        } else if (fx < best[sp]) {
+          best[sp] = fx;
+          for (int k = 0; k < d; ++k) x_best[(size_t)sp * d + k] = xs[at * d + k];
+        }
+        running[r] = lbfgs_advance(st[r], fx, g.data()) ? 1 : 0;
+      }
+    }
+  }
+  for (int sp = 0; sp < S; ++sp) {
+    f_best[sp] = best[sp];
+    if (n_evals) {
+      n_evals[sp] = 0;
+      for (int r = 0; r < R; ++r) n_evals[sp] += st[(size_t)sp * R + r].nevals;
+    }
+  }
+  return HBEGP_OK;
+}
+
+// argument checks of the sample-path entry points: everything is refused before any device call
+template <typename T>
+static int check_paths_create(hbegp_model* model, const T* omega0, const T* phase, const T* w, int F, int S, hbegp_paths** paths) {
+  if (F < 1 || F > HBEGP_PATHS_MAX_FEATURES) return fail(HBEGP_EINVAL, "F must be in [1, %d] (got %d)", HBEGP_PATHS_MAX_FEATURES, F);
+  if (S < 1 || S > HBEGP_PATHS_MAX_PATHS) return fail(HBEGP_EINVAL, "S must be in [1, %d] (got %d)", HBEGP_PATHS_MAX_PATHS, S);
+  if (!model) return fail(HBEGP_EINVAL, "NULL model");
+  if (!omega0 || !phase || !w || !paths) return fail(HBEGP_EINVAL, "omega0/phase/w/paths is NULL");
+  if (model->is_f32 != (sizeof(T) == 4)) return fail(HBEGP_EINVAL, "model holds %s data", model->is_f32 ? "f32" : "f64");
+  return HBEGP_OK;
+}
+template <typename T>
+static int check_paths_eval(hbegp_paths* paths, const T* Xs, int m, int per_path, T* f) {
+  if (m < 0) return fail(HBEGP_EINVAL, "m must be >= 0 (got %d)", m);
+  if (per_path != 0 && per_path != 1) return fail(HBEGP_EINVAL, "per_path must be 0 or 1 (got %d)", per_path);
+  if (!paths) return fail(HBEGP_EINVAL, "NULL paths handle");
+  if (paths->is_f32 != (sizeof(T) == 4)) return fail(HBEGP_EINVAL, "paths handle holds %s data", paths->is_f32 ? "f32" : "f64");
+  if (m > 0 && (!Xs || !f)) return fail(HBEGP_EINVAL, "Xs/f is NULL");
+  return HBEGP_OK;
+}
+template <typename T>
+static int check_paths_minimize(hbegp_paths* paths, const T* starts, int R, const double* lo, const double* hi, int maxeval, T* x_best,
+                                double* f_best) {
+  if (R < 1) return fail(HBEGP_EINVAL, "R must be >= 1 (got %d)", R);
+  if (maxeval < 1) return fail(HBEGP_EINVAL, "maxeval must be >= 1 (got %d)", maxeval);
+  if (!paths) return fail(HBEGP_EINVAL, "NULL paths handle");
+  if (!starts || !lo || !hi || !x_best || !f_best) return fail(HBEGP_EINVAL, "starts/lo/hi/x_best/f_best is NULL");
+  if (paths->is_f32 != (sizeof(T) == 4)) return fail(HBEGP_EINVAL, "paths handle holds %s data", paths->is_f32 ? "f32" : "f64");
+  const int d = paths->model->d;
+  if (d > LBFGS_MAXN) return fail(HBEGP_EINVAL, "d = %d exceeds the optimiser's %d variables", d, LBFGS_MAXN);
+  for (int k = 0; k < d; ++k)
+    if (!(lo[k] <= hi[k])) return fail(HBEGP_EINVAL, "lo[%d] > hi[%d] (%g > %g)", k, k, lo[k], hi[k]);
+  for (size_t r = 0; r < (size_t)paths->S * R; ++r)
+    for (int k = 0; k < d; ++k) {
+      const double v = (double)starts[r * d + k];
+      if (!(v >= lo[k] && v <= hi[k])) return fail(HBEGP_EINVAL, "start %zu lies outside the box (feature %d: %g)", r, k, v);
+    }
   return HBEGP_OK;
 }
 
@@ -3244,6 +3546,64 @@ int hbegp_maximize_qei_f32(hbegp_model* model, const float* starts, int R, int q
   GUARD_BEGIN
   return model_maximize_qei<float>(model, starts, R, q, lo, hi, z, S, fmin_normalized, jitter, maxeval, x_out, qei_out, nevals_out);
   GUARD_END
+}
+int hbegp_paths_create_f64(hbegp_model* model, const double* omega0, const double* phase, const double* w, const double* eps, int F, int S,
+                           hbegp_paths** paths) {
+  if (int rc = check_paths_create<double>(model, omega0, phase, w, F, S, paths)) return rc;
+  GUARD_BEGIN
+  return paths_create<double>(model, omega0, phase, w, eps, F, S, paths);
+  GUARD_END
+}
+int hbegp_paths_create_f32(hbegp_model* model, const float* omega0, const float* phase, const float* w, const float* eps, int F, int S,
+                           hbegp_paths** paths) {
+  if (int rc = check_paths_create<float>(model, omega0, phase, w, F, S, paths)) return rc;
+  GUARD_BEGIN
+  return paths_create<float>(model, omega0, phase, w, eps, F, S, paths);
+  GUARD_END
+}
+int hbegp_paths_eval_f64(hbegp_paths* paths, const double* Xs, int m, int per_path, double* f, double* df) {
+  if (int rc = check_paths_eval<double>(paths, Xs, m, per_path, f)) return rc;
+  if (m == 0) return HBEGP_OK;
+  GUARD_BEGIN
+  return paths_eval<double>(paths, Xs, m, per_path, f, df);
+  GUARD_END
+}
+int hbegp_paths_eval_f32(hbegp_paths* paths, const float* Xs, int m, int per_path, float* f, float* df) {
+  if (int rc = check_paths_eval<float>(paths, Xs, m, per_path, f)) return rc;
+  if (m == 0) return HBEGP_OK;
+  GUARD_BEGIN
+  return paths_eval<float>(paths, Xs, m, per_path, f, df);
+  GUARD_END
+}
+int hbegp_paths_minimize_f64(hbegp_paths* paths, const double* starts, int R, const double* lo, const double* hi, int maxeval,
+                             double* x_best, double* f_best, int* n_evals) {
+  if (int rc = check_paths_minimize<double>(paths, starts, R, lo, hi, maxeval, x_best, f_best)) return rc;
+  GUARD_BEGIN
+  return paths_minimize<double>(paths, starts, R, lo, hi, maxeval, x_best, f_best, n_evals);
+  GUARD_END
+}
+int hbegp_paths_minimize_f32(hbegp_paths* paths, const float* starts, int R, const double* lo, const double* hi, int maxeval,
+                             float* x_best, double* f_best, int* n_evals) {
+  if (int rc = check_paths_minimize<float>(paths, starts, R, lo, hi, maxeval, x_best, f_best)) return rc;
+  GUARD_BEGIN
+  return paths_minimize<float>(paths, starts, R, lo, hi, maxeval, x_best, f_best, n_evals);
+  GUARD_END
+}
+int hbegp_paths_info(const hbegp_paths* paths, int* n, int* d, int* n_features, int* n_paths, int* is_f32) {
+  if (!paths) return fail(HBEGP_EINVAL, "NULL paths handle");
+  if (n) *n = paths->model->n;
+  if (d) *d = paths->model->d;
+  if (n_features) *n_features = paths->F;
+  if (n_paths) *n_paths = paths->S;
+  if (is_f32) *is_f32 = paths->is_f32 ? 1 : 0;
+  return HBEGP_OK;
+}
+void hbegp_paths_release(hbegp_paths* paths) { delete paths; }
+int hbegp_debug_paths_phases(int enable, double* phase_ms) {
+  if (phase_ms)
+    for (int i = 0; i < 3; ++i) phase_ms[i] = t_paths_ms[i];
+  t_time_paths = enable != 0;
+  return HBEGP_OK;
 }
 int hbegp_debug_qei_phases(int enable, double* phase_ms) {
   if (phase_ms)

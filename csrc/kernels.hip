@@ -3291,6 +3291,311 @@ void launch_small_eval(const SmallEval& g, int nu2, hipStream_t s) {
 template void launch_small_eval<double>(const SmallEval&, int, hipStream_t);
 template void launch_small_eval<float>(const SmallEval&, int, hipStream_t);
 
+// =================================================================================================================
+// posterior sample paths (hbegp_paths_*): pathwise conditioning on a random-Fourier-feature prior draw
+//   f_s(x) = A sum_j w_sj cos(th_j(x)) + sum_i k(x, x_i) v_is,   th_j(x) = om_j . x + b_j,  A = sqrt(2 c / F),  om_jk = om0_jk / ell_k
+//   df_s/dx_k = -A sum_j w_sj sin(th_j) om_jk + sum_i c psi(r_i) (x_k - x_ik) / ell_k^2 v_is
+//   v_s = L^-T L^-1 r_s,  r_s = y - Phi(X) w_s - sqrt(sigma^2) eps_s    (two triangular tile GEMMs over an [S_p][n_p] operand)
+// The phase, sin / cos, psi and every sum are fp64 for both element types: nu = 1/2 has a Cauchy spectral density, |th| reaches
+// 1e4 .. 1e6, where an f32 argument has lost the 1e-4 bar before the cosine is taken.  r^2 is accumulated in the element type
+// with kstar_kernel's scaling and order, so that k(x, x_i) agrees with the predict path.
+//
+// paths_project_kernel (preparation): grid (ceil(n/64), feature chunks (paths_project_chunks), ceil(S/64)).  A workgroup takes 64 training points (the
+// lane) and walks its feature chunk 32 features at a time: the four waves fill phi[32][64] = cos(th) in the LDS (a feature is
+// wave-uniform: its frequencies and the weights w_sj are scalar loads), then wave w adds the 32 features in ascending order
+// into 16 accumulators, paths 64 z + 16 w .. + 15.  Phi(X) [n][F] is never stored.  part[chunk][s][i];
+// paths_project_finish_kernel adds the chunks in ascending order and writes r into R^T [S_p][n_p] (zero padding).
+//
+// paths_eval_kernel<T, SB, DATA>: two launches, grid (ceil(items/4), data chunks) and (ceil(items/4), feature chunks), item = (point, block of SB paths): wave w of a
+// workgroup is one item, the lane walks the chunk's terms -- PE_CHUNK training points (pred_grad_kernel's shape: 64 at a time
+// through the LDS) or PE_CHUNK features -- 64 apart in ascending order.  A term's kernel value / slope or cosine / sine is
+// computed once and used for the item's SB paths: SB (1 + PE_KB) fp64 accumulators per lane, PE_KB gradient components per pass.
+// One wave_sum each -> part[chunk][row][1 + d], row = s m + point; paths_eval_finish_kernel adds the chunks in ascending
+// order, data chunks first.  SB = 1 serves per-path points (every path its own x), SB = PE_SB shared points.  A path's sums do
+// not depend on SB, on the other paths of its block or on the other points of the call: the same (path, point) gives the same
+// bits alone, in a batch, shared or per path.  No atomics.
+// =================================================================================================================
+constexpr int PP_FT = 32;       // features per LDS tile of the projection
+constexpr int PE_CHUNK = 512;   // terms per workgroup of the evaluation
+constexpr int PE_KB = 8;        // gradient components per pass
+constexpr int PE_SB = 2;        // paths per item at shared points (4: 151 VGPRs and a handful of SGPR spills)
+
+template <typename T>
+__global__ void __launch_bounds__(256) paths_project_kernel(const T* __restrict__ X, int n, int d, const double* __restrict__ omT,
+                                                            const double* __restrict__ phase, int F, int fch,
+                                                            const double* __restrict__ Wf, int S, double* __restrict__ part) {
+#pragma clang fp contract(off)
+  extern __shared__ __align__(16) char smem_raw[];
+  double* phi = reinterpret_cast<double*>(smem_raw);  // [PP_FT][64]
+  T* sx = reinterpret_cast<T*>(phi + PP_FT * 64);      // [d][64] features of the 64 training points (unscaled)
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const int i0 = blockIdx.x * 64, gi = i0 + lane;
+  const int f0 = blockIdx.y * fch, f1 = min(F, f0 + fch);
+  const int s0 = blockIdx.z * 64 + w * 16;
+  for (int e = t; e < 64 * d; e += 256) {
+    const int row = e / d, k = e - row * d;
+    sx[k * 64 + row] = (i0 + row < n) ? X[(size_t)(i0 + row) * d + k] : T(0);
+  }
+  double acc[16];
+#pragma unroll
+  for (int q = 0; q < 16; ++q) acc[q] = 0.0;
+  for (int j0 = f0; j0 < f1; j0 += PP_FT) {
+    __syncthreads();  // the previous tile is consumed (first time: sx is written)
+    for (int e = 0; e < PP_FT / 4; ++e) {
+      const int jj = w + 4 * e, j = j0 + jj;  // wave-uniform
+      double c = 0.0;
+      if (j < f1) {
+        double th = phase[j];
+        for (int k = 0; k < d; ++k) th = __builtin_fma((double)sx[k * 64 + lane], omT[(size_t)k * F + j], th);
+        c = cos(th);
+      }
+      phi[jj * 64 + lane] = c;
+    }
+    __syncthreads();
+    const int jn = min(PP_FT, f1 - j0);
+    for (int jj = 0; jj < jn; ++jj) {
+      const double p = phi[jj * 64 + lane];
+#pragma unroll
+      for (int q = 0; q < 16; ++q)
+        if (s0 + q < S) acc[q] = __builtin_fma(Wf[(size_t)(s0 + q) * F + j0 + jj], p, acc[q]);
+    }
+  }
+  if (gi < n) {
+#pragma unroll
+    for (int q = 0; q < 16; ++q)
+      if (s0 + q < S) part[((size_t)blockIdx.y * S + s0 + q) * n + gi] = acc[q];
+  }
+}
+
+// R^T[s][i] = y_i - A sum_chunks part[c][s][i] - sqrt(sigma^2) eps[s][i] (eps may be null); zero for s >= S or i >= n
+template <typename T>
+__global__ void __launch_bounds__(256) paths_project_finish_kernel(const double* __restrict__ part, int nch, int n, int np, int S, int F,
+                                                                   const T* __restrict__ y, const T* __restrict__ eps,
+                                                                   const EvalParams* __restrict__ P, T* __restrict__ Rt) {
+#pragma clang fp contract(off)
+  const int i = blockIdx.x * 256 + threadIdx.x, s = blockIdx.y;
+  if (i >= np) return;
+  T r = T(0);
+  if (s < S && i < n) {
+    double sm = 0.0;
+    for (int c = 0; c < nch; ++c) sm += part[((size_t)c * S + s) * n + i];
+    double v = (double)y[i] - sqrt(2.0 * P->amp / (double)F) * sm;
+    if (eps) v -= sqrt(P->noise) * (double)eps[(size_t)s * n + i];
+    r = (T)v;
+  }
+  Rt[(size_t)s * np + i] = r;
+}
+
+// om^T[k][j] = om0[j][k] / ell_k (fp64 for both element types)
+template <typename T>
+__global__ void __launch_bounds__(256) paths_scale_omega_kernel(const T* __restrict__ om0, int F, int d, const EvalParams* __restrict__ P,
+                                                                double* __restrict__ omT) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= F * d) return;
+  const int k = e / F, j = e - k * F;
+  omT[e] = (double)om0[(size_t)j * d + k] / P->ell[k];
+}
+
+template <typename T, int SB, bool DATA>
+__global__ void __launch_bounds__(256) paths_eval_kernel(const T* __restrict__ Xs, int m, int per_path, int S, const T* __restrict__ X, int n,
+                                                         int d, int nu2, const EvalParams* __restrict__ P, const T* __restrict__ Vt, int np,
+                                                         const double* __restrict__ omT, const double* __restrict__ phase,
+                                                         const double* __restrict__ Wf, int F, int nchd, int want_grad,
+                                                         double* __restrict__ part) {
+#pragma clang fp contract(off)
+  extern __shared__ __align__(16) char smem_raw[];
+  T* sx = reinterpret_cast<T*>(smem_raw);  // [d][64] scaled features of 64 training points
+  T* sq = sx + (size_t)d * 64;             // [4][d] this workgroup's query points: scaled (data chunks) or raw (feature chunks)
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const int nsb = (S + SB - 1) / SB, items = m * nsb, d1 = d + 1;
+  constexpr bool data = DATA;
+  const int chunk = DATA ? (int)blockIdx.y : nchd + (int)blockIdx.y;  // data chunks first
+  for (int e = t; e < 4 * d; e += 256) {
+    const int q = e / d, k = e - q * d, it = blockIdx.x * 4 + q;
+    T v = T(0);
+    if (it < items) {
+      const int pt = it / nsb, sb = it - pt * nsb;
+      v = Xs[(per_path ? (size_t)sb * SB * m + pt : (size_t)pt) * d + k];  // per_path: SB = 1, the path's own point
+      if (data) v = v / (T)P->ell[k];
+    }
+    sq[e] = v;
+  }
+  const int item = blockIdx.x * 4 + w;
+  const bool live = item < items;
+  const int pt = live ? item / nsb : 0, s0 = live ? (item - pt * nsb) * SB : 0;
+  const T* xq = sq + w * d;
+  const int npass = want_grad ? (d + PE_KB - 1) / PE_KB : 1;
+  for (int ps = 0; ps < npass; ++ps) {
+    const int kb = ps * PE_KB;
+    double af[SB], ag[SB][PE_KB];
+#pragma unroll
+    for (int q = 0; q < SB; ++q) {
+      af[q] = 0.0;
+#pragma unroll
+      for (int kk = 0; kk < PE_KB; ++kk) ag[q][kk] = 0.0;
+    }
+    if constexpr (data) {
+      const int jc0 = blockIdx.y * PE_CHUNK, jc1 = min(n, jc0 + PE_CHUNK);
+      const double amp = P->amp;
+      for (int j0 = jc0; j0 < jc1; j0 += 64) {
+        __syncthreads();  // the previous 64 points are consumed (first time: sq is written)
+        for (int e = t; e < 64 * d; e += 256) {
+          const int jj = e / d, k = e - jj * d, gj = j0 + jj;
+          sx[k * 64 + jj] = (gj < n) ? X[(size_t)gj * d + k] / (T)P->ell[k] : T(0);
+        }
+        __syncthreads();
+        const int j = j0 + lane;
+        if (live && j < jc1) {
+          T r2 = T(0);
+          for (int k = 0; k < d; ++k) {  // kstar_kernel's accumulation
+            const T df = xq[k] - sx[k * 64 + lane];
+            r2 += df * df;
+          }
+          const double kv = (double)kmat_entry<T>(r2, nu2, (T)amp, T(0), false);
+          const double sl = (!want_grad || r2 == T(0)) ? 0.0 : amp * matern_psi((double)r2, nu2);
+          double dk[PE_KB];
+#pragma unroll
+          for (int kk = 0; kk < PE_KB; ++kk) {  // components past d repeat the last one (never written)
+            const int kc = min(kb + kk, d - 1);
+            dk[kk] = (double)(xq[kc] - sx[kc * 64 + lane]);
+          }
+#pragma unroll
+          for (int q = 0; q < SB; ++q) {  // a block's tail repeats the last path (never written)
+            const double v = (double)Vt[(size_t)min(s0 + q, S - 1) * np + j];
+            af[q] = __builtin_fma(kv, v, af[q]);
+            const double a = sl * v;
+#pragma unroll
+            for (int kk = 0; kk < PE_KB; ++kk) ag[q][kk] = __builtin_fma(a, dk[kk], ag[q][kk]);
+          }
+        }
+      }
+    } else {
+      __syncthreads();  // sq is written
+      const int jc0 = (int)blockIdx.y * PE_CHUNK, jc1 = min(F, jc0 + PE_CHUNK);
+      for (int j = jc0 + lane; j < jc1 && live; j += 64) {
+        double th = phase[j];
+        for (int k = 0; k < d; ++k) th = __builtin_fma((double)xq[k], omT[(size_t)k * F + j], th);
+        double sn, cs;
+        sincos(th, &sn, &cs);  // one range reduction for both
+        double om[PE_KB];
+#pragma unroll
+        for (int kk = 0; kk < PE_KB; ++kk) om[kk] = omT[(size_t)min(kb + kk, d - 1) * F + j];
+#pragma unroll
+        for (int q = 0; q < SB; ++q) {
+          const double wv = Wf[(size_t)min(s0 + q, S - 1) * F + j];
+          af[q] = __builtin_fma(wv, cs, af[q]);
+          const double a = -(wv * sn);
+#pragma unroll
+          for (int kk = 0; kk < PE_KB; ++kk) ag[q][kk] = __builtin_fma(a, om[kk], ag[q][kk]);
+        }
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < SB; ++q) {
+      const bool on = live && s0 + q < S;  // wave-uniform
+      double* pr = part + (((size_t)chunk * S + (on ? s0 + q : 0)) * m + pt) * d1;
+      if (ps == 0) {
+        const double sm = wave_sum(af[q]);
+        if (on && lane == 0) pr[0] = sm;
+      }
+      if (want_grad) {
+#pragma unroll
+        for (int kk = 0; kk < PE_KB; ++kk) {
+          if (kb + kk < d) {
+            const double sm = wave_sum(ag[q][kk]);
+            if (on && lane == 0) pr[1 + kb + kk] = sm;
+          }
+        }
+      }
+    }
+  }
+}
+
+// f[s][i] = sum of the data chunks + A * sum of the feature chunks; df[s][i][k] = (data sum) / ell_k + A * (feature sum)
+template <typename T>
+__global__ void __launch_bounds__(256) paths_eval_finish_kernel(const double* __restrict__ part, int nchd, int nch, int rows, int d, int F,
+                                                                const EvalParams* __restrict__ P, int want_grad, T* __restrict__ f,
+                                                                T* __restrict__ df) {
+#pragma clang fp contract(off)
+  const int d1 = d + 1;
+  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (size_t)rows * d1) return;
+  const int c0 = (int)(e % d1);
+  const size_t row = e / d1;
+  if (c0 > 0 && !want_grad) return;
+  double sd = 0.0, sf = 0.0;
+  for (int c = 0; c < nchd; ++c) sd += part[(size_t)c * rows * d1 + e];
+  for (int c = nchd; c < nch; ++c) sf += part[(size_t)c * rows * d1 + e];
+  const double A = sqrt(2.0 * P->amp / (double)F);
+  if (c0 == 0) f[row] = (T)(sd + A * sf);
+  else df[row * d + (c0 - 1)] = (T)(sd / P->ell[c0 - 1] + A * sf);
+}
+
+// Feature chunks of the projection.  A workgroup walks its chunk serially (one fp64 cosine per lane and feature), so the chunk
+// length is the launch's latency: chunks of 64 features while the partial sums (chunks x S x n doubles) stay within 128 MiB and
+// there are at most 64 of them, longer ones beyond.  The split depends only on (F, n, S): one handle, one summation order.
+int paths_project_chunks(int F, int n, int S, int* fch_out) {
+  const size_t per_chunk = sizeof(double) * (size_t)S * (size_t)n;
+  const int cap = (int)std::max<size_t>(1, std::min<size_t>(64, ((size_t)128 << 20) / per_chunk));
+  int nch = std::max(1, std::min(cap, (F + 63) / 64));
+  int fch = ((F + nch - 1) / nch + PP_FT - 1) / PP_FT * PP_FT;
+  nch = (F + fch - 1) / fch;
+  if (fch_out) *fch_out = fch;
+  return nch;
+}
+int paths_eval_chunks(int n, int F, int* nchd_out) {
+  const int nchd = (n + PE_CHUNK - 1) / PE_CHUNK;
+  if (nchd_out) *nchd_out = nchd;
+  return nchd + (F + PE_CHUNK - 1) / PE_CHUNK;
+}
+template <typename T>
+void launch_paths_scale_omega(const T* om0, int F, int d, const EvalParams* P, double* omT, hipStream_t s) {
+  hipLaunchKernelGGL((paths_scale_omega_kernel<T>), dim3((F * d + 255) / 256), dim3(256), 0, s, om0, F, d, P, omT);
+}
+template <typename T>
+void launch_paths_project(const T* X, int n, int d, int np, const double* omT, const double* phase, int F, const double* Wf, int S, int Sp,
+                          const T* y, const T* eps, const EvalParams* P, double* part, T* Rt, hipStream_t s) {
+  int fch = 0;
+  const int nch = paths_project_chunks(F, n, S, &fch);
+  const size_t lds = sizeof(double) * PP_FT * 64 + sizeof(T) * (size_t)d * 64;
+  hipLaunchKernelGGL((paths_project_kernel<T>), dim3((n + 63) / 64, nch, (S + 63) / 64), dim3(256), lds, s, X, n, d, omT, phase, F, fch, Wf,
+                     S, part);
+  hipLaunchKernelGGL((paths_project_finish_kernel<T>), dim3((np + 255) / 256, Sp), dim3(256), 0, s, part, nch, n, np, S, F, y, eps, P, Rt);
+}
+template <typename T>
+void launch_paths_eval(const T* Xs, int m, int per_path, int S, const T* X, int n, int d, int np, int nu2, const EvalParams* P, const T* Vt,
+                       const double* omT, const double* phase, const double* Wf, int F, int want_grad, double* part, T* f, T* df,
+                       hipStream_t s) {
+  int nchd = 0;
+  const int nch = paths_eval_chunks(n, F, &nchd);
+  const size_t lds = (size_t)(64 + 4) * d * sizeof(T);
+  const int rows = S * m;
+  if (per_path) {
+    hipLaunchKernelGGL((paths_eval_kernel<T, 1, true>), dim3((rows + 3) / 4, nchd), dim3(256), lds, s, Xs, m, 1, S, X, n, d, nu2, P, Vt, np, omT,
+                       phase, Wf, F, nchd, want_grad, part);
+    hipLaunchKernelGGL((paths_eval_kernel<T, 1, false>), dim3((rows + 3) / 4, nch - nchd), dim3(256), lds, s, Xs, m, 1, S, X, n, d, nu2, P, Vt, np,
+                       omT, phase, Wf, F, nchd, want_grad, part);
+  } else {
+    const int items = m * ((S + PE_SB - 1) / PE_SB);
+    hipLaunchKernelGGL((paths_eval_kernel<T, PE_SB, true>), dim3((items + 3) / 4, nchd), dim3(256), lds, s, Xs, m, 0, S, X, n, d, nu2, P, Vt, np, omT,
+                       phase, Wf, F, nchd, want_grad, part);
+    hipLaunchKernelGGL((paths_eval_kernel<T, PE_SB, false>), dim3((items + 3) / 4, nch - nchd), dim3(256), lds, s, Xs, m, 0, S, X, n, d, nu2, P, Vt, np,
+                       omT, phase, Wf, F, nchd, want_grad, part);
+  }
+  const size_t tot = (size_t)rows * (d + 1);
+  hipLaunchKernelGGL((paths_eval_finish_kernel<T>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, part, nchd, nch, rows, d, F, P,
+                     want_grad, f, df);
+}
+#define PATHS_INST(T)                                                                                                                     \
+  template void launch_paths_scale_omega<T>(const T*, int, int, const EvalParams*, double*, hipStream_t);                                  \
+  template void launch_paths_project<T>(const T*, int, int, int, const double*, const double*, int, const double*, int, int, const T*,     \
+                                        const T*, const EvalParams*, double*, T*, hipStream_t);                                            \
+  template void launch_paths_eval<T>(const T*, int, int, int, const T*, int, int, int, int, const EvalParams*, const T*, const double*,    \
+                                     const double*, const double*, int, int, double*, T*, T*, hipStream_t);
+PATHS_INST(double)
+PATHS_INST(float)
+#undef PATHS_INST
+
 // Per-device one-time setup: kernels that use more than 64 KiB of dynamic LDS need the attribute raised.  Called from
 // hbegp_ctx_create() for every device, before any stream capture.
 static void init_dag_kernels();  // dag_kernel.inc.hpp (end of this file)

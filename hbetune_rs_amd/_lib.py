@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("HBEGP_LIB") or os.path.join(HERE, "libhbegp.so")  # H
 
 OK, NOT_PD, ALL_FAILED = 0, 1, 2
 EINVAL, EHIP, ENODEV, ENOMEM = -1, -2, -3, -4
+PATHS_MAX_FEATURES, PATHS_MAX_PATHS = 16384, 1024  # HBEGP_PATHS_MAX_* of include/hbegp.h
 
 
 class HbegpError(RuntimeError):
@@ -97,6 +98,15 @@ SIGNATURES = {
     "hbegp_maximize_qei_f32": (C.c_int, [_vp, _fp, C.c_int, C.c_int, _dp, _dp, _fp, C.c_int, C.c_double, C.c_double, C.c_int, _fp,
                                          _dp, _ip]),
     "hbegp_debug_qei_phases": (C.c_int, [C.c_int, _dp]),
+    "hbegp_paths_create_f64": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_int, C.c_int, C.POINTER(_vp)]),
+    "hbegp_paths_create_f32": (C.c_int, [_vp, _fp, _fp, _fp, _fp, C.c_int, C.c_int, C.POINTER(_vp)]),
+    "hbegp_paths_eval_f64": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp]),
+    "hbegp_paths_eval_f32": (C.c_int, [_vp, _fp, C.c_int, C.c_int, _fp, _fp]),
+    "hbegp_paths_minimize_f64": (C.c_int, [_vp, _dp, C.c_int, _dp, _dp, C.c_int, _dp, _dp, _ip]),
+    "hbegp_paths_minimize_f32": (C.c_int, [_vp, _fp, C.c_int, _dp, _dp, C.c_int, _fp, _dp, _ip]),
+    "hbegp_paths_info": (C.c_int, [_vp, _ip, _ip, _ip, _ip, _ip]),
+    "hbegp_paths_release": (None, [_vp]),
+    "hbegp_debug_paths_phases": (C.c_int, [C.c_int, _dp]),
     "hbegp_debug_posterior_phases": (C.c_int, [C.c_int, _dp]),
     "hbegp_debug_batch_select_phases": (C.c_int, [C.c_int, _dp]),
     "hbegp_model_info": (C.c_int, [_vp, _ip, _ip, _ip, _dp, _dp]),

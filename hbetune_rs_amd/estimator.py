@@ -326,6 +326,18 @@ class SurrogateModelGPR:
         z = rng.standard_normal((int(n_samples), starts.shape[-2])).astype(self.dtype)
         return self.fitted.maximize_qei(starts, lo, hi, z, self._fmin_normalized(fmin), jitter=jitter, maxeval=maxeval)
 
+    # Posterior sample paths (opt-in; nothing the estimator suggests by default uses them).
+    def sample_paths_a(self, n_paths, n_features, rng, noise_draw=True):
+        """n_paths posterior draws of the surrogate that are functions (FittedKernel.sample_paths), in the normalised y space:
+        random Fourier frequencies from gpr.draw_spectral, weights and, with noise_draw, the noise draw from rng.standard_normal.
+        Project values with y_norm.project_location_from_normalized as sample_a does; the projection is monotone increasing, so
+        a path's minimiser is the projected path's."""
+        fk = self.fitted
+        omega0, phase = gpr.draw_spectral(fk.nu, int(n_features), fk.d, rng)
+        w = rng.standard_normal((int(n_paths), int(n_features)))
+        eps = rng.standard_normal((int(n_paths), fk.n)) if noise_draw else None
+        return fk.sample_paths(omega0, phase, w, eps)
+
     # Batched forms of the scalar trait methods (SURVEY.md 8f rank 1: the acquisition loops call these once per generation
     # instead of m single-point predicts, each of which reads all of K^-1).
     def predict_confidence_bound_a(self, x, cb):
@@ -389,6 +401,30 @@ def acquire_by_thompson(candidates, model, k, rng, jitter=0.0):
     z = rng.standard_normal((int(k), c.shape[0])).astype(model.dtype)
     _, argmin = model.fitted.sample_posterior(c, z, jitter=jitter, want_samples=False)
     return np.asarray(argmin, dtype=np.int64)
+
+
+def acquire_by_path_thompson(model, k, rng, bounds, n_features=1024, n_restarts=8, starts=None, maxeval=150, noise_draw=True):
+    """Batch Thompson sampling without a candidate set: k posterior sample paths of the surrogate (sample_paths_a) and, for
+    each, its minimiser in the box `bounds` = [(lo, hi)] per feature, found by n_restarts bounded L-BFGS descents per path from
+    `starts` [k, n_restarts, d] (or [n_restarts, d], shared; default: uniform in the box from rng).  Returns x [k, n_features
+    of the space], one point per path.  The y projection is monotone increasing, so the minimiser of a normalised path is the
+    minimiser of the projected one.  Opt-in: the grid-free twin of acquire_by_thompson."""
+    k = int(k)
+    lo = np.array([b[0] for b in bounds], dtype=np.float64)
+    hi = np.array([b[1] for b in bounds], dtype=np.float64)
+    d = lo.shape[0]
+    if starts is None:
+        u = np.asarray(rng.uniform(0.0, 1.0, k * int(n_restarts) * d), dtype=np.float64).reshape(k, int(n_restarts), d)
+        starts = lo + (hi - lo) * u
+    paths = model.sample_paths_a(k, n_features, rng, noise_draw=noise_draw)
+    try:
+        st = np.asarray(starts, dtype=model.dtype)  # rounded into the box where the cast left it
+        st = np.where(st.astype(np.float64) > hi, np.nextafter(st, st.dtype.type(-np.inf)), st)
+        st = np.where(st.astype(np.float64) < lo, np.nextafter(st, st.dtype.type(np.inf)), st)
+        x, _, _ = paths.minimize(st, lo, hi, maxeval=maxeval)
+    finally:
+        paths.release()
+    return x
 
 
 def acquire_by_batch_ei(candidates, model, k, fmin, lie=None):

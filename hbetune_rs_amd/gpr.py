@@ -423,6 +423,26 @@ class FittedKernel:
                       float(jitter), int(maxeval), _lib.aptr(x), _lib.dptr(qei), nevals.ctypes.data_as(C.POINTER(C.c_int))))
         return x, qei, nevals
 
+    def sample_paths(self, omega0, phase, w, eps=None):
+        """Posterior sample paths (hbegp_paths_create_*) in the normalised y space: draws of the posterior that are functions,
+        f_s(x) = phi(x) . w_s + k(x, X) . v_s (pathwise conditioning on a random-Fourier-feature prior draw).  omega0 [F, d] and
+        phase [F] from draw_spectral, w [S, F] standard normals, eps [S, n] standard normals or None (no noise draw).  Returns
+        a PosteriorPaths, which keeps the model alive."""
+        lib = _lib.load()
+        omega0 = _lib.as_c(omega0, self.dtype)
+        phase = _lib.as_c(phase, self.dtype)
+        w = _lib.as_c(np.atleast_2d(w), self.dtype)
+        assert omega0.ndim == 2 and omega0.shape[1] == self.d, omega0.shape
+        F, S = omega0.shape[0], w.shape[0]
+        assert phase.shape == (F,) and w.shape == (S, F), (phase.shape, w.shape)
+        if eps is not None:
+            eps = _lib.as_c(np.atleast_2d(eps), self.dtype)
+            assert eps.shape == (S, self.n), eps.shape
+        h = C.c_void_p()
+        fn = getattr(lib, f"hbegp_paths_create_{self._sfx}")
+        _lib.check(fn(self._h, _lib.aptr(omega0), _lib.aptr(phase), _lib.aptr(w), _lib.aptr(eps), F, S, C.byref(h)))
+        return PosteriorPaths(h, self.dtype, self.d, F, S)
+
     def release(self):
         if self._h:
             _lib.load().hbegp_model_release(self._h)
@@ -433,6 +453,80 @@ class FittedKernel:
             self.release()
         except Exception:
             pass
+
+
+class PosteriorPaths:
+    """S posterior sample paths of one model (the hbegp_paths handle; FittedKernel.sample_paths)."""
+
+    def __init__(self, handle, dtype, d, n_features, n_paths):
+        self._h = handle
+        self.dtype = np.dtype(dtype)
+        self.d, self.n_features, self.n_paths = d, n_features, n_paths
+        self._sfx = _suffix(dtype)
+
+    def evaluate(self, x, want_grad=True):
+        """x [m, d]: every path at the same m points; x [S, m, d]: path s at its own points x[s].  Returns (f[S, m], df[S, m, d]
+        or None).  The same (path, point) gives the same bits either way, alone or in a batch."""
+        x = _lib.as_c(x, self.dtype)
+        assert x.ndim in (2, 3) and x.shape[-1] == self.d, x.shape
+        per_path = x.ndim == 3
+        if per_path:
+            assert x.shape[0] == self.n_paths, x.shape
+        m = x.shape[-2]
+        f = np.zeros((self.n_paths, m), dtype=self.dtype)
+        df = np.zeros((self.n_paths, m, self.d), dtype=self.dtype) if want_grad else None
+        fn = getattr(_lib.load(), f"hbegp_paths_eval_{self._sfx}")
+        _lib.check(fn(self._h, _lib.aptr(x), m, 1 if per_path else 0, _lib.aptr(f), _lib.aptr(df)))
+        return f, df
+
+    def minimize(self, starts, lo, hi, maxeval=150):
+        """Bounded L-BFGS descents of every path from its own starts [S, R, d] (or [R, d]: the same starts for every path) inside
+        the box [lo, hi], all S R runs in lockstep.  Returns (x_best[S, d], f_best[S], nevals[S]): per path the best point any of
+        its runs evaluated."""
+        starts = _lib.as_c(starts, self.dtype)
+        if starts.ndim == 2:
+            starts = np.ascontiguousarray(np.broadcast_to(starts, (self.n_paths,) + starts.shape))
+        assert starts.ndim == 3 and starts.shape[0] == self.n_paths and starts.shape[2] == self.d, starts.shape
+        lo = _lib.as_c(lo, np.float64)
+        hi = _lib.as_c(hi, np.float64)
+        assert lo.shape == (self.d,) and hi.shape == (self.d,)
+        x = np.zeros((self.n_paths, self.d), dtype=self.dtype)
+        fb = np.zeros(self.n_paths)
+        nevals = np.zeros(self.n_paths, dtype=np.int32)
+        fn = getattr(_lib.load(), f"hbegp_paths_minimize_{self._sfx}")
+        _lib.check(fn(self._h, _lib.aptr(starts), starts.shape[1], _lib.dptr(lo), _lib.dptr(hi), int(maxeval), _lib.aptr(x), _lib.dptr(fb),
+                      nevals.ctypes.data_as(C.POINTER(C.c_int))))
+        return x, fb, nevals
+
+    def release(self):
+        if self._h:
+            _lib.load().hbegp_paths_release(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
+
+
+def draw_spectral(nu, n_features, d, rng):
+    """Random Fourier frequencies and phases of the Matern-nu kernel at unit length scale, from rng.standard_normal and
+    rng.uniform only: omega0 [F, d] and phase [F] in [0, 2 pi).  nu = inf (the squared-exponential kernel): standard normals.
+    Matern nu (2 nu in {1, 3, 5}): a multivariate Student-t with 2 nu degrees of freedom -- a standard normal vector divided by
+    sqrt(chi2_{2 nu} / (2 nu)), the chi-square being a sum of 2 nu squared standard normals."""
+    F, d = int(n_features), int(d)
+    z = np.asarray(rng.standard_normal((F, d)), dtype=np.float64)
+    if math.isinf(nu):
+        omega0 = z
+    else:
+        dof = int(round(2 * nu))
+        if dof not in (1, 3, 5) or abs(2 * nu - dof) > 1e-12:
+            raise ValueError("nu must be 0.5, 1.5, 2.5 or inf")
+        g = (np.asarray(rng.standard_normal((F, dof)), dtype=np.float64) ** 2).sum(axis=1)
+        omega0 = z * np.sqrt(dof / g)[:, None]
+    phase = 2.0 * math.pi * np.asarray(rng.uniform(0.0, 1.0, F), dtype=np.float64)
+    return omega0, phase
 
 
 def minimize_by_gradient(objective, x0, bounds, maxeval=150):

@@ -375,6 +375,54 @@ int hbegp_debug_batch_select_phases(int enable, double* phase_ms);
  * z), the qEI kernel -- in milliseconds; then enable != 0 makes this thread's later qEI calls timed. */
 int hbegp_debug_qei_phases(int enable, double* phase_ms);
 
+/* ---- posterior sample paths: draws of the posterior that are FUNCTIONS (pathwise conditioning, Matheron's rule, on a
+ * random-Fourier-feature prior draw).  In the model's normalised y space,
+ *   f_s(x) = phi(x) . w_s + k(x, X) . v_s,    v_s = K^-1 (y - Phi(X) w_s - sqrt(sigma^2) eps_s),   K = k(X, X) + sigma^2 I
+ *   phi_j(x) = sqrt(2 c / F) cos(om_j . x + b_j),   om_jk = omega0_jk / ell_k
+ * All randomness is the caller's: omega0[F*d] drawn from the kernel's spectral density at unit length scale (nu = inf: standard
+ * normals; Matern nu: a standard normal vector divided by sqrt(chi2_{2 nu} / (2 nu)) per feature), phase[F] uniform in
+ * [0, 2 pi), w[S*F] standard normals, eps[S*n] standard normals or NULL (no noise draw: eps = 0; bit-identical to zeros).
+ * hbegp_paths_create_* computes v on the device through L^-1 (two triangular tile products over all S right-hand sides,
+ * never the stored K^-1) and keeps V, w and the scaled frequencies there.  The handle retains the model (the model may be
+ * released first) and lives on the model's device.
+ * Limits: 1 <= F <= HBEGP_PATHS_MAX_FEATURES, 1 <= S <= HBEGP_PATHS_MAX_PATHS; larger values are HBEGP_EINVAL, never
+ * truncated.  The handle holds 8 (S F + F d + F) bytes and S_p n_p elements; the preparation borrows at most max(128 MiB, 8 n S bytes) of
+ * partial sums and two more S_p n_p operands from the block pool (S_p, n_p: rounded up to 128), and gives them back.
+ *
+ * hbegp_paths_eval_*: f[S*m] (path-major) and, unless df is NULL, df[S*m*d] = d f_s / d x at
+ *   per_path = 0: the same m points Xs[m*d] for every path;   per_path = 1: path s at its own m points Xs[(s*m + i)*d ..].
+ * The phase, sin / cos, the kernel's slope psi and every sum are fp64 for both element types; r^2 is formed as in hbegp_predict_*.
+ * A training point at r = 0 contributes 0 to the gradient (as in hbegp_predict_grad_*).  A NaN in a query row gives NaN in that
+ * row's outputs only.  Sums run in a fixed order without atomics, and a (path, point) pair's sums do not depend on the rest of
+ * the call: the same pair gives the same bits alone, in a batch of any m, with shared or per-path points, from any thread.
+ * m = 0 is a no-op.  Points are evaluated in blocks, so m is bounded only by the caller's arrays.
+ *
+ * hbegp_paths_minimize_*: S*R bounded L-BFGS descents (the fit optimiser's method and constants), R per path from
+ * starts[(s*R + r)*d ..] inside [lo, hi], in lockstep: one per-path evaluation per round over the runs still going.  Each path
+ * returns the best point any of its R runs evaluated: x_best[S*d], f_best[S] (the value hbegp_paths_eval_* gives there, bit for
+ * bit), n_evals[S] (may be NULL; summed over the path's runs).  f32 points are rounded into the box.  d <= 66 (the optimiser's
+ * state).  maxeval >= 1 is per run. */
+#define HBEGP_PATHS_MAX_FEATURES 16384
+#define HBEGP_PATHS_MAX_PATHS 1024
+typedef struct hbegp_paths hbegp_paths;
+int hbegp_paths_create_f64(hbegp_model* model, const double* omega0, const double* phase, const double* w, const double* eps, int F, int S,
+                           hbegp_paths** paths);
+int hbegp_paths_create_f32(hbegp_model* model, const float* omega0, const float* phase, const float* w, const float* eps, int F, int S,
+                           hbegp_paths** paths);
+int hbegp_paths_eval_f64(hbegp_paths* paths, const double* Xs, int m, int per_path, double* f, double* df);
+int hbegp_paths_eval_f32(hbegp_paths* paths, const float* Xs, int m, int per_path, float* f, float* df);
+int hbegp_paths_minimize_f64(hbegp_paths* paths, const double* starts, int R, const double* lo, const double* hi, int maxeval,
+                             double* x_best, double* f_best, int* n_evals);
+int hbegp_paths_minimize_f32(hbegp_paths* paths, const float* starts, int R, const double* lo, const double* hi, int maxeval,
+                             float* x_best, double* f_best, int* n_evals);
+/* n, d of the model, F, S, element type; any pointer may be NULL */
+int hbegp_paths_info(const hbegp_paths* paths, int* n, int* d, int* n_features, int* n_paths, int* is_f32);
+void hbegp_paths_release(hbegp_paths* paths);
+/* ---- timing hook (tools/paths_bench.py): phase_ms[3] (may be NULL) receives the device time of the phases of the calling
+ * thread's last timed hbegp_paths_create_* call -- uploads and the frequency scaling, the feature projection, the two triangular
+ * products -- in milliseconds; then enable != 0 makes this thread's later create calls timed. */
+int hbegp_debug_paths_phases(int enable, double* phase_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -69,6 +69,15 @@ template <> struct Abi<double> {
                           double j, int maxeval, double* x, double* v, int* ne) {
     return hbegp_maximize_qei_f64(m, st, r, q, lo, hi, z, s, fmin, j, maxeval, x, v, ne);
   }
+  static int paths_create(hbegp_model* m, const double* om, const double* ph, const double* w, const double* eps, int F, int S, hbegp_paths** p) {
+    return hbegp_paths_create_f64(m, om, ph, w, eps, F, S, p);
+  }
+  static int paths_eval(hbegp_paths* p, const double* xs, int m, int per_path, double* f, double* df) {
+    return hbegp_paths_eval_f64(p, xs, m, per_path, f, df);
+  }
+  static int paths_minimize(hbegp_paths* p, const double* st, int R, const double* lo, const double* hi, int maxeval, double* x, double* f, int* ne) {
+    return hbegp_paths_minimize_f64(p, st, R, lo, hi, maxeval, x, f, ne);
+  }
   static int get(hbegp_model* m, double* t, double* a, double* ki) { return hbegp_model_get_f64(m, t, a, ki); }
 };
 template <> struct Abi<float> {
@@ -98,6 +107,15 @@ template <> struct Abi<float> {
                           double j, int maxeval, float* x, double* v, int* ne) {
     return hbegp_maximize_qei_f32(m, st, r, q, lo, hi, z, s, fmin, j, maxeval, x, v, ne);
   }
+  static int paths_create(hbegp_model* m, const float* om, const float* ph, const float* w, const float* eps, int F, int S, hbegp_paths** p) {
+    return hbegp_paths_create_f32(m, om, ph, w, eps, F, S, p);
+  }
+  static int paths_eval(hbegp_paths* p, const float* xs, int m, int per_path, float* f, float* df) {
+    return hbegp_paths_eval_f32(p, xs, m, per_path, f, df);
+  }
+  static int paths_minimize(hbegp_paths* p, const float* st, int R, const double* lo, const double* hi, int maxeval, float* x, double* f, int* ne) {
+    return hbegp_paths_minimize_f32(p, st, R, lo, hi, maxeval, x, f, ne);
+  }
   static int get(hbegp_model* m, double* t, float* a, float* ki) { return hbegp_model_get_f32(m, t, a, ki); }
 };
 }  // namespace detail
@@ -106,6 +124,9 @@ template <> struct Abi<float> {
 struct KernelBounds {
   std::vector<double> lo, hi;  // order [noise, amplitude, ell_1..ell_d]
 };
+
+template <typename A>
+class PathsT;
 
 template <typename A>
 class FittedKernel {
@@ -197,6 +218,8 @@ class FittedKernel {
                     int maxeval, A* x_out, double* qei_out, int* nevals = nullptr, double jitter = 0.0) const {
     check(detail::Abi<A>::maximize_qei(h_, starts, R, q, lo, hi, z, S, fmin_normalized, jitter, maxeval, x_out, qei_out, nevals));
   }
+  // S posterior sample paths (draws that are functions) from the caller's omega0[F*d], phase[F], w[S*F], eps[S*n] or nullptr
+  PathsT<A> sample_paths(const A* omega0, const A* phase, const A* w, const A* eps, int F, int S) const;
   double lml() const { return lml_; }
   double noise() const { return std::exp(theta_[0]); }
   double amplitude() const { return std::exp(theta_[1]); }
@@ -215,5 +238,35 @@ class FittedKernel {
   std::vector<double> theta_;
   double lml_ = 0;
 };
+
+// RAII owner of an hbegp_paths handle (FittedKernel::sample_paths); it keeps its model alive
+template <typename A>
+class PathsT {
+ public:
+  PathsT() = default;
+  explicit PathsT(hbegp_paths* h) : h_(h) {}
+  PathsT(const PathsT&) = delete;
+  PathsT& operator=(const PathsT&) = delete;
+  PathsT(PathsT&& o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+  PathsT& operator=(PathsT&& o) noexcept { std::swap(h_, o.h_); return *this; }
+  ~PathsT() { hbegp_paths_release(h_); }
+  // f[S*m], df[S*m*d] (may be nullptr) at xs[m*d] (per_path = false) or xs[S*m*d] (per_path = true)
+  void eval(const A* xs, int m, bool per_path, A* f, A* df) const { check(detail::Abi<A>::paths_eval(h_, xs, m, per_path ? 1 : 0, f, df)); }
+  // per path the best point of R bounded L-BFGS descents from starts[S*R*d]: x_best[S*d], f_best[S], nevals[S] (may be nullptr)
+  void minimize(const A* starts, int R, const double* lo, const double* hi, int maxeval, A* x_best, double* f_best, int* nevals = nullptr) const {
+    check(detail::Abi<A>::paths_minimize(h_, starts, R, lo, hi, maxeval, x_best, f_best, nevals));
+  }
+  hbegp_paths* handle() const { return h_; }
+
+ private:
+  hbegp_paths* h_ = nullptr;
+};
+
+template <typename A>
+PathsT<A> FittedKernel<A>::sample_paths(const A* omega0, const A* phase, const A* w, const A* eps, int F, int S) const {
+  hbegp_paths* p = nullptr;
+  check(detail::Abi<A>::paths_create(h_, omega0, phase, w, eps, F, S, &p));
+  return PathsT<A>(p);
+}
 
 }  // namespace hbegp
