@@ -178,6 +178,25 @@ void launch_gradtrace(const T* X, int n, int d, int np, int nu2, const EvalParam
                       double* part, EvalOut* out, const int* info, hipStream_t s, int* ticket = nullptr, EvalOut* hout = nullptr);
 size_t gradtrace_part_elems(int np, int d);
 
+// Leave-one-out cross-validation (hbegp_model_loo / hbegp_problem_eval_loo; kernels.hip: loo_*_kernel), all on one stream:
+//   diag:  m_j = column sums of squares of Xinv = L^-1 (rows < n), then mean / var / lpd [n] (T), avec = alpha / m and
+//          sbvec = sqrt((1 + alpha^2 / m) / (2 m)) [np] (fp64, zero on the padding), out->lml = loo, out->done |= 1;
+//          part: loo_diag_part_elems(np, n) doubles
+//   uy:    Y = K^-1 diag(sbvec) (full np x np, zero padding) and u = K^-1 avec [np] (T) from the LOWER triangle of Kinv;
+//          pu: loo_u_part_elems(np) doubles
+//   trace: out->grad[j] = 1/2 sum_ik (u_i alpha_k + alpha_i u_k - 2 Cm_ik) dK_ik/dtheta_j over the lower triangle of Cm = Y Y^T,
+//          out->done |= 2; part: gradtrace_part_elems(np, d) doubles; skipped when out->info != 0
+size_t loo_diag_part_elems(int np, int n);
+size_t loo_u_part_elems(int np);
+template <typename T>
+void launch_loo_diag(const T* Xinv, int np, int n, const T* y, const T* alpha, double* part, T* mean, T* var, T* lpd, double* avec,
+                     double* sbvec, EvalOut* out, hipStream_t s);
+template <typename T>
+void launch_loo_uy(const T* Kinv, int np, int n, const double* avec, const double* sbvec, T* Y, double* pu, T* u, hipStream_t s);
+template <typename T>
+void launch_loo_trace(const T* X, int n, int d, int np, int nu2, const EvalParams* P, const T* Cm, const T* alpha, const T* u,
+                      double* part, EvalOut* out, hipStream_t s);
+
 template <typename T>
 void launch_symmetrize(T* A, int np, hipStream_t s);  // mirror lower -> upper
 

@@ -656,6 +656,19 @@ struct DagPlanKey {
 };
 static std::atomic<int> g_dev_busy[MAX_DEVS];  // optimiser runs in flight per device id, over all fits of the process
 
+// What the leave-one-out tail (loo_tail, below the model) reads: the results an evaluation left on the device.  Kinv is read on and
+// below the diagonal only (a slot's buffer is not mirrored), P may be a pinned host block.
+template <typename T>
+struct LooIn {
+  int dev;
+  hipStream_t s;
+  int n, d, np, nu2;
+  const T *X, *y, *alpha, *Xinv, *Kinv;
+  const EvalParams* P;
+};
+template <typename T>
+static int loo_tail(const LooIn<T>& in, T* mean, T* var, T* lpd, double* loo, double* grad);
+
 template <typename T>
 struct Slot {
   int dev = 0;
@@ -698,6 +711,7 @@ struct ProblemBase {
   bool is_f32 = false;
   virtual ~ProblemBase() {}
   virtual int eval(int dev, int slot, const double* theta, const double* lo, const double* hi, double* lml, double* grad) = 0;
+  virtual int eval_loo(int dev, int slot, const double* theta, const double* lo, const double* hi, double* loo, double* grad) = 0;
   virtual int time_eval(int dev, int slot, const double* theta, int reps, double* phase_ms) = 0;
   virtual int time_concurrent(int dev, const double* theta, int reps, double* out) = 0;
 };
@@ -1444,6 +1458,28 @@ struct Problem : ProblemBase {
     // never overwrite the captured best: write into the other buffer
     const int target = (s.best_idx < 0) ? 0 : 1 - s.best_idx;
     return run_eval((size_t)dev, slot, target, grad != nullptr, true, lml, grad);
+  }
+
+  // The leave-one-out tail on what the slot's last evaluation left behind: L^-1 in W2 (every evaluation path -- the single launch
+  // in the LDS, the launches, the task queue -- writes it there), K^-1 and alpha in the buffer it wrote, the parameters in the
+  // pinned block.  Reads only; its work arrays are borrowed for the call.
+  int loo_on_slot(size_t di, int si, double* loo, double* grad) {
+    Slot<T>& s = slots[di][si];
+    const LooIn<T> in{s.dev, s.stream, n, d, np, nu2, Xd[di], yd[di], s.alpha[s.last_target], s.W2, s.Kinv[s.last_target], s.hP};
+    return loo_tail<T>(in, nullptr, nullptr, nullptr, loo, grad);
+  }
+
+  int eval_loo(int dev, int slot, const double* theta, const double* lo, const double* hi, double* loo, double* grad) override {
+    double lml;
+    const int st = eval(dev, slot, theta, lo, hi, &lml, nullptr);
+    if (st != HBEGP_OK) {
+      if (st == HBEGP_NOT_PD) {
+        *loo = -std::numeric_limits<double>::infinity();
+        if (grad) for (int j = 0; j < d + 2; ++j) grad[j] = 0.0;
+      }
+      return st;
+    }
+    return loo_on_slot((size_t)dev, slot, loo, grad);
   }
 
   int time_eval(int dev, int slot, const double* theta, int reps, double* phase_ms) override {
@@ -2314,6 +2350,107 @@ static int model_maximize_qei(hbegp_model* m, const T* starts, int R, int q, con
   return HBEGP_OK;
 }
 
+// ---- leave-one-out cross-validation (hbegp_model_loo / hbegp_problem_eval_loo / hbegp_fit_loo) ----------
+// phase times of the calling thread's last timed call with a gradient (hbegp_debug_loo_phases): diagonal pass, u and Y, the
+// SYRK, the weighted trace, in ms
+static thread_local bool t_time_loo = false;
+static thread_local double t_loo_ms[4] = {0, 0, 0, 0};
+
+// The diagnostics from L^-1 and alpha (one memory-bound pass), and with `grad` the gradient of their sum: u = K^-1 a and
+// Y = K^-1 diag(sqrt b) in one pass over K^-1, C = Y Y^T by ONE tile GEMM for all p parameters, and gradtrace's pass with the
+// weight u alpha^T + alpha u^T - 2 C.  Y and C (np^2 elements each) are borrowed only with `grad`; everything borrowed goes
+// back cleared.  Any of the outputs may be null.  A result that is not finite (NaN data) is HBEGP_NOT_PD: loo = -inf, grad = 0.
+template <typename T>
+static int loo_tail(const LooIn<T>& in, T* mean, T* var, T* lpd, double* loo, double* grad) {
+  HIPCHECK(hipSetDevice(in.dev));
+  const int n = in.n, np = in.np, p = in.d + 2;
+  const size_t nn = (size_t)np * np;
+  if (grad && 2.0 * (double)sizeof(T) * (double)np * np > 1e15)
+    return fail(HBEGP_ENOMEM, "the leave-one-out gradient of %d rows needs %.3g bytes of device memory", n, 2.0 * sizeof(T) * (double)np * np);
+  hipStream_t s = in.s;
+  CallScratch ws{in.dev, s, {}};
+  // the small arrays: one borrowed block
+  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+  const size_t b_vec = up(sizeof(T) * np), b_dvec = up(sizeof(double) * np), b_out = up(sizeof(EvalOut));
+  const size_t b_part = up(sizeof(double) * loo_diag_part_elems(np, n));
+  const size_t b_pu = grad ? up(sizeof(double) * loo_u_part_elems(np)) : 0;
+  const size_t b_pg = grad ? up(sizeof(double) * gradtrace_part_elems(np, in.d)) : 0;
+  char* q = static_cast<char*>(ws.get(b_out + 4 * b_vec + 2 * b_dvec + b_part + b_pu + b_pg));
+  EvalOut* dout = reinterpret_cast<EvalOut*>(q); q += b_out;
+  T* dmean = reinterpret_cast<T*>(q); q += b_vec;
+  T* dvar = reinterpret_cast<T*>(q); q += b_vec;
+  T* dlpd = reinterpret_cast<T*>(q); q += b_vec;
+  T* du = reinterpret_cast<T*>(q); q += b_vec;
+  double* avec = reinterpret_cast<double*>(q); q += b_dvec;
+  double* sbvec = reinterpret_cast<double*>(q); q += b_dvec;
+  double* part = reinterpret_cast<double*>(q); q += b_part;
+  double* pu = reinterpret_cast<double*>(q); q += b_pu;
+  double* part_g = reinterpret_cast<double*>(q);
+  HIPCHECK(hipMemsetAsync(dout, 0, sizeof(EvalOut), s));  // info = 0, done = 0 (a recycled block holds its earlier owner's numbers)
+  hipEvent_t ev[5] = {};
+  const bool timed = t_time_loo && grad;
+  if (timed)
+    for (auto& e : ev) HIPCHECK(hipEventCreate(&e));
+  if (timed) HIPCHECK(hipEventRecord(ev[0], s));
+  launch_loo_diag<T>(in.Xinv, np, n, in.y, in.alpha, part, dmean, dvar, dlpd, avec, sbvec, dout, s);
+  if (timed) HIPCHECK(hipEventRecord(ev[1], s));
+  if (grad) {
+    T* Y = static_cast<T*>(ws.get(sizeof(T) * nn));
+    T* Cm = static_cast<T*>(ws.get(sizeof(T) * nn));
+    launch_loo_uy<T>(in.Kinv, np, n, avec, sbvec, Y, pu, du, s);
+    if (timed) HIPCHECK(hipEventRecord(ev[2], s));
+    {
+      // C = Y Y^T (lower tiles), contraction over all columns of Y
+      GemmLaunch g{};
+      g.nops = 1;
+      GemmOp& op = g.op[0];
+      op.A = Y; op.B = Y; op.C = Cm;
+      op.lda = op.ldb = op.ldc = np;
+      op.mi = np / NB; op.nj = np / NB; op.c_lower = 1;
+      op.k0 = 0; op.k1 = np / NB;
+      gemm_adhoc<T>(g, &dout->info, s);
+    }
+    if (timed) HIPCHECK(hipEventRecord(ev[3], s));
+    launch_loo_trace<T>(in.X, n, in.d, np, in.nu2, in.P, Cm, in.alpha, du, part_g, dout, s);
+    if (timed) HIPCHECK(hipEventRecord(ev[4], s));
+  }
+  CHECK_LAUNCHES();
+  EvalOut out;
+  HIPCHECK(hipMemcpyAsync(&out, dout, sizeof(EvalOut), hipMemcpyDeviceToHost, s));
+  if (mean) HIPCHECK(hipMemcpyAsync(mean, dmean, sizeof(T) * n, hipMemcpyDeviceToHost, s));
+  if (var) HIPCHECK(hipMemcpyAsync(var, dvar, sizeof(T) * n, hipMemcpyDeviceToHost, s));
+  if (lpd) HIPCHECK(hipMemcpyAsync(lpd, dlpd, sizeof(T) * n, hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
+  if (timed) {
+    for (int i = 0; i < 4; ++i) {
+      float ms = 0;
+      HIPCHECK(hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
+      t_loo_ms[i] = ms;
+    }
+    for (auto& e : ev) (void)hipEventDestroy(e);
+  }
+  if (!(out.done & 1) || (grad && !(out.done & 2)))
+    throw HipError{hipErrorLaunchFailure, "leave-one-out: the kernels did not run", __LINE__};
+  bool finite = std::isfinite(out.lml);
+  if (grad) for (int j = 0; j < p; ++j) finite = finite && std::isfinite(out.grad[j]);
+  if (!finite) {
+    if (loo) *loo = -std::numeric_limits<double>::infinity();
+    if (grad) for (int j = 0; j < p; ++j) grad[j] = 0.0;
+    return fail(HBEGP_NOT_PD, "the leave-one-out pseudo-likelihood is not finite");
+  }
+  if (loo) *loo = out.lml;
+  if (grad) for (int j = 0; j < p; ++j) grad[j] = out.grad[j];
+  return HBEGP_OK;
+}
+
+template <typename T>
+static int model_loo(hbegp_model* m, T* mean, T* var, T* lpd, double* loo, double* grad) {
+  std::lock_guard<std::mutex> lock(m->mu);
+  const LooIn<T> in{m->dev, m->stream, m->n, m->d, m->np, m->nu2, static_cast<const T*>(m->X), static_cast<const T*>(m->y),
+                    static_cast<const T*>(m->alpha), static_cast<const T*>(m->Xinv), static_cast<const T*>(m->Kinv), m->dP};
+  return loo_tail<T>(in, mean, var, lpd, loo, grad);
+}
+
 // ---- posterior sample paths (hbegp_paths_*) ------------------------------------------------------------
 // The handle keeps, on the model's device: om^T [d][F] = omega0^T / ell, the phases [F] and the weights [S][F] in fp64, and
 // V^T [S_p][n_p] (one path per row: the tile GEMMs' operand layout).  Its calls run on the model's stream under the model's
@@ -2629,9 +2766,16 @@ static int read_fit_options(const hbegp_fit_options* in, hbegp_fit_options* out)
 }
 
 template <typename T>
+static int do_extend(hbegp_ctx* ctx, const T* X, const T* y, int n, int d, double nu, const double* theta, const double* lo,
+                     const double* hi, hbegp_model** model_out);
+
+// loo: the objective is the leave-one-out log pseudo-likelihood (hbegp_fit_loo_*) -- every evaluation is the slot's normal one
+// without the lml gradient plus the leave-one-out tail on its results, always under the host-driven optimiser, and the model
+// is `extend` at the captured theta.  Nothing else differs; loo = false is the fit as it always was.
+template <typename T>
 static int do_fit(hbegp_ctx* ctx, const T* X, const T* y, int n, int d, double nu, const double* theta0, const double* lo,
                   const double* hi, const double* starts, int n_restarts, const hbegp_fit_options* opt_in,
-                  double* theta_best, double* lml_best, hbegp_model** model_out) {
+                  double* theta_best, double* lml_best, hbegp_model** model_out, bool loo = false) {
   hbegp_fit_options opt{};
   if (int e = read_fit_options(opt_in, &opt)) return e;
   if (opt.maxeval <= 0) opt.maxeval = 150;
@@ -2647,7 +2791,7 @@ static int do_fit(hbegp_ctx* ctx, const T* X, const T* y, int n, int d, double n
   // Up to 128 rows an optimiser run is ONE persistent launch on ONE compute unit (small_fit_kernel: evaluation + L-BFGS step +
   // capture on the device): every run gets a slot of its own and all of them run side by side
   constexpr int SMALL_FIT_MAX_RUNS = 64;  // per device
-  bool small_fit = round_up(n, NB) == NB && d <= SMALL_EVAL_MAXD && env_int("HBEGP_SMALL", 1) != 0 && env_int("HBEGP_SMALL_FIT", 1) != 0;
+  bool small_fit = !loo && round_up(n, NB) == NB && d <= SMALL_EVAL_MAXD && env_int("HBEGP_SMALL", 1) != 0 && env_int("HBEGP_SMALL_FIT", 1) != 0;
   for (int di = 0; di < ndev; ++di) small_fit = small_fit && runs_on[di] <= SMALL_FIT_MAX_RUNS;
   if (small_fit)
     for (int di = 0; di < ndev; ++di) n_slots = std::max(n_slots, runs_on[di]);
@@ -2882,7 +3026,12 @@ static int do_fit(hbegp_ctx* ctx, const T* X, const T* y, int n, int d, double n
           theta_to_params(th, lo, hi, d, s.hP);
           const int target = (s.best_idx < 0) ? 0 : 1 - s.best_idx;
           double lml;
-          const int st = prob.run_eval((size_t)di, si, target, true, true, &lml, grad);
+          int st = prob.run_eval((size_t)di, si, target, !loo, true, &lml, loo ? nullptr : grad);
+          if (loo) {
+            if (st == HBEGP_OK) st = prob.loo_on_slot((size_t)di, si, &lml, grad);
+            else for (int j = 0; j < p; ++j) grad[j] = 0.0;
+            if (st != HBEGP_OK && st != HBEGP_NOT_PD) throw std::runtime_error(g_last_error);
+          }
           const int my_eval = eval_idx++;
           n_evals.fetch_add(1);
           if (st != HBEGP_OK) n_not_pd.fetch_add(1);
@@ -2983,6 +3132,12 @@ static int do_fit(hbegp_ctx* ctx, const T* X, const T* y, int n, int d, double n
   }
   if (theta_best) memcpy(theta_best, th.data(), sizeof(double) * p);
   if (lml_best) *lml_best = best.best_lml;
+  if (loo) {
+    // the model is what `extend` gives at theta_best, bit for bit: built through that very path, once the fit's slots are back
+    // in the pool
+    prob.release();
+    return model_out ? do_extend<T>(ctx, X, y, n, d, nu, th.data(), nullptr, nullptr, model_out) : HBEGP_OK;
+  }
   const auto tf2 = std::chrono::steady_clock::now();
   if (host_serial && prob.small_ && !host_lk.owns_lock()) host_lk.lock();
   const auto th1 = std::chrono::steady_clock::now();
@@ -3171,6 +3326,15 @@ int hbegp_problem_eval(hbegp_problem* prob, int dev, int slot, const double* the
   GUARD_END
 }
 
+int hbegp_problem_eval_loo(hbegp_problem* prob, int dev, int slot, const double* theta, const double* lo, const double* hi,
+                           double* loo, double* grad) {
+  if (!prob) return fail(HBEGP_EINVAL, "NULL problem");
+  if (!theta || !loo) return fail(HBEGP_EINVAL, "theta / loo is NULL");
+  GUARD_BEGIN
+  return prob->impl->eval_loo(dev, slot, theta, lo, hi, loo, grad);
+  GUARD_END
+}
+
 int hbegp_problem_time_concurrent(hbegp_problem* prob, int dev, const double* theta, int reps, double* out) {
   if (!prob || !theta || !out || reps < 1) return fail(HBEGP_EINVAL, "bad argument");
   GUARD_BEGIN
@@ -3300,6 +3464,33 @@ int hbegp_fit_f32(hbegp_ctx* ctx, const float* X, const float* y, int n, int d, 
   if (!theta0 || !lo || !hi || (n_restarts > 0 && !starts)) return fail(HBEGP_EINVAL, "theta0/lo/hi/starts is NULL");
   GUARD_BEGIN
   return do_fit<float>(ctx, X, y, n, d, nu, theta0, lo, hi, starts, n_restarts, opt, theta_best, lml_best, model);
+  GUARD_END
+}
+
+int hbegp_fit_loo_f64(hbegp_ctx* ctx, const double* X, const double* y, int n, int d, double nu, const double* theta0,
+                      const double* lo, const double* hi, const double* starts, int n_restarts,
+                      const hbegp_fit_options* opt, double* theta_best, double* loo_best, hbegp_model** model) {
+  {
+    hbegp_fit_options probe;
+    if (int e = read_fit_options(opt, &probe)) return e;
+  }
+  if (int e = check_args(ctx, X, y, n, d, nu)) return e;
+  if (!theta0 || !lo || !hi || (n_restarts > 0 && !starts)) return fail(HBEGP_EINVAL, "NULL theta0/lo/hi/starts");
+  GUARD_BEGIN
+  return do_fit<double>(ctx, X, y, n, d, nu, theta0, lo, hi, starts, n_restarts, opt, theta_best, loo_best, model, true);
+  GUARD_END
+}
+int hbegp_fit_loo_f32(hbegp_ctx* ctx, const float* X, const float* y, int n, int d, double nu, const double* theta0,
+                      const double* lo, const double* hi, const double* starts, int n_restarts,
+                      const hbegp_fit_options* opt, double* theta_best, double* loo_best, hbegp_model** model) {
+  {
+    hbegp_fit_options probe;
+    if (int e = read_fit_options(opt, &probe)) return e;
+  }
+  if (int e = check_args(ctx, X, y, n, d, nu)) return e;
+  if (!theta0 || !lo || !hi || (n_restarts > 0 && !starts)) return fail(HBEGP_EINVAL, "NULL theta0/lo/hi/starts");
+  GUARD_BEGIN
+  return do_fit<float>(ctx, X, y, n, d, nu, theta0, lo, hi, starts, n_restarts, opt, theta_best, loo_best, model, true);
   GUARD_END
 }
 
@@ -3603,6 +3794,31 @@ int hbegp_debug_paths_phases(int enable, double* phase_ms) {
   if (phase_ms)
     for (int i = 0; i < 3; ++i) phase_ms[i] = t_paths_ms[i];
   t_time_paths = enable != 0;
+  return HBEGP_OK;
+}
+// the check that needs no model comes first, so that each one has its own message whatever else is wrong
+static int check_model_loo(hbegp_model* model, bool want_f32, bool any_output) {
+  if (!any_output) return fail(HBEGP_EINVAL, "every output is NULL");
+  if (!model) return fail(HBEGP_EINVAL, "NULL model");
+  if (model->is_f32 != want_f32) return fail(HBEGP_EINVAL, "model holds %s data", model->is_f32 ? "f32" : "f64");
+  return HBEGP_OK;
+}
+int hbegp_model_loo_f64(hbegp_model* model, double* mean, double* var, double* lpd, double* loo, double* grad) {
+  if (int rc = check_model_loo(model, false, mean || var || lpd || loo || grad)) return rc;
+  GUARD_BEGIN
+  return model_loo<double>(model, mean, var, lpd, loo, grad);
+  GUARD_END
+}
+int hbegp_model_loo_f32(hbegp_model* model, float* mean, float* var, float* lpd, double* loo, double* grad) {
+  if (int rc = check_model_loo(model, true, mean || var || lpd || loo || grad)) return rc;
+  GUARD_BEGIN
+  return model_loo<float>(model, mean, var, lpd, loo, grad);
+  GUARD_END
+}
+int hbegp_debug_loo_phases(int enable, double* phase_ms) {
+  if (phase_ms)
+    for (int i = 0; i < 4; ++i) phase_ms[i] = t_loo_ms[i];
+  t_time_loo = enable != 0;
   return HBEGP_OK;
 }
 int hbegp_debug_qei_phases(int enable, double* phase_ms) {

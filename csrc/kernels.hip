@@ -1430,10 +1430,14 @@ __device__ __forceinline__ void block_sums_publish(const double (&v)[NV], int nv
   }
 }
 
-template <typename T, int NU2>
+// LOO (loo_trace_kernel, the gradient of the leave-one-out pseudo-likelihood): the same pass with the weight
+// u_i alpha_k + alpha_i u_k - 2 C_ik, C = K^-1 diag(b) K^-1 read through `Kinv`; nothing else differs, and the lml instantiations
+// compile to the instructions they had before the parameter existed.
+template <typename T, int NU2, bool LOO = false>
 __device__ __forceinline__ void gradtrace_tile(int tile, const T* __restrict__ X, int n, int d, int np, T amp, T noise,
                                                const double* inv_l2, const T* __restrict__ Kinv, const T* __restrict__ alpha,
-                                               double* __restrict__ part, T* xi, T* xj, double* red) {
+                                               double* __restrict__ part, T* xi, T* xj, double* red,
+                                               const T* __restrict__ uvec = nullptr) {
   const int li = tri_row(tile), lj = tile - li * (li + 1) / 2;
   const int i0 = li * 64, j0 = lj * 64;
   const int t = threadIdx.x;
@@ -1495,19 +1499,24 @@ __device__ __forceinline__ void gradtrace_tile(int tile, const T* __restrict__ X
     if (li > lj && i0 + 64 <= n) {
       // a tile strictly below the diagonal and wholly inside the matrix: every entry counts twice, no bounds tests
       const vec4 aj = *reinterpret_cast<const vec4*>(alpha + j0 + tx * 4);
+      vec4 uj{};
+      if constexpr (LOO) uj = *reinterpret_cast<const vec4*>(uvec + j0 + tx * 4);
       vec4 kv[4];
-      T ai[4];
+      T ai[4], ui[4];
 #pragma unroll
       for (int r = 0; r < 4; ++r) {  // the four rows' loads together
         const int gi = i0 + ty + 16 * r;
         ai[r] = alpha[gi];
+        if constexpr (LOO) ui[r] = uvec[gi];
         kv[r] = *reinterpret_cast<const vec4*>(Kinv + (size_t)gi * np + j0 + tx * 4);
       }
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-          const T w = ai[r] * aj[c] - kv[r][c];  // lml.rs:62 (tmp)
+          T w;
+          if constexpr (LOO) w = (ui[r] * aj[c] + ai[r] * uj[c]) - T(2) * kv[r][c];
+          else w = ai[r] * aj[c] - kv[r][c];  // lml.rs:62 (tmp)
           T km, gr;
           km_gr(dsum[r][c], &km, &gr);
           g_amp += (double)(T(2) * w * (amp * km));  // constant_kernel.rs:31-38 x K_matern
@@ -1519,12 +1528,16 @@ __device__ __forceinline__ void gradtrace_tile(int tile, const T* __restrict__ X
       for (int r = 0; r < 4; ++r) {
         const int gi = i0 + ty + 16 * r;
         const T ai = (gi < n) ? alpha[gi] : T(0);
+        T ui = T(0);
+        if constexpr (LOO) ui = (gi < n) ? uvec[gi] : T(0);
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
           const int gj = j0 + tx * 4 + c;
           T cf = T(0);
           if (gi < n && gj <= gi) {
-            const T w = ai * alpha[gj] - Kinv[(size_t)gi * np + gj];  // lml.rs:62 (tmp)
+            T w;
+            if constexpr (LOO) w = (ui * alpha[gj] + ai * uvec[gj]) - T(2) * Kinv[(size_t)gi * np + gj];
+            else w = ai * alpha[gj] - Kinv[(size_t)gi * np + gj];  // lml.rs:62 (tmp)
             const T wgt = (gi == gj) ? T(1) : T(2);
             T km, gr;
             km_gr(dsum[r][c], &km, &gr);
@@ -1684,6 +1697,229 @@ template void launch_gradtrace<double>(const double*, int, int, int, int, const 
                                        double*, EvalOut*, const int*, hipStream_t, int*, EvalOut*);
 template void launch_gradtrace<float>(const float*, int, int, int, int, const EvalParams*, const float*, const float*,
                                       double*, EvalOut*, const int*, hipStream_t, int*, EvalOut*);
+
+// =================================================================================================================
+// Leave-one-out cross-validation in closed form (Rasmussen & Williams 5.4.2).  With M = K^-1, m_i = M_ii:
+//   mu_i = y_i - alpha_i / m_i,  var_i = 1 / m_i,  lpd_i = 1/2 ln m_i - alpha_i^2 / (2 m_i) - 1/2 ln 2 pi,  loo = sum_i lpd_i
+//   dloo/dtheta_j = 1/2 sum_ik (u_i alpha_k + alpha_i u_k - 2 C_ik) dK_ik/dtheta_j,
+//   a_i = alpha_i / m_i,  b_i = (1 + alpha_i^2 / m_i) / (2 m_i),  u = M a,  C = Y Y^T,  Y = M diag(sqrt b)
+// Every sum is fp64 in a fixed order for both element types; no atomics on results.
+// =================================================================================================================
+// part[chunk][j] = sum_{i in chunk, j <= i < n} X[i][j]^2 of the lower-triangular X = L^-1: the column sums of squares that
+// make m_j = (X^T X)_jj from positive terms alone (the diagonal of the stored K^-1 loses digits with cond(K)).  The access pattern of
+// trmv_t_kernel (a thread owns VEC adjacent columns, wave q takes the rows i = q mod 4, eight 16-byte loads in flight per lane);
+// per column the rows of a wave in ascending order, then the four waves' sums in order.  Rows of the identity padding are left out.
+template <typename T>
+__global__ void __launch_bounds__(256) loo_colsq_kernel(const T* __restrict__ Xinv, int np, int n, double* __restrict__ part) {
+  using C = Cfg<T>;
+  using vec_t = typename C::vec_t;
+  constexpr int VEC = C::VEC, COLS = 64 * VEC;
+  __shared__ double red[4][COLS];
+  const int lane = threadIdx.x & 63, sgrp = threadIdx.x >> 6;
+  const int col0 = blockIdx.x * COLS, j0 = col0 + lane * VEC, chunk = blockIdx.y;
+  const int i_begin = chunk * 256, i_end = min(i_begin + 256, n);
+  if (i_end <= col0) return;  // the whole chunk lies above these columns' diagonal entries (uniform); never read by the finish
+  double acc[VEC];
+#pragma unroll
+  for (int e = 0; e < VEC; ++e) acc[e] = 0;
+  if (j0 < np) {
+    int i = i_begin + sgrp;
+    for (; i + 28 < i_end; i += 32) {
+      vec_t xv[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int iu = i + 4 * u;
+        xv[u] = (iu >= j0) ? *reinterpret_cast<const vec_t*>(Xinv + (size_t)iu * np + j0) : vec_t{};
+      }
+#pragma unroll
+      for (int u = 0; u < 8; ++u)
+#pragma unroll
+        for (int e = 0; e < VEC; ++e)
+          if (i + 4 * u >= j0 + e) acc[e] = __builtin_fma((double)xv[u][e], (double)xv[u][e], acc[e]);
+    }
+    for (; i < i_end; i += 4) {
+      if (i < j0) continue;
+      const vec_t xv = *reinterpret_cast<const vec_t*>(Xinv + (size_t)i * np + j0);
+#pragma unroll
+      for (int e = 0; e < VEC; ++e)
+        if (i >= j0 + e) acc[e] = __builtin_fma((double)xv[e], (double)xv[e], acc[e]);
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < VEC; ++e) red[sgrp][lane * VEC + e] = acc[e];
+  __syncthreads();
+  for (int c = threadIdx.x; c < COLS; c += 256)
+    if (col0 + c < np) part[(size_t)chunk * np + col0 + c] = red[0][c] + red[1][c] + red[2][c] + red[3][c];
+}
+
+// m_j = sum over the chunks from the column's own one on, ascending; then the row's diagnostics and the gradient's vectors
+// a, sqrt b (fp64; zero on the padding); sums[block] = the block's share of loo (256 columns per workgroup)
+template <typename T>
+__global__ void __launch_bounds__(256) loo_diag_finish_kernel(const double* __restrict__ part, int nchunks, int np, int n,
+                                                              const T* __restrict__ y, const T* __restrict__ alpha,
+                                                              T* __restrict__ mean, T* __restrict__ var, T* __restrict__ lpd,
+                                                              double* __restrict__ avec, double* __restrict__ sbvec,
+                                                              double* __restrict__ sums) {
+  __shared__ double red[4];
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  double l = 0;
+  if (j < np) {
+    double a = 0, sb = 0;
+    if (j < n) {
+      double m = 0;
+      for (int c = j / 256; c < nchunks; ++c) m += part[(size_t)c * np + j];
+      const double al = (double)alpha[j];
+      a = al / m;
+      const double q = al * a;  // alpha_j^2 / m_j
+      l = 0.5 * log(m) - 0.5 * q - 0.5 * log(2.0 * 3.14159265358979323846);
+      sb = sqrt(0.5 * (1.0 + q) / m);
+      mean[j] = (T)((double)y[j] - a);
+      var[j] = (T)(1.0 / m);
+      lpd[j] = (T)l;
+    }
+    avec[j] = a;
+    sbvec[j] = sb;
+  }
+  const double s = block_sum(l, red);
+  if (threadIdx.x == 0) sums[blockIdx.x] = s;
+}
+
+// loo = the blocks' shares in ascending order (one thread)
+__global__ void loo_sum_kernel(const double* __restrict__ sums, int nblocks, EvalOut* out) {
+  if (threadIdx.x != 0) return;
+  double s = 0;
+  for (int b = 0; b < nblocks; ++b) s += sums[b];
+  out->lml = s;
+  atomicOr(&out->done, 1);
+}
+
+// One pass over the lower triangle of K^-1 (64 x 64 tiles; only entries on or below the diagonal are read, so the slot's
+// unmirrored buffer and the model's full matrix give the same bits): the full matrix Y = K^-1 diag(sqrt b) -- the tile and its
+// mirror image, zeros on the padding -- and the tile's share of u = K^-1 a: pu[q][i], q the 64-block of the contraction index.
+// Wave 0 / 1 add the two halves of a row's 64 terms in ascending order, wave 2 / 3 those of a column (the mirror image's rows).
+template <typename T>
+__global__ void __launch_bounds__(256) loo_uy_kernel(const T* __restrict__ Kinv, int np, int n, const double* __restrict__ avec,
+                                                     const double* __restrict__ sbvec, T* __restrict__ Y, double* __restrict__ pu) {
+  __shared__ T tile[64][65];
+  __shared__ double a_i[64], a_j[64], sb_i[64], sb_j[64];
+  __shared__ double red[4][64];
+  const int li = tri_row(blockIdx.x), lj = blockIdx.x - li * (li + 1) / 2;
+  const int i0 = li * 64, j0 = lj * 64;
+  const int t = threadIdx.x, tx = t & 63, ty = t >> 6;
+  for (int r = ty; r < 64; r += 4) {
+    const int gi = i0 + r, gj = j0 + tx;
+    tile[r][tx] = (gi < n && gj <= gi) ? Kinv[(size_t)gi * np + gj] : T(0);
+  }
+  if (ty == 0) { a_i[tx] = avec[i0 + tx]; sb_i[tx] = sbvec[i0 + tx]; }
+  if (ty == 1) { a_j[tx] = avec[j0 + tx]; sb_j[tx] = sbvec[j0 + tx]; }
+  __syncthreads();
+  if (li == lj) {  // the diagonal tile: fill in its upper half (reads entries below the diagonal, writes entries above it)
+    for (int r = ty; r < 64; r += 4)
+      if (tx > r) tile[r][tx] = tile[tx][r];
+    __syncthreads();
+  }
+  for (int r = ty; r < 64; r += 4) Y[(size_t)(i0 + r) * np + j0 + tx] = (T)((double)tile[r][tx] * sb_j[tx]);
+  if (li != lj)
+    for (int r = ty; r < 64; r += 4) Y[(size_t)(j0 + r) * np + i0 + tx] = (T)((double)tile[tx][r] * sb_i[tx]);
+  const int h0 = (ty & 1) * 32;
+  double s = 0;
+  if (ty < 2) {
+    for (int c = h0; c < h0 + 32; ++c) s = __builtin_fma((double)tile[tx][c], a_j[c], s);
+  } else if (li != lj) {
+    for (int r = h0; r < h0 + 32; ++r) s = __builtin_fma((double)tile[r][tx], a_i[r], s);
+  }
+  red[ty][tx] = s;
+  __syncthreads();
+  if (t < 64) pu[(size_t)lj * np + i0 + t] = red[0][t] + red[1][t];
+  else if (t < 128 && li != lj) pu[(size_t)li * np + j0 + (t - 64)] = red[2][t - 64] + red[3][t - 64];
+}
+
+// u_i = sum_q pu[q][i], q ascending
+template <typename T>
+__global__ void __launch_bounds__(256) loo_u_finish_kernel(const double* __restrict__ pu, int nt, int np, T* __restrict__ u) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= np) return;
+  double s = 0;
+  int q = 0;
+  for (; q + 8 <= nt; q += 8) {
+    double pv[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) pv[e] = pu[(size_t)(q + e) * np + i];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) s += pv[e];
+  }
+  for (; q < nt; ++q) s += pu[(size_t)q * np + i];
+  u[i] = (T)s;
+}
+
+// the weighted trace: gradtrace_kernel's tiles with the leave-one-out weight (gradtrace_tile<.., LOO = true>); finalize_grad_kernel
+// behind it forms the gradient
+template <typename T, int NU2>
+__global__ void __launch_bounds__(256) loo_trace_kernel(const T* __restrict__ X, int n, int d, int np,
+                                                        const EvalParams* __restrict__ P, const T* __restrict__ Cm,
+                                                        const T* __restrict__ alpha, const T* __restrict__ u,
+                                                        double* __restrict__ part, const int* info) {
+  extern __shared__ __align__(16) char smem_raw[];
+  T* xi = reinterpret_cast<T*>(smem_raw);
+  T* xj = xi + (size_t)d * 64;
+  __shared__ double red[(GT_CHUNK + 2) * 256];
+  __shared__ double inv_l2[MAXD];
+  if (*info != 0) return;
+  const int t = threadIdx.x;
+  if (t < d) {
+    const T ell = (T)P->ell[t];
+    inv_l2[t] = (double)(T(1) / (ell * ell));
+  }
+  const T amp = (T)P->amp, noise = (T)P->noise;
+  gradtrace_tile<T, NU2, true>((int)blockIdx.x, X, n, d, np, amp, noise, inv_l2, Cm, alpha, part, xi, xj, red, u);
+}
+
+size_t loo_diag_part_elems(int np, int n) { return (size_t)((n + 255) / 256) * np + (size_t)((np + 255) / 256); }
+size_t loo_u_part_elems(int np) { return (size_t)(np / 64) * np; }
+
+template <typename T>
+void launch_loo_diag(const T* Xinv, int np, int n, const T* y, const T* alpha, double* part, T* mean, T* var, T* lpd, double* avec,
+                     double* sbvec, EvalOut* out, hipStream_t s) {
+  const int nchunks = (n + 255) / 256;
+  constexpr int TCOLS = 64 * Cfg<T>::VEC;
+  hipLaunchKernelGGL((loo_colsq_kernel<T>), dim3((np + TCOLS - 1) / TCOLS, nchunks), dim3(256), 0, s, Xinv, np, n, part);
+  double* sums = part + (size_t)nchunks * np;
+  const int nblocks = (np + 255) / 256;
+  hipLaunchKernelGGL((loo_diag_finish_kernel<T>), dim3(nblocks), dim3(256), 0, s, part, nchunks, np, n, y, alpha, mean, var, lpd, avec,
+                     sbvec, sums);
+  hipLaunchKernelGGL(loo_sum_kernel, dim3(1), dim3(64), 0, s, sums, nblocks, out);
+}
+template <typename T>
+void launch_loo_uy(const T* Kinv, int np, int n, const double* avec, const double* sbvec, T* Y, double* pu, T* u, hipStream_t s) {
+  const int nt = np / 64;
+  hipLaunchKernelGGL((loo_uy_kernel<T>), dim3(nt * (nt + 1) / 2), dim3(256), 0, s, Kinv, np, n, avec, sbvec, Y, pu);
+  hipLaunchKernelGGL((loo_u_finish_kernel<T>), dim3((np + 255) / 256), dim3(256), 0, s, pu, nt, np, u);
+}
+template <typename T>
+void launch_loo_trace(const T* X, int n, int d, int np, int nu2, const EvalParams* P, const T* Cm, const T* alpha, const T* u,
+                      double* part, EvalOut* out, hipStream_t s) {
+  const int nt = np / 64;
+  const int ntiles = nt * (nt + 1) / 2;
+  const size_t lds = (size_t)2 * d * 64 * sizeof(T);
+  const dim3 grid(ntiles), block(256);
+  const int* info = &out->info;
+  switch (nu2) {
+    case 0: hipLaunchKernelGGL((loo_trace_kernel<T, 0>), grid, block, lds, s, X, n, d, np, P, Cm, alpha, u, part, info); break;
+    case 1: hipLaunchKernelGGL((loo_trace_kernel<T, 1>), grid, block, lds, s, X, n, d, np, P, Cm, alpha, u, part, info); break;
+    case 3: hipLaunchKernelGGL((loo_trace_kernel<T, 3>), grid, block, lds, s, X, n, d, np, P, Cm, alpha, u, part, info); break;
+    default: hipLaunchKernelGGL((loo_trace_kernel<T, 5>), grid, block, lds, s, X, n, d, np, P, Cm, alpha, u, part, info); break;
+  }
+  hipLaunchKernelGGL(finalize_grad_kernel, dim3(d + 2), dim3(256), 0, s, part, ntiles, d + 2, out, info);
+}
+#define LOO_INST(T)                                                                                                               \
+  template void launch_loo_diag<T>(const T*, int, int, const T*, const T*, double*, T*, T*, T*, double*, double*, EvalOut*,       \
+                                   hipStream_t);                                                                                  \
+  template void launch_loo_uy<T>(const T*, int, int, const double*, const double*, T*, double*, T*, hipStream_t);                 \
+  template void launch_loo_trace<T>(const T*, int, int, int, int, const EvalParams*, const T*, const T*, const T*, double*,       \
+                                    EvalOut*, hipStream_t);
+LOO_INST(double)
+LOO_INST(float)
+#undef LOO_INST
 
 // =================================================================================================================
 // symmetrize: mirror the lower triangle into the upper one (what invc() hands back, lml.rs:62)

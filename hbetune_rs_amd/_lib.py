@@ -98,6 +98,14 @@ SIGNATURES = {
     "hbegp_maximize_qei_f32": (C.c_int, [_vp, _fp, C.c_int, C.c_int, _dp, _dp, _fp, C.c_int, C.c_double, C.c_double, C.c_int, _fp,
                                          _dp, _ip]),
     "hbegp_debug_qei_phases": (C.c_int, [C.c_int, _dp]),
+    "hbegp_problem_eval_loo": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp]),
+    "hbegp_fit_loo_f64": (C.c_int, [_vp, _dp, _dp, C.c_int, C.c_int, C.c_double, _dp, _dp, _dp, _dp, C.c_int,
+                                    C.POINTER(FitOptions), _dp, _dp, C.POINTER(_vp)]),
+    "hbegp_fit_loo_f32": (C.c_int, [_vp, _fp, _fp, C.c_int, C.c_int, C.c_double, _dp, _dp, _dp, _dp, C.c_int,
+                                    C.POINTER(FitOptions), _dp, _dp, C.POINTER(_vp)]),
+    "hbegp_model_loo_f64": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp]),
+    "hbegp_model_loo_f32": (C.c_int, [_vp, _fp, _fp, _fp, _dp, _dp]),
+    "hbegp_debug_loo_phases": (C.c_int, [C.c_int, _dp]),
     "hbegp_paths_create_f64": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_int, C.c_int, C.POINTER(_vp)]),
     "hbegp_paths_create_f32": (C.c_int, [_vp, _fp, _fp, _fp, _fp, C.c_int, C.c_int, C.POINTER(_vp)]),
     "hbegp_paths_eval_f64": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp]),

@@ -338,6 +338,17 @@ class SurrogateModelGPR:
         eps = rng.standard_normal((int(n_paths), fk.n)) if noise_draw else None
         return fk.sample_paths(omega0, phase, w, eps)
 
+    # Leave-one-out diagnostics (opt-in; nothing the estimator suggests by default uses them).
+    def loo_a(self):
+        """Leave-one-out cross-validation of the surrogate on its own observations (FittedKernel.loo): per training row the
+        prediction from all other rows, projected back like predict_mean_std_a -- (mean[n], std[n]) in y units -- and the
+        standardised residuals (y_i - mu_i) / sqrt(var_i) in the normalised space (= alpha_i sqrt(var_i)), which a well
+        specified model keeps near a standard normal.  var is the observation's: it includes the noise."""
+        m, v, _, _ = self.fitted.loo()
+        alpha, _ = self.fitted.arrays(want_kinv=False)
+        resid = alpha * np.sqrt(v)
+        return self.y_norm.project_mean_from_normalized(m, v), self.y_norm.project_std_from_normalized(m, v), resid
+
     # Batched forms of the scalar trait methods (SURVEY.md 8f rank 1: the acquisition loops call these once per generation
     # instead of m single-point predicts, each of which reads all of K^-1).
     def predict_confidence_bound_a(self, x, cb):
@@ -531,6 +542,7 @@ class EstimatorGPR:
         self._amplitude_bounds = None
         self._y_projection = "linear"
         self._known_optimum = None
+        self._objective = "lml"
         self.ctx = ctx
 
     @staticmethod
@@ -567,6 +579,14 @@ class EstimatorGPR:
         self._known_optimum = value
         return self
 
+    def objective(self, name="lml"):
+        """What `estimate` maximises over the hyper-parameters: "lml", the log marginal likelihood (the reference's and the
+        default), or "loo", the leave-one-out log pseudo-likelihood (FittedKernel.new_by_loo)."""
+        if name not in ("lml", "loo"):
+            raise ValueError(name)
+        self._objective = name
+        return self
+
     def _theta_and_bounds(self, prior, y_train):  # get_kernel_or_default gpr.rs:402-427
         if prior is not None:
             lo = np.array([prior.noise_bounds[0], prior.amplitude_bounds[0]] + [b[0] for b in prior.length_scale_bounds])
@@ -595,7 +615,8 @@ class EstimatorGPR:
         # a prior hands over its whole kernel -- theta, bounds AND the Matern nu (prior.kernel.clone(), gpr.rs:407-409);
         # the estimator's own nu only configures the default kernel
         nu = prior.fitted.nu if prior is not None else self._matern_nu
-        fitted = gpr.FittedKernel.new(x, y_train.astype(x.dtype), theta0, lo, hi, starts, nu=nu, ctx=self.ctx)
+        fit = gpr.FittedKernel.new_by_loo if self._objective == "loo" else gpr.FittedKernel.new
+        fitted = fit(x, y_train.astype(x.dtype), theta0, lo, hi, starts, nu=nu, ctx=self.ctx)
         return SurrogateModelGPR(fitted, (lo[0], hi[0]), (lo[1], hi[1]), list(zip(lo[2:], hi[2:])), y_norm, x.dtype)
 
     def extend(self, x, y, prior, rng=None):  # gpr.rs:293-337

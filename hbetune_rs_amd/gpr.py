@@ -104,6 +104,20 @@ class Problem:
             return None
         return lml.value, grad
 
+    def loo_with_gradient(self, theta, lo=None, hi=None, want_grad=True, dev=0, slot=0):
+        """The leave-one-out log pseudo-likelihood at log-space theta and its gradient (hbegp_problem_eval_loo): the slot's
+        evaluation, then the closed-form leave-one-out tail on its results.  Returns (loo, grad) or None when not PD."""
+        lib = _lib.load()
+        theta = _lib.as_c(theta, np.float64)
+        lo = None if lo is None else _lib.as_c(lo, np.float64)
+        hi = None if hi is None else _lib.as_c(hi, np.float64)
+        loo = C.c_double()
+        grad = np.zeros(self.p) if want_grad else None
+        code = lib.hbegp_problem_eval_loo(self._h, dev, slot, _lib.dptr(theta), _lib.dptr(lo), _lib.dptr(hi), C.byref(loo), _lib.dptr(grad))
+        if _lib.check(code, allow=(NOT_PD,)) == NOT_PD:
+            return None
+        return loo.value, grad
+
     def results(self, want_kinv=True, dev=0, slot=0):
         """(alpha, k_inv, diag(L)) of the most recent evaluation."""
         lib = _lib.load()
@@ -200,6 +214,16 @@ class FittedKernel:
     @staticmethod
     def new(x_train, y_train, theta0, lo, hi, starts=None, nu=2.5, ctx=None, maxeval=150, fixed_work=False, trace=False):
         """FittedKernel::new (fit.rs:18-31, 71-176): 1 + len(starts) bounded L-BFGS runs, capture the best lml."""
+        return FittedKernel._fit("hbegp_fit", x_train, y_train, theta0, lo, hi, starts, nu, ctx, maxeval, fixed_work, trace)
+
+    @staticmethod
+    def new_by_loo(x_train, y_train, theta0, lo, hi, starts=None, nu=2.5, ctx=None, maxeval=150, fixed_work=False, trace=False):
+        """`new` with the leave-one-out log pseudo-likelihood as the objective (hbegp_fit_loo_*): the same runs, options and
+        trace (trace["lml"] holds loo), capture of the best loo in `.loo_best`; the model is `extend` at the captured theta."""
+        return FittedKernel._fit("hbegp_fit_loo", x_train, y_train, theta0, lo, hi, starts, nu, ctx, maxeval, fixed_work, trace)
+
+    @staticmethod
+    def _fit(symbol, x_train, y_train, theta0, lo, hi, starts, nu, ctx, maxeval, fixed_work, trace):
         lib = _lib.load()
         ctx = ctx or default_context()
         dtype = np.dtype(x_train.dtype)
@@ -234,11 +258,14 @@ class FittedKernel:
         handle = C.c_void_p()
         theta_best = np.zeros(p)
         lml_best = C.c_double()
-        fit = getattr(lib, f"hbegp_fit_{sfx}")
+        fit = getattr(lib, f"{symbol}_{sfx}")
         _lib.check(fit(ctx._h, _lib.aptr(x), _lib.aptr(y), n, d, float(nu), _lib.dptr(theta0), _lib.dptr(lo), _lib.dptr(hi),
                        _lib.dptr(starts_c), n_restarts, C.byref(opt), _lib.dptr(theta_best), C.byref(lml_best), C.byref(handle)))
         fk = FittedKernel(handle, dtype, n, d, nu)
         fk.n_evals, fk.n_not_pd = n_evals.value, n_not_pd.value
+        fk.theta_best = theta_best
+        if symbol == "hbegp_fit_loo":
+            fk.loo_best = lml_best.value
         if trace:
             k = tr["count"].value
             fk.trace = dict(theta=tr["theta"][:k], lml=tr["lml"][:k], grad=tr["grad"][:k], run=tr["run"][:k])
@@ -280,6 +307,19 @@ class FittedKernel:
         fk = FittedKernel(handle, self.dtype, n, d, self.nu)
         fk.incremental = bool(inc.value)
         return fk
+
+    def loo(self, want_grad=False):
+        """Leave-one-out cross-validation of the model on its own training rows in closed form (hbegp_model_loo_*), in the
+        normalised y space: returns (mean[n], var[n], lpd[n], loo) and, with want_grad, d loo / d theta [p] at the model's
+        theta.  var is the predictive variance of the observation y_i: it includes the noise (predict() excludes it)."""
+        mean = np.zeros(self.n, dtype=self.dtype)
+        var = np.zeros(self.n, dtype=self.dtype)
+        lpd = np.zeros(self.n, dtype=self.dtype)
+        loo = C.c_double()
+        grad = np.zeros(self.d + 2) if want_grad else None
+        fn = getattr(_lib.load(), f"hbegp_model_loo_{self._sfx}")
+        _lib.check(fn(self._h, _lib.aptr(mean), _lib.aptr(var), _lib.aptr(lpd), C.byref(loo), _lib.dptr(grad)))
+        return (mean, var, lpd, loo.value, grad) if want_grad else (mean, var, lpd, loo.value)
 
     def predict(self, x, want_variance=True):
         """predict() (predict.rs:7-52): returns (mean, variance or None, n_warn)."""

@@ -105,6 +105,19 @@ void hbegp_problem_destroy(hbegp_problem* prob);
 int hbegp_problem_eval(hbegp_problem* prob, int dev, int slot, const double* theta, const double* lo,
                        const double* hi, double* lml, double* grad);
 
+/* The leave-one-out log pseudo-likelihood (see hbegp_model_loo_* below) at theta as an evaluation, next to hbegp_problem_eval:
+ * the slot's normal evaluation at theta (without the lml gradient), then the leave-one-out tail on its results.  theta/lo/hi and
+ * the clamping as hbegp_problem_eval; grad[p] (may be NULL: skips the n^3 product and the trace) = d loo / d theta in the order and
+ * with the clamping convention of the gradient hbegp_problem_eval returns (a clamped parameter's entry is the derivative at the
+ * clamped value).  Returns HBEGP_NOT_PD with *loo = -inf and grad = 0 where hbegp_problem_eval does.  Afterwards the slot is in
+ * the state hbegp_problem_eval at that theta leaves it in: hbegp_problem_get_* returns the same bits, and a following
+ * hbegp_problem_eval is undisturbed.  Every evaluation path (the single launch of at most 128 rows, the launch path, the task
+ * queue; f64 and f32) leaves L^-1 in the slot, so m_i is always the column sum of squares of L^-1, never the diagonal of the stored
+ * K^-1.  Two work matrices of n_p^2 elements are borrowed for a call with a gradient (HBEGP_ENOMEM as in hbegp_predict_cov_*).
+ * Slots may be evaluated from several threads at once, one thread per slot; the same call gives the same bits. */
+int hbegp_problem_eval_loo(hbegp_problem* prob, int dev, int slot, const double* theta, const double* lo, const double* hi,
+                           double* loo, double* grad);
+
 /* Copy out device results of the most recent successful evaluation on (dev, slot); any pointer may be NULL.
  * alpha[n]; kinv[n*n] full symmetric row-major (what invc() returns, lml.rs:62); ldiag[n] = diag(L). */
 int hbegp_problem_get_f64(hbegp_problem* prob, int dev, int slot, double* alpha, double* kinv, double* ldiag);
@@ -170,6 +183,22 @@ int hbegp_fit_f64(hbegp_ctx* ctx, const double* X, const double* y, int n, int d
 int hbegp_fit_f32(hbegp_ctx* ctx, const float* X, const float* y, int n, int d, double nu, const double* theta0,
                   const double* lo, const double* hi, const double* starts, int n_restarts,
                   const hbegp_fit_options* opt, double* theta_best, double* lml_best, hbegp_model** model);
+
+/* The same fit with the leave-one-out log pseudo-likelihood as the objective (Rasmussen & Williams 5.4.2: the standard alternative
+ * to maximising the marginal likelihood, more robust when the kernel family is wrong): 1 + n_restarts bounded L-BFGS runs on -loo
+ * over [ln lo, ln hi] with hbegp_problem_eval_loo's value and gradient, always driven by the host state machine
+ * (csrc/lbfgs_step.hpp; the persistent small-fit kernel is not used), one slot per run, run r on device r mod n_devices.  Same
+ * signature, options and trace as hbegp_fit_*: maxeval, fixed_work and lbfgs_memory are honoured, trace_lml records loo and
+ * trace_grad its gradient.  Capture rule = arg-max loo over every evaluation of every run, ties to the lowest (run, eval).
+ * theta_best as in hbegp_fit_*; *loo_best = the best loo.  *model is what hbegp_extend_*(X, y, theta_best, lo = hi = NULL) returns, bit
+ * for bit (it is built through that path; hbegp_model_info's lml is the log marginal likelihood there).  Deterministic: the same
+ * call gives the same theta and the same model bits. */
+int hbegp_fit_loo_f64(hbegp_ctx* ctx, const double* X, const double* y, int n, int d, double nu, const double* theta0,
+                      const double* lo, const double* hi, const double* starts, int n_restarts,
+                      const hbegp_fit_options* opt, double* theta_best, double* loo_best, hbegp_model** model);
+int hbegp_fit_loo_f32(hbegp_ctx* ctx, const float* X, const float* y, int n, int d, double nu, const double* theta0,
+                      const double* lo, const double* hi, const double* starts, int n_restarts,
+                      const hbegp_fit_options* opt, double* theta_best, double* loo_best, hbegp_model** model);
 
 /* One evaluation at fixed theta + K^-1 (fit.rs:33-68).  HBEGP_NOT_PD where the reference panics (fit.rs:55).  For f64 the result is
  * bit for bit what an evaluation of the same theta inside hbegp_fit_f64 produces (one order of operations for one theta). */
@@ -314,6 +343,26 @@ int hbegp_maximize_qei_f64(hbegp_model* model, const double* starts, int R, int 
 int hbegp_maximize_qei_f32(hbegp_model* model, const float* starts, int R, int q, const double* lo, const double* hi, const float* z,
                            int S, double fmin_normalized, double jitter, int maxeval, float* x_out, double* qei_out, int* nevals_out);
 
+/* Leave-one-out cross-validation of the model on its own training data, in closed form (Rasmussen & Williams 5.4.2), in the
+ * model's normalised y space.  With K = c Matern(X, X) + s2 I, M = K^-1, m_i = M_ii:
+ *   mean[i] = y_i - alpha_i / m_i    the prediction of y_i from the other n - 1 rows at the model's theta
+ *   var[i]  = 1 / m_i                the predictive variance of the OBSERVATION y_i: it includes the noise s2 (the latent
+ *                                    function's is var[i] - s2).  hbegp_predict_* predicts the latent function (c + 1e-5 - ..):
+ *                                    deleting row i, extending at the same theta and predicting at x_i gives mean[i] and
+ *                                    var[i] - s2 + 1e-5
+ *   lpd[i]  = 1/2 ln m_i - alpha_i^2 / (2 m_i) - 1/2 ln 2 pi     the log predictive density of y_i;    *loo = sum_i lpd[i]
+ * m_i is the column sum of squares of L^-1, sum_{a >= i} (L^-1)_ai^2 -- positive terms only, summed in fp64 in a fixed order for
+ * both element types; the diagonal of the stored K^-1 loses digits in proportion to cond(K) (DESIGN.md sections 10, 15).
+ * grad[p]: d loo / d theta at the model's theta, order [ln s2, ln c, ln ell_k], as hbegp_problem_eval_loo returns it
+ * (R&W eq. 5.13 reduced to one symmetric n^3 product for all p parameters: DESIGN.md section 15).
+ * mean, var, lpd [n] have the model's element type; loo and grad are fp64.  Every output may be NULL, but not all of them.
+ * Two work matrices of n_p^2 elements (n_p = n rounded up to 128) are borrowed from the block pool only when grad is asked for;
+ * work that does not fit in device memory is HBEGP_ENOMEM.  HBEGP_EINVAL (before any device call) when every output is NULL, for a
+ * NULL model or a model of the other element type.  A value that is not finite (NaN data) is HBEGP_NOT_PD with *loo = -inf and
+ * grad = 0.  Serialised per model like predict: threads may call it on one model at once; the same call gives the same bits. */
+int hbegp_model_loo_f64(hbegp_model* model, double* mean, double* var, double* lpd, double* loo, double* grad);
+int hbegp_model_loo_f32(hbegp_model* model, float* mean, float* var, float* lpd, double* loo, double* grad);
+
 int hbegp_model_info(const hbegp_model* model, int* n, int* d, int* is_f32, double* nu, double* lml);
 /* theta[p] (log space, clamped), alpha[n], kinv[n*n] full symmetric; any pointer may be NULL. */
 int hbegp_model_get_f64(hbegp_model* model, double* theta, double* alpha, double* kinv);
@@ -374,6 +423,11 @@ int hbegp_debug_batch_select_phases(int enable, double* phase_ms);
  * last timed hbegp_qei_* call -- the shared launches (upload of the points, Kstar, mean, Q; with a gradient dmean, G, W; upload of
  * z), the qEI kernel -- in milliseconds; then enable != 0 makes this thread's later qEI calls timed. */
 int hbegp_debug_qei_phases(int enable, double* phase_ms);
+
+/* ---- timing hook (tools/loo_bench.py): phase_ms[4] (may be NULL) receives the device time of the phases of the calling thread's
+ * last timed leave-one-out call with a gradient (hbegp_model_loo_*, hbegp_problem_eval_loo) -- the diagonal pass, u and Y, the
+ * SYRK C = Y Y^T, the weighted trace -- in milliseconds; then enable != 0 makes this thread's later calls timed. */
+int hbegp_debug_loo_phases(int enable, double* phase_ms);
 
 /* ---- posterior sample paths: draws of the posterior that are FUNCTIONS (pathwise conditioning, Matheron's rule, on a
  * random-Fourier-feature prior draw).  In the model's normalised y space,
