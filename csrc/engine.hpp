@@ -232,6 +232,19 @@ void launch_sample_epilogue(T* Y, int ld, const T* mean, int m, int S, int store
 template <typename T>
 void launch_batch_select(const T* Sig, int ld, const T* mean, int m, int k, const EvalParams* P, double fmin, int use_lie, double lie,
                          double* C, double* v, double* mu, int* picked, int* idx, double* ei, T* mean_out, T* var_out, hipStream_t s);
+// knowledge gradient over a candidate set (hbegp_knowledge_gradient; kg_kernel: one workgroup per candidate): Sig the symmetrised
+// Sigma [ld][ld] at jitter 0, mean[m], P->noise the sample's noise s2.  Out: kg[mc] (fp64), res[2] = {the last index of the maximum
+// of kg (-1 for mc = 0), the lowest index of the minimum of the mean}, var_out[m] = max(diag Sigma, 0).  0 <= mc <= m, m >= 1.
+// The (b, a) lines of a candidate, padded to kg_padded_rows(m) (a power of two), live in the LDS up to KG_LDS_ROWS of them; beyond,
+// in ws: kg_global_workgroups(m, mc) * kg_padded_rows(m) lines of 16 bytes (ws is unused, and may be null, where that is 0).
+constexpr int KG_LDS_ROWS = 8192;
+constexpr int KG_GLOBAL_WGS = 512;
+constexpr size_t kg_lds_bytes(int rows) { return 16 * (size_t)rows + 8 * 256 + 16; }  // the lines, the sum's tree, the stack height
+int kg_padded_rows(int m);
+int kg_global_workgroups(int m, int mc);
+template <typename T>
+void launch_knowledge_gradient(const T* Sig, int ld, const T* mean, int m, int mc, const EvalParams* P, void* ws, double* kg, int* res,
+                               T* var_out, hipStream_t s);
 // batch expected improvement by Monte Carlo (hbegp_qei; qei_batch_kernel: one workgroup per batch of q points).  Rows b q .. b q + q - 1
 // of Xs [B q][d], Q [mp][np], mean, dmean [mp][d] and W [d][mp][np] (W and dmean are read only with want_grad); z [S][q] shared by
 // the batches; noise = 1e-5 + jitter.  Out: qei[B], grad[B q][d] (want_grad), info[B] (0, or 1 + the column whose pivot failed).

@@ -2132,6 +2132,64 @@ static int model_select_batch(hbegp_model* m, const T* Xs, int cnt, int k, doubl
   return HBEGP_OK;
 }
 
+// phase times of the calling thread's last knowledge-gradient call (hbegp_debug_kg_phases): Sigma, kg in ms
+static thread_local bool t_time_kg = false;
+static thread_local double t_kg_ms[2] = {0, 0};
+
+// Knowledge gradient over a candidate set (hbegp_knowledge_gradient): Sigma at jitter 0 as predict_cov builds it (posterior_sigma,
+// then mirrored), then kg_kernel with one workgroup per candidate and the epilogue (best, imin, the clamped diagonal).  Only the mc
+// values, two ints and the optional mean / variance leave the device; Sigma and the workspace are borrowed for the call and go back
+// cleared.  Beyond KG_LDS_ROWS padded rows the lines live in a global workspace of kg_global_workgroups(m, mc) workgroups.
+template <typename T>
+static int model_knowledge_gradient(hbegp_model* m, const T* Xs, int cnt, int mc, double* kg, int* best, int* imin, T* mean_out,
+                                    T* var_out) {
+  std::lock_guard<std::mutex> lock(m->mu);
+  HIPCHECK(hipSetDevice(m->dev));
+  const int mp = round_up(cnt, NB);
+  const size_t ws_lines = (size_t)kg_global_workgroups(cnt, mc) * (size_t)kg_padded_rows(cnt);
+  // everything the call borrows, counted before anything is taken: an m far beyond the device is ENOMEM, not an overflow
+  const double need = (double)sizeof(T) * ((double)mp * mp + 2.0 * (double)mp * m->np + 2.0 * mp) + 8.0 * mc + 16.0 * (double)ws_lines;
+  if (need > 1e15) return fail(HBEGP_ENOMEM, "the knowledge gradient over %d points needs %.3g bytes of device memory", cnt, need);
+  predict_batched_reserve<T>(m, mp);
+  if (!m->dPcov) m->dPcov = static_cast<EvalParams*>(m->palloc(sizeof(EvalParams)));
+  hipStream_t s = m->stream;
+  const double noise = 1e-5;  // jitter 0: predict_cov's Sigma, whose diagonal is hbegp_predict's variance before clamping
+  CallScratch ws{m->dev, s, {}};
+  T* W1 = static_cast<T*>(ws.get(sizeof(T) * (size_t)mp * mp));
+  double* dkg = static_cast<double*>(ws.get(sizeof(double) * (size_t)std::max(mc, 1)));
+  int* dres = static_cast<int*>(ws.get(sizeof(int) * 2));
+  T* dvar = static_cast<T*>(ws.get(sizeof(T) * (size_t)mp));
+  void* lines = ws_lines ? ws.get(16 * ws_lines) : nullptr;
+  hipEvent_t ev[3] = {};
+  const bool timed = t_time_kg;
+  if (timed)
+    for (auto& e : ev) HIPCHECK(hipEventCreate(&e));
+  if (timed) HIPCHECK(hipEventRecord(ev[0], s));
+  posterior_sigma<T>(m, Xs, cnt, mp, &noise, W1, nullptr);
+  launch_symmetrize<T>(W1, mp, s);  // the kernel reads row j of Sigma
+  if (timed) HIPCHECK(hipEventRecord(ev[1], s));
+  launch_knowledge_gradient<T>(W1, mp, static_cast<const T*>(m->mean), cnt, mc, m->dP, lines, dkg, dres, dvar, s);
+  if (timed) HIPCHECK(hipEventRecord(ev[2], s));
+  CHECK_LAUNCHES();
+  int res[2] = {-1, -1};
+  if (mc > 0) HIPCHECK(hipMemcpyAsync(kg, dkg, sizeof(double) * (size_t)mc, hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipMemcpyAsync(res, dres, sizeof(res), hipMemcpyDeviceToHost, s));
+  if (mean_out) HIPCHECK(hipMemcpyAsync(mean_out, m->mean, sizeof(T) * cnt, hipMemcpyDeviceToHost, s));
+  if (var_out) HIPCHECK(hipMemcpyAsync(var_out, dvar, sizeof(T) * cnt, hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
+  if (best) *best = res[0];
+  if (imin) *imin = res[1];
+  if (timed) {
+    for (int i = 0; i < 2; ++i) {
+      float ms = 0;
+      HIPCHECK(hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
+      t_kg_ms[i] = ms;
+    }
+    for (auto& e : ev) (void)hipEventDestroy(e);
+  }
+  return HBEGP_OK;
+}
+
 // Expected improvement of acquisition.rs:141-171 (estimator.expected_improvement) at mean mu and variance var, and its gradient
 // from the posterior gradients: dEI = -Phi(z) dmu + phi(z) dsigma, dsigma = dvar / (2 sigma); sigma = 0: -dmu where mu < fmin.
 static double ei_with_gradient(double mu, double var, const double* dmu, const double* dvar, double fmin, int d, double* g) {
@@ -3861,6 +3919,44 @@ int hbegp_debug_batch_select_phases(int enable, double* phase_ms) {
   if (phase_ms)
     for (int i = 0; i < 2; ++i) phase_ms[i] = t_select_ms[i];
   t_time_select = enable != 0;
+  return HBEGP_OK;
+}
+}  // extern "C"
+
+// argument checks of hbegp_knowledge_gradient_*: everything is refused before any device call, the checks that need no model first
+template <typename T>
+static int check_kg(hbegp_model* model, const T* Xs, int m, int mc, const double* kg) {
+  if (m < 0) return fail(HBEGP_EINVAL, "m must be >= 0 (got %d)", m);
+  if (mc < 0) return fail(HBEGP_EINVAL, "mc must be >= 0 (got %d)", mc);
+  if (mc > m) return fail(HBEGP_EINVAL, "mc must be <= m (got mc = %d, m = %d)", mc, m);
+  if (mc > 0 && !kg) return fail(HBEGP_EINVAL, "kg is NULL");
+  return check_posterior<T>(model, Xs, m, 0.0);
+}
+extern "C" {
+int hbegp_knowledge_gradient_f64(hbegp_model* model, const double* Xs, int m, int mc, double* kg, int* best, int* imin, double* mean_out,
+                                 double* var_out) {
+  if (int rc = check_kg<double>(model, Xs, m, mc, kg)) return rc;
+  if (best) *best = -1;
+  if (imin) *imin = -1;
+  if (m == 0) return HBEGP_OK;
+  GUARD_BEGIN
+  return model_knowledge_gradient<double>(model, Xs, m, mc, kg, best, imin, mean_out, var_out);
+  GUARD_END
+}
+int hbegp_knowledge_gradient_f32(hbegp_model* model, const float* Xs, int m, int mc, double* kg, int* best, int* imin, float* mean_out,
+                                 float* var_out) {
+  if (int rc = check_kg<float>(model, Xs, m, mc, kg)) return rc;
+  if (best) *best = -1;
+  if (imin) *imin = -1;
+  if (m == 0) return HBEGP_OK;
+  GUARD_BEGIN
+  return model_knowledge_gradient<float>(model, Xs, m, mc, kg, best, imin, mean_out, var_out);
+  GUARD_END
+}
+int hbegp_debug_kg_phases(int enable, double* phase_ms) {
+  if (phase_ms)
+    for (int i = 0; i < 2; ++i) phase_ms[i] = t_kg_ms[i];
+  t_time_kg = enable != 0;
   return HBEGP_OK;
 }
 int hbegp_debug_posterior_phases(int enable, double* phase_ms) {

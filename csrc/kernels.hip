@@ -2412,6 +2412,223 @@ template void launch_batch_select<float>(const float*, int, const float*, int, i
                                          double*, double*, int*, int*, double*, float*, float*, hipStream_t);
 
 // =================================================================================================================
+// knowledge gradient over a candidate set (hbegp.cpp: model_knowledge_gradient).  One workgroup per candidate
+// j < mc, all arithmetic in fp64 for both element types:
+//   lines   row j of the symmetrised Sigma (read contiguously in T) and the mean: r_i = Sigma_ji, r_j = Sigma_jj - 1e-5,
+//           sd = sqrt(max(r_j, 0) + s2); line i = (b_i, a_i) = (-(r_i / sd), -mu_i), padded with (+inf, +inf) to P, the power of two
+//           at or above m
+//   sort    bitonic network over the P lines by (b, a) ascending: KG_THREADS threads, one barrier per stage
+//   scan    ONE lane walks the sorted lines (Frazier, Powell, Dayanik 2009, Algorithm 1): of a run of equal slopes only the last
+//           (the largest a) is kept; a kept line pops the top of the stack while its breakpoint with the top,
+//           c = (a_top - a) / (b - b_top), is <= the breakpoint at which the top begins.  The stack is written over the head of the
+//           sorted array (its height never exceeds the lines consumed), and the breakpoints are not stored but recomputed from
+//           adjacent stack lines -- the same quotient of the same operands, so the same bits -- which keeps a line at 16 bytes
+//   sum     KG_j = sum_k (b_{k+1} - b_k) f(-|c_k|) over adjacent stack lines, f(z) = phi(z) + z Phi(z): thread t adds the terms
+//           k = t (mod KG_THREADS) in ascending k, then a fixed LDS tree.  A single surviving line gives exactly 0.
+// kg_kernel keeps the lines in dynamic LDS (16 P + 2064 bytes: 130 KiB at P = KG_LDS_ROWS = 8192); kg_global_kernel, for larger
+// m, keeps them in a global workspace of P lines per workgroup and strides its workgroups over the candidates.  A line another
+// thread wrote is read only behind a __syncthreads (workgroup-scope fence: one CU, one L1).  No atomics; KG_j depends on nothing
+// but row j, the mean and s2, so it is the same for any mc and any grid.
+// =================================================================================================================
+constexpr int KG_THREADS = 256;
+static_assert(kg_lds_bytes(0) == 8 * KG_THREADS + 16, "kg_lds_bytes counts KG_THREADS doubles for the sum's tree");
+
+// not inlined: erfc's fp64 coefficients (as bsel_ei).  ac = |c| >= 0; beyond 38 both terms are below 1e-314 (and an infinite
+// breakpoint would give inf * 0)
+__device__ __noinline__ double kg_tail(double ac) {
+  if (!(ac < 38.0)) return 0.0;
+  const double cdf = 0.5 * erfc(ac / 1.4142135623730951);
+  const double pdf = exp(-0.5 * ac * ac) / 2.5066282746310002;
+  return fmax(pdf - ac * cdf, 0.0);
+}
+
+__device__ __forceinline__ bool kg_less(const double2 x, const double2 y) { return x.x < y.x || (x.x == y.x && x.y < y.y); }
+
+// KG of candidate j by the whole workgroup (every thread returns it).  ln: P lines (LDS or global), red: KG_THREADS doubles and
+// cnt: one int in the LDS.  The caller puts a barrier between two calls.
+template <typename T>
+__device__ __forceinline__ double kg_candidate(const T* __restrict__ Sig, int ld, const T* __restrict__ mean, int m, int P, double s2,
+                                               int j, double2* ln, double* red, int* cnt) {
+  const int tid = threadIdx.x;
+  const T* __restrict__ row = Sig + (size_t)j * ld;
+  const double rj = (double)row[j] - 1e-5;  // the latent variance: the sample's own noise is s2
+  const double sd = sqrt(fmax(rj, 0.0) + s2);
+  for (int i = tid; i < P; i += KG_THREADS) {
+    double2 e = make_double2(INFINITY, INFINITY);
+    if (i < m) {
+      const double r = i == j ? rj : (double)row[i];
+      e.x = -(r / sd);
+      e.y = -(double)mean[i];
+    }
+    ln[i] = e;
+  }
+  __syncthreads();
+  for (int k = 2; k <= P; k <<= 1) {
+#pragma unroll 1
+    for (int w = k >> 1; w > 0; w >>= 1) {
+      for (int p = tid; p < (P >> 1); p += KG_THREADS) {
+        const int lo = ((p & ~(w - 1)) << 1) | (p & (w - 1));
+        const int hi = lo | w;
+        const double2 x = ln[lo], y = ln[hi];
+        if ((lo & k) == 0 ? kg_less(y, x) : kg_less(x, y)) { ln[lo] = y; ln[hi] = x; }
+      }
+      __syncthreads();
+    }
+  }
+  if (tid == 0) {
+#ifdef KG_NO_SCAN  // diagnostics (make variant DEFS=-DKG_NO_SCAN): the time of everything but the scan; kg comes out 0
+    *cnt = 0;
+  }
+  if (tid == 0 && m < 0) {
+#endif
+    int t = 0;                // the stack is ln[0 .. t)
+    double2 top = ln[0];      // its top, and the breakpoint at which the top begins
+    double ctop = -INFINITY;
+    double2 nx = top;
+    for (int i = 0; i < m; ++i) {
+      const double2 e = nx;
+      if (i + 1 < m) {
+        nx = ln[i + 1];
+        if (nx.x == e.x) continue;  // equal slopes: sorted by a within the run, the last one dominates
+      }
+      double c = -INFINITY;
+      while (t > 0) {
+        c = (top.y - e.y) / (e.x - top.x);
+        if (t == 1 || c > ctop) break;
+        --t;
+        top = ln[t - 1];
+        if (t >= 2) {
+          const double2 u = ln[t - 2];
+          ctop = (u.y - top.y) / (top.x - u.x);
+        }
+      }
+      ln[t++] = e;
+      top = e;
+      ctop = c;
+    }
+    *cnt = t;
+  }
+  __syncthreads();
+  const int t = *cnt;
+  double acc = 0.0;
+  for (int k = tid; k + 1 < t; k += KG_THREADS) {
+    const double2 x = ln[k], y = ln[k + 1];
+    const double c = (x.y - y.y) / (y.x - x.x);
+    acc += (y.x - x.x) * kg_tail(fabs(c));
+  }
+  red[tid] = acc;
+  __syncthreads();
+#pragma unroll 1
+  for (int w = KG_THREADS / 2; w > 0; w >>= 1) {
+    if (tid < w) red[tid] += red[tid + w];
+    __syncthreads();
+  }
+  return red[0];
+}
+
+template <typename T>
+__global__ void __launch_bounds__(KG_THREADS) kg_kernel(const T* __restrict__ Sig, int ld, const T* __restrict__ mean, int m, int P,
+                                                        const EvalParams* __restrict__ Pm, double* __restrict__ kg) {
+  extern __shared__ __align__(16) char smem_raw[];
+  double2* ln = reinterpret_cast<double2*>(smem_raw);
+  double* red = reinterpret_cast<double*>(ln + P);
+  int* cnt = reinterpret_cast<int*>(red + KG_THREADS);
+  const double v = kg_candidate<T>(Sig, ld, mean, m, P, Pm->noise, blockIdx.x, ln, red, cnt);
+  if (threadIdx.x == 0) kg[blockIdx.x] = v;
+}
+
+template <typename T>
+__global__ void __launch_bounds__(KG_THREADS) kg_global_kernel(const T* __restrict__ Sig, int ld, const T* __restrict__ mean, int m,
+                                                               int P, int mc, const EvalParams* __restrict__ Pm, double2* ws,
+                                                               double* __restrict__ kg) {
+  __shared__ double red[KG_THREADS];
+  __shared__ int cnt;
+  double2* ln = ws + (size_t)blockIdx.x * P;
+  const double s2 = Pm->noise;
+  for (int j = blockIdx.x; j < mc; j += gridDim.x) {
+    const double v = kg_candidate<T>(Sig, ld, mean, m, P, s2, j, ln, red, &cnt);
+    if (threadIdx.x == 0) kg[j] = v;
+    __syncthreads();  // red and the lines are rewritten by the next candidate
+  }
+}
+
+// best = the LAST index of the maximum of kg[0 .. mc) (Rust's max_by; -1 for mc = 0), imin = the lowest index of the minimum of
+// the mean over all m rows, both through a fixed LDS tree; var_out = max(diag Sigma, 0)
+template <typename T>
+__global__ void __launch_bounds__(BSEL_THREADS) kg_epilogue_kernel(const T* __restrict__ Sig, int ld, const T* __restrict__ mean, int m,
+                                                                   const double* __restrict__ kg, int mc, int* __restrict__ res,
+                                                                   T* __restrict__ var_out) {
+  __shared__ double sv[BSEL_THREADS];
+  __shared__ int si[BSEL_THREADS];
+  const int tid = threadIdx.x;
+  for (int i = tid; i < m; i += BSEL_THREADS) var_out[i] = (T)fmax((double)Sig[(size_t)i * ld + i], 0.0);
+  double best = 0.0;
+  int bi = -1;
+  for (int i = tid; i < mc; i += BSEL_THREADS) {
+    const double e = kg[i];
+    if (bi < 0 || e >= best) { best = e; bi = i; }  // ascending i: an equal value moves to the later index
+  }
+  sv[tid] = best;
+  si[tid] = bi;
+  __syncthreads();
+#pragma unroll 1
+  for (int w = BSEL_THREADS / 2; w > 0; w >>= 1) {
+    if (tid < w) {
+      const double o = sv[tid + w];
+      const int oi = si[tid + w];
+      if (oi >= 0 && (si[tid] < 0 || o > sv[tid] || (o == sv[tid] && oi > si[tid]))) { sv[tid] = o; si[tid] = oi; }
+    }
+    __syncthreads();
+  }
+  if (tid == 0) res[0] = si[0];
+  __syncthreads();
+  best = 0.0;
+  bi = -1;
+  for (int i = tid; i < m; i += BSEL_THREADS) {
+    const double e = (double)mean[i];
+    if (bi < 0 || e < best) { best = e; bi = i; }  // ascending i: an equal value stays at the earlier index
+  }
+  sv[tid] = best;
+  si[tid] = bi;
+  __syncthreads();
+#pragma unroll 1
+  for (int w = BSEL_THREADS / 2; w > 0; w >>= 1) {
+    if (tid < w) {
+      const double o = sv[tid + w];
+      const int oi = si[tid + w];
+      if (oi >= 0 && (si[tid] < 0 || o < sv[tid] || (o == sv[tid] && oi < si[tid]))) { sv[tid] = o; si[tid] = oi; }
+    }
+    __syncthreads();
+  }
+  if (tid == 0) res[1] = si[0];
+}
+
+int kg_padded_rows(int m) {
+  int P = 1;
+  while (P < m) P <<= 1;
+  return P;
+}
+int kg_global_workgroups(int m, int mc) { return kg_padded_rows(m) <= KG_LDS_ROWS ? 0 : (mc < KG_GLOBAL_WGS ? mc : KG_GLOBAL_WGS); }
+
+template <typename T>
+void launch_knowledge_gradient(const T* Sig, int ld, const T* mean, int m, int mc, const EvalParams* P, void* ws, double* kg, int* res,
+                               T* var_out, hipStream_t s) {
+  const int Pr = kg_padded_rows(m);
+  if (mc > 0) {
+    if (Pr <= KG_LDS_ROWS)
+      hipLaunchKernelGGL((kg_kernel<T>), dim3(mc), dim3(KG_THREADS), kg_lds_bytes(Pr), s, Sig, ld, mean, m, Pr, P, kg);
+    else
+      hipLaunchKernelGGL((kg_global_kernel<T>), dim3(kg_global_workgroups(m, mc)), dim3(KG_THREADS), 0, s, Sig, ld, mean, m, Pr, mc, P,
+                         static_cast<double2*>(ws), kg);
+  }
+  hipLaunchKernelGGL((kg_epilogue_kernel<T>), dim3(1), dim3(BSEL_THREADS), 0, s, Sig, ld, mean, m, kg, mc, res, var_out);
+}
+template void launch_knowledge_gradient<double>(const double*, int, const double*, int, int, const EvalParams*, void*, double*, int*, double*,
+                                                hipStream_t);
+template void launch_knowledge_gradient<float>(const float*, int, const float*, int, int, const EvalParams*, void*, double*, int*, float*,
+                                               hipStream_t);
+
+// =================================================================================================================
 // batch expected improvement by Monte Carlo (hbegp.cpp: model_qei).  One workgroup per batch b of q points
 // (rows b q .. b q + q - 1 of the batched predict's Q [mp][np], mean, dmean [mp][d] and W [d][mp][np]):
 //   Sigma = K** + noise I - Q_b Q_b^T   (fp64: K** from the points, q (q+1) / 2 wave dots over np, ascending lane stride)
@@ -3853,6 +4070,8 @@ void init_kernels() {
   set_lds_attr(reinterpret_cast<const void*>(&leaf_keep_kernel<double, float>), (int)LeafGeom<double>::LDS_BYTES, "leaf_keep_kernel<f32>: dynamic LDS limit");
   set_lds_attr(reinterpret_cast<const void*>(&qei_batch_kernel<double>), (int)qei_lds_bytes(QEI_MAXQ, MAXD), "qei_batch_kernel<f64>: dynamic LDS limit");
   set_lds_attr(reinterpret_cast<const void*>(&qei_batch_kernel<float>), (int)qei_lds_bytes(QEI_MAXQ, MAXD), "qei_batch_kernel<f32>: dynamic LDS limit");
+  set_lds_attr(reinterpret_cast<const void*>(&kg_kernel<double>), (int)kg_lds_bytes(KG_LDS_ROWS), "kg_kernel<f64>: dynamic LDS limit");
+  set_lds_attr(reinterpret_cast<const void*>(&kg_kernel<float>), (int)kg_lds_bytes(KG_LDS_ROWS), "kg_kernel<f32>: dynamic LDS limit");
   init_dag_kernels();
   const int lb = 163840;
   // kmat / gradtrace: 2 d 64 elements of dynamic LDS (64 KiB at d = 64 in f64) beside ~21 KiB of static LDS

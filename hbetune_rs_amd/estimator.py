@@ -308,6 +308,23 @@ class SurrogateModelGPR:
         means, _, _ = self.fitted.predict(x[idx], want_variance=False) if len(idx) else (np.zeros(0, self.dtype), None, 0)
         return idx, self.y_norm.project_location_from_normalized(means), ei
 
+    # Knowledge gradient over a candidate set (opt-in; nothing the estimator suggests by default uses it).
+    def knowledge_gradient_a(self, x, n_candidates=None):
+        """Knowledge gradient of one more noisy observation at each of the first n_candidates rows of x [m, d] (all by default),
+        the minimum of the posterior mean taken over all m rows (FittedKernel.knowledge_gradient).  It needs no fmin.  KG is
+        returned in the NORMALISED y space, as predict_mean_ei_a returns EI: no projection is applied (the y projection is
+        monotone increasing, so the ranking of rows by mean is the projected one's, but a difference of means is not a
+        difference in y units under the logarithmic projection).  Returns (kg[n_candidates] float64, best): best the last index of
+        the maximum of kg, -1 without candidates."""
+        kg, best, _ = self.fitted.knowledge_gradient(np.asarray(x, dtype=self.dtype), n_candidates=n_candidates)
+        return kg, best
+
+    def best_by_mean_a(self, x):
+        """The row of x [m, d] with the lowest posterior mean (ties to the lowest index) and that mean projected like
+        predict_mean_a: what a tuner of a noisy objective should report instead of its best observation."""
+        _, _, imin, mean, _ = self.fitted.knowledge_gradient(np.asarray(x, dtype=self.dtype), n_candidates=0, want_posterior=True)
+        return imin, self.y_norm.project_location_from_normalized(mean[imin:imin + 1])[0]
+
     # Batch expected improvement by Monte Carlo (opt-in; nothing the estimator suggests by default uses it).
     def qei_a(self, x, fmin, n_samples, rng, jitter=0.0, want_grad=True):
         """q-EI of batches x [B, q, d] (or [q, d]) in the normalised space (FittedKernel.qei), fmin projected as predict_mean_ei_a
@@ -448,6 +465,54 @@ def acquire_by_batch_ei(candidates, model, k, fmin, lie=None):
     if c.ndim != 2:
         raise ValueError("candidates must be [m, n_features]")
     return model.select_batch_a(c, int(k), fmin, lie=lie)
+
+
+def acquire_by_knowledge_gradient(candidates, model, k, n_candidates=None, ctx=None):
+    """Batch acquisition for a noisy objective by the knowledge gradient over a candidate set [m, n_features]: k distinct rows among
+    the first n_candidates (all by default), each the row where one more noisy observation is expected to lower the minimum of the
+    posterior mean over all m rows the most (FittedKernel.knowledge_gradient: closed form, no fmin, no random numbers).  After a
+    pick the surrogate is conditioned on the kriging-believer fantasy (x_pick, its posterior mean) through extend_with at the same
+    theta, and rows already picked leave the places to sample but stay in the minimum.  A composition of existing calls: k
+    knowledge-gradient calls and k - 1 extends; k = 1 is knowledge_gradient_a's best.  Returns (idx[k] int64, the projected means
+    of the picks at the time they were picked, kg[k] in the normalised space).  Opt-in: nothing the estimator suggests by default
+    calls it."""
+    c = np.asarray(candidates, dtype=model.dtype)
+    if c.ndim != 2:
+        raise ValueError("candidates must be [m, n_features]")
+    m = c.shape[0]
+    mc = m if n_candidates is None else int(n_candidates)
+    k = int(k)
+    if not 0 <= mc <= m:
+        raise ValueError("n_candidates must lie in [0, number of rows]")
+    if not 0 <= k <= mc:
+        raise ValueError("k must lie in [0, n_candidates]")
+    fk = model.fitted
+    X, y = fk.x_train, fk.y_train
+    if k > 1 and (X is None or y is None):
+        raise ValueError("the model does not hold its training rows: it cannot be conditioned on a fantasy")
+    avail = list(range(mc))
+    rest = list(range(mc, m))
+    idx, means, kgs = [], [], []
+    try:
+        for t in range(k):
+            order = avail + idx + rest  # the places to sample first; every row takes part in the minimum
+            kg, best, _, mean, _ = fk.knowledge_gradient(c[order], n_candidates=len(avail), want_posterior=True)
+            j = avail.pop(best)
+            idx.append(j)
+            means.append(mean[best])
+            kgs.append(kg[best])
+            if t + 1 < k:
+                X = np.vstack([X, c[j:j + 1]])
+                y = np.concatenate([y, mean[best:best + 1]])
+                nxt = fk.extend_with(X, y, ctx=ctx)
+                if fk is not model.fitted:
+                    fk.release()
+                fk = nxt
+    finally:
+        if fk is not model.fitted:
+            fk.release()
+    means = np.array(means, dtype=model.dtype)
+    return np.array(idx, dtype=np.int64), model.y_norm.project_location_from_normalized(means), np.array(kgs, dtype=np.float64)
 
 
 def acquire_by_qei(candidates, model, q, fmin, rng, n_samples=512, n_restarts=8, maxeval=150, jitter=0.0):

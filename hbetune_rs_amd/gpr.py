@@ -175,6 +175,7 @@ class FittedKernel:
         self._h = handle
         self.dtype = np.dtype(dtype)
         self.n, self.d, self.nu = n, d, nu
+        self.x_train = self.y_train = None  # the host copies of the training rows (normalised y), set by new / extend / extend_with
         self._sfx = _suffix(dtype)
         lml = C.c_double()
         _lib.check(_lib.load().hbegp_model_info(self._h, None, None, None, None, C.byref(lml)))
@@ -262,6 +263,7 @@ class FittedKernel:
         _lib.check(fit(ctx._h, _lib.aptr(x), _lib.aptr(y), n, d, float(nu), _lib.dptr(theta0), _lib.dptr(lo), _lib.dptr(hi),
                        _lib.dptr(starts_c), n_restarts, C.byref(opt), _lib.dptr(theta_best), C.byref(lml_best), C.byref(handle)))
         fk = FittedKernel(handle, dtype, n, d, nu)
+        fk.x_train, fk.y_train = x, y
         fk.n_evals, fk.n_not_pd = n_evals.value, n_not_pd.value
         fk.theta_best = theta_best
         if symbol == "hbegp_fit_loo":
@@ -288,7 +290,9 @@ class FittedKernel:
         ext = getattr(lib, f"hbegp_extend_{sfx}")
         _lib.check(ext(ctx._h, _lib.aptr(x), _lib.aptr(y), n, d, float(nu), _lib.dptr(theta), _lib.dptr(lo), _lib.dptr(hi),
                        C.byref(handle)))
-        return FittedKernel(handle, dtype, n, d, nu)
+        fk = FittedKernel(handle, dtype, n, d, nu)
+        fk.x_train, fk.y_train = x, y
+        return fk
 
     def extend_with(self, x_train, y_train, ctx=None):
         """FittedKernel::extend (fit.rs:33-68) at this model's theta on data whose leading rows are this model's training
@@ -305,6 +309,7 @@ class FittedKernel:
         ext = getattr(lib, f"hbegp_extend_from_{self._sfx}")
         _lib.check(ext(ctx._h, self._h, _lib.aptr(x), _lib.aptr(y), n, C.byref(handle), C.byref(inc)))
         fk = FittedKernel(handle, self.dtype, n, d, self.nu)
+        fk.x_train, fk.y_train = x, y
         fk.incremental = bool(inc.value)
         return fk
 
@@ -417,6 +422,27 @@ class FittedKernel:
         _lib.check(fn(self._h, _lib.aptr(x), m, k, float(fmin_normalized), lie_c, idx.ctypes.data_as(C.POINTER(C.c_int)), _lib.dptr(ei),
                       _lib.aptr(mean), _lib.aptr(var)))
         return idx.astype(np.int64), ei, mean, var
+
+    def knowledge_gradient(self, x, n_candidates=None, want_posterior=False):
+        """Knowledge gradient over a candidate set (hbegp_knowledge_gradient_*), in the normalised y space: for each of the first
+        n_candidates rows of x (all of them by default) the expected drop of min_i mean_i over ALL rows of x after one more noisy
+        sample there.  It needs no fmin.  Returns (kg[n_candidates] float64, best, imin): best the last index of the maximum of kg
+        (-1 without candidates), imin the lowest index of the minimum of the posterior mean -- the row to recommend.  With
+        want_posterior also (mean[m], var[m]): predict_cov()'s mean and its diagonal clamped at 0, bit for bit."""
+        lib = _lib.load()
+        x = _lib.as_c(np.atleast_2d(x), self.dtype)
+        assert x.ndim == 2 and x.shape[1] == self.d
+        m = x.shape[0]
+        mc = m if n_candidates is None else int(n_candidates)
+        kg = np.zeros(max(mc, 0))
+        best, imin = C.c_int(-1), C.c_int(-1)
+        mean = np.zeros(m, dtype=self.dtype) if want_posterior else None
+        var = np.zeros(m, dtype=self.dtype) if want_posterior else None
+        fn = getattr(lib, f"hbegp_knowledge_gradient_{self._sfx}")
+        _lib.check(fn(self._h, _lib.aptr(x), m, mc, _lib.dptr(kg), C.byref(best), C.byref(imin), _lib.aptr(mean), _lib.aptr(var)))
+        if want_posterior:
+            return kg, best.value, imin.value, mean, var
+        return kg, best.value, imin.value
 
     def qei(self, x, z, fmin_normalized, jitter=0.0, want_grad=True, raise_not_pd=False):
         """Batch expected improvement by Monte Carlo (hbegp_qei_*) in the normalised y space: x [B, q, d] (or [q, d]: B = 1) batches

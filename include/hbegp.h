@@ -303,6 +303,31 @@ int hbegp_select_batch_f64(hbegp_model* model, const double* Xs, int m, int k, d
 int hbegp_select_batch_f32(hbegp_model* model, const float* Xs, int m, int k, double fmin_normalized, const double* lie, int* idx,
                            double* ei, float* mean_out, float* var_out);
 
+/* Knowledge gradient over a candidate set (Frazier, Powell, Dayanik 2009: correlated normal beliefs), in the normalised y space
+ * like hbegp_predict_*: the value of ONE more noisy sample at row j, measured by how much it is expected to lower the minimum of
+ * the posterior mean over the m rows of Xs.  It needs no fmin.  The first mc <= m rows are the places a sample may be taken; the
+ * minimum runs over all m rows (mc = m: the classic correlated KG).  With mu and Sigma of hbegp_predict_cov at jitter 0 and the
+ * model's noise s2, for j < mc:
+ *   r_i = Sigma_ij (i != j),  r_j = Sigma_jj - 1e-5 (the latent variance),  d_j = max(r_j, 0) + s2,  st_i = r_i / sqrt(d_j)
+ *   (hbegp_select_batch's first conditioning with f = mu_j + sqrt(d_j) Z: the mean after the sample is mu + st Z, Z ~ N(0, 1));
+ *   kg[j] = min_i mu_i - E_Z[ min_i (mu_i + st_i Z) ] >= 0,
+ * in closed form by the paper's Algorithm 1 on the lines a_i = -mu_i, b_i = -st_i: sorted by (b, a), of equal slopes the largest a
+ * kept, the upper envelope with strictly increasing breakpoints c_k, kg[j] = sum_k (b_{k+1} - b_k) f(-|c_k|), f(z) = phi(z) + z Phi(z).
+ * A single surviving line (m = 1, all slopes equal) gives exactly 0.  All of it is fp64 for both element types, so kg is double.
+ * kg[mc] (required for mc > 0); best (may be NULL): the LAST index of the maximum of kg, as Rust's max_by and hbegp_select_batch
+ * (-1 for mc = 0); imin (may be NULL): the lowest index of the minimum of mu over all m rows -- what a noisy tuner should
+ * recommend instead of its best observation; mean_out[m], var_out[m] (may be NULL): mu and max(diag Sigma, 0), bit for bit
+ * hbegp_predict_cov's mean and clamped diagonal (the mean is hbegp_predict's too for m > 16).  mc = 0 still fills imin / mean_out / var_out; m = 0 is a no-op (best = imin = -1).
+ * HBEGP_EINVAL (before any device call) for a NULL model, m < 0, mc < 0, mc > m, a NULL kg with mc > 0, a model of the other
+ * element type or a non-finite query coordinate.  Serialised per model like predict; fixed-order sums and no atomics: the same
+ * call gives the same bits, and kg[j] does not depend on mc.  Sigma (m_p^2 elements) is borrowed for the call, and for m > 8192 a
+ * workspace of at most 512 x 16 P bytes (P the power of two at or above m); work that does not fit in device memory is
+ * HBEGP_ENOMEM. */
+int hbegp_knowledge_gradient_f64(hbegp_model* model, const double* Xs, int m, int mc, double* kg, int* best, int* imin,
+                                 double* mean_out, double* var_out);
+int hbegp_knowledge_gradient_f32(hbegp_model* model, const float* Xs, int m, int mc, double* kg, int* best, int* imin,
+                                 float* mean_out, float* var_out);
+
 /* Batch expected improvement by Monte Carlo (q-EI) in the normalised y space like hbegp_predict_*, for B batches of q points:
  * Xb[B*q*d] (batch b = rows b*q .. b*q + q - 1, feature space), z[S*q] the CALLER's standard normals (draw s = row s), shared by
  * every batch (common random numbers; the RNG stays on the caller side).  Per batch b:
@@ -419,6 +444,10 @@ int hbegp_debug_posterior_phases(int enable, double* phase_ms);
  * calling thread's last timed hbegp_select_batch_* call -- Sigma (upload, K*, mean, Q, kmat, Q Q^T, mirror), the selection
  * kernel -- in milliseconds; then enable != 0 makes this thread's later selection calls timed. */
 int hbegp_debug_batch_select_phases(int enable, double* phase_ms);
+/* ---- timing hook (tools/kg_bench.py): phase_ms[2] (may be NULL) receives the device time of the phases of the calling thread's
+ * last timed hbegp_knowledge_gradient_* call -- Sigma (upload, K*, mean, Q, kmat, Q Q^T, mirror), kg (the per-candidate kernel and
+ * the epilogue) -- in milliseconds; then enable != 0 makes this thread's later knowledge-gradient calls timed. */
+int hbegp_debug_kg_phases(int enable, double* phase_ms);
 /* ---- timing hook (tools/qei_bench.py): phase_ms[2] (may be NULL) receives the device time of the phases of the calling thread's
  * last timed hbegp_qei_* call -- the shared launches (upload of the points, Kstar, mean, Q; with a gradient dmean, G, W; upload of
  * z), the qEI kernel -- in milliseconds; then enable != 0 makes this thread's later qEI calls timed. */

@@ -62,6 +62,9 @@ template <> struct Abi<double> {
   }
   static int select_batch(hbegp_model* m, const double* xs, int n, int k, double fmin, const double* lie, int* idx, double* ei, double* mean,
                           double* var) { return hbegp_select_batch_f64(m, xs, n, k, fmin, lie, idx, ei, mean, var); }
+  static int knowledge_gradient(hbegp_model* m, const double* xs, int n, int mc, double* kg, int* best, int* imin, double* mean, double* var) {
+    return hbegp_knowledge_gradient_f64(m, xs, n, mc, kg, best, imin, mean, var);
+  }
   static int qei(hbegp_model* m, const double* xb, int b, int q, const double* z, int s, double fmin, double j, double* v, double* g, int* info) {
     return hbegp_qei_f64(m, xb, b, q, z, s, fmin, j, v, g, info);
   }
@@ -100,6 +103,9 @@ template <> struct Abi<float> {
   }
   static int select_batch(hbegp_model* m, const float* xs, int n, int k, double fmin, const double* lie, int* idx, double* ei, float* mean,
                           float* var) { return hbegp_select_batch_f32(m, xs, n, k, fmin, lie, idx, ei, mean, var); }
+  static int knowledge_gradient(hbegp_model* m, const float* xs, int n, int mc, double* kg, int* best, int* imin, float* mean, float* var) {
+    return hbegp_knowledge_gradient_f32(m, xs, n, mc, kg, best, imin, mean, var);
+  }
   static int qei(hbegp_model* m, const float* xb, int b, int q, const float* z, int s, double fmin, double j, double* v, float* g, int* info) {
     return hbegp_qei_f32(m, xb, b, q, z, s, fmin, j, v, g, info);
   }
@@ -204,6 +210,13 @@ class FittedKernel {
   void select_batch(const A* xs, int m, int k, double fmin_normalized, int* idx, double* ei = nullptr, A* mean = nullptr,
                     A* var = nullptr, const double* lie = nullptr) const {
     check(detail::Abi<A>::select_batch(h_, xs, m, k, fmin_normalized, lie, idx, ei, mean, var));
+  }
+  // knowledge gradient of one more noisy sample at each of the first mc rows of xs[m*d], the minimum of the posterior mean taken
+  // over all m rows (normalised y space): kg[mc]; best (the last index of the maximum of kg), imin (the lowest index of the
+  // minimum of the mean), mean[m], var[m] may be nullptr
+  void knowledge_gradient(const A* xs, int m, int mc, double* kg, int* best = nullptr, int* imin = nullptr, A* mean = nullptr,
+                          A* var = nullptr) const {
+    check(detail::Abi<A>::knowledge_gradient(h_, xs, m, mc, kg, best, imin, mean, var));
   }
   // Monte Carlo q-EI of B batches xb[B*q*d] with the caller's normals z[S*q]: qei[B]; grad[B*q*d] and info[B] may be nullptr.
   // Returns HBEGP_OK or HBEGP_NOT_PD (some batch's Sigma did not factor: its qei is NaN, info says where); throws otherwise

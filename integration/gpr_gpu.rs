@@ -143,6 +143,14 @@ extern "C" {
         model: *mut HbegpModel, xs: *const c_float, m: c_int, k: c_int, fmin_normalized: c_double, lie: *const c_double,
         idx: *mut c_int, ei: *mut c_double, mean_out: *mut c_float, var_out: *mut c_float,
     ) -> c_int;
+    fn hbegp_knowledge_gradient_f64(
+        model: *mut HbegpModel, xs: *const c_double, m: c_int, mc: c_int, kg: *mut c_double, best: *mut c_int, imin: *mut c_int,
+        mean_out: *mut c_double, var_out: *mut c_double,
+    ) -> c_int;
+    fn hbegp_knowledge_gradient_f32(
+        model: *mut HbegpModel, xs: *const c_float, m: c_int, mc: c_int, kg: *mut c_double, best: *mut c_int, imin: *mut c_int,
+        mean_out: *mut c_float, var_out: *mut c_float,
+    ) -> c_int;
     fn hbegp_qei_f64(
         model: *mut HbegpModel, xb: *const c_double, b: c_int, q: c_int, z: *const c_double, s: c_int, fmin_normalized: c_double,
         jitter: c_double, qei: *mut c_double, grad: *mut c_double, info: *mut c_int,
@@ -238,6 +246,11 @@ pub trait GpuScalar: Scalar + sealed::Sealed {
         model: *mut HbegpModel, xs: *const Self, m: c_int, k: c_int, fmin_normalized: f64, lie: *const f64, idx: *mut c_int,
         ei: *mut f64, mean_out: *mut Self, var_out: *mut Self,
     ) -> c_int;
+    /// `hbegp_knowledge_gradient_*`
+    unsafe fn ffi_knowledge_gradient(
+        model: *mut HbegpModel, xs: *const Self, m: c_int, mc: c_int, kg: *mut f64, best: *mut c_int, imin: *mut c_int,
+        mean_out: *mut Self, var_out: *mut Self,
+    ) -> c_int;
     /// `hbegp_qei_*`
     unsafe fn ffi_qei(
         model: *mut HbegpModel, xb: *const Self, b: c_int, q: c_int, z: *const Self, s: c_int, fmin_normalized: f64, jitter: f64,
@@ -303,6 +316,12 @@ impl GpuScalar for f64 {
         ei: *mut f64, mean_out: *mut f64, var_out: *mut f64,
     ) -> c_int {
         hbegp_select_batch_f64(model, xs, m, k, fmin_normalized, lie, idx, ei, mean_out, var_out)
+    }
+    unsafe fn ffi_knowledge_gradient(
+        model: *mut HbegpModel, xs: *const f64, m: c_int, mc: c_int, kg: *mut f64, best: *mut c_int, imin: *mut c_int,
+        mean_out: *mut f64, var_out: *mut f64,
+    ) -> c_int {
+        hbegp_knowledge_gradient_f64(model, xs, m, mc, kg, best, imin, mean_out, var_out)
     }
     unsafe fn ffi_qei(
         model: *mut HbegpModel, xb: *const f64, b: c_int, q: c_int, z: *const f64, s: c_int, fmin_normalized: f64, jitter: f64,
@@ -371,6 +390,12 @@ impl GpuScalar for f32 {
         ei: *mut f64, mean_out: *mut f32, var_out: *mut f32,
     ) -> c_int {
         hbegp_select_batch_f32(model, xs, m, k, fmin_normalized, lie, idx, ei, mean_out, var_out)
+    }
+    unsafe fn ffi_knowledge_gradient(
+        model: *mut HbegpModel, xs: *const f32, m: c_int, mc: c_int, kg: *mut f64, best: *mut c_int, imin: *mut c_int,
+        mean_out: *mut f32, var_out: *mut f32,
+    ) -> c_int {
+        hbegp_knowledge_gradient_f32(model, xs, m, mc, kg, best, imin, mean_out, var_out)
     }
     unsafe fn ffi_qei(
         model: *mut HbegpModel, xb: *const f32, b: c_int, q: c_int, z: *const f32, s: c_int, fmin_normalized: f64, jitter: f64,
@@ -643,6 +668,28 @@ impl<A: GpuScalar> SurrogateModelGpu<A> {
             panic!("hbegp_select_batch failed: {}", last_error());
         }
         (idx.into_iter().map(|i| i as usize).collect(), ei)
+    }
+
+    /// Knowledge gradient over a candidate set (`hbegp_knowledge_gradient_*`; Frazier, Powell, Dayanik 2009): for each of the first
+    /// `n_candidates` rows of `x` the expected drop of the minimum of the posterior mean over ALL rows of `x` after one more noisy
+    /// observation there, in closed form, in the normalised y space -- no fmin, no random numbers.  Returns (kg [n_candidates],
+    /// best = the last index of its maximum as `max_by` (None without candidates), imin = the lowest index of the minimum of the
+    /// posterior mean: the row a tuner of a noisy objective should recommend instead of its best observation).  Opt-in.
+    pub fn knowledge_gradient_normalized(&self, x: ArrayView2<A>, n_candidates: usize) -> (Vec<f64>, Option<usize>, Option<usize>) {
+        let (m, _d) = x.dim();
+        assert!(n_candidates <= m, "n_candidates must be <= the number of rows");
+        let x = x.as_standard_layout();
+        let mut kg = vec![0.0f64; n_candidates];
+        let (mut best, mut imin): (c_int, c_int) = (-1, -1);
+        let kg_ptr = if n_candidates > 0 { kg.as_mut_ptr() } else { std::ptr::null_mut() };
+        let rc = unsafe {
+            A::ffi_knowledge_gradient(self.handle, x.as_ptr(), m as c_int, n_candidates as c_int, kg_ptr, &mut best, &mut imin,
+                                      std::ptr::null_mut(), std::ptr::null_mut())
+        };
+        if rc != HBEGP_OK {
+            panic!("hbegp_knowledge_gradient failed: {}", last_error());
+        }
+        (kg, usize::try_from(best).ok(), usize::try_from(imin).ok())
     }
 
     /// Monte Carlo q-EI (`hbegp_qei_*`) of `b` batches of q points, `xb` [b q, d] (batch i = rows i q .. i q + q - 1), with the
