@@ -739,6 +739,50 @@ class DagBuilder {
   void set_big128(bool on, bool with_acc = false) { big128_ = on; big128_acc_ = on && with_acc; }
 };
 
+// The K^-1 = X^T X tiles of a plan as a queue of their own: the second phase of a line-search trial whose gradient turned out
+// to be wanted (hbegp.cpp: lazy evaluation), launched once the first phase -- the same plan built with lauum = false -- has left
+// the complete X = L^-1 in W2.  The tasks are the full plan's DAGF_CKINV tasks as they are (same tiles, same contraction ranges,
+// so every element keeps its one k-ascending accumulation chain in f64 and its per-range rounding in f32), in the full queue's
+// order among themselves (a subsequence of a topological order is one).  Waits for the factorisation's counters are dropped --
+// a previous launch has completed them -- and the K^-1 tasks' own gates (a range's tiles behind the previous range's, the second
+// part of a split sum behind the first) stay, renumbered from zero.  Empty when the plan has no such task, or when a counter is
+// shared between K^-1 tasks and others (no builder emits that).
+inline DagPlan dag_plan_kinv_only(const DagPlan& full) {
+  DagPlan out;
+  const int nc = (int)full.totals.size();
+  std::vector<int> kept_bumps(nc, 0), remap(nc, -1);
+  for (const DagTask& t : full.tasks)
+    if (t.flags & DAGF_CKINV)
+      for (int q = 0; q < DAG_MAXSIG; ++q)
+        if (t.sig[q] != DAG_NOSIG) kept_bumps[t.sig[q]]++;
+  for (int c = 0; c < nc; ++c) {
+    if (kept_bumps[c] == 0) continue;
+    if (kept_bumps[c] != full.totals[c]) return DagPlan();
+    remap[c] = (int)out.totals.size();
+    out.totals.push_back(kept_bumps[c]);
+  }
+  for (const DagTask& src : full.tasks) {
+    if (!(src.flags & DAGF_CKINV)) continue;
+    DagTask t = src;
+    for (int q = 0; q < DAG_MAXSIG; ++q)
+      if (t.sig[q] != DAG_NOSIG) t.sig[q] = (uint16_t)remap[t.sig[q]];
+    t.nwait = 0;
+    for (int w = 0; w < DAG_MAXWAIT; ++w) t.wcnt[w] = t.wval[w] = 0;
+    for (int w = 0; w < src.nwait; ++w) {
+      if (remap[src.wcnt[w]] < 0) continue;
+      t.wcnt[t.nwait] = (uint16_t)remap[src.wcnt[w]];
+      t.wval[t.nwait] = src.wval[w];
+      ++t.nwait;
+    }
+    out.tasks.push_back(t);
+  }
+  out.gflop = out.gflop_lauum = full.gflop_lauum;
+  out.n_lauum = (int)out.tasks.size();
+  out.sim_us = full.sim_us;    // bounds of the whole evaluation: only used to size the wait bound
+  out.crit_us = full.crit_us;
+  return out;
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // Checks of a plan, all on the host:
 //  1. the queue order is a topological order: executing the tasks one by one in queue order never waits (this is what

@@ -690,7 +690,7 @@ struct Slot {
   size_t small_slab_bytes = 0;
   void* host_slab = nullptr;    // one pooled pinned block behind hP, hOut
   size_t host_slab_bytes = 0;
-  hipGraphExec_t graph[DAG_MAX_VARIANTS + 1 + DAG_CROWD_LEVELS][2][2] = {};  // [task-queue variant][target][want_grad]
+  hipGraphExec_t graph[DAG_MAX_VARIANTS + 1 + DAG_CROWD_LEVELS][2][4] = {};  // [task-queue variant][target][EvalMode]
   // capture state (fit.rs:116-125)
   int best_idx = -1;  // which ping-pong buffer holds the best evaluation so far
   double best_lml = -std::numeric_limits<double>::infinity();
@@ -699,10 +699,11 @@ struct Slot {
   std::vector<double> best_params;  // persistent fit kernel only: the clamped linear parameters the device evaluated the captured theta with
   int last_target = 0;  // buffer written by the most recent evaluation
   int dag_variant = 1;  // which ordering / launch size the next task-queue launch uses (Problem::DagVariant)
+  int dag_part = 0;     // which of the variant's queues the last launch ran (launch_queue): the timeout report reads its task list
   unsigned long long seq = 0;  // serial number of the last evaluation handed to the device (EvalParams::seq)
   bool ctrl_cleared = false;   // the evaluation's first kernel clears dag_ctrl itself (EvalPrologue): no memset node
   bool published = false;      // the evaluation ends with publish_out_kernel: the host may spin on hOut->seq
-  long long expect_ns = 0;     // how long the last published evaluation took from launch to publication (wait_eval sleeps through most of it)
+  long long expect_ns[4] = {0, 0, 0, 0};  // per EvalMode: how long the last published evaluation took from launch to publication (wait_eval sleeps through most of it)
 };
 
 struct ProblemBase {
@@ -737,17 +738,31 @@ struct Problem : ProblemBase {
     int nwg = 0;
     std::vector<DagTask*> tasks;            // per device
     std::vector<DagTask> host_tasks;        // kept for the trace dump
+    // lazy fits (lazy_): the two queues of a line-search trial evaluated in two phases.  p1: the same plan built without the K^-1
+    // tiles (what the lml needs); kinv: the full queue's K^-1 tasks alone (dag_plan_kinv_only), run when the gradient is wanted
+    int nwg_p1 = 0, ntasks_p1 = 0, nwg_kinv = 0, ntasks_kinv = 0;
+    std::vector<DagTask*> tasks_p1, tasks_kinv;  // per device
+    std::vector<DagTask> host_tasks_p1, host_tasks_kinv;
   };
   std::vector<DagVariant> dag_var;          // [0] unused, [v] for v busy slots
   std::unique_ptr<std::atomic<int>[]> busy_slots_;  // per device: slots inside an optimiser run (0: not known -> all of them)
   int dag_ntasks = 0, dag_nwg = 0;          // dag_nwg: workgroups of the default variant (all slots busy)
   int dag_nvar_ = 1, dag_ncrowd_ = 0;       // variants [1..dag_nvar_] for this fit's own busy slots, then dag_ncrowd_ crowded-device levels
   unsigned long long dag_wait_ticks_ = 200000000ull;  // bound of one dependency wait (100 MHz ticks), see init()
-  size_t dag_ctrl_bytes = 0;
+  size_t dag_ctrl_bytes = 0;                // one region of control words (queue head + counters)
+  // A lazy fit's slots hold two regions: the second is the K^-1-only queue's.  The first kernel of every evaluation clears both
+  // (EvalPrologue), and nothing but that queue touches the second one, so the second phase of a trial finds it clear: no fill node
+  // in front of its launch.
+  int dag_ctrl_regions_ = 1;
   double dag_gflop = 0;
   bool adhoc_ = false;                      // single-shot problem: no schedule table, every GEMM launch is ad hoc
   bool small_ = false;                      // np = 128, d <= 32: one evaluation = ONE launch (small_eval_kernel), everything in the LDS
   bool like_fit_ = false;                   // path selection of a fit (task queue from DAG_MIN_BLOCKS_FIT blocks on) although there is one slot
+  // HBEGP_LAZY_GRAD (default 1; read when the problem is created; fits only): a line-search trial is evaluated in two phases --
+  // everything the lml needs first (EVAL_LML_ONLY), K^-1 and the gradient (EVAL_GRAD_ONLY) only when the optimiser or the capture
+  // rule will read them (do_fit).  0: every trial is one fused evaluation.  Same kernels, same tiles, same bits either way.
+  bool lazy_ = false;
+  std::function<std::shared_ptr<const DagPlan>(int, bool)> plan_for_;  // (workgroups, with the K^-1 tiles) -> the cached plan
   // HBEGP_HOSTIO (default 1): an evaluation is driven through the slot's pinned blocks -- the first kernel reads the parameters
   // there and prepares the device-side blocks (EvalPrologue), the last one copies the results back and publishes the
   // evaluation's serial number, which the host thread spins on.  0: parameter copy + reset kernel + memset in front, a result
@@ -778,10 +793,12 @@ struct Problem : ProblemBase {
   // single_shot: the problem runs one evaluation (extend): skip the static schedule tables, every GEMM launch is ad hoc
   // like_fit: choose the evaluation path (launches / task queue) as a fit of this size does, whatever the slot count --
   // `extend` then repeats the fit's own evaluation of a theta bit for bit
-  Problem(hbegp_ctx* c, const T* X, const T* y, int n_, int d_, double nu, int n_slots_, bool single_shot = false, bool like_fit = false) {
+  Problem(hbegp_ctx* c, const T* X, const T* y, int n_, int d_, double nu, int n_slots_, bool single_shot = false, bool like_fit = false,
+          bool lazy_fit = false) {
     try {
       adhoc_ = single_shot;
       like_fit_ = like_fit;
+      lazy_ = lazy_fit && env_int("HBEGP_LAZY_GRAD", 1) != 0;
       init(c, X, y, n_, d_, nu, n_slots_);
     } catch (...) {
       release();  // a constructor that throws never runs the destructor: give back what was allocated so far
@@ -799,6 +816,9 @@ struct Problem : ProblemBase {
     // instead (HBEGP_SMALL=0: the general path, which the tests compare it with).
     small_ = np == NB && d <= SMALL_EVAL_MAXD && env_int("HBEGP_SMALL", 1) != 0;
     hostio_ = env_int("HBEGP_HOSTIO", 1) != 0;
+    // two phases need the published evaluation (the second phase republishes the result block); the single-launch evaluation
+    // of up to 128 rows stays fused
+    lazy_ = lazy_ && eval_published() && !adhoc_;
     const size_t nn = (size_t)np * np;
     Xd.assign(c->devs.size(), nullptr);
     yd.assign(c->devs.size(), nullptr);
@@ -910,8 +930,8 @@ struct Problem : ProblemBase {
       dag_rl_ = env_int("HBEGP_DAG_RL", np / NB <= 80 ? 1 : 0) != 0;
       static std::mutex cache_mu;
       static std::map<DagPlanKey, std::shared_ptr<const DagPlan>> cache;
-      auto plan_for = [&](int nwg) {
-        const DagPlanKey key = {np / NB, dag_stage_depth(is_f32), env_int("HBEGP_DAG_SMALLH", dag_rl_ ? 4 : 8), nwg, dag_lauum_, dag_rl_,
+      plan_for_ = [this](int nwg, bool lauum) {
+        const DagPlanKey key = {np / NB, dag_stage_depth(is_f32), env_int("HBEGP_DAG_SMALLH", dag_rl_ ? 4 : 8), nwg, lauum, dag_rl_,
                                 env_int("HBEGP_DAG_RL_GROUP", 32), env_int("HBEGP_DAG_RL_NEAR", 1),
                                 env_int("HBEGP_DAG_LAUUM_SPLIT", n_slots <= 1 ? 1 : 0),
                                 env_int("HBEGP_DAG_CHAIN32", 1),
@@ -944,15 +964,16 @@ struct Problem : ProblemBase {
           builder.set_rl(key.rl_group, key.rl_near, key.lauum_split != 0, key.chain32 != 0);
           builder.set_rl_progressive(key.prog != 0);
           builder.set_big128(key.big128 != 0, key.big128 >= 2);
-          cached = std::make_shared<const DagPlan>(builder.build(0, np / NB, dag_lauum_, dag_rl_));
+          cached = std::make_shared<const DagPlan>(builder.build(0, np / NB, lauum, dag_rl_));
           std::lock_guard<std::mutex> lk(cache_mu);
-          if (cache.size() > 64) cache.clear();
+          if (cache.size() > 256) cache.clear();  // (a lazy fit keeps two plans per launch size)
           cache[key] = cached;
         }
         return cached;
       };
       const int nvar = std::min(n_slots, DAG_MAX_VARIANTS);
       dag_nwg = share_of(n_slots);  // the default variant: every slot busy
+      auto plan_for = [this](int nwg) { return plan_for_(nwg, dag_lauum_); };
       std::shared_ptr<const DagPlan> cached = plan_for(dag_nwg);
       if (cached->tasks.empty() && dag_rl_) {  // too many counters for 16-bit ids (n > ~12k): the recursion plan needs far fewer
         dag_rl_ = false;
@@ -970,6 +991,7 @@ struct Problem : ProblemBase {
         dag_gflop = plan.gflop;
         dag_gflop_lauum = plan.gflop_lauum;
         dag_ctrl_bytes = (sizeof(int) * (DAG_CTRL_WORDS + plan.totals.size()) + 15) / 16 * 16;
+        dag_ctrl_regions_ = (lazy_ && dag_lauum_) ? 2 : 1;
         // A dependency wait longer than this is reported as a scheduling bug (info = -2).  The clock runs on while the queue is
         // preempted or time-sliced (another process, a profiler serialising dispatches) and single waits grow with the plan, so
         // the bound follows the plan: 200 x its simulated makespan with every slot sharing the chip, at least 2 s.
@@ -1001,6 +1023,39 @@ struct Problem : ProblemBase {
             var.tasks[di] = palloc<DagTask>(c->devs[di], pv->tasks.size());
             HIPCHECK(hipMemcpyAsync(var.tasks[di], var.host_tasks.data(), sizeof(DagTask) * var.host_tasks.size(), hipMemcpyHostToDevice, slots[di][0].stream));  // (the source outlives the copy: it is the problem's own)
           }
+          if (lazy_ && dag_lauum_) {
+            // the two queues of a trial evaluated in two phases, from THIS variant's plan: phase 1 the same plan built without
+            // the K^-1 tiles (the planner's lauum = false form, as factor_only's arithmetic: the same tiles of the factorisation),
+            // phase 2 the full queue's K^-1 tasks alone, in its order.  Workgroups per launch as the fused launch of the variant.
+            const int wg_p1 = lazy_wg(var.nwg, 1), wg_kinv = lazy_wg(var.nwg, 2);
+            const std::shared_ptr<const DagPlan> p1 = plan_for_(wg_p1, false);
+            const DagPlan kv = dag_plan_kinv_only(*pv);
+            if (p1->tasks.empty() || kv.tasks.empty() || p1->totals.size() > plan.totals.size() || kv.totals.size() > plan.totals.size()) {
+              // the full plan exists and these are parts of it: anything else is a planner bug, not a reason to half-disable the path
+              throw std::runtime_error("task queues of a two-phase evaluation could not be derived from the plan");
+            } else {
+              if (env_int("HBEGP_DAG_VALIDATE", 0)) {
+                std::string why = dag_plan_validate(*p1, np / NB);
+                if (why.empty()) why = dag_plan_validate(kv, np / NB);
+                if (!why.empty()) throw std::runtime_error("task queue of a two-phase evaluation is unsound: " + why);
+              }
+              var.host_tasks_p1 = p1->tasks;
+              var.host_tasks_kinv = kv.tasks;
+              var.ntasks_p1 = (int)p1->tasks.size();
+              var.ntasks_kinv = (int)kv.tasks.size();
+              var.nwg_p1 = std::min(wg_p1, var.ntasks_p1);
+              var.nwg_kinv = std::min(wg_kinv, var.ntasks_kinv);
+              var.tasks_p1.assign(c->devs.size(), nullptr);
+              var.tasks_kinv.assign(c->devs.size(), nullptr);
+              for (size_t di = 0; di < c->devs.size(); ++di) {
+                HIPCHECK(hipSetDevice(c->devs[di]));
+                var.tasks_p1[di] = palloc<DagTask>(c->devs[di], var.host_tasks_p1.size());
+                var.tasks_kinv[di] = palloc<DagTask>(c->devs[di], var.host_tasks_kinv.size());
+                HIPCHECK(hipMemcpyAsync(var.tasks_p1[di], var.host_tasks_p1.data(), sizeof(DagTask) * var.host_tasks_p1.size(), hipMemcpyHostToDevice, slots[di][0].stream));
+                HIPCHECK(hipMemcpyAsync(var.tasks_kinv[di], var.host_tasks_kinv.data(), sizeof(DagTask) * var.host_tasks_kinv.size(), hipMemcpyHostToDevice, slots[di][0].stream));
+              }
+            }
+          }
         }
         for (size_t di = 0; di < c->devs.size(); ++di) {
           HIPCHECK(hipSetDevice(c->devs[di]));
@@ -1009,8 +1064,8 @@ struct Problem : ProblemBase {
               bool f3 = false;
               s.W3 = static_cast<T*>(g_pool.get(s.dev, sizeof(T) * nn, &f3));  // the factor L: every tile read has been written
             }
-            s.dag_ctrl = palloc<int>(s.dev, dag_ctrl_bytes / sizeof(int));
-            HIPCHECK(hipMemsetAsync(s.dag_ctrl, 0, dag_ctrl_bytes, slots[di][0].stream));
+            s.dag_ctrl = palloc<int>(s.dev, dag_ctrl_regions_ * dag_ctrl_bytes / sizeof(int));
+            HIPCHECK(hipMemsetAsync(s.dag_ctrl, 0, dag_ctrl_regions_ * dag_ctrl_bytes, slots[di][0].stream));
             if (getenv("HBEGP_DAG_TRACE")) {
               s.dag_trace = palloc<unsigned long long>(s.dev, 5 * plan.tasks.size());
               HIPCHECK(hipMemsetAsync(s.dag_trace, 0, sizeof(unsigned long long) * 5 * plan.tasks.size(), slots[di][0].stream));
@@ -1055,7 +1110,7 @@ struct Problem : ProblemBase {
         if (s.stream) (void)hipStreamSynchronize(s.stream);
         for (int v = 0; v <= DAG_MAX_VARIANTS + DAG_CROWD_LEVELS; ++v)
           for (int a = 0; a < 2; ++a)
-            for (int b = 0; b < 2; ++b)
+            for (int b = 0; b < 4; ++b)
               if (s.graph[v][a][b]) (void)hipGraphExecDestroy(s.graph[v][a][b]);
         const size_t nnb = sizeof(T) * (size_t)np * np;
         g_pool.put(s.dev, s.W1, nnb); g_pool.put(s.dev, s.W2, nnb); g_pool.put(s.dev, s.W3, nnb);
@@ -1076,8 +1131,8 @@ struct Problem : ProblemBase {
 
   // The GEMMs of an evaluation of the launch path are issued by this dispatcher: the i-th launch by the i-th static schedule
   // (init records them by walking eval_gemms); a single-shot problem has no table and issues them ad hoc.
-  auto scheduled(Slot<T>& s, size_t di, PhaseTimer* tm) {
-    return [this, &s, di, tm, ord = 0](GemmLaunch& g, int kind) mutable {
+  auto scheduled(Slot<T>& s, size_t di, PhaseTimer* tm, int ord0 = 0) {
+    return [this, &s, di, tm, ord = ord0](GemmLaunch& g, int kind) mutable {
       if (adhoc_) return gemm_adhoc<T>(g, &s.dOut->info, s.stream);
       const Sched& sc = scheds[di][ord++];
       g.info = &s.dOut->info;
@@ -1091,6 +1146,17 @@ struct Problem : ProblemBase {
       launch_gemm<T>(g, sc.tile, s.stream);
       if (tm) tm->end();
     };
+  }
+
+  // Workgroups of the two launches of a lazily evaluated trial (part 1: the queue without K^-1 tasks, 2: the K^-1 tasks alone):
+  // the fused launch's count of the same variant, which is the measured optimum for both (config M, three slots, fits/s;
+  // profiles/lazy_grad_workgroups_per_launch.txt): phase 1 at 80 / 88 / 96 / 104 / 112 / 128 -> 1.896 / 1.924 / 1.936 / 1.830 / 1.801 /
+  // 1.702 -- as sharp as the fused launch's, for the same reason: three launches share 256 CUs; K^-1 alone at 48 / 64 / 80 / 96 / 112 /
+  // 128 / 160 -> 1.714 / 1.858 / 1.899 / 1.936 / 1.923 / 1.930 / 1.926 -- flat from 96 on.  HBEGP_DAG_WG_P1 / HBEGP_DAG_WG_KINV force a
+  // count (the sweep's knobs).
+  static int lazy_wg(int fused_nwg, int part) {
+    const int forced = env_int(part == 1 ? "HBEGP_DAG_WG_P1" : "HBEGP_DAG_WG_KINV", 0);
+    return forced > 0 ? forced : fused_nwg;
   }
 
   // the diagonal-block step of the fit's chol_inv_rec: X_kk -> W2, diag(L_kk) -> ldiag
@@ -1107,12 +1173,16 @@ struct Problem : ProblemBase {
   // dispatcher to build the schedule table, then with the scheduled one for every evaluation.
   // (round 1: a right-looking sweep over 512- / 1024-wide big blocks in front of the recursion -- 3.55 vs 3.43 ms per evaluation at
   // n = 4096, removed in round 5)
+  // part: 0 the whole evaluation | 1 without K^-1 (first phase of a lazily evaluated trial) | 2 K^-1 alone (its second phase: the
+  // LAUUM launch is the LAST of the sequence, so a dispatcher that starts at scheds[di].size() - 1 hands it its own schedule)
   template <class Gemm, class Leaf, class Alpha>
-  void eval_gemms(Slot<T>& s, T* Kinv, Gemm&& gemm, Leaf&& leaf, Alpha&& alpha) {
+  void eval_gemms(Slot<T>& s, T* Kinv, Gemm&& gemm, Leaf&& leaf, Alpha&& alpha, int part = 0) {
     const int nb = np / NB;
-    if (!dag_) chol_inv_rec<T>(s.W1, s.W2, s.W2, np, 0, nb / 2, nb, false, true, gemm, leaf);
-    alpha();
-    if (!(dag_ && dag_lauum_)) {
+    if (part != 2) {
+      if (!dag_) chol_inv_rec<T>(s.W1, s.W2, s.W2, np, 0, nb / 2, nb, false, true, gemm, leaf);
+      alpha();
+    }
+    if (part != 1 && !(dag_ && dag_lauum_)) {
       // K^-1 = X^T X (lower)  [LAUUM]   (task-queue path: tiles of the same queue, dag_plan.hpp build_lauum)
       GemmLaunch g{};
       g.nops = 1;
@@ -1131,10 +1201,12 @@ struct Problem : ProblemBase {
   void dag_report_timeout(Slot<T>& s) {
     if (!s.dag_ctrl) return;
     std::vector<int> ctrl(dag_ctrl_bytes / sizeof(int));
-    if (hipMemcpyAsync(ctrl.data(), s.dag_ctrl, dag_ctrl_bytes, hipMemcpyDeviceToHost, s.stream) != hipSuccess || hipStreamSynchronize(s.stream) != hipSuccess) return;
+    if (hipMemcpyAsync(ctrl.data(), s.dag_ctrl + (s.dag_part == 2 ? dag_ctrl_bytes / sizeof(int) : 0), dag_ctrl_bytes, hipMemcpyDeviceToHost, s.stream) != hipSuccess || hipStreamSynchronize(s.stream) != hipSuccess) return;
     const int row = ctrl[1] - 1;
-    fprintf(stderr, "task queue timeout: queue head %d of %d, first task that gave up: %d\n", ctrl[0], dag_ntasks, row);
-    const std::vector<DagTask>& host_tasks = dag_var[s.dag_variant].host_tasks;
+    const DagVariant& var = dag_var[s.dag_variant];
+    const int ntasks_here = s.dag_part == 1 ? var.ntasks_p1 : (s.dag_part == 2 ? var.ntasks_kinv : dag_ntasks);
+    fprintf(stderr, "task queue timeout: queue head %d of %d, first task that gave up: %d\n", ctrl[0], ntasks_here, row);
+    const std::vector<DagTask>& host_tasks = s.dag_part == 1 ? var.host_tasks_p1 : (s.dag_part == 2 ? var.host_tasks_kinv : var.host_tasks);
     if (row >= 0 && row < (int)host_tasks.size()) {
       const DagTask& t = host_tasks[row];
       fprintf(stderr, "  kind %d flags %x row0 %d col0 %d k [%d, %d) waits:", t.kind, t.flags, t.row0, t.col0, t.kbeg, t.kend);
@@ -1146,20 +1218,26 @@ struct Problem : ProblemBase {
 
   // The factorisation as ONE persistent launch of the task queue: workgroups pull diagonal-block and tile tasks from an ordered
   // queue.  With dag_lauum_ its tiles of K^-1 = X^T X go to Kinv (null: factorisation only).
-  void launch_queue(Slot<T>& s, size_t di, T* Kinv, PhaseTimer* tm) {
-    if (!s.ctrl_cleared) HIPCHECK(hipMemsetAsync(s.dag_ctrl, 0, dag_ctrl_bytes, s.stream));
-    s.ctrl_cleared = false;
+  // part: 0 the variant's full queue | 1 its queue without the K^-1 tasks | 2 its K^-1 tasks alone (X = L^-1 complete in W2)
+  void launch_queue(Slot<T>& s, size_t di, T* Kinv, PhaseTimer* tm, int part = 0) {
+    // (part 2: its own region of control words, clear since the first phase's kernel-matrix launch)
+    if (part != 2 && !s.ctrl_cleared) HIPCHECK(hipMemsetAsync(s.dag_ctrl, 0, dag_ctrl_regions_ * dag_ctrl_bytes, s.stream));
+    if (part != 2) s.ctrl_cleared = false;
     DagLaunch g{};
     const DagVariant& var = dag_var[s.dag_variant];
     g.tasks = var.tasks[di]; g.ntasks = dag_ntasks; g.ctrl = s.dag_ctrl;
+    int nwg = var.nwg;
+    s.dag_part = part;
+    if (part == 1) { g.tasks = var.tasks_p1[di]; g.ntasks = var.ntasks_p1; nwg = var.nwg_p1; }
+    if (part == 2) { g.tasks = var.tasks_kinv[di]; g.ntasks = var.ntasks_kinv; nwg = var.nwg_kinv; g.ctrl = s.dag_ctrl + dag_ctrl_bytes / sizeof(int); }
     g.W1 = s.W1; g.W2 = s.W2; g.ld = np; g.ldiag = s.ldiag; g.info = &s.dOut->info;
     g.W3 = s.W3;
-    g.Kinv = dag_lauum_ ? Kinv : nullptr;
+    g.Kinv = (dag_lauum_ && part != 1) ? Kinv : nullptr;
     g.trace = s.dag_trace;
     g.wait_ticks = dag_wait_ticks_;
     g.leaf_dbg = leaf_dbg_;
-    if (tm) tm->begin(PhaseTimer::DAG, 0, g.Kinv ? dag_gflop : dag_gflop - dag_gflop_lauum);
-    launch_dag<T>(g, var.nwg, s.stream);
+    if (tm) tm->begin(PhaseTimer::DAG, 0, part == 2 ? dag_gflop_lauum : (g.Kinv ? dag_gflop : dag_gflop - dag_gflop_lauum));
+    launch_dag<T>(g, nwg, s.stream);
     if (tm) tm->end();
   }
 
@@ -1174,8 +1252,30 @@ struct Problem : ProblemBase {
     launch_small_eval<T>(g, nu2, s.stream);
   }
 
-  void enqueue_eval(Slot<T>& s, size_t di, int target, bool want_grad, PhaseTimer* tm) {
+  // What one enqueued evaluation computes.  The first two are what `want_grad` = false / true always were (the index of the
+  // captured graph is the mode); the last two are the phases of a lazily evaluated line-search trial (lazy_, do_fit):
+  // EVAL_LML_ONLY = kmat, factorisation and inverse factor, alpha / lml, publish -- no K^-1; EVAL_GRAD_ONLY = on what that left
+  // in W2, alpha[target] and dP: the K^-1 tiles into Kinv[target], gradtrace / finalize_grad, publish again.
+  enum EvalMode { EVAL_LML_KINV = 0, EVAL_FULL = 1, EVAL_LML_ONLY = 2, EVAL_GRAD_ONLY = 3 };
+
+  void enqueue_eval(Slot<T>& s, size_t di, int target, int mode, PhaseTimer* tm) {
     const int* info = &s.dOut->info;
+    const bool want_grad = mode == EVAL_FULL || mode == EVAL_GRAD_ONLY;
+    if (mode == EVAL_GRAD_ONLY) {
+      // second phase: nothing in front of the K^-1 tiles (the queue's control words are a region of their own, still clear)
+      if (dag_ && dag_lauum_) launch_queue(s, di, s.Kinv[target], tm, 2);
+      else eval_gemms(s, s.Kinv[target], scheduled(s, di, tm, (int)scheds[di].size() - 1), leaf_step(s, tm), [] {}, 2);
+      const bool fuse_grad = (np / 64) * (np / 64 + 1) / 2 <= 512;  // as below
+      if (tm) tm->begin(PhaseTimer::GRAD);
+      launch_gradtrace<T>(Xd[di], n, d, np, nu2, s.dP, s.Kinv[target], s.alpha[target], s.part_g, s.dOut, info, s.stream,
+                          fuse_grad ? s.tickets + 1 : nullptr, fuse_grad ? s.hOut : nullptr);
+      if (tm) tm->end();
+      if (!fuse_grad) launch_publish_out(s.dOut, s.hOut, s.dP, s.stream);
+      s.published = true;
+      CHECK_LAUNCHES();
+      return;
+    }
+    const int part = mode == EVAL_LML_ONLY ? 1 : 0;
     if (small_) {
       if (tm) tm->begin(PhaseTimer::LEAF);
       small_eval(s, di, target, 1 | 2 | (want_grad ? 4 : 0));
@@ -1188,7 +1288,7 @@ struct Problem : ProblemBase {
       EvalPrologue pro;
       pro.dP = s.dP; pro.out = s.dOut;
       if (dag_) {
-        pro.ctrl = s.dag_ctrl; pro.ctrl_words = (int)(dag_ctrl_bytes / sizeof(int));
+        pro.ctrl = s.dag_ctrl; pro.ctrl_words = (int)(dag_ctrl_regions_ * dag_ctrl_bytes / sizeof(int));
         s.ctrl_cleared = true;
       }
       if (tm) tm->begin(PhaseTimer::KMAT);
@@ -1201,12 +1301,12 @@ struct Problem : ProblemBase {
       launch_kmat<T>(Xd[di], n, d, np, nu2, s.dP, s.W1, info, s.stream);
       if (tm) tm->end();
     }
-    if (dag_) launch_queue(s, di, s.Kinv[target], tm);
+    if (dag_) launch_queue(s, di, s.Kinv[target], tm, dag_lauum_ ? part : 0);
     eval_gemms(s, s.Kinv[target], scheduled(s, di, tm), leaf_step(s, tm), [&] {
       if (tm) tm->begin(PhaseTimer::ALPHA);
       launch_alpha_lml<T>(s.W2, np, n, yd[di], s.ldiag, s.wbuf, s.part_t, s.alpha[target], s.dOut, info, s.stream, hostio ? s.tickets : nullptr);
       if (tm) tm->end();
-    });
+    }, part);
     bool fuse_grad = false;
     if (want_grad) {
       if (tm) tm->begin(PhaseTimer::GRAD);
@@ -1237,16 +1337,17 @@ struct Problem : ProblemBase {
   // Long evaluations are slept through first: the thread remembers how long this slot's last evaluation took (they are all
   // alike) and, from 1.5 ms on, sleeps until an eighth of it (at least 300 us) before that: a fit at n = 4096 then keeps 1.4 cores busy
   // instead of 4 (hipStreamSynchronize spins as well: 4 cores with HBEGP_HOSTIO=0 too; tools/cpu_cost_probe.py).  A sleep that ran past the end shortens the next one.
-  void wait_eval(Slot<T>& s, std::chrono::steady_clock::time_point t_launch) {
+  void wait_eval(Slot<T>& s, std::chrono::steady_clock::time_point t_launch, int mode) {
+    long long& expect_ns = s.expect_ns[mode];
     if (s.published) {
       using namespace std::chrono;
       const volatile unsigned long long* q = &s.hOut->seq;
-      if (s.expect_ns > 1500000) {  // below ~1.5 ms a timer's wake-up jitter (50-100 us) costs more than it saves: n=512 fits 29.7 -> 21.6 /s with a 0.4 ms threshold
-        const long long margin = std::max<long long>(300000, s.expect_ns / 8);  // concurrent runs stretch each other by a few per cent, unevenly
-        std::this_thread::sleep_until(t_launch + nanoseconds(s.expect_ns - margin));
+      if (expect_ns > 1500000) {  // below ~1.5 ms a timer's wake-up jitter (50-100 us) costs more than it saves: n=512 fits 29.7 -> 21.6 /s with a 0.4 ms threshold
+        const long long margin = std::max<long long>(300000, expect_ns / 8);  // concurrent runs stretch each other by a few per cent, unevenly
+        std::this_thread::sleep_until(t_launch + nanoseconds(expect_ns - margin));
         if (*q == s.seq) {  // slept too long: the measurement below would include the oversleep
           std::atomic_thread_fence(std::memory_order_acquire);
-          s.expect_ns = s.expect_ns * 9 / 10;
+          expect_ns = expect_ns * 9 / 10;
           return;
         }
       }
@@ -1254,7 +1355,7 @@ struct Problem : ProblemBase {
       for (unsigned it = 1;; ++it) {
         if (*q == s.seq) {
           std::atomic_thread_fence(std::memory_order_acquire);
-          s.expect_ns = duration_cast<nanoseconds>(steady_clock::now() - t_launch).count();
+          expect_ns = duration_cast<nanoseconds>(steady_clock::now() - t_launch).count();
           return;
         }
         __builtin_ia32_pause();
@@ -1386,20 +1487,32 @@ struct Problem : ProblemBase {
     return busy <= 0 ? nvar : std::min(busy, nvar);
   }
   // Run one evaluation on (device index di, slot si) into ping-pong buffer `target`; blocks until the result is on the host.
-  int run_eval(size_t di, int si, int target, bool want_grad, bool use_graph, double* lml, double* grad) {
+  // mode: EvalMode (a bool converts as it always meant: false = lml + K^-1, true = the whole evaluation).  EVAL_GRAD_ONLY continues
+  // the slot's last EVAL_LML_ONLY evaluation (same target, parameters still in dP): *lml is not touched, grad must not be null.
+  int run_eval(size_t di, int si, int target, int mode, bool use_graph, double* lml, double* grad) {
     Slot<T>& s = slots[di][si];
     HIPCHECK(hipSetDevice(s.dev));
     static const bool graphs_on = env_int("HBEGP_NO_GRAPH", 0) == 0;
-    s.dag_variant = variant_now(di);
-    s.hP->seq = ++s.seq;
+    const bool want_grad = mode == EVAL_FULL || mode == EVAL_GRAD_ONLY;
+    if (mode == EVAL_GRAD_ONLY) {
+      // the same evaluation, published a second time under the same serial number (dP still carries it): the host takes the
+      // number back first, so that the word it spins on changes again when the second phase is over.  The queue variant stays the
+      // first phase's: both phases of a trial come from one plan.
+      if (!lazy_ || !eval_published() || !grad) throw std::logic_error("run_eval: the gradient phase needs a lazily evaluated, published problem");
+      reinterpret_cast<volatile unsigned long long*>(&s.hOut->seq)[0] = 0;
+      std::atomic_thread_fence(std::memory_order_seq_cst);
+    } else {
+      s.dag_variant = variant_now(di);
+      s.hP->seq = ++s.seq;
+    }
     const auto t_launch = std::chrono::steady_clock::now();
     if (use_graph && graphs_on) {
-      hipGraphExec_t& ge = s.graph[s.dag_variant][target][want_grad ? 1 : 0];
+      hipGraphExec_t& ge = s.graph[s.dag_variant][target][mode];
       if (!ge) {
         hipGraph_t gr = nullptr;
         HIPCHECK(hipStreamBeginCapture(s.stream, hipStreamCaptureModeThreadLocal));
         try {
-          enqueue_eval(s, di, target, want_grad, nullptr);
+          enqueue_eval(s, di, target, mode, nullptr);
         } catch (...) {
           (void)hipStreamEndCapture(s.stream, &gr);
           throw;
@@ -1410,10 +1523,10 @@ struct Problem : ProblemBase {
       }
       HIPCHECK(hipGraphLaunch(ge, s.stream));
     } else {
-      enqueue_eval(s, di, target, want_grad, nullptr);
+      enqueue_eval(s, di, target, mode, nullptr);
     }
     s.published = eval_published();  // what enqueue_eval records when it is not replayed from a graph (ONE rule for both: eval_published)
-    wait_eval(s, t_launch);
+    wait_eval(s, t_launch, mode);
     s.last_target = target;
     const int p = d + 2;
     if (s.hOut->info < 0) {
@@ -1421,10 +1534,12 @@ struct Problem : ProblemBase {
       throw HipError{hipErrorLaunchTimeOut, "factorisation task queue: a dependency wait exceeded its bound", __LINE__};
     }
     if (s.hOut->info != 0) {
-      *lml = -std::numeric_limits<double>::infinity();
+      if (mode != EVAL_GRAD_ONLY) *lml = -std::numeric_limits<double>::infinity();
       if (grad) for (int j = 0; j < p; ++j) grad[j] = 0.0;  // fit.rs:105-112
       return HBEGP_NOT_PD;
     }
+    double lml_kept = s.hOut->lml;
+    if (mode == EVAL_GRAD_ONLY) lml = &lml_kept;  // (already handed out by the first phase; checked again below all the same)
     // the evaluation starts by poisoning its outputs and clearing `done`: a kernel that was skipped cannot pass for a result
     if (!(s.hOut->done & 1) || (want_grad && !(s.hOut->done & 2)))
       throw HipError{hipErrorLaunchFailure, "evaluation: the lml/gradient kernels did not run", __LINE__};
@@ -2812,6 +2927,11 @@ static int check_paths_minimize(hbegp_paths* paths, const T* starts, int R, cons
 // fit (fit.rs:71-176 + gradmin.rs:7-60)
 // The caller's options struct may be older (shorter) or newer (longer) than this library's: copy what both know, the rest
 // stays zero / NULL.  Nothing is read or written beyond min(struct_size, sizeof).
+// What the calling thread's most recent fit did (hbegp_last_fit_stats): evaluations, failed ones, and the line-search trials
+// that ended after their first phase (lml only: no K^-1, no gradient).
+struct LastFitStats { int n_evals, n_not_pd, n_lml_only; };
+static thread_local LastFitStats g_last_fit_stats = {0, 0, 0};
+
 static int read_fit_options(const hbegp_fit_options* in, hbegp_fit_options* out) {
   *out = hbegp_fit_options{};
   out->struct_size = sizeof(hbegp_fit_options);
@@ -2835,6 +2955,7 @@ static int do_fit(hbegp_ctx* ctx, const T* X, const T* y, int n, int d, double n
                   const double* hi, const double* starts, int n_restarts, const hbegp_fit_options* opt_in,
                   double* theta_best, double* lml_best, hbegp_model** model_out, bool loo = false) {
   hbegp_fit_options opt{};
+  g_last_fit_stats = {0, 0, 0};  // a fit that fails leaves zeros, not the previous fit's numbers
   if (int e = read_fit_options(opt_in, &opt)) return e;
   if (opt.maxeval <= 0) opt.maxeval = 150;
   const int p = d + 2;
@@ -2876,7 +2997,7 @@ static int do_fit(hbegp_ctx* ctx, const T* X, const T* y, int n, int d, double n
   if (host_serial) host_lk.lock();
   const auto th0 = std::chrono::steady_clock::now();  // (HBEGP_TIMING: how long the turns are)
   double held_ms = 0;
-  Problem<T> prob(ctx, X, y, n, d, nu, n_slots, false, true);
+  Problem<T> prob(ctx, X, y, n, d, nu, n_slots, false, true, !loo);
   const auto tf1 = std::chrono::steady_clock::now();
   if (!(small_fit && prob.small_)) arrival.arrived();
   if (!(small_fit && prob.small_) && host_lk.owns_lock()) host_lk.unlock();
@@ -2888,7 +3009,10 @@ static int do_fit(hbegp_ctx* ctx, const T* X, const T* y, int n, int d, double n
   }
   std::mutex trace_mu;
   int trace_n = 0;
-  std::atomic<int> n_evals{0}, n_not_pd{0};
+  std::atomic<int> n_evals{0}, n_not_pd{0}, n_lml_only{0};
+  // lazy evaluation of line-search trials (Problem::lazy_: HBEGP_LAZY_GRAD, published evaluations, not the single-launch path).  A
+  // trace that records gradients reads every evaluation's gradient: such a fit evaluates every trial whole.
+  const bool lazy = prob.lazy_ && !loo && !(opt.trace_cap > 0 && opt.trace_grad);
   std::string err;
   std::mutex err_mu;
 
@@ -3043,6 +3167,7 @@ static int do_fit(hbegp_ctx* ctx, const T* X, const T* y, int n, int d, double n
       if (opt.trace_count) *opt.trace_count = trace_n;
       if (opt.n_evals) *opt.n_evals = total_evals;
       if (opt.n_not_pd) *opt.n_not_pd = total_not_pd;
+      g_last_fit_stats = {total_evals, total_not_pd, 0};  // the persistent kernel evaluates every point whole
       n_evals.store(total_evals);
     } catch (...) {
       for (int di = 0; di < ndev && di < (int)prob.slots.size(); ++di) {  // let the launched kernels finish before their workspaces go
@@ -3080,11 +3205,32 @@ static int do_fit(hbegp_ctx* ctx, const T* X, const T* y, int n, int d, double n
         if (r == 0) for (int i = 0; i < p; ++i) x[i] = theta0[i];
         else for (int i = 0; i < p; ++i) x[i] = starts[(size_t)(r - 1) * p + i];
         int eval_idx = 0;
-        Objective obj = [&](const double* th, double* grad) -> double {
+        // trial: the evaluation is a line-search trial of `ls` (lbfgs_is_trial) and the problem evaluates those lazily -- the lml
+        // first; K^-1 and the gradient only if lbfgs_advance will read the gradient (the Armijo test accepts the value:
+        // lbfgs_trial_accepted) or the capture rule below will keep the evaluation (a new best lml: a rejected trial can lie
+        // between f + 1e-4 gs and f).  Every other evaluation -- a run's start point, the fixed-work burn -- is one fused launch
+        // sequence as ever.  The values the optimiser reads have the same bits either way, so the iterates do.
+        auto obj = [&](const double* th, double* grad, const LbfgsState* ls) -> double {
           theta_to_params(th, lo, hi, d, s.hP);
           const int target = (s.best_idx < 0) ? 0 : 1 - s.best_idx;
           double lml;
-          int st = prob.run_eval((size_t)di, si, target, !loo, true, &lml, loo ? nullptr : grad);
+          int st;
+          if (ls) {
+            st = prob.run_eval((size_t)di, si, target, Problem<T>::EVAL_LML_ONLY, true, &lml, nullptr);
+            const bool new_best = st == HBEGP_OK && (s.best_idx < 0 || lml > s.best_lml);
+            if (st == HBEGP_OK && (new_best || lbfgs_trial_accepted(*ls, -lml))) {
+              // (a gradient that is not finite fails the whole evaluation here as in the fused form: +inf, never captured.  The one
+              // difference from the fused form is on the other branch: a trial with a finite lml whose gradient WOULD be non-finite,
+              // rejected and not a new best, keeps its finite lml and is not counted in n_not_pd -- its gradient is never formed)
+              st = prob.run_eval((size_t)di, si, target, Problem<T>::EVAL_GRAD_ONLY, true, nullptr, grad);
+              if (st != HBEGP_OK) lml = -std::numeric_limits<double>::infinity();
+            } else {
+              for (int j = 0; j < p; ++j) grad[j] = 0.0;  // never read
+              n_lml_only.fetch_add(1);
+            }
+          } else {
+            st = prob.run_eval((size_t)di, si, target, !loo, true, &lml, loo ? nullptr : grad);
+          }
           if (loo) {
             if (st == HBEGP_OK) st = prob.loo_on_slot((size_t)di, si, &lml, grad);
             else for (int j = 0; j < p; ++j) grad[j] = 0.0;
@@ -3119,7 +3265,16 @@ static int do_fit(hbegp_ctx* ctx, const T* X, const T* y, int n, int d, double n
         lo_opt.maxeval = opt.maxeval;
         lo_opt.fixed_work = opt.fixed_work != 0;
         if (opt.lbfgs_memory > 0) lo_opt.memory = opt.lbfgs_memory;
-        lbfgsb_minimize(obj, x.data(), lnlo.data(), lnhi.data(), p, lo_opt);
+        // lbfgsb_minimize's loop around the state machine (lbfgsb.hpp), with the objective told which evaluations are trials
+        static_assert(MAXP <= LBFGS_MAXN, "the GP's parameters fit the fixed-size optimiser state");
+        std::vector<double> g(p);
+        std::unique_ptr<LbfgsState> ls(new LbfgsState);
+        lbfgs_begin(*ls, x.data(), lnlo.data(), lnhi.data(), p, lo_opt.maxeval, lo_opt.memory, lo_opt.pgtol, lo_opt.ftol, lo_opt.fixed_work);
+        for (;;) {
+          const bool trial = lazy && lbfgs_is_trial(*ls);
+          const double f = obj(lbfgs_request(*ls), g.data(), trial ? ls.get() : nullptr);
+          if (!lbfgs_advance(*ls, f, g.data())) break;
+        }
       }
     } catch (const HipError& he) {
       hip_fail(he);
@@ -3161,6 +3316,7 @@ static int do_fit(hbegp_ctx* ctx, const T* X, const T* y, int n, int d, double n
   if (opt.trace_count) *opt.trace_count = trace_n;
   if (opt.n_evals) *opt.n_evals = n_evals.load();
   if (opt.n_not_pd) *opt.n_not_pd = n_not_pd.load();
+  g_last_fit_stats = {n_evals.load(), n_not_pd.load(), n_lml_only.load()};
   if (!err.empty()) return fail(HBEGP_EHIP, "%s", err.c_str());
   }  // host-driven optimiser runs
 
@@ -4020,19 +4176,37 @@ void hbegp_model_release(hbegp_model* model) {
   if (model && model->refs.fetch_sub(1) == 1) delete model;
 }
 
-int hbegp_debug_lbfgs_replay(int n, const double* x0, const double* lo, const double* hi, int maxeval, int memory, int fixed_work,
-                             int count, const double* f, const double* g, double* requested, int* n_requested) {
-  if (n < 1 || n > LBFGS_MAXN || count < 0 || !x0 || !lo || !hi || !requested || !n_requested || (count > 0 && (!f || !g)))
-    return fail(HBEGP_EINVAL, "bad argument");
-  GUARD_BEGIN
+int hbegp_last_fit_stats(hbegp_fit_stats* out) {
+  if (!out || out->struct_size < offsetof(hbegp_fit_stats, n_evals) + sizeof(int) || out->struct_size > ((size_t)1 << 16))
+    return fail(HBEGP_EINVAL, "hbegp_fit_stats.struct_size: set it to sizeof(hbegp_fit_stats) (HBEGP_FIT_STATS_INIT)");
+  hbegp_fit_stats full{};
+  full.struct_size = out->struct_size;
+  full.n_evals = g_last_fit_stats.n_evals;
+  full.n_not_pd = g_last_fit_stats.n_not_pd;
+  full.n_lml_only = g_last_fit_stats.n_lml_only;
+  memcpy(out, &full, std::min(out->struct_size, sizeof(full)));  // nothing beyond the caller's struct is written
+  return HBEGP_OK;
+}
+
+// The optimiser's state machine replayed on a recorded sequence of values (tests): ONE loop behind hbegp_debug_lbfgs_replay and
+// hbegp_debug_lbfgs_decisions.  trial / accepted / took (all three or none): per evaluation, lbfgs_is_trial, what
+// lbfgs_trial_accepted said of f[i] BEFORE lbfgs_advance took it, and whether lbfgs_advance then took its accepted branch.
+static int lbfgs_replay_impl(int n, const double* x0, const double* lo, const double* hi, int maxeval, int memory, int fixed_work, int count,
+                             const double* f, const double* g, double* requested, int* trial, int* accepted, int* took, int* n_requested) {
   LbfgsOptions o;
   std::unique_ptr<LbfgsState> st(new LbfgsState);
   lbfgs_begin(*st, x0, lo, hi, n, maxeval, memory > 0 ? memory : o.memory, o.pgtol, o.ftol, fixed_work != 0);
-  int produced = 0;
   memcpy(requested, lbfgs_request(*st), sizeof(double) * n);
-  produced = 1;
+  int produced = 1;
   for (int i = 0; i < count; ++i) {
-    if (!lbfgs_advance(*st, f[i], g + (size_t)i * n)) break;
+    if (trial) {
+      trial[i] = lbfgs_is_trial(*st) ? 1 : 0;
+      accepted[i] = lbfgs_trial_accepted(*st, f[i]) ? 1 : 0;
+    }
+    const int it0 = st->iterations;
+    const bool more = lbfgs_advance(*st, f[i], g + (size_t)i * n);
+    if (took) took[i] = st->iterations != it0 ? 1 : 0;
+    if (!more) break;
     if (i + 1 < count) {
       memcpy(requested + (size_t)(i + 1) * n, lbfgs_request(*st), sizeof(double) * n);
       produced = i + 2;
@@ -4040,6 +4214,52 @@ int hbegp_debug_lbfgs_replay(int n, const double* x0, const double* lo, const do
   }
   *n_requested = produced;
   return HBEGP_OK;
+}
+
+int hbegp_debug_lbfgs_decisions(int n, const double* x0, const double* lo, const double* hi, int maxeval, int memory, int fixed_work,
+                                int count, const double* f, const double* g, double* requested, int* trial, int* accepted, int* took,
+                                int* n_requested) {
+  if (n < 1 || n > LBFGS_MAXN || count < 0 || !x0 || !lo || !hi || !requested || !n_requested || !trial || !accepted || !took ||
+      (count > 0 && (!f || !g)))
+    return fail(HBEGP_EINVAL, "bad argument");
+  GUARD_BEGIN
+  return lbfgs_replay_impl(n, x0, lo, hi, maxeval, memory, fixed_work, count, f, g, requested, trial, accepted, took, n_requested);
+  GUARD_END
+}
+
+// The three queues of a task-queue evaluation for the tests: which = 0 the full plan (with the K^-1 tiles), 1 the plan without
+// them (first phase of a lazily evaluated trial), 2 the K^-1 tasks alone (dag_plan_kinv_only of the full plan).  fine as in
+// hbegp_debug_dag_plan (bit 2 is implied).  tasks (may be NULL): 6 ints per task -- kind, flags, row0, col0, kbeg, kend -- for the
+// first `cap` tasks in queue order.  The plan is validated; err receives the reason when it is unsound.
+int hbegp_debug_dag_queues(int nblocks, int bk, int small_h, int nwg, int fine, int big128, int which, int* ntasks, int* tasks, int cap,
+                           char* err, int errlen) {
+  if (nblocks < 1 || (bk != 16 && bk != 32) || small_h < 0 || nwg < 0 || which < 0 || which > 2 || !ntasks) return fail(HBEGP_EINVAL, "bad argument");
+  GUARD_BEGIN
+  DagBuilder builder(bk, small_h, nwg, (fine & 1) != 0);
+  builder.set_rl_progressive((fine & 16) != 0);
+  builder.set_big128(big128 != 0, big128 >= 2);
+  builder.set_rl(32, 1, (fine & 32) == 0, true);  // the engine's grouping; bit 5: no split K^-1 sums (a fit with several slots)
+  DagPlan plan = builder.build(0, nblocks, which != 1, (fine & 8) != 0);
+  if (which == 2) plan = dag_plan_kinv_only(plan);
+  const std::string why = plan.tasks.empty() ? std::string("no tasks") : dag_plan_validate(plan, nblocks);
+  *ntasks = (int)plan.tasks.size();
+  if (tasks)
+    for (int i = 0; i < std::min(cap, (int)plan.tasks.size()); ++i) {
+      const DagTask& t = plan.tasks[i];
+      const int v[6] = {t.kind, t.flags, t.row0, t.col0, t.kbeg, t.kend};
+      memcpy(tasks + (size_t)6 * i, v, sizeof v);
+    }
+  if (err && errlen > 0) snprintf(err, (size_t)errlen, "%s", why.c_str());
+  return why.empty() ? HBEGP_OK : fail(HBEGP_EINVAL, "%s", why.c_str());
+  GUARD_END
+}
+
+int hbegp_debug_lbfgs_replay(int n, const double* x0, const double* lo, const double* hi, int maxeval, int memory, int fixed_work,
+                             int count, const double* f, const double* g, double* requested, int* n_requested) {
+  if (n < 1 || n > LBFGS_MAXN || count < 0 || !x0 || !lo || !hi || !requested || !n_requested || (count > 0 && (!f || !g)))
+    return fail(HBEGP_EINVAL, "bad argument");
+  GUARD_BEGIN
+  return lbfgs_replay_impl(n, x0, lo, hi, maxeval, memory, fixed_work, count, f, g, requested, nullptr, nullptr, nullptr, n_requested);
   GUARD_END
 }
 

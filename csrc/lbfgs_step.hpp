@@ -179,6 +179,21 @@ LBFGS_HD inline void lbfgs_begin(St& s, const double* x0, const double* lo, cons
 template <class St>
 LBFGS_HD inline const double* lbfgs_request(const St& s) { return s.phase == 1 ? s.xn : s.x; }
 
+// True while the pending evaluation is a line-search trial: the only kind whose gradient lbfgs_advance may never look at.
+template <class St>
+LBFGS_HD inline bool lbfgs_is_trial(const St& s) { return s.phase == 1; }
+
+// What lbfgs_advance will do with the pending line-search trial, from its value alone: true = the Armijo test accepts it, and
+// lbfgs_advance then reads its gradient (curvature pair, next direction); false = rejected (or a failed evaluation: +inf / NaN),
+// the gradient is never looked at.  A caller that pays for gradients separately (hbegp.cpp: the fit's two-phase evaluation of a
+// trial) asks this first.  The test is lbfgs_advance's own, term for term.
+template <class St>
+LBFGS_HD inline bool lbfgs_trial_accepted(const St& s, double fe) {
+  if (s.phase != 1) return false;
+  if (fe != fe) fe = INFINITY;
+  return lbfgs_detail::finite(fe) && fe <= s.f + 1e-4 * s.gs;
+}
+
 // Feeds the evaluation of lbfgs_request(): f (may be +inf / NaN: a failed evaluation, grad then ignored) and grad.
 // Returns true while another evaluation is wanted.
 template <class St>
@@ -195,8 +210,8 @@ LBFGS_HD inline bool lbfgs_advance(St& s, double fe, const double* ge) {
     next = finite(fe) ? begin_iteration(s) : 2;
   } else if (s.phase == 1) {
     const double fn = fe;
-    if (finite(fn) && fn <= s.f + 1e-4 * s.gs) {
-      // accepted: curvature pair, move
+    if (lbfgs_trial_accepted(s, fn)) {
+      // accepted (finite and fn <= f + 1e-4 gs): curvature pair, move
       ++s.iterations;
       double sv_stack[LbfgsWork<St>::N], yv_stack[LbfgsWork<St>::N];
       double* sv = LbfgsWork<St>::get(s, sv_stack, 2);

@@ -45,6 +45,16 @@ class FitOptions(C.Structure):
         self.struct_size = C.sizeof(FitOptions)
 
 
+class FitStats(C.Structure):
+    """hbegp_fit_stats; `struct_size` is filled in by __init__ (the library writes min(struct_size, its own size))."""
+
+    _fields_ = [("struct_size", C.c_size_t), ("n_evals", C.c_int), ("n_not_pd", C.c_int), ("n_lml_only", C.c_int)]
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.struct_size = C.sizeof(FitStats)
+
+
 OBJECTIVE_FN = C.CFUNCTYPE(C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p)
 
 _dp = C.POINTER(C.c_double)
@@ -127,6 +137,10 @@ SIGNATURES = {
     "hbegp_model_retain": (None, [_vp]),
     "hbegp_model_release": (None, [_vp]),
     "hbegp_debug_lbfgs_replay": (C.c_int, [C.c_int, _dp, _dp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _ip]),
+    "hbegp_last_fit_stats": (C.c_int, [C.POINTER(FitStats)]),
+    "hbegp_debug_lbfgs_decisions": (C.c_int, [C.c_int, _dp, _dp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _ip, _ip, _ip, _ip]),
+    "hbegp_debug_dag_queues": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip, _ip, C.c_int, C.c_char_p,
+                                         C.c_int]),
     "hbegp_debug_dag_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip, _ip, _ip, _dp, _dp, _dp, C.c_char_p,
                                        C.c_int]),
     "hbegp_minimize_by_gradient": (C.c_double, [OBJECTIVE_FN, _vp, _dp, _dp, _dp, C.c_int, C.c_int]),

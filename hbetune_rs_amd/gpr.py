@@ -214,7 +214,11 @@ class FittedKernel:
 
     @staticmethod
     def new(x_train, y_train, theta0, lo, hi, starts=None, nu=2.5, ctx=None, maxeval=150, fixed_work=False, trace=False):
-        """FittedKernel::new (fit.rs:18-31, 71-176): 1 + len(starts) bounded L-BFGS runs, capture the best lml."""
+        """FittedKernel::new (fit.rs:18-31, 71-176): 1 + len(starts) bounded L-BFGS runs, capture the best lml.
+
+        trace=True records (theta, lml, gradient, run) of every evaluation; a fit that records gradients evaluates every
+        line-search trial whole.  trace="lml" records (theta, lml, run) only and leaves the evaluation as an untraced fit's:
+        trials the optimiser rejects end after their lml (`n_lml_only` counts them; HBEGP_LAZY_GRAD=0 turns that off)."""
         return FittedKernel._fit("hbegp_fit", x_train, y_train, theta0, lo, hi, starts, nu, ctx, maxeval, fixed_work, trace)
 
     @staticmethod
@@ -253,7 +257,8 @@ class FittedKernel:
             opt.trace_cap = cap
             opt.trace_theta = _lib.dptr(tr["theta"])
             opt.trace_lml = _lib.dptr(tr["lml"])
-            opt.trace_grad = _lib.dptr(tr["grad"])
+            if trace != "lml":
+                opt.trace_grad = _lib.dptr(tr["grad"])
             opt.trace_run = tr["run"].ctypes.data_as(C.POINTER(C.c_int))
             opt.trace_count = C.pointer(tr["count"])
         handle = C.c_void_p()
@@ -265,12 +270,17 @@ class FittedKernel:
         fk = FittedKernel(handle, dtype, n, d, nu)
         fk.x_train, fk.y_train = x, y
         fk.n_evals, fk.n_not_pd = n_evals.value, n_not_pd.value
+        stats = _lib.FitStats()
+        _lib.check(lib.hbegp_last_fit_stats(C.byref(stats)))  # this thread's fit, the one above
+        fk.n_lml_only = stats.n_lml_only
         fk.theta_best = theta_best
         if symbol == "hbegp_fit_loo":
             fk.loo_best = lml_best.value
         if trace:
             k = tr["count"].value
-            fk.trace = dict(theta=tr["theta"][:k], lml=tr["lml"][:k], grad=tr["grad"][:k], run=tr["run"][:k])
+            fk.trace = dict(theta=tr["theta"][:k], lml=tr["lml"][:k], run=tr["run"][:k])
+            if trace != "lml":
+                fk.trace["grad"] = tr["grad"][:k]
         return fk
 
     @staticmethod

@@ -155,7 +155,16 @@ typedef struct hbegp_fit_options {
    * NULL, so the struct can grow at its end.  0 or a size that does not cover `maxeval` is HBEGP_EINVAL. */
   size_t struct_size;
   int maxeval;      /* evaluations per optimiser run; the reference uses 150 (gradmin.rs:54) */
-  int fixed_work;   /* 0: stop a run when the optimiser converges; 1: keep evaluating up to maxeval (bench) */
+  int fixed_work;   /* 0: stop a run when the optimiser converges; 1: keep evaluating up to maxeval (bench).  A fixed-work run still
+                     * makes maxeval objective evaluations, and each returns the lml the optimiser reads.  K^-1 and the gradient are
+                     * computed where they are read: at a run's start point, at line-search trials the Armijo test accepts, at trials
+                     * that become the fit's new best (their K^-1 and alpha are the model's), and at the burn evaluations at the
+                     * incumbent.  A rejected trial ends after its lml (HBEGP_LAZY_GRAD=0 in the environment when the fit starts:
+                     * every trial whole, as before; so does a fit whose trace records gradients, trace_grad != NULL).  The values
+                     * the optimiser reads, hence its iterates and the fitted model, are bit for bit the same either way -- with one
+                     * exception: an evaluation whose lml is finite and whose gradient is not used to fail as a whole (objective +inf,
+                     * counted in n_not_pd); as a rejected trial that is no new best its gradient is no longer formed, so its finite
+                     * lml is what the line search sees and n_not_pd does not count it. */
   int lbfgs_memory; /* history pairs, 0 = default (10) */
   int trace_cap;    /* capacity (in evaluations) of the trace buffers below, 0 = no trace */
   /* optional trace of the evaluations, for replay parity against the oracle: trace_theta[trace_cap*p],
@@ -171,6 +180,21 @@ typedef struct hbegp_fit_options {
   int* n_not_pd;    /* out (may be NULL): evaluations whose kernel matrix was not positive definite (objective +inf, fit.rs:105-112) */
 } hbegp_fit_options;
 #define HBEGP_FIT_OPTIONS_INIT { sizeof(hbegp_fit_options) }
+
+/* Statistics of the calling thread's most recent hbegp_fit_* / hbegp_fit_loo_* call (zeros before the first).  struct_size as in
+ * hbegp_fit_options: the library writes min(struct_size, its own sizeof) bytes, so the struct can grow at its end.
+ * n_evals / n_not_pd: as the fit options' outputs of the same names.  n_lml_only: the evaluations among n_evals that computed the
+ * lml alone -- line-search trials that the optimiser rejected and the capture rule did not keep, so that nobody would have read
+ * their K^-1 or gradient (0 with HBEGP_LAZY_GRAD=0, for fits of at most 128 rows, leave-one-out fits, and fits that trace
+ * gradients). */
+typedef struct hbegp_fit_stats {
+  size_t struct_size;
+  int n_evals;
+  int n_not_pd;
+  int n_lml_only;
+} hbegp_fit_stats;
+#define HBEGP_FIT_STATS_INIT { sizeof(hbegp_fit_stats) }
+int hbegp_last_fit_stats(hbegp_fit_stats* out);
 
 /* Maximise the log marginal likelihood over theta in [ln lo, ln hi] with 1 + n_restarts bounded L-BFGS runs:
  * run 0 starts at theta0, run r>0 at starts[(r-1)*p .. ] (uniform draws in log-bounds made by the caller's RNG,
@@ -434,6 +458,23 @@ int hbegp_debug_dag_plan(int nblocks, int bk, int small_h, int nwg, int fine, in
  * gradmin.rs:35-60) through it and compare every point. */
 int hbegp_debug_lbfgs_replay(int n, const double* x0, const double* lo, const double* hi, int maxeval, int memory, int fixed_work,
                              int count, const double* f, const double* g, double* requested, int* n_requested);
+
+/* ---- test hook (host only, no GPU): the same replay, with the decision query a two-phase evaluation asks before it pays for a
+ * gradient (csrc/lbfgs_step.hpp: lbfgs_is_trial / lbfgs_trial_accepted).  Per evaluation i: trial[i] = it is a line-search trial,
+ * accepted[i] = the query's answer for f[i] before the state machine sees it, took[i] = lbfgs_advance then took its accepted
+ * branch (read the gradient).  accepted == took at every evaluation is what the fit relies on. */
+int hbegp_debug_lbfgs_decisions(int n, const double* x0, const double* lo, const double* hi, int maxeval, int memory, int fixed_work,
+                                int count, const double* f, const double* g, double* requested, int* trial, int* accepted, int* took,
+                                int* n_requested);
+
+/* ---- test hook (host only, no GPU): the queues of a task-queue evaluation.  which = 0: the full plan (K^-1 tiles included),
+ * 1: the plan without them (first phase of a lazily evaluated trial), 2: the full plan's K^-1 tasks alone, in its order (second
+ * phase).  nblocks .. fine as in hbegp_debug_dag_plan (bit 2 is implied by `which`; bit 5: the K^-1 sums of the top-left quadrant
+ * are not split in two, as in a fit with several slots), big128 as HBEGP_DAG_BIG128.  tasks (may be NULL)
+ * receives 6 ints per task -- kind, flags, row0, col0, kbeg, kend -- for the first cap tasks in queue order.  The queue is checked
+ * as in hbegp_debug_dag_plan. */
+int hbegp_debug_dag_queues(int nblocks, int bk, int small_h, int nwg, int fine, int big128, int which, int* ntasks, int* tasks, int cap,
+                           char* err, int errlen);
 
 /* ---- timing hook (tools/posterior_cov_bench.py): phase_ms[4] (may be NULL) receives the device time of the phases of the
  * calling thread's last timed hbegp_sample_posterior_* call -- Q (Kstar, mean, Q = Kstar L^-T), Sigma, its factor, the draws
