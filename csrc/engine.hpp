@@ -245,6 +245,17 @@ int kg_global_workgroups(int m, int mc);
 template <typename T>
 void launch_knowledge_gradient(const T* Sig, int ld, const T* mean, int m, int mc, const EvalParams* P, void* ws, double* kg, int* res,
                                T* var_out, hipStream_t s);
+// noisy expected improvement over a candidate set (hbegp_noisy_ei).  The baseline takes rows 0 .. mb - 1 of every
+// matrix, the candidates rows mbp .. mbp + mc - 1 (mbp = mb rounded up to NB).
+//   pad:    rows and columns mb .. mbp - 1 of Sigma's lower tiles W [ld][ld] become identity padding (nothing to do for mb = mbp)
+//   reduce: Sig = Sigma (its diagonal is read), LA = [L_b; A] (rows mbp .. of its first mb columns are read), Y [S][ld] the draw
+//           product, mean [ld].  Out (fp64): fmin_draws[S]; with mc > 0 rho[mc], nei[mc] and *best = the last index of the maximum of
+//           nei.  Nothing is written when *info != 0.
+template <typename T>
+void launch_nei_pad(T* W, int ld, int mb, int mbp, hipStream_t s);
+template <typename T>
+void launch_nei_reduce(const T* Sig, const T* LA, const T* Y, int ld, const T* mean, int mb, int mbp, int mc, int S, double* fmin_draws,
+                       double* rho, double* nei, int* best, const int* info, hipStream_t s);
 // batch expected improvement by Monte Carlo (hbegp_qei; qei_batch_kernel: one workgroup per batch of q points).  Rows b q .. b q + q - 1
 // of Xs [B q][d], Q [mp][np], mean, dmean [mp][d] and W [d][mp][np] (W and dmean are read only with want_grad); z [S][q] shared by
 // the batches; noise = 1e-5 + jitter.  Out: qei[B], grad[B q][d] (want_grad), info[B] (0, or 1 + the column whose pivot failed).

@@ -2305,6 +2305,125 @@ static int model_knowledge_gradient(hbegp_model* m, const T* Xs, int cnt, int mc
   return HBEGP_OK;
 }
 
+// phase times of the calling thread's last noisy-EI call (hbegp_debug_nei_phases): Sigma, baseline factor, products, reductions in ms
+static thread_local bool t_time_nei = false;
+static thread_local double t_nei_ms[4] = {0, 0, 0, 0};
+
+// Noisy expected improvement over a candidate set (hbegp_noisy_ei).  On the device the baseline rows come first,
+// padded to mbp (a multiple of NB) with copies of row 0, then the candidates, so that the baseline block of Sigma is whole
+// 128-blocks: Sigma's lower tiles as predict_cov builds them (posterior_sigma; all of them, the cc block's off-diagonal tiles too),
+// the gap turned into identity padding, then
+//   the fit's recursion with L kept on the leading nbb blocks only: L_b -> W3, X_b = L_b^-1 -> W2 (rows >= mbp of W1 are not touched)
+//   A = Sigma_cb X_b^T -> W3 below L_b (one tile GEMM of the recursion's TRSM shape)
+//   Y = Z [L_b; A]^T (one tile GEMM; Z [Sp][mbp] zero-padded)
+//   the reductions (kernels.hip: nei_*_kernel).
+// Only Sigma_bb is ever factored: the candidates may repeat.  Only S + 2 mc doubles and two ints leave the device, and nothing is
+// written when the factor fails; the work matrices are borrowed for the call and go back cleared.
+template <typename T>
+static int model_noisy_ei(hbegp_model* m, const T* Xs, int cnt, int mb, const T* z, int S, double jitter, double* nei, int* best,
+                          double* fmin_draws, double* rho, int* info_out) {
+  std::lock_guard<std::mutex> lock(m->mu);
+  HIPCHECK(hipSetDevice(m->dev));
+  const int mc = cnt - mb;
+  const int mbp = round_up(mb, NB);
+  const int rows = mc > 0 ? mbp + mc : mb;  // rows of the device copy of the points
+  const int mp = round_up(rows, NB);
+  const int Sp = round_up(S, NB);
+  const int nbb = mbp / NB;
+  // everything the call borrows, counted before anything is taken: an m far beyond the device is ENOMEM, not an overflow
+  const double need = (double)sizeof(T) * (2.0 * (double)mp * mp + (double)mbp * mp + (double)Sp * mbp + (double)Sp * mp + (double)mbp +
+                                           2.0 * (double)mp * m->np) + 8.0 * ((double)S + 2.0 * mc);
+  if (need > 1e15) return fail(HBEGP_ENOMEM, "the noisy expected improvement over %d points needs %.3g bytes of device memory", cnt, need);
+  std::vector<T> hx;  // declared before the scratch: it outlives the stream work
+  if (mc > 0 && mbp > mb) {
+    const size_t d = (size_t)m->d;
+    hx.resize((size_t)rows * d);
+    std::copy(Xs, Xs + (size_t)mb * d, hx.begin());
+    for (int g = mb; g < mbp; ++g) std::copy(Xs, Xs + d, hx.begin() + (size_t)g * d);
+    std::copy(Xs + (size_t)mb * d, Xs + (size_t)cnt * d, hx.begin() + (size_t)mbp * d);
+  }
+  predict_batched_reserve<T>(m, mp);
+  if (!m->dPcov) m->dPcov = static_cast<EvalParams*>(m->palloc(sizeof(EvalParams)));
+  hipStream_t s = m->stream;
+  int* info = &m->dOut->info;
+  const double noise = 1e-5 + jitter;  // as model_posterior (copied from here: outlives the stream work)
+  CallScratch ws{m->dev, s, {}};
+  T* W1 = static_cast<T*>(ws.get(sizeof(T) * (size_t)mp * mp));
+  T* W2 = static_cast<T*>(ws.get(sizeof(T) * (size_t)mbp * mp));  // X_b: the baseline's rows only
+  T* W3 = static_cast<T*>(ws.get(sizeof(T) * (size_t)mp * mp));
+  T* ld = static_cast<T*>(ws.get(sizeof(T) * (size_t)mbp));
+  T* Z = static_cast<T*>(ws.get(sizeof(T) * (size_t)Sp * mbp));
+  T* Y = static_cast<T*>(ws.get(sizeof(T) * (size_t)Sp * mp));
+  double* dfmin = static_cast<double*>(ws.get(sizeof(double) * ((size_t)S + 2 * (size_t)mc)));
+  double* drho = dfmin + S;
+  double* dnei = drho + mc;
+  int* dbest = static_cast<int*>(ws.get(sizeof(int)));
+  hipEvent_t ev[5] = {};
+  const bool timed = t_time_nei;
+  if (timed)
+    for (auto& e : ev) HIPCHECK(hipEventCreate(&e));
+  if (timed) HIPCHECK(hipEventRecord(ev[0], s));
+  posterior_sigma<T>(m, hx.empty() ? Xs : hx.data(), rows, mp, &noise, W1, nullptr);
+  if (mc > 0) launch_nei_pad<T>(W1, mp, mb, mbp, s);  // without candidates kmat's own identity padding follows the baseline
+  if (timed) HIPCHECK(hipEventRecord(ev[1], s));
+  // triangular operands must be zero above the diagonal in memory, and a recycled block holds its earlier owner's numbers
+  HIPCHECK(hipMemsetAsync(W2, 0, sizeof(T) * (size_t)mbp * mp, s));
+  HIPCHECK(hipMemsetAsync(W3, 0, sizeof(T) * (size_t)mp * mp, s));
+  chol_inv_rec<T>(W1, W2, W3, mp, 0, nbb / 2, nbb, false, true, [&](GemmLaunch& g, int) { gemm_adhoc<T>(g, info, s); },
+                  [&](int k) { launch_leaf_keep<T>(W1, W2, W3, mp, k, ld, info, s); });
+  if (timed) HIPCHECK(hipEventRecord(ev[2], s));
+  if (mp > mbp) {
+    // A = Sigma_cb X_b^T below L_b  (X_b lower: k <= j)
+    GemmLaunch g{};
+    g.nops = 1;
+    GemmOp& op = g.op[0];
+    op.A = W1; op.B = W2; op.C = W3;
+    op.lda = mp; op.ldb = mp; op.ldc = mp;
+    op.ci0 = nbb; op.mi = mp / NB - nbb; op.cj0 = 0; op.nj = nbb;
+    op.k0 = 0; op.k1 = nbb; op.klim = 1; op.maskB = 1;
+    gemm_adhoc<T>(g, info, s);
+  }
+  HIPCHECK(hipMemsetAsync(Z, 0, sizeof(T) * (size_t)Sp * mbp, s));
+  HIPCHECK(hipMemcpy2DAsync(Z, sizeof(T) * mbp, z, sizeof(T) * mb, sizeof(T) * mb, S, hipMemcpyHostToDevice, s));
+  {
+    // Y = Z [L_b; A]^T: Y[s][i] = sum_k z_s[k] W3[i][k] over the baseline's columns (L_b lower: k <= j inside its block range)
+    GemmLaunch g{};
+    g.nops = 1;
+    GemmOp& op = g.op[0];
+    op.A = Z; op.B = W3; op.C = Y;
+    op.lda = mbp; op.ldb = mp; op.ldc = mp;
+    op.mi = Sp / NB; op.nj = mp / NB;
+    op.k0 = 0; op.k1 = nbb; op.klim = 1; op.maskB = 1;
+    gemm_adhoc<T>(g, info, s);
+  }
+  if (timed) HIPCHECK(hipEventRecord(ev[3], s));
+  launch_nei_reduce<T>(W1, W3, Y, mp, static_cast<const T*>(m->mean), mb, mbp, mc, S, dfmin, drho, dnei, dbest, info, s);
+  if (timed) HIPCHECK(hipEventRecord(ev[4], s));
+  CHECK_LAUNCHES();
+  EvalOut out;
+  HIPCHECK(hipMemcpyAsync(&out, m->dOut, sizeof(EvalOut), hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
+  if (timed) {
+    for (int i = 0; i < 4; ++i) {
+      float ms = 0;
+      HIPCHECK(hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
+      t_nei_ms[i] = ms;
+    }
+    for (auto& e : ev) (void)hipEventDestroy(e);
+  }
+  if (info_out) *info_out = out.info;
+  if (out.info != 0) return fail(HBEGP_NOT_PD, "the baseline block of Sigma is not positive definite (pivot panel at column %d); a larger "
+                                 "jitter may help", out.info - 1);
+  int b = -1;
+  if (mc > 0) HIPCHECK(hipMemcpyAsync(nei, dnei, sizeof(double) * (size_t)mc, hipMemcpyDeviceToHost, s));
+  if (mc > 0 && best) HIPCHECK(hipMemcpyAsync(&b, dbest, sizeof(int), hipMemcpyDeviceToHost, s));
+  if (mc > 0 && rho) HIPCHECK(hipMemcpyAsync(rho, drho, sizeof(double) * (size_t)mc, hipMemcpyDeviceToHost, s));
+  if (fmin_draws) HIPCHECK(hipMemcpyAsync(fmin_draws, dfmin, sizeof(double) * (size_t)S, hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
+  if (best) *best = b;
+  return HBEGP_OK;
+}
+
 // Expected improvement of acquisition.rs:141-171 (estimator.expected_improvement) at mean mu and variance var, and its gradient
 // from the posterior gradients: dEI = -Phi(z) dmu + phi(z) dsigma, dsigma = dvar / (2 sigma); sigma = 0: -dmu where mu < fmin.
 static double ei_with_gradient(double mu, double var, const double* dmu, const double* dvar, double fmin, int d, double* g) {
@@ -4113,6 +4232,40 @@ int hbegp_debug_kg_phases(int enable, double* phase_ms) {
   if (phase_ms)
     for (int i = 0; i < 2; ++i) phase_ms[i] = t_kg_ms[i];
   t_time_kg = enable != 0;
+  return HBEGP_OK;
+}
+}  // extern "C"
+
+// argument checks of hbegp_noisy_ei_*: everything is refused before any device call, the checks that need no model first
+template <typename T>
+static int check_nei(hbegp_model* model, const T* Xs, int m, int mb, const T* z, int S, double jitter, const double* nei) {
+  if (m < 1) return fail(HBEGP_EINVAL, "m must be >= 1 (got %d): without a baseline there is no incumbent", m);
+  if (mb < 1) return fail(HBEGP_EINVAL, "mb must be >= 1 (got %d)", mb);
+  if (mb > m) return fail(HBEGP_EINVAL, "mb must be <= m (got mb = %d, m = %d)", mb, m);
+  if (S < 1) return fail(HBEGP_EINVAL, "S must be >= 1 (got %d)", S);
+  if (!z) return fail(HBEGP_EINVAL, "z is NULL");
+  if (m > mb && !nei) return fail(HBEGP_EINVAL, "nei is NULL");
+  return check_posterior<T>(model, Xs, m, jitter);
+}
+extern "C" {
+int hbegp_noisy_ei_f64(hbegp_model* model, const double* Xs, int m, int mb, const double* z, int S, double jitter, double* nei, int* best,
+                       double* fmin_draws, double* rho, int* info) {
+  if (int rc = check_nei<double>(model, Xs, m, mb, z, S, jitter, nei)) return rc;
+  GUARD_BEGIN
+  return model_noisy_ei<double>(model, Xs, m, mb, z, S, jitter, nei, best, fmin_draws, rho, info);
+  GUARD_END
+}
+int hbegp_noisy_ei_f32(hbegp_model* model, const float* Xs, int m, int mb, const float* z, int S, double jitter, double* nei, int* best,
+                       double* fmin_draws, double* rho, int* info) {
+  if (int rc = check_nei<float>(model, Xs, m, mb, z, S, jitter, nei)) return rc;
+  GUARD_BEGIN
+  return model_noisy_ei<float>(model, Xs, m, mb, z, S, jitter, nei, best, fmin_draws, rho, info);
+  GUARD_END
+}
+int hbegp_debug_nei_phases(int enable, double* phase_ms) {
+  if (phase_ms)
+    for (int i = 0; i < 4; ++i) phase_ms[i] = t_nei_ms[i];
+  t_time_nei = enable != 0;
   return HBEGP_OK;
 }
 int hbegp_debug_posterior_phases(int enable, double* phase_ms) {

@@ -2629,6 +2629,151 @@ template void launch_knowledge_gradient<float>(const float*, int, const float*, 
                                                hipStream_t);
 
 // =================================================================================================================
+// noisy expected improvement over a candidate set (hbegp.cpp: model_noisy_ei).  The tile products around these
+// kernels leave Sigma's lower tiles in W1, L_b (the factor of the baseline block alone) with A = Sigma_cb L_b^-T below it in W3, and
+// Y = Z [L_b; A]^T [S][ld].  The baseline takes rows 0 .. mb - 1, the candidates rows mbp .. mbp + mc - 1 (mbp = mb rounded up to NB).
+//   nei_pad_kernel:      rows and columns mb .. mbp - 1 of Sigma (a copy of row 0 stands there) become identity padding, so that the
+//                        baseline's 128-blocks factor as a matrix of their own; one workgroup per gap index
+//   nei_fmin_kernel:     one workgroup per draw s: fmin_s = min_{i < mb} (mean_i + Y[s][i]) in fp64; every thread scans its entries in
+//                        ascending i, then a fixed tree (a NaN never replaces a number, as in sample_epilogue_kernel)
+//   nei_rho_kernel:      one wave per candidate j: rho_j = max(Sigma_jj - sum_{k < mb} A_jk^2, 0), lanes along k, fp64, a fixed
+//                        shuffle tree
+//   nei_kernel:          NEI_JL lanes along j (the reads of Y coalesce) times NEI_SG groups along s: group g adds
+//                        EI(mean_j + Y[s][j], rho_j, fmin_s) for s = g, g + NEI_SG, .. in ascending s, then the groups' sums are added
+//                        in ascending g and divided by S
+//   nei_best_kernel:     the LAST index of the maximum of nei (Rust's max_by), a fixed LDS tree
+// No atomics anywhere: the same inputs give the same bits.  All but the padding return at once when `info` is set.
+// =================================================================================================================
+constexpr int NEI_THREADS = 256;
+constexpr int NEI_JL = 32;
+constexpr int NEI_SG = NEI_THREADS / NEI_JL;
+
+template <typename T>
+__global__ void __launch_bounds__(NEI_THREADS) nei_pad_kernel(T* __restrict__ W, int ld, int mb, int mbp) {
+  const int g = mb + blockIdx.x;
+  for (int t = threadIdx.x; t < ld; t += NEI_THREADS) {
+    if (t < mbp) W[(size_t)g * ld + t] = t == g ? T(1) : T(0);
+    // column g in the lower tiles: the diagonal block's rows above the gap, and every row below the baseline (the gap's own rows
+    // are written by their workgroups' row loops)
+    if ((t >= mbp - NB && t < mb) || t >= mbp) W[(size_t)t * ld + g] = T(0);
+  }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(NEI_THREADS) nei_fmin_kernel(const T* __restrict__ Y, int ld, const T* __restrict__ mean, int mb,
+                                                               double* __restrict__ fmin_out, const int* info) {
+  if (*info != 0) return;
+  __shared__ double sv[NEI_THREADS];
+  __shared__ int sh[NEI_THREADS];
+  const int t = threadIdx.x;
+  const T* y = Y + (size_t)blockIdx.x * ld;
+  double best = 0.0;
+  int have = 0;
+  for (int i = t; i < mb; i += NEI_THREADS) {
+    const double v = (double)y[i] + (double)mean[i];
+    if (!have || v < best) { best = v; have = 1; }
+  }
+  sv[t] = best;
+  sh[t] = have;
+  __syncthreads();
+  for (int w = NEI_THREADS / 2; w > 0; w >>= 1) {
+    if (t < w && sh[t + w] && (!sh[t] || sv[t + w] < sv[t])) { sv[t] = sv[t + w]; sh[t] = 1; }
+    __syncthreads();
+  }
+  if (t == 0) fmin_out[blockIdx.x] = sv[0];
+}
+
+template <typename T>
+__global__ void __launch_bounds__(NEI_THREADS) nei_rho_kernel(const T* __restrict__ Sig, const T* __restrict__ A, int ld, int mb, int mbp,
+                                                              int mc, double* __restrict__ rho, const int* info) {
+  if (*info != 0) return;
+  const int lane = threadIdx.x & 63;
+  const int j = blockIdx.x * (NEI_THREADS / 64) + (threadIdx.x >> 6);
+  if (j >= mc) return;  // whole waves leave: the shuffles below see full waves
+  const T* a = A + (size_t)(mbp + j) * ld;
+  double acc = 0.0;
+  for (int k = lane; k < mb; k += 64) {
+    const double v = (double)a[k];
+    acc += v * v;
+  }
+  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+  if (lane == 0) rho[j] = fmax((double)Sig[(size_t)(mbp + j) * ld + mbp + j] - acc, 0.0);
+}
+
+template <typename T>
+__global__ void __launch_bounds__(NEI_THREADS) nei_kernel(const T* __restrict__ Y, int ld, int mbp, const T* __restrict__ mean,
+                                                          const double* __restrict__ rho, const double* __restrict__ fmin_draws, int mc,
+                                                          int S, double* __restrict__ nei, const int* info) {
+  if (*info != 0) return;
+  __shared__ double part[NEI_SG][NEI_JL];
+  const int l = threadIdx.x % NEI_JL, g = threadIdx.x / NEI_JL;
+  const int j = blockIdx.x * NEI_JL + l;
+  double acc = 0.0;
+  if (j < mc) {
+    const double mu = (double)mean[mbp + j], r = rho[j];
+    const T* y = Y + mbp + j;
+#pragma unroll 1
+    for (int s = g; s < S; s += NEI_SG) acc += bsel_ei(mu + (double)y[(size_t)s * ld], r, fmin_draws[s]);
+  }
+  part[g][l] = acc;
+  __syncthreads();
+  if (g == 0 && j < mc) {
+    double sum = 0.0;
+    for (int q = 0; q < NEI_SG; ++q) sum += part[q][l];
+    nei[j] = sum / (double)S;
+  }
+}
+
+__global__ void __launch_bounds__(BSEL_THREADS) nei_best_kernel(const double* __restrict__ nei, int mc, int* __restrict__ best_out,
+                                                                const int* info) {
+  if (*info != 0) return;
+  __shared__ double sv[BSEL_THREADS];
+  __shared__ int si[BSEL_THREADS];
+  const int tid = threadIdx.x;
+  double best = 0.0;
+  int bi = -1;
+  for (int i = tid; i < mc; i += BSEL_THREADS) {
+    const double e = nei[i];
+    if (bi < 0 || e >= best) { best = e; bi = i; }  // ascending i: an equal value moves to the later index
+  }
+  sv[tid] = best;
+  si[tid] = bi;
+  __syncthreads();
+#pragma unroll 1
+  for (int w = BSEL_THREADS / 2; w > 0; w >>= 1) {
+    if (tid < w) {
+      const double o = sv[tid + w];
+      const int oi = si[tid + w];
+      if (oi >= 0 && (si[tid] < 0 || o > sv[tid] || (o == sv[tid] && oi > si[tid]))) { sv[tid] = o; si[tid] = oi; }
+    }
+    __syncthreads();
+  }
+  if (tid == 0) *best_out = si[0];
+}
+
+template <typename T>
+void launch_nei_pad(T* W, int ld, int mb, int mbp, hipStream_t s) {
+  if (mbp > mb) hipLaunchKernelGGL((nei_pad_kernel<T>), dim3(mbp - mb), dim3(NEI_THREADS), 0, s, W, ld, mb, mbp);
+}
+template <typename T>
+void launch_nei_reduce(const T* Sig, const T* LA, const T* Y, int ld, const T* mean, int mb, int mbp, int mc, int S, double* fmin_draws,
+                       double* rho, double* nei, int* best, const int* info, hipStream_t s) {
+  hipLaunchKernelGGL((nei_fmin_kernel<T>), dim3(S), dim3(NEI_THREADS), 0, s, Y, ld, mean, mb, fmin_draws, info);
+  if (mc <= 0) return;
+  constexpr int per = NEI_THREADS / 64;
+  hipLaunchKernelGGL((nei_rho_kernel<T>), dim3((mc + per - 1) / per), dim3(NEI_THREADS), 0, s, Sig, LA, ld, mb, mbp, mc, rho, info);
+  hipLaunchKernelGGL((nei_kernel<T>), dim3((mc + NEI_JL - 1) / NEI_JL), dim3(NEI_THREADS), 0, s, Y, ld, mbp, mean, rho, fmin_draws, mc, S,
+                     nei, info);
+  hipLaunchKernelGGL(nei_best_kernel, dim3(1), dim3(BSEL_THREADS), 0, s, nei, mc, best, info);
+}
+template void launch_nei_pad<double>(double*, int, int, int, hipStream_t);
+template void launch_nei_pad<float>(float*, int, int, int, hipStream_t);
+template void launch_nei_reduce<double>(const double*, const double*, const double*, int, const double*, int, int, int, int, double*, double*,
+                                        double*, int*, const int*, hipStream_t);
+template void launch_nei_reduce<float>(const float*, const float*, const float*, int, const float*, int, int, int, int, double*, double*,
+                                       double*, int*, const int*, hipStream_t);
+
+// =================================================================================================================
 // batch expected improvement by Monte Carlo (hbegp.cpp: model_qei).  One workgroup per batch b of q points
 // (rows b q .. b q + q - 1 of the batched predict's Q [mp][np], mean, dmean [mp][d] and W [d][mp][np]):
 //   Sigma = K** + noise I - Q_b Q_b^T   (fp64: K** from the points, q (q+1) / 2 wave dots over np, ascending lane stride)

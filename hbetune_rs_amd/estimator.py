@@ -325,6 +325,17 @@ class SurrogateModelGPR:
         _, _, imin, mean, _ = self.fitted.knowledge_gradient(np.asarray(x, dtype=self.dtype), n_candidates=0, want_posterior=True)
         return imin, self.y_norm.project_location_from_normalized(mean[imin:imin + 1])[0]
 
+    # Noisy expected improvement over a candidate set (opt-in; nothing the estimator suggests by default uses it).
+    def noisy_ei_a(self, x, n_samples, rng, baseline=None, jitter=0.0, max_baseline=None):
+        """Noisy EI of the rows of x [mc, d] (FittedKernel.noisy_ei): EI averaged over n_samples joint posterior draws of the latent
+        function at the baseline, each with its own incumbent, so no fmin is needed.  The baseline defaults to the model's training
+        rows; with max_baseline only its rows of lowest posterior mean are kept (deterministic: no random numbers).  z
+        [n_samples, mb] comes from rng.standard_normal.  NEI is returned in the NORMALISED y space, as knowledge_gradient_a returns
+        KG.  Returns (nei[mc] float64, best): best the last index of the maximum of nei, -1 without candidates."""
+        b = _nei_baseline(self.fitted, baseline, max_baseline, self.dtype)
+        z = rng.standard_normal((int(n_samples), b.shape[0])).astype(self.dtype)
+        return self.fitted.noisy_ei(b, np.asarray(x, dtype=self.dtype), z, jitter=jitter)
+
     # Batch expected improvement by Monte Carlo (opt-in; nothing the estimator suggests by default uses it).
     def qei_a(self, x, fmin, n_samples, rng, jitter=0.0, want_grad=True):
         """q-EI of batches x [B, q, d] (or [q, d]) in the normalised space (FittedKernel.qei), fmin projected as predict_mean_ei_a
@@ -513,6 +524,73 @@ def acquire_by_knowledge_gradient(candidates, model, k, n_candidates=None, ctx=N
             fk.release()
     means = np.array(means, dtype=model.dtype)
     return np.array(idx, dtype=np.int64), model.y_norm.project_location_from_normalized(means), np.array(kgs, dtype=np.float64)
+
+
+def _nei_baseline(fk, baseline, max_baseline, dtype):
+    """The baseline of a noisy-EI call: `baseline` or the model's training rows; with max_baseline the rows of lowest posterior
+    mean under fk (ties to the lower index), kept in their order."""
+    b = fk.x_train if baseline is None else baseline
+    if b is None:
+        raise ValueError("the model does not hold its training rows: pass a baseline")
+    b = np.asarray(b, dtype=dtype)
+    if b.ndim != 2 or b.shape[0] < 1:
+        raise ValueError("the baseline must be [mb >= 1, n_features]")
+    if max_baseline is not None:
+        if int(max_baseline) < 1:
+            raise ValueError("max_baseline must be >= 1")
+        if b.shape[0] > int(max_baseline):
+            mean, _, _ = fk.predict(b, want_variance=False)
+            b = b[np.sort(np.argsort(mean, kind="stable")[:int(max_baseline)])]
+    return b
+
+
+def acquire_by_noisy_ei(candidates, model, k, rng, n_samples=256, baseline=None, jitter=0.0, max_baseline=None, ctx=None):
+    """Batch acquisition for a noisy objective by noisy EI over a candidate set [m, n_features]: k distinct rows, each the row of
+    largest noisy EI (FittedKernel.noisy_ei; the incumbent is the minimum of a joint posterior draw at the baseline, not a
+    plugged-in number).  The baseline defaults to the model's training rows, cut to the max_baseline rows of lowest posterior mean
+    when that is given.  After a pick the surrogate is conditioned on the kriging-believer fantasy (x_pick, its posterior mean)
+    through extend_with at the same theta, as acquire_by_knowledge_gradient does, and the picked point joins the baseline.  The
+    normals z [n_samples, mb] come from rng.standard_normal once and are reused while the baseline keeps its size (max_baseline);
+    otherwise they are drawn again.  k = 1 is noisy_ei_a's best.  Returns (idx[k] int64, the projected means of the picks at the
+    time they were picked, nei[k] in the normalised space).  Opt-in: nothing the estimator suggests by default calls it."""
+    c = np.asarray(candidates, dtype=model.dtype)
+    if c.ndim != 2:
+        raise ValueError("candidates must be [m, n_features]")
+    k = int(k)
+    if not 0 <= k <= c.shape[0]:
+        raise ValueError("k must lie in [0, number of candidates]")
+    fk = model.fitted
+    X, y = fk.x_train, fk.y_train
+    if k > 1 and (X is None or y is None):
+        raise ValueError("the model does not hold its training rows: it cannot be conditioned on a fantasy")
+    base = None if k == 0 else np.asarray(fk.x_train if baseline is None else baseline, dtype=model.dtype)
+    avail = list(range(c.shape[0]))
+    idx, means, neis = [], [], []
+    z = None
+    try:
+        for t in range(k):
+            b = _nei_baseline(fk, base, max_baseline, model.dtype)
+            if z is None or z.shape[1] != b.shape[0]:
+                z = rng.standard_normal((int(n_samples), b.shape[0])).astype(model.dtype)
+            nei, best = fk.noisy_ei(b, c[avail], z, jitter=jitter)
+            j = avail.pop(best)
+            mean, _, _ = fk.predict(c, want_variance=False)  # the batched predict of every row, as predict_mean_a runs it
+            idx.append(j)
+            means.append(mean[j])
+            neis.append(nei[best])
+            if t + 1 < k:
+                X = np.vstack([X, c[j:j + 1]])
+                y = np.concatenate([y, mean[j:j + 1]])
+                base = np.vstack([base, c[j:j + 1]])
+                nxt = fk.extend_with(X, y, ctx=ctx)
+                if fk is not model.fitted:
+                    fk.release()
+                fk = nxt
+    finally:
+        if fk is not model.fitted:
+            fk.release()
+    means = np.array(means, dtype=model.dtype)
+    return np.array(idx, dtype=np.int64), model.y_norm.project_location_from_normalized(means), np.array(neis, dtype=np.float64)
 
 
 def acquire_by_qei(candidates, model, q, fmin, rng, n_samples=512, n_restarts=8, maxeval=150, jitter=0.0):

@@ -454,6 +454,34 @@ class FittedKernel:
             return kg, best.value, imin.value, mean, var
         return kg, best.value, imin.value
 
+    def noisy_ei(self, baseline, candidates, z, jitter=0.0, want_details=False):
+        """Noisy expected improvement over a candidate set (hbegp_noisy_ei_*; Letham et al. 2019), in the normalised y space: EI
+        of every row of candidates [mc, d] averaged over the S joint posterior draws of the latent function at baseline [mb, d]
+        that the caller's standard normals z [S, mb] select, each draw with its own incumbent and its own conditioned belief about
+        the candidate.  It needs no fmin.  Only the baseline's covariance is factored: candidates may repeat.  Returns
+        (nei[mc] float64, best): best the last index of the maximum of nei, -1 without candidates.  With want_details also
+        (fmin_draws[S], rho[mc]): each draw's incumbent and the candidates' variance given the baseline's latent values.  Raises
+        HbegpError with code NOT_PD when the baseline's covariance is not positive definite (retry with a larger jitter)."""
+        lib = _lib.load()
+        b = _lib.as_c(np.atleast_2d(baseline), self.dtype)
+        assert b.ndim == 2 and b.shape[1] == self.d
+        c = np.asarray(candidates, dtype=self.dtype).reshape(-1, self.d)
+        mb, mc = b.shape[0], c.shape[0]
+        x = _lib.as_c(np.vstack([b, c]), self.dtype)
+        z = _lib.as_c(np.atleast_2d(z), self.dtype)
+        assert z.ndim == 2 and z.shape[1] == mb, (z.shape, mb)
+        S = z.shape[0]
+        nei = np.zeros(mc)
+        best = C.c_int(-1)
+        fmin_draws = np.zeros(S) if want_details else None
+        rho = np.zeros(mc) if want_details else None
+        fn = getattr(lib, f"hbegp_noisy_ei_{self._sfx}")
+        _lib.check(fn(self._h, _lib.aptr(x), mb + mc, mb, _lib.aptr(z), S, float(jitter), _lib.dptr(nei), C.byref(best),
+                      _lib.dptr(fmin_draws), _lib.dptr(rho), None))
+        if want_details:
+            return nei, best.value, fmin_draws, rho
+        return nei, best.value
+
     def qei(self, x, z, fmin_normalized, jitter=0.0, want_grad=True, raise_not_pd=False):
         """Batch expected improvement by Monte Carlo (hbegp_qei_*) in the normalised y space: x [B, q, d] (or [q, d]: B = 1) batches
         of q points, z [S, q] the caller's standard normals, shared by every batch.  Returns (qei[B], grad[B, q, d] or None,

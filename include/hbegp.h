@@ -352,6 +352,31 @@ int hbegp_knowledge_gradient_f64(hbegp_model* model, const double* Xs, int m, in
 int hbegp_knowledge_gradient_f32(hbegp_model* model, const float* Xs, int m, int mc, double* kg, int* best, int* imin,
                                  float* mean_out, float* var_out);
 
+/* Noisy expected improvement over a candidate set (Letham, Karrer, Ottoni, Bakshy 2019), in the normalised y space like
+ * hbegp_predict_*: EI averaged over joint posterior draws of the latent function at the BASELINE, each draw with its own incumbent
+ * and its own conditioned belief about the candidate.  It needs no fmin.  Xs[m*d]: the first mb rows are the baseline (normally the
+ * training rows), the other mc = m - mb rows the candidates; z[S*mb] the CALLER's standard normals, one row per draw (the RNG stays
+ * on the caller side).  With mu and Sigma of hbegp_predict_cov for the m rows at the same jitter, split into b and c parts:
+ *   L_b = chol(Sigma_bb), lower;   A = Sigma_cb L_b^-T;   rho_j = max(Sigma_jj - sum_k A_jk^2, 0)
+ *   draw s:  f_s = mu_b + L_b z_s,   fmin_s = min_i f_s,i,   mu_js = mu_j + A_j . z_s
+ *   nei[j] = (1/S) sum_s EI(mu_js, sqrt(rho_j), fmin_s) >= 0
+ * with EI of acquisition.rs:141-171 (its std == 0 branch included): the exact expectation over f(x_j) given each draw of the
+ * baseline, no inner sampling.  Sigma, L_b, A and the two products with z are in the element type like hbegp_sample_posterior_*; the
+ * sums of squares for rho, every EI, the minima and the averages are fp64 in a fixed order without atomics, so nei is double.
+ * Only Sigma_bb is factored, the candidates never: identical candidates are as fine as distinct ones.  HBEGP_NOT_PD is decided
+ * by Sigma_bb alone, with *info = 1 + the first column of the failing 16-column panel as hbegp_sample_posterior_* reports it; then
+ * no other output is written.  The library never raises the jitter by itself.
+ * nei[mc] (required for mc > 0); best (may be NULL): the LAST index of the maximum of nei, as hbegp_knowledge_gradient_* (-1 for
+ * mc = 0); fmin_draws[S] (may be NULL): fmin_s; rho[mc] (may be NULL); info (may be NULL).  mc = 0 fills fmin_draws only.
+ * HBEGP_EINVAL (before any device call; a refused call writes nothing) for a NULL model, m < 1, mb < 1, mb > m, S < 1, a NULL z, a
+ * NULL nei with mc > 0, a jitter that is negative or not finite, a model of the other element type or a non-finite coordinate.
+ * Serialised per model like predict; the same call gives the same bits.  The work matrices (about 2.5 m_p^2 elements, m_p =
+ * round128(mb) + mc rounded up to 128) are borrowed for the call; work that does not fit in device memory is HBEGP_ENOMEM. */
+int hbegp_noisy_ei_f64(hbegp_model* model, const double* Xs, int m, int mb, const double* z, int S, double jitter, double* nei,
+                       int* best, double* fmin_draws, double* rho, int* info);
+int hbegp_noisy_ei_f32(hbegp_model* model, const float* Xs, int m, int mb, const float* z, int S, double jitter, double* nei,
+                       int* best, double* fmin_draws, double* rho, int* info);
+
 /* Batch expected improvement by Monte Carlo (q-EI) in the normalised y space like hbegp_predict_*, for B batches of q points:
  * Xb[B*q*d] (batch b = rows b*q .. b*q + q - 1, feature space), z[S*q] the CALLER's standard normals (draw s = row s), shared by
  * every batch (common random numbers; the RNG stays on the caller side).  Per batch b:
@@ -489,6 +514,11 @@ int hbegp_debug_batch_select_phases(int enable, double* phase_ms);
  * last timed hbegp_knowledge_gradient_* call -- Sigma (upload, K*, mean, Q, kmat, Q Q^T, mirror), kg (the per-candidate kernel and
  * the epilogue) -- in milliseconds; then enable != 0 makes this thread's later knowledge-gradient calls timed. */
 int hbegp_debug_kg_phases(int enable, double* phase_ms);
+/* ---- timing hook (tools/nei_bench.py): phase_ms[4] (may be NULL) receives the device time of the phases of the calling thread's
+ * last timed hbegp_noisy_ei_* call -- Sigma (upload, K*, mean, Q, kmat, Q Q^T, the padding), the baseline's factor, the panel and
+ * draw products (with the upload of z), the reductions -- in milliseconds; then enable != 0 makes this thread's later noisy-EI
+ * calls timed. */
+int hbegp_debug_nei_phases(int enable, double* phase_ms);
 /* ---- timing hook (tools/qei_bench.py): phase_ms[2] (may be NULL) receives the device time of the phases of the calling thread's
  * last timed hbegp_qei_* call -- the shared launches (upload of the points, Kstar, mean, Q; with a gradient dmean, G, W; upload of
  * z), the qEI kernel -- in milliseconds; then enable != 0 makes this thread's later qEI calls timed. */

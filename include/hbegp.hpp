@@ -65,6 +65,8 @@ template <> struct Abi<double> {
   static int knowledge_gradient(hbegp_model* m, const double* xs, int n, int mc, double* kg, int* best, int* imin, double* mean, double* var) {
     return hbegp_knowledge_gradient_f64(m, xs, n, mc, kg, best, imin, mean, var);
   }
+  static int noisy_ei(hbegp_model* m, const double* xs, int n, int mb, const double* z, int s, double j, double* nei, int* best, double* fmin,
+                      double* rho, int* info) { return hbegp_noisy_ei_f64(m, xs, n, mb, z, s, j, nei, best, fmin, rho, info); }
   static int qei(hbegp_model* m, const double* xb, int b, int q, const double* z, int s, double fmin, double j, double* v, double* g, int* info) {
     return hbegp_qei_f64(m, xb, b, q, z, s, fmin, j, v, g, info);
   }
@@ -106,6 +108,8 @@ template <> struct Abi<float> {
   static int knowledge_gradient(hbegp_model* m, const float* xs, int n, int mc, double* kg, int* best, int* imin, float* mean, float* var) {
     return hbegp_knowledge_gradient_f32(m, xs, n, mc, kg, best, imin, mean, var);
   }
+  static int noisy_ei(hbegp_model* m, const float* xs, int n, int mb, const float* z, int s, double j, double* nei, int* best, double* fmin,
+                      double* rho, int* info) { return hbegp_noisy_ei_f32(m, xs, n, mb, z, s, j, nei, best, fmin, rho, info); }
   static int qei(hbegp_model* m, const float* xb, int b, int q, const float* z, int s, double fmin, double j, double* v, float* g, int* info) {
     return hbegp_qei_f32(m, xb, b, q, z, s, fmin, j, v, g, info);
   }
@@ -217,6 +221,14 @@ class FittedKernel {
   void knowledge_gradient(const A* xs, int m, int mc, double* kg, int* best = nullptr, int* imin = nullptr, A* mean = nullptr,
                           A* var = nullptr) const {
     check(detail::Abi<A>::knowledge_gradient(h_, xs, m, mc, kg, best, imin, mean, var));
+  }
+  // noisy expected improvement of the candidates xs[mb*d ..] given S joint draws of the latent function at the baseline, the first mb
+  // rows of xs[m*d], from the caller's normals z[S*mb] (normalised y space): nei[m - mb]; best (the last index of the maximum of
+  // nei), fmin_draws[S], rho[m - mb] may be nullptr.  Only the baseline block is factored: throws Error(HBEGP_NOT_PD) when it does
+  // not factor (retry with a larger jitter)
+  void noisy_ei(const A* xs, int m, int mb, const A* z, int S, double* nei, int* best = nullptr, double* fmin_draws = nullptr,
+                double* rho = nullptr, double jitter = 0.0) const {
+    check(detail::Abi<A>::noisy_ei(h_, xs, m, mb, z, S, jitter, nei, best, fmin_draws, rho, nullptr));
   }
   // Monte Carlo q-EI of B batches xb[B*q*d] with the caller's normals z[S*q]: qei[B]; grad[B*q*d] and info[B] may be nullptr.
   // Returns HBEGP_OK or HBEGP_NOT_PD (some batch's Sigma did not factor: its qei is NaN, info says where); throws otherwise

@@ -151,6 +151,14 @@ extern "C" {
         model: *mut HbegpModel, xs: *const c_float, m: c_int, mc: c_int, kg: *mut c_double, best: *mut c_int, imin: *mut c_int,
         mean_out: *mut c_float, var_out: *mut c_float,
     ) -> c_int;
+    fn hbegp_noisy_ei_f64(
+        model: *mut HbegpModel, xs: *const c_double, m: c_int, mb: c_int, z: *const c_double, s: c_int, jitter: c_double,
+        nei: *mut c_double, best: *mut c_int, fmin_draws: *mut c_double, rho: *mut c_double, info: *mut c_int,
+    ) -> c_int;
+    fn hbegp_noisy_ei_f32(
+        model: *mut HbegpModel, xs: *const c_float, m: c_int, mb: c_int, z: *const c_float, s: c_int, jitter: c_double,
+        nei: *mut c_double, best: *mut c_int, fmin_draws: *mut c_double, rho: *mut c_double, info: *mut c_int,
+    ) -> c_int;
     fn hbegp_qei_f64(
         model: *mut HbegpModel, xb: *const c_double, b: c_int, q: c_int, z: *const c_double, s: c_int, fmin_normalized: c_double,
         jitter: c_double, qei: *mut c_double, grad: *mut c_double, info: *mut c_int,
@@ -251,6 +259,12 @@ pub trait GpuScalar: Scalar + sealed::Sealed {
         model: *mut HbegpModel, xs: *const Self, m: c_int, mc: c_int, kg: *mut f64, best: *mut c_int, imin: *mut c_int,
         mean_out: *mut Self, var_out: *mut Self,
     ) -> c_int;
+    /// `hbegp_noisy_ei_*`
+    #[allow(clippy::too_many_arguments)]
+    unsafe fn ffi_noisy_ei(
+        model: *mut HbegpModel, xs: *const Self, m: c_int, mb: c_int, z: *const Self, s: c_int, jitter: f64, nei: *mut f64,
+        best: *mut c_int, fmin_draws: *mut f64, rho: *mut f64, info: *mut c_int,
+    ) -> c_int;
     /// `hbegp_qei_*`
     unsafe fn ffi_qei(
         model: *mut HbegpModel, xb: *const Self, b: c_int, q: c_int, z: *const Self, s: c_int, fmin_normalized: f64, jitter: f64,
@@ -322,6 +336,12 @@ impl GpuScalar for f64 {
         mean_out: *mut f64, var_out: *mut f64,
     ) -> c_int {
         hbegp_knowledge_gradient_f64(model, xs, m, mc, kg, best, imin, mean_out, var_out)
+    }
+    unsafe fn ffi_noisy_ei(
+        model: *mut HbegpModel, xs: *const f64, m: c_int, mb: c_int, z: *const f64, s: c_int, jitter: f64, nei: *mut f64,
+        best: *mut c_int, fmin_draws: *mut f64, rho: *mut f64, info: *mut c_int,
+    ) -> c_int {
+        hbegp_noisy_ei_f64(model, xs, m, mb, z, s, jitter, nei, best, fmin_draws, rho, info)
     }
     unsafe fn ffi_qei(
         model: *mut HbegpModel, xb: *const f64, b: c_int, q: c_int, z: *const f64, s: c_int, fmin_normalized: f64, jitter: f64,
@@ -396,6 +416,12 @@ impl GpuScalar for f32 {
         mean_out: *mut f32, var_out: *mut f32,
     ) -> c_int {
         hbegp_knowledge_gradient_f32(model, xs, m, mc, kg, best, imin, mean_out, var_out)
+    }
+    unsafe fn ffi_noisy_ei(
+        model: *mut HbegpModel, xs: *const f32, m: c_int, mb: c_int, z: *const f32, s: c_int, jitter: f64, nei: *mut f64,
+        best: *mut c_int, fmin_draws: *mut f64, rho: *mut f64, info: *mut c_int,
+    ) -> c_int {
+        hbegp_noisy_ei_f32(model, xs, m, mb, z, s, jitter, nei, best, fmin_draws, rho, info)
     }
     unsafe fn ffi_qei(
         model: *mut HbegpModel, xb: *const f32, b: c_int, q: c_int, z: *const f32, s: c_int, fmin_normalized: f64, jitter: f64,
@@ -690,6 +716,40 @@ impl<A: GpuScalar> SurrogateModelGpu<A> {
             panic!("hbegp_knowledge_gradient failed: {}", last_error());
         }
         (kg, usize::try_from(best).ok(), usize::try_from(imin).ok())
+    }
+
+    /// Noisy expected improvement over a candidate set (`hbegp_noisy_ei_*`; Letham, Karrer, Ottoni, Bakshy 2019): EI of every row
+    /// of `candidates` averaged over the joint posterior draws of the latent function at `baseline` (normally the training rows)
+    /// that the caller's normals `z` [S, mb] select, each draw with its own incumbent and its own conditioned belief about the
+    /// candidate, in the normalised y space -- no fmin.  Only the baseline's covariance is factored, so candidates may repeat.
+    /// Returns `Ok((nei [mc], best = the last index of its maximum as `max_by`, None without candidates))`, or `Err(info)` when the
+    /// baseline's covariance does not factor (info = 1 + the first column of the failing panel; retry with a larger jitter).  Opt-in.
+    pub fn noisy_ei_normalized(&self, baseline: ArrayView2<A>, candidates: ArrayView2<A>, z: ArrayView2<A>, jitter: f64)
+        -> Result<(Vec<f64>, Option<usize>), c_int> {
+        let (mb, d) = baseline.dim();
+        let (mc, dc) = candidates.dim();
+        let (s, zc) = z.dim();
+        assert!(mb > 0 && zc == mb && (mc == 0 || dc == d), "z must be [S, mb] and the candidates must have the baseline's features");
+        let mut x = Array2::<A>::zeros((mb + mc, d));
+        x.slice_mut(ndarray::s![..mb, ..]).assign(&baseline);
+        if mc > 0 {
+            x.slice_mut(ndarray::s![mb.., ..]).assign(&candidates);
+        }
+        let z = z.as_standard_layout();
+        let mut nei = vec![0.0f64; mc];
+        let (mut best, mut info): (c_int, c_int) = (-1, 0);
+        let nei_ptr = if mc > 0 { nei.as_mut_ptr() } else { std::ptr::null_mut() };
+        let rc = unsafe {
+            A::ffi_noisy_ei(self.handle, x.as_ptr(), (mb + mc) as c_int, mb as c_int, z.as_ptr(), s as c_int, jitter, nei_ptr, &mut best,
+                            std::ptr::null_mut(), std::ptr::null_mut(), &mut info)
+        };
+        if rc == HBEGP_NOT_PD {
+            return Err(info);
+        }
+        if rc != HBEGP_OK {
+            panic!("hbegp_noisy_ei failed: {}", last_error());
+        }
+        Ok((nei, usize::try_from(best).ok()))
     }
 
     /// Monte Carlo q-EI (`hbegp_qei_*`) of `b` batches of q points, `xb` [b q, d] (batch i = rows i q .. i q + q - 1), with the
