@@ -218,6 +218,23 @@ void launch_kstar_grad(const T* Xs, int m, int mp, const T* X, int n, int d, int
 template <typename T>
 void launch_pred_dvar(const T* W, const T* Q, int m, int mp, int np, int d, const T* var, T* dvar, hipStream_t s);
 int pred_grad_chunks(int n);
+// sensitivity of the posterior mean (hbegp_sobol_* / hbegp_main_effects_*; kernels.hip: sens_kernel).  Xb holds
+// all base rows [.][d]; one call takes the slab of `rows` rows from r0 on.  Rows below nsub get every feature k substituted:
+//   G = 0 (per row):  by sub[i][k] (sub [nsub][d], unscaled)                -> fsub[k][i] (T, leading dimension nsub)
+//   G > 0 (per grid): by sg[k][0..G) (sub = sg [d][G] from launch_sens_scale_grid) -> chunk 0's slot of part, fp64, for
+//                     launch_sens_effect: eff[k][g] (zero before the first slab) += the slab's rows in ascending order, / N at `last`
+// The base value of every row of the slab -> fbase[r0 + row] (T).  part: sens_chunks(n) * rows * (1 + d * max(G, 1)) doubles.
+// ev_mid (may be null) is recorded between the evaluation and the chunk sums.
+// launch_sobol_reduce: fbase = [f_A | f_B] (N each), fsub = f_AB -> out = first[d], total[d], f0, V (fp64).
+int sens_chunks(int n);
+template <typename T>
+void launch_sens_eval(const T* Xb, int r0, int rows, int nsub, const T* sub, int G, const T* X, int n, int d, int nu2, const EvalParams* P,
+                      const T* alpha, double* part, T* fbase, T* fsub, hipStream_t s, hipEvent_t ev_mid = nullptr);
+template <typename T>
+void launch_sens_scale_grid(T* sg, int d, int G, const EvalParams* P, hipStream_t s);
+void launch_sens_effect(const double* part, int rows, int d, int G, double* eff, int N, int last, hipStream_t s);
+template <typename T>
+void launch_sobol_reduce(const T* fbase, const T* fsub, int N, int d, double* out, hipStream_t s);
 // joint posterior (hbegp_predict_cov / hbegp_sample_posterior): launch_leaf plus L_kk itself -> W3's block (lower, zeros above
 // the diagonal); then, per draw s (row s of Y [S][ld] = (L z_s)^T): Y[s][i] += mean[i] when `store`, amin[s] = argmin_i, ties
 // to the lowest index.  Both do nothing when *info != 0.

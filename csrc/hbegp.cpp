@@ -2424,6 +2424,123 @@ static int model_noisy_ei(hbegp_model* m, const T* Xs, int cnt, int mb, const T*
   return HBEGP_OK;
 }
 
+// phase times of the calling thread's last sensitivity call (hbegp_debug_sens_phases): upload, substituted means, chunk and row
+// sums, reduction and download in ms
+static thread_local bool t_time_sens = false;
+static thread_local double t_sens_ms[4] = {0, 0, 0, 0};
+// the chunk partial sums of one slab of base rows stay under this many bytes (one row's worth where a single row needs more)
+constexpr size_t SENS_PART_CAP = (size_t)128 << 20;
+
+// Sobol indices (G = 0: A, B [N][d] -> first, total, f0, variance and the optional f_a, f_b [N], f_ab [d][N]) and main-effect
+// curves (G > 0: A [N][d], grid [d][G] -> effect [d][G] and the optional f_a) of the posterior mean.  The base
+// rows (A, then B) go to the device once; they are evaluated in slabs of rows so that sens_kernel's chunk partial sums stay under
+// SENS_PART_CAP (HBEGP_SENS_SLAB_ROWS, read per call, forces a slab size: tests).  Every value depends on its own row only and
+// the row sums of the main effects continue from slab to slab in ascending row order, so the slab size never shows in a result.
+// No query matrix and no Kstar exist; everything is borrowed for the call and goes back cleared.
+template <typename T>
+static int model_sensitivity(hbegp_model* m, const T* A, const T* B, int N, const T* grid, int G, double* first, double* total, double* f0,
+                             double* variance, T* f_a, T* f_b, T* f_ab, double* effect) {
+  std::lock_guard<std::mutex> lock(m->mu);
+  HIPCHECK(hipSetDevice(m->dev));
+  const int d = m->d, nch = sens_chunks(m->n);
+  const bool sobol = G == 0;
+  const size_t mrows = (size_t)N * (sobol ? 2 : 1);
+  const size_t nv = 1 + (size_t)d * (sobol ? 1 : G);
+  const size_t row_bytes = sizeof(double) * (size_t)nch * nv;
+  size_t slab = std::max<size_t>(1, SENS_PART_CAP / row_bytes);
+  if (slab >= 4) slab = slab / 4 * 4;  // whole workgroups of four rows
+  const int forced = env_int("HBEGP_SENS_SLAB_ROWS", 0);
+  if (forced > 0) slab = (size_t)forced;
+  slab = std::min(slab, mrows);
+  // everything the call borrows, counted before anything is taken: an N or G far beyond the device is ENOMEM, not an overflow
+  const double need = (double)sizeof(T) * ((double)mrows * (d + 1) + (double)d * G + (sobol ? (double)d * N : 0.0)) +
+                      (double)row_bytes * (double)slab + 8.0 * (double)nv;
+  if (need > 1e15 || mrows > ((size_t)1 << 29) || nv > ((size_t)1 << 28) || mrows * d > ((size_t)1 << 40))
+    return fail(HBEGP_ENOMEM, "the sensitivity call over %d rows (G = %d) needs %.3g bytes of device memory", N, G, need);
+  hipStream_t s = m->stream;
+  CallScratch ws{m->dev, s, {}};
+  T* dXb = static_cast<T*>(ws.get(sizeof(T) * mrows * d));
+  T* dsub = sobol ? dXb + (size_t)N * d : static_cast<T*>(ws.get(sizeof(T) * (size_t)d * G));
+  double* part = static_cast<double*>(ws.get(row_bytes * slab));
+  T* fbase = static_cast<T*>(ws.get(sizeof(T) * mrows));
+  T* fsub = sobol ? static_cast<T*>(ws.get(sizeof(T) * (size_t)d * N)) : nullptr;
+  double* dres = static_cast<double*>(ws.get(sizeof(double) * (sobol ? (size_t)2 * d + 2 : (size_t)d * G)));
+  const bool timed = t_time_sens;
+  struct Events {  // destroyed however the call ends (a throwing HIPCHECK included)
+    std::vector<hipEvent_t> v;
+    ~Events() {
+      for (auto& e : v) (void)hipEventDestroy(e);
+    }
+  } evs;
+  std::vector<hipEvent_t>& ev = evs.v;
+  auto mark = [&]() -> hipEvent_t {
+    if (!timed) return nullptr;
+    hipEvent_t e;
+    HIPCHECK(hipEventCreate(&e));
+    ev.push_back(e);
+    return e;
+  };
+  auto record = [&]() {
+    if (hipEvent_t e = mark()) HIPCHECK(hipEventRecord(e, s));
+  };
+  record();
+  HIPCHECK(hipMemcpyAsync(dXb, A, sizeof(T) * (size_t)N * d, hipMemcpyHostToDevice, s));
+  if (sobol) {
+    HIPCHECK(hipMemcpyAsync(dsub, B, sizeof(T) * (size_t)N * d, hipMemcpyHostToDevice, s));
+  } else {
+    HIPCHECK(hipMemcpyAsync(dsub, grid, sizeof(T) * (size_t)d * G, hipMemcpyHostToDevice, s));
+    launch_sens_scale_grid<T>(dsub, d, G, m->dP, s);
+    HIPCHECK(hipMemsetAsync(dres, 0, sizeof(double) * (size_t)d * G, s));  // the row sums start from zero
+  }
+  record();
+  for (size_t r0 = 0; r0 < mrows; r0 += slab) {
+    const int rows = (int)std::min(slab, mrows - r0);
+    hipEvent_t mid = mark();
+    launch_sens_eval<T>(dXb, (int)r0, rows, N, dsub, G, static_cast<const T*>(m->X), m->n, d, m->nu2, m->dP, static_cast<const T*>(m->alpha),
+                        part, fbase, fsub, s, mid);
+    if (!sobol) launch_sens_effect(part, rows, d, G, dres, N, r0 + slab >= mrows, s);
+    record();
+  }
+  if (sobol) launch_sobol_reduce<T>(fbase, fsub, N, d, dres, s);
+  CHECK_LAUNCHES();
+  std::vector<double> res(sobol ? (size_t)2 * d + 2 : 0);
+  if (sobol) {
+    HIPCHECK(hipMemcpyAsync(res.data(), dres, sizeof(double) * res.size(), hipMemcpyDeviceToHost, s));
+    if (f_b) HIPCHECK(hipMemcpyAsync(f_b, fbase + N, sizeof(T) * (size_t)N, hipMemcpyDeviceToHost, s));
+    if (f_ab) HIPCHECK(hipMemcpyAsync(f_ab, fsub, sizeof(T) * (size_t)d * N, hipMemcpyDeviceToHost, s));
+  } else {
+    HIPCHECK(hipMemcpyAsync(effect, dres, sizeof(double) * (size_t)d * G, hipMemcpyDeviceToHost, s));
+  }
+  if (f_a) HIPCHECK(hipMemcpyAsync(f_a, fbase, sizeof(T) * (size_t)N, hipMemcpyDeviceToHost, s));
+  record();
+  HIPCHECK(hipStreamSynchronize(s));
+  if (sobol) {
+    for (int k = 0; k < d; ++k) {
+      first[k] = res[k];
+      total[k] = res[d + k];
+    }
+    if (f0) *f0 = res[2 * (size_t)d];
+    if (variance) *variance = res[2 * (size_t)d + 1];
+  }
+  if (timed) {
+    // events: start, uploaded, then (mid, end) per slab, then the end of the call
+    auto ms = [&](size_t a, size_t b) {
+      float v = 0;
+      HIPCHECK(hipEventElapsedTime(&v, ev[a], ev[b]));
+      return (double)v;
+    };
+    const size_t last = ev.size() - 1;
+    t_sens_ms[0] = ms(0, 1);
+    t_sens_ms[1] = t_sens_ms[2] = 0;
+    for (size_t i = 2; i + 1 < last; i += 2) {
+      t_sens_ms[1] += ms(i - 1, i);
+      t_sens_ms[2] += ms(i, i + 1);
+    }
+    t_sens_ms[3] = ms(last - 1, last);
+  }
+  return HBEGP_OK;
+}
+
 // Expected improvement of acquisition.rs:141-171 (estimator.expected_improvement) at mean mu and variance var, and its gradient
 // from the posterior gradients: dEI = -Phi(z) dmu + phi(z) dsigma, dsigma = dvar / (2 sigma); sigma = 0: -dmu where mu < fmin.
 static double ei_with_gradient(double mu, double var, const double* dmu, const double* dvar, double fmin, int d, double* g) {
@@ -4266,6 +4383,56 @@ int hbegp_debug_nei_phases(int enable, double* phase_ms) {
   if (phase_ms)
     for (int i = 0; i < 4; ++i) phase_ms[i] = t_nei_ms[i];
   t_time_nei = enable != 0;
+  return HBEGP_OK;
+}
+}  // extern "C"
+
+// argument checks of hbegp_sobol_* / hbegp_main_effects_*: everything is refused before any device call, the checks that need no
+// model first.  The sample rows are not screened: a NaN coordinate propagates to that row's values (include/hbegp.h).
+static int check_sens(hbegp_model* model, bool want_f32, const void* A, const void* second, const char* second_name, int N, int min_n,
+                      const void* out1, const char* out1_name, const void* out2, const char* out2_name) {
+  if (N < min_n) return fail(HBEGP_EINVAL, "N must be >= %d (got %d)", min_n, N);
+  if (!A) return fail(HBEGP_EINVAL, "A is NULL");
+  if (!second) return fail(HBEGP_EINVAL, "%s is NULL", second_name);
+  if (!out1) return fail(HBEGP_EINVAL, "%s is NULL", out1_name);
+  if (!out2) return fail(HBEGP_EINVAL, "%s is NULL", out2_name);
+  if (!model) return fail(HBEGP_EINVAL, "NULL model");
+  if (model->is_f32 != want_f32) return fail(HBEGP_EINVAL, "model holds %s data", model->is_f32 ? "f32" : "f64");
+  return HBEGP_OK;
+}
+extern "C" {
+int hbegp_sobol_f64(hbegp_model* model, const double* A, const double* B, int N, double* first, double* total, double* f0, double* variance,
+                    double* f_a, double* f_b, double* f_ab) {
+  if (int rc = check_sens(model, false, A, B, "B", N, 2, first, "first", total, "total")) return rc;
+  GUARD_BEGIN
+  return model_sensitivity<double>(model, A, B, N, nullptr, 0, first, total, f0, variance, f_a, f_b, f_ab, nullptr);
+  GUARD_END
+}
+int hbegp_sobol_f32(hbegp_model* model, const float* A, const float* B, int N, double* first, double* total, double* f0, double* variance,
+                    float* f_a, float* f_b, float* f_ab) {
+  if (int rc = check_sens(model, true, A, B, "B", N, 2, first, "first", total, "total")) return rc;
+  GUARD_BEGIN
+  return model_sensitivity<float>(model, A, B, N, nullptr, 0, first, total, f0, variance, f_a, f_b, f_ab, nullptr);
+  GUARD_END
+}
+int hbegp_main_effects_f64(hbegp_model* model, const double* A, int N, const double* grid, int G, double* effect, double* f_a) {
+  if (G < 1) return fail(HBEGP_EINVAL, "G must be >= 1 (got %d)", G);
+  if (int rc = check_sens(model, false, A, grid, "grid", N, 1, effect, "effect", effect, "effect")) return rc;
+  GUARD_BEGIN
+  return model_sensitivity<double>(model, A, nullptr, N, grid, G, nullptr, nullptr, nullptr, nullptr, f_a, nullptr, nullptr, effect);
+  GUARD_END
+}
+int hbegp_main_effects_f32(hbegp_model* model, const float* A, int N, const float* grid, int G, double* effect, float* f_a) {
+  if (G < 1) return fail(HBEGP_EINVAL, "G must be >= 1 (got %d)", G);
+  if (int rc = check_sens(model, true, A, grid, "grid", N, 1, effect, "effect", effect, "effect")) return rc;
+  GUARD_BEGIN
+  return model_sensitivity<float>(model, A, nullptr, N, grid, G, nullptr, nullptr, nullptr, nullptr, f_a, nullptr, nullptr, effect);
+  GUARD_END
+}
+int hbegp_debug_sens_phases(int enable, double* phase_ms) {
+  if (phase_ms)
+    for (int i = 0; i < 4; ++i) phase_ms[i] = t_sens_ms[i];
+  t_time_sens = enable != 0;
   return HBEGP_OK;
 }
 int hbegp_debug_posterior_phases(int enable, double* phase_ms) {

@@ -2231,6 +2231,264 @@ template void launch_pred_dvar<float>(const float*, const float*, int, int, int,
 int pred_grad_chunks(int n) { return (n + PG_CHUNK - 1) / PG_CHUNK; }
 
 // =================================================================================================================
+// sensitivity of the posterior mean: the mean at base rows with ONE coordinate substituted (hbegp_sobol_* /
+// hbegp_main_effects_*)
+//   mu(a | k <- s) = sum_j c phi(r_j) alpha_j,   r_j^2 = sum_{l != k} ((a_l - x_jl) / ell_l)^2 + ((s - x_jk) / ell_k)^2
+// No query matrix and no Kstar exist: for a pair (base row, training point) the squared differences of the features are formed
+// once per pass, a substituted point replaces one term of the sum, and only the Matern map and one FMA scale with the number of
+// substituted points.
+//
+// sens_kernel: pred_grad_kernel's shape -- grid (ceil(rows/4), ceil(n/SENS_CHUNK)); wave w of a workgroup is base row
+// 4 blockIdx.x + w of the slab, lane l takes the training points j0 + l of the chunk, 64 at a time through the LDS (features
+// scaled as in kstar_kernel, terms accumulated in T).  One pass over the chunk takes KB features x VB values: KB x VB fp64
+// sums per lane (the map and the sums are fp64 for both element types), then one wave_sum each: part[chunk][row][1 + k GV + g].
+//   per row (GRID = false, GV = 1): the value of feature k of row i is sub[i][k]             -- pick-freeze, KB = 8, VB = 1
+//   per grid (GRID = true, GV = G): the values of feature k are sg[k][0..G), already / ell_k -- main effects, KB = 2, VB = 8
+// r^2 of a substituted point is a sum of NON-NEGATIVE terms only, never r^2_base - t_k + u_k (at nu = 1/2 the square root turns
+// a cancellation residue of 1e-17 into 3e-9 of the amplitude per training point): with t_l the terms of the pass,
+//   r^2 = ((sum_{l < kb} t_l + t_kb + .. + t_{k-1}) + (t_{k+1} + (.. + (t_{kb+KB-1} + sum_{l >= kb+KB} t_l)))) + u_k
+// so a substituted point that coincides with a training point has r^2 == 0 exactly.  The two outer sums are re-read from the LDS
+// per pass (d - KB terms; the maps of the pass cost KB x VB x ~40 fp64 instructions).
+// The base value mu(a) (part[chunk][row][0]) comes from the first pass, r^2 in kstar_kernel's order.  Rows from nsub on (the
+// second sample matrix of the pick-freeze scheme) get the base value only: their workgroups make one pass.
+// No atomics; every value depends on its own row (and k, and the value) only: the same bits alone, in a batch or in any slab.
+// sens_finish_kernel adds the chunks in ascending order; the reductions below are fixed-order fp64.
+// =================================================================================================================
+constexpr int SENS_CHUNK = 512;  // training points per workgroup
+
+template <typename T, int NU2, int KB, int VB, bool GRID>
+__global__ void __launch_bounds__(256) sens_kernel(const T* __restrict__ Xb, int r0, int rows, int nsub, const T* __restrict__ sub, int G,
+                                                   const T* __restrict__ X, int n, int d, const EvalParams* __restrict__ P,
+                                                   const T* __restrict__ alpha, double* __restrict__ part) {
+  extern __shared__ __align__(16) char smem_raw[];
+  T* sx = reinterpret_cast<T*>(smem_raw);  // [d][64] scaled features of 64 training points
+  T* sq = sx + (size_t)d * 64;             // [4][d] scaled features of this workgroup's base rows
+  T* sb = sq + 4 * d;                      // [4][d] their scaled substitution values (per row)
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const int r = blockIdx.x * 4 + w;  // row of the slab
+  const bool live = r < rows;
+  const bool wsub = live && r0 + r < nsub;
+  const bool any_sub = r0 + blockIdx.x * 4 < nsub;  // rows ascend: the workgroup's first row decides
+  const int GV = GRID ? G : 1;
+  const int nv = 1 + d * GV;
+  const int jc0 = blockIdx.y * SENS_CHUNK, jc1 = min(n, jc0 + SENS_CHUNK);
+  const double amp = P->amp;
+  for (int e = t; e < 4 * d; e += 256) {
+    const int q = e / d, k = e - q * d, rq = blockIdx.x * 4 + q;
+    const size_t gi = (size_t)r0 + rq;
+    sq[e] = (rq < rows) ? Xb[gi * d + k] / (T)P->ell[k] : T(0);
+    if (!GRID) sb[e] = (rq < rows && gi < (size_t)nsub) ? sub[gi * d + k] / (T)P->ell[k] : T(0);
+  }
+  const T* xq = sq + w * d;
+  const T* xb = sb + w * d;
+  double* prow = part + ((size_t)blockIdx.y * rows + (live ? r : 0)) * nv;
+  const int kend = any_sub ? d : 1, gend = any_sub ? GV : 1;  // base rows only: one pass, for the base value
+  for (int kb = 0; kb < kend; kb += KB) {
+    for (int gb = 0; gb < gend; gb += VB) {
+      const bool first = kb == 0 && gb == 0;
+      double acc[KB][VB];
+#pragma unroll
+      for (int kk = 0; kk < KB; ++kk)
+#pragma unroll
+        for (int v = 0; v < VB; ++v) acc[kk][v] = 0.0;
+      double accb = 0.0;
+      for (int j0 = jc0; j0 < jc1; j0 += 64) {
+        __syncthreads();  // the previous 64 points are consumed (first time: sq / sb are written)
+        for (int e = t; e < 64 * d; e += 256) {
+          const int jj = e / d, k = e - jj * d, gj = j0 + jj;
+          sx[k * 64 + jj] = (gj < n) ? X[(size_t)gj * d + k] / (T)P->ell[k] : T(0);
+        }
+        __syncthreads();
+        const int j = j0 + lane;
+        if (live && j < jc1) {
+          const double aj = amp * (double)alpha[j];
+          if (first) {
+            T r2 = T(0);
+            for (int k = 0; k < d; ++k) {  // kstar_kernel's accumulation (cdist order, matern_kernel.rs:274-278)
+              const T df = xq[k] - sx[k * 64 + lane];
+              r2 += df * df;
+            }
+            accb += aj * matern_map<double>(sqrt_nonneg((double)r2), NU2);
+          }
+          if (wsub) {
+            T pfx = T(0), post = T(0);
+            for (int l = 0; l < kb; ++l) {
+              const T df = xq[l] - sx[l * 64 + lane];
+              pfx += df * df;
+            }
+            for (int l = kb + KB; l < d; ++l) {
+              const T df = xq[l] - sx[l * 64 + lane];
+              post += df * df;
+            }
+            T tt[KB], xj[KB], sfx[KB];
+#pragma unroll
+            for (int kk = 0; kk < KB; ++kk) {
+              const bool in = kb + kk < d;
+              xj[kk] = in ? sx[(kb + kk) * 64 + lane] : T(0);
+              const T df = in ? xq[kb + kk] - xj[kk] : T(0);
+              tt[kk] = df * df;
+            }
+            sfx[KB - 1] = post;
+#pragma unroll
+            for (int kk = KB - 2; kk >= 0; --kk) sfx[kk] = tt[kk + 1] + sfx[kk + 1];
+#pragma unroll
+            for (int kk = 0; kk < KB; ++kk) {
+              if (kb + kk < d) {
+                const T others = pfx + sfx[kk];
+#pragma unroll
+                for (int v = 0; v < VB; ++v) {
+                  if (gb + v < GV) {
+                    const T sv = GRID ? sub[(size_t)(kb + kk) * G + gb + v] : xb[kb + kk];
+                    const T df = sv - xj[kk];
+                    const T r2 = others + df * df;
+                    acc[kk][v] += aj * matern_map<double>(sqrt_nonneg((double)r2), NU2);
+                  }
+                }
+                pfx += tt[kk];
+              }
+            }
+          }
+        }
+      }
+      if (first) {
+        const double sm = wave_sum(accb);
+        if (live && lane == 0) prow[0] = sm;
+      }
+      if (any_sub) {
+#pragma unroll
+        for (int kk = 0; kk < KB; ++kk)
+#pragma unroll
+          for (int v = 0; v < VB; ++v)
+            if (kb + kk < d && gb + v < GV) {
+              const double sm = wave_sum(acc[kk][v]);
+              if (wsub && lane == 0) prow[1 + (size_t)(kb + kk) * GV + gb + v] = sm;
+            }
+      }
+    }
+  }
+}
+
+// sg[k][g] = grid[k][g] / ell_k (in place), the scaling of every feature in T
+template <typename T>
+__global__ void __launch_bounds__(256) sens_scale_grid_kernel(T* __restrict__ sg, int d, int G, const EvalParams* __restrict__ P) {
+  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (size_t)d * G) return;
+  sg[e] = sg[e] / (T)P->ell[e / G];
+}
+
+// One thread per (row of the slab, value): the chunks in ascending order.  Value 0 -> fbase[r0 + row] (T); value 1 + k of row
+// i < nsub -> fsub[k][i] (T, leading dimension nsub) per row, or, per grid, back into chunk 0's slot as fp64 for sens_effect_kernel.
+template <typename T, bool GRID>
+__global__ void __launch_bounds__(256) sens_finish_kernel(double* __restrict__ part, int nch, int r0, int rows, int nsub, int nv,
+                                                          T* __restrict__ fbase, T* __restrict__ fsub) {
+  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x, per = (size_t)rows * nv;
+  if (e >= per) return;
+  const size_t r = e / nv, gi = (size_t)r0 + r;
+  const int v = (int)(e - r * nv);
+  if (v > 0 && gi >= (size_t)nsub) return;  // never written: a base row of the second sample matrix
+  double sm = 0.0;
+  for (int c = 0; c < nch; ++c) sm += part[(size_t)c * per + e];
+  if (v == 0) fbase[gi] = (T)sm;
+  else if (GRID) part[e] = sm;
+  else fsub[(size_t)(v - 1) * nsub + gi] = (T)sm;
+}
+
+// eff[k][g] += the slab's rows in ascending order (one thread per (k, g)): whatever the slabs, the sum over the rows runs
+// 0, 1, 2, ...; the last slab divides by N.
+__global__ void __launch_bounds__(256) sens_effect_kernel(const double* __restrict__ part, int rows, int nv, double* __restrict__ eff, int N,
+                                                          int last) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= nv - 1) return;
+  double acc = eff[e];
+  for (int r = 0; r < rows; ++r) acc += part[(size_t)r * nv + 1 + e];
+  eff[e] = last ? acc / (double)N : acc;
+}
+
+// The pick-freeze estimators (Saltelli et al. 2010 for the first-order index, Jansen 1999 for the total index) from the T values
+// the caller gets: fbase = [f_A | f_B] (N each), fsub[k][i] = f_AB.  One workgroup; thread t adds i = t, t + 256, ... in ascending
+// order, then block_sum.  out: first[d], total[d], f0, V.
+template <typename T>
+__global__ void __launch_bounds__(256) sobol_reduce_kernel(const T* __restrict__ fbase, const T* __restrict__ fsub, int N, int d,
+                                                           double* __restrict__ out) {
+  __shared__ double red[4];
+  const int t = threadIdx.x;
+  double s = 0.0;
+  for (int i = t; i < 2 * N; i += 256) s += (double)fbase[i];
+  const double f0 = block_sum(s, red) / (2.0 * N);
+  s = 0.0;
+  for (int i = t; i < 2 * N; i += 256) {
+    const double dv = (double)fbase[i] - f0;
+    s += dv * dv;
+  }
+  const double V = block_sum(s, red) / (2.0 * N);
+  for (int k = 0; k < d; ++k) {
+    double s1 = 0.0, st = 0.0;
+    for (int i = t; i < N; i += 256) {
+      const double fa = (double)fbase[i], fb = (double)fbase[N + i], fab = (double)fsub[(size_t)k * N + i];
+      s1 += (fb - f0) * (fab - fa);
+      st += (fa - fab) * (fa - fab);
+    }
+    s1 = block_sum(s1, red);
+    st = block_sum(st, red);
+    if (t == 0) {
+      out[k] = (V == 0.0) ? 0.0 : s1 / N / V;
+      out[d + k] = (V == 0.0) ? 0.0 : st / (2.0 * N) / V;
+    }
+  }
+  if (t == 0) {
+    out[2 * d] = f0;
+    out[2 * d + 1] = V;
+  }
+}
+
+int sens_chunks(int n) { return (n + SENS_CHUNK - 1) / SENS_CHUNK; }
+
+template <typename T, int NU2>
+static void launch_sens_eval_nu(const T* Xb, int r0, int rows, int nsub, const T* sub, int G, const T* X, int n, int d, const EvalParams* P,
+                                const T* alpha, double* part, hipStream_t s) {
+  const dim3 grid((rows + 3) / 4, sens_chunks(n));
+  const size_t lds = (size_t)(64 + 8) * d * sizeof(T);
+  if (G > 0)
+    hipLaunchKernelGGL((sens_kernel<T, NU2, 2, 8, true>), grid, dim3(256), lds, s, Xb, r0, rows, nsub, sub, G, X, n, d, P, alpha, part);
+  else
+    hipLaunchKernelGGL((sens_kernel<T, NU2, 8, 1, false>), grid, dim3(256), lds, s, Xb, r0, rows, nsub, sub, G, X, n, d, P, alpha, part);
+}
+template <typename T>
+void launch_sens_eval(const T* Xb, int r0, int rows, int nsub, const T* sub, int G, const T* X, int n, int d, int nu2, const EvalParams* P,
+                      const T* alpha, double* part, T* fbase, T* fsub, hipStream_t s, hipEvent_t ev_mid) {
+  if (nu2 == 0) launch_sens_eval_nu<T, 0>(Xb, r0, rows, nsub, sub, G, X, n, d, P, alpha, part, s);
+  else if (nu2 == 1) launch_sens_eval_nu<T, 1>(Xb, r0, rows, nsub, sub, G, X, n, d, P, alpha, part, s);
+  else if (nu2 == 3) launch_sens_eval_nu<T, 3>(Xb, r0, rows, nsub, sub, G, X, n, d, P, alpha, part, s);
+  else launch_sens_eval_nu<T, 5>(Xb, r0, rows, nsub, sub, G, X, n, d, P, alpha, part, s);
+  if (ev_mid) (void)hipEventRecord(ev_mid, s);
+  const int nv = 1 + d * (G > 0 ? G : 1);
+  const unsigned nb = (unsigned)(((size_t)rows * nv + 255) / 256);
+  if (G > 0)
+    hipLaunchKernelGGL((sens_finish_kernel<T, true>), dim3(nb), dim3(256), 0, s, part, sens_chunks(n), r0, rows, nsub, nv, fbase, fsub);
+  else
+    hipLaunchKernelGGL((sens_finish_kernel<T, false>), dim3(nb), dim3(256), 0, s, part, sens_chunks(n), r0, rows, nsub, nv, fbase, fsub);
+}
+template <typename T>
+void launch_sens_scale_grid(T* sg, int d, int G, const EvalParams* P, hipStream_t s) {
+  hipLaunchKernelGGL((sens_scale_grid_kernel<T>), dim3((unsigned)(((size_t)d * G + 255) / 256)), dim3(256), 0, s, sg, d, G, P);
+}
+void launch_sens_effect(const double* part, int rows, int d, int G, double* eff, int N, int last, hipStream_t s) {
+  hipLaunchKernelGGL(sens_effect_kernel, dim3((unsigned)(((size_t)d * G + 255) / 256)), dim3(256), 0, s, part, rows, 1 + d * G, eff, N, last);
+}
+template <typename T>
+void launch_sobol_reduce(const T* fbase, const T* fsub, int N, int d, double* out, hipStream_t s) {
+  hipLaunchKernelGGL((sobol_reduce_kernel<T>), dim3(1), dim3(256), 0, s, fbase, fsub, N, d, out);
+}
+#define SENS_INST(T)                                                                                                                       \
+  template void launch_sens_eval<T>(const T*, int, int, int, const T*, int, const T*, int, int, int, const EvalParams*, const T*, double*, \
+                                    T*, T*, hipStream_t, hipEvent_t);                                                                      \
+  template void launch_sens_scale_grid<T>(T*, int, int, const EvalParams*, hipStream_t);                                                   \
+  template void launch_sobol_reduce<T>(const T*, const T*, int, int, double*, hipStream_t);
+SENS_INST(double)
+SENS_INST(float)
+#undef SENS_INST
+
+// =================================================================================================================
 // joint posterior at the candidates (hbegp.cpp: model_posterior).  Sigma = K** + (1e-5 + jitter) I - Q Q^T comes from kmat_kernel
 // and one tile GEMM; its factor from the recursion of the fit with the diagonal blocks below, which keep L; the draws
 // Y = Z L^T from one more tile GEMM.  Two kernels of their own:

@@ -366,6 +366,44 @@ class SurrogateModelGPR:
         eps = rng.standard_normal((int(n_paths), fk.n)) if noise_draw else None
         return fk.sample_paths(omega0, phase, w, eps)
 
+    # Sensitivity of the surrogate to its features (opt-in; nothing the estimator suggests by default uses it).
+    def _uniform_rows(self, n_samples, rng, bounds):
+        """[n_samples, d] uniform rows from rng.uniform in the unit box, or in `bounds` = [(lo, hi)] per feature."""
+        d = self.fitted.d
+        u = np.asarray(rng.uniform(0.0, 1.0, int(n_samples) * d), dtype=np.float64).reshape(int(n_samples), d)
+        if bounds is not None:
+            lo = np.array([b[0] for b in bounds], dtype=np.float64)
+            hi = np.array([b[1] for b in bounds], dtype=np.float64)
+            assert lo.shape == (d,) and hi.shape == (d,)
+            u = lo + (hi - lo) * u
+        return u.astype(self.dtype)
+
+    def sobol_indices_a(self, n_samples, rng, bounds=None):
+        """First-order and total Sobol indices of the surrogate's mean per feature (FittedKernel.sobol_indices): which parameters
+        mattered, and whether through a main effect (first) or through interactions too (total - first).  The two pick-freeze
+        sample matrices [n_samples, d] are drawn uniformly in the unit box, or in `bounds` = [(lo, hi)] per feature, from
+        rng.uniform (A first, then B).  Under the linear y projection the indices are those of y itself, because a variance ratio
+        is invariant under affine maps; under the logarithmic projection they are those of the normalised response (of
+        log(y - expected)), not of y.  Returns (first[d], total[d]) float64."""
+        A = self._uniform_rows(n_samples, rng, bounds)
+        B = self._uniform_rows(n_samples, rng, bounds)
+        first, total, _, _ = self.fitted.sobol_indices(A, B)
+        return first, total
+
+    def main_effects_a(self, n_samples, grid_size, rng, bounds=None):
+        """Main-effect (partial dependence) curves of the surrogate's mean (FittedKernel.main_effects): per feature the mean
+        prediction over n_samples uniform rows (unit box or `bounds`, from rng.uniform) with that feature set to each of
+        grid_size midpoints of its range.  The averages are taken in the normalised space and projected like predict_mean_a:
+        under the linear projection that is the average in y units, under the logarithmic one the projection of the average
+        normalised response.  Returns (grid[d, grid_size], effect[d, grid_size]) float64, both in the caller's units."""
+        d, G = self.fitted.d, int(grid_size)
+        A = self._uniform_rows(n_samples, rng, bounds)
+        lo = np.zeros(d) if bounds is None else np.array([b[0] for b in bounds], dtype=np.float64)
+        hi = np.ones(d) if bounds is None else np.array([b[1] for b in bounds], dtype=np.float64)
+        grid = lo[:, None] + (hi - lo)[:, None] * ((np.arange(G) + 0.5) / G)[None, :]
+        effect = self.fitted.main_effects(A, grid.astype(self.dtype))
+        return grid, self.y_norm.project_location_from_normalized(effect)
+
     # Leave-one-out diagnostics (opt-in; nothing the estimator suggests by default uses them).
     def loo_a(self):
         """Leave-one-out cross-validation of the surrogate on its own observations (FittedKernel.loo): per training row the
@@ -390,6 +428,15 @@ class SurrogateModelGPR:
     def predict_mean_ei(self, x, fmin):  # surrogate_model.rs:49-52
         mean, ei = self.predict_mean_ei_a(np.asarray(x, dtype=self.dtype)[None, :], fmin)
         return mean[0], ei[0]
+
+
+def rank_parameters(model, n_samples, rng, bounds=None):
+    """The features of `model` (a SurrogateModelGPR) ordered by their total Sobol index, the most influential first, ties to the
+    lower index (SurrogateModelGPR.sobol_indices_a with n_samples rows per sample matrix).  Opt-in: nothing that is suggested by
+    default changes.  Returns (order[d] int64, first[d], total[d])."""
+    first, total = model.sobol_indices_a(n_samples, rng, bounds=bounds)
+    order = np.argsort(-total, kind="stable").astype(np.int64)
+    return order, first, total
 
 
 def find_best_candidate_by_ei(candidates, model, fmin):

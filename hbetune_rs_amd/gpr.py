@@ -482,6 +482,49 @@ class FittedKernel:
             return nei, best.value, fmin_draws, rho
         return nei, best.value
 
+    def sobol_indices(self, A, B, want_values=False):
+        """Variance-based (Sobol) indices of the posterior mean by pick-freeze sampling (hbegp_sobol_*), in the normalised y space:
+        A, B [N, d] two independent sample matrices in the feature coordinates of the fit, drawn by the caller.  Returns
+        (first[d], total[d], f0, variance): the first-order indices (Saltelli et al. 2010), the total indices (Jansen 1999), the
+        mean and the variance of the posterior mean over the 2N rows.  With want_values also (f_a[N], f_b[N], f_ab[d, N]): the
+        means at A, at B and at A with column k taken from B, in the element type -- the numbers the indices were formed from."""
+        lib = _lib.load()
+        A = _lib.as_c(np.atleast_2d(A), self.dtype)
+        B = _lib.as_c(np.atleast_2d(B), self.dtype)
+        assert A.ndim == 2 and A.shape[1] == self.d and B.shape == A.shape, (A.shape, B.shape)
+        N = A.shape[0]
+        first, total = np.zeros(self.d), np.zeros(self.d)
+        f0, var = C.c_double(), C.c_double()
+        f_a = np.zeros(N, dtype=self.dtype) if want_values else None
+        f_b = np.zeros(N, dtype=self.dtype) if want_values else None
+        f_ab = np.zeros((self.d, N), dtype=self.dtype) if want_values else None
+        fn = getattr(lib, f"hbegp_sobol_{self._sfx}")
+        _lib.check(fn(self._h, _lib.aptr(A), _lib.aptr(B), N, _lib.dptr(first), _lib.dptr(total), C.byref(f0), C.byref(var),
+                      _lib.aptr(f_a), _lib.aptr(f_b), _lib.aptr(f_ab)))
+        if want_values:
+            return first, total, f0.value, var.value, f_a, f_b, f_ab
+        return first, total, f0.value, var.value
+
+    def main_effects(self, A, grid, want_base=False):
+        """Main-effect (partial dependence) curves of the posterior mean (hbegp_main_effects_*; Friedman 2001), in the normalised
+        y space: effect[k, g] = the mean over the rows of A [N, d] of the posterior mean with feature k set to grid[k, g].  grid
+        [d, G], or [G]: the same values for every feature.  N = 1 gives that row's conditional curves.  Returns effect[d, G]
+        (float64); with want_base (effect, f_a[N]): the posterior mean at the rows themselves."""
+        lib = _lib.load()
+        A = _lib.as_c(np.atleast_2d(A), self.dtype)
+        assert A.ndim == 2 and A.shape[1] == self.d, A.shape
+        grid = np.asarray(grid, dtype=self.dtype)
+        if grid.ndim == 1:
+            grid = np.broadcast_to(grid, (self.d, grid.shape[0]))
+        grid = _lib.as_c(grid, self.dtype)
+        assert grid.ndim == 2 and grid.shape[0] == self.d, grid.shape
+        N, G = A.shape[0], grid.shape[1]
+        effect = np.zeros((self.d, G))
+        f_a = np.zeros(N, dtype=self.dtype) if want_base else None
+        fn = getattr(lib, f"hbegp_main_effects_{self._sfx}")
+        _lib.check(fn(self._h, _lib.aptr(A), N, _lib.aptr(grid), G, _lib.dptr(effect), _lib.aptr(f_a)))
+        return (effect, f_a) if want_base else effect
+
     def qei(self, x, z, fmin_normalized, jitter=0.0, want_grad=True, raise_not_pd=False):
         """Batch expected improvement by Monte Carlo (hbegp_qei_*) in the normalised y space: x [B, q, d] (or [q, d]: B = 1) batches
         of q points, z [S, q] the caller's standard normals, shared by every batch.  Returns (qei[B], grad[B, q, d] or None,

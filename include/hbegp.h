@@ -377,6 +377,40 @@ int hbegp_noisy_ei_f64(hbegp_model* model, const double* Xs, int m, int mb, cons
 int hbegp_noisy_ei_f32(hbegp_model* model, const float* Xs, int m, int mb, const float* z, int S, double jitter, double* nei,
                        int* best, double* fmin_draws, double* rho, int* info);
 
+/* Sensitivity of the posterior mean mu (hbegp_predict_*'s mean, normalised y space) to each feature, from the CALLER's sample
+ * matrices in the feature coordinates the model was fitted on (the RNG stays on the caller side).  Both calls evaluate the mean at
+ * base rows with ONE coordinate substituted,
+ *   mu(a | k <- s) = sum_j c phi(r_j) alpha_j,   r_j^2 = sum_{l != k} ((a_l - x_jl) / ell_l)^2 + ((s - x_jk) / ell_k)^2,
+ * in one fused pass: no query matrix and no K* are formed.  r^2 is accumulated in the element type from non-negative terms only (a
+ * substituted point that coincides with a training row has r^2 == 0 exactly); the Matern map, the sums over j and every reduction
+ * are fp64 in a fixed order without atomics.  Every value depends only on its own row (and k, and the substituted value): the same
+ * bits alone or in a batch, whatever the library's internal slabs of rows.
+ *
+ * hbegp_sobol_*: variance-based (Sobol) indices by pick-freeze sampling.  A[N*d], B[N*d]: two independent sample matrices.  With
+ * f_A[i] = mu(A_i), f_B[i] = mu(B_i), f_AB[k][i] = mu(A_i | k <- B_ik), rounded to the element type (the optional outputs f_a[N],
+ * f_b[N], f_ab[d*N] with f_ab[k*N + i]; may be NULL):
+ *   f0 = mean of the 2N values f_A and f_B,   V = their mean squared deviation from f0,
+ *   first[k] = (1/N) sum_i (f_B[i] - f0) (f_AB[k][i] - f_A[i]) / V      (Saltelli et al. 2010),
+ *   total[k] = (1/(2N)) sum_i (f_A[i] - f_AB[k][i])^2 / V               (Jansen 1999);   V == 0 gives first = total = 0.
+ * first[d], total[d] (required), *f0, *variance (may be NULL) are double.
+ *
+ * hbegp_main_effects_*: main-effect (partial dependence) curves (Friedman 2001).  A[N*d]: the sample; grid[d*G]: G values per
+ * feature (grid[k*G + g]);  effect[k*G + g] = (1/N) sum_i mu(A_i | k <- grid[k][g])  (required, double), the rows added in
+ * ascending i; f_a[N] (may be NULL): mu(A_i).  N = 1 gives one row's conditional curve.
+ *
+ * HBEGP_EINVAL (before any device call; a refused call writes nothing) for a NULL model, A, B, first or total (sobol), a NULL grid
+ * or effect (main effects), N < 2 (sobol), N < 1 (main effects), G < 1, or a model of the other element type.  The rows are not
+ * screened: a NaN coordinate makes that row's values NaN (and with them the sums the row enters), nothing else, and nothing is left
+ * behind for a later call.  Serialised per model like predict.  The workspace is the chunk partial sums of one slab of rows, at
+ * most 128 MiB (one row's worth where a single row needs more) plus the samples and the per-row values; work that does not fit in
+ * device memory is HBEGP_ENOMEM.  HBEGP_SENS_SLAB_ROWS (environment, read per call) forces the slab size: tests only. */
+int hbegp_sobol_f64(hbegp_model* model, const double* A, const double* B, int N, double* first, double* total, double* f0,
+                    double* variance, double* f_a, double* f_b, double* f_ab);
+int hbegp_sobol_f32(hbegp_model* model, const float* A, const float* B, int N, double* first, double* total, double* f0,
+                    double* variance, float* f_a, float* f_b, float* f_ab);
+int hbegp_main_effects_f64(hbegp_model* model, const double* A, int N, const double* grid, int G, double* effect, double* f_a);
+int hbegp_main_effects_f32(hbegp_model* model, const float* A, int N, const float* grid, int G, double* effect, float* f_a);
+
 /* Batch expected improvement by Monte Carlo (q-EI) in the normalised y space like hbegp_predict_*, for B batches of q points:
  * Xb[B*q*d] (batch b = rows b*q .. b*q + q - 1, feature space), z[S*q] the CALLER's standard normals (draw s = row s), shared by
  * every batch (common random numbers; the RNG stays on the caller side).  Per batch b:
@@ -519,6 +553,11 @@ int hbegp_debug_kg_phases(int enable, double* phase_ms);
  * draw products (with the upload of z), the reductions -- in milliseconds; then enable != 0 makes this thread's later noisy-EI
  * calls timed. */
 int hbegp_debug_nei_phases(int enable, double* phase_ms);
+/* ---- timing hook (tools/sens_bench.py): phase_ms[4] (may be NULL) receives the device time of the phases of the calling thread's
+ * last timed hbegp_sobol_* / hbegp_main_effects_* call -- the upload (with the grid's scaling), the substituted means, the chunk and
+ * row sums (both summed over the slabs), the final reduction with the downloads -- in milliseconds; then enable != 0 makes this
+ * thread's later sensitivity calls timed. */
+int hbegp_debug_sens_phases(int enable, double* phase_ms);
 /* ---- timing hook (tools/qei_bench.py): phase_ms[2] (may be NULL) receives the device time of the phases of the calling thread's
  * last timed hbegp_qei_* call -- the shared launches (upload of the points, Kstar, mean, Q; with a gradient dmean, G, W; upload of
  * z), the qEI kernel -- in milliseconds; then enable != 0 makes this thread's later qEI calls timed. */

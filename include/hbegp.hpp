@@ -67,6 +67,11 @@ template <> struct Abi<double> {
   }
   static int noisy_ei(hbegp_model* m, const double* xs, int n, int mb, const double* z, int s, double j, double* nei, int* best, double* fmin,
                       double* rho, int* info) { return hbegp_noisy_ei_f64(m, xs, n, mb, z, s, j, nei, best, fmin, rho, info); }
+  static int sobol(hbegp_model* m, const double* a, const double* b, int n, double* first, double* total, double* f0, double* var, double* fa, double* fb,
+                   double* fab) { return hbegp_sobol_f64(m, a, b, n, first, total, f0, var, fa, fb, fab); }
+  static int main_effects(hbegp_model* m, const double* a, int n, const double* grid, int g, double* effect, double* fa) {
+    return hbegp_main_effects_f64(m, a, n, grid, g, effect, fa);
+  }
   static int qei(hbegp_model* m, const double* xb, int b, int q, const double* z, int s, double fmin, double j, double* v, double* g, int* info) {
     return hbegp_qei_f64(m, xb, b, q, z, s, fmin, j, v, g, info);
   }
@@ -110,6 +115,11 @@ template <> struct Abi<float> {
   }
   static int noisy_ei(hbegp_model* m, const float* xs, int n, int mb, const float* z, int s, double j, double* nei, int* best, double* fmin,
                       double* rho, int* info) { return hbegp_noisy_ei_f32(m, xs, n, mb, z, s, j, nei, best, fmin, rho, info); }
+  static int sobol(hbegp_model* m, const float* a, const float* b, int n, double* first, double* total, double* f0, double* var, float* fa, float* fb,
+                   float* fab) { return hbegp_sobol_f32(m, a, b, n, first, total, f0, var, fa, fb, fab); }
+  static int main_effects(hbegp_model* m, const float* a, int n, const float* grid, int g, double* effect, float* fa) {
+    return hbegp_main_effects_f32(m, a, n, grid, g, effect, fa);
+  }
   static int qei(hbegp_model* m, const float* xb, int b, int q, const float* z, int s, double fmin, double j, double* v, float* g, int* info) {
     return hbegp_qei_f32(m, xb, b, q, z, s, fmin, j, v, g, info);
   }
@@ -229,6 +239,17 @@ class FittedKernel {
   void noisy_ei(const A* xs, int m, int mb, const A* z, int S, double* nei, int* best = nullptr, double* fmin_draws = nullptr,
                 double* rho = nullptr, double jitter = 0.0) const {
     check(detail::Abi<A>::noisy_ei(h_, xs, m, mb, z, S, jitter, nei, best, fmin_draws, rho, nullptr));
+  }
+  // Sobol indices of the posterior mean by pick-freeze sampling from the caller's sample matrices a[N*d], b[N*d]: first[d], total[d];
+  // f0, variance and the values f_a[N], f_b[N], f_ab[d*N] (f_ab[k*N + i]: row i of a with column k from b) may be nullptr
+  void sobol_indices(const A* a, const A* b, int N, double* first, double* total, double* f0 = nullptr, double* variance = nullptr,
+                     A* f_a = nullptr, A* f_b = nullptr, A* f_ab = nullptr) const {
+    check(detail::Abi<A>::sobol(h_, a, b, N, first, total, f0, variance, f_a, f_b, f_ab));
+  }
+  // main-effect (partial dependence) curves: effect[k*G + g] = the mean over the rows of a[N*d] of the posterior mean with feature k
+  // set to grid[k*G + g] (normalised y space); f_a[N] may be nullptr.  N = 1: one row's conditional curves
+  void main_effects(const A* a, int N, const A* grid, int G, double* effect, A* f_a = nullptr) const {
+    check(detail::Abi<A>::main_effects(h_, a, N, grid, G, effect, f_a));
   }
   // Monte Carlo q-EI of B batches xb[B*q*d] with the caller's normals z[S*q]: qei[B]; grad[B*q*d] and info[B] may be nullptr.
   // Returns HBEGP_OK or HBEGP_NOT_PD (some batch's Sigma did not factor: its qei is NaN, info says where); throws otherwise

@@ -159,6 +159,22 @@ extern "C" {
         model: *mut HbegpModel, xs: *const c_float, m: c_int, mb: c_int, z: *const c_float, s: c_int, jitter: c_double,
         nei: *mut c_double, best: *mut c_int, fmin_draws: *mut c_double, rho: *mut c_double, info: *mut c_int,
     ) -> c_int;
+    fn hbegp_sobol_f64(
+        model: *mut HbegpModel, a: *const c_double, b: *const c_double, n: c_int, first: *mut c_double, total: *mut c_double,
+        f0: *mut c_double, variance: *mut c_double, f_a: *mut c_double, f_b: *mut c_double, f_ab: *mut c_double,
+    ) -> c_int;
+    fn hbegp_sobol_f32(
+        model: *mut HbegpModel, a: *const c_float, b: *const c_float, n: c_int, first: *mut c_double, total: *mut c_double,
+        f0: *mut c_double, variance: *mut c_double, f_a: *mut c_float, f_b: *mut c_float, f_ab: *mut c_float,
+    ) -> c_int;
+    fn hbegp_main_effects_f64(
+        model: *mut HbegpModel, a: *const c_double, n: c_int, grid: *const c_double, g: c_int, effect: *mut c_double,
+        f_a: *mut c_double,
+    ) -> c_int;
+    fn hbegp_main_effects_f32(
+        model: *mut HbegpModel, a: *const c_float, n: c_int, grid: *const c_float, g: c_int, effect: *mut c_double,
+        f_a: *mut c_float,
+    ) -> c_int;
     fn hbegp_qei_f64(
         model: *mut HbegpModel, xb: *const c_double, b: c_int, q: c_int, z: *const c_double, s: c_int, fmin_normalized: c_double,
         jitter: c_double, qei: *mut c_double, grad: *mut c_double, info: *mut c_int,
