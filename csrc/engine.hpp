@@ -273,6 +273,16 @@ void launch_nei_pad(T* W, int ld, int mb, int mbp, hipStream_t s);
 template <typename T>
 void launch_nei_reduce(const T* Sig, const T* LA, const T* Y, int ld, const T* mean, int mb, int mbp, int mc, int S, double* fmin_draws,
                        double* rho, double* nei, int* best, const int* info, hipStream_t s);
+// expected hypervolume improvement of two independent objectives (hbegp_ehvi; ehvi_kernel: one wave per candidate).
+// mean / var [m] and, with want_grad, dmean / dvar [m][d] of the two models; thr = [up | hb], ns = P + 1 strips each: up[i] the upper
+// end of strip i along objective 0 (up[ns - 1] = r1), hb[i] its height threshold along objective 1 (hb[0] = r2).  Out: ehvi[m] (fp64),
+// grad[m][d] (want_grad), *best = the last index of the maximum of ehvi (NaN never wins; m >= 1).  Up to EHVI_LDS_STRIPS strips are
+// staged in the LDS.
+constexpr int EHVI_LDS_STRIPS = 4096;
+constexpr size_t ehvi_lds_bytes(int ns) { return 16 * (size_t)ns; }
+template <typename T>
+void launch_ehvi(const T* mean1, const T* var1, const T* dmean1, const T* dvar1, const T* mean2, const T* var2, const T* dmean2,
+                 const T* dvar2, int m, int d, const double* thr, int ns, int want_grad, double* ehvi, T* grad, int* best, hipStream_t s);
 // batch expected improvement by Monte Carlo (hbegp_qei; qei_batch_kernel: one workgroup per batch of q points).  Rows b q .. b q + q - 1
 // of Xs [B q][d], Q [mp][np], mean, dmean [mp][d] and W [d][mp][np] (W and dmean are read only with want_grad); z [S][q] shared by
 // the batches; noise = 1e-5 + jitter.  Out: qei[B], grad[B q][d] (want_grad), info[B] (0, or 1 + the column whose pivot failed).

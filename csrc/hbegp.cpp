@@ -21,6 +21,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <limits>
 #include <memory>
 #include <mutex>
@@ -2624,6 +2625,210 @@ static int model_maximize_ei(hbegp_model* m, const T* starts, int S, const doubl
   return HBEGP_OK;
 }
 
+// ---- expected hypervolume improvement of two independent objectives (hbegp_ehvi / hbegp_maximize_ehvi) ----------
+// phase times of the calling thread's last timed EHVI call (hbegp_debug_ehvi_phases): the predict of objective 0 and of objective 1
+// (each on its model's stream: they overlap), the EHVI kernels, in ms
+static thread_local bool t_time_ehvi = false;
+static thread_local double t_ehvi_ms[3] = {0, 0, 0};
+
+// The caller's front reduced to the non-dominated points strictly inside the reference box, a ascending (so b descends), as the
+// kernel's strips: thr = [up | hb], ns = P' + 1 each; up = a_1 .. a_P', r1 and hb = r2, b_1 .. b_P'.  The result depends on the set
+// of points only: not on their order, on duplicates, on dominated points or on points outside the box.
+static int ehvi_thresholds(const double* front, int P, const double* ref, std::vector<double>* thr) {
+  std::vector<std::pair<double, double>> pts;
+  pts.reserve((size_t)P);
+  for (int i = 0; i < P; ++i)
+    if (front[2 * (size_t)i] < ref[0] && front[2 * (size_t)i + 1] < ref[1]) pts.push_back({front[2 * (size_t)i], front[2 * (size_t)i + 1]});
+  std::sort(pts.begin(), pts.end());
+  std::vector<double> a, b;
+  double bmin = ref[1];
+  for (const auto& p : pts)
+    if (p.second < bmin) {  // among equal a the lowest b comes first and dominates the others
+      a.push_back(p.first);
+      b.push_back(p.second);
+      bmin = p.second;
+    }
+  const int ns = (int)a.size() + 1;
+  thr->assign(2 * (size_t)ns, 0.0);
+  for (int i = 0; i + 1 < ns; ++i) {
+    (*thr)[i] = a[i];
+    (*thr)[ns + i + 1] = b[i];
+  }
+  (*thr)[ns - 1] = ref[0];
+  (*thr)[ns] = ref[1];
+  return ns;
+}
+
+// EHVI at cnt >= 1 candidates.  Both models' mutexes are taken in the order of their addresses (two calls with the models in either
+// order cannot wait for each other).  Each model's predict launches -- hbegp_predict's batched ones, or hbegp_predict_grad's with a
+// gradient, in their order -- go to its own stream; the stream of objective 0 then waits for an event behind objective 1's launches
+// and runs the EHVI kernel and every copy back.  Thresholds and outputs are borrowed for the call (CallScratch) and go back cleared.
+// mean_out / var_out [cnt][2] (may be null): the two posteriors interleaved.
+template <typename T>
+static int model_ehvi(hbegp_model* const* M, const T* Xs, int cnt, const std::vector<double>& thr, int ns, hipEvent_t ev_join, double* ehvi,
+                      T* grad, int* best, T* mean_out, T* var_out) {
+  const bool want_grad = grad != nullptr;
+  const int d = M[0]->d;
+  // everything the call takes, counted before anything is taken: an m far beyond the device is ENOMEM, not an overflow
+  const double rows = std::ceil(std::max(1.0, (double)cnt) / NB) * NB;
+  double need = 8.0 * cnt + 16.0 * ns + (want_grad ? (double)sizeof(T) * cnt * d : 0.0);
+  for (int k = 0; k < 2; ++k)
+    need += (double)sizeof(T) * ((2.0 + (want_grad ? 2.0 * d : 0.0)) * rows * M[k]->np + rows * (d + 2) + (want_grad ? 2.0 * rows * d : 0.0)) +
+            8.0 * (want_grad ? (double)pred_grad_chunks(M[k]->n) * rows * d : 0.0);
+  if (need > 1e15 || rows > (double)(1 << 30))
+    return fail(HBEGP_ENOMEM, "EHVI at %d points needs %.3g bytes of device memory", cnt, need);
+  hbegp_model* first = M[0];
+  hbegp_model* second = M[1];
+  if (std::less<hbegp_model*>()(second, first)) std::swap(first, second);
+  std::lock_guard<std::mutex> lock_a(first->mu);
+  std::lock_guard<std::mutex> lock_b(second->mu);
+  HIPCHECK(hipSetDevice(M[0]->dev));
+  const int mp = round_up(cnt, NB);
+  for (int k = 0; k < 2; ++k) {
+    if (want_grad) predict_grad_reserve<T>(M[k], mp);
+    else predict_batched_reserve<T>(M[k], mp);
+  }
+  hipStream_t s0 = M[0]->stream, s1 = M[1]->stream;
+  CallScratch ws{M[0]->dev, s0, {}};
+  double* dthr = static_cast<double*>(ws.get(sizeof(double) * 2 * (size_t)ns));
+  double* dval = static_cast<double*>(ws.get(sizeof(double) * (size_t)cnt));
+  int* dbest = static_cast<int*>(ws.get(sizeof(int)));
+  T* dg = want_grad ? static_cast<T*>(ws.get(sizeof(T) * (size_t)cnt * d)) : nullptr;
+  hipEvent_t ev[6] = {};  // [2 k], [2 k + 1]: around model k's predict; [4], [5]: around the EHVI kernels
+  const bool timed = t_time_ehvi;
+  if (timed)
+    for (auto& e : ev) HIPCHECK(hipEventCreate(&e));
+  for (int k = 0; k < 2; ++k) {
+    hbegp_model* m = M[k];
+    hipStream_t s = m->stream;
+    if (timed) HIPCHECK(hipEventRecord(ev[2 * k], s));
+    HIPCHECK(hipMemcpyAsync(m->Xs, Xs, sizeof(T) * (size_t)cnt * d, hipMemcpyHostToDevice, s));
+    predict_batched_launches<T>(m, cnt, mp, true);
+    if (want_grad) {
+      launch_pred_grad<T>(static_cast<T*>(m->Xs), cnt, static_cast<T*>(m->X), m->n, d, m->nu2, m->dP, static_cast<T*>(m->alpha),
+                          static_cast<double*>(m->gpart), static_cast<T*>(m->dmean), s);
+      predict_grad_w_launches<T>(m, cnt, mp);
+      launch_pred_dvar<T>(static_cast<T*>(m->W), static_cast<T*>(m->Q), cnt, mp, m->np, d, static_cast<T*>(m->var), static_cast<T*>(m->dvar), s);
+    }
+    CHECK_LAUNCHES();
+    if (timed) HIPCHECK(hipEventRecord(ev[2 * k + 1], s));
+  }
+  HIPCHECK(hipEventRecord(ev_join, s1));
+  HIPCHECK(hipMemcpyAsync(dthr, thr.data(), sizeof(double) * 2 * (size_t)ns, hipMemcpyHostToDevice, s0));
+  HIPCHECK(hipStreamWaitEvent(s0, ev_join, 0));
+  if (timed) HIPCHECK(hipEventRecord(ev[4], s0));
+  const T* g0m = want_grad ? static_cast<const T*>(M[0]->dmean) : nullptr;  // (not read without a gradient)
+  const T* g0v = want_grad ? static_cast<const T*>(M[0]->dvar) : nullptr;
+  const T* g1m = want_grad ? static_cast<const T*>(M[1]->dmean) : nullptr;
+  const T* g1v = want_grad ? static_cast<const T*>(M[1]->dvar) : nullptr;
+  launch_ehvi<T>(static_cast<const T*>(M[0]->mean), static_cast<const T*>(M[0]->var), g0m, g0v, static_cast<const T*>(M[1]->mean),
+                 static_cast<const T*>(M[1]->var), g1m, g1v, cnt, d, dthr, ns, want_grad ? 1 : 0, dval, dg, dbest, s0);
+  if (timed) HIPCHECK(hipEventRecord(ev[5], s0));
+  CHECK_LAUNCHES();
+  int hbest = -1;
+  std::vector<T> hm, hv;
+  HIPCHECK(hipMemcpyAsync(ehvi, dval, sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost, s0));
+  HIPCHECK(hipMemcpyAsync(&hbest, dbest, sizeof(int), hipMemcpyDeviceToHost, s0));
+  if (want_grad) HIPCHECK(hipMemcpyAsync(grad, dg, sizeof(T) * (size_t)cnt * d, hipMemcpyDeviceToHost, s0));
+  if (mean_out) {
+    hm.resize(2 * (size_t)cnt);
+    for (int k = 0; k < 2; ++k)
+      HIPCHECK(hipMemcpyAsync(hm.data() + (size_t)k * cnt, M[k]->mean, sizeof(T) * (size_t)cnt, hipMemcpyDeviceToHost, s0));
+  }
+  if (var_out) {
+    hv.resize(2 * (size_t)cnt);
+    for (int k = 0; k < 2; ++k)
+      HIPCHECK(hipMemcpyAsync(hv.data() + (size_t)k * cnt, M[k]->var, sizeof(T) * (size_t)cnt, hipMemcpyDeviceToHost, s0));
+  }
+  HIPCHECK(hipStreamSynchronize(s0));  // behind the event: objective 1's stream has finished this call's work too
+  if (best) *best = hbest;
+  for (int k = 0; k < 2; ++k)
+    for (int i = 0; i < cnt; ++i) {
+      if (mean_out) mean_out[2 * (size_t)i + k] = hm[(size_t)k * cnt + i];
+      if (var_out) var_out[2 * (size_t)i + k] = hv[(size_t)k * cnt + i];
+    }
+  if (timed) {
+    HIPCHECK(hipEventSynchronize(ev[3]));
+    for (int i = 0; i < 3; ++i) {
+      float ms = 0;
+      HIPCHECK(hipEventElapsedTime(&ms, ev[2 * i], ev[2 * i + 1]));
+      t_ehvi_ms[i] = ms;
+    }
+    for (auto& e : ev) (void)hipEventDestroy(e);
+  }
+  return HBEGP_OK;
+}
+
+// the event objective 0's stream waits on, for the length of one C call
+struct EhviJoin {
+  hipEvent_t ev = nullptr;
+  explicit EhviJoin(int dev) {
+    HIPCHECK(hipSetDevice(dev));
+    HIPCHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+  }
+  ~EhviJoin() {
+    if (ev) (void)hipEventDestroy(ev);
+  }
+};
+
+// S bounded L-BFGS runs on -EHVI (lbfgs_step.hpp, the fit optimiser's constants) in lockstep, as model_maximize_ei: every round
+// gathers the point each unfinished run asks for and evaluates them all with ONE model_ehvi with a gradient (one batched gradient
+// predict per model, then the EHVI kernel).  Each run returns the best point it evaluated; a NaN is a failed evaluation.
+template <typename T>
+static int model_maximize_ehvi(hbegp_model* const* M, const T* starts, int S, const double* lo, const double* hi,
+                               const std::vector<double>& thr, int ns, int maxeval, T* x_out, double* ehvi_out, int* nevals_out) {
+  const int d = M[0]->d;
+  const LbfgsOptions o;
+  EhviJoin join(M[0]->dev);
+  std::vector<LbfgsState> st(S);
+  std::vector<char> running(S, 1);
+  std::vector<double> best(S, -std::numeric_limits<double>::infinity());
+  std::vector<double> x0(d), g(d);
+  for (int r = 0; r < S; ++r) {
+    for (int k = 0; k < d; ++k) x0[k] = (double)starts[(size_t)r * d + k];
+    lbfgs_begin(st[r], x0.data(), lo, hi, d, maxeval, o.memory, o.pgtol, o.ftol, false);
+    for (int k = 0; k < d; ++k) x_out[(size_t)r * d + k] = starts[(size_t)r * d + k];
+  }
+  std::vector<int> act;
+  std::vector<T> xs((size_t)S * d), gr((size_t)S * d);
+  std::vector<double> val(S);
+  for (;;) {
+    act.clear();
+    for (int r = 0; r < S; ++r)
+      if (running[r]) act.push_back(r);
+    if (act.empty()) break;
+    const int cnt = (int)act.size();
+    for (int i = 0; i < cnt; ++i) {
+      const double* q = lbfgs_request(st[act[i]]);
+      for (int k = 0; k < d; ++k) xs[(size_t)i * d + k] = to_box<T>(q[k], lo[k], hi[k]);
+    }
+    const int rc = model_ehvi<T>(M, xs.data(), cnt, thr, ns, join.ev, val.data(), gr.data(), nullptr, nullptr, nullptr);
+    if (rc != HBEGP_OK) return rc;
+    for (int i = 0; i < cnt; ++i) {
+      const int r = act[i];
+      double f = std::numeric_limits<double>::infinity();  // a NaN prediction is a failed evaluation
+      double v = -std::numeric_limits<double>::infinity();
+      bool ok = std::isfinite(val[i]);
+      for (int k = 0; k < d && ok; ++k) ok = std::isfinite((double)gr[(size_t)i * d + k]);
+      if (ok) {
+        v = val[i];
+        f = -v;
+        for (int k = 0; k < d; ++k) g[k] = -(double)gr[(size_t)i * d + k];
+      }
+      if (v > best[r]) {
+        best[r] = v;
+        for (int k = 0; k < d; ++k) x_out[(size_t)r * d + k] = xs[(size_t)i * d + k];
+      }
+      running[r] = lbfgs_advance(st[r], f, g.data()) ? 1 : 0;
+    }
+  }
+  for (int r = 0; r < S; ++r) {
+    ehvi_out[r] = best[r];
+    if (nevals_out) nevals_out[r] = st[r].nevals;
+  }
+  return HBEGP_OK;
+}
+
 // phase times of the calling thread's last timed qEI call (hbegp_debug_qei_phases): the shared launches, the qEI kernel in ms
 static thread_local bool t_time_qei = false;
 static thread_local double t_qei_ms[2] = {0, 0};
@@ -4383,6 +4588,79 @@ int hbegp_debug_nei_phases(int enable, double* phase_ms) {
   if (phase_ms)
     for (int i = 0; i < 4; ++i) phase_ms[i] = t_nei_ms[i];
   t_time_nei = enable != 0;
+  return HBEGP_OK;
+}
+}  // extern "C"
+
+// argument checks of hbegp_ehvi_* / hbegp_maximize_ehvi_*: everything is refused before any device call, the checks that need no
+// model first
+template <typename T>
+static int check_ehvi_models(hbegp_model* const* models, int n_obj, const double* front, int P, const double* ref) {
+  if (n_obj != 2) return fail(HBEGP_EINVAL, "n_obj must be 2 (got %d)", n_obj);
+  if (P < 0) return fail(HBEGP_EINVAL, "P must be >= 0 (got %d)", P);
+  if (!models) return fail(HBEGP_EINVAL, "models is NULL");
+  if (!models[0] || !models[1]) return fail(HBEGP_EINVAL, "NULL model");
+  if (models[0] == models[1]) return fail(HBEGP_EINVAL, "the same model was passed for both objectives");
+  for (int k = 0; k < 2; ++k)
+    if (models[k]->is_f32 != (sizeof(T) == 4)) return fail(HBEGP_EINVAL, "model %d holds %s data", k, models[k]->is_f32 ? "f32" : "f64");
+  if (models[0]->d != models[1]->d) return fail(HBEGP_EINVAL, "the models differ in d (%d and %d)", models[0]->d, models[1]->d);
+  if (models[0]->dev != models[1]->dev)
+    return fail(HBEGP_EINVAL, "the models live on different devices (%d and %d)", models[0]->dev, models[1]->dev);
+  if (!ref) return fail(HBEGP_EINVAL, "ref is NULL");
+  if (P > 0 && !front) return fail(HBEGP_EINVAL, "front is NULL");
+  if (!std::isfinite(ref[0]) || !std::isfinite(ref[1])) return fail(HBEGP_EINVAL, "non-finite reference point");
+  for (size_t i = 0; i < 2 * (size_t)P; ++i)
+    if (!std::isfinite(front[i])) return fail(HBEGP_EINVAL, "non-finite front value (point %d)", (int)(i / 2));
+  return HBEGP_OK;
+}
+template <typename T>
+static int do_ehvi(hbegp_model* const* models, int n_obj, const T* Xs, int m, const double* front, int P, const double* ref, double* ehvi,
+                   T* grad, int* best, T* mean, T* var) {
+  if (m < 0) return fail(HBEGP_EINVAL, "m must be >= 0 (got %d)", m);
+  if (int rc = check_ehvi_models<T>(models, n_obj, front, P, ref)) return rc;
+  if (m > 0 && (!Xs || !ehvi)) return fail(HBEGP_EINVAL, "Xs/ehvi is NULL");
+  if (best) *best = -1;
+  if (m == 0) return HBEGP_OK;
+  GUARD_BEGIN
+  std::vector<double> thr;
+  const int ns = ehvi_thresholds(front, P, ref, &thr);
+  EhviJoin join(models[0]->dev);
+  return model_ehvi<T>(models, Xs, m, thr, ns, join.ev, ehvi, grad, best, mean, var);
+  GUARD_END
+}
+template <typename T>
+static int do_maximize_ehvi(hbegp_model* const* models, int n_obj, const T* starts, int S, const double* lo, const double* hi,
+                            const double* front, int P, const double* ref, int maxeval, T* x_out, double* ehvi_out, int* nevals_out) {
+  if (S < 1) return fail(HBEGP_EINVAL, "S must be >= 1 (got %d)", S);
+  if (int rc = check_ehvi_models<T>(models, n_obj, front, P, ref)) return rc;
+  if (int rc = check_maximize_ei<T>(models[0], starts, S, lo, hi, 0.0, maxeval, x_out, ehvi_out)) return rc;
+  GUARD_BEGIN
+  std::vector<double> thr;
+  const int ns = ehvi_thresholds(front, P, ref, &thr);
+  return model_maximize_ehvi<T>(models, starts, S, lo, hi, thr, ns, maxeval, x_out, ehvi_out, nevals_out);
+  GUARD_END
+}
+extern "C" {
+int hbegp_ehvi_f64(hbegp_model* const* models, int n_obj, const double* Xs, int m, const double* front, int P, const double* ref,
+                   double* ehvi, double* grad, int* best, double* mean, double* var) {
+  return do_ehvi<double>(models, n_obj, Xs, m, front, P, ref, ehvi, grad, best, mean, var);
+}
+int hbegp_ehvi_f32(hbegp_model* const* models, int n_obj, const float* Xs, int m, const double* front, int P, const double* ref,
+                   double* ehvi, float* grad, int* best, float* mean, float* var) {
+  return do_ehvi<float>(models, n_obj, Xs, m, front, P, ref, ehvi, grad, best, mean, var);
+}
+int hbegp_maximize_ehvi_f64(hbegp_model* const* models, int n_obj, const double* starts, int S, const double* lo, const double* hi,
+                            const double* front, int P, const double* ref, int maxeval, double* x_out, double* ehvi_out, int* nevals_out) {
+  return do_maximize_ehvi<double>(models, n_obj, starts, S, lo, hi, front, P, ref, maxeval, x_out, ehvi_out, nevals_out);
+}
+int hbegp_maximize_ehvi_f32(hbegp_model* const* models, int n_obj, const float* starts, int S, const double* lo, const double* hi,
+                            const double* front, int P, const double* ref, int maxeval, float* x_out, double* ehvi_out, int* nevals_out) {
+  return do_maximize_ehvi<float>(models, n_obj, starts, S, lo, hi, front, P, ref, maxeval, x_out, ehvi_out, nevals_out);
+}
+int hbegp_debug_ehvi_phases(int enable, double* phase_ms) {
+  if (phase_ms)
+    for (int i = 0; i < 3; ++i) phase_ms[i] = t_ehvi_ms[i];
+  t_time_ehvi = enable != 0;
   return HBEGP_OK;
 }
 }  // extern "C"

@@ -4452,6 +4452,172 @@ PATHS_INST(double)
 PATHS_INST(float)
 #undef PATHS_INST
 
+// =================================================================================================================
+// expected hypervolume improvement of two independent objectives over a candidate set (hbegp.cpp: model_ehvi).
+// The host reduces the front to P non-dominated points inside the reference box, a ascending and b descending, and hands over
+// ns = P + 1 strips: strip i spans objective 0 from a_i (a_0 = -inf) to up[i] = a_{i+1} (up[P] = r1) below the height
+// hb[i] = b_i (hb[0] = r2).  thr = [up | hb].  With G_k(t) = E[(t - Y_k)^+] = sigma_k h((t - mu_k) / sigma_k), h(z) = z Phi(z) + phi(z),
+//   EHVI = sum_i [G_1(up_i) - G_1(up_{i-1})] G_2(hb_i),   dG/dmu = -Phi(z),  dG/dsigma = phi(z).
+// One WAVE per candidate, EHVI_WAVES candidates per workgroup; lane l takes the strips l, l + 64, ..: it evaluates (G_1, Phi, phi)
+// at up_i and (G_2, Phi, phi) at hb_i once each and takes the values at up_{i-1} from lane l - 1 (lane 0: from lane 63's previous
+// strip, nothing for strip 0) -- the same function of the same threshold, so the same bits as evaluating it twice.  Each lane adds
+// its strips in ascending order into five sums (the value and the partials w.r.t. mu_1, sigma_1, mu_2, sigma_2), which then go
+// through one xor butterfly (a fixed tree: every lane ends with the same bits).  Lane k < d forms grad[j][k] by the chain rule,
+// dsigma = dvar / (2 sigma).  All of it in fp64 for both element types, the five sums with or without a gradient: a candidate's
+// bits depend on nothing but its own posterior and the thresholds.  sigma = 0 (ei_with_gradient's test): G(t) = (t - mu)^+,
+// Phi = [t > mu], phi = 0 and dsigma counts as 0.  A NaN in a candidate's posterior gives NaN in its value and its gradient row.
+// The thresholds are staged in dynamic LDS up to EHVI_LDS_STRIPS strips (16 bytes each); beyond, they are read from global memory
+// (every wave reads the same few KiB: they stay in the L2).
+// =================================================================================================================
+constexpr int EHVI_WAVES = 4;
+
+struct EhviG {
+  double g, cdf, pdf;  // G(t), Phi(z), phi(z)
+};
+// not inlined: erfc's fp64 coefficients (as kg_tail, whose evaluation of phi(a) - a Phi(-a) this is for z <= 0; h(z) = z + h(-z)
+// above).  Beyond |z| = 38 the tail terms are below 1e-314.
+__device__ __noinline__ EhviG ehvi_g(double t, double mu, double sd) {
+  EhviG r;
+  if (!(sd > 2.220446049250313e-16)) {  // sigma = 0
+    r.g = fmax(t - mu, 0.0);
+    r.cdf = t > mu ? 1.0 : 0.0;
+    r.pdf = 0.0;
+    return r;
+  }
+  const double z = (t - mu) / sd;
+  const double az = fabs(z);
+  double tail = 0.0, cl = 0.0, pdf = 0.0;  // h(-|z|), Phi(-|z|), phi(z)
+  if (az < 38.0) {
+    cl = 0.5 * erfc(az / 1.4142135623730951);
+    pdf = exp(-0.5 * az * az) / 2.5066282746310002;
+    tail = fmax(pdf - az * cl, 0.0);
+  }
+  r.g = sd * (z > 0.0 ? z + tail : tail);
+  r.cdf = z > 0.0 ? 1.0 - cl : cl;
+  r.pdf = pdf;
+  return r;
+}
+
+__device__ __forceinline__ double ehvi_wave_sum(double v) {
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+template <typename T, bool LDS>
+__global__ void __launch_bounds__(64 * EHVI_WAVES) ehvi_kernel(const T* __restrict__ mean1, const T* __restrict__ var1,
+                                                               const T* __restrict__ dmean1, const T* __restrict__ dvar1,
+                                                               const T* __restrict__ mean2, const T* __restrict__ var2,
+                                                               const T* __restrict__ dmean2, const T* __restrict__ dvar2, int m, int d,
+                                                               const double* __restrict__ thr, int ns, int want_grad,
+                                                               double* __restrict__ ehvi, T* __restrict__ grad) {
+  extern __shared__ __align__(16) char smem_raw[];
+  const double* up = thr;
+  const double* hb = thr + ns;
+  if (LDS) {
+    double* st = reinterpret_cast<double*>(smem_raw);
+    for (int i = threadIdx.x; i < 2 * ns; i += 64 * EHVI_WAVES) st[i] = thr[i];
+    __syncthreads();
+    up = st;
+    hb = st + ns;
+  }
+  const int lane = threadIdx.x & 63;
+  const int j = blockIdx.x * EHVI_WAVES + (threadIdx.x >> 6);
+  if (j >= m) return;  // whole waves leave, behind the only barrier
+  const double mu1 = (double)mean1[j], v1 = (double)var1[j], mu2 = (double)mean2[j], v2 = (double)var2[j];
+  const double sd1 = sqrt(v1), sd2 = sqrt(v2);
+  const bool bad = (mu1 != mu1) || (v1 != v1) || (mu2 != mu2) || (v2 != v2);
+  double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0, s4 = 0.0;
+  EhviG carry = {0.0, 0.0, 0.0};  // lane 63's upper threshold of the previous chunk (strip 0: G_1(-inf) = 0)
+  for (int base = 0; base < ns; base += 64) {  // a uniform trip count: every lane takes part in the shuffles
+    const int i = base + lane;
+    const bool on = i < ns;
+    EhviG u = {0.0, 0.0, 0.0}, h = {0.0, 0.0, 0.0};
+    if (on) {
+      u = ehvi_g(up[i], mu1, sd1);
+      h = ehvi_g(hb[i], mu2, sd2);
+    }
+    EhviG lo;
+    lo.g = __shfl_up(u.g, 1, 64);
+    lo.cdf = __shfl_up(u.cdf, 1, 64);
+    lo.pdf = __shfl_up(u.pdf, 1, 64);
+    if (lane == 0) lo = carry;
+    carry.g = __shfl(u.g, 63, 64);
+    carry.cdf = __shfl(u.cdf, 63, 64);
+    carry.pdf = __shfl(u.pdf, 63, 64);
+    if (on) {
+      const double dg = u.g - lo.g;
+      s0 += fmax(dg, 0.0) * h.g;            // G_1 is monotone: a negative difference is rounding
+      s1 += (lo.cdf - u.cdf) * h.g;         // d/dmu_1
+      s2 += (u.pdf - lo.pdf) * h.g;         // d/dsigma_1
+      s3 -= dg * h.cdf;                     // d/dmu_2
+      s4 += dg * h.pdf;                     // d/dsigma_2
+    }
+  }
+  s0 = ehvi_wave_sum(s0);
+  s1 = ehvi_wave_sum(s1);
+  s2 = ehvi_wave_sum(s2);
+  s3 = ehvi_wave_sum(s3);
+  s4 = ehvi_wave_sum(s4);
+  const double nan = __longlong_as_double(0x7ff8000000000000LL);
+  if (lane == 0) ehvi[j] = bad ? nan : s0;
+  if (want_grad && lane < d) {
+    const size_t e = (size_t)j * d + lane;
+    const double ds1 = sd1 > 2.220446049250313e-16 ? (double)dvar1[e] / (2.0 * sd1) : 0.0;
+    const double ds2 = sd2 > 2.220446049250313e-16 ? (double)dvar2[e] / (2.0 * sd2) : 0.0;
+    double g = s1 * (double)dmean1[e];
+    g += s2 * ds1;
+    g += s3 * (double)dmean2[e];
+    g += s4 * ds2;
+    grad[e] = bad ? (T)nan : (T)g;
+  }
+}
+
+// best = the LAST index of the maximum of v[0 .. m) through a fixed LDS tree (kg_epilogue_kernel's rule); a NaN never wins,
+// -1 where no entry is a number
+__global__ void __launch_bounds__(BSEL_THREADS) ehvi_best_kernel(const double* __restrict__ v, int m, int* __restrict__ res) {
+  __shared__ double sv[BSEL_THREADS];
+  __shared__ int si[BSEL_THREADS];
+  const int tid = threadIdx.x;
+  double best = 0.0;
+  int bi = -1;
+  for (int i = tid; i < m; i += BSEL_THREADS) {
+    const double e = v[i];
+    if (e == e && (bi < 0 || e >= best)) { best = e; bi = i; }  // ascending i: an equal value moves to the later index
+  }
+  sv[tid] = best;
+  si[tid] = bi;
+  __syncthreads();
+#pragma unroll 1
+  for (int w = BSEL_THREADS / 2; w > 0; w >>= 1) {
+    if (tid < w) {
+      const double o = sv[tid + w];
+      const int oi = si[tid + w];
+      if (oi >= 0 && (si[tid] < 0 || o > sv[tid] || (o == sv[tid] && oi > si[tid]))) { sv[tid] = o; si[tid] = oi; }
+    }
+    __syncthreads();
+  }
+  if (tid == 0) res[0] = si[0];
+}
+
+template <typename T>
+void launch_ehvi(const T* mean1, const T* var1, const T* dmean1, const T* dvar1, const T* mean2, const T* var2, const T* dmean2,
+                 const T* dvar2, int m, int d, const double* thr, int ns, int want_grad, double* ehvi, T* grad, int* best,
+                 hipStream_t s) {
+  const dim3 grid((unsigned)((m + EHVI_WAVES - 1) / EHVI_WAVES)), block(64 * EHVI_WAVES);
+  if (ns <= EHVI_LDS_STRIPS)
+    hipLaunchKernelGGL((ehvi_kernel<T, true>), grid, block, ehvi_lds_bytes(ns), s, mean1, var1, dmean1, dvar1, mean2, var2, dmean2, dvar2,
+                       m, d, thr, ns, want_grad, ehvi, grad);
+  else
+    hipLaunchKernelGGL((ehvi_kernel<T, false>), grid, block, 0, s, mean1, var1, dmean1, dvar1, mean2, var2, dmean2, dvar2, m, d, thr, ns,
+                       want_grad, ehvi, grad);
+  hipLaunchKernelGGL(ehvi_best_kernel, dim3(1), dim3(BSEL_THREADS), 0, s, ehvi, m, best);
+}
+template void launch_ehvi<double>(const double*, const double*, const double*, const double*, const double*, const double*, const double*,
+                                  const double*, int, int, const double*, int, int, double*, double*, int*, hipStream_t);
+template void launch_ehvi<float>(const float*, const float*, const float*, const float*, const float*, const float*, const float*,
+                                 const float*, int, int, const double*, int, int, double*, float*, int*, hipStream_t);
+
 // Per-device one-time setup: kernels that use more than 64 KiB of dynamic LDS need the attribute raised.  Called from
 // hbegp_ctx_create() for every device, before any stream capture.
 static void init_dag_kernels();  // dag_kernel.inc.hpp (end of this file)

@@ -105,6 +105,12 @@ SIGNATURES = {
     "hbegp_knowledge_gradient_f32": (C.c_int, [_vp, _fp, C.c_int, C.c_int, _dp, _ip, _ip, _fp, _fp]),
     "hbegp_noisy_ei_f64": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, C.c_int, C.c_double, _dp, _ip, _dp, _dp, _ip]),
     "hbegp_noisy_ei_f32": (C.c_int, [_vp, _fp, C.c_int, C.c_int, _fp, C.c_int, C.c_double, _dp, _ip, _dp, _dp, _ip]),
+    "hbegp_ehvi_f64": (C.c_int, [C.POINTER(_vp), C.c_int, _dp, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _ip, _dp, _dp]),
+    "hbegp_ehvi_f32": (C.c_int, [C.POINTER(_vp), C.c_int, _fp, C.c_int, _dp, C.c_int, _dp, _dp, _fp, _ip, _fp, _fp]),
+    "hbegp_maximize_ehvi_f64": (C.c_int, [C.POINTER(_vp), C.c_int, _dp, C.c_int, _dp, _dp, _dp, C.c_int, _dp, C.c_int, _dp, _dp,
+                                          _ip]),
+    "hbegp_maximize_ehvi_f32": (C.c_int, [C.POINTER(_vp), C.c_int, _fp, C.c_int, _dp, _dp, _dp, C.c_int, _dp, C.c_int, _fp, _dp,
+                                          _ip]),
     "hbegp_sobol_f64": (C.c_int, [_vp, _dp, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "hbegp_sobol_f32": (C.c_int, [_vp, _fp, _fp, C.c_int, _dp, _dp, _dp, _dp, _fp, _fp, _fp]),
     "hbegp_main_effects_f64": (C.c_int, [_vp, _dp, C.c_int, _dp, C.c_int, _dp, _dp]),
@@ -138,6 +144,7 @@ SIGNATURES = {
     "hbegp_debug_kg_phases": (C.c_int, [C.c_int, _dp]),
     "hbegp_debug_nei_phases": (C.c_int, [C.c_int, _dp]),
     "hbegp_debug_sens_phases": (C.c_int, [C.c_int, _dp]),
+    "hbegp_debug_ehvi_phases": (C.c_int, [C.c_int, _dp]),
     "hbegp_model_info": (C.c_int, [_vp, _ip, _ip, _ip, _dp, _dp]),
     "hbegp_model_get_f64": (C.c_int, [_vp, _dp, _dp, _dp]),
     "hbegp_model_get_f32": (C.c_int, [_vp, _dp, _fp, _fp]),

@@ -573,6 +573,143 @@ def acquire_by_knowledge_gradient(candidates, model, k, n_candidates=None, ctx=N
     return np.array(idx, dtype=np.int64), model.y_norm.project_location_from_normalized(means), np.array(kgs, dtype=np.float64)
 
 
+def pareto_front(y2):
+    """The non-dominated rows of y2 [N, 2] when both columns are minimised, sorted by the first column ascending (the second then
+    descends strictly); duplicates appear once.  float64 [P, 2]."""
+    y = np.asarray(y2, dtype=np.float64).reshape(-1, 2)
+    y = y[np.lexsort((y[:, 1], y[:, 0]))]
+    keep, bmin = [], math.inf
+    for i in range(len(y)):
+        if y[i, 1] < bmin:  # among equal first values the lowest second one comes first and dominates the others
+            keep.append(i)
+            bmin = y[i, 1]
+    return y[keep]
+
+
+def hypervolume_2d(front, ref):
+    """The area that the points of front [..., P, 2] dominate inside the box below ref [2], both objectives minimised: a sweep
+    over the points sorted by the first objective with the running minimum of the second.  Points need not be non-dominated, nor
+    inside the box (those add nothing).  A leading shape is a batch of fronts: returns a float, or an array of that shape."""
+    f = np.asarray(front, dtype=np.float64)
+    r1, r2 = float(ref[0]), float(ref[1])
+    if f.size == 0:
+        return 0.0 if f.ndim <= 2 else np.zeros(f.shape[:-2])
+    a = np.minimum(f[..., 0], r1)
+    b = np.minimum(f[..., 1], r2)
+    order = np.argsort(a, axis=-1, kind="stable")
+    a = np.take_along_axis(a, order, axis=-1)
+    b = np.minimum.accumulate(np.take_along_axis(b, order, axis=-1), axis=-1)
+    nxt = np.concatenate([a[..., 1:], np.full(a.shape[:-1] + (1,), r1)], axis=-1)
+    hv = ((nxt - a) * (r2 - b)).sum(axis=-1)
+    return float(hv) if np.ndim(hv) == 0 else hv
+
+
+def default_reference_point(front):
+    """The reference point used where none is given: per objective the worst value of front [P >= 1, 2] plus 10 % of the front's
+    range in that objective; where the range is 0 (a one-point front) plus 10 % of max(1, |value|)."""
+    f = np.asarray(front, dtype=np.float64).reshape(-1, 2)
+    if len(f) < 1:
+        raise ValueError("an empty front has no default reference point")
+    worst, span = f.max(axis=0), f.max(axis=0) - f.min(axis=0)
+    return worst + 0.1 * np.where(span > 0, span, np.maximum(1.0, np.abs(worst)))
+
+
+def _ehvi_normalized(models, front, ref):
+    """front [P, 2] and ref [2] in y units -> each column through that model's YNormalize (float64).  The projections are monotone
+    increasing, so dominance, the front and the inside of the box are preserved."""
+    if len(models) != 2:
+        raise ValueError("EHVI takes exactly two models")
+    f = np.asarray(front if front is not None else [], dtype=np.float64).reshape(-1, 2)
+    r = np.asarray(ref, dtype=np.float64).reshape(2)
+    fn = np.stack([np.asarray(mo.y_norm.project_into_normalized(f[:, k]), dtype=np.float64) for k, mo in enumerate(models)], axis=1)
+    rn = np.array([float(mo.y_norm.project_into_normalized(r[k:k + 1])[0]) for k, mo in enumerate(models)])
+    return fn, rn
+
+
+# Two-objective expected hypervolume improvement (opt-in; nothing the estimator suggests by default uses it).
+def ehvi_a(models, x, front, ref):
+    """EHVI of the rows of x [m, d] under two SurrogateModelGPRs (objective 0, objective 1), both minimised and taken as
+    independent (gpr.ehvi).  front [P, 2] and ref [2] are in y units; each column goes through that model's y projection.  The
+    AREA is measured in the normalised units of the two models, as knowledge_gradient_a returns KG: under the logarithmic
+    projection it is not an area in y units, but the front, the box and the ranking of dominance are those of the y units.
+    Returns (ehvi[m] float64, best): best the last index of the maximum, -1 without rows."""
+    fn, rn = _ehvi_normalized(models, front, ref)
+    return gpr.ehvi([mo.fitted for mo in models], np.asarray(x, dtype=models[0].dtype), fn, rn)
+
+
+def maximize_ehvi(models, starts, bounds, front, ref, maxeval=150):
+    """Bounded L-BFGS ascents of ehvi_a from every row of `starts` (the box: `bounds` = [(lo, hi)] per feature), all runs in
+    lockstep on the two device models (gpr.maximize_ehvi).  front and ref in y units.  Returns (x[S, d], ehvi[S], nevals[S])."""
+    fn, rn = _ehvi_normalized(models, front, ref)
+    return gpr.maximize_ehvi([mo.fitted for mo in models], np.asarray(starts, dtype=models[0].dtype), bounds, fn, rn, maxeval=maxeval)
+
+
+def _ehvi_default_front(models):
+    """pareto_front of the two models' training targets in y units; the models must have been trained on the very same rows."""
+    fks = [mo.fitted for mo in models]
+    xs = [fk.x_train for fk in fks]
+    if any(x is None for x in xs) or any(fk.y_train is None for fk in fks):
+        raise ValueError("the models do not hold their training rows: pass a front")
+    if xs[0].shape != xs[1].shape or xs[0].tobytes() != xs[1].tobytes():
+        raise ValueError("the models were not trained on the same rows: pass a front")
+    y = [np.asarray(mo.y_norm.project_location_from_normalized(np.asarray(mo.fitted.y_train)), dtype=np.float64) for mo in models]
+    return pareto_front(np.stack(y, axis=1))
+
+
+def acquire_by_ehvi(candidates, models, k, front=None, ref=None, ctx=None):
+    """Batch acquisition for two minimised objectives by the expected hypervolume improvement over a candidate set [m, n_features]:
+    k distinct rows, each the row of largest EHVI (gpr.ehvi: closed form, no random numbers) under the two SurrogateModelGPRs
+    `models`.  After a pick BOTH surrogates are conditioned on the kriging-believer fantasy (x_pick, that model's posterior mean)
+    through extend_with at the same theta, as acquire_by_knowledge_gradient does, and the believed point joins the front.  front
+    [P, 2] and ref [2] are in y units.  Without a front: pareto_front of the two models' training targets, which needs models
+    trained on the very same rows (else ValueError).  Without a ref: default_reference_point of the front.  Returns (idx[k] int64,
+    the projected means [k, 2] of the picks at the time they were picked, ehvi[k] and the believed hypervolume hv[k] after each
+    pick, both in the normalised units of ehvi_a).  Opt-in: nothing the estimator suggests by default calls it."""
+    if len(models) != 2:
+        raise ValueError("EHVI takes exactly two models")
+    dtype = models[0].dtype
+    c = np.asarray(candidates, dtype=dtype)
+    if c.ndim != 2:
+        raise ValueError("candidates must be [m, n_features]")
+    k = int(k)
+    if not 0 <= k <= c.shape[0]:
+        raise ValueError("k must lie in [0, number of rows]")
+    if front is None:
+        front = _ehvi_default_front(models)
+    if ref is None:
+        ref = default_reference_point(front)
+    fn, rn = _ehvi_normalized(models, front, ref)
+    fks = [mo.fitted for mo in models]
+    data = [(fk.x_train, fk.y_train) for fk in fks]
+    if k > 1 and any(X is None or y is None for X, y in data):
+        raise ValueError("the models do not hold their training rows: they cannot be conditioned on a fantasy")
+    avail = list(range(c.shape[0]))
+    idx, means, vals, hvs = [], [], [], []
+    try:
+        for t in range(k):
+            val, best, mean, _ = gpr.ehvi(fks, c[avail], fn, rn, want_posterior=True)
+            idx.append(avail.pop(best))
+            means.append(mean[best])
+            vals.append(val[best])
+            fn = np.vstack([fn, np.asarray(mean[best], dtype=np.float64)[None, :]])
+            hvs.append(hypervolume_2d(fn, rn))
+            if t + 1 < k:
+                for o in range(2):
+                    X, y = data[o]
+                    data[o] = (np.vstack([X, c[idx[-1]:idx[-1] + 1]]), np.concatenate([y, mean[best, o:o + 1]]))
+                    nxt = fks[o].extend_with(*data[o], ctx=ctx)
+                    if fks[o] is not models[o].fitted:
+                        fks[o].release()
+                    fks[o] = nxt
+    finally:
+        for o in range(2):
+            if fks[o] is not models[o].fitted:
+                fks[o].release()
+    means = np.array(means, dtype=dtype).reshape(-1, 2)
+    proj = np.stack([models[o].y_norm.project_location_from_normalized(means[:, o]) for o in range(2)], axis=1)
+    return np.array(idx, dtype=np.int64), proj, np.array(vals, dtype=np.float64), np.array(hvs, dtype=np.float64)
+
+
 def _nei_baseline(fk, baseline, max_baseline, dtype):
     """The baseline of a noisy-EI call: `baseline` or the model's training rows; with max_baseline the rows of lowest posterior
     mean under fk (ties to the lower index), kept in their order."""

@@ -676,6 +676,61 @@ def draw_spectral(nu, n_features, d, rng):
     return omega0, phase
 
 
+def _ehvi_args(models, front, ref):
+    """(handle array, suffix, dtype, d, front [P, 2] float64, ref [2] float64) of a two-objective call."""
+    models = list(models)
+    handles = (C.c_void_p * max(len(models), 1))(*[fk._h for fk in models])
+    fk = models[0]
+    front = _lib.as_c(np.asarray(front if front is not None else [], dtype=np.float64).reshape(-1, 2), np.float64)
+    ref = _lib.as_c(np.asarray(ref, dtype=np.float64).reshape(2), np.float64)
+    return models, handles, fk._sfx, fk.dtype, fk.d, front, ref
+
+
+def ehvi(models, x, front, ref, want_grad=False, want_posterior=False):
+    """Expected hypervolume improvement of two minimised objectives (hbegp_ehvi_*), in the models' normalised y spaces:
+    models = (objective 0, objective 1), two FittedKernels of the same d, element type and device, taken as independent;
+    front [P, 2] the points reached so far, in any order (dominated points, duplicates and points outside the box change nothing);
+    ref [2] the reference point.  Returns (ehvi[m] float64, best) -- best the last index of the maximum, -1 for m = 0 -- then
+    grad[m, d] with want_grad, then (mean[m, 2], var[m, 2]) with want_posterior: predict()'s numbers, bit for bit."""
+    models, handles, sfx, dtype, d, front, ref = _ehvi_args(models, front, ref)
+    x = _lib.as_c(np.asarray(x, dtype=dtype).reshape(-1, d), dtype)
+    m = x.shape[0]
+    val = np.zeros(m)
+    best = C.c_int(-1)
+    grad = np.zeros((m, d), dtype=dtype) if want_grad else None
+    mean = np.zeros((m, 2), dtype=dtype) if want_posterior else None
+    var = np.zeros((m, 2), dtype=dtype) if want_posterior else None
+    fn = getattr(_lib.load(), f"hbegp_ehvi_{sfx}")
+    _lib.check(fn(handles, len(models), _lib.aptr(x), m, _lib.dptr(front), front.shape[0], _lib.dptr(ref), _lib.dptr(val),
+                  _lib.aptr(grad), C.byref(best), _lib.aptr(mean), _lib.aptr(var)))
+    out = (val, best.value)
+    if want_grad:
+        out += (grad,)
+    if want_posterior:
+        out += (mean, var)
+    return out
+
+
+def maximize_ehvi(models, starts, bounds, front, ref, maxeval=150):
+    """S bounded L-BFGS runs maximising ehvi() over the box (hbegp_maximize_ehvi_*), one batched gradient predict per model and
+    round.  starts: [S, d] inside the box; bounds: d pairs (lo, hi).  Returns (x[S, d], ehvi[S], nevals[S]): each run's best
+    point, never worse than its start; ehvi(models, x, front, ref) reproduces the values bit for bit."""
+    models, handles, sfx, dtype, d, front, ref = _ehvi_args(models, front, ref)
+    starts = _lib.as_c(np.atleast_2d(starts), dtype)
+    assert starts.shape[1] == d
+    S = starts.shape[0]
+    bounds = np.asarray(bounds, dtype=np.float64).reshape(d, 2)
+    lo = _lib.as_c(bounds[:, 0], np.float64)
+    hi = _lib.as_c(bounds[:, 1], np.float64)
+    x = np.zeros((S, d), dtype=dtype)
+    val = np.zeros(S)
+    nevals = np.zeros(S, dtype=np.int32)
+    fn = getattr(_lib.load(), f"hbegp_maximize_ehvi_{sfx}")
+    _lib.check(fn(handles, len(models), _lib.aptr(starts), S, _lib.dptr(lo), _lib.dptr(hi), _lib.dptr(front), front.shape[0],
+                  _lib.dptr(ref), int(maxeval), _lib.aptr(x), _lib.dptr(val), nevals.ctypes.data_as(C.POINTER(C.c_int))))
+    return x, val, nevals
+
+
 def minimize_by_gradient(objective, x0, bounds, maxeval=150):
     """util::minimize_by_gradient (gradmin.rs:35-60) through the library's bounded L-BFGS."""
     lib = _lib.load()

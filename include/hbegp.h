@@ -377,6 +377,48 @@ int hbegp_noisy_ei_f64(hbegp_model* model, const double* Xs, int m, int mb, cons
 int hbegp_noisy_ei_f32(hbegp_model* model, const float* Xs, int m, int mb, const float* z, int S, double jitter, double* nei,
                        int* best, double* fmin_draws, double* rho, int* info);
 
+/* Expected hypervolume improvement (EHVI) of TWO objectives, both minimised, each modelled by its own model; the two posteriors
+ * are taken as independent.  Everything is in each model's normalised y space.  models[n_obj]: objective 0 then objective 1
+ * (n_obj must be 2); they share d, the element type and the device and may differ in n and nu.  At a row of Xs[m*d] objective k has
+ * the posterior N(mu_k, sigma_k^2) of hbegp_predict_* (the variance clamped at 0, without the noise).  ref[2] is the reference point
+ * r = (r1, r2), front[P*2] the caller's points (a_i, b_i) in any order -- both always double, like bounds.  The library reduces the
+ * front on the host to its non-dominated points strictly inside the box (a_i < r1, b_i < r2), sorted by a ascending (b descends), with
+ * a_0 = -inf, a_{P+1} = r1, b_0 = r2: dominated points, duplicates and points outside the box change nothing, bit for bit.  With
+ *   G_k(t) = E[(t - Y_k)^+] = sigma_k h((t - mu_k) / sigma_k),  h(z) = z Phi(z) + phi(z),  G_k(-inf) = 0,
+ *   ehvi = sum_{i=0..P} [G_1(a_{i+1}) - G_1(a_i)] G_2(b_i) >= 0
+ * is the expected area, inside the box, that the point would add to what the front dominates; P = 0 gives G_1(r1) G_2(r2).
+ * dG/dmu = -Phi(z) and dG/dsigma = phi(z) give the partials from the same sum; grad[m*d] (may be NULL: then no gradient launch is
+ * issued) follows through hbegp_predict_grad_*'s dmean and dvar with dsigma = dvar / (2 sigma).  sigma_k = 0: G_k(t) = (t - mu_k)^+
+ * and dsigma_k counts as 0, as in hbegp_maximize_ei_*.  h is evaluated without cancellation (phi(a) - a Phi(-a) for z = -a <= 0,
+ * z + h(-z) above).  All arithmetic and sums are fp64 for both element types, in a fixed order without atomics: ehvi is double, and a
+ * row's bits depend neither on m, nor on its position, nor on whether a gradient was asked for.
+ * ehvi[m] (required for m > 0); best (may be NULL): the LAST index of the maximum of ehvi, as hbegp_knowledge_gradient_* (a NaN never
+ * wins; -1 for m = 0); mean[m*2], var[m*2] (each may be NULL): row j holds objective 0 then objective 1, bit for bit what
+ * hbegp_predict_* returns on its batched path (m > 16), or hbegp_predict_grad_* with a gradient.  A NaN coordinate gives NaN in
+ * that row of ehvi and grad only.  m = 0 is a no-op.
+ * HBEGP_EINVAL (before any device call) for n_obj != 2, a NULL model, the same model twice, models of different d, element type or
+ * device, a model of the other element type, m < 0, P < 0, a NULL Xs or ehvi with m > 0, a NULL ref, a NULL front with P > 0, or a
+ * non-finite front or ref value.  Both models are locked for the call, in a fixed order: calls that name them in either order never
+ * wait for each other.  Each model's predict runs on its own stream; thresholds and outputs are borrowed for the call; work that
+ * does not fit in device memory is HBEGP_ENOMEM. */
+int hbegp_ehvi_f64(hbegp_model* const* models, int n_obj, const double* Xs, int m, const double* front, int P, const double* ref,
+                   double* ehvi, double* grad, int* best, double* mean, double* var);
+int hbegp_ehvi_f32(hbegp_model* const* models, int n_obj, const float* Xs, int m, const double* front, int P, const double* ref,
+                   double* ehvi, float* grad, int* best, float* mean, float* var);
+/* S bounded L-BFGS runs maximising hbegp_ehvi_* over the box [lo, hi] in lockstep, with the contract of hbegp_maximize_ei_*
+ * (lbfgs_step.hpp with the fit's constants): every round is one batched gradient predict per model over the runs still going and
+ * the EHVI kernel with its gradient.  starts[S*d] inside the box; x_out[S*d], ehvi_out[S]: each run's best evaluated point (never
+ * worse than its start; an f32 run evaluates and returns f32 points of the box) -- hbegp_ehvi_* at x_out reproduces ehvi_out bit
+ * for bit; nevals_out[S] (may be NULL) <= maxeval.  A NaN prediction is a failed evaluation.  HBEGP_EINVAL for everything
+ * hbegp_ehvi_* refuses about models, front and ref, and for S < 1, a NULL starts / lo / hi / x_out / ehvi_out, maxeval < 1,
+ * lo > hi or a start outside the box. */
+int hbegp_maximize_ehvi_f64(hbegp_model* const* models, int n_obj, const double* starts, int S, const double* lo, const double* hi,
+                            const double* front, int P, const double* ref, int maxeval, double* x_out, double* ehvi_out,
+                            int* nevals_out);
+int hbegp_maximize_ehvi_f32(hbegp_model* const* models, int n_obj, const float* starts, int S, const double* lo, const double* hi,
+                            const double* front, int P, const double* ref, int maxeval, float* x_out, double* ehvi_out,
+                            int* nevals_out);
+
 /* Sensitivity of the posterior mean mu (hbegp_predict_*'s mean, normalised y space) to each feature, from the CALLER's sample
  * matrices in the feature coordinates the model was fitted on (the RNG stays on the caller side).  Both calls evaluate the mean at
  * base rows with ONE coordinate substituted,
@@ -553,6 +595,10 @@ int hbegp_debug_kg_phases(int enable, double* phase_ms);
  * draw products (with the upload of z), the reductions -- in milliseconds; then enable != 0 makes this thread's later noisy-EI
  * calls timed. */
 int hbegp_debug_nei_phases(int enable, double* phase_ms);
+/* ---- timing hook (tools/ehvi_bench.py): phase_ms[3] (may be NULL) receives the device time of the phases of the calling thread's
+ * last timed hbegp_ehvi_* call -- objective 0's predict and objective 1's (each with its upload, on its own stream: they overlap),
+ * the EHVI kernel with the arg-max -- in milliseconds; then enable != 0 makes this thread's later EHVI calls timed. */
+int hbegp_debug_ehvi_phases(int enable, double* phase_ms);
 /* ---- timing hook (tools/sens_bench.py): phase_ms[4] (may be NULL) receives the device time of the phases of the calling thread's
  * last timed hbegp_sobol_* / hbegp_main_effects_* call -- the upload (with the grid's scaling), the substituted means, the chunk and
  * row sums (both summed over the slabs), the final reduction with the downloads -- in milliseconds; then enable != 0 makes this

@@ -88,6 +88,12 @@ template <> struct Abi<double> {
   static int paths_minimize(hbegp_paths* p, const double* st, int R, const double* lo, const double* hi, int maxeval, double* x, double* f, int* ne) {
     return hbegp_paths_minimize_f64(p, st, R, lo, hi, maxeval, x, f, ne);
   }
+  static int ehvi(hbegp_model* const* ms, int no, const double* xs, int m, const double* front, int P, const double* ref, double* v, double* g, int* best,
+                  double* mean, double* var) { return hbegp_ehvi_f64(ms, no, xs, m, front, P, ref, v, g, best, mean, var); }
+  static int maximize_ehvi(hbegp_model* const* ms, int no, const double* st, int s, const double* lo, const double* hi, const double* front, int P,
+                           const double* ref, int maxeval, double* x, double* v, int* ne) {
+    return hbegp_maximize_ehvi_f64(ms, no, st, s, lo, hi, front, P, ref, maxeval, x, v, ne);
+  }
   static int get(hbegp_model* m, double* t, double* a, double* ki) { return hbegp_model_get_f64(m, t, a, ki); }
 };
 template <> struct Abi<float> {
@@ -135,6 +141,12 @@ template <> struct Abi<float> {
   }
   static int paths_minimize(hbegp_paths* p, const float* st, int R, const double* lo, const double* hi, int maxeval, float* x, double* f, int* ne) {
     return hbegp_paths_minimize_f32(p, st, R, lo, hi, maxeval, x, f, ne);
+  }
+  static int ehvi(hbegp_model* const* ms, int no, const float* xs, int m, const double* front, int P, const double* ref, double* v, float* g, int* best,
+                  float* mean, float* var) { return hbegp_ehvi_f32(ms, no, xs, m, front, P, ref, v, g, best, mean, var); }
+  static int maximize_ehvi(hbegp_model* const* ms, int no, const float* st, int s, const double* lo, const double* hi, const double* front, int P,
+                           const double* ref, int maxeval, float* x, double* v, int* ne) {
+    return hbegp_maximize_ehvi_f32(ms, no, st, s, lo, hi, front, P, ref, maxeval, x, v, ne);
   }
   static int get(hbegp_model* m, double* t, float* a, float* ki) { return hbegp_model_get_f32(m, t, a, ki); }
 };
@@ -266,6 +278,7 @@ class FittedKernel {
   }
   // S posterior sample paths (draws that are functions) from the caller's omega0[F*d], phase[F], w[S*F], eps[S*n] or nullptr
   PathsT<A> sample_paths(const A* omega0, const A* phase, const A* w, const A* eps, int F, int S) const;
+  hbegp_model* handle() const { return h_; }
   double lml() const { return lml_; }
   double noise() const { return std::exp(theta_[0]); }
   double amplitude() const { return std::exp(theta_[1]); }
@@ -284,6 +297,23 @@ class FittedKernel {
   std::vector<double> theta_;
   double lml_ = 0;
 };
+
+// Expected hypervolume improvement of two minimised, independent objectives at xs[m*d], each objective modelled by its own
+// FittedKernel (normalised y spaces): front[P*2] the points reached so far in any order, ref[2] the reference point; ehvi[m];
+// grad[m*d], best (the last index of the maximum), mean[m*2], var[m*2] (objective 0 then 1 per row) may be nullptr
+template <typename A>
+void ehvi(const FittedKernel<A>& obj0, const FittedKernel<A>& obj1, const A* xs, int m, const double* front, int P, const double* ref,
+          double* ehvi_out, A* grad = nullptr, int* best = nullptr, A* mean = nullptr, A* var = nullptr) {
+  hbegp_model* ms[2] = {obj0.handle(), obj1.handle()};
+  check(detail::Abi<A>::ehvi(ms, 2, xs, m, front, P, ref, ehvi_out, grad, best, mean, var));
+}
+// S bounded L-BFGS ascents of that EHVI from starts[S*d] inside [lo, hi]; x_out[S*d], ehvi_out[S], nevals[S] (may be nullptr)
+template <typename A>
+void maximize_ehvi(const FittedKernel<A>& obj0, const FittedKernel<A>& obj1, const A* starts, int S, const double* lo, const double* hi,
+                   const double* front, int P, const double* ref, int maxeval, A* x_out, double* ehvi_out, int* nevals = nullptr) {
+  hbegp_model* ms[2] = {obj0.handle(), obj1.handle()};
+  check(detail::Abi<A>::maximize_ehvi(ms, 2, starts, S, lo, hi, front, P, ref, maxeval, x_out, ehvi_out, nevals));
+}
 
 // RAII owner of an hbegp_paths handle (FittedKernel::sample_paths); it keeps its model alive
 template <typename A>

@@ -151,6 +151,14 @@ extern "C" {
         model: *mut HbegpModel, xs: *const c_float, m: c_int, mc: c_int, kg: *mut c_double, best: *mut c_int, imin: *mut c_int,
         mean_out: *mut c_float, var_out: *mut c_float,
     ) -> c_int;
+    fn hbegp_ehvi_f64(
+        models: *const *mut HbegpModel, n_obj: c_int, xs: *const c_double, m: c_int, front: *const c_double, p: c_int,
+        reference: *const c_double, ehvi: *mut c_double, grad: *mut c_double, best: *mut c_int, mean: *mut c_double, var: *mut c_double,
+    ) -> c_int;
+    fn hbegp_ehvi_f32(
+        models: *const *mut HbegpModel, n_obj: c_int, xs: *const c_float, m: c_int, front: *const c_double, p: c_int,
+        reference: *const c_double, ehvi: *mut c_double, grad: *mut c_float, best: *mut c_int, mean: *mut c_float, var: *mut c_float,
+    ) -> c_int;
     fn hbegp_noisy_ei_f64(
         model: *mut HbegpModel, xs: *const c_double, m: c_int, mb: c_int, z: *const c_double, s: c_int, jitter: c_double,
         nei: *mut c_double, best: *mut c_int, fmin_draws: *mut c_double, rho: *mut c_double, info: *mut c_int,
@@ -275,6 +283,12 @@ pub trait GpuScalar: Scalar + sealed::Sealed {
         model: *mut HbegpModel, xs: *const Self, m: c_int, mc: c_int, kg: *mut f64, best: *mut c_int, imin: *mut c_int,
         mean_out: *mut Self, var_out: *mut Self,
     ) -> c_int;
+    /// `hbegp_ehvi_*`
+    #[allow(clippy::too_many_arguments)]
+    unsafe fn ffi_ehvi(
+        models: *const *mut HbegpModel, n_obj: c_int, xs: *const Self, m: c_int, front: *const f64, p: c_int, reference: *const f64,
+        ehvi: *mut f64, grad: *mut Self, best: *mut c_int, mean: *mut Self, var: *mut Self,
+    ) -> c_int;
     /// `hbegp_noisy_ei_*`
     #[allow(clippy::too_many_arguments)]
     unsafe fn ffi_noisy_ei(
@@ -352,6 +366,12 @@ impl GpuScalar for f64 {
         mean_out: *mut f64, var_out: *mut f64,
     ) -> c_int {
         hbegp_knowledge_gradient_f64(model, xs, m, mc, kg, best, imin, mean_out, var_out)
+    }
+    unsafe fn ffi_ehvi(
+        models: *const *mut HbegpModel, n_obj: c_int, xs: *const f64, m: c_int, front: *const f64, p: c_int, reference: *const f64,
+        ehvi: *mut f64, grad: *mut f64, best: *mut c_int, mean: *mut f64, var: *mut f64,
+    ) -> c_int {
+        hbegp_ehvi_f64(models, n_obj, xs, m, front, p, reference, ehvi, grad, best, mean, var)
     }
     unsafe fn ffi_noisy_ei(
         model: *mut HbegpModel, xs: *const f64, m: c_int, mb: c_int, z: *const f64, s: c_int, jitter: f64, nei: *mut f64,
@@ -432,6 +452,12 @@ impl GpuScalar for f32 {
         mean_out: *mut f32, var_out: *mut f32,
     ) -> c_int {
         hbegp_knowledge_gradient_f32(model, xs, m, mc, kg, best, imin, mean_out, var_out)
+    }
+    unsafe fn ffi_ehvi(
+        models: *const *mut HbegpModel, n_obj: c_int, xs: *const f32, m: c_int, front: *const f64, p: c_int, reference: *const f64,
+        ehvi: *mut f64, grad: *mut f32, best: *mut c_int, mean: *mut f32, var: *mut f32,
+    ) -> c_int {
+        hbegp_ehvi_f32(models, n_obj, xs, m, front, p, reference, ehvi, grad, best, mean, var)
     }
     unsafe fn ffi_noisy_ei(
         model: *mut HbegpModel, xs: *const f32, m: c_int, mb: c_int, z: *const f32, s: c_int, jitter: f64, nei: *mut f64,
@@ -732,6 +758,33 @@ impl<A: GpuScalar> SurrogateModelGpu<A> {
             panic!("hbegp_knowledge_gradient failed: {}", last_error());
         }
         (kg, usize::try_from(best).ok(), usize::try_from(imin).ok())
+    }
+
+    /// Expected hypervolume improvement of TWO minimised objectives (`hbegp_ehvi_*`): `self` models objective 0, `other` objective 1
+    /// (same features, element type and device; their posteriors are taken as independent).  `front` [P, 2] holds the points reached
+    /// so far in any order and `reference` the reference point, both in the two models' NORMALISED y spaces (project each column
+    /// with that model's `YNormalize`: the projections are monotone, so dominance is preserved; the area is measured in normalised
+    /// units).  Closed form, no fmin, no random numbers.  Returns (ehvi [m], best = the last index of its maximum as `max_by`, None
+    /// without rows).  Opt-in.
+    pub fn ehvi_normalized(&self, other: &Self, x: ArrayView2<A>, front: ArrayView2<f64>, reference: [f64; 2]) -> (Vec<f64>, Option<usize>) {
+        let (m, _d) = x.dim();
+        let (p, two) = front.dim();
+        assert!(p == 0 || two == 2, "front must be [P, 2]");
+        let x = x.as_standard_layout();
+        let front = front.as_standard_layout();
+        let models = [self.handle, other.handle];
+        let mut ehvi = vec![0.0f64; m];
+        let mut best: c_int = -1;
+        let ehvi_ptr = if m > 0 { ehvi.as_mut_ptr() } else { std::ptr::null_mut() };
+        let front_ptr = if p > 0 { front.as_ptr() } else { std::ptr::null() };
+        let rc = unsafe {
+            A::ffi_ehvi(models.as_ptr(), 2, x.as_ptr(), m as c_int, front_ptr, p as c_int, reference.as_ptr(), ehvi_ptr,
+                        std::ptr::null_mut(), &mut best, std::ptr::null_mut(), std::ptr::null_mut())
+        };
+        if rc != HBEGP_OK {
+            panic!("hbegp_ehvi failed: {}", last_error());
+        }
+        (ehvi, usize::try_from(best).ok())
     }
 
     /// Noisy expected improvement over a candidate set (`hbegp_noisy_ei_*`; Letham, Karrer, Ottoni, Bakshy 2019): EI of every row
