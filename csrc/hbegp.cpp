@@ -25,6 +25,7 @@
 #include <limits>
 #include <memory>
 #include <mutex>
+#include <numeric>
 #include <string>
 #include <thread>
 #include <type_traits>
@@ -34,6 +35,7 @@
 #include "engine.hpp"
 #include "lbfgsb.hpp"
 #include "lbfgs_step.hpp"
+#include "lockstep.hpp"
 
 
 using namespace hbegp;
@@ -490,6 +492,20 @@ template <typename T>
 static void gemm_adhoc(GemmLaunch& g, const int* info, hipStream_t s) {
   g.info = info;
   launch_gemm<T>(g, pick_tile(g), s);
+}
+
+// The one-op launch C = A B^T against a lower-triangular B (X = L^-1 or L itself: k <= j, klim 1 / maskB) from tile (0, 0):
+// C is mi x nj tiles, the contraction runs over the tiles [0, k1).
+static GemmLaunch gemm_lower_b(const void* A, int lda, const void* B, int ldb, void* C, int ldc, int mi, int nj, int k1) {
+  GemmLaunch g{};
+  g.nops = 1;
+  GemmOp& op = g.op[0];
+  op.A = A; op.B = B; op.C = C;
+  op.lda = lda; op.ldb = ldb; op.ldc = ldc;
+  op.mi = mi; op.nj = nj;
+  op.k0 = 0; op.k1 = k1;
+  op.klim = 1; op.maskB = 1;
+  return g;
 }
 
 // Cholesky + inverse of the factor of the SPD matrix in W1 (lower) on the diagonal block range [lo, hi) (units of 128), split
@@ -1908,14 +1924,7 @@ static void predict_batched_launches(hbegp_model* m, int cnt, int mp, bool want_
     // The reference's k*^T K^-1 k* (predict.rs:30-37) as |L^-1 k*|^2: Q = Kstar * X^T (X = L^-1 lower: k <= j, half the
     // flops), then var = c + 1e-5 - rowsum(Q o Q).  A sum of squares has no cancellation inside the quadratic form, so the
     // result is at least as close to the exact value as the K^-1 form.
-    GemmLaunch g{};
-    g.nops = 1;
-    GemmOp& op = g.op[0];
-    op.lda = m->np; op.ldb = m->np; op.ldc = m->np;
-    op.ci0 = 0; op.cj0 = 0; op.mi = mp / NB; op.nj = m->np / NB;
-    op.k0 = 0; op.k1 = m->np / NB;
-    op.A = m->Ks; op.B = m->Xinv; op.C = m->Q;
-    op.klim = 1; op.maskB = 1;
+    GemmLaunch g = gemm_lower_b(m->Ks, m->np, m->Xinv, m->np, m->Q, m->np, mp / NB, m->np / NB, m->np / NB);
     gemm_adhoc<T>(g, &m->dOut->info, s);
     launch_pred_var<T>(static_cast<T*>(m->Q), static_cast<T*>(m->Q), cnt, m->np, m->dP, static_cast<T*>(m->var), m->dOut, s);
   }
@@ -1995,15 +2004,21 @@ static void predict_grad_w_launches(hbegp_model* m, int cnt, int mp) {
   hipStream_t s = m->stream;
   launch_kstar_grad<T>(static_cast<T*>(m->Xs), cnt, mp, static_cast<T*>(m->X), m->n, m->d, m->np, m->nu2, m->dP,
                        static_cast<T*>(m->G), s);
-  GemmLaunch g{};
-  g.nops = 1;
-  GemmOp& op = g.op[0];
-  op.lda = m->np; op.ldb = m->np; op.ldc = m->np;
-  op.ci0 = 0; op.cj0 = 0; op.mi = m->d * mp / NB; op.nj = m->np / NB;
-  op.k0 = 0; op.k1 = m->np / NB;
-  op.A = m->G; op.B = m->Xinv; op.C = m->W;
-  op.klim = 1; op.maskB = 1;  // X = L^-1 lower, as for Q
+  GemmLaunch g = gemm_lower_b(m->G, m->np, m->Xinv, m->np, m->W, m->np, m->d * mp / NB, m->np / NB, m->np / NB);  // X = L^-1 lower, as for Q
   gemm_adhoc<T>(g, &m->dOut->info, s);
+}
+
+// The gradient launches behind predict_batched_launches, on the model stream: dmean, then with want_w W = G X^T and with
+// want_dvar (needs W, and Q: the batched launches' variance) dvar.
+template <typename T>
+static void predict_grad_launches(hbegp_model* m, int cnt, int mp, bool want_w, bool want_dvar) {
+  hipStream_t s = m->stream;
+  launch_pred_grad<T>(static_cast<T*>(m->Xs), cnt, static_cast<T*>(m->X), m->n, m->d, m->nu2, m->dP, static_cast<T*>(m->alpha),
+                      static_cast<double*>(m->gpart), static_cast<T*>(m->dmean), s);
+  if (want_w) predict_grad_w_launches<T>(m, cnt, mp);
+  if (want_dvar)
+    launch_pred_dvar<T>(static_cast<T*>(m->W), static_cast<T*>(m->Q), cnt, mp, m->np, m->d, static_cast<T*>(m->var),
+                        static_cast<T*>(m->dvar), s);
 }
 
 // Posterior mean / variance as the batched predict computes them (for every m, also m <= 8) plus their gradients w.r.t. the
@@ -2022,13 +2037,7 @@ static int model_predict_grad(hbegp_model* m, const T* Xs, int cnt, T* mean, T* 
   const bool want_var = var != nullptr;
   HIPCHECK(hipMemcpyAsync(m->Xs, Xs, sizeof(T) * (size_t)cnt * m->d, hipMemcpyHostToDevice, s));
   predict_batched_launches<T>(m, cnt, mp, want_var);
-  launch_pred_grad<T>(static_cast<T*>(m->Xs), cnt, static_cast<T*>(m->X), m->n, m->d, m->nu2, m->dP, static_cast<T*>(m->alpha),
-                      static_cast<double*>(m->gpart), static_cast<T*>(m->dmean), s);
-  if (want_var) {
-    predict_grad_w_launches<T>(m, cnt, mp);
-    launch_pred_dvar<T>(static_cast<T*>(m->W), static_cast<T*>(m->Q), cnt, mp, m->np, m->d, static_cast<T*>(m->var),
-                        static_cast<T*>(m->dvar), s);
-  }
+  predict_grad_launches<T>(m, cnt, mp, want_var, want_var);
   CHECK_LAUNCHES();
   HIPCHECK(hipMemcpyAsync(mean, m->mean, sizeof(T) * cnt, hipMemcpyDeviceToHost, s));
   HIPCHECK(hipMemcpyAsync(dmean, m->dmean, sizeof(T) * (size_t)cnt * m->d, hipMemcpyDeviceToHost, s));
@@ -2066,21 +2075,90 @@ struct CallScratch {
   }
 };
 
-// phase times of the calling thread's last sampling call (hbegp_debug_posterior_phases): Q, Sigma, factor, draws in ms
-static thread_local bool t_time_posterior = false;
-static thread_local double t_posterior_ms[4] = {0, 0, 0, 0};
+// ---- phase times of the posterior-side calls (hbegp_debug_*_phases) ----------------------------------------------------------
+// One record per kind and calling thread: whether the thread's calls of that kind are timed, and the phase times (ms) of its last
+// timed call of that kind that reached its end.
+enum PhaseKind { PH_POSTERIOR, PH_SELECT, PH_KG, PH_NEI, PH_SENS, PH_EHVI, PH_QEI, PH_LOO, PH_PATHS, PH_KINDS };
+struct PhaseRecord {
+  bool on = false;
+  double ms[4] = {0, 0, 0, 0};
+};
+static thread_local PhaseRecord t_phase[PH_KINDS];
+
+// hbegp_debug_X_phases: hands out the kind's stored phases, then switches its timing on or off
+static int debug_phases(PhaseKind kind, int count, int enable, double* phase_ms) {
+  PhaseRecord& r = t_phase[kind];
+  if (phase_ms)
+    for (int i = 0; i < count; ++i) phase_ms[i] = r.ms[i];
+  r.on = enable != 0;
+  return HBEGP_OK;
+}
+
+// The events of one timed call.  Disabled, every method does nothing and returns nothing; enabled, mark() creates an event and
+// records it, and the destructor destroys every event however the call ends (a throwing HIPCHECK, an early return).
+class PhaseClock {
+ public:
+  PhaseClock(bool enabled, size_t capacity) : on_(enabled) {
+    if (on_) ev_.reserve(capacity);
+  }
+  ~PhaseClock() {
+    for (auto& e : ev_) (void)hipEventDestroy(e);
+  }
+  PhaseClock(const PhaseClock&) = delete;
+  PhaseClock& operator=(const PhaseClock&) = delete;
+  bool on() const { return on_; }
+  int marks() const { return (int)ev_.size(); }
+  // an event the callee records itself (launch_sens_eval: between its two kernels)
+  hipEvent_t slot() {
+    if (!on_) return nullptr;
+    hipEvent_t e = nullptr;
+    HIPCHECK(hipEventCreate(&e));
+    ev_.push_back(e);
+    return e;
+  }
+  void mark(hipStream_t s) {
+    if (hipEvent_t e = slot()) HIPCHECK(hipEventRecord(e, s));
+  }
+  // ms from mark i to mark j, waiting for j first: it may sit on another stream than the one the caller synchronised
+  double elapsed_ms(int i, int j) {
+    float ms = 0;
+    HIPCHECK(hipEventSynchronize(ev_[j]));
+    HIPCHECK(hipEventElapsedTime(&ms, ev_[i], ev_[j]));
+    return ms;
+  }
+  // the successful end of a timed call whose phases are the intervals between consecutive marks
+  void store(PhaseKind kind, int count) {
+    if (!on_) return;
+    for (int i = 0; i < count; ++i) t_phase[kind].ms[i] = elapsed_ms(i, i + 1);
+  }
+
+ private:
+  bool on_;
+  std::vector<hipEvent_t> ev_;
+};
+
+// The stored phases, by kind (include/hbegp.h has each one's meaning):
+//   posterior  Q, Sigma, factor, draws -- sampling calls only, predict_cov is never timed
+//   select     Sigma, select                      kg    Sigma, kg
+//   nei        Sigma, baseline factor, products, reductions
+//   sens       upload, substituted means, chunk and row sums, reduction and download (summed over the slabs)
+//   ehvi       the predict of objective 0 and of objective 1 (each on its model's stream: they overlap), the EHVI kernels
+//   qei        the shared launches, the qEI kernel
+//   loo        diagonal pass, u and Y, the SYRK, the weighted trace -- calls with a gradient only
+//   paths      hbegp_paths_create: uploads + frequency scaling, the feature projection, the two triangular products
 
 // Sigma = K** + noise I - Q Q^T at the candidates into W (lower tiles; m_p x m_p, kmat's identity padding): the candidates'
 // upload, the batched predict's launches (Kstar, the mean, Q = Kstar X^T; the variance too, unused), then kmat_kernel over
 // the candidates with a parameter block whose noise is *noise and one tile GEMM.  `noise` is copied from the caller's variable:
-// it has to outlive the stream work.  ev_q (may be null) is recorded behind Q.
+// it has to outlive the stream work.  clk_q (may be null) gets a mark behind Q.
 template <typename T>
-static void posterior_sigma(hbegp_model* m, const T* Xs, int cnt, int mp, const double* noise, T* W, hipEvent_t ev_q) {
+static void posterior_sigma(hbegp_model* m, const T* Xs, int cnt, int mp, const double* noise, T* W, PhaseClock* clk_q) {
   hipStream_t s = m->stream;
   int* info = &m->dOut->info;
+  if (!m->dPcov) m->dPcov = static_cast<EvalParams*>(m->palloc(sizeof(EvalParams)));
   HIPCHECK(hipMemcpyAsync(m->Xs, Xs, sizeof(T) * (size_t)cnt * m->d, hipMemcpyHostToDevice, s));
   predict_batched_launches<T>(m, cnt, mp, true);
-  if (ev_q) HIPCHECK(hipEventRecord(ev_q, s));
+  if (clk_q) clk_q->mark(s);
   HIPCHECK(hipMemcpyAsync(m->dPcov, m->dP, sizeof(EvalParams), hipMemcpyDeviceToDevice, s));
   HIPCHECK(hipMemcpyAsync(&m->dPcov->noise, noise, sizeof(double), hipMemcpyHostToDevice, s));
   launch_kmat<T>(static_cast<T*>(m->Xs), cnt, m->d, mp, m->nu2, m->dPcov, W, info, s);
@@ -2116,18 +2194,14 @@ static int model_posterior(hbegp_model* m, const T* Xs, int cnt, double jitter, 
   const double need = (double)sizeof(T) * ((cov ? 1.0 : 3.0) * (double)mp * mp + 2.0 * (double)Sp * mp + 2.0 * (double)mp * m->np);
   if (need > 1e15) return fail(HBEGP_ENOMEM, "the joint posterior of %d points needs %.3g bytes of device memory", cnt, need);
   predict_batched_reserve<T>(m, mp);
-  if (!m->dPcov) m->dPcov = static_cast<EvalParams*>(m->palloc(sizeof(EvalParams)));
   hipStream_t s = m->stream;
   int* info = &m->dOut->info;
   const double noise = 1e-5 + jitter;  // predict.rs:25-29's min_noise, plus the caller's jitter (copied from here: outlives the stream work)
   CallScratch ws{m->dev, s, {}};
   T* W1 = static_cast<T*>(ws.get(sizeof(T) * nn));
-  hipEvent_t ev[5] = {};
-  const bool timed = t_time_posterior && !cov;
-  if (timed)
-    for (auto& e : ev) HIPCHECK(hipEventCreate(&e));
-  if (timed) HIPCHECK(hipEventRecord(ev[0], s));
-  posterior_sigma<T>(m, Xs, cnt, mp, &noise, W1, timed ? ev[1] : nullptr);
+  PhaseClock clk(t_phase[PH_POSTERIOR].on && !cov, 5);  // the sampling branch only
+  clk.mark(s);
+  posterior_sigma<T>(m, Xs, cnt, mp, &noise, W1, &clk);
   if (cov) {
     launch_symmetrize<T>(W1, mp, s);
     CHECK_LAUNCHES();
@@ -2136,7 +2210,7 @@ static int model_posterior(hbegp_model* m, const T* Xs, int cnt, double jitter, 
     HIPCHECK(hipStreamSynchronize(s));
     return HBEGP_OK;
   }
-  if (timed) HIPCHECK(hipEventRecord(ev[2], s));
+  clk.mark(s);
   T* W2 = static_cast<T*>(ws.get(sizeof(T) * nn));
   T* W3 = static_cast<T*>(ws.get(sizeof(T) * nn));
   T* ld = static_cast<T*>(ws.get(sizeof(T) * mp));
@@ -2148,7 +2222,7 @@ static int model_posterior(hbegp_model* m, const T* Xs, int cnt, double jitter, 
   const int nbm = mp / NB;
   chol_inv_rec<T>(W1, W2, W3, mp, 0, nbm / 2, nbm, false, false, [&](GemmLaunch& g, int) { gemm_adhoc<T>(g, info, s); },
                   [&](int k) { launch_leaf_keep<T>(W1, W2, W3, mp, k, ld, info, s); });
-  if (timed) HIPCHECK(hipEventRecord(ev[3], s));
+  clk.mark(s);
   T* Z = static_cast<T*>(ws.get(sizeof(T) * (size_t)Sp * mp));
   T* Y = static_cast<T*>(ws.get(sizeof(T) * (size_t)Sp * mp));
   int* amin = static_cast<int*>(ws.get(sizeof(int) * (size_t)S));
@@ -2156,29 +2230,16 @@ static int model_posterior(hbegp_model* m, const T* Xs, int cnt, double jitter, 
   HIPCHECK(hipMemcpy2DAsync(Z, sizeof(T) * mp, z, sizeof(T) * cnt, sizeof(T) * cnt, S, hipMemcpyHostToDevice, s));
   {
     // Y = Z L^T: Y[s][i] = sum_{k <= i} z_s[k] L[i][k]  (L lower: k <= j, as for Q = Kstar X^T)
-    GemmLaunch g{};
-    g.nops = 1;
-    GemmOp& op = g.op[0];
-    op.A = Z; op.B = W3; op.C = Y;
-    op.lda = mp; op.ldb = mp; op.ldc = mp;
-    op.mi = Sp / NB; op.nj = mp / NB;
-    op.k0 = 0; op.k1 = mp / NB; op.klim = 1; op.maskB = 1;
+    GemmLaunch g = gemm_lower_b(Z, mp, W3, mp, Y, mp, Sp / NB, mp / NB, mp / NB);
     gemm_adhoc<T>(g, info, s);
   }
   launch_sample_epilogue<T>(Y, mp, static_cast<T*>(m->mean), cnt, S, samples != nullptr, amin, info, s);
-  if (timed) HIPCHECK(hipEventRecord(ev[4], s));
+  clk.mark(s);
   CHECK_LAUNCHES();
   EvalOut out;
   HIPCHECK(hipMemcpyAsync(&out, m->dOut, sizeof(EvalOut), hipMemcpyDeviceToHost, s));
   HIPCHECK(hipStreamSynchronize(s));
-  if (timed) {
-    for (int i = 0; i < 4; ++i) {
-      float ms = 0;
-      HIPCHECK(hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
-      t_posterior_ms[i] = ms;
-    }
-    for (auto& e : ev) (void)hipEventDestroy(e);
-  }
+  clk.store(PH_POSTERIOR, 4);
   if (info_out) *info_out = out.info;
   if (out.info != 0) return fail(HBEGP_NOT_PD, "Sigma is not positive definite (pivot panel at column %d); a larger jitter may help",
                                  out.info - 1);
@@ -2188,9 +2249,6 @@ static int model_posterior(hbegp_model* m, const T* Xs, int cnt, double jitter, 
   return HBEGP_OK;
 }
 
-// phase times of the calling thread's last batch selection (hbegp_debug_batch_select_phases): Sigma, select in ms
-static thread_local bool t_time_select = false;
-static thread_local double t_select_ms[2] = {0, 0};
 
 // Greedy batch selection by EI with fantasised observations (hbegp_select_batch): Sigma at jitter 0 as predict_cov builds it
 // (posterior_sigma, then mirrored), then the whole k-step loop in one launch of batch_select_kernel.  Only idx / ei (k each) and
@@ -2207,7 +2265,6 @@ static int model_select_batch(hbegp_model* m, const T* Xs, int cnt, int k, doubl
                       8.0 * ((double)k * mp + 2.0 * mp + k) + 4.0 * ((double)mp + k);
   if (need > 1e15) return fail(HBEGP_ENOMEM, "the batch selection over %d points needs %.3g bytes of device memory", cnt, need);
   predict_batched_reserve<T>(m, mp);
-  if (!m->dPcov) m->dPcov = static_cast<EvalParams*>(m->palloc(sizeof(EvalParams)));
   hipStream_t s = m->stream;
   const double noise = 1e-5;  // jitter 0: predict_cov's Sigma, whose diagonal is hbegp_predict's variance before clamping
   CallScratch ws{m->dev, s, {}};
@@ -2220,37 +2277,24 @@ static int model_select_batch(hbegp_model* m, const T* Xs, int cnt, int k, doubl
   int* didx = picked + mp;
   T* dmean = static_cast<T*>(ws.get(sizeof(T) * 2 * (size_t)mp));
   T* dvar = dmean + mp;
-  hipEvent_t ev[3] = {};
-  const bool timed = t_time_select;
-  if (timed)
-    for (auto& e : ev) HIPCHECK(hipEventCreate(&e));
-  if (timed) HIPCHECK(hipEventRecord(ev[0], s));
+  PhaseClock clk(t_phase[PH_SELECT].on, 3);
+  clk.mark(s);
   posterior_sigma<T>(m, Xs, cnt, mp, &noise, W1, nullptr);
   launch_symmetrize<T>(W1, mp, s);  // the kernel reads row j of Sigma
-  if (timed) HIPCHECK(hipEventRecord(ev[1], s));
+  clk.mark(s);
   launch_batch_select<T>(W1, mp, static_cast<const T*>(m->mean), cnt, k, m->dP, fmin, lie ? 1 : 0, lie ? *lie : 0.0, Cw, v, mu, picked,
                          didx, dei, dmean, dvar, s);
-  if (timed) HIPCHECK(hipEventRecord(ev[2], s));
+  clk.mark(s);
   CHECK_LAUNCHES();
   HIPCHECK(hipMemcpyAsync(idx, didx, sizeof(int) * (size_t)k, hipMemcpyDeviceToHost, s));
   if (ei) HIPCHECK(hipMemcpyAsync(ei, dei, sizeof(double) * (size_t)k, hipMemcpyDeviceToHost, s));
   if (mean_out) HIPCHECK(hipMemcpyAsync(mean_out, dmean, sizeof(T) * cnt, hipMemcpyDeviceToHost, s));
   if (var_out) HIPCHECK(hipMemcpyAsync(var_out, dvar, sizeof(T) * cnt, hipMemcpyDeviceToHost, s));
   HIPCHECK(hipStreamSynchronize(s));
-  if (timed) {
-    for (int i = 0; i < 2; ++i) {
-      float ms = 0;
-      HIPCHECK(hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
-      t_select_ms[i] = ms;
-    }
-    for (auto& e : ev) (void)hipEventDestroy(e);
-  }
+  clk.store(PH_SELECT, 2);
   return HBEGP_OK;
 }
 
-// phase times of the calling thread's last knowledge-gradient call (hbegp_debug_kg_phases): Sigma, kg in ms
-static thread_local bool t_time_kg = false;
-static thread_local double t_kg_ms[2] = {0, 0};
 
 // Knowledge gradient over a candidate set (hbegp_knowledge_gradient): Sigma at jitter 0 as predict_cov builds it (posterior_sigma,
 // then mirrored), then kg_kernel with one workgroup per candidate and the epilogue (best, imin, the clamped diagonal).  Only the mc
@@ -2267,7 +2311,6 @@ static int model_knowledge_gradient(hbegp_model* m, const T* Xs, int cnt, int mc
   const double need = (double)sizeof(T) * ((double)mp * mp + 2.0 * (double)mp * m->np + 2.0 * mp) + 8.0 * mc + 16.0 * (double)ws_lines;
   if (need > 1e15) return fail(HBEGP_ENOMEM, "the knowledge gradient over %d points needs %.3g bytes of device memory", cnt, need);
   predict_batched_reserve<T>(m, mp);
-  if (!m->dPcov) m->dPcov = static_cast<EvalParams*>(m->palloc(sizeof(EvalParams)));
   hipStream_t s = m->stream;
   const double noise = 1e-5;  // jitter 0: predict_cov's Sigma, whose diagonal is hbegp_predict's variance before clamping
   CallScratch ws{m->dev, s, {}};
@@ -2276,16 +2319,13 @@ static int model_knowledge_gradient(hbegp_model* m, const T* Xs, int cnt, int mc
   int* dres = static_cast<int*>(ws.get(sizeof(int) * 2));
   T* dvar = static_cast<T*>(ws.get(sizeof(T) * (size_t)mp));
   void* lines = ws_lines ? ws.get(16 * ws_lines) : nullptr;
-  hipEvent_t ev[3] = {};
-  const bool timed = t_time_kg;
-  if (timed)
-    for (auto& e : ev) HIPCHECK(hipEventCreate(&e));
-  if (timed) HIPCHECK(hipEventRecord(ev[0], s));
+  PhaseClock clk(t_phase[PH_KG].on, 3);
+  clk.mark(s);
   posterior_sigma<T>(m, Xs, cnt, mp, &noise, W1, nullptr);
   launch_symmetrize<T>(W1, mp, s);  // the kernel reads row j of Sigma
-  if (timed) HIPCHECK(hipEventRecord(ev[1], s));
+  clk.mark(s);
   launch_knowledge_gradient<T>(W1, mp, static_cast<const T*>(m->mean), cnt, mc, m->dP, lines, dkg, dres, dvar, s);
-  if (timed) HIPCHECK(hipEventRecord(ev[2], s));
+  clk.mark(s);
   CHECK_LAUNCHES();
   int res[2] = {-1, -1};
   if (mc > 0) HIPCHECK(hipMemcpyAsync(kg, dkg, sizeof(double) * (size_t)mc, hipMemcpyDeviceToHost, s));
@@ -2295,20 +2335,10 @@ static int model_knowledge_gradient(hbegp_model* m, const T* Xs, int cnt, int mc
   HIPCHECK(hipStreamSynchronize(s));
   if (best) *best = res[0];
   if (imin) *imin = res[1];
-  if (timed) {
-    for (int i = 0; i < 2; ++i) {
-      float ms = 0;
-      HIPCHECK(hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
-      t_kg_ms[i] = ms;
-    }
-    for (auto& e : ev) (void)hipEventDestroy(e);
-  }
+  clk.store(PH_KG, 2);
   return HBEGP_OK;
 }
 
-// phase times of the calling thread's last noisy-EI call (hbegp_debug_nei_phases): Sigma, baseline factor, products, reductions in ms
-static thread_local bool t_time_nei = false;
-static thread_local double t_nei_ms[4] = {0, 0, 0, 0};
 
 // Noisy expected improvement over a candidate set (hbegp_noisy_ei).  On the device the baseline rows come first,
 // padded to mbp (a multiple of NB) with copies of row 0, then the candidates, so that the baseline block of Sigma is whole
@@ -2344,7 +2374,6 @@ static int model_noisy_ei(hbegp_model* m, const T* Xs, int cnt, int mb, const T*
     std::copy(Xs + (size_t)mb * d, Xs + (size_t)cnt * d, hx.begin() + (size_t)mbp * d);
   }
   predict_batched_reserve<T>(m, mp);
-  if (!m->dPcov) m->dPcov = static_cast<EvalParams*>(m->palloc(sizeof(EvalParams)));
   hipStream_t s = m->stream;
   int* info = &m->dOut->info;
   const double noise = 1e-5 + jitter;  // as model_posterior (copied from here: outlives the stream work)
@@ -2359,20 +2388,17 @@ static int model_noisy_ei(hbegp_model* m, const T* Xs, int cnt, int mb, const T*
   double* drho = dfmin + S;
   double* dnei = drho + mc;
   int* dbest = static_cast<int*>(ws.get(sizeof(int)));
-  hipEvent_t ev[5] = {};
-  const bool timed = t_time_nei;
-  if (timed)
-    for (auto& e : ev) HIPCHECK(hipEventCreate(&e));
-  if (timed) HIPCHECK(hipEventRecord(ev[0], s));
+  PhaseClock clk(t_phase[PH_NEI].on, 5);
+  clk.mark(s);
   posterior_sigma<T>(m, hx.empty() ? Xs : hx.data(), rows, mp, &noise, W1, nullptr);
   if (mc > 0) launch_nei_pad<T>(W1, mp, mb, mbp, s);  // without candidates kmat's own identity padding follows the baseline
-  if (timed) HIPCHECK(hipEventRecord(ev[1], s));
+  clk.mark(s);
   // triangular operands must be zero above the diagonal in memory, and a recycled block holds its earlier owner's numbers
   HIPCHECK(hipMemsetAsync(W2, 0, sizeof(T) * (size_t)mbp * mp, s));
   HIPCHECK(hipMemsetAsync(W3, 0, sizeof(T) * (size_t)mp * mp, s));
   chol_inv_rec<T>(W1, W2, W3, mp, 0, nbb / 2, nbb, false, true, [&](GemmLaunch& g, int) { gemm_adhoc<T>(g, info, s); },
                   [&](int k) { launch_leaf_keep<T>(W1, W2, W3, mp, k, ld, info, s); });
-  if (timed) HIPCHECK(hipEventRecord(ev[2], s));
+  clk.mark(s);
   if (mp > mbp) {
     // A = Sigma_cb X_b^T below L_b  (X_b lower: k <= j)
     GemmLaunch g{};
@@ -2388,30 +2414,17 @@ static int model_noisy_ei(hbegp_model* m, const T* Xs, int cnt, int mb, const T*
   HIPCHECK(hipMemcpy2DAsync(Z, sizeof(T) * mbp, z, sizeof(T) * mb, sizeof(T) * mb, S, hipMemcpyHostToDevice, s));
   {
     // Y = Z [L_b; A]^T: Y[s][i] = sum_k z_s[k] W3[i][k] over the baseline's columns (L_b lower: k <= j inside its block range)
-    GemmLaunch g{};
-    g.nops = 1;
-    GemmOp& op = g.op[0];
-    op.A = Z; op.B = W3; op.C = Y;
-    op.lda = mbp; op.ldb = mp; op.ldc = mp;
-    op.mi = Sp / NB; op.nj = mp / NB;
-    op.k0 = 0; op.k1 = nbb; op.klim = 1; op.maskB = 1;
+    GemmLaunch g = gemm_lower_b(Z, mbp, W3, mp, Y, mp, Sp / NB, mp / NB, nbb);
     gemm_adhoc<T>(g, info, s);
   }
-  if (timed) HIPCHECK(hipEventRecord(ev[3], s));
+  clk.mark(s);
   launch_nei_reduce<T>(W1, W3, Y, mp, static_cast<const T*>(m->mean), mb, mbp, mc, S, dfmin, drho, dnei, dbest, info, s);
-  if (timed) HIPCHECK(hipEventRecord(ev[4], s));
+  clk.mark(s);
   CHECK_LAUNCHES();
   EvalOut out;
   HIPCHECK(hipMemcpyAsync(&out, m->dOut, sizeof(EvalOut), hipMemcpyDeviceToHost, s));
   HIPCHECK(hipStreamSynchronize(s));
-  if (timed) {
-    for (int i = 0; i < 4; ++i) {
-      float ms = 0;
-      HIPCHECK(hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
-      t_nei_ms[i] = ms;
-    }
-    for (auto& e : ev) (void)hipEventDestroy(e);
-  }
+  clk.store(PH_NEI, 4);
   if (info_out) *info_out = out.info;
   if (out.info != 0) return fail(HBEGP_NOT_PD, "the baseline block of Sigma is not positive definite (pivot panel at column %d); a larger "
                                  "jitter may help", out.info - 1);
@@ -2425,10 +2438,6 @@ static int model_noisy_ei(hbegp_model* m, const T* Xs, int cnt, int mb, const T*
   return HBEGP_OK;
 }
 
-// phase times of the calling thread's last sensitivity call (hbegp_debug_sens_phases): upload, substituted means, chunk and row
-// sums, reduction and download in ms
-static thread_local bool t_time_sens = false;
-static thread_local double t_sens_ms[4] = {0, 0, 0, 0};
 // the chunk partial sums of one slab of base rows stay under this many bytes (one row's worth where a single row needs more)
 constexpr size_t SENS_PART_CAP = (size_t)128 << 20;
 
@@ -2466,25 +2475,8 @@ static int model_sensitivity(hbegp_model* m, const T* A, const T* B, int N, cons
   T* fbase = static_cast<T*>(ws.get(sizeof(T) * mrows));
   T* fsub = sobol ? static_cast<T*>(ws.get(sizeof(T) * (size_t)d * N)) : nullptr;
   double* dres = static_cast<double*>(ws.get(sizeof(double) * (sobol ? (size_t)2 * d + 2 : (size_t)d * G)));
-  const bool timed = t_time_sens;
-  struct Events {  // destroyed however the call ends (a throwing HIPCHECK included)
-    std::vector<hipEvent_t> v;
-    ~Events() {
-      for (auto& e : v) (void)hipEventDestroy(e);
-    }
-  } evs;
-  std::vector<hipEvent_t>& ev = evs.v;
-  auto mark = [&]() -> hipEvent_t {
-    if (!timed) return nullptr;
-    hipEvent_t e;
-    HIPCHECK(hipEventCreate(&e));
-    ev.push_back(e);
-    return e;
-  };
-  auto record = [&]() {
-    if (hipEvent_t e = mark()) HIPCHECK(hipEventRecord(e, s));
-  };
-  record();
+  PhaseClock clk(t_phase[PH_SENS].on, 3 + 2 * ((mrows + slab - 1) / slab));
+  clk.mark(s);
   HIPCHECK(hipMemcpyAsync(dXb, A, sizeof(T) * (size_t)N * d, hipMemcpyHostToDevice, s));
   if (sobol) {
     HIPCHECK(hipMemcpyAsync(dsub, B, sizeof(T) * (size_t)N * d, hipMemcpyHostToDevice, s));
@@ -2493,14 +2485,14 @@ static int model_sensitivity(hbegp_model* m, const T* A, const T* B, int N, cons
     launch_sens_scale_grid<T>(dsub, d, G, m->dP, s);
     HIPCHECK(hipMemsetAsync(dres, 0, sizeof(double) * (size_t)d * G, s));  // the row sums start from zero
   }
-  record();
+  clk.mark(s);
   for (size_t r0 = 0; r0 < mrows; r0 += slab) {
     const int rows = (int)std::min(slab, mrows - r0);
-    hipEvent_t mid = mark();
+    hipEvent_t mid = clk.slot();
     launch_sens_eval<T>(dXb, (int)r0, rows, N, dsub, G, static_cast<const T*>(m->X), m->n, d, m->nu2, m->dP, static_cast<const T*>(m->alpha),
                         part, fbase, fsub, s, mid);
     if (!sobol) launch_sens_effect(part, rows, d, G, dres, N, r0 + slab >= mrows, s);
-    record();
+    clk.mark(s);
   }
   if (sobol) launch_sobol_reduce<T>(fbase, fsub, N, d, dres, s);
   CHECK_LAUNCHES();
@@ -2513,7 +2505,7 @@ static int model_sensitivity(hbegp_model* m, const T* A, const T* B, int N, cons
     HIPCHECK(hipMemcpyAsync(effect, dres, sizeof(double) * (size_t)d * G, hipMemcpyDeviceToHost, s));
   }
   if (f_a) HIPCHECK(hipMemcpyAsync(f_a, fbase, sizeof(T) * (size_t)N, hipMemcpyDeviceToHost, s));
-  record();
+  clk.mark(s);
   HIPCHECK(hipStreamSynchronize(s));
   if (sobol) {
     for (int k = 0; k < d; ++k) {
@@ -2523,21 +2515,17 @@ static int model_sensitivity(hbegp_model* m, const T* A, const T* B, int N, cons
     if (f0) *f0 = res[2 * (size_t)d];
     if (variance) *variance = res[2 * (size_t)d + 1];
   }
-  if (timed) {
-    // events: start, uploaded, then (mid, end) per slab, then the end of the call
-    auto ms = [&](size_t a, size_t b) {
-      float v = 0;
-      HIPCHECK(hipEventElapsedTime(&v, ev[a], ev[b]));
-      return (double)v;
-    };
-    const size_t last = ev.size() - 1;
-    t_sens_ms[0] = ms(0, 1);
-    t_sens_ms[1] = t_sens_ms[2] = 0;
-    for (size_t i = 2; i + 1 < last; i += 2) {
-      t_sens_ms[1] += ms(i - 1, i);
-      t_sens_ms[2] += ms(i, i + 1);
+  if (clk.on()) {
+    // marks: start, uploaded, then (mid, end) per slab, then the end of the call
+    double* ms = t_phase[PH_SENS].ms;
+    const int last = clk.marks() - 1;
+    ms[0] = clk.elapsed_ms(0, 1);
+    ms[1] = ms[2] = 0;
+    for (int i = 2; i + 1 < last; i += 2) {
+      ms[1] += clk.elapsed_ms(i - 1, i);
+      ms[2] += clk.elapsed_ms(i, i + 1);
     }
-    t_sens_ms[3] = ms(last - 1, last);
+    ms[3] = clk.elapsed_ms(last - 1, last);
   }
   return HBEGP_OK;
 }
@@ -2558,78 +2546,38 @@ static double ei_with_gradient(double mu, double var, const double* dmu, const d
   return std::max(ei, 0.0);
 }
 
-// the element of type T nearest to v that lies in [lo, hi] (an f32 run evaluates, and returns, points of the box)
-template <typename T>
-static T to_box(double v, double lo, double hi) {
-  T t = (T)v;
-  if ((double)t > hi) t = std::nextafter(t, -std::numeric_limits<T>::infinity());
-  if ((double)t < lo) t = std::nextafter(t, std::numeric_limits<T>::infinity());
-  return t;
+// the lockstep driver's options for the posterior-side optimisers: the fit optimiser's constants
+static LockstepOptions lockstep_options(int maxeval, bool maximize) {
+  const LbfgsOptions o;
+  return LockstepOptions{maxeval, o.memory, o.pgtol, o.ftol, maximize};
 }
 
-// S bounded L-BFGS runs on -EI (lbfgs_step.hpp, the fit optimiser's constants) in lockstep: every round gathers the point each
-// unfinished run asks for and evaluates them all with ONE model_predict_grad.  Each run returns the best point it evaluated.
+// S bounded L-BFGS runs on -EI in lockstep (lockstep.hpp): every round evaluates the points of the unfinished runs with ONE
+// model_predict_grad.  Each run returns the best point it evaluated; a prediction that is not finite is a failed evaluation.
 template <typename T>
 static int model_maximize_ei(hbegp_model* m, const T* starts, int S, const double* lo, const double* hi, double fmin, int maxeval,
                              T* x_out, double* ei_out, int* nevals_out) {
   const int d = m->d;
-  const LbfgsOptions o;
-  std::vector<LbfgsState> st(S);
-  std::vector<char> running(S, 1);
-  std::vector<double> best(S, -std::numeric_limits<double>::infinity());
-  std::vector<double> x0(d), g(d), gd(d), dmu_d(d), dvar_d(d);
-  for (int r = 0; r < S; ++r) {
-    for (int k = 0; k < d; ++k) x0[k] = (double)starts[(size_t)r * d + k];
-    lbfgs_begin(st[r], x0.data(), lo, hi, d, maxeval, o.memory, o.pgtol, o.ftol, false);
-    for (int k = 0; k < d; ++k) x_out[(size_t)r * d + k] = starts[(size_t)r * d + k];
-  }
-  std::vector<int> act;
-  std::vector<T> xs((size_t)S * d), mu(S), var(S), dmu((size_t)S * d), dvar((size_t)S * d);
-  for (;;) {
-    act.clear();
-    for (int r = 0; r < S; ++r)
-      if (running[r]) act.push_back(r);
-    if (act.empty()) break;
-    const int cnt = (int)act.size();
-    for (int i = 0; i < cnt; ++i) {
-      const double* q = lbfgs_request(st[act[i]]);
-      for (int k = 0; k < d; ++k) xs[(size_t)i * d + k] = to_box<T>(q[k], lo[k], hi[k]);
-    }
-    const int rc = model_predict_grad<T>(m, xs.data(), cnt, mu.data(), var.data(), dmu.data(), dvar.data(), nullptr);
+  std::vector<T> mu(S), var(S), dmu((size_t)S * d), dvar((size_t)S * d);
+  std::vector<double> dmu_d(d), dvar_d(d);
+  auto eval = [&](const T* xs, const int*, int cnt, double* val, double* grad, char* ok) {
+    const int rc = model_predict_grad<T>(m, xs, cnt, mu.data(), var.data(), dmu.data(), dvar.data(), nullptr);
     if (rc != HBEGP_OK) return rc;
     for (int i = 0; i < cnt; ++i) {
-      const int r = act[i];
       for (int k = 0; k < d; ++k) {
         dmu_d[k] = (double)dmu[(size_t)i * d + k];
         dvar_d[k] = (double)dvar[(size_t)i * d + k];
       }
       const double mu_i = (double)mu[i], var_i = (double)var[i];
-      double f = std::numeric_limits<double>::infinity();  // a NaN prediction is a failed evaluation
-      double ei = -std::numeric_limits<double>::infinity();
-      if (std::isfinite(mu_i) && std::isfinite(var_i)) {
-        ei = ei_with_gradient(mu_i, var_i, dmu_d.data(), dvar_d.data(), fmin, d, gd.data());
-        f = -ei;
-        for (int k = 0; k < d; ++k) g[k] = -gd[k];
-      }
-      if (ei > best[r]) {
-        best[r] = ei;
-        for (int k = 0; k < d; ++k) x_out[(size_t)r * d + k] = xs[(size_t)i * d + k];
-      }
-      running[r] = lbfgs_advance(st[r], f, g.data()) ? 1 : 0;
+      ok[i] = std::isfinite(mu_i) && std::isfinite(var_i);
+      if (ok[i]) val[i] = ei_with_gradient(mu_i, var_i, dmu_d.data(), dvar_d.data(), fmin, d, grad + (size_t)i * d);
     }
-  }
-  for (int r = 0; r < S; ++r) {
-    ei_out[r] = best[r];
-    if (nevals_out) nevals_out[r] = st[r].nevals;
-  }
-  return HBEGP_OK;
+    return (int)HBEGP_OK;
+  };
+  return lockstep_optimize<T, LbfgsState>(starts, S, d, lo, hi, lockstep_options(maxeval, true), eval, x_out, ei_out, nevals_out);
 }
 
 // ---- expected hypervolume improvement of two independent objectives (hbegp_ehvi / hbegp_maximize_ehvi) ----------
-// phase times of the calling thread's last timed EHVI call (hbegp_debug_ehvi_phases): the predict of objective 0 and of objective 1
-// (each on its model's stream: they overlap), the EHVI kernels, in ms
-static thread_local bool t_time_ehvi = false;
-static thread_local double t_ehvi_ms[3] = {0, 0, 0};
 
 // The caller's front reduced to the non-dominated points strictly inside the reference box, a ascending (so b descends), as the
 // kernel's strips: thr = [up | hb], ns = P' + 1 each; up = a_1 .. a_P', r1 and hb = r2, b_1 .. b_P'.  The result depends on the set
@@ -2694,36 +2642,28 @@ static int model_ehvi(hbegp_model* const* M, const T* Xs, int cnt, const std::ve
   double* dval = static_cast<double*>(ws.get(sizeof(double) * (size_t)cnt));
   int* dbest = static_cast<int*>(ws.get(sizeof(int)));
   T* dg = want_grad ? static_cast<T*>(ws.get(sizeof(T) * (size_t)cnt * d)) : nullptr;
-  hipEvent_t ev[6] = {};  // [2 k], [2 k + 1]: around model k's predict; [4], [5]: around the EHVI kernels
-  const bool timed = t_time_ehvi;
-  if (timed)
-    for (auto& e : ev) HIPCHECK(hipEventCreate(&e));
+  PhaseClock clk(t_phase[PH_EHVI].on, 6);  // marks 2 k, 2 k + 1: around model k's predict; 4, 5: around the EHVI kernels
   for (int k = 0; k < 2; ++k) {
     hbegp_model* m = M[k];
     hipStream_t s = m->stream;
-    if (timed) HIPCHECK(hipEventRecord(ev[2 * k], s));
+    clk.mark(s);
     HIPCHECK(hipMemcpyAsync(m->Xs, Xs, sizeof(T) * (size_t)cnt * d, hipMemcpyHostToDevice, s));
     predict_batched_launches<T>(m, cnt, mp, true);
-    if (want_grad) {
-      launch_pred_grad<T>(static_cast<T*>(m->Xs), cnt, static_cast<T*>(m->X), m->n, d, m->nu2, m->dP, static_cast<T*>(m->alpha),
-                          static_cast<double*>(m->gpart), static_cast<T*>(m->dmean), s);
-      predict_grad_w_launches<T>(m, cnt, mp);
-      launch_pred_dvar<T>(static_cast<T*>(m->W), static_cast<T*>(m->Q), cnt, mp, m->np, d, static_cast<T*>(m->var), static_cast<T*>(m->dvar), s);
-    }
+    if (want_grad) predict_grad_launches<T>(m, cnt, mp, true, true);
     CHECK_LAUNCHES();
-    if (timed) HIPCHECK(hipEventRecord(ev[2 * k + 1], s));
+    clk.mark(s);
   }
   HIPCHECK(hipEventRecord(ev_join, s1));
   HIPCHECK(hipMemcpyAsync(dthr, thr.data(), sizeof(double) * 2 * (size_t)ns, hipMemcpyHostToDevice, s0));
   HIPCHECK(hipStreamWaitEvent(s0, ev_join, 0));
-  if (timed) HIPCHECK(hipEventRecord(ev[4], s0));
+  clk.mark(s0);
   const T* g0m = want_grad ? static_cast<const T*>(M[0]->dmean) : nullptr;  // (not read without a gradient)
   const T* g0v = want_grad ? static_cast<const T*>(M[0]->dvar) : nullptr;
   const T* g1m = want_grad ? static_cast<const T*>(M[1]->dmean) : nullptr;
   const T* g1v = want_grad ? static_cast<const T*>(M[1]->dvar) : nullptr;
   launch_ehvi<T>(static_cast<const T*>(M[0]->mean), static_cast<const T*>(M[0]->var), g0m, g0v, static_cast<const T*>(M[1]->mean),
                  static_cast<const T*>(M[1]->var), g1m, g1v, cnt, d, dthr, ns, want_grad ? 1 : 0, dval, dg, dbest, s0);
-  if (timed) HIPCHECK(hipEventRecord(ev[5], s0));
+  clk.mark(s0);
   CHECK_LAUNCHES();
   int hbest = -1;
   std::vector<T> hm, hv;
@@ -2747,15 +2687,8 @@ static int model_ehvi(hbegp_model* const* M, const T* Xs, int cnt, const std::ve
       if (mean_out) mean_out[2 * (size_t)i + k] = hm[(size_t)k * cnt + i];
       if (var_out) var_out[2 * (size_t)i + k] = hv[(size_t)k * cnt + i];
     }
-  if (timed) {
-    HIPCHECK(hipEventSynchronize(ev[3]));
-    for (int i = 0; i < 3; ++i) {
-      float ms = 0;
-      HIPCHECK(hipEventElapsedTime(&ms, ev[2 * i], ev[2 * i + 1]));
-      t_ehvi_ms[i] = ms;
-    }
-    for (auto& e : ev) (void)hipEventDestroy(e);
-  }
+  if (clk.on())
+    for (int i = 0; i < 3; ++i) t_phase[PH_EHVI].ms[i] = clk.elapsed_ms(2 * i, 2 * i + 1);
   return HBEGP_OK;
 }
 
@@ -2771,67 +2704,29 @@ struct EhviJoin {
   }
 };
 
-// S bounded L-BFGS runs on -EHVI (lbfgs_step.hpp, the fit optimiser's constants) in lockstep, as model_maximize_ei: every round
-// gathers the point each unfinished run asks for and evaluates them all with ONE model_ehvi with a gradient (one batched gradient
-// predict per model, then the EHVI kernel).  Each run returns the best point it evaluated; a NaN is a failed evaluation.
+// S bounded L-BFGS runs on -EHVI in lockstep (lockstep.hpp), as model_maximize_ei: every round is ONE model_ehvi with a gradient
+// (one batched gradient predict per model, then the EHVI kernel).  Each run returns the best point it evaluated; a value or a
+// gradient component that is not finite is a failed evaluation.
 template <typename T>
 static int model_maximize_ehvi(hbegp_model* const* M, const T* starts, int S, const double* lo, const double* hi,
                                const std::vector<double>& thr, int ns, int maxeval, T* x_out, double* ehvi_out, int* nevals_out) {
   const int d = M[0]->d;
-  const LbfgsOptions o;
   EhviJoin join(M[0]->dev);
-  std::vector<LbfgsState> st(S);
-  std::vector<char> running(S, 1);
-  std::vector<double> best(S, -std::numeric_limits<double>::infinity());
-  std::vector<double> x0(d), g(d);
-  for (int r = 0; r < S; ++r) {
-    for (int k = 0; k < d; ++k) x0[k] = (double)starts[(size_t)r * d + k];
-    lbfgs_begin(st[r], x0.data(), lo, hi, d, maxeval, o.memory, o.pgtol, o.ftol, false);
-    for (int k = 0; k < d; ++k) x_out[(size_t)r * d + k] = starts[(size_t)r * d + k];
-  }
-  std::vector<int> act;
-  std::vector<T> xs((size_t)S * d), gr((size_t)S * d);
-  std::vector<double> val(S);
-  for (;;) {
-    act.clear();
-    for (int r = 0; r < S; ++r)
-      if (running[r]) act.push_back(r);
-    if (act.empty()) break;
-    const int cnt = (int)act.size();
-    for (int i = 0; i < cnt; ++i) {
-      const double* q = lbfgs_request(st[act[i]]);
-      for (int k = 0; k < d; ++k) xs[(size_t)i * d + k] = to_box<T>(q[k], lo[k], hi[k]);
-    }
-    const int rc = model_ehvi<T>(M, xs.data(), cnt, thr, ns, join.ev, val.data(), gr.data(), nullptr, nullptr, nullptr);
+  std::vector<T> gr((size_t)S * d);
+  auto eval = [&](const T* xs, const int*, int cnt, double* val, double* grad, char* ok) {
+    const int rc = model_ehvi<T>(M, xs, cnt, thr, ns, join.ev, val, gr.data(), nullptr, nullptr, nullptr);
     if (rc != HBEGP_OK) return rc;
     for (int i = 0; i < cnt; ++i) {
-      const int r = act[i];
-      double f = std::numeric_limits<double>::infinity();  // a NaN prediction is a failed evaluation
-      double v = -std::numeric_limits<double>::infinity();
-      bool ok = std::isfinite(val[i]);
-      for (int k = 0; k < d && ok; ++k) ok = std::isfinite((double)gr[(size_t)i * d + k]);
-      if (ok) {
-        v = val[i];
-        f = -v;
-        for (int k = 0; k < d; ++k) g[k] = -(double)gr[(size_t)i * d + k];
+      ok[i] = std::isfinite(val[i]);
+      for (int k = 0; k < d; ++k) {
+        grad[(size_t)i * d + k] = (double)gr[(size_t)i * d + k];
+        ok[i] = ok[i] && std::isfinite(grad[(size_t)i * d + k]);
       }
-      if (v > best[r]) {
-        best[r] = v;
-        for (int k = 0; k < d; ++k) x_out[(size_t)r * d + k] = xs[(size_t)i * d + k];
-      }
-      running[r] = lbfgs_advance(st[r], f, g.data()) ? 1 : 0;
     }
-  }
-  for (int r = 0; r < S; ++r) {
-    ehvi_out[r] = best[r];
-    if (nevals_out) nevals_out[r] = st[r].nevals;
-  }
-  return HBEGP_OK;
+    return (int)HBEGP_OK;
+  };
+  return lockstep_optimize<T, LbfgsState>(starts, S, d, lo, hi, lockstep_options(maxeval, true), eval, x_out, ehvi_out, nevals_out);
 }
-
-// phase times of the calling thread's last timed qEI call (hbegp_debug_qei_phases): the shared launches, the qEI kernel in ms
-static thread_local bool t_time_qei = false;
-static thread_local double t_qei_ms[2] = {0, 0};
 
 // Batch expected improvement by Monte Carlo (hbegp_qei) for B batches of q points: the B q points go through the batched predict's
 // launches (Kstar, mean, Q) and, with a gradient, the gradient's (dmean; G and W = G X^T), in the order hbegp_predict_grad issues
@@ -2861,39 +2756,25 @@ static int model_qei(hbegp_model* m, const T* Xb, int B, int q, const T* z, int 
   double* dq = static_cast<double*>(ws.get(sizeof(double) * (size_t)B));
   int* dinfo = static_cast<int*>(ws.get(sizeof(int) * (size_t)B));
   T* dg = want_grad ? static_cast<T*>(ws.get(sizeof(T) * (size_t)cnt * d)) : nullptr;
-  hipEvent_t ev[3] = {};
-  const bool timed = t_time_qei;
-  if (timed)
-    for (auto& e : ev) HIPCHECK(hipEventCreate(&e));
-  if (timed) HIPCHECK(hipEventRecord(ev[0], s));
+  PhaseClock clk(t_phase[PH_QEI].on, 3);
+  clk.mark(s);
   HIPCHECK(hipMemcpyAsync(m->Xs, Xb, sizeof(T) * (size_t)cnt * d, hipMemcpyHostToDevice, s));
   predict_batched_launches<T>(m, cnt, mp, true);
-  if (want_grad) {
-    launch_pred_grad<T>(static_cast<T*>(m->Xs), cnt, static_cast<T*>(m->X), m->n, d, m->nu2, m->dP, static_cast<T*>(m->alpha),
-                        static_cast<double*>(m->gpart), static_cast<T*>(m->dmean), s);
-    predict_grad_w_launches<T>(m, cnt, mp);
-  }
+  if (want_grad) predict_grad_launches<T>(m, cnt, mp, true, false);
   HIPCHECK(hipMemcpyAsync(dz, z, sizeof(T) * (size_t)S * q, hipMemcpyHostToDevice, s));
-  if (timed) HIPCHECK(hipEventRecord(ev[1], s));
+  clk.mark(s);
   const T* W = want_grad ? static_cast<const T*>(m->W) : static_cast<const T*>(m->Q);         // (not read without a gradient)
   const T* dmean = want_grad ? static_cast<const T*>(m->dmean) : static_cast<const T*>(m->mean);
   launch_qei_batch<T>(static_cast<const T*>(m->Xs), B, q, d, static_cast<const T*>(m->Q), W, mp, m->np, static_cast<const T*>(m->mean),
                       dmean, m->dP, noise, m->nu2, dz, S, fmin, want_grad ? 1 : 0, dq, dg, dinfo, s);
-  if (timed) HIPCHECK(hipEventRecord(ev[2], s));
+  clk.mark(s);
   CHECK_LAUNCHES();
   std::vector<int> hinfo(B);
   HIPCHECK(hipMemcpyAsync(qei, dq, sizeof(double) * (size_t)B, hipMemcpyDeviceToHost, s));
   HIPCHECK(hipMemcpyAsync(hinfo.data(), dinfo, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost, s));
   if (want_grad) HIPCHECK(hipMemcpyAsync(grad, dg, sizeof(T) * (size_t)cnt * d, hipMemcpyDeviceToHost, s));
   HIPCHECK(hipStreamSynchronize(s));
-  if (timed) {
-    for (int i = 0; i < 2; ++i) {
-      float ms = 0;
-      HIPCHECK(hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
-      t_qei_ms[i] = ms;
-    }
-    for (auto& e : ev) (void)hipEventDestroy(e);
-  }
+  clk.store(PH_QEI, 2);
   if (info_out) memcpy(info_out, hinfo.data(), sizeof(int) * (size_t)B);
   for (int b = 0; b < B; ++b)
     if (hinfo[b] != 0)
@@ -2902,73 +2783,37 @@ static int model_qei(hbegp_model* m, const T* Xb, int B, int q, const T* z, int 
   return HBEGP_OK;
 }
 
-// R bounded L-BFGS runs on -qEI over q d coordinates each (lbfgs_step.hpp with the host state sized per run: q d exceeds
-// LbfgsState's LBFGS_MAXN), the box [lo, hi] applied to every point, in lockstep: every round is ONE model_qei over the runs still
-// going, with the same z (a deterministic sample-average objective).  A batch whose factor failed is a failed evaluation.
+// R bounded L-BFGS runs on -qEI over q d coordinates each (the host state sized per run: q d exceeds LbfgsState's LBFGS_MAXN), the
+// box [lo, hi] applied to every point, in lockstep (lockstep.hpp): every round is ONE model_qei over the runs still going, with
+// the same z (a deterministic sample-average objective).  A batch whose factor failed is a failed evaluation, not an error of the
+// call; a run whose every evaluation failed (its start batch included) keeps its start with qei_out = -inf, as maximize_ei does.
 template <typename T>
 static int model_maximize_qei(hbegp_model* m, const T* starts, int R, int q, const double* lo, const double* hi, const T* z, int S,
                               double fmin, double jitter, int maxeval, T* x_out, double* qei_out, int* nevals_out) {
   const int d = m->d, n = q * d;
-  const LbfgsOptions o;
-  std::vector<double> lof(n), hif(n), x0(n), g(n);
+  std::vector<double> lof(n), hif(n);
   for (int e = 0; e < n; ++e) {
     lof[e] = lo[e % d];
     hif[e] = hi[e % d];
   }
-  std::vector<std::unique_ptr<LbfgsStateHost>> st;
-  std::vector<char> running(R, 1);
-  std::vector<double> best(R, -std::numeric_limits<double>::infinity());
-  for (int r = 0; r < R; ++r) {
-    st.emplace_back(new LbfgsStateHost(n));
-    for (int e = 0; e < n; ++e) x0[e] = (double)starts[(size_t)r * n + e];
-    lbfgs_begin(*st[r], x0.data(), lof.data(), hif.data(), n, maxeval, o.memory, o.pgtol, o.ftol, false);
-    for (int e = 0; e < n; ++e) x_out[(size_t)r * n + e] = starts[(size_t)r * n + e];
-  }
-  std::vector<int> act, info(R);
-  std::vector<T> xs((size_t)R * n), gr((size_t)R * n);
-  std::vector<double> qv(R);
-  for (;;) {
-    act.clear();
-    for (int r = 0; r < R; ++r)
-      if (running[r]) act.push_back(r);
-    if (act.empty()) break;
-    const int cnt = (int)act.size();
-    for (int i = 0; i < cnt; ++i) {
-      const double* p = lbfgs_request(*st[act[i]]);
-      for (int e = 0; e < n; ++e) xs[(size_t)i * n + e] = to_box<T>(p[e], lof[e], hif[e]);
-    }
-    const int rc = model_qei<T>(m, xs.data(), cnt, q, z, S, fmin, jitter, qv.data(), gr.data(), info.data());
+  std::vector<int> info(R);
+  std::vector<T> gr((size_t)R * n);
+  auto eval = [&](const T* xs, const int*, int cnt, double* val, double* grad, char* ok) {
+    const int rc = model_qei<T>(m, xs, cnt, q, z, S, fmin, jitter, val, gr.data(), info.data());
     if (rc != HBEGP_OK && rc != HBEGP_NOT_PD) return rc;
     for (int i = 0; i < cnt; ++i) {
-      const int r = act[i];
-      double f = std::numeric_limits<double>::infinity();  // a failed factor is a failed evaluation
-      double v = -std::numeric_limits<double>::infinity();
-      if (info[i] == 0 && std::isfinite(qv[i])) {
-        v = qv[i];
-        f = -v;
-        for (int e = 0; e < n; ++e) g[e] = -(double)gr[(size_t)i * n + e];
-      }
-      if (v > best[r]) {
-        best[r] = v;
-        for (int e = 0; e < n; ++e) x_out[(size_t)r * n + e] = xs[(size_t)i * n + e];
-      }
-      running[r] = lbfgs_advance(*st[r], f, g.data()) ? 1 : 0;
+      ok[i] = info[i] == 0 && std::isfinite(val[i]);
+      for (int e = 0; e < n; ++e) grad[(size_t)i * n + e] = (double)gr[(size_t)i * n + e];
     }
-  }
-  // a run whose every evaluation failed (its start batch included) keeps its start with qei_out = -inf, as maximize_ei does
-  for (int r = 0; r < R; ++r) {
-    qei_out[r] = best[r];
-    if (nevals_out) nevals_out[r] = st[r]->nevals;
-  }
-  g_last_error.clear();  // a failed batch inside a round is an evaluation result, not an error of this call
-  return HBEGP_OK;
+    return (int)HBEGP_OK;
+  };
+  const int rc = lockstep_optimize<T, LbfgsStateHost>(starts, R, n, lof.data(), hif.data(), lockstep_options(maxeval, true), eval, x_out,
+                                                      qei_out, nevals_out);
+  if (rc == HBEGP_OK) g_last_error.clear();  // a failed batch inside a round has left its message behind
+  return rc;
 }
 
 // ---- leave-one-out cross-validation (hbegp_model_loo / hbegp_problem_eval_loo / hbegp_fit_loo) ----------
-// phase times of the calling thread's last timed call with a gradient (hbegp_debug_loo_phases): diagonal pass, u and Y, the
-// SYRK, the weighted trace, in ms
-static thread_local bool t_time_loo = false;
-static thread_local double t_loo_ms[4] = {0, 0, 0, 0};
 
 // The diagnostics from L^-1 and alpha (one memory-bound pass), and with `grad` the gradient of their sum: u = K^-1 a and
 // Y = K^-1 diag(sqrt b) in one pass over K^-1, C = Y Y^T by ONE tile GEMM for all p parameters, and gradtrace's pass with the
@@ -3001,18 +2846,15 @@ static int loo_tail(const LooIn<T>& in, T* mean, T* var, T* lpd, double* loo, do
   double* pu = reinterpret_cast<double*>(q); q += b_pu;
   double* part_g = reinterpret_cast<double*>(q);
   HIPCHECK(hipMemsetAsync(dout, 0, sizeof(EvalOut), s));  // info = 0, done = 0 (a recycled block holds its earlier owner's numbers)
-  hipEvent_t ev[5] = {};
-  const bool timed = t_time_loo && grad;
-  if (timed)
-    for (auto& e : ev) HIPCHECK(hipEventCreate(&e));
-  if (timed) HIPCHECK(hipEventRecord(ev[0], s));
+  PhaseClock clk(t_phase[PH_LOO].on && grad, 5);
+  clk.mark(s);
   launch_loo_diag<T>(in.Xinv, np, n, in.y, in.alpha, part, dmean, dvar, dlpd, avec, sbvec, dout, s);
-  if (timed) HIPCHECK(hipEventRecord(ev[1], s));
+  clk.mark(s);
   if (grad) {
     T* Y = static_cast<T*>(ws.get(sizeof(T) * nn));
     T* Cm = static_cast<T*>(ws.get(sizeof(T) * nn));
     launch_loo_uy<T>(in.Kinv, np, n, avec, sbvec, Y, pu, du, s);
-    if (timed) HIPCHECK(hipEventRecord(ev[2], s));
+    clk.mark(s);
     {
       // C = Y Y^T (lower tiles), contraction over all columns of Y
       GemmLaunch g{};
@@ -3024,9 +2866,9 @@ static int loo_tail(const LooIn<T>& in, T* mean, T* var, T* lpd, double* loo, do
       op.k0 = 0; op.k1 = np / NB;
       gemm_adhoc<T>(g, &dout->info, s);
     }
-    if (timed) HIPCHECK(hipEventRecord(ev[3], s));
+    clk.mark(s);
     launch_loo_trace<T>(in.X, n, in.d, np, in.nu2, in.P, Cm, in.alpha, du, part_g, dout, s);
-    if (timed) HIPCHECK(hipEventRecord(ev[4], s));
+    clk.mark(s);
   }
   CHECK_LAUNCHES();
   EvalOut out;
@@ -3035,14 +2877,7 @@ static int loo_tail(const LooIn<T>& in, T* mean, T* var, T* lpd, double* loo, do
   if (var) HIPCHECK(hipMemcpyAsync(var, dvar, sizeof(T) * n, hipMemcpyDeviceToHost, s));
   if (lpd) HIPCHECK(hipMemcpyAsync(lpd, dlpd, sizeof(T) * n, hipMemcpyDeviceToHost, s));
   HIPCHECK(hipStreamSynchronize(s));
-  if (timed) {
-    for (int i = 0; i < 4; ++i) {
-      float ms = 0;
-      HIPCHECK(hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
-      t_loo_ms[i] = ms;
-    }
-    for (auto& e : ev) (void)hipEventDestroy(e);
-  }
+  clk.store(PH_LOO, 4);
   if (!(out.done & 1) || (grad && !(out.done & 2)))
     throw HipError{hipErrorLaunchFailure, "leave-one-out: the kernels did not run", __LINE__};
   bool finite = std::isfinite(out.lml);
@@ -3119,10 +2954,6 @@ struct hbegp_paths {
   }
 };
 
-// phase times of the calling thread's last timed hbegp_paths_create call (hbegp_debug_paths_phases): uploads + frequency scaling,
-// the feature projection, the two triangular products, in ms
-static thread_local bool t_time_paths = false;
-static thread_local double t_paths_ms[3] = {0, 0, 0};
 
 template <typename T>
 static int paths_create(hbegp_model* m, const T* omega0, const T* phase, const T* w, const T* eps, int F, int S, hbegp_paths** out) {
@@ -3147,56 +2978,30 @@ static int paths_create(hbegp_model* m, const T* omega0, const T* phase, const T
   double* part = static_cast<double*>(ws.get(sizeof(double) * (size_t)paths_project_chunks(F, n, S) * S * n));
   T* Rt = static_cast<T*>(ws.get(sizeof(T) * (size_t)Sp * np));
   T* T1 = static_cast<T*>(ws.get(sizeof(T) * (size_t)Sp * np));
-  struct Events {  // destroyed on every way out, a throwing HIPCHECK included
-    hipEvent_t e[4] = {};
-    ~Events() {
-      for (auto& x : e)
-        if (x) (void)hipEventDestroy(x);
-    }
-  } evs;
-  hipEvent_t* ev = evs.e;
-  const bool timed = t_time_paths;
-  if (timed)
-    for (auto& e : evs.e) HIPCHECK(hipEventCreate(&e));
-  if (timed) HIPCHECK(hipEventRecord(ev[0], s));
+  PhaseClock clk(t_phase[PH_PATHS].on, 4);
+  clk.mark(s);
   HIPCHECK(hipMemcpyAsync(p->Wf, hw.data(), sizeof(double) * (size_t)S * F, hipMemcpyHostToDevice, s));
   HIPCHECK(hipMemcpyAsync(p->phase, hw.data() + (size_t)S * F, sizeof(double) * (size_t)F, hipMemcpyHostToDevice, s));
   HIPCHECK(hipMemcpyAsync(om0, omega0, sizeof(T) * (size_t)F * d, hipMemcpyHostToDevice, s));
   if (eps) HIPCHECK(hipMemcpyAsync(deps, eps, sizeof(T) * (size_t)S * n, hipMemcpyHostToDevice, s));
   HIPCHECK(hipMemsetAsync(m->dOut, 0, sizeof(EvalOut), s));
   launch_paths_scale_omega<T>(om0, F, d, m->dP, p->omT, s);
-  if (timed) HIPCHECK(hipEventRecord(ev[1], s));
+  clk.mark(s);
   launch_paths_project<T>(static_cast<T*>(m->X), n, d, np, p->omT, p->phase, F, p->Wf, S, Sp, static_cast<T*>(m->y), deps, m->dP, part, Rt, s);
-  if (timed) HIPCHECK(hipEventRecord(ev[2], s));
+  clk.mark(s);
   {
     // v = L^-T (L^-1 r) for all paths, one path per row: T1 = R^T X^T (X = L^-1 lower: k <= j, as Q = Kstar X^T), then
     // V^T = T1 X (k >= j).  Never through the stored K^-1 (section 10).
-    GemmLaunch g{};
-    g.nops = 1;
-    GemmOp& op = g.op[0];
-    op.lda = np; op.ldb = np; op.ldc = np;
-    op.mi = Sp / NB; op.nj = np / NB; op.k0 = 0; op.k1 = np / NB;
-    op.A = Rt; op.B = m->Xinv; op.C = T1;
-    op.klim = 1; op.maskB = 1;
+    GemmLaunch g = gemm_lower_b(Rt, np, m->Xinv, np, T1, np, Sp / NB, np / NB, np / NB);
     gemm_adhoc<T>(g, &m->dOut->info, s);
-    GemmLaunch g2{};
-    g2.nops = 1;
-    GemmOp& o2 = g2.op[0];
-    o2 = op;
-    o2.A = T1; o2.C = p->Vt;
-    o2.b_kmajor = 1; o2.klim = 2;
+    GemmLaunch g2 = gemm_lower_b(T1, np, m->Xinv, np, p->Vt, np, Sp / NB, np / NB, np / NB);
+    g2.op[0].b_kmajor = 1; g2.op[0].klim = 2;
     gemm_adhoc<T>(g2, &m->dOut->info, s);
   }
-  if (timed) HIPCHECK(hipEventRecord(ev[3], s));
+  clk.mark(s);
   CHECK_LAUNCHES();
   HIPCHECK(hipStreamSynchronize(s));
-  if (timed) {
-    for (int i = 0; i < 3; ++i) {
-      float ms = 0;
-      HIPCHECK(hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
-      t_paths_ms[i] = ms;
-    }
-  }
+  clk.store(PH_PATHS, 3);
   *out = p.release();
   return HBEGP_OK;
 }
@@ -3244,10 +3049,11 @@ static int paths_eval(hbegp_paths* p, const T* Xs, int cnt, int per_path, T* f, 
   return HBEGP_OK;
 }
 
-// S R bounded L-BFGS descents (lbfgs_step.hpp, the fit optimiser's constants), R per path, in lockstep: every round gathers the
-// point each unfinished run asks for and evaluates them with ONE per-path evaluation ([S][mr] points, mr the largest number of
-// unfinished runs of any path; a path with fewer repeats its last point).  Each path returns the best point any of its runs
-// evaluated (a NaN value is a failed evaluation; a path without a finite value returns its first start and +inf).
+// S R bounded L-BFGS descents, R per path, in lockstep (lockstep.hpp; run sp R + r is run r of path sp): every round evaluates the
+// points of the unfinished runs with ONE per-path evaluation ([S][mr] points, mr the largest number of unfinished runs of any path;
+// a path with fewer repeats its last point, one with none its best point so far).  Each path returns the best point any of its runs
+// evaluated: the earliest evaluation on ties, rounds in order and a round's runs in order (a value or a gradient component that is
+// not finite is a failed evaluation; a path without a finite value returns its first start and +inf).
 template <typename T>
 static int paths_minimize(hbegp_paths* p, const T* starts, int R, const double* lo, const double* hi, int maxeval, T* x_best, double* f_best,
                           int* n_evals) {
@@ -3256,72 +3062,55 @@ static int paths_minimize(hbegp_paths* p, const T* starts, int R, const double* 
   HIPCHECK(hipSetDevice(m->dev));
   const int d = m->d, S = p->S;
   const size_t NR = (size_t)S * R;
-  const LbfgsOptions o;
-  std::vector<LbfgsState> st(NR);
-  std::vector<char> running(NR, 1);
-  std::vector<double> best(S, std::numeric_limits<double>::infinity());
-  std::vector<double> x0(d), g(d);
-  for (size_t r = 0; r < NR; ++r) {
-    for (int k = 0; k < d; ++k) x0[k] = (double)starts[r * d + k];
-    lbfgs_begin(st[r], x0.data(), lo, hi, d, maxeval, o.memory, o.pgtol, o.ftol, false);
-  }
-  for (int sp = 0; sp < S; ++sp)
+  std::vector<T> x_run(NR * d), xs, fv, dfv;
+  std::vector<double> f_run(NR);
+  std::vector<int> nev(NR), slot(NR), na(S);
+  for (int sp = 0; sp < S; ++sp) {
+    f_best[sp] = std::numeric_limits<double>::infinity();
     for (int k = 0; k < d; ++k) x_best[(size_t)sp * d + k] = starts[(size_t)sp * R * d + k];
-  std::vector<std::vector<int>> act(S);
-  std::vector<T> xs, fv, dfv;
-  for (;;) {
-    int mr = 0;
-    for (int sp = 0; sp < S; ++sp) {
-      act[sp].clear();
-      for (int r = 0; r < R; ++r)
-        if (running[(size_t)sp * R + r]) act[sp].push_back(r);
-      mr = std::max(mr, (int)act[sp].size());
-    }
-    if (mr == 0) break;
+  }
+  // the driver keeps every run's best; a path's best follows them after every round, in run order
+  auto fold = [&]() {
+    for (size_t r = 0; r < NR; ++r)
+      if (f_run[r] < f_best[r / R]) {
+        f_best[r / R] = f_run[r];
+        for (int k = 0; k < d; ++k) x_best[(r / R) * d + k] = x_run[r * d + k];
+      }
+  };
+  auto eval = [&](const T* pts, const int* runs, int cnt, double* val, double* grad, char* ok) {
+    fold();
+    std::fill(na.begin(), na.end(), 0);
+    for (int i = 0; i < cnt; ++i) slot[i] = na[runs[i] / R]++;
+    const int mr = *std::max_element(na.begin(), na.end());
     xs.assign((size_t)S * mr * d, T(0));
     fv.resize((size_t)S * mr);
     dfv.resize((size_t)S * mr * d);
+    for (int i = 0; i < cnt; ++i) std::copy(pts + (size_t)i * d, pts + (size_t)(i + 1) * d, xs.begin() + ((size_t)(runs[i] / R) * mr + slot[i]) * d);
     for (int sp = 0; sp < S; ++sp) {
       T* row = xs.data() + (size_t)sp * mr * d;
-      const int na = (int)act[sp].size();
-      for (int i = 0; i < mr; ++i) {
-        if (i < na) {
-          const double* q = lbfgs_request(st[(size_t)sp * R + act[sp][i]]);
-          for (int k = 0; k < d; ++k) row[(size_t)i * d + k] = to_box<T>(q[k], lo[k], hi[k]);
-        } else {
-          const T* src = i > 0 ? row + (size_t)(i - 1) * d : x_best + (size_t)sp * d;
-          for (int k = 0; k < d; ++k) row[(size_t)i * d + k] = src[k];
-        }
+      for (int i = na[sp]; i < mr; ++i) {
+        const T* src = i > 0 ? row + (size_t)(i - 1) * d : x_best + (size_t)sp * d;
+        for (int k = 0; k < d; ++k) row[(size_t)i * d + k] = src[k];
       }
     }
     paths_eval_locked<T>(p, xs.data(), mr, 1, fv.data(), dfv.data());
-    for (int sp = 0; sp < S; ++sp) {
-      for (int i = 0; i < (int)act[sp].size(); ++i) {
-        const size_t r = (size_t)sp * R + act[sp][i], at = (size_t)sp * mr + i;
-        double fx = (double)fv[at];
-        bool ok = std::isfinite(fx);
-        for (int k = 0; k < d; ++k) {
-          g[k] = (double)dfv[at * d + k];
-          ok = ok && std::isfinite(g[k]);
-        }
-        if (!ok) {
-          fx = std::numeric_limits<double>::infinity();
-          for (int k = 0; k < d; ++k) g[k] = 0.0;
-        } else if (fx < best[sp]) {
-          best[sp] = fx;
-          for (int k = 0; k < d; ++k) x_best[(size_t)sp * d + k] = xs[at * d + k];
-        }
-        running[r] = lbfgs_advance(st[r], fx, g.data()) ? 1 : 0;
+    for (int i = 0; i < cnt; ++i) {
+      const size_t at = (size_t)(runs[i] / R) * mr + slot[i];
+      val[i] = (double)fv[at];
+      ok[i] = std::isfinite(val[i]);
+      for (int k = 0; k < d; ++k) {
+        grad[(size_t)i * d + k] = (double)dfv[at * d + k];
+        ok[i] = ok[i] && std::isfinite(grad[(size_t)i * d + k]);
       }
     }
-  }
-  for (int sp = 0; sp < S; ++sp) {
-    f_best[sp] = best[sp];
-    if (n_evals) {
-      n_evals[sp] = 0;
-      for (int r = 0; r < R; ++r) n_evals[sp] += st[(size_t)sp * R + r].nevals;
-    }
-  }
+    return (int)HBEGP_OK;
+  };
+  const int rc = lockstep_optimize<T, LbfgsState>(starts, (int)NR, d, lo, hi, lockstep_options(maxeval, false), eval, x_run.data(), f_run.data(),
+                                                  nev.data());
+  if (rc != HBEGP_OK) return rc;
+  fold();
+  if (n_evals)
+    for (int sp = 0; sp < S; ++sp) n_evals[sp] = std::accumulate(nev.begin() + (size_t)sp * R, nev.begin() + (size_t)(sp + 1) * R, 0);
   return HBEGP_OK;
 }
 
@@ -4445,12 +4234,7 @@ int hbegp_paths_info(const hbegp_paths* paths, int* n, int* d, int* n_features, 
   return HBEGP_OK;
 }
 void hbegp_paths_release(hbegp_paths* paths) { delete paths; }
-int hbegp_debug_paths_phases(int enable, double* phase_ms) {
-  if (phase_ms)
-    for (int i = 0; i < 3; ++i) phase_ms[i] = t_paths_ms[i];
-  t_time_paths = enable != 0;
-  return HBEGP_OK;
-}
+int hbegp_debug_paths_phases(int enable, double* phase_ms) { return debug_phases(PH_PATHS, 3, enable, phase_ms); }
 // the check that needs no model comes first, so that each one has its own message whatever else is wrong
 static int check_model_loo(hbegp_model* model, bool want_f32, bool any_output) {
   if (!any_output) return fail(HBEGP_EINVAL, "every output is NULL");
@@ -4470,18 +4254,8 @@ int hbegp_model_loo_f32(hbegp_model* model, float* mean, float* var, float* lpd,
   return model_loo<float>(model, mean, var, lpd, loo, grad);
   GUARD_END
 }
-int hbegp_debug_loo_phases(int enable, double* phase_ms) {
-  if (phase_ms)
-    for (int i = 0; i < 4; ++i) phase_ms[i] = t_loo_ms[i];
-  t_time_loo = enable != 0;
-  return HBEGP_OK;
-}
-int hbegp_debug_qei_phases(int enable, double* phase_ms) {
-  if (phase_ms)
-    for (int i = 0; i < 2; ++i) phase_ms[i] = t_qei_ms[i];
-  t_time_qei = enable != 0;
-  return HBEGP_OK;
-}
+int hbegp_debug_loo_phases(int enable, double* phase_ms) { return debug_phases(PH_LOO, 4, enable, phase_ms); }
+int hbegp_debug_qei_phases(int enable, double* phase_ms) { return debug_phases(PH_QEI, 2, enable, phase_ms); }
 }  // extern "C"
 
 // argument checks of hbegp_select_batch_*: everything is refused before any device call, the checks that need no model first
@@ -4512,12 +4286,7 @@ int hbegp_select_batch_f32(hbegp_model* model, const float* Xs, int m, int k, do
   return model_select_batch<float>(model, Xs, m, k, fmin_normalized, lie, idx, ei, mean_out, var_out);
   GUARD_END
 }
-int hbegp_debug_batch_select_phases(int enable, double* phase_ms) {
-  if (phase_ms)
-    for (int i = 0; i < 2; ++i) phase_ms[i] = t_select_ms[i];
-  t_time_select = enable != 0;
-  return HBEGP_OK;
-}
+int hbegp_debug_batch_select_phases(int enable, double* phase_ms) { return debug_phases(PH_SELECT, 2, enable, phase_ms); }
 }  // extern "C"
 
 // argument checks of hbegp_knowledge_gradient_*: everything is refused before any device call, the checks that need no model first
@@ -4550,12 +4319,7 @@ int hbegp_knowledge_gradient_f32(hbegp_model* model, const float* Xs, int m, int
   return model_knowledge_gradient<float>(model, Xs, m, mc, kg, best, imin, mean_out, var_out);
   GUARD_END
 }
-int hbegp_debug_kg_phases(int enable, double* phase_ms) {
-  if (phase_ms)
-    for (int i = 0; i < 2; ++i) phase_ms[i] = t_kg_ms[i];
-  t_time_kg = enable != 0;
-  return HBEGP_OK;
-}
+int hbegp_debug_kg_phases(int enable, double* phase_ms) { return debug_phases(PH_KG, 2, enable, phase_ms); }
 }  // extern "C"
 
 // argument checks of hbegp_noisy_ei_*: everything is refused before any device call, the checks that need no model first
@@ -4584,12 +4348,7 @@ int hbegp_noisy_ei_f32(hbegp_model* model, const float* Xs, int m, int mb, const
   return model_noisy_ei<float>(model, Xs, m, mb, z, S, jitter, nei, best, fmin_draws, rho, info);
   GUARD_END
 }
-int hbegp_debug_nei_phases(int enable, double* phase_ms) {
-  if (phase_ms)
-    for (int i = 0; i < 4; ++i) phase_ms[i] = t_nei_ms[i];
-  t_time_nei = enable != 0;
-  return HBEGP_OK;
-}
+int hbegp_debug_nei_phases(int enable, double* phase_ms) { return debug_phases(PH_NEI, 4, enable, phase_ms); }
 }  // extern "C"
 
 // argument checks of hbegp_ehvi_* / hbegp_maximize_ehvi_*: everything is refused before any device call, the checks that need no
@@ -4657,12 +4416,7 @@ int hbegp_maximize_ehvi_f32(hbegp_model* const* models, int n_obj, const float* 
                             const double* front, int P, const double* ref, int maxeval, float* x_out, double* ehvi_out, int* nevals_out) {
   return do_maximize_ehvi<float>(models, n_obj, starts, S, lo, hi, front, P, ref, maxeval, x_out, ehvi_out, nevals_out);
 }
-int hbegp_debug_ehvi_phases(int enable, double* phase_ms) {
-  if (phase_ms)
-    for (int i = 0; i < 3; ++i) phase_ms[i] = t_ehvi_ms[i];
-  t_time_ehvi = enable != 0;
-  return HBEGP_OK;
-}
+int hbegp_debug_ehvi_phases(int enable, double* phase_ms) { return debug_phases(PH_EHVI, 3, enable, phase_ms); }
 }  // extern "C"
 
 // argument checks of hbegp_sobol_* / hbegp_main_effects_*: everything is refused before any device call, the checks that need no
@@ -4707,18 +4461,8 @@ int hbegp_main_effects_f32(hbegp_model* model, const float* A, int N, const floa
   return model_sensitivity<float>(model, A, nullptr, N, grid, G, nullptr, nullptr, nullptr, nullptr, f_a, nullptr, nullptr, effect);
   GUARD_END
 }
-int hbegp_debug_sens_phases(int enable, double* phase_ms) {
-  if (phase_ms)
-    for (int i = 0; i < 4; ++i) phase_ms[i] = t_sens_ms[i];
-  t_time_sens = enable != 0;
-  return HBEGP_OK;
-}
-int hbegp_debug_posterior_phases(int enable, double* phase_ms) {
-  if (phase_ms)
-    for (int i = 0; i < 4; ++i) phase_ms[i] = t_posterior_ms[i];
-  t_time_posterior = enable != 0;
-  return HBEGP_OK;
-}
+int hbegp_debug_sens_phases(int enable, double* phase_ms) { return debug_phases(PH_SENS, 4, enable, phase_ms); }
+int hbegp_debug_posterior_phases(int enable, double* phase_ms) { return debug_phases(PH_POSTERIOR, 4, enable, phase_ms); }
 
 int hbegp_model_info(const hbegp_model* model, int* n, int* d, int* is_f32, double* nu, double* lml) {
   if (!model) return fail(HBEGP_EINVAL, "NULL model");
