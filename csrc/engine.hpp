@@ -283,6 +283,23 @@ constexpr size_t ehvi_lds_bytes(int ns) { return 16 * (size_t)ns; }
 template <typename T>
 void launch_ehvi(const T* mean1, const T* var1, const T* dmean1, const T* dvar1, const T* mean2, const T* var2, const T* dmean2,
                  const T* dvar2, int m, int d, const double* thr, int ns, int want_grad, double* ehvi, T* grad, int* best, hipStream_t s);
+// constrained expected improvement over K = 1 + C independent models (hbegp_constrained_ei; cei_kernel: one wave per candidate;
+// DESIGN section 22).  Model 0 is the objective, models 1 .. C the constraints g_k <= thr[k]; thr[0] = fmin (+inf: no feasible
+// incumbent, EI counts as 1).  mean / var [m] and, with want_grad, dmean / dvar [m][d] of every model (dmean / dvar are not read
+// without a gradient).  Out: cei[m] (fp64), ei[m], pof[m] (fp64; each may be null), grad[m][d] (want_grad), *best = the last index
+// of the maximum of cei (NaN never wins; m >= 1).
+constexpr int CEI_MAX_MODELS = 9;  // 1 + HBEGP_CEI_MAX_CONSTRAINTS
+template <typename T>
+struct CeiArgs {
+  const T* mean[CEI_MAX_MODELS];
+  const T* var[CEI_MAX_MODELS];
+  const T* dmean[CEI_MAX_MODELS];
+  const T* dvar[CEI_MAX_MODELS];
+  double thr[CEI_MAX_MODELS];
+  int K;
+};
+template <typename T>
+void launch_cei(const CeiArgs<T>& a, int m, int d, int want_grad, double* cei, double* ei, double* pof, T* grad, int* best, hipStream_t s);
 // batch expected improvement by Monte Carlo (hbegp_qei; qei_batch_kernel: one workgroup per batch of q points).  Rows b q .. b q + q - 1
 // of Xs [B q][d], Q [mp][np], mean, dmean [mp][d] and W [d][mp][np] (W and dmean are read only with want_grad); z [S][q] shared by
 // the batches; noise = 1e-5 + jitter.  Out: qei[B], grad[B q][d] (want_grad), info[B] (0, or 1 + the column whose pivot failed).

@@ -2078,7 +2078,7 @@ struct CallScratch {
 // ---- phase times of the posterior-side calls (hbegp_debug_*_phases) ----------------------------------------------------------
 // One record per kind and calling thread: whether the thread's calls of that kind are timed, and the phase times (ms) of its last
 // timed call of that kind that reached its end.
-enum PhaseKind { PH_POSTERIOR, PH_SELECT, PH_KG, PH_NEI, PH_SENS, PH_EHVI, PH_QEI, PH_LOO, PH_PATHS, PH_KINDS };
+enum PhaseKind { PH_POSTERIOR, PH_SELECT, PH_KG, PH_NEI, PH_SENS, PH_EHVI, PH_QEI, PH_LOO, PH_PATHS, PH_CEI, PH_KINDS };
 struct PhaseRecord {
   bool on = false;
   double ms[4] = {0, 0, 0, 0};
@@ -2146,6 +2146,7 @@ class PhaseClock {
 //   qei        the shared launches, the qEI kernel
 //   loo        diagonal pass, u and Y, the SYRK, the weighted trace -- calls with a gradient only
 //   paths      hbegp_paths_create: uploads + frequency scaling, the feature projection, the two triangular products
+//   cei        the K predicts (the objective's upload .. the join of the K streams), the cEI kernel with the arg-max
 
 // Sigma = K** + noise I - Q Q^T at the candidates into W (lower tiles; m_p x m_p, kmat's identity padding): the candidates'
 // upload, the batched predict's launches (Kstar, the mean, Q = Kstar X^T; the variance too, unused), then kmat_kernel over
@@ -2726,6 +2727,141 @@ static int model_maximize_ehvi(hbegp_model* const* M, const T* starts, int S, co
     return (int)HBEGP_OK;
   };
   return lockstep_optimize<T, LbfgsState>(starts, S, d, lo, hi, lockstep_options(maxeval, true), eval, x_out, ehvi_out, nevals_out);
+}
+
+// ---- constrained expected improvement over an objective and C constraint models (hbegp_constrained_ei /
+// hbegp_maximize_constrained_ei) ----------------------------------------------------------------------------
+
+// the events the objective's stream waits on, one per constraint model, for the length of one C call
+struct CeiJoin {
+  std::vector<hipEvent_t> ev;
+  CeiJoin(int dev, int n_con) {
+    HIPCHECK(hipSetDevice(dev));
+    ev.reserve((size_t)n_con);
+    for (int k = 0; k < n_con; ++k) {
+      hipEvent_t e = nullptr;
+      HIPCHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+      ev.push_back(e);
+    }
+  }
+  ~CeiJoin() {
+    for (auto& e : ev) (void)hipEventDestroy(e);
+  }
+  CeiJoin(const CeiJoin&) = delete;
+  CeiJoin& operator=(const CeiJoin&) = delete;
+};
+
+// cEI at cnt >= 1 candidates under K = 1 + C models, M[0] the objective: model_ehvi's call pattern over a variable number of
+// models.  All K mutexes are taken in the order of the models' addresses (calls that name the same models in any order cannot wait
+// for each other).  Each model's upload and predict launches -- hbegp_predict's batched ones, or hbegp_predict_grad's with a
+// gradient, in their order -- go to its own stream; every constraint's stream records its own event, the objective's stream waits
+// for all of them and runs the cEI kernel, the arg-max and every copy back.  thr[0] = fmin, thr[k] = limits[k - 1] travel in the
+// kernel's arguments; the outputs are borrowed for the call (CallScratch) and go back cleared.  mean_out / var_out [cnt][K] (may be
+// null): the K posteriors of a row, the objective first.
+template <typename T>
+static int model_constrained_ei(hbegp_model* const* M, int K, const T* Xs, int cnt, const double* thr, const CeiJoin& join, double* cei,
+                                T* grad, int* best, double* ei, double* pof, T* mean_out, T* var_out) {
+  const bool want_grad = grad != nullptr;
+  const int d = M[0]->d;
+  // everything the call takes, counted before anything is taken: an m far beyond the device is ENOMEM, not an overflow
+  const double rows = std::ceil(std::max(1.0, (double)cnt) / NB) * NB;
+  double need = 3.0 * 8.0 * cnt + (want_grad ? (double)sizeof(T) * cnt * d : 0.0);
+  for (int k = 0; k < K; ++k)
+    need += (double)sizeof(T) * ((2.0 + (want_grad ? 2.0 * d : 0.0)) * rows * M[k]->np + rows * (d + 2) + (want_grad ? 2.0 * rows * d : 0.0)) +
+            8.0 * (want_grad ? (double)pred_grad_chunks(M[k]->n) * rows * d : 0.0);
+  if (need > 1e15 || rows > (double)(1 << 30))
+    return fail(HBEGP_ENOMEM, "constrained EI at %d points under %d models needs %.3g bytes of device memory", cnt, K, need);
+  std::vector<hbegp_model*> order(M, M + K);
+  std::sort(order.begin(), order.end(), std::less<hbegp_model*>());
+  std::vector<std::unique_lock<std::mutex>> locks;
+  locks.reserve((size_t)K);
+  for (hbegp_model* m : order) locks.emplace_back(m->mu);
+  HIPCHECK(hipSetDevice(M[0]->dev));
+  const int mp = round_up(cnt, NB);
+  for (int k = 0; k < K; ++k) {
+    if (want_grad) predict_grad_reserve<T>(M[k], mp);
+    else predict_batched_reserve<T>(M[k], mp);
+  }
+  hipStream_t s0 = M[0]->stream;
+  CallScratch ws{M[0]->dev, s0, {}};
+  double* dval = static_cast<double*>(ws.get(sizeof(double) * 3 * (size_t)cnt));  // cei | ei | pof
+  int* dbest = static_cast<int*>(ws.get(sizeof(int)));
+  T* dg = want_grad ? static_cast<T*>(ws.get(sizeof(T) * (size_t)cnt * d)) : nullptr;
+  PhaseClock clk(t_phase[PH_CEI].on, 3);  // all on the objective's stream: before its upload, behind the join, behind the arg-max
+  clk.mark(s0);
+  for (int k = 0; k < K; ++k) {
+    hbegp_model* m = M[k];
+    hipStream_t s = m->stream;
+    HIPCHECK(hipMemcpyAsync(m->Xs, Xs, sizeof(T) * (size_t)cnt * d, hipMemcpyHostToDevice, s));
+    predict_batched_launches<T>(m, cnt, mp, true);
+    if (want_grad) predict_grad_launches<T>(m, cnt, mp, true, true);
+    CHECK_LAUNCHES();
+    if (k > 0) HIPCHECK(hipEventRecord(join.ev[(size_t)k - 1], s));
+  }
+  for (int k = 1; k < K; ++k) HIPCHECK(hipStreamWaitEvent(s0, join.ev[(size_t)k - 1], 0));
+  clk.mark(s0);
+  CeiArgs<T> a{};
+  a.K = K;
+  for (int k = 0; k < K; ++k) {
+    a.mean[k] = static_cast<const T*>(M[k]->mean);
+    a.var[k] = static_cast<const T*>(M[k]->var);
+    a.dmean[k] = want_grad ? static_cast<const T*>(M[k]->dmean) : nullptr;  // (not read without a gradient)
+    a.dvar[k] = want_grad ? static_cast<const T*>(M[k]->dvar) : nullptr;
+    a.thr[k] = thr[k];
+  }
+  launch_cei<T>(a, cnt, d, want_grad ? 1 : 0, dval, dval + cnt, dval + 2 * (size_t)cnt, dg, dbest, s0);
+  clk.mark(s0);
+  CHECK_LAUNCHES();
+  int hbest = -1;
+  std::vector<T> hm, hv;
+  HIPCHECK(hipMemcpyAsync(cei, dval, sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost, s0));
+  if (ei) HIPCHECK(hipMemcpyAsync(ei, dval + cnt, sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost, s0));
+  if (pof) HIPCHECK(hipMemcpyAsync(pof, dval + 2 * (size_t)cnt, sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost, s0));
+  HIPCHECK(hipMemcpyAsync(&hbest, dbest, sizeof(int), hipMemcpyDeviceToHost, s0));
+  if (want_grad) HIPCHECK(hipMemcpyAsync(grad, dg, sizeof(T) * (size_t)cnt * d, hipMemcpyDeviceToHost, s0));
+  if (mean_out) {
+    hm.resize((size_t)K * cnt);
+    for (int k = 0; k < K; ++k)
+      HIPCHECK(hipMemcpyAsync(hm.data() + (size_t)k * cnt, M[k]->mean, sizeof(T) * (size_t)cnt, hipMemcpyDeviceToHost, s0));
+  }
+  if (var_out) {
+    hv.resize((size_t)K * cnt);
+    for (int k = 0; k < K; ++k)
+      HIPCHECK(hipMemcpyAsync(hv.data() + (size_t)k * cnt, M[k]->var, sizeof(T) * (size_t)cnt, hipMemcpyDeviceToHost, s0));
+  }
+  HIPCHECK(hipStreamSynchronize(s0));  // behind the events: every constraint's stream has finished this call's work too
+  if (best) *best = hbest;
+  for (int k = 0; k < K; ++k)
+    for (int i = 0; i < cnt; ++i) {
+      if (mean_out) mean_out[(size_t)K * i + k] = hm[(size_t)k * cnt + i];
+      if (var_out) var_out[(size_t)K * i + k] = hv[(size_t)k * cnt + i];
+    }
+  clk.store(PH_CEI, 2);
+  return HBEGP_OK;
+}
+
+// S bounded L-BFGS runs on -cEI in lockstep (lockstep.hpp), as model_maximize_ehvi: every round is ONE model_constrained_ei with a
+// gradient (one batched gradient predict per model, then the cEI kernel).  Each run returns the best point it evaluated; a value or
+// a gradient component that is not finite is a failed evaluation.
+template <typename T>
+static int model_maximize_constrained_ei(hbegp_model* const* M, int K, const T* starts, int S, const double* lo, const double* hi,
+                                         const double* thr, int maxeval, T* x_out, double* cei_out, int* nevals_out) {
+  const int d = M[0]->d;
+  CeiJoin join(M[0]->dev, K - 1);
+  std::vector<T> gr((size_t)S * d);
+  auto eval = [&](const T* xs, const int*, int cnt, double* val, double* grad, char* ok) {
+    const int rc = model_constrained_ei<T>(M, K, xs, cnt, thr, join, val, gr.data(), nullptr, nullptr, nullptr, nullptr, nullptr);
+    if (rc != HBEGP_OK) return rc;
+    for (int i = 0; i < cnt; ++i) {
+      ok[i] = std::isfinite(val[i]);
+      for (int k = 0; k < d; ++k) {
+        grad[(size_t)i * d + k] = (double)gr[(size_t)i * d + k];
+        ok[i] = ok[i] && std::isfinite(grad[(size_t)i * d + k]);
+      }
+    }
+    return (int)HBEGP_OK;
+  };
+  return lockstep_optimize<T, LbfgsState>(starts, S, d, lo, hi, lockstep_options(maxeval, true), eval, x_out, cei_out, nevals_out);
 }
 
 // Batch expected improvement by Monte Carlo (hbegp_qei) for B batches of q points: the B q points go through the batched predict's
@@ -4417,6 +4553,93 @@ int hbegp_maximize_ehvi_f32(hbegp_model* const* models, int n_obj, const float* 
   return do_maximize_ehvi<float>(models, n_obj, starts, S, lo, hi, front, P, ref, maxeval, x_out, ehvi_out, nevals_out);
 }
 int hbegp_debug_ehvi_phases(int enable, double* phase_ms) { return debug_phases(PH_EHVI, 3, enable, phase_ms); }
+}  // extern "C"
+
+// argument checks of hbegp_constrained_ei_* / hbegp_maximize_constrained_ei_*: everything is refused before any device call, the
+// checks that need no model first.  On success M = (objective, constraints ..) and thr = (fmin, limits ..).
+template <typename T>
+static int check_cei_models(hbegp_model* objective, hbegp_model* const* constraints, int n_con, double fmin, const double* limits,
+                            std::vector<hbegp_model*>* M, std::vector<double>* thr) {
+  if (n_con < 0 || n_con > HBEGP_CEI_MAX_CONSTRAINTS)
+    return fail(HBEGP_EINVAL, "n_con must lie in [0, %d] (got %d)", HBEGP_CEI_MAX_CONSTRAINTS, n_con);
+  if (std::isnan(fmin) || fmin == -std::numeric_limits<double>::infinity())
+    return fail(HBEGP_EINVAL, "fmin_normalized must be finite or +inf (got %g)", fmin);
+  if (n_con == 0 && std::isinf(fmin)) return fail(HBEGP_EINVAL, "n_con = 0 with fmin_normalized = +inf: nothing to compute");
+  if (!objective) return fail(HBEGP_EINVAL, "NULL objective");
+  if (n_con > 0 && (!constraints || !limits)) return fail(HBEGP_EINVAL, "constraints/limits is NULL");
+  M->assign(1, objective);
+  thr->assign(1, fmin);
+  for (int k = 0; k < n_con; ++k) {
+    if (!constraints[k]) return fail(HBEGP_EINVAL, "NULL model (constraint %d)", k);
+    for (hbegp_model* seen : *M)
+      if (seen == constraints[k])
+        return fail(HBEGP_EINVAL, seen == objective ? "constraint %d is the objective's model" : "the same model was passed twice (constraint %d)", k);
+    M->push_back(constraints[k]);
+  }
+  for (int k = 0; k <= n_con; ++k)
+    if ((*M)[k]->is_f32 != (sizeof(T) == 4)) return fail(HBEGP_EINVAL, "model %d holds %s data", k, (*M)[k]->is_f32 ? "f32" : "f64");
+  for (int k = 1; k <= n_con; ++k) {
+    if ((*M)[k]->d != objective->d) return fail(HBEGP_EINVAL, "the models differ in d (%d and %d)", objective->d, (*M)[k]->d);
+    if ((*M)[k]->dev != objective->dev)
+      return fail(HBEGP_EINVAL, "the models live on different devices (%d and %d)", objective->dev, (*M)[k]->dev);
+  }
+  for (int k = 0; k < n_con; ++k) {
+    if (!std::isfinite(limits[k])) return fail(HBEGP_EINVAL, "non-finite limit (constraint %d)", k);
+    thr->push_back(limits[k]);
+  }
+  return HBEGP_OK;
+}
+template <typename T>
+static int do_cei(hbegp_model* objective, hbegp_model* const* constraints, int n_con, const T* Xs, int m, double fmin, const double* limits,
+                  double* cei, T* grad, int* best, double* ei, double* pof, T* mean, T* var) {
+  if (m < 0) return fail(HBEGP_EINVAL, "m must be >= 0 (got %d)", m);
+  GUARD_BEGIN
+  std::vector<hbegp_model*> M;
+  std::vector<double> thr;
+  if (int rc = check_cei_models<T>(objective, constraints, n_con, fmin, limits, &M, &thr)) return rc;
+  if (m > 0 && (!Xs || !cei)) return fail(HBEGP_EINVAL, "Xs/cei is NULL");
+  if (best) *best = -1;
+  if (m == 0) return HBEGP_OK;
+  CeiJoin join(objective->dev, n_con);
+  return model_constrained_ei<T>(M.data(), 1 + n_con, Xs, m, thr.data(), join, cei, grad, best, ei, pof, mean, var);
+  GUARD_END
+}
+template <typename T>
+static int do_maximize_cei(hbegp_model* objective, hbegp_model* const* constraints, int n_con, const T* starts, int S, const double* lo,
+                           const double* hi, double fmin, const double* limits, int maxeval, T* x_out, double* cei_out, int* nevals_out) {
+  if (S < 1) return fail(HBEGP_EINVAL, "S must be >= 1 (got %d)", S);
+  GUARD_BEGIN
+  std::vector<hbegp_model*> M;
+  std::vector<double> thr;
+  if (int rc = check_cei_models<T>(objective, constraints, n_con, fmin, limits, &M, &thr)) return rc;
+  if (int rc = check_maximize_ei<T>(objective, starts, S, lo, hi, 0.0, maxeval, x_out, cei_out)) return rc;
+  return model_maximize_constrained_ei<T>(M.data(), 1 + n_con, starts, S, lo, hi, thr.data(), maxeval, x_out, cei_out, nevals_out);
+  GUARD_END
+}
+extern "C" {
+int hbegp_constrained_ei_f64(hbegp_model* objective, hbegp_model* const* constraints, int n_con, const double* Xs, int m,
+                             double fmin_normalized, const double* limits, double* cei, double* grad, int* best, double* ei, double* pof,
+                             double* mean, double* var) {
+  return do_cei<double>(objective, constraints, n_con, Xs, m, fmin_normalized, limits, cei, grad, best, ei, pof, mean, var);
+}
+int hbegp_constrained_ei_f32(hbegp_model* objective, hbegp_model* const* constraints, int n_con, const float* Xs, int m,
+                             double fmin_normalized, const double* limits, double* cei, float* grad, int* best, double* ei, double* pof,
+                             float* mean, float* var) {
+  return do_cei<float>(objective, constraints, n_con, Xs, m, fmin_normalized, limits, cei, grad, best, ei, pof, mean, var);
+}
+int hbegp_maximize_constrained_ei_f64(hbegp_model* objective, hbegp_model* const* constraints, int n_con, const double* starts, int S,
+                                      const double* lo, const double* hi, double fmin_normalized, const double* limits, int maxeval,
+                                      double* x_out, double* cei_out, int* nevals_out) {
+  return do_maximize_cei<double>(objective, constraints, n_con, starts, S, lo, hi, fmin_normalized, limits, maxeval, x_out, cei_out,
+                                 nevals_out);
+}
+int hbegp_maximize_constrained_ei_f32(hbegp_model* objective, hbegp_model* const* constraints, int n_con, const float* starts, int S,
+                                      const double* lo, const double* hi, double fmin_normalized, const double* limits, int maxeval,
+                                      float* x_out, double* cei_out, int* nevals_out) {
+  return do_maximize_cei<float>(objective, constraints, n_con, starts, S, lo, hi, fmin_normalized, limits, maxeval, x_out, cei_out,
+                                nevals_out);
+}
+int hbegp_debug_cei_phases(int enable, double* phase_ms) { return debug_phases(PH_CEI, 2, enable, phase_ms); }
 }  // extern "C"
 
 // argument checks of hbegp_sobol_* / hbegp_main_effects_*: everything is refused before any device call, the checks that need no

@@ -4618,6 +4618,99 @@ template void launch_ehvi<double>(const double*, const double*, const double*, c
 template void launch_ehvi<float>(const float*, const float*, const float*, const float*, const float*, const float*, const float*,
                                  const float*, int, int, const double*, int, int, double*, float*, int*, hipStream_t);
 
+// =================================================================================================================
+// constrained expected improvement over K = 1 + C independent models (hbegp.cpp: model_constrained_ei):
+//   cEI = EI_0 prod_{k=1..C} F_k,   EI_0 = G_0(fmin) (ehvi_g's G; 1 for fmin = +inf),   F_k = Phi((t_k - mu_k) / sigma_k).
+// One WAVE per candidate, CEI_WAVES candidates per workgroup.  Lane k < K evaluates ehvi_g for model k once and keeps its factor
+// f_k (EI_0 or F_k) with the factor's partials w.r.t. mu_k and sigma_k:
+//   dEI/dmu = -Phi(z), dEI/dsigma = phi(z);   dF/dmu = -phi(z) / sigma, dF/dsigma = -z phi(z) / sigma   (all 0 for sigma = 0 but
+//   dEI/dmu = -[fmin > mu]).
+// Every lane then reads f_1 .. f_C from the lanes that hold them and forms, in the same fixed order, pof = f_1 f_2 .. f_C
+// (ascending), the prefix product of the factors below its own index (ascending) and the suffix product of those above
+// (descending): lane k's partials get the weight EI_0 (prefix suffix) -- never pof / f_k, so f_k = 0 gives a finite gradient -- and
+// lane 0's get pof.  The lanes then stride over the features, adding the K models' chain-rule terms in ascending k
+// (dsigma = dvar / (2 sigma), 0 for sigma = 0).  All of it in fp64 for both element types, with or without a gradient, no LDS and
+// no atomics: a candidate's bits depend on nothing but its own posteriors and the thresholds.  A NaN in any model's posterior
+// gives NaN in the candidate's cei, ei, pof and gradient row.
+// =================================================================================================================
+constexpr int CEI_WAVES = 4;
+
+template <typename T>
+__global__ void __launch_bounds__(64 * CEI_WAVES) cei_kernel(const CeiArgs<T> a, int m, int d, int want_grad, double* __restrict__ cei,
+                                                             double* __restrict__ ei, double* __restrict__ pof, T* __restrict__ grad) {
+  const int lane = threadIdx.x & 63;
+  const int j = blockIdx.x * CEI_WAVES + (threadIdx.x >> 6);
+  if (j >= m) return;  // whole waves leave: every lane of a wave that stays takes part in the shuffles
+  const int K = a.K;
+  double f = 1.0, pm = 0.0, ps = 0.0, sd = 0.0;  // model `lane`: its factor, the factor's partials w.r.t. mu and sigma, sigma
+  bool bad = false;
+  if (lane < K) {
+    const double mu = (double)a.mean[lane][j], v = (double)a.var[lane][j], t = a.thr[lane];
+    sd = sqrt(v);
+    bad = (mu != mu) || (v != v);
+    const EhviG g = ehvi_g(t, mu, sd);
+    if (lane == 0) {
+      if (t < __longlong_as_double(0x7ff0000000000000LL)) {  // fmin = +inf: EI counts as 1, its partials as 0
+        f = g.g;
+        pm = -g.cdf;
+        ps = g.pdf;
+      }
+    } else {
+      f = g.cdf;
+      if (sd > 2.220446049250313e-16) {
+        const double z = (t - mu) / sd;
+        pm = -g.pdf / sd;
+        ps = -z * g.pdf / sd;
+      }
+    }
+  }
+  const bool anybad = __any(bad) != 0;
+  const double e = __shfl(f, 0, 64);
+  double all = 1.0, pre = 1.0, suf = 1.0;
+  for (int k = 1; k < K; ++k) {
+    const double fk = __shfl(f, k, 64);
+    all *= fk;
+    if (k < lane) pre *= fk;
+  }
+  for (int k = K - 1; k >= 1; --k) {
+    const double fk = __shfl(f, k, 64);
+    if (k > lane) suf *= fk;
+  }
+  const double nan = __longlong_as_double(0x7ff8000000000000LL);
+  if (lane == 0) {
+    cei[j] = anybad ? nan : e * all;
+    if (ei) ei[j] = anybad ? nan : e;
+    if (pof) pof[j] = anybad ? nan : all;
+  }
+  if (!want_grad) return;
+  const double w = lane == 0 ? all : e * (pre * suf);
+  const double cm = w * pm, cs = w * ps;  // d cei / d mu_lane, d cei / d sigma_lane
+  for (int base = 0; base < d; base += 64) {  // a uniform trip count: every lane takes part in the shuffles
+    const int i = base + lane;
+    const bool on = i < d;
+    const size_t x = (size_t)j * d + (on ? i : 0);
+    double g = 0.0;
+    for (int k = 0; k < K; ++k) {
+      const double cmk = __shfl(cm, k, 64), csk = __shfl(cs, k, 64), sdk = __shfl(sd, k, 64);
+      if (on) {
+        const double ds = sdk > 2.220446049250313e-16 ? (double)a.dvar[k][x] / (2.0 * sdk) : 0.0;
+        g += cmk * (double)a.dmean[k][x] + csk * ds;
+      }
+    }
+    if (on) grad[x] = anybad ? (T)nan : (T)g;
+  }
+}
+
+template <typename T>
+void launch_cei(const CeiArgs<T>& a, int m, int d, int want_grad, double* cei, double* ei, double* pof, T* grad, int* best,
+                hipStream_t s) {
+  const dim3 grid((unsigned)((m + CEI_WAVES - 1) / CEI_WAVES)), block(64 * CEI_WAVES);
+  hipLaunchKernelGGL((cei_kernel<T>), grid, block, 0, s, a, m, d, want_grad, cei, ei, pof, grad);
+  hipLaunchKernelGGL(ehvi_best_kernel, dim3(1), dim3(BSEL_THREADS), 0, s, cei, m, best);
+}
+template void launch_cei<double>(const CeiArgs<double>&, int, int, int, double*, double*, double*, double*, int*, hipStream_t);
+template void launch_cei<float>(const CeiArgs<float>&, int, int, int, double*, double*, double*, float*, int*, hipStream_t);
+
 // Per-device one-time setup: kernels that use more than 64 KiB of dynamic LDS need the attribute raised.  Called from
 // hbegp_ctx_create() for every device, before any stream capture.
 static void init_dag_kernels();  // dag_kernel.inc.hpp (end of this file)

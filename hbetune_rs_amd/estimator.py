@@ -710,6 +710,112 @@ def acquire_by_ehvi(candidates, models, k, front=None, ref=None, ctx=None):
     return np.array(idx, dtype=np.int64), proj, np.array(vals, dtype=np.float64), np.array(hvs, dtype=np.float64)
 
 
+# Constrained expected improvement (opt-in; nothing the estimator suggests by default uses it).
+def feasible_fmin(y, g, limits):
+    """The smallest objective y[i] among the rows whose constraint values all hold, g[i, k] <= limits[k] (a row exactly on a limit
+    is feasible); math.inf when no row qualifies -- the "no feasible incumbent" input of constrained_ei_a.  y [N], g [N, C]."""
+    y = np.asarray(y, dtype=np.float64).reshape(-1)
+    limits = np.asarray(limits, dtype=np.float64).reshape(-1)
+    g = np.asarray(g, dtype=np.float64).reshape(len(y), len(limits))
+    ok = (g <= limits[None, :]).all(axis=1)
+    return float(y[ok].min()) if ok.any() else math.inf
+
+
+def _cei_normalized(model, constraint_models, fmin, limits):
+    """fmin and every limit in y units -> that model's normalised space (float64); an infinite fmin stays infinite."""
+    limits = np.asarray(limits if limits is not None else [], dtype=np.float64).reshape(-1)
+    if len(limits) != len(constraint_models):
+        raise ValueError(f"{len(constraint_models)} constraint models but {len(limits)} limits")
+    fn = math.inf if math.isinf(fmin) and fmin > 0 else float(model.y_norm.project_into_normalized(np.array([fmin], dtype=np.float64))[0])
+    ln = np.array([float(mo.y_norm.project_into_normalized(limits[k:k + 1])[0]) for k, mo in enumerate(constraint_models)], dtype=np.float64)
+    return fn, ln
+
+
+def constrained_ei_a(model, constraint_models, x, fmin, limits):
+    """Constrained EI of the rows of x [m, d]: the EI of SurrogateModelGPR `model` (minimised) below fmin times the probability that
+    every constraint_models[k] stays at or below limits[k], the posteriors taken as independent (gpr.constrained_ei).  fmin and
+    limits are in y units; each goes through its own model's y projection, and EI is measured in the objective's normalised units.
+    fmin = math.inf (feasible_fmin without a feasible row): the probability of feasibility alone.  Returns (cei[m] float64, best):
+    best the last index of the maximum, -1 without rows."""
+    fn, ln = _cei_normalized(model, constraint_models, fmin, limits)
+    return gpr.constrained_ei(model.fitted, [mo.fitted for mo in constraint_models], np.asarray(x, dtype=model.dtype), fn, ln)
+
+
+def maximize_constrained_ei(model, constraint_models, starts, bounds, fmin, limits, maxeval=150):
+    """Bounded L-BFGS ascents of constrained_ei_a from every row of `starts` (the box: `bounds` = [(lo, hi)] per feature), all runs
+    in lockstep on the device models (gpr.maximize_constrained_ei).  fmin and limits in y units.  Returns (x[S, d], cei[S],
+    nevals[S])."""
+    fn, ln = _cei_normalized(model, constraint_models, fmin, limits)
+    return gpr.maximize_constrained_ei(model.fitted, [mo.fitted for mo in constraint_models], np.asarray(starts, dtype=model.dtype), bounds,
+                                       fn, ln, maxeval=maxeval)
+
+
+def _cei_default_fmin(models, limits):
+    """feasible_fmin of the models' training targets in y units; the models must have been trained on the very same rows."""
+    fks = [mo.fitted for mo in models]
+    xs = [fk.x_train for fk in fks]
+    if any(x is None for x in xs) or any(fk.y_train is None for fk in fks):
+        raise ValueError("the models do not hold their training rows: pass fmin")
+    if any(x.shape != xs[0].shape or x.tobytes() != xs[0].tobytes() for x in xs[1:]):
+        raise ValueError("the models were not trained on the same rows: pass fmin")
+    y = [np.asarray(mo.y_norm.project_location_from_normalized(np.asarray(mo.fitted.y_train)), dtype=np.float64) for mo in models]
+    return feasible_fmin(y[0], np.stack(y[1:], axis=1) if len(y) > 1 else np.zeros((len(y[0]), 0)), limits)
+
+
+def acquire_by_constrained_ei(candidates, model, constraint_models, k, limits, fmin=None, ctx=None):
+    """Batch acquisition under constraints by constrained EI over a candidate set [m, n_features]: k distinct rows, each the row of
+    largest cEI (gpr.constrained_ei: closed form, no random numbers).  After a pick EVERY surrogate is conditioned on the
+    kriging-believer fantasy (x_pick, that model's posterior mean) through extend_with at the same theta, as acquire_by_ehvi does;
+    when the believed constraint values all hold and the believed objective lies below fmin, fmin falls to it.  limits and fmin are
+    in y units.  Without fmin: feasible_fmin of the models' training targets, which needs models trained on the very same rows (else
+    ValueError); it is math.inf while no feasible row is known.  Returns (idx[k] int64, the projected means [k, 1 + C] of the picks
+    at the time they were picked, cei[k], and the fmin in force after each pick, in the objective's normalised units).  Opt-in:
+    nothing the estimator suggests by default calls it."""
+    models = [model] + list(constraint_models)
+    K = len(models)
+    dtype = model.dtype
+    c = np.asarray(candidates, dtype=dtype)
+    if c.ndim != 2:
+        raise ValueError("candidates must be [m, n_features]")
+    k = int(k)
+    if not 0 <= k <= c.shape[0]:
+        raise ValueError("k must lie in [0, number of rows]")
+    if fmin is None:
+        fmin = _cei_default_fmin(models, limits)
+    fn, ln = _cei_normalized(model, models[1:], fmin, limits)
+    fks = [mo.fitted for mo in models]
+    data = [(fk.x_train, fk.y_train) for fk in fks]
+    if k > 1 and any(X is None or y is None for X, y in data):
+        raise ValueError("the models do not hold their training rows: they cannot be conditioned on a fantasy")
+    avail = list(range(c.shape[0]))
+    idx, means, vals, fmins = [], [], [], []
+    try:
+        for t in range(k):
+            val, best, _, _, mean, _ = gpr.constrained_ei(fks[0], fks[1:], c[avail], fn, ln, want_details=True)
+            idx.append(avail.pop(best))
+            means.append(mean[best])
+            vals.append(val[best])
+            believed = np.asarray(mean[best], dtype=np.float64)
+            if (believed[1:] <= ln).all() and believed[0] < fn:
+                fn = float(believed[0])
+            fmins.append(fn)
+            if t + 1 < k:
+                for o in range(K):
+                    X, y = data[o]
+                    data[o] = (np.vstack([X, c[idx[-1]:idx[-1] + 1]]), np.concatenate([y, mean[best, o:o + 1]]))
+                    nxt = fks[o].extend_with(*data[o], ctx=ctx)
+                    if fks[o] is not models[o].fitted:
+                        fks[o].release()
+                    fks[o] = nxt
+    finally:
+        for o in range(K):
+            if fks[o] is not models[o].fitted:
+                fks[o].release()
+    means = np.array(means, dtype=dtype).reshape(-1, K)
+    proj = np.stack([models[o].y_norm.project_location_from_normalized(means[:, o]) for o in range(K)], axis=1)
+    return np.array(idx, dtype=np.int64), proj, np.array(vals, dtype=np.float64), np.array(fmins, dtype=np.float64)
+
+
 def _nei_baseline(fk, baseline, max_baseline, dtype):
     """The baseline of a noisy-EI call: `baseline` or the model's training rows; with max_baseline the rows of lowest posterior
     mean under fk (ties to the lower index), kept in their order."""

@@ -731,6 +731,68 @@ def maximize_ehvi(models, starts, bounds, front, ref, maxeval=150):
     return x, val, nevals
 
 
+def _cei_args(objective, constraints, limits):
+    """(constraints as a list, their handle array, limits [C] float64) of a constrained-EI call."""
+    constraints = list(constraints)
+    handles = (C.c_void_p * max(len(constraints), 1))(*[fk._h for fk in constraints])
+    limits = _lib.as_c(np.asarray(limits if limits is not None else [], dtype=np.float64).reshape(-1), np.float64)
+    if len(limits) != len(constraints):
+        raise ValueError(f"{len(constraints)} constraint models but {len(limits)} limits")
+    return constraints, handles, limits
+
+
+def constrained_ei(objective, constraints, x, fmin_normalized, limits, want_grad=False, want_details=False):
+    """Constrained expected improvement (hbegp_constrained_ei_*), in the models' normalised y spaces: the EI of the minimised
+    `objective` below fmin_normalized times the probability that every constraints[k] stays at or below limits[k].  objective and
+    constraints are FittedKernels of the same d, element type and device, taken as independent; at most CEI_MAX_CONSTRAINTS
+    constraints.  fmin_normalized = math.inf: no feasible point is known, EI counts as 1 and cei is the probability of
+    feasibility.  Returns (cei[m] float64, best) -- best the last index of the maximum, -1 for m = 0 -- then grad[m, d] with
+    want_grad, then (ei[m], pof[m], mean[m, 1 + C], var[m, 1 + C]) with want_details: the objective first, predict()'s numbers
+    bit for bit."""
+    constraints, handles, limits = _cei_args(objective, constraints, limits)
+    dtype, d, K = objective.dtype, objective.d, 1 + len(constraints)
+    x = _lib.as_c(np.asarray(x, dtype=dtype).reshape(-1, d), dtype)
+    m = x.shape[0]
+    val = np.zeros(m)
+    best = C.c_int(-1)
+    grad = np.zeros((m, d), dtype=dtype) if want_grad else None
+    ei = np.zeros(m) if want_details else None
+    pof = np.zeros(m) if want_details else None
+    mean = np.zeros((m, K), dtype=dtype) if want_details else None
+    var = np.zeros((m, K), dtype=dtype) if want_details else None
+    fn = getattr(_lib.load(), f"hbegp_constrained_ei_{objective._sfx}")
+    _lib.check(fn(objective._h, handles, len(constraints), _lib.aptr(x), m, float(fmin_normalized), _lib.dptr(limits), _lib.dptr(val),
+                  _lib.aptr(grad), C.byref(best), _lib.dptr(ei), _lib.dptr(pof), _lib.aptr(mean), _lib.aptr(var)))
+    out = (val, best.value)
+    if want_grad:
+        out += (grad,)
+    if want_details:
+        out += (ei, pof, mean, var)
+    return out
+
+
+def maximize_constrained_ei(objective, constraints, starts, bounds, fmin_normalized, limits, maxeval=150):
+    """S bounded L-BFGS runs maximising constrained_ei() over the box (hbegp_maximize_constrained_ei_*), one batched gradient
+    predict per model and round.  starts: [S, d] inside the box; bounds: d pairs (lo, hi).  Returns (x[S, d], cei[S], nevals[S]):
+    each run's best point, never worse than its start; constrained_ei(objective, constraints, x, ...) reproduces the values bit
+    for bit."""
+    constraints, handles, limits = _cei_args(objective, constraints, limits)
+    dtype, d = objective.dtype, objective.d
+    starts = _lib.as_c(np.atleast_2d(starts), dtype)
+    assert starts.shape[1] == d
+    S = starts.shape[0]
+    bounds = np.asarray(bounds, dtype=np.float64).reshape(d, 2)
+    lo = _lib.as_c(bounds[:, 0], np.float64)
+    hi = _lib.as_c(bounds[:, 1], np.float64)
+    x = np.zeros((S, d), dtype=dtype)
+    val = np.zeros(S)
+    nevals = np.zeros(S, dtype=np.int32)
+    fn = getattr(_lib.load(), f"hbegp_maximize_constrained_ei_{objective._sfx}")
+    _lib.check(fn(objective._h, handles, len(constraints), _lib.aptr(starts), S, _lib.dptr(lo), _lib.dptr(hi), float(fmin_normalized),
+                  _lib.dptr(limits), int(maxeval), _lib.aptr(x), _lib.dptr(val), nevals.ctypes.data_as(C.POINTER(C.c_int))))
+    return x, val, nevals
+
+
 def minimize_by_gradient(objective, x0, bounds, maxeval=150):
     """util::minimize_by_gradient (gradmin.rs:35-60) through the library's bounded L-BFGS."""
     lib = _lib.load()

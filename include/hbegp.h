@@ -419,6 +419,64 @@ int hbegp_maximize_ehvi_f32(hbegp_model* const* models, int n_obj, const float* 
                             const double* front, int P, const double* ref, int maxeval, float* x_out, double* ehvi_out,
                             int* nevals_out);
 
+/* Constrained expected improvement (cEI; Gardner et al. 2014, Gelbart et al. 2014): the expected improvement of a minimised objective
+ * times the probability that C constraints g_k(x) <= t_k hold, each quantity modelled by its own model; the 1 + C posteriors are
+ * taken as independent.  Everything is in each model's own normalised y space.  Model 0 is `objective`, models 1 .. C are
+ * constraints[0 .. n_con) with limits[k - 1] = t_k (0 <= n_con <= HBEGP_CEI_MAX_CONSTRAINTS); they share d, the element type and the
+ * device and may differ in n and nu.  limits and fmin_normalized are always double.  At a row of Xs[m*d] model k has the posterior
+ * N(mu_k, sigma_k^2) of hbegp_predict_* (the variance clamped at 0, without the noise), sigma_k = sqrt(var_k); "sigma = 0" means
+ * !(sigma > 2.220446049250313e-16), as in hbegp_ehvi_*.  With h(z) = z Phi(z) + phi(z), z_0 = (fmin - mu_0) / sigma_0 and
+ * z_k = (t_k - mu_k) / sigma_k:
+ *   ei  = sigma_0 h(z_0)              -- hbegp_ehvi_*'s G_0(fmin), evaluated the same way: phi(a) - a Phi(-a) for z = -a <= 0,
+ *                                        z + h(-z) above, the tail terms exactly 0 beyond |z| = 38
+ *   F_k = Phi(z_k)                    -- from the same evaluation; exactly 0 (or 1) beyond |z| = 38
+ *   pof = F_1 F_2 .. F_C              -- multiplied in ascending k; 1.0 for n_con = 0
+ *   cei = ei * pof >= 0.
+ * ei is expected_improvement (acquisition.rs:141-171) up to rounding; it is NOT bit for bit the host formula inside
+ * hbegp_maximize_ei_*.  sigma_0 = 0: ei = (fmin - mu_0)^+.  sigma_k = 0: F_k = [t_k > mu_k].
+ * fmin_normalized = +inf means "no feasible point is known": ei counts as 1 and its partials as 0, so cei = pof and the call is a
+ * search for feasibility.  -inf and NaN are refused, and so is n_con = 0 with fmin = +inf (nothing would be computed).
+ * grad[m*d] (may be NULL: then no gradient launch is issued) is formed WITHOUT dividing by F_k:
+ *   d cei / d(.)_0 = pof * d ei / d(.)_0,           d ei / d mu_0 = -Phi(z_0),        d ei / d sigma_0 = phi(z_0)
+ *   d cei / d(.)_k = ei * W_k * d F_k / d(.)_k,     d F_k / d mu_k = -phi(z_k) / sigma_k,  d F_k / d sigma_k = -z_k phi(z_k) / sigma_k
+ * with W_k = prod_{j != k} F_j from a prefix (ascending) and a suffix (descending) product in a fixed order, so a factor that is
+ * exactly 0 leaves the gradient finite.  sigma = 0: the partial w.r.t. that sigma counts as 0, and so do both partials of F_k.
+ *   grad[j][i] = sum_{k=0..C} (d cei / d mu_k * dmean_k[j][i] + d cei / d sigma_k * dvar_k[j][i] / (2 sigma_k)),  ascending k,
+ * dmean and dvar being hbegp_predict_grad_*'s.  All arithmetic is fp64 for both element types, in a fixed order without atomics:
+ * cei, ei and pof are double, and a row's bits depend only on its own posteriors, fmin and limits -- not on m, on the row's
+ * position, or on whether a gradient was asked for.  There is no log-space form: a product that falls below the normal range
+ * (about 1e-308) loses its digits to gradual underflow and ends as exactly 0, with a zero gradient.
+ * cei[m] (required for m > 0); best (may be NULL): the LAST index of the maximum of cei (a NaN never wins; -1 for m = 0); ei[m],
+ * pof[m] (each may be NULL); mean[m*(1+C)], var[m*(1+C)] (each may be NULL): row j holds the objective then the constraints, bit
+ * for bit what hbegp_predict_* returns on its batched path (m > 16), or hbegp_predict_grad_* with a gradient.  A NaN coordinate
+ * gives NaN in that row of cei, ei, pof and grad only.  m = 0 is a no-op.
+ * HBEGP_EINVAL (before any device call; a refused call writes nothing) for a NULL objective, n_con < 0 or
+ * > HBEGP_CEI_MAX_CONSTRAINTS, a NULL constraints or limits with n_con > 0, a NULL entry in constraints, any model named twice (the
+ * objective included), models of different d, element type or device, a model of the other element type, a non-finite limit, a
+ * fmin that is NaN or -inf, n_con = 0 with fmin = +inf, m < 0, or a NULL Xs or cei with m > 0.  All 1 + C models are locked for the
+ * call, in a fixed order: calls that name them in any order never wait for each other.  Each model's predict runs on its own
+ * stream; the outputs are borrowed for the call; work that does not fit in device memory is HBEGP_ENOMEM. */
+#define HBEGP_CEI_MAX_CONSTRAINTS 8
+int hbegp_constrained_ei_f64(hbegp_model* objective, hbegp_model* const* constraints, int n_con, const double* Xs, int m,
+                             double fmin_normalized, const double* limits, double* cei, double* grad, int* best, double* ei,
+                             double* pof, double* mean, double* var);
+int hbegp_constrained_ei_f32(hbegp_model* objective, hbegp_model* const* constraints, int n_con, const float* Xs, int m,
+                             double fmin_normalized, const double* limits, double* cei, float* grad, int* best, double* ei,
+                             double* pof, float* mean, float* var);
+/* S bounded L-BFGS runs maximising hbegp_constrained_ei_* over the box [lo, hi] in lockstep, with the contract of
+ * hbegp_maximize_ehvi_*: every round is one batched gradient predict per model over the runs still going and the cEI kernel with its
+ * gradient.  starts[S*d] inside the box; x_out[S*d], cei_out[S]: each run's best evaluated point (never worse than its start; an f32
+ * run evaluates and returns f32 points of the box) -- hbegp_constrained_ei_* at x_out reproduces cei_out bit for bit; nevals_out[S]
+ * (may be NULL) <= maxeval.  A value or a gradient component that is not finite is a failed evaluation.  HBEGP_EINVAL for
+ * everything hbegp_constrained_ei_* refuses about the models, fmin and limits, and for S < 1, a NULL starts / lo / hi / x_out /
+ * cei_out, maxeval < 1, lo > hi or a start outside the box. */
+int hbegp_maximize_constrained_ei_f64(hbegp_model* objective, hbegp_model* const* constraints, int n_con, const double* starts, int S,
+                                      const double* lo, const double* hi, double fmin_normalized, const double* limits, int maxeval,
+                                      double* x_out, double* cei_out, int* nevals_out);
+int hbegp_maximize_constrained_ei_f32(hbegp_model* objective, hbegp_model* const* constraints, int n_con, const float* starts, int S,
+                                      const double* lo, const double* hi, double fmin_normalized, const double* limits, int maxeval,
+                                      float* x_out, double* cei_out, int* nevals_out);
+
 /* Sensitivity of the posterior mean mu (hbegp_predict_*'s mean, normalised y space) to each feature, from the CALLER's sample
  * matrices in the feature coordinates the model was fitted on (the RNG stays on the caller side).  Both calls evaluate the mean at
  * base rows with ONE coordinate substituted,
@@ -599,6 +657,10 @@ int hbegp_debug_nei_phases(int enable, double* phase_ms);
  * last timed hbegp_ehvi_* call -- objective 0's predict and objective 1's (each with its upload, on its own stream: they overlap),
  * the EHVI kernel with the arg-max -- in milliseconds; then enable != 0 makes this thread's later EHVI calls timed. */
 int hbegp_debug_ehvi_phases(int enable, double* phase_ms);
+/* ---- timing hook (tools/cei_bench.py): phase_ms[2] (may be NULL) receives the device time of the phases of the calling thread's
+ * last timed hbegp_constrained_ei_* call -- the 1 + C predicts (from the objective's upload to the join of the streams: they
+ * overlap), the cEI kernel with the arg-max -- in milliseconds; then enable != 0 makes this thread's later cEI calls timed. */
+int hbegp_debug_cei_phases(int enable, double* phase_ms);
 /* ---- timing hook (tools/sens_bench.py): phase_ms[4] (may be NULL) receives the device time of the phases of the calling thread's
  * last timed hbegp_sobol_* / hbegp_main_effects_* call -- the upload (with the grid's scaling), the substituted means, the chunk and
  * row sums (both summed over the slabs), the final reduction with the downloads -- in milliseconds; then enable != 0 makes this

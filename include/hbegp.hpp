@@ -94,6 +94,14 @@ template <> struct Abi<double> {
                            const double* ref, int maxeval, double* x, double* v, int* ne) {
     return hbegp_maximize_ehvi_f64(ms, no, st, s, lo, hi, front, P, ref, maxeval, x, v, ne);
   }
+  static int constrained_ei(hbegp_model* o, hbegp_model* const* cs, int nc, const double* xs, int m, double fmin, const double* lim, double* v, double* g,
+                            int* best, double* ei, double* pof, double* mean, double* var) {
+    return hbegp_constrained_ei_f64(o, cs, nc, xs, m, fmin, lim, v, g, best, ei, pof, mean, var);
+  }
+  static int maximize_constrained_ei(hbegp_model* o, hbegp_model* const* cs, int nc, const double* st, int s, const double* lo, const double* hi,
+                                     double fmin, const double* lim, int maxeval, double* x, double* v, int* ne) {
+    return hbegp_maximize_constrained_ei_f64(o, cs, nc, st, s, lo, hi, fmin, lim, maxeval, x, v, ne);
+  }
   static int get(hbegp_model* m, double* t, double* a, double* ki) { return hbegp_model_get_f64(m, t, a, ki); }
 };
 template <> struct Abi<float> {
@@ -147,6 +155,14 @@ template <> struct Abi<float> {
   static int maximize_ehvi(hbegp_model* const* ms, int no, const float* st, int s, const double* lo, const double* hi, const double* front, int P,
                            const double* ref, int maxeval, float* x, double* v, int* ne) {
     return hbegp_maximize_ehvi_f32(ms, no, st, s, lo, hi, front, P, ref, maxeval, x, v, ne);
+  }
+  static int constrained_ei(hbegp_model* o, hbegp_model* const* cs, int nc, const float* xs, int m, double fmin, const double* lim, double* v, float* g,
+                            int* best, double* ei, double* pof, float* mean, float* var) {
+    return hbegp_constrained_ei_f32(o, cs, nc, xs, m, fmin, lim, v, g, best, ei, pof, mean, var);
+  }
+  static int maximize_constrained_ei(hbegp_model* o, hbegp_model* const* cs, int nc, const float* st, int s, const double* lo, const double* hi,
+                                     double fmin, const double* lim, int maxeval, float* x, double* v, int* ne) {
+    return hbegp_maximize_constrained_ei_f32(o, cs, nc, st, s, lo, hi, fmin, lim, maxeval, x, v, ne);
   }
   static int get(hbegp_model* m, double* t, float* a, float* ki) { return hbegp_model_get_f32(m, t, a, ki); }
 };
@@ -313,6 +329,30 @@ void maximize_ehvi(const FittedKernel<A>& obj0, const FittedKernel<A>& obj1, con
                    const double* front, int P, const double* ref, int maxeval, A* x_out, double* ehvi_out, int* nevals = nullptr) {
   hbegp_model* ms[2] = {obj0.handle(), obj1.handle()};
   check(detail::Abi<A>::maximize_ehvi(ms, 2, starts, S, lo, hi, front, P, ref, maxeval, x_out, ehvi_out, nevals));
+}
+
+// Constrained expected improvement at xs[m*d]: the EI of the minimised `objective` below fmin (normalised y space; +infinity: no
+// feasible point is known, EI counts as 1) times the probability that every constraints[k] stays at or below limits[k], each
+// quantity modelled by its own FittedKernel, taken as independent; at most HBEGP_CEI_MAX_CONSTRAINTS constraints.  cei[m]; grad[m*d],
+// best (the last index of the maximum), ei[m], pof[m], mean[m*(1+C)], var[m*(1+C)] (the objective then the constraints per row) may
+// be nullptr
+template <typename A>
+void constrained_ei(const FittedKernel<A>& objective, const std::vector<const FittedKernel<A>*>& constraints, const A* xs, int m, double fmin,
+                    const double* limits, double* cei, A* grad = nullptr, int* best = nullptr, double* ei = nullptr, double* pof = nullptr,
+                    A* mean = nullptr, A* var = nullptr) {
+  std::vector<hbegp_model*> cs;
+  for (const auto* c : constraints) cs.push_back(c ? c->handle() : nullptr);
+  check(detail::Abi<A>::constrained_ei(objective.handle(), cs.data(), (int)cs.size(), xs, m, fmin, limits, cei, grad, best, ei, pof, mean, var));
+}
+// S bounded L-BFGS ascents of that cEI from starts[S*d] inside [lo, hi]; x_out[S*d], cei_out[S], nevals[S] (may be nullptr)
+template <typename A>
+void maximize_constrained_ei(const FittedKernel<A>& objective, const std::vector<const FittedKernel<A>*>& constraints, const A* starts, int S,
+                             const double* lo, const double* hi, double fmin, const double* limits, int maxeval, A* x_out, double* cei_out,
+                             int* nevals = nullptr) {
+  std::vector<hbegp_model*> cs;
+  for (const auto* c : constraints) cs.push_back(c ? c->handle() : nullptr);
+  check(detail::Abi<A>::maximize_constrained_ei(objective.handle(), cs.data(), (int)cs.size(), starts, S, lo, hi, fmin, limits, maxeval, x_out,
+                                                cei_out, nevals));
 }
 
 // RAII owner of an hbegp_paths handle (FittedKernel::sample_paths); it keeps its model alive
