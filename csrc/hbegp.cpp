@@ -88,8 +88,13 @@ static std::atomic<int> g_live_ctx{0};  // the block pool is process-global: it 
 // ---------------------------------------------------------------------------------------------------------------
 // Device-memory pool for the large work matrices (np x np).  hipMalloc/hipFree of 128 MiB blocks costs tens of
 // milliseconds per fit; the caller fits one model per generation with slowly growing n, so blocks are recycled by
-// exact size.  Recycled blocks hold finite numbers from their previous life, which is all the engine requires of
-// never-written regions (strict upper triangles).
+// exact size.  What a block holds when it is handed out: zeros if it is fresh, otherwise whatever its last owner left --
+// not necessarily finite numbers (an evaluation whose factorisation failed leaves NaN in L, L^-1 and K^-1, a NaN feature
+// leaves NaN in K, a model at extreme parameters a K^-1 of 1e302).  So the engine requires NOTHING of a region its owner
+// never writes: every such region is either never read, or only read into a place that is itself never read (W1's strict upper
+// part: the upper tiles, and the upper right quadrant of the diagonal tiles, which SYRK's C += updates in place), or it is
+// cleared by the owner (W2 / Xalt: triangular GEMM operands, whose diagonal tiles are loaded whole).  The table of every block
+// is DESIGN section 23; tests/test_gpu_pool_hygiene.py holds every entry point to it under HBEGP_POOL_POISON.
 #include <chrono>
 #include <condition_variable>
 #include <map>
@@ -119,7 +124,11 @@ struct DevPool {
     //   HBEGP_POOL_NULL_DELAY_MB=N queue an N MiB fill on the null stream in front of every fresh block's clear (makes the
     //                              clear LATE on purpose: a first writer on a non-blocking stream then runs before it)
     //   HBEGP_POOL_OLD_CLEAR=1     round 1-4's clear: hipMemset with no synchronisation (the race the test must see fail)
+    //   HBEGP_POOL_POISON=1|2      fill every block handed out, fresh (after its clear) or recycled, with finite garbage (1)
+    //                              or with quiet NaNs (2): no result may depend on it (tests/test_gpu_pool_hygiene.py)
     const bool always_fresh = getenv("HBEGP_POOL_FRESH") != nullptr && atoi(getenv("HBEGP_POOL_FRESH")) != 0;
+    void* recycled = nullptr;
+    unsigned word = 0;
     if (!always_fresh) {
       std::lock_guard<std::mutex> lk(mu);
       auto it = free_list.find({dev, bytes});
@@ -128,8 +137,19 @@ struct DevPool {
         it->second.pop_back();
         cached -= bytes;
         *fresh = false;
-        return p;
+        recycled = p;
       }
+    }
+    if (recycled) {
+      if (poison_word(&word)) {
+        try {
+          poison(dev, recycled, bytes, word);
+        } catch (...) {
+          put(dev, recycled, bytes);
+          throw;
+        }
+      }
+      return recycled;
     }
     void* p = nullptr;
     hipError_t e = hipMalloc(&p, bytes);
@@ -138,8 +158,7 @@ struct DevPool {
       e = hipMalloc(&p, bytes);
       if (e != hipSuccess) throw HipError{e, "hipMalloc (pool)", __LINE__};
     }
-    // a fresh block is cleared once, here: every later owner may rely on "finite numbers everywhere" (recycled blocks
-    // hold finite results of their previous life)
+    // a fresh block is cleared once, here (a recycled one is handed out as its last owner left it: see above)
     // hipMemset on device memory returns before the fill has run (it is queued on the null stream), and the engine's streams are
     // non-blocking ones that do not wait for the null stream: without the synchronisation below the fill runs CONCURRENTLY with,
     // or after, the block's first writer on such a stream (the model's copy of L^-1 in make_model, the kernel-matrix tiles of an
@@ -175,8 +194,40 @@ struct DevPool {
       (void)hipFree(p);
       throw HipError{e, "hipMemset (pool)", __LINE__};
     }
+    if (poison_word(&word)) {
+      try {
+        poison(dev, p, bytes, word);
+      } catch (...) {
+        (void)hipFree(p);
+        throw;
+      }
+    }
     *fresh = true;
     return p;
+  }
+  // HBEGP_POOL_POISON, read per call: 1 = 0x40490FDB (3.1415927f as a float, ~50.12 as the double 0x40490FDB40490FDB),
+  // 2 = 0x7FF80000 (a quiet NaN in both element types).  Unset or 0: nothing.
+  static bool poison_word(unsigned* word) {
+    const char* v = getenv("HBEGP_POOL_POISON");
+    const int mode = v ? atoi(v) : 0;
+    if (mode == 1) *word = 0x40490FDBu;
+    else if (mode == 2) *word = 0x7FF80000u;
+    else return false;
+    return true;
+  }
+  std::atomic<long long> poisoned_blocks{0}, poisoned_bytes{0};  // totals since process start (hbegp_debug_pool_poisoned)
+  // The fill runs on the pool's own stream and is waited for, as the clear of a fresh block is; the trailing bytes % 4 bytes
+  // get the word's low byte.
+  void poison(int dev, void* p, size_t bytes, unsigned word) {
+    hipStream_t st = stream_of(dev);
+    hipError_t e = hipSuccess;
+    const size_t words = bytes / 4, tail = bytes % 4;
+    if (words) e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(p), (int)word, words, st);
+    if (e == hipSuccess && tail) e = hipMemsetD8Async(reinterpret_cast<hipDeviceptr_t>(static_cast<char*>(p) + 4 * words), (unsigned char)(word & 0xff), tail, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) throw HipError{e, "poison fill (pool)", __LINE__};
+    poisoned_blocks.fetch_add(1, std::memory_order_relaxed);
+    poisoned_bytes.fetch_add((long long)bytes, std::memory_order_relaxed);
   }
   void put(int dev, void* p, size_t bytes) {
     if (!p) return;
@@ -863,7 +914,10 @@ struct Problem : ProblemBase {
         // W2 carries the triangular operand X = L^-1.  The GEMM loader does not mask: the strict upper triangle of W2 must
         // BE zero (tiles on the diagonal are loaded whole).  Nothing in the engine writes there, so clearing the buffer
         // once per slot is enough -- also when it is recycled from the pool (it may have held a full symmetric K^-1).
-        // W1's strict upper part is only ever multiplied by those zeros or ignored: it just has to be finite.
+        // W1 needs no clear: it is a GEMM operand only through tiles strictly below the diagonal, which kmat_kernel writes
+        // whole; of its diagonal tiles the diagonal-block kernels read the lower triangle, and what the SYRK updates leave in
+        // their upper right quadrants (whatever was there, NaN included, minus L21 L21^T) is never read.  K^-1 and W3 (L)
+        // likewise: only written tiles are read.
         HIPCHECK(hipMemsetAsync(s.W2, 0, sizeof(T) * nn, st0));
         (void)fresh1; (void)fresh2; (void)fk;  // fresh blocks were cleared by the pool
         // the small per-slot arrays: one pooled block
@@ -4718,6 +4772,11 @@ int hbegp_model_get_f64(hbegp_model* model, double* theta, double* alpha, double
 }
 int hbegp_model_get_f32(hbegp_model* model, double* theta, float* alpha, float* kinv) {
   return model_get<float>(model, theta, alpha, kinv);
+}
+int hbegp_debug_pool_poisoned(long long* blocks, long long* bytes) {
+  if (blocks) *blocks = g_pool.poisoned_blocks.load(std::memory_order_relaxed);
+  if (bytes) *bytes = g_pool.poisoned_bytes.load(std::memory_order_relaxed);
+  return HBEGP_OK;
 }
 int hbegp_model_debug_params(hbegp_model* model, double* out) {
   if (!model) return fail(HBEGP_EINVAL, "NULL model");

@@ -155,6 +155,7 @@ SIGNATURES = {
     "hbegp_debug_sens_phases": (C.c_int, [C.c_int, _dp]),
     "hbegp_debug_ehvi_phases": (C.c_int, [C.c_int, _dp]),
     "hbegp_debug_cei_phases": (C.c_int, [C.c_int, _dp]),
+    "hbegp_debug_pool_poisoned": (C.c_int, [C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "hbegp_model_info": (C.c_int, [_vp, _ip, _ip, _ip, _dp, _dp]),
     "hbegp_model_get_f64": (C.c_int, [_vp, _dp, _dp, _dp]),
     "hbegp_model_get_f32": (C.c_int, [_vp, _dp, _fp, _fp]),

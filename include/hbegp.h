@@ -635,6 +635,10 @@ int hbegp_debug_lbfgs_decisions(int n, const double* x0, const double* lo, const
 int hbegp_debug_dag_queues(int nblocks, int bk, int small_h, int nwg, int fine, int big128, int which, int* ntasks, int* tasks, int cap,
                            char* err, int errlen);
 
+/* ---- test hook (tests/test_gpu_pool_hygiene.py): how many blocks of the device pool, and how many bytes, have been filled on
+ * hand-out under HBEGP_POOL_POISON (1: the word 0x40490FDB, finite in both element types; 2: 0x7FF80000, a quiet NaN in both)
+ * since the process started.  Either pointer may be NULL.  Needs no GPU. */
+int hbegp_debug_pool_poisoned(long long* blocks, long long* bytes);
 /* ---- timing hook (tools/posterior_cov_bench.py): phase_ms[4] (may be NULL) receives the device time of the phases of the
  * calling thread's last timed hbegp_sample_posterior_* call -- Q (Kstar, mean, Q = Kstar L^-T), Sigma, its factor, the draws
  * (upload of z, Z L^T, epilogue) -- in milliseconds; then enable != 0 makes this thread's later sampling calls timed (events

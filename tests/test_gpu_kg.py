@@ -48,7 +48,7 @@ def _replay(fk, Xs, mc, dtype):
     kg, best, imin, mean, var = fk.knowledge_gradient(Xs, n_candidates=mc, want_posterior=True)
     assert kg.dtype == np.float64 and kg.shape == (mc,) and mean.dtype == dtype and var.dtype == dtype
     mean0, cov = fk.predict_cov(Xs)
-    ref = KG.kg(mean0, cov, fk.device_params()[0], mc=mc)
+    ref = KG.kg(mean0, np.asarray(cov, np.float64), fk.device_params()[0], mc=mc)  # (one conversion, not one per candidate)
     dev = float(np.abs(kg - ref).max()) if mc else 0.0
     assert dev <= KG.bars(dtype, fk.amplitude), (m, mc, dev)
     assert (kg >= 0.0).all()
@@ -87,6 +87,37 @@ def test_replay_past_the_lds_limit():
     fk, X, y = _model(300, 2.5, np.float64, seed=4)
     dev = _replay(fk, _candidates(10000, 6, np.float64), 8, np.float64)  # 16384 padded lines: the global workspace
     print(f"n=300 m=10000 mc=8: kg deviation {dev:.1e}")
+    fk.release()
+
+
+@pytest.mark.parametrize("m", [4096, 4097, 8192, 8193])
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_replay_around_the_line_storage_limits(dtype, m):
+    """The lines of a candidate live in dynamic LDS up to P = 8192 padded rows, above that in a pool block: m = 4096 is the first
+    launch above the 64 KiB a kernel gets by default (P = 4096: 67,600 B), 4097 and 8192 the largest (P = 8192: 133,136 B), 8193
+    the first with the global workspace (P = 16384)."""
+    fk, X, y = _model(300, 2.5, dtype, seed=4)
+    dev = _replay(fk, _candidates(m, 6, dtype), 8, dtype)
+    print(f"{np.dtype(dtype).name} n=300 m={m} mc=8: kg deviation {dev:.1e} (bar {KG.bars(dtype, fk.amplitude):.1e})")
+    fk.release()
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_a_workgroups_second_candidate_in_the_global_workspace(dtype):
+    """mc = 520 > KG_GLOBAL_WGS = 512 at m = 8193: workgroups 0 .. 7 run candidates 512 .. 519 in the lines their first candidate
+    left behind."""
+    fk, X, y = _model(300, 2.5, dtype, seed=4)
+    Xs = _candidates(8193, 6, dtype)
+    kg8, _, _ = fk.knowledge_gradient(Xs, n_candidates=8)
+    kg, best, imin = fk.knowledge_gradient(Xs, n_candidates=520)
+    assert kg[:8].tobytes() == kg8.tobytes()
+    mean, cov = fk.predict_cov(Xs)
+    s2 = fk.device_params()[0]
+    cov64, mean64 = np.asarray(cov, np.float64), np.asarray(mean, np.float64)
+    for j in (0, 511, 512, 513, 519):
+        ref = KG.h(-mean64, -KG.sigma_tilde(cov64, j, s2)[0])
+        assert abs(kg[j] - ref) <= KG.bars(dtype, fk.amplitude), (j, kg[j], ref)
+    assert best == KG.argmax_last(kg) and imin == int(np.argmin(mean))
     fk.release()
 
 
