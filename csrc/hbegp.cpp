@@ -2132,7 +2132,7 @@ struct CallScratch {
 // ---- phase times of the posterior-side calls (hbegp_debug_*_phases) ----------------------------------------------------------
 // One record per kind and calling thread: whether the thread's calls of that kind are timed, and the phase times (ms) of its last
 // timed call of that kind that reached its end.
-enum PhaseKind { PH_POSTERIOR, PH_SELECT, PH_KG, PH_NEI, PH_SENS, PH_EHVI, PH_QEI, PH_LOO, PH_PATHS, PH_CEI, PH_KINDS };
+enum PhaseKind { PH_POSTERIOR, PH_SELECT, PH_KG, PH_NEI, PH_SENS, PH_EHVI, PH_QEI, PH_LOO, PH_PATHS, PH_CEI, PH_LCEI, PH_KINDS };
 struct PhaseRecord {
   bool on = false;
   double ms[4] = {0, 0, 0, 0};
@@ -2201,6 +2201,7 @@ class PhaseClock {
 //   loo        diagonal pass, u and Y, the SYRK, the weighted trace -- calls with a gradient only
 //   paths      hbegp_paths_create: uploads + frequency scaling, the feature projection, the two triangular products
 //   cei        the K predicts (the objective's upload .. the join of the K streams), the cEI kernel with the arg-max
+//   lcei       as cei, the second phase being the log-space kernel with the arg-max
 
 // Sigma = K** + noise I - Q Q^T at the candidates into W (lower tiles; m_p x m_p, kmat's identity padding): the candidates'
 // upload, the batched predict's launches (Kstar, the mean, Q = Kstar X^T; the variance too, unused), then kmat_kernel over
@@ -2811,10 +2812,12 @@ struct CeiJoin {
 // gradient, in their order -- go to its own stream; every constraint's stream records its own event, the objective's stream waits
 // for all of them and runs the cEI kernel, the arg-max and every copy back.  thr[0] = fmin, thr[k] = limits[k - 1] travel in the
 // kernel's arguments; the outputs are borrowed for the call (CallScratch) and go back cleared.  mean_out / var_out [cnt][K] (may be
-// null): the K posteriors of a row, the objective first.
+// null): the K posteriors of a row, the objective first.  log_space (hbegp_log_constrained_ei) changes the
+// kernel that follows the join -- lcei_kernel: cei / ei / pof receive lcei / lei / lpof -- and the phase record, nothing else.
 template <typename T>
 static int model_constrained_ei(hbegp_model* const* M, int K, const T* Xs, int cnt, const double* thr, const CeiJoin& join, double* cei,
-                                T* grad, int* best, double* ei, double* pof, T* mean_out, T* var_out) {
+                                T* grad, int* best, double* ei, double* pof, T* mean_out, T* var_out, bool log_space = false) {
+  const PhaseKind kind = log_space ? PH_LCEI : PH_CEI;
   const bool want_grad = grad != nullptr;
   const int d = M[0]->d;
   // everything the call takes, counted before anything is taken: an m far beyond the device is ENOMEM, not an overflow
@@ -2841,7 +2844,7 @@ static int model_constrained_ei(hbegp_model* const* M, int K, const T* Xs, int c
   double* dval = static_cast<double*>(ws.get(sizeof(double) * 3 * (size_t)cnt));  // cei | ei | pof
   int* dbest = static_cast<int*>(ws.get(sizeof(int)));
   T* dg = want_grad ? static_cast<T*>(ws.get(sizeof(T) * (size_t)cnt * d)) : nullptr;
-  PhaseClock clk(t_phase[PH_CEI].on, 3);  // all on the objective's stream: before its upload, behind the join, behind the arg-max
+  PhaseClock clk(t_phase[kind].on, 3);  // all on the objective's stream: before its upload, behind the join, behind the arg-max
   clk.mark(s0);
   for (int k = 0; k < K; ++k) {
     hbegp_model* m = M[k];
@@ -2863,7 +2866,8 @@ static int model_constrained_ei(hbegp_model* const* M, int K, const T* Xs, int c
     a.dvar[k] = want_grad ? static_cast<const T*>(M[k]->dvar) : nullptr;
     a.thr[k] = thr[k];
   }
-  launch_cei<T>(a, cnt, d, want_grad ? 1 : 0, dval, dval + cnt, dval + 2 * (size_t)cnt, dg, dbest, s0);
+  if (log_space) launch_lcei<T>(a, cnt, d, want_grad ? 1 : 0, dval, dval + cnt, dval + 2 * (size_t)cnt, dg, dbest, s0);
+  else launch_cei<T>(a, cnt, d, want_grad ? 1 : 0, dval, dval + cnt, dval + 2 * (size_t)cnt, dg, dbest, s0);
   clk.mark(s0);
   CHECK_LAUNCHES();
   int hbest = -1;
@@ -2890,21 +2894,22 @@ static int model_constrained_ei(hbegp_model* const* M, int K, const T* Xs, int c
       if (mean_out) mean_out[(size_t)K * i + k] = hm[(size_t)k * cnt + i];
       if (var_out) var_out[(size_t)K * i + k] = hv[(size_t)k * cnt + i];
     }
-  clk.store(PH_CEI, 2);
+  clk.store(kind, 2);
   return HBEGP_OK;
 }
 
 // S bounded L-BFGS runs on -cEI in lockstep (lockstep.hpp), as model_maximize_ehvi: every round is ONE model_constrained_ei with a
 // gradient (one batched gradient predict per model, then the cEI kernel).  Each run returns the best point it evaluated; a value or
-// a gradient component that is not finite is a failed evaluation.
+// a gradient component that is not finite is a failed evaluation (in log space a row at -inf is one).
 template <typename T>
 static int model_maximize_constrained_ei(hbegp_model* const* M, int K, const T* starts, int S, const double* lo, const double* hi,
-                                         const double* thr, int maxeval, T* x_out, double* cei_out, int* nevals_out) {
+                                         const double* thr, int maxeval, T* x_out, double* cei_out, int* nevals_out,
+                                         bool log_space = false) {
   const int d = M[0]->d;
   CeiJoin join(M[0]->dev, K - 1);
   std::vector<T> gr((size_t)S * d);
   auto eval = [&](const T* xs, const int*, int cnt, double* val, double* grad, char* ok) {
-    const int rc = model_constrained_ei<T>(M, K, xs, cnt, thr, join, val, gr.data(), nullptr, nullptr, nullptr, nullptr, nullptr);
+    const int rc = model_constrained_ei<T>(M, K, xs, cnt, thr, join, val, gr.data(), nullptr, nullptr, nullptr, nullptr, nullptr, log_space);
     if (rc != HBEGP_OK) return rc;
     for (int i = 0; i < cnt; ++i) {
       ok[i] = std::isfinite(val[i]);
@@ -4645,29 +4650,31 @@ static int check_cei_models(hbegp_model* objective, hbegp_model* const* constrai
 }
 template <typename T>
 static int do_cei(hbegp_model* objective, hbegp_model* const* constraints, int n_con, const T* Xs, int m, double fmin, const double* limits,
-                  double* cei, T* grad, int* best, double* ei, double* pof, T* mean, T* var) {
+                  double* cei, T* grad, int* best, double* ei, double* pof, T* mean, T* var, bool log_space = false) {
   if (m < 0) return fail(HBEGP_EINVAL, "m must be >= 0 (got %d)", m);
   GUARD_BEGIN
   std::vector<hbegp_model*> M;
   std::vector<double> thr;
   if (int rc = check_cei_models<T>(objective, constraints, n_con, fmin, limits, &M, &thr)) return rc;
-  if (m > 0 && (!Xs || !cei)) return fail(HBEGP_EINVAL, "Xs/cei is NULL");
+  if (m > 0 && (!Xs || !cei)) return fail(HBEGP_EINVAL, log_space ? "Xs/lcei is NULL" : "Xs/cei is NULL");
   if (best) *best = -1;
   if (m == 0) return HBEGP_OK;
   CeiJoin join(objective->dev, n_con);
-  return model_constrained_ei<T>(M.data(), 1 + n_con, Xs, m, thr.data(), join, cei, grad, best, ei, pof, mean, var);
+  return model_constrained_ei<T>(M.data(), 1 + n_con, Xs, m, thr.data(), join, cei, grad, best, ei, pof, mean, var, log_space);
   GUARD_END
 }
 template <typename T>
 static int do_maximize_cei(hbegp_model* objective, hbegp_model* const* constraints, int n_con, const T* starts, int S, const double* lo,
-                           const double* hi, double fmin, const double* limits, int maxeval, T* x_out, double* cei_out, int* nevals_out) {
+                           const double* hi, double fmin, const double* limits, int maxeval, T* x_out, double* cei_out, int* nevals_out,
+                           bool log_space = false) {
   if (S < 1) return fail(HBEGP_EINVAL, "S must be >= 1 (got %d)", S);
   GUARD_BEGIN
   std::vector<hbegp_model*> M;
   std::vector<double> thr;
   if (int rc = check_cei_models<T>(objective, constraints, n_con, fmin, limits, &M, &thr)) return rc;
   if (int rc = check_maximize_ei<T>(objective, starts, S, lo, hi, 0.0, maxeval, x_out, cei_out)) return rc;
-  return model_maximize_constrained_ei<T>(M.data(), 1 + n_con, starts, S, lo, hi, thr.data(), maxeval, x_out, cei_out, nevals_out);
+  return model_maximize_constrained_ei<T>(M.data(), 1 + n_con, starts, S, lo, hi, thr.data(), maxeval, x_out, cei_out, nevals_out,
+                                          log_space);
   GUARD_END
 }
 extern "C" {
@@ -4694,6 +4701,29 @@ int hbegp_maximize_constrained_ei_f32(hbegp_model* objective, hbegp_model* const
                                 nevals_out);
 }
 int hbegp_debug_cei_phases(int enable, double* phase_ms) { return debug_phases(PH_CEI, 2, enable, phase_ms); }
+int hbegp_log_constrained_ei_f64(hbegp_model* objective, hbegp_model* const* constraints, int n_con, const double* Xs, int m,
+                                 double fmin_normalized, const double* limits, double* lcei, double* grad, int* best, double* lei,
+                                 double* lpof, double* mean, double* var) {
+  return do_cei<double>(objective, constraints, n_con, Xs, m, fmin_normalized, limits, lcei, grad, best, lei, lpof, mean, var, true);
+}
+int hbegp_log_constrained_ei_f32(hbegp_model* objective, hbegp_model* const* constraints, int n_con, const float* Xs, int m,
+                                 double fmin_normalized, const double* limits, double* lcei, float* grad, int* best, double* lei,
+                                 double* lpof, float* mean, float* var) {
+  return do_cei<float>(objective, constraints, n_con, Xs, m, fmin_normalized, limits, lcei, grad, best, lei, lpof, mean, var, true);
+}
+int hbegp_maximize_log_constrained_ei_f64(hbegp_model* objective, hbegp_model* const* constraints, int n_con, const double* starts, int S,
+                                          const double* lo, const double* hi, double fmin_normalized, const double* limits, int maxeval,
+                                          double* x_out, double* lcei_out, int* nevals_out) {
+  return do_maximize_cei<double>(objective, constraints, n_con, starts, S, lo, hi, fmin_normalized, limits, maxeval, x_out, lcei_out,
+                                 nevals_out, true);
+}
+int hbegp_maximize_log_constrained_ei_f32(hbegp_model* objective, hbegp_model* const* constraints, int n_con, const float* starts, int S,
+                                          const double* lo, const double* hi, double fmin_normalized, const double* limits, int maxeval,
+                                          float* x_out, double* lcei_out, int* nevals_out) {
+  return do_maximize_cei<float>(objective, constraints, n_con, starts, S, lo, hi, fmin_normalized, limits, maxeval, x_out, lcei_out,
+                                nevals_out, true);
+}
+int hbegp_debug_lcei_phases(int enable, double* phase_ms) { return debug_phases(PH_LCEI, 2, enable, phase_ms); }
 }  // extern "C"
 
 // argument checks of hbegp_sobol_* / hbegp_main_effects_*: everything is refused before any device call, the checks that need no

@@ -4711,6 +4711,152 @@ void launch_cei(const CeiArgs<T>& a, int m, int d, int want_grad, double* cei, d
 template void launch_cei<double>(const CeiArgs<double>&, int, int, int, double*, double*, double*, double*, int*, hipStream_t);
 template void launch_cei<float>(const CeiArgs<float>&, int, int, int, double*, double*, double*, float*, int*, hipStream_t);
 
+// =================================================================================================================
+// log-space constrained expected improvement (hbegp.cpp: model_constrained_ei with log_space):
+//   lcei = lei + lpof,   lei = log sigma_0 + log h(z_0) (0 for fmin = +inf),   lpof = sum_{k=1..C} log Phi(z_k)   (ascending k).
+// cei_kernel's shape: one WAVE per candidate, lane k < K evaluates lcei_term for model k once -- its log-term and the term's
+// partials w.r.t. mu_k and sigma_k, which ARE lcei's (the log of a product is a sum: no prefix or suffix products) -- the K terms
+// are read from the lanes that hold them and added in ascending k, then the lanes stride over the features as cei_kernel does.
+// All of it in fp64 for both element types, with or without a gradient, no LDS and no atomics.
+//
+// lcei_term works through the Mills ratio for z = -a <= -1: u = Phi(-a) / phi(a) = sqrt(pi/2) erfcx(a / sqrt 2) and
+// b = h(-a) / phi(a) = 1 - a u, so that
+//   log h = -a^2/2 - log sqrt(2 pi) + log b,   log Phi = -a^2/2 - log sqrt(2 pi) + log u,   Phi/h = u/b,  phi/h = 1/b,  phi/Phi = 1/u
+// and nothing that underflows is ever formed.  1 - a u cancels about a^2 eps; from a = LCEI_SERIES_A on both come from the
+// asymptotic series in x = 1/a^2 (ten terms: the first omitted one is below 2e-18 at a = 25)
+//   a u = 1 - x + 3 x^2 - 15 x^3 + ..,     b = x (1 - 3 x + 15 x^2 - 105 x^3 + ..).
+// Above z = -1 the direct forms hold: h = phi(a) - a Phi(-a) for z = -a <= 0 and z + h(-z) above, log Phi = log(Phi(z)) up to
+// z = 0 and log1p(-Phi(-z)) above.  z is clamped to +-1.7e308 (an overflowing quotient stays a number).
+// =================================================================================================================
+constexpr double LCEI_SERIES_A = 25.0;
+
+struct LceiTerm {
+  double v, pm, ps;  // the log-term and its partials w.r.t. mu and sigma
+};
+// not inlined: erfcx's, log's and exp's fp64 coefficients, once per lane
+__device__ __noinline__ LceiTerm lcei_term(double t, double mu, double sd, int objective) {
+  const double inf = __longlong_as_double(0x7ff0000000000000LL);
+  LceiTerm r = {0.0, 0.0, 0.0};
+  if (objective && !(t < inf)) return r;  // fmin = +inf: the objective drops out
+  if (!(sd > 2.220446049250313e-16)) {    // sigma = 0
+    if (objective) {
+      const double gap = t - mu;
+      r.v = log(fmax(gap, 0.0));
+      r.pm = gap > 0.0 ? -1.0 / gap : 0.0;
+    } else {
+      r.v = t > mu ? 0.0 : -inf;
+    }
+    return r;
+  }
+  const double z = fmin(fmax((t - mu) / sd, -1.7e308), 1.7e308);
+  double lf, rr, qq;  // log h or log Phi;  Phi/h or phi/Phi;  phi/h or z phi/Phi
+  if (z > -1.0) {
+    const double az = fabs(z);
+    const double cl = 0.5 * erfc(az / 1.4142135623730951);            // Phi(-|z|)
+    const double pdf = exp(-0.5 * az * az) / 2.5066282746310002;      // phi(z)
+    const double cdf = z > 0.0 ? 1.0 - cl : cl;
+    if (objective) {
+      const double tail = pdf - az * cl;                               // h(-|z|) > 0: |z| < 1 below 0, and z is added above
+      const double h = z > 0.0 ? z + tail : tail;
+      lf = log(h);
+      rr = cdf / h;
+      qq = pdf / h;
+    } else {
+      lf = z > 0.0 ? log1p(-cl) : log(cl);
+      rr = pdf / cdf;
+      qq = pdf > 0.0 ? z * rr : 0.0;                                   // (z = 1.7e308 times an underflowed phi is 0)
+    }
+  } else {
+    const double a = -z;
+    double au, bx;  // a u and b / x; below the switch point b itself sits in bx with x = 1
+    double x = 1.0;
+    if (a < LCEI_SERIES_A) {
+      au = a * (1.2533141373155003 * erfcx(a / 1.4142135623730951));
+      bx = 1.0 - au;
+    } else {
+      x = 1.0 / a / a;  // (a * a may overflow where 1 / a / a only underflows)
+      au = 1.0 + x * (-1.0 + x * (3.0 + x * (-15.0 + x * (105.0 + x * (-945.0 + x * (10395.0 + x * (-135135.0 + x * (2027025.0 + x * -34459425.0))))))));
+      bx = 1.0 + x * (-3.0 + x * (15.0 + x * (-105.0 + x * (945.0 + x * (-10395.0 + x * (135135.0 + x * (-2027025.0 + x * (34459425.0 + x * -654729075.0))))))));
+    }
+    // u = au / a, b = x bx
+    const double base = -0.5 * a * a - 0.91893853320467274;
+    if (objective) {
+      lf = base + (log(bx) + log(x));
+      rr = a < LCEI_SERIES_A ? au / a / bx : a * (au / bx);  // u / b
+      qq = a < LCEI_SERIES_A ? 1.0 / bx : a * (a / bx);      // 1 / b
+    } else {
+      lf = base + (log(au) - log(a));
+      rr = a / au;           // 1 / u
+      qq = -a * rr;          // z / u
+    }
+  }
+  if (objective) {
+    r.v = log(sd) + lf;
+    r.pm = -rr / sd;
+    r.ps = qq / sd;
+  } else {
+    r.v = lf;
+    r.pm = -rr / sd;
+    r.ps = -qq / sd;
+  }
+  return r;
+}
+
+template <typename T>
+__global__ void __launch_bounds__(64 * CEI_WAVES) lcei_kernel(const CeiArgs<T> a, int m, int d, int want_grad, double* __restrict__ lcei,
+                                                              double* __restrict__ lei, double* __restrict__ lpof, T* __restrict__ grad) {
+  const int lane = threadIdx.x & 63;
+  const int j = blockIdx.x * CEI_WAVES + (threadIdx.x >> 6);
+  if (j >= m) return;  // whole waves leave: every lane of a wave that stays takes part in the shuffles
+  const int K = a.K;
+  double v = 0.0, cm = 0.0, cs = 0.0, sd = 0.0;  // model `lane`: its log-term, d lcei / d mu_lane, d lcei / d sigma_lane, sigma
+  bool bad = false;
+  if (lane < K) {
+    const double mu = (double)a.mean[lane][j], var = (double)a.var[lane][j];
+    sd = sqrt(var);
+    bad = (mu != mu) || (var != var);
+    const LceiTerm g = lcei_term(a.thr[lane], mu, sd, lane == 0);
+    v = g.v;
+    cm = g.pm;
+    cs = g.ps;
+  }
+  const bool anybad = __any(bad) != 0;
+  const double e = __shfl(v, 0, 64);
+  double all = 0.0;
+  for (int k = 1; k < K; ++k) all += __shfl(v, k, 64);
+  const double nan = __longlong_as_double(0x7ff8000000000000LL);
+  if (lane == 0) {
+    lcei[j] = anybad ? nan : e + all;
+    if (lei) lei[j] = anybad ? nan : e;
+    if (lpof) lpof[j] = anybad ? nan : all;
+  }
+  if (!want_grad) return;
+  for (int base = 0; base < d; base += 64) {  // a uniform trip count: every lane takes part in the shuffles
+    const int i = base + lane;
+    const bool on = i < d;
+    const size_t x = (size_t)j * d + (on ? i : 0);
+    double g = 0.0;
+    for (int k = 0; k < K; ++k) {
+      const double cmk = __shfl(cm, k, 64), csk = __shfl(cs, k, 64), sdk = __shfl(sd, k, 64);
+      if (on) {
+        const double ds = sdk > 2.220446049250313e-16 ? (double)a.dvar[k][x] / (2.0 * sdk) : 0.0;
+        g += cmk * (double)a.dmean[k][x] + csk * ds;
+      }
+    }
+    if (on) grad[x] = anybad ? (T)nan : (T)g;
+  }
+}
+
+template <typename T>
+void launch_lcei(const CeiArgs<T>& a, int m, int d, int want_grad, double* lcei, double* lei, double* lpof, T* grad, int* best,
+                 hipStream_t s) {
+  const dim3 grid((unsigned)((m + CEI_WAVES - 1) / CEI_WAVES)), block(64 * CEI_WAVES);
+  hipLaunchKernelGGL((lcei_kernel<T>), grid, block, 0, s, a, m, d, want_grad, lcei, lei, lpof, grad);
+  hipLaunchKernelGGL(ehvi_best_kernel, dim3(1), dim3(BSEL_THREADS), 0, s, lcei, m, best);
+}
+template void launch_lcei<double>(const CeiArgs<double>&, int, int, int, double*, double*, double*, double*, int*, hipStream_t);
+template void launch_lcei<float>(const CeiArgs<float>&, int, int, int, double*, double*, double*, float*, int*, hipStream_t);
+
 // Per-device one-time setup: kernels that use more than 64 KiB of dynamic LDS need the attribute raised.  Called from
 // hbegp_ctx_create() for every device, before any stream capture.
 static void init_dag_kernels();  // dag_kernel.inc.hpp (end of this file)

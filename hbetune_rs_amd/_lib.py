@@ -120,6 +120,14 @@ SIGNATURES = {
                                                     _dp, _ip]),
     "hbegp_maximize_constrained_ei_f32": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, _fp, C.c_int, _dp, _dp, C.c_double, _dp, C.c_int, _fp,
                                                     _dp, _ip]),
+    "hbegp_log_constrained_ei_f64": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, _dp, C.c_int, C.c_double, _dp, _dp, _dp, _ip, _dp, _dp,
+                                               _dp, _dp]),
+    "hbegp_log_constrained_ei_f32": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, _fp, C.c_int, C.c_double, _dp, _dp, _fp, _ip, _dp, _dp,
+                                               _fp, _fp]),
+    "hbegp_maximize_log_constrained_ei_f64": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, _dp, C.c_int, _dp, _dp, C.c_double, _dp, C.c_int,
+                                                        _dp, _dp, _ip]),
+    "hbegp_maximize_log_constrained_ei_f32": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, _fp, C.c_int, _dp, _dp, C.c_double, _dp, C.c_int,
+                                                        _fp, _dp, _ip]),
     "hbegp_sobol_f64": (C.c_int, [_vp, _dp, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "hbegp_sobol_f32": (C.c_int, [_vp, _fp, _fp, C.c_int, _dp, _dp, _dp, _dp, _fp, _fp, _fp]),
     "hbegp_main_effects_f64": (C.c_int, [_vp, _dp, C.c_int, _dp, C.c_int, _dp, _dp]),
@@ -155,6 +163,7 @@ SIGNATURES = {
     "hbegp_debug_sens_phases": (C.c_int, [C.c_int, _dp]),
     "hbegp_debug_ehvi_phases": (C.c_int, [C.c_int, _dp]),
     "hbegp_debug_cei_phases": (C.c_int, [C.c_int, _dp]),
+    "hbegp_debug_lcei_phases": (C.c_int, [C.c_int, _dp]),
     "hbegp_debug_pool_poisoned": (C.c_int, [C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "hbegp_model_info": (C.c_int, [_vp, _ip, _ip, _ip, _dp, _dp]),
     "hbegp_model_get_f64": (C.c_int, [_vp, _dp, _dp, _dp]),

@@ -288,6 +288,13 @@ class SurrogateModelGPR:
         hi = np.array([b[1] for b in bounds], dtype=np.float64)
         return self.fitted.maximize_ei(np.asarray(starts, dtype=self.dtype), lo, hi, self._fmin_normalized(fmin), maxeval=maxeval)
 
+    def maximize_log_ei(self, starts, bounds, fmin, maxeval=150):
+        """maximize_ei on log EI (FittedKernel.maximize_log_ei): the runs move where EI itself underflows to 0.  Opt-in.
+        Returns (x[S, d], log ei[S], nevals[S])."""
+        lo = np.array([b[0] for b in bounds], dtype=np.float64)
+        hi = np.array([b[1] for b in bounds], dtype=np.float64)
+        return self.fitted.maximize_log_ei(np.asarray(starts, dtype=self.dtype), lo, hi, self._fmin_normalized(fmin), maxeval=maxeval)
+
     # Joint posterior draws (opt-in; nothing the estimator suggests by default uses them).
     def sample_a(self, x, n_samples, rng, jitter=0.0):
         """n_samples joint draws of the surrogate at the rows of x [m, d], projected like predict_mean_a: [n_samples, m].
@@ -750,6 +757,21 @@ def maximize_constrained_ei(model, constraint_models, starts, bounds, fmin, limi
                                        fn, ln, maxeval=maxeval)
 
 
+def log_constrained_ei_a(model, constraint_models, x, fmin, limits):
+    """constrained_ei_a in log space (gpr.log_constrained_ei): finite, with a usable ranking, where constrained_ei_a is exactly 0.
+    fmin and limits in y units.  Returns (lcei[m] float64, best)."""
+    fn, ln = _cei_normalized(model, constraint_models, fmin, limits)
+    return gpr.log_constrained_ei(model.fitted, [mo.fitted for mo in constraint_models], np.asarray(x, dtype=model.dtype), fn, ln)
+
+
+def maximize_log_constrained_ei(model, constraint_models, starts, bounds, fmin, limits, maxeval=150):
+    """maximize_constrained_ei on log_constrained_ei_a (gpr.maximize_log_constrained_ei): the runs move where every start has a
+    constrained EI of exactly 0.  fmin and limits in y units.  Returns (x[S, d], lcei[S], nevals[S])."""
+    fn, ln = _cei_normalized(model, constraint_models, fmin, limits)
+    return gpr.maximize_log_constrained_ei(model.fitted, [mo.fitted for mo in constraint_models], np.asarray(starts, dtype=model.dtype),
+                                           bounds, fn, ln, maxeval=maxeval)
+
+
 def _cei_default_fmin(models, limits):
     """feasible_fmin of the models' training targets in y units; the models must have been trained on the very same rows."""
     fks = [mo.fitted for mo in models]
@@ -762,15 +784,9 @@ def _cei_default_fmin(models, limits):
     return feasible_fmin(y[0], np.stack(y[1:], axis=1) if len(y) > 1 else np.zeros((len(y[0]), 0)), limits)
 
 
-def acquire_by_constrained_ei(candidates, model, constraint_models, k, limits, fmin=None, ctx=None):
-    """Batch acquisition under constraints by constrained EI over a candidate set [m, n_features]: k distinct rows, each the row of
-    largest cEI (gpr.constrained_ei: closed form, no random numbers).  After a pick EVERY surrogate is conditioned on the
-    kriging-believer fantasy (x_pick, that model's posterior mean) through extend_with at the same theta, as acquire_by_ehvi does;
-    when the believed constraint values all hold and the believed objective lies below fmin, fmin falls to it.  limits and fmin are
-    in y units.  Without fmin: feasible_fmin of the models' training targets, which needs models trained on the very same rows (else
-    ValueError); it is math.inf while no feasible row is known.  Returns (idx[k] int64, the projected means [k, 1 + C] of the picks
-    at the time they were picked, cei[k], and the fmin in force after each pick, in the objective's normalised units).  Opt-in:
-    nothing the estimator suggests by default calls it."""
+def _acquire_by_cei(evaluate, candidates, model, constraint_models, k, limits, fmin, ctx):
+    """The greedy loop behind acquire_by_constrained_ei (evaluate = gpr.constrained_ei) and acquire_by_log_constrained_ei
+    (gpr.log_constrained_ei)."""
     models = [model] + list(constraint_models)
     K = len(models)
     dtype = model.dtype
@@ -791,7 +807,7 @@ def acquire_by_constrained_ei(candidates, model, constraint_models, k, limits, f
     idx, means, vals, fmins = [], [], [], []
     try:
         for t in range(k):
-            val, best, _, _, mean, _ = gpr.constrained_ei(fks[0], fks[1:], c[avail], fn, ln, want_details=True)
+            val, best, _, _, mean, _ = evaluate(fks[0], fks[1:], c[avail], fn, ln, want_details=True)
             idx.append(avail.pop(best))
             means.append(mean[best])
             vals.append(val[best])
@@ -814,6 +830,26 @@ def acquire_by_constrained_ei(candidates, model, constraint_models, k, limits, f
     means = np.array(means, dtype=dtype).reshape(-1, K)
     proj = np.stack([models[o].y_norm.project_location_from_normalized(means[:, o]) for o in range(K)], axis=1)
     return np.array(idx, dtype=np.int64), proj, np.array(vals, dtype=np.float64), np.array(fmins, dtype=np.float64)
+
+
+def acquire_by_constrained_ei(candidates, model, constraint_models, k, limits, fmin=None, ctx=None):
+    """Batch acquisition under constraints by constrained EI over a candidate set [m, n_features]: k distinct rows, each the row of
+    largest cEI (gpr.constrained_ei: closed form, no random numbers).  After a pick EVERY surrogate is conditioned on the
+    kriging-believer fantasy (x_pick, that model's posterior mean) through extend_with at the same theta, as acquire_by_ehvi does;
+    when the believed constraint values all hold and the believed objective lies below fmin, fmin falls to it.  limits and fmin are
+    in y units.  Without fmin: feasible_fmin of the models' training targets, which needs models trained on the very same rows (else
+    ValueError); it is math.inf while no feasible row is known.  Returns (idx[k] int64, the projected means [k, 1 + C] of the picks
+    at the time they were picked, cei[k], and the fmin in force after each pick, in the objective's normalised units).  Opt-in:
+    nothing the estimator suggests by default calls it."""
+    return _acquire_by_cei(gpr.constrained_ei, candidates, model, constraint_models, k, limits, fmin, ctx)
+
+
+def acquire_by_log_constrained_ei(candidates, model, constraint_models, k, limits, fmin=None, ctx=None):
+    """acquire_by_constrained_ei ranking by the log-space value (gpr.log_constrained_ei): the same greedy loop, fantasies and fmin
+    rule, but a pick is the row of largest lcei, which still orders the rows where every cEI underflows to 0 (there
+    acquire_by_constrained_ei falls back to the last row).  Returns (idx[k], the projected means [k, 1 + C], lcei[k], fmin after
+    each pick).  Opt-in."""
+    return _acquire_by_cei(gpr.log_constrained_ei, candidates, model, constraint_models, k, limits, fmin, ctx)
 
 
 def _nei_baseline(fk, baseline, max_baseline, dtype):

@@ -383,6 +383,16 @@ class FittedKernel:
                       _lib.dptr(ei), nevals.ctypes.data_as(C.POINTER(C.c_int))))
         return x, ei, nevals
 
+    def log_ei(self, x, fmin_normalized, want_grad=False):
+        """log EI below fmin_normalized at the rows of x (log_constrained_ei without constraints): (lei[m] float64, best), then
+        grad[m, d] with want_grad.  Finite where EI itself underflows."""
+        return log_constrained_ei(self, [], x, fmin_normalized, None, want_grad=want_grad)
+
+    def maximize_log_ei(self, starts, lo, hi, fmin_normalized, maxeval=150):
+        """maximize_ei's runs on log EI (maximize_log_constrained_ei without constraints).  Returns (x[S, d], lei[S], nevals[S])."""
+        bounds = np.stack([np.asarray(lo, dtype=np.float64).reshape(-1), np.asarray(hi, dtype=np.float64).reshape(-1)], axis=1)
+        return maximize_log_constrained_ei(self, [], starts, bounds, fmin_normalized, None, maxeval=maxeval)
+
     def predict_cov(self, x, jitter=0.0):
         """Joint posterior at the query points (hbegp_predict_cov_*): returns (mean[m], cov[m, m]) in the normalised y space,
         cov = K** + (1e-5 + jitter) I - K*^T K^-1 K* (unclamped; its diagonal is predict()'s variance before clamping)."""
@@ -741,14 +751,8 @@ def _cei_args(objective, constraints, limits):
     return constraints, handles, limits
 
 
-def constrained_ei(objective, constraints, x, fmin_normalized, limits, want_grad=False, want_details=False):
-    """Constrained expected improvement (hbegp_constrained_ei_*), in the models' normalised y spaces: the EI of the minimised
-    `objective` below fmin_normalized times the probability that every constraints[k] stays at or below limits[k].  objective and
-    constraints are FittedKernels of the same d, element type and device, taken as independent; at most CEI_MAX_CONSTRAINTS
-    constraints.  fmin_normalized = math.inf: no feasible point is known, EI counts as 1 and cei is the probability of
-    feasibility.  Returns (cei[m] float64, best) -- best the last index of the maximum, -1 for m = 0 -- then grad[m, d] with
-    want_grad, then (ei[m], pof[m], mean[m, 1 + C], var[m, 1 + C]) with want_details: the objective first, predict()'s numbers
-    bit for bit."""
+def _constrained_ei(symbol, objective, constraints, x, fmin_normalized, limits, want_grad, want_details):
+    """The call behind constrained_ei and log_constrained_ei: `symbol` without its element-type suffix."""
     constraints, handles, limits = _cei_args(objective, constraints, limits)
     dtype, d, K = objective.dtype, objective.d, 1 + len(constraints)
     x = _lib.as_c(np.asarray(x, dtype=dtype).reshape(-1, d), dtype)
@@ -760,7 +764,7 @@ def constrained_ei(objective, constraints, x, fmin_normalized, limits, want_grad
     pof = np.zeros(m) if want_details else None
     mean = np.zeros((m, K), dtype=dtype) if want_details else None
     var = np.zeros((m, K), dtype=dtype) if want_details else None
-    fn = getattr(_lib.load(), f"hbegp_constrained_ei_{objective._sfx}")
+    fn = getattr(_lib.load(), f"{symbol}_{objective._sfx}")
     _lib.check(fn(objective._h, handles, len(constraints), _lib.aptr(x), m, float(fmin_normalized), _lib.dptr(limits), _lib.dptr(val),
                   _lib.aptr(grad), C.byref(best), _lib.dptr(ei), _lib.dptr(pof), _lib.aptr(mean), _lib.aptr(var)))
     out = (val, best.value)
@@ -771,11 +775,28 @@ def constrained_ei(objective, constraints, x, fmin_normalized, limits, want_grad
     return out
 
 
-def maximize_constrained_ei(objective, constraints, starts, bounds, fmin_normalized, limits, maxeval=150):
-    """S bounded L-BFGS runs maximising constrained_ei() over the box (hbegp_maximize_constrained_ei_*), one batched gradient
-    predict per model and round.  starts: [S, d] inside the box; bounds: d pairs (lo, hi).  Returns (x[S, d], cei[S], nevals[S]):
-    each run's best point, never worse than its start; constrained_ei(objective, constraints, x, ...) reproduces the values bit
-    for bit."""
+def constrained_ei(objective, constraints, x, fmin_normalized, limits, want_grad=False, want_details=False):
+    """Constrained expected improvement (hbegp_constrained_ei_*), in the models' normalised y spaces: the EI of the minimised
+    `objective` below fmin_normalized times the probability that every constraints[k] stays at or below limits[k].  objective and
+    constraints are FittedKernels of the same d, element type and device, taken as independent; at most CEI_MAX_CONSTRAINTS
+    constraints.  fmin_normalized = math.inf: no feasible point is known, EI counts as 1 and cei is the probability of
+    feasibility.  Returns (cei[m] float64, best) -- best the last index of the maximum, -1 for m = 0 -- then grad[m, d] with
+    want_grad, then (ei[m], pof[m], mean[m, 1 + C], var[m, 1 + C]) with want_details: the objective first, predict()'s numbers
+    bit for bit."""
+    return _constrained_ei("hbegp_constrained_ei", objective, constraints, x, fmin_normalized, limits, want_grad, want_details)
+
+
+def log_constrained_ei(objective, constraints, x, fmin_normalized, limits, want_grad=False, want_details=False):
+    """The logarithm of constrained_ei by stable forms (hbegp_log_constrained_ei_*): lcei = lei + lpof with lei = log EI (0 for
+    fmin_normalized = math.inf) and lpof the sum of the log feasibility probabilities.  Value and gradient stay finite and
+    informative where constrained_ei underflows to exactly 0 (|z| beyond 38); a sigma = 0 row on the wrong side is -inf.
+    Arguments and returns as constrained_ei: (lcei[m] float64, best), then grad[m, d] -- the gradient of lcei -- with want_grad,
+    then (lei[m], lpof[m], mean[m, 1 + C], var[m, 1 + C]) with want_details.  Without constraints it is log EI."""
+    return _constrained_ei("hbegp_log_constrained_ei", objective, constraints, x, fmin_normalized, limits, want_grad, want_details)
+
+
+def _maximize_constrained_ei(symbol, objective, constraints, starts, bounds, fmin_normalized, limits, maxeval):
+    """The call behind maximize_constrained_ei and maximize_log_constrained_ei: `symbol` without its element-type suffix."""
     constraints, handles, limits = _cei_args(objective, constraints, limits)
     dtype, d = objective.dtype, objective.d
     starts = _lib.as_c(np.atleast_2d(starts), dtype)
@@ -787,10 +808,27 @@ def maximize_constrained_ei(objective, constraints, starts, bounds, fmin_normali
     x = np.zeros((S, d), dtype=dtype)
     val = np.zeros(S)
     nevals = np.zeros(S, dtype=np.int32)
-    fn = getattr(_lib.load(), f"hbegp_maximize_constrained_ei_{objective._sfx}")
+    fn = getattr(_lib.load(), f"{symbol}_{objective._sfx}")
     _lib.check(fn(objective._h, handles, len(constraints), _lib.aptr(starts), S, _lib.dptr(lo), _lib.dptr(hi), float(fmin_normalized),
                   _lib.dptr(limits), int(maxeval), _lib.aptr(x), _lib.dptr(val), nevals.ctypes.data_as(C.POINTER(C.c_int))))
     return x, val, nevals
+
+
+def maximize_constrained_ei(objective, constraints, starts, bounds, fmin_normalized, limits, maxeval=150):
+    """S bounded L-BFGS runs maximising constrained_ei() over the box (hbegp_maximize_constrained_ei_*), one batched gradient
+    predict per model and round.  starts: [S, d] inside the box; bounds: d pairs (lo, hi).  Returns (x[S, d], cei[S], nevals[S]):
+    each run's best point, never worse than its start; constrained_ei(objective, constraints, x, ...) reproduces the values bit
+    for bit."""
+    return _maximize_constrained_ei("hbegp_maximize_constrained_ei", objective, constraints, starts, bounds, fmin_normalized, limits,
+                                    maxeval)
+
+
+def maximize_log_constrained_ei(objective, constraints, starts, bounds, fmin_normalized, limits, maxeval=150):
+    """maximize_constrained_ei on log_constrained_ei (hbegp_maximize_log_constrained_ei_*): the runs move where every start has
+    cei = 0 in plain space.  Returns (x[S, d], lcei[S], nevals[S]); log_constrained_ei at x reproduces the values bit for bit.
+    A row at -inf counts as a failed evaluation."""
+    return _maximize_constrained_ei("hbegp_maximize_log_constrained_ei", objective, constraints, starts, bounds, fmin_normalized,
+                                    limits, maxeval)
 
 
 def minimize_by_gradient(objective, x0, bounds, maxeval=150):

@@ -444,8 +444,9 @@ int hbegp_maximize_ehvi_f32(hbegp_model* const* models, int n_obj, const float* 
  *   grad[j][i] = sum_{k=0..C} (d cei / d mu_k * dmean_k[j][i] + d cei / d sigma_k * dvar_k[j][i] / (2 sigma_k)),  ascending k,
  * dmean and dvar being hbegp_predict_grad_*'s.  All arithmetic is fp64 for both element types, in a fixed order without atomics:
  * cei, ei and pof are double, and a row's bits depend only on its own posteriors, fmin and limits -- not on m, on the row's
- * position, or on whether a gradient was asked for.  There is no log-space form: a product that falls below the normal range
- * (about 1e-308) loses its digits to gradual underflow and ends as exactly 0, with a zero gradient.
+ * position, or on whether a gradient was asked for.  A product that falls below the normal range (about 1e-308)
+ * loses its digits to gradual underflow and ends as exactly 0, with a zero gradient: where that matters -- a maximiser started where
+ * every start has pof = 0 does not move -- use the log-space form hbegp_log_constrained_ei_* below.
  * cei[m] (required for m > 0); best (may be NULL): the LAST index of the maximum of cei (a NaN never wins; -1 for m = 0); ei[m],
  * pof[m] (each may be NULL); mean[m*(1+C)], var[m*(1+C)] (each may be NULL): row j holds the objective then the constraints, bit
  * for bit what hbegp_predict_* returns on its batched path (m > 16), or hbegp_predict_grad_* with a gradient.  A NaN coordinate
@@ -476,6 +477,52 @@ int hbegp_maximize_constrained_ei_f64(hbegp_model* objective, hbegp_model* const
 int hbegp_maximize_constrained_ei_f32(hbegp_model* objective, hbegp_model* const* constraints, int n_con, const float* starts, int S,
                                       const double* lo, const double* hi, double fmin_normalized, const double* limits, int maxeval,
                                       float* x_out, double* cei_out, int* nevals_out);
+
+/* Constrained expected improvement in log space (log EI: Ament et al. 2023): the logarithm of hbegp_constrained_ei_*'s cei, formed
+ * so that the value and the gradient stay finite and informative where cei itself underflows to 0.  The models, the normalised
+ * spaces, fmin_normalized, limits, HBEGP_CEI_MAX_CONSTRAINTS, "sigma = 0", the refusals, the locking order and the per-model streams
+ * are exactly those of hbegp_constrained_ei_*.  With z_0 = (fmin - mu_0) / sigma_0, z_k = (t_k - mu_k) / sigma_k and
+ * h(z) = z Phi(z) + phi(z):
+ *   lei  = log sigma_0 + log h(z_0)      -- 0 with zero partials for fmin = +inf
+ *   lF_k = log Phi(z_k)
+ *   lpof = lF_1 + .. + lF_C              -- added in ascending k; 0.0 for n_con = 0
+ *   lcei = lei + lpof.
+ * The log of a product is a sum, so every partial of lcei is the partial of one term and none divides plain-space quantities that
+ * can underflow:
+ *   d lei / d mu_0 = -r(z_0) / sigma_0,   d lei / d sigma_0 = q(z_0) / sigma_0,              r = Phi / h,  q = phi / h
+ *   d lF_k / d mu_k = -lambda(z_k) / sigma_k,   d lF_k / d sigma_k = -z_k lambda(z_k) / sigma_k,   lambda = phi / Phi
+ *   grad[j][i] = sum_{k=0..C} (d lcei / d mu_k * dmean_k[j][i] + d lcei / d sigma_k * dvar_k[j][i] / (2 sigma_k)),  ascending k.
+ * Evaluation, fp64 for both element types: for z > -1 the direct forms (h = phi(a) - a Phi(-a) for z = -a <= 0, z + h(-z) above;
+ * log Phi = log1p(-Phi(-z)) for z > 0); for z = -a <= -1 through the Mills ratio u = sqrt(pi/2) erfcx(a / sqrt 2) = Phi(-a) / phi(a)
+ * and b = 1 - a u = h / phi:  log h = -a^2/2 - log sqrt(2 pi) + log b,  log Phi = -a^2/2 - log sqrt(2 pi) + log u,  r = u / b,
+ * q = 1 / b,  lambda = 1 / u;  from a = 25 on, a u and b come from ten terms of their asymptotic series in 1 / a^2 (below, 1 - a u
+ * loses about a^2 eps to cancellation: r and q are good to about 2e-13 just below 25, to a few eps elsewhere).  z is clamped to
+ * +-1.7e308.  Every value is finite for |z| <= 1e150 (about -z^2/2 on the far side); beyond, a^2 overflows and the term is -inf, or
+ * stays finite for z > 0 -- never NaN.  The partials grow like |z| / sigma and z^2 / sigma and are finite while those are.
+ * sigma_0 = 0: lei = log((fmin - mu_0)^+), -inf for fmin <= mu_0; d / d mu_0 = -1 / (fmin - mu_0) where that is positive, else 0;
+ * d / d sigma_0 = 0.  sigma_k = 0: lF_k = 0 if t_k > mu_k, else -inf; both partials 0.  A -inf term makes lcei = -inf; the
+ * gradient row is still the sum of the partials above.  A row's bits depend only on its own posteriors, fmin and limits -- not on
+ * m, on the row's position, or on whether a gradient was asked for.
+ * lcei[m] (required for m > 0); best (may be NULL): the LAST index of the maximum of lcei (a NaN never wins, -inf wins only where
+ * no row is finite; -1 for m = 0); lei[m], lpof[m], grad[m*d], mean[m*(1+C)], var[m*(1+C)] (each may be NULL) as in
+ * hbegp_constrained_ei_*: mean and var are the same bits.  A NaN coordinate gives NaN in that row of lcei, lei, lpof and grad
+ * only.  n_con = 0 is log EI.  HBEGP_EINVAL and HBEGP_ENOMEM as for hbegp_constrained_ei_*. */
+int hbegp_log_constrained_ei_f64(hbegp_model* objective, hbegp_model* const* constraints, int n_con, const double* Xs, int m,
+                                 double fmin_normalized, const double* limits, double* lcei, double* grad, int* best, double* lei,
+                                 double* lpof, double* mean, double* var);
+int hbegp_log_constrained_ei_f32(hbegp_model* objective, hbegp_model* const* constraints, int n_con, const float* Xs, int m,
+                                 double fmin_normalized, const double* limits, double* lcei, float* grad, int* best, double* lei,
+                                 double* lpof, float* mean, float* var);
+/* hbegp_maximize_constrained_ei_*'s S lockstep L-BFGS runs on lcei instead of cei, with the same contract: x_out[S*d], lcei_out[S]
+ * each run's best evaluated point (never worse than its start) -- hbegp_log_constrained_ei_* at x_out reproduces lcei_out bit for
+ * bit; nevals_out[S] (may be NULL) <= maxeval.  A value or a gradient component that is not finite is a failed evaluation, so a
+ * row at -inf is one.  With n_con = 0 it maximises log EI.  Refusals as for hbegp_maximize_constrained_ei_*. */
+int hbegp_maximize_log_constrained_ei_f64(hbegp_model* objective, hbegp_model* const* constraints, int n_con, const double* starts,
+                                          int S, const double* lo, const double* hi, double fmin_normalized, const double* limits,
+                                          int maxeval, double* x_out, double* lcei_out, int* nevals_out);
+int hbegp_maximize_log_constrained_ei_f32(hbegp_model* objective, hbegp_model* const* constraints, int n_con, const float* starts,
+                                          int S, const double* lo, const double* hi, double fmin_normalized, const double* limits,
+                                          int maxeval, float* x_out, double* lcei_out, int* nevals_out);
 
 /* Sensitivity of the posterior mean mu (hbegp_predict_*'s mean, normalised y space) to each feature, from the CALLER's sample
  * matrices in the feature coordinates the model was fitted on (the RNG stays on the caller side).  Both calls evaluate the mean at
@@ -665,6 +712,10 @@ int hbegp_debug_ehvi_phases(int enable, double* phase_ms);
  * last timed hbegp_constrained_ei_* call -- the 1 + C predicts (from the objective's upload to the join of the streams: they
  * overlap), the cEI kernel with the arg-max -- in milliseconds; then enable != 0 makes this thread's later cEI calls timed. */
 int hbegp_debug_cei_phases(int enable, double* phase_ms);
+/* ---- timing hook (tools/lcei_bench.py): phase_ms[2] (may be NULL) receives the device time of the phases of the calling thread's
+ * last timed hbegp_log_constrained_ei_* call -- the 1 + C predicts as above, the log-space kernel with the arg-max -- in
+ * milliseconds; then enable != 0 makes this thread's later log-cEI calls timed.  A record of its own: cEI's is not touched. */
+int hbegp_debug_lcei_phases(int enable, double* phase_ms);
 /* ---- timing hook (tools/sens_bench.py): phase_ms[4] (may be NULL) receives the device time of the phases of the calling thread's
  * last timed hbegp_sobol_* / hbegp_main_effects_* call -- the upload (with the grid's scaling), the substituted means, the chunk and
  * row sums (both summed over the slabs), the final reduction with the downloads -- in milliseconds; then enable != 0 makes this

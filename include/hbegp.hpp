@@ -102,6 +102,14 @@ template <> struct Abi<double> {
                                      double fmin, const double* lim, int maxeval, double* x, double* v, int* ne) {
     return hbegp_maximize_constrained_ei_f64(o, cs, nc, st, s, lo, hi, fmin, lim, maxeval, x, v, ne);
   }
+  static int log_constrained_ei(hbegp_model* o, hbegp_model* const* cs, int nc, const double* xs, int m, double fmin, const double* lim, double* v,
+                                double* g, int* best, double* lei, double* lpof, double* mean, double* var) {
+    return hbegp_log_constrained_ei_f64(o, cs, nc, xs, m, fmin, lim, v, g, best, lei, lpof, mean, var);
+  }
+  static int maximize_log_constrained_ei(hbegp_model* o, hbegp_model* const* cs, int nc, const double* st, int s, const double* lo, const double* hi,
+                                         double fmin, const double* lim, int maxeval, double* x, double* v, int* ne) {
+    return hbegp_maximize_log_constrained_ei_f64(o, cs, nc, st, s, lo, hi, fmin, lim, maxeval, x, v, ne);
+  }
   static int get(hbegp_model* m, double* t, double* a, double* ki) { return hbegp_model_get_f64(m, t, a, ki); }
 };
 template <> struct Abi<float> {
@@ -163,6 +171,14 @@ template <> struct Abi<float> {
   static int maximize_constrained_ei(hbegp_model* o, hbegp_model* const* cs, int nc, const float* st, int s, const double* lo, const double* hi,
                                      double fmin, const double* lim, int maxeval, float* x, double* v, int* ne) {
     return hbegp_maximize_constrained_ei_f32(o, cs, nc, st, s, lo, hi, fmin, lim, maxeval, x, v, ne);
+  }
+  static int log_constrained_ei(hbegp_model* o, hbegp_model* const* cs, int nc, const float* xs, int m, double fmin, const double* lim, double* v,
+                                float* g, int* best, double* lei, double* lpof, float* mean, float* var) {
+    return hbegp_log_constrained_ei_f32(o, cs, nc, xs, m, fmin, lim, v, g, best, lei, lpof, mean, var);
+  }
+  static int maximize_log_constrained_ei(hbegp_model* o, hbegp_model* const* cs, int nc, const float* st, int s, const double* lo, const double* hi,
+                                         double fmin, const double* lim, int maxeval, float* x, double* v, int* ne) {
+    return hbegp_maximize_log_constrained_ei_f32(o, cs, nc, st, s, lo, hi, fmin, lim, maxeval, x, v, ne);
   }
   static int get(hbegp_model* m, double* t, float* a, float* ki) { return hbegp_model_get_f32(m, t, a, ki); }
 };
@@ -353,6 +369,30 @@ void maximize_constrained_ei(const FittedKernel<A>& objective, const std::vector
   for (const auto* c : constraints) cs.push_back(c ? c->handle() : nullptr);
   check(detail::Abi<A>::maximize_constrained_ei(objective.handle(), cs.data(), (int)cs.size(), starts, S, lo, hi, fmin, limits, maxeval, x_out,
                                                 cei_out, nevals));
+}
+
+// The logarithm of that cEI by stable forms (hbegp_log_constrained_ei_*): lcei[m] = lei + lpof with lei = log EI (0 for fmin = +infinity)
+// and lpof = sum_k log P[constraint k holds]; grad[m*d] is the gradient of lcei.  Finite, with a gradient, where constrained_ei
+// underflows to exactly 0; -infinity only for a sigma = 0 on the wrong side.  Without constraints it is log EI.  Arguments as
+// constrained_ei
+template <typename A>
+void log_constrained_ei(const FittedKernel<A>& objective, const std::vector<const FittedKernel<A>*>& constraints, const A* xs, int m,
+                        double fmin, const double* limits, double* lcei, A* grad = nullptr, int* best = nullptr, double* lei = nullptr,
+                        double* lpof = nullptr, A* mean = nullptr, A* var = nullptr) {
+  std::vector<hbegp_model*> cs;
+  for (const auto* c : constraints) cs.push_back(c ? c->handle() : nullptr);
+  check(detail::Abi<A>::log_constrained_ei(objective.handle(), cs.data(), (int)cs.size(), xs, m, fmin, limits, lcei, grad, best, lei, lpof, mean,
+                                           var));
+}
+// maximize_constrained_ei on lcei: the runs move where every start has cei = 0; a row at -infinity is a failed evaluation
+template <typename A>
+void maximize_log_constrained_ei(const FittedKernel<A>& objective, const std::vector<const FittedKernel<A>*>& constraints, const A* starts,
+                                 int S, const double* lo, const double* hi, double fmin, const double* limits, int maxeval, A* x_out,
+                                 double* lcei_out, int* nevals = nullptr) {
+  std::vector<hbegp_model*> cs;
+  for (const auto* c : constraints) cs.push_back(c ? c->handle() : nullptr);
+  check(detail::Abi<A>::maximize_log_constrained_ei(objective.handle(), cs.data(), (int)cs.size(), starts, S, lo, hi, fmin, limits, maxeval,
+                                                    x_out, lcei_out, nevals));
 }
 
 // RAII owner of an hbegp_paths handle (FittedKernel::sample_paths); it keeps its model alive

@@ -181,6 +181,28 @@ extern "C" {
     ) -> c_int;
     #[allow(dead_code)]
     fn hbegp_debug_cei_phases(enable: c_int, phase_ms: *mut c_double) -> c_int;
+    fn hbegp_log_constrained_ei_f64(
+        objective: *mut HbegpModel, constraints: *const *mut HbegpModel, n_con: c_int, xs: *const c_double, m: c_int,
+        fmin_normalized: c_double, limits: *const c_double, lcei: *mut c_double, grad: *mut c_double, best: *mut c_int,
+        lei: *mut c_double, lpof: *mut c_double, mean: *mut c_double, var: *mut c_double,
+    ) -> c_int;
+    fn hbegp_maximize_log_constrained_ei_f64(
+        objective: *mut HbegpModel, constraints: *const *mut HbegpModel, n_con: c_int, starts: *const c_double, s: c_int,
+        lo: *const c_double, hi: *const c_double, fmin_normalized: c_double, limits: *const c_double, maxeval: c_int,
+        x_out: *mut c_double, lcei_out: *mut c_double, nevals_out: *mut c_int,
+    ) -> c_int;
+    fn hbegp_log_constrained_ei_f32(
+        objective: *mut HbegpModel, constraints: *const *mut HbegpModel, n_con: c_int, xs: *const c_float, m: c_int,
+        fmin_normalized: c_double, limits: *const c_double, lcei: *mut c_double, grad: *mut c_float, best: *mut c_int,
+        lei: *mut c_double, lpof: *mut c_double, mean: *mut c_float, var: *mut c_float,
+    ) -> c_int;
+    fn hbegp_maximize_log_constrained_ei_f32(
+        objective: *mut HbegpModel, constraints: *const *mut HbegpModel, n_con: c_int, starts: *const c_float, s: c_int,
+        lo: *const c_double, hi: *const c_double, fmin_normalized: c_double, limits: *const c_double, maxeval: c_int,
+        x_out: *mut c_float, lcei_out: *mut c_double, nevals_out: *mut c_int,
+    ) -> c_int;
+    #[allow(dead_code)]
+    fn hbegp_debug_lcei_phases(enable: c_int, phase_ms: *mut c_double) -> c_int;
     fn hbegp_noisy_ei_f64(
         model: *mut HbegpModel, xs: *const c_double, m: c_int, mb: c_int, z: *const c_double, s: c_int, jitter: c_double,
         nei: *mut c_double, best: *mut c_int, fmin_draws: *mut c_double, rho: *mut c_double, info: *mut c_int,
@@ -325,6 +347,20 @@ pub trait GpuScalar: Scalar + sealed::Sealed {
         hi: *const f64, fmin_normalized: f64, limits: *const f64, maxeval: c_int, x_out: *mut Self, cei_out: *mut f64,
         nevals_out: *mut c_int,
     ) -> c_int;
+    /// `hbegp_log_constrained_ei_*`
+    #[allow(clippy::too_many_arguments)]
+    unsafe fn ffi_log_constrained_ei(
+        objective: *mut HbegpModel, constraints: *const *mut HbegpModel, n_con: c_int, xs: *const Self, m: c_int, fmin_normalized: f64,
+        limits: *const f64, cei: *mut f64, grad: *mut Self, best: *mut c_int, ei: *mut f64, pof: *mut f64, mean: *mut Self,
+        var: *mut Self,
+    ) -> c_int;
+    /// `hbegp_maximize_log_constrained_ei_*`
+    #[allow(clippy::too_many_arguments)]
+    unsafe fn ffi_maximize_log_constrained_ei(
+        objective: *mut HbegpModel, constraints: *const *mut HbegpModel, n_con: c_int, starts: *const Self, s: c_int, lo: *const f64,
+        hi: *const f64, fmin_normalized: f64, limits: *const f64, maxeval: c_int, x_out: *mut Self, cei_out: *mut f64,
+        nevals_out: *mut c_int,
+    ) -> c_int;
     /// `hbegp_noisy_ei_*`
     #[allow(clippy::too_many_arguments)]
     unsafe fn ffi_noisy_ei(
@@ -423,6 +459,21 @@ impl GpuScalar for f64 {
     ) -> c_int {
         hbegp_maximize_constrained_ei_f64(objective, constraints, n_con, starts, s, lo, hi, fmin_normalized, limits, maxeval, x_out,
                                           cei_out, nevals_out)
+    }
+    unsafe fn ffi_log_constrained_ei(
+        objective: *mut HbegpModel, constraints: *const *mut HbegpModel, n_con: c_int, xs: *const f64, m: c_int, fmin_normalized: f64,
+        limits: *const f64, cei: *mut f64, grad: *mut f64, best: *mut c_int, ei: *mut f64, pof: *mut f64, mean: *mut f64,
+        var: *mut f64,
+    ) -> c_int {
+        hbegp_log_constrained_ei_f64(objective, constraints, n_con, xs, m, fmin_normalized, limits, cei, grad, best, ei, pof, mean, var)
+    }
+    unsafe fn ffi_maximize_log_constrained_ei(
+        objective: *mut HbegpModel, constraints: *const *mut HbegpModel, n_con: c_int, starts: *const f64, s: c_int, lo: *const f64,
+        hi: *const f64, fmin_normalized: f64, limits: *const f64, maxeval: c_int, x_out: *mut f64, cei_out: *mut f64,
+        nevals_out: *mut c_int,
+    ) -> c_int {
+        hbegp_maximize_log_constrained_ei_f64(objective, constraints, n_con, starts, s, lo, hi, fmin_normalized, limits, maxeval,
+                                              x_out, cei_out, nevals_out)
     }
     unsafe fn ffi_noisy_ei(
         model: *mut HbegpModel, xs: *const f64, m: c_int, mb: c_int, z: *const f64, s: c_int, jitter: f64, nei: *mut f64,
@@ -524,6 +575,21 @@ impl GpuScalar for f32 {
     ) -> c_int {
         hbegp_maximize_constrained_ei_f32(objective, constraints, n_con, starts, s, lo, hi, fmin_normalized, limits, maxeval, x_out,
                                           cei_out, nevals_out)
+    }
+    unsafe fn ffi_log_constrained_ei(
+        objective: *mut HbegpModel, constraints: *const *mut HbegpModel, n_con: c_int, xs: *const f32, m: c_int, fmin_normalized: f64,
+        limits: *const f64, cei: *mut f64, grad: *mut f32, best: *mut c_int, ei: *mut f64, pof: *mut f64, mean: *mut f32,
+        var: *mut f32,
+    ) -> c_int {
+        hbegp_log_constrained_ei_f32(objective, constraints, n_con, xs, m, fmin_normalized, limits, cei, grad, best, ei, pof, mean, var)
+    }
+    unsafe fn ffi_maximize_log_constrained_ei(
+        objective: *mut HbegpModel, constraints: *const *mut HbegpModel, n_con: c_int, starts: *const f32, s: c_int, lo: *const f64,
+        hi: *const f64, fmin_normalized: f64, limits: *const f64, maxeval: c_int, x_out: *mut f32, cei_out: *mut f64,
+        nevals_out: *mut c_int,
+    ) -> c_int {
+        hbegp_maximize_log_constrained_ei_f32(objective, constraints, n_con, starts, s, lo, hi, fmin_normalized, limits, maxeval,
+                                              x_out, cei_out, nevals_out)
     }
     unsafe fn ffi_noisy_ei(
         model: *mut HbegpModel, xs: *const f32, m: c_int, mb: c_int, z: *const f32, s: c_int, jitter: f64, nei: *mut f64,
@@ -902,6 +968,56 @@ impl<A: GpuScalar> SurrogateModelGpu<A> {
             panic!("hbegp_maximize_constrained_ei failed: {}", last_error());
         }
         (x_out, cei, nevals)
+    }
+
+    /// `constrained_ei_normalized` in log space (`hbegp_log_constrained_ei_*`; log EI, Ament et al. 2023): lcei = log EI + sum_k log
+    /// P[constraint k holds] from stable forms, finite -- with a usable ranking and gradient -- where `constrained_ei_normalized`
+    /// underflows to exactly 0 (every |z| beyond 38); -inf only for a sigma = 0 on the wrong side of its threshold.  Arguments as
+    /// `constrained_ei_normalized`; without constraints it is log EI.  Returns (lcei [m], best = the last index of its maximum,
+    /// None without rows).  Opt-in.
+    pub fn log_constrained_ei_normalized(&self, constraints: &[&Self], x: ArrayView2<A>, fmin_normalized: f64, limits: &[f64])
+        -> (Vec<f64>, Option<usize>) {
+        assert_eq!(constraints.len(), limits.len(), "one limit per constraint");
+        let (m, _d) = x.dim();
+        let x = x.as_standard_layout();
+        let handles: Vec<*mut HbegpModel> = constraints.iter().map(|c| c.handle).collect();
+        let mut lcei = vec![0.0f64; m];
+        let mut best: c_int = -1;
+        let lcei_ptr = if m > 0 { lcei.as_mut_ptr() } else { std::ptr::null_mut() };
+        let rc = unsafe {
+            A::ffi_log_constrained_ei(self.handle, handles.as_ptr(), handles.len() as c_int, x.as_ptr(), m as c_int, fmin_normalized,
+                                      limits.as_ptr(), lcei_ptr, std::ptr::null_mut(), &mut best, std::ptr::null_mut(),
+                                      std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut())
+        };
+        if rc != HBEGP_OK {
+            panic!("hbegp_log_constrained_ei failed: {}", last_error());
+        }
+        (lcei, usize::try_from(best).ok())
+    }
+
+    /// `maximize_constrained_ei` on `log_constrained_ei_normalized` (`hbegp_maximize_log_constrained_ei_*`): the runs move where
+    /// every start has a constrained EI of exactly 0.  Returns (x [S, d] row-major, lcei [S], evaluations [S]); a row at -inf is a
+    /// failed evaluation.  Opt-in.
+    #[allow(clippy::too_many_arguments)]
+    pub fn maximize_log_constrained_ei(&self, constraints: &[&Self], starts: ArrayView2<A>, lo: &[f64], hi: &[f64], fmin_normalized: f64,
+                                       limits: &[f64], maxeval: usize) -> (Vec<A>, Vec<f64>, Vec<c_int>) {
+        assert_eq!(constraints.len(), limits.len(), "one limit per constraint");
+        let (s, d) = starts.dim();
+        assert!(lo.len() == d && hi.len() == d, "one bound pair per feature");
+        let starts = starts.as_standard_layout();
+        let handles: Vec<*mut HbegpModel> = constraints.iter().map(|c| c.handle).collect();
+        let mut x_out = vec![A::zero(); s * d];
+        let mut lcei = vec![0.0f64; s];
+        let mut nevals = vec![0 as c_int; s];
+        let rc = unsafe {
+            A::ffi_maximize_log_constrained_ei(self.handle, handles.as_ptr(), handles.len() as c_int, starts.as_ptr(), s as c_int,
+                                               lo.as_ptr(), hi.as_ptr(), fmin_normalized, limits.as_ptr(), maxeval as c_int,
+                                               x_out.as_mut_ptr(), lcei.as_mut_ptr(), nevals.as_mut_ptr())
+        };
+        if rc != HBEGP_OK {
+            panic!("hbegp_maximize_log_constrained_ei failed: {}", last_error());
+        }
+        (x_out, lcei, nevals)
     }
 
     /// Noisy expected improvement over a candidate set (`hbegp_noisy_ei_*`; Letham, Karrer, Ottoni, Bakshy 2019): EI of every row

@@ -46,3 +46,5 @@ rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/c5" -o run -- pyth
 cp "$OUT/c5/run_kernel_stats.csv" "$OUT/${TAG}_c5_f32_kernel_stats.csv"
 rm -rf "$OUT/c5"
 cd "$ROOT"
+echo "[extra] log-space constrained EI beside cEI (profiles/lcei_bench.txt: prepend its header by hand)"
+python3 "$ROOT/tools/lcei_bench.py" --reps 3 > "$OUT/lcei_bench.txt" 2>&1
