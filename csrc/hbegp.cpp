@@ -1536,6 +1536,9 @@ struct Problem : ProblemBase {
     HIPCHECK(hipStreamSynchronize(s.stream));
     s.last_target = 0;
     if (s.hOut->info == 0 && !(s.hOut->done & 1)) throw HipError{hipErrorLaunchFailure, "extend: the evaluation kernels did not run", __LINE__};
+    // a non-finite lml (a NaN target: the factor itself is fine) is handled like a failed factorisation, as run_eval handles it on
+    // the full path: no model with NaN alpha and lml is handed out
+    if (s.hOut->info == 0 && !std::isfinite(s.hOut->lml)) return HBEGP_NOT_PD;
     return s.hOut->info != 0 ? HBEGP_NOT_PD : HBEGP_OK;
   }
 
