@@ -304,6 +304,11 @@ void launch_cei(const CeiArgs<T>& a, int m, int d, int want_grad, double* cei, d
 // lpof = sum_k log F_k from stable forms, the gradient of lcei, *best = the last index of the maximum of lcei.
 template <typename T>
 void launch_lcei(const CeiArgs<T>& a, int m, int d, int want_grad, double* lcei, double* lei, double* lpof, T* grad, int* best, hipStream_t s);
+// max-value entropy search (hbegp_mes; mes_kernel: one wave per candidate): mean, var [m] and, with want_grad, dmean, dvar [m][d] of
+// ONE model; ystar [S] on the device, S >= 1.  Out: mes[m], grad[m][d] (want_grad), *best = the last index of the maximum of mes.
+template <typename T>
+void launch_mes(const T* mean, const T* var, const T* dmean, const T* dvar, int m, int d, const double* ystar, int S, int want_grad,
+                double* mes, T* grad, int* best, hipStream_t s);
 // batch expected improvement by Monte Carlo (hbegp_qei; qei_batch_kernel: one workgroup per batch of q points).  Rows b q .. b q + q - 1
 // of Xs [B q][d], Q [mp][np], mean, dmean [mp][d] and W [d][mp][np] (W and dmean are read only with want_grad); z [S][q] shared by
 // the batches; noise = 1e-5 + jitter.  Out: qei[B], grad[B q][d] (want_grad), info[B] (0, or 1 + the column whose pivot failed).

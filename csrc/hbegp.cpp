@@ -2135,7 +2135,7 @@ struct CallScratch {
 // ---- phase times of the posterior-side calls (hbegp_debug_*_phases) ----------------------------------------------------------
 // One record per kind and calling thread: whether the thread's calls of that kind are timed, and the phase times (ms) of its last
 // timed call of that kind that reached its end.
-enum PhaseKind { PH_POSTERIOR, PH_SELECT, PH_KG, PH_NEI, PH_SENS, PH_EHVI, PH_QEI, PH_LOO, PH_PATHS, PH_CEI, PH_LCEI, PH_KINDS };
+enum PhaseKind { PH_POSTERIOR, PH_SELECT, PH_KG, PH_NEI, PH_SENS, PH_EHVI, PH_QEI, PH_LOO, PH_PATHS, PH_CEI, PH_LCEI, PH_MES, PH_KINDS };
 struct PhaseRecord {
   bool on = false;
   double ms[4] = {0, 0, 0, 0};
@@ -2205,6 +2205,7 @@ class PhaseClock {
 //   paths      hbegp_paths_create: uploads + frequency scaling, the feature projection, the two triangular products
 //   cei        the K predicts (the objective's upload .. the join of the K streams), the cEI kernel with the arg-max
 //   lcei       as cei, the second phase being the log-space kernel with the arg-max
+//   mes        the predict (the uploads .. the last predict or gradient launch), the MES kernel with the arg-max
 
 // Sigma = K** + noise I - Q Q^T at the candidates into W (lower tiles; m_p x m_p, kmat's identity padding): the candidates'
 // upload, the batched predict's launches (Kstar, the mean, Q = Kstar X^T; the variance too, unused), then kmat_kernel over
@@ -2924,6 +2925,82 @@ static int model_maximize_constrained_ei(hbegp_model* const* M, int K, const T* 
     return (int)HBEGP_OK;
   };
   return lockstep_optimize<T, LbfgsState>(starts, S, d, lo, hi, lockstep_options(maxeval, true), eval, x_out, cei_out, nevals_out);
+}
+
+// ---- max-value entropy search (hbegp_mes / hbegp_maximize_mes) ----------------------------------------------
+
+// MES at cnt >= 1 candidates under ONE model and S sampled minimum values: the candidates' and y*'s uploads, the batched predict's
+// launches (hbegp_predict's, or hbegp_predict_grad's with a gradient, in their order), then mes_kernel and the arg-max, all on the
+// model's stream under the model's mutex.  The outputs and y* are borrowed for the call (CallScratch) and go back cleared; each is
+// written in full before it is read: y* by its upload, mes [cnt] and the gradient [cnt][d] by mes_kernel, best by the arg-max.
+template <typename T>
+static int model_mes(hbegp_model* m, const T* Xs, int cnt, const double* ystar, int S, double* mes, T* grad, int* best, T* mean_out,
+                     T* var_out) {
+  const bool want_grad = grad != nullptr;
+  const int d = m->d;
+  // everything the call takes, counted before anything is taken: an m far beyond the device is ENOMEM, not an overflow
+  const double rows = std::ceil(std::max(1.0, (double)cnt) / NB) * NB;
+  const double need = 8.0 * cnt + 8.0 * S + (want_grad ? (double)sizeof(T) * cnt * d : 0.0) +
+                      (double)sizeof(T) * ((2.0 + (want_grad ? 2.0 * d : 0.0)) * rows * m->np + rows * (d + 2) + (want_grad ? 2.0 * rows * d : 0.0)) +
+                      8.0 * (want_grad ? (double)pred_grad_chunks(m->n) * rows * d : 0.0);
+  if (need > 1e15 || rows > (double)(1 << 30))
+    return fail(HBEGP_ENOMEM, "max-value entropy search at %d points needs %.3g bytes of device memory", cnt, need);
+  std::lock_guard<std::mutex> lock(m->mu);
+  HIPCHECK(hipSetDevice(m->dev));
+  const int mp = round_up(cnt, NB);
+  if (want_grad) predict_grad_reserve<T>(m, mp);
+  else predict_batched_reserve<T>(m, mp);
+  hipStream_t s = m->stream;
+  CallScratch ws{m->dev, s, {}};
+  double* dval = static_cast<double*>(ws.get(sizeof(double) * (size_t)cnt));
+  double* dys = static_cast<double*>(ws.get(sizeof(double) * (size_t)S));
+  int* dbest = static_cast<int*>(ws.get(sizeof(int)));
+  T* dg = want_grad ? static_cast<T*>(ws.get(sizeof(T) * (size_t)cnt * d)) : nullptr;
+  PhaseClock clk(t_phase[PH_MES].on, 3);  // before the uploads, behind the predict's launches, behind the arg-max
+  clk.mark(s);
+  HIPCHECK(hipMemcpyAsync(m->Xs, Xs, sizeof(T) * (size_t)cnt * d, hipMemcpyHostToDevice, s));
+  HIPCHECK(hipMemcpyAsync(dys, ystar, sizeof(double) * (size_t)S, hipMemcpyHostToDevice, s));
+  predict_batched_launches<T>(m, cnt, mp, true);
+  if (want_grad) predict_grad_launches<T>(m, cnt, mp, true, true);
+  CHECK_LAUNCHES();
+  clk.mark(s);
+  launch_mes<T>(static_cast<const T*>(m->mean), static_cast<const T*>(m->var), want_grad ? static_cast<const T*>(m->dmean) : nullptr,
+                want_grad ? static_cast<const T*>(m->dvar) : nullptr, cnt, d, dys, S, want_grad ? 1 : 0, dval, dg, dbest, s);
+  clk.mark(s);
+  CHECK_LAUNCHES();
+  int hbest = -1;
+  HIPCHECK(hipMemcpyAsync(mes, dval, sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipMemcpyAsync(&hbest, dbest, sizeof(int), hipMemcpyDeviceToHost, s));
+  if (want_grad) HIPCHECK(hipMemcpyAsync(grad, dg, sizeof(T) * (size_t)cnt * d, hipMemcpyDeviceToHost, s));
+  if (mean_out) HIPCHECK(hipMemcpyAsync(mean_out, m->mean, sizeof(T) * (size_t)cnt, hipMemcpyDeviceToHost, s));
+  if (var_out) HIPCHECK(hipMemcpyAsync(var_out, m->var, sizeof(T) * (size_t)cnt, hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
+  if (best) *best = hbest;
+  clk.store(PH_MES, 2);
+  return HBEGP_OK;
+}
+
+// R bounded L-BFGS runs on -MES in lockstep (lockstep.hpp), as model_maximize_constrained_ei: every round is ONE model_mes with a
+// gradient.  Each run returns the best point it evaluated; a value or a gradient component that is not finite is a failed
+// evaluation.
+template <typename T>
+static int model_maximize_mes(hbegp_model* m, const T* starts, int R, const double* lo, const double* hi, const double* ystar, int S,
+                              int maxeval, T* x_out, double* mes_out, int* nevals_out) {
+  const int d = m->d;
+  std::vector<T> gr((size_t)R * d);
+  auto eval = [&](const T* xs, const int*, int cnt, double* val, double* grad, char* ok) {
+    const int rc = model_mes<T>(m, xs, cnt, ystar, S, val, gr.data(), nullptr, nullptr, nullptr);
+    if (rc != HBEGP_OK) return rc;
+    for (int i = 0; i < cnt; ++i) {
+      ok[i] = std::isfinite(val[i]);
+      for (int k = 0; k < d; ++k) {
+        grad[(size_t)i * d + k] = (double)gr[(size_t)i * d + k];
+        ok[i] = ok[i] && std::isfinite(grad[(size_t)i * d + k]);
+      }
+    }
+    return (int)HBEGP_OK;
+  };
+  return lockstep_optimize<T, LbfgsState>(starts, R, d, lo, hi, lockstep_options(maxeval, true), eval, x_out, mes_out, nevals_out);
 }
 
 // Batch expected improvement by Monte Carlo (hbegp_qei) for B batches of q points: the B q points go through the batched predict's
@@ -4727,6 +4804,58 @@ int hbegp_maximize_log_constrained_ei_f32(hbegp_model* objective, hbegp_model* c
                                 nevals_out, true);
 }
 int hbegp_debug_lcei_phases(int enable, double* phase_ms) { return debug_phases(PH_LCEI, 2, enable, phase_ms); }
+}  // extern "C"
+
+// argument checks of hbegp_mes_* / hbegp_maximize_mes_*: everything is refused before any device call
+template <typename T>
+static int check_mes(hbegp_model* model, const double* ystar, int S) {
+  if (S < 1 || S > HBEGP_MES_MAX_SAMPLES) return fail(HBEGP_EINVAL, "S must lie in [1, %d] (got %d)", HBEGP_MES_MAX_SAMPLES, S);
+  if (!ystar) return fail(HBEGP_EINVAL, "ystar is NULL");
+  for (int s = 0; s < S; ++s)
+    if (!std::isfinite(ystar[s])) return fail(HBEGP_EINVAL, "ystar[%d] is not finite", s);
+  if (!model) return fail(HBEGP_EINVAL, "NULL model");
+  if (model->is_f32 != (sizeof(T) == 4)) return fail(HBEGP_EINVAL, "model holds %s data", model->is_f32 ? "f32" : "f64");
+  return HBEGP_OK;
+}
+template <typename T>
+static int do_mes(hbegp_model* model, const T* Xs, int m, const double* ystar, int S, double* mes, T* grad, int* best, T* mean, T* var) {
+  if (int rc = check_mes<T>(model, ystar, S)) return rc;
+  if (m < 0) return fail(HBEGP_EINVAL, "m must be >= 0 (got %d)", m);
+  if (m > 0 && (!Xs || !mes)) return fail(HBEGP_EINVAL, "Xs/mes is NULL");
+  if (best) *best = -1;
+  if (m == 0) return HBEGP_OK;
+  GUARD_BEGIN
+  return model_mes<T>(model, Xs, m, ystar, S, mes, grad, best, mean, var);
+  GUARD_END
+}
+template <typename T>
+static int do_maximize_mes(hbegp_model* model, const T* starts, int R, const double* lo, const double* hi, const double* ystar, int S,
+                           int maxeval, T* x_out, double* mes_out, int* nevals_out) {
+  if (R < 1) return fail(HBEGP_EINVAL, "R must be >= 1 (got %d)", R);
+  if (int rc = check_mes<T>(model, ystar, S)) return rc;
+  if (int rc = check_maximize_ei<T>(model, starts, R, lo, hi, 0.0, maxeval, x_out, mes_out)) return rc;
+  GUARD_BEGIN
+  return model_maximize_mes<T>(model, starts, R, lo, hi, ystar, S, maxeval, x_out, mes_out, nevals_out);
+  GUARD_END
+}
+extern "C" {
+int hbegp_mes_f64(hbegp_model* model, const double* Xs, int m, const double* ystar, int S, double* mes, double* grad, int* best,
+                  double* mean, double* var) {
+  return do_mes<double>(model, Xs, m, ystar, S, mes, grad, best, mean, var);
+}
+int hbegp_mes_f32(hbegp_model* model, const float* Xs, int m, const double* ystar, int S, double* mes, float* grad, int* best, float* mean,
+                  float* var) {
+  return do_mes<float>(model, Xs, m, ystar, S, mes, grad, best, mean, var);
+}
+int hbegp_maximize_mes_f64(hbegp_model* model, const double* starts, int R, const double* lo, const double* hi, const double* ystar, int S,
+                           int maxeval, double* x_out, double* mes_out, int* nevals_out) {
+  return do_maximize_mes<double>(model, starts, R, lo, hi, ystar, S, maxeval, x_out, mes_out, nevals_out);
+}
+int hbegp_maximize_mes_f32(hbegp_model* model, const float* starts, int R, const double* lo, const double* hi, const double* ystar, int S,
+                           int maxeval, float* x_out, double* mes_out, int* nevals_out) {
+  return do_maximize_mes<float>(model, starts, R, lo, hi, ystar, S, maxeval, x_out, mes_out, nevals_out);
+}
+int hbegp_debug_mes_phases(int enable, double* phase_ms) { return debug_phases(PH_MES, 2, enable, phase_ms); }
 }  // extern "C"
 
 // argument checks of hbegp_sobol_* / hbegp_main_effects_*: everything is refused before any device call, the checks that need no

@@ -4857,6 +4857,124 @@ void launch_lcei(const CeiArgs<T>& a, int m, int d, int want_grad, double* lcei,
 template void launch_lcei<double>(const CeiArgs<double>&, int, int, int, double*, double*, double*, double*, int*, hipStream_t);
 template void launch_lcei<float>(const CeiArgs<float>&, int, int, int, double*, double*, double*, float*, int*, hipStream_t);
 
+// =================================================================================================================
+// max-value entropy search over ONE model and S sampled minimum values y*_s (hbegp.cpp: model_mes):
+//   mes = (1/S) sum_s t(gamma_s),   gamma_s = (mu - y*_s) / sigma,   t(g) = g lambda(g) / 2 - log Phi(g),   lambda = phi / Phi,
+//   t'(g) = -(lambda / 2) (1 + g^2 + g lambda),   d mes / d mu = (1/S) sum t' / sigma,   d mes / d sigma = -(1/S) sum g t' / sigma.
+// One WAVE per candidate, CEI_WAVES candidates per workgroup; y* is staged once per workgroup in the LDS when S fits
+// (S <= MES_LDS_SAMPLES: every call through the C ABI), else read from global memory.  Lane l evaluates mes_term for
+// s = l, l + 64, .. in ascending s and keeps three partial sums (t, t', g t'), which go through ehvi_wave_sum's fixed butterfly and
+// are then scaled by 1/S; every lane holds the same three totals, so the lanes stride over the features without another shuffle.
+// All of it in fp64 for both element types, with or without a gradient, no atomics: a candidate's bits depend on nothing but its
+// own posterior and the y* array in the order given.  sigma = 0: mes = 0 with a zero gradient.  A NaN in the posterior gives NaN
+// in the candidate's mes and gradient row.
+//
+// mes_term has lcei_term's branch points.  For g > -1 the direct forms (g lambda and t' count as 0 where phi has underflowed).
+// For g = -a <= -1 both terms of t grow like a^2 / 2 and cancel to O(log a); with au = a u (u the Mills ratio, as in lcei_term) and
+// b = 1 - au:  w = a^2 b / au = -g (g + lambda),   t = -w / 2 + log sqrt(2 pi) + (log a - log au),   t' = -(a / au) (1 - w) / 2.
+// From a = LCEI_SERIES_A on, au and bx = b / x (x = 1 / a^2) come from lcei_term's ten-term series and (au - bx) / x from the
+// term-wise difference of the two coefficient lists (the constant terms cancel exactly):  w = bx / au,
+// 1 - w = x ((au - bx) / x) / au; a * a is never formed.  g is clamped to +-1.7e308 by the caller.
+// =================================================================================================================
+constexpr int MES_LDS_SAMPLES = 1024;
+
+struct MesTerm {
+  double t, dt;  // t(g) and t'(g)
+};
+// not inlined: erfcx's, erfc's, log's and exp's fp64 coefficients, once per lane
+__device__ __noinline__ MesTerm mes_term(double g) {
+  MesTerm r = {0.0, 0.0};
+  if (g > -1.0) {
+    const double az = fabs(g);
+    const double cl = 0.5 * erfc(az / 1.4142135623730951);        // Phi(-|g|)
+    const double pdf = exp(-0.5 * az * az) / 2.5066282746310002;  // phi(g)
+    const double cdf = g > 0.0 ? 1.0 - cl : cl;
+    const double lam = pdf / cdf;
+    const double lphi = g > 0.0 ? log1p(-cl) : log(cl);
+    const double gl = pdf > 0.0 ? g * lam : 0.0;                  // (g = 1.7e308 times an underflowed phi is 0)
+    r.t = 0.5 * gl - lphi;
+    r.dt = pdf > 0.0 ? -0.5 * lam * (1.0 + g * g + gl) : 0.0;
+  } else {
+    const double a = -g;
+    if (a < LCEI_SERIES_A) {
+      const double au = a * (1.2533141373155003 * erfcx(a / 1.4142135623730951));
+      const double w = a * a * (1.0 - au) / au;
+      r.t = -0.5 * w + 0.91893853320467274 + (log(a) - log(au));
+      r.dt = -(a / au) * (1.0 - w) / 2.0;
+    } else {
+      const double x = 1.0 / a / a;  // (a * a may overflow where 1 / a / a only underflows)
+      const double au = 1.0 + x * (-1.0 + x * (3.0 + x * (-15.0 + x * (105.0 + x * (-945.0 + x * (10395.0 + x * (-135135.0 + x * (2027025.0 + x * -34459425.0))))))));
+      const double bx = 1.0 + x * (-3.0 + x * (15.0 + x * (-105.0 + x * (945.0 + x * (-10395.0 + x * (135135.0 + x * (-2027025.0 + x * (34459425.0 + x * -654729075.0))))))));
+      const double dq = 2.0 + x * (-12.0 + x * (90.0 + x * (-840.0 + x * (9450.0 + x * (-124740.0 + x * (1891890.0 + x * (-32432400.0 + x * 620269650.0)))))));  // (au - bx) / x
+      r.t = -bx / (2.0 * au) + 0.91893853320467274 + (log(a) - log(au));
+      r.dt = -(a / au) * (x * dq / au) / 2.0;
+    }
+  }
+  return r;
+}
+
+template <typename T, bool LDS>
+__global__ void __launch_bounds__(64 * CEI_WAVES) mes_kernel(const T* __restrict__ mean, const T* __restrict__ var,
+                                                             const T* __restrict__ dmean, const T* __restrict__ dvar, int m, int d,
+                                                             const double* __restrict__ ystar, int S, int want_grad,
+                                                             double* __restrict__ mes, T* __restrict__ grad) {
+  __shared__ double st[LDS ? MES_LDS_SAMPLES : 1];
+  const double* ys = ystar;
+  if (LDS) {
+    for (int i = threadIdx.x; i < S; i += 64 * CEI_WAVES) st[i] = ystar[i];
+    __syncthreads();
+    ys = st;
+  }
+  const int lane = threadIdx.x & 63;
+  const int j = blockIdx.x * CEI_WAVES + (threadIdx.x >> 6);
+  if (j >= m) return;  // whole waves leave, behind the only barrier
+  const double mu = (double)mean[j], v = (double)var[j];
+  const double sd = sqrt(v);
+  const bool bad = (mu != mu) || (v != v);
+  const bool live = sd > 2.220446049250313e-16;  // wave-uniform
+  double s0 = 0.0, s1 = 0.0, s2 = 0.0;           // this lane's sums of t, t' and g t'
+  if (live)
+    for (int base = 0; base < S; base += 64) {  // a uniform trip count, ascending s
+      const int i = base + lane;
+      if (i < S) {
+        const double g = fmin(fmax((mu - ys[i]) / sd, -1.7e308), 1.7e308);
+        const MesTerm r = mes_term(g);
+        s0 += r.t;
+        s1 += r.dt;
+        s2 += g * r.dt;
+      }
+    }
+  s0 = ehvi_wave_sum(s0);  // the whole wave is here: `live` is uniform and the loop has ended for every lane
+  s1 = ehvi_wave_sum(s1);
+  s2 = ehvi_wave_sum(s2);
+  const double nan = __longlong_as_double(0x7ff8000000000000LL);
+  if (lane == 0) mes[j] = bad ? nan : s0 / (double)S;
+  if (!want_grad) return;
+  const double cm = live ? s1 / (double)S / sd : 0.0;   // d mes / d mu
+  const double cs = live ? -s2 / (double)S / sd : 0.0;  // d mes / d sigma
+  for (int i = lane; i < d; i += 64) {
+    const size_t x = (size_t)j * d + i;
+    const double ds = live ? (double)dvar[x] / (2.0 * sd) : 0.0;
+    const double gx = cm * (double)dmean[x] + cs * ds;
+    grad[x] = bad ? (T)nan : (T)gx;
+  }
+}
+
+template <typename T>
+void launch_mes(const T* mean, const T* var, const T* dmean, const T* dvar, int m, int d, const double* ystar, int S, int want_grad,
+                double* mes, T* grad, int* best, hipStream_t s) {
+  const dim3 grid((unsigned)((m + CEI_WAVES - 1) / CEI_WAVES)), block(64 * CEI_WAVES);
+  if (S <= MES_LDS_SAMPLES)
+    hipLaunchKernelGGL((mes_kernel<T, true>), grid, block, 0, s, mean, var, dmean, dvar, m, d, ystar, S, want_grad, mes, grad);
+  else
+    hipLaunchKernelGGL((mes_kernel<T, false>), grid, block, 0, s, mean, var, dmean, dvar, m, d, ystar, S, want_grad, mes, grad);
+  hipLaunchKernelGGL(ehvi_best_kernel, dim3(1), dim3(BSEL_THREADS), 0, s, mes, m, best);
+}
+template void launch_mes<double>(const double*, const double*, const double*, const double*, int, int, const double*, int, int, double*,
+                                 double*, int*, hipStream_t);
+template void launch_mes<float>(const float*, const float*, const float*, const float*, int, int, const double*, int, int, double*,
+                                float*, int*, hipStream_t);
+
 // Per-device one-time setup: kernels that use more than 64 KiB of dynamic LDS need the attribute raised.  Called from
 // hbegp_ctx_create() for every device, before any stream capture.
 static void init_dag_kernels();  // dag_kernel.inc.hpp (end of this file)

@@ -15,6 +15,7 @@ OK, NOT_PD, ALL_FAILED = 0, 1, 2
 EINVAL, EHIP, ENODEV, ENOMEM = -1, -2, -3, -4
 PATHS_MAX_FEATURES, PATHS_MAX_PATHS = 16384, 1024  # HBEGP_PATHS_MAX_* of include/hbegp.h
 CEI_MAX_CONSTRAINTS = 8  # HBEGP_CEI_MAX_CONSTRAINTS of include/hbegp.h
+MES_MAX_SAMPLES = 1024  # HBEGP_MES_MAX_SAMPLES of include/hbegp.h
 
 
 class HbegpError(RuntimeError):
@@ -128,6 +129,10 @@ SIGNATURES = {
                                                         _dp, _dp, _ip]),
     "hbegp_maximize_log_constrained_ei_f32": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, _fp, C.c_int, _dp, _dp, C.c_double, _dp, C.c_int,
                                                         _fp, _dp, _ip]),
+    "hbegp_mes_f64": (C.c_int, [_vp, _dp, C.c_int, _dp, C.c_int, _dp, _dp, _ip, _dp, _dp]),
+    "hbegp_mes_f32": (C.c_int, [_vp, _fp, C.c_int, _dp, C.c_int, _dp, _fp, _ip, _fp, _fp]),
+    "hbegp_maximize_mes_f64": (C.c_int, [_vp, _dp, C.c_int, _dp, _dp, _dp, C.c_int, C.c_int, _dp, _dp, _ip]),
+    "hbegp_maximize_mes_f32": (C.c_int, [_vp, _fp, C.c_int, _dp, _dp, _dp, C.c_int, C.c_int, _fp, _dp, _ip]),
     "hbegp_sobol_f64": (C.c_int, [_vp, _dp, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "hbegp_sobol_f32": (C.c_int, [_vp, _fp, _fp, C.c_int, _dp, _dp, _dp, _dp, _fp, _fp, _fp]),
     "hbegp_main_effects_f64": (C.c_int, [_vp, _dp, C.c_int, _dp, C.c_int, _dp, _dp]),
@@ -164,6 +169,7 @@ SIGNATURES = {
     "hbegp_debug_ehvi_phases": (C.c_int, [C.c_int, _dp]),
     "hbegp_debug_cei_phases": (C.c_int, [C.c_int, _dp]),
     "hbegp_debug_lcei_phases": (C.c_int, [C.c_int, _dp]),
+    "hbegp_debug_mes_phases": (C.c_int, [C.c_int, _dp]),
     "hbegp_debug_pool_poisoned": (C.c_int, [C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "hbegp_model_info": (C.c_int, [_vp, _ip, _ip, _ip, _dp, _dp]),
     "hbegp_model_get_f64": (C.c_int, [_vp, _dp, _dp, _dp]),

@@ -373,6 +373,46 @@ class SurrogateModelGPR:
         eps = rng.standard_normal((int(n_paths), fk.n)) if noise_draw else None
         return fk.sample_paths(omega0, phase, w, eps)
 
+    # Max-value entropy search (opt-in; nothing the estimator suggests by default uses it).
+    def sample_min_values(self, n_samples, rng, bounds, n_features=1024, n_restarts=8, maxeval=150, grid=None, starts=None):
+        """n_samples draws y* of the VALUE of the surrogate's global minimum over the box `bounds` = [(lo, hi)] per feature, in the
+        NORMALISED y space (what mes_a and maximize_mes take): float64 [n_samples].  Default: n_samples posterior sample paths
+        (sample_paths_a with n_features random features) and each path's lowest value over n_restarts bounded L-BFGS descents
+        (PosteriorPaths.minimize's f_best) from `starts` [n_samples, n_restarts, d] or [n_restarts, d] (default: uniform in the
+        box from rng, drawn before the paths).  With `grid` [m, d]: the row minima of n_samples joint posterior draws at the grid
+        (FittedKernel.sample_posterior with z from rng.standard_normal); bounds is then not used."""
+        S = int(n_samples)
+        if grid is not None:
+            g = np.asarray(grid, dtype=self.dtype)
+            z = rng.standard_normal((S, g.shape[0])).astype(self.dtype)
+            samples, _ = self.fitted.sample_posterior(g, z)
+            return np.asarray(samples, dtype=np.float64).min(axis=1)
+        lo = np.array([b[0] for b in bounds], dtype=np.float64)
+        hi = np.array([b[1] for b in bounds], dtype=np.float64)
+        if starts is None:
+            u = np.asarray(rng.uniform(0.0, 1.0, S * int(n_restarts) * lo.shape[0]), dtype=np.float64)
+            starts = lo + (hi - lo) * u.reshape(S, int(n_restarts), lo.shape[0])
+        st = _starts_in_box(starts, lo, hi, self.dtype)
+        paths = self.sample_paths_a(S, n_features, rng)
+        try:
+            _, f_best, _ = paths.minimize(st, lo, hi, maxeval=maxeval)
+        finally:
+            paths.release()
+        return np.asarray(f_best, dtype=np.float64)
+
+    def mes_a(self, x, ystar):
+        """Max-value entropy search at the rows of x [m, d] (FittedKernel.mes) given sampled minimum values ystar in the normalised
+        y space (sample_min_values).  MES is an entropy difference in nats: no projection applies.  Returns (mes[m] float64,
+        best): best the last index of the maximum, -1 without rows."""
+        return self.fitted.mes(np.asarray(x, dtype=self.dtype), ystar)
+
+    def maximize_mes(self, starts, bounds, ystar, maxeval=150):
+        """Bounded L-BFGS ascent of MES from every row of `starts` (the box: `bounds` = [(lo, hi)] per feature), all runs in
+        lockstep on the device model (FittedKernel.maximize_mes).  Returns (x[R, d], mes[R], nevals[R])."""
+        lo = np.array([b[0] for b in bounds], dtype=np.float64)
+        hi = np.array([b[1] for b in bounds], dtype=np.float64)
+        return self.fitted.maximize_mes(np.asarray(starts, dtype=self.dtype), lo, hi, ystar, maxeval=maxeval)
+
     # Sensitivity of the surrogate to its features (opt-in; nothing the estimator suggests by default uses it).
     def _uniform_rows(self, n_samples, rng, bounds):
         """[n_samples, d] uniform rows from rng.uniform in the unit box, or in `bounds` = [(lo, hi)] per feature."""
@@ -511,13 +551,53 @@ def acquire_by_path_thompson(model, k, rng, bounds, n_features=1024, n_restarts=
         starts = lo + (hi - lo) * u
     paths = model.sample_paths_a(k, n_features, rng, noise_draw=noise_draw)
     try:
-        st = np.asarray(starts, dtype=model.dtype)  # rounded into the box where the cast left it
-        st = np.where(st.astype(np.float64) > hi, np.nextafter(st, st.dtype.type(-np.inf)), st)
-        st = np.where(st.astype(np.float64) < lo, np.nextafter(st, st.dtype.type(np.inf)), st)
-        x, _, _ = paths.minimize(st, lo, hi, maxeval=maxeval)
+        x, _, _ = paths.minimize(_starts_in_box(starts, lo, hi, model.dtype), lo, hi, maxeval=maxeval)
     finally:
         paths.release()
     return x
+
+
+def _starts_in_box(starts, lo, hi, dtype):
+    """`starts` in the model's element type, rounded into the box [lo, hi] where the cast left it."""
+    st = np.asarray(starts, dtype=dtype)
+    st = np.where(st.astype(np.float64) > hi, np.nextafter(st, st.dtype.type(-np.inf)), st)
+    return np.where(st.astype(np.float64) < lo, np.nextafter(st, st.dtype.type(np.inf)), st)
+
+
+def acquire_by_max_value_entropy(model, k, rng, bounds, n_samples=64, n_starts=32, candidates=None, n_features=1024, n_restarts=8,
+                                 maxeval=150, grid=None, starts=None):
+    """Batch acquisition by max-value entropy search (Wang & Jegelka 2017): n_samples draws of the value of the global minimum
+    over the box (model.sample_min_values: sample paths, or joint draws at `grid`), then the points where observing tells most
+    about that value.  With `candidates` [m, n_features]: (idx[k] int64, mes[k]), the k rows of largest MES (model.mes_a), ties
+    to the LAST index as find_best_candidate_by_ei breaks them; a NaN MES raises.  Without: (x[<= k, d], mes[<= k]), the best
+    distinct end points of n_starts bounded L-BFGS ascents of MES (model.maximize_mes) from `starts` [n_starts, d] (default:
+    uniform in the box from rng, drawn after the minimum values), best first; fewer than k rows only where fewer runs ended at
+    distinct points.  The k points are chosen under ONE posterior: there is no fantasy between picks (joint MES is out of
+    scope).  Opt-in: nothing the estimator suggests by default calls it."""
+    k = int(k)
+    ystar = model.sample_min_values(n_samples, rng, bounds, n_features=n_features, n_restarts=n_restarts, maxeval=maxeval, grid=grid)
+    if candidates is not None:
+        c = np.asarray(candidates, dtype=model.dtype)
+        if c.ndim != 2:
+            raise ValueError("candidates must be [m, n_features]")
+        if not 0 <= k <= c.shape[0]:
+            raise ValueError("k must lie in [0, m]")
+        val, _ = model.mes_a(c, ystar)
+        if np.isnan(val).any():
+            raise ValueError("MES should be comparable")
+        idx = np.lexsort((np.arange(len(val)), val))[::-1][:k].astype(np.int64)  # descending MES, the later index first among equals
+        return idx, val[idx]
+    lo = np.array([b[0] for b in bounds], dtype=np.float64)
+    hi = np.array([b[1] for b in bounds], dtype=np.float64)
+    if starts is None:
+        u = np.asarray(rng.uniform(0.0, 1.0, int(n_starts) * lo.shape[0]), dtype=np.float64).reshape(int(n_starts), lo.shape[0])
+        starts = lo + (hi - lo) * u
+    x, val, _ = model.maximize_mes(_starts_in_box(starts, lo, hi, model.dtype), bounds, ystar, maxeval=maxeval)
+    picks = []
+    for r in np.lexsort((np.arange(len(val)), val))[::-1]:
+        if len(picks) < k and not any((x[r] == x[p]).all() for p in picks):
+            picks.append(int(r))
+    return x[picks], val[picks]
 
 
 def acquire_by_batch_ei(candidates, model, k, fmin, lie=None):

@@ -393,6 +393,50 @@ class FittedKernel:
         bounds = np.stack([np.asarray(lo, dtype=np.float64).reshape(-1), np.asarray(hi, dtype=np.float64).reshape(-1)], axis=1)
         return maximize_log_constrained_ei(self, [], starts, bounds, fmin_normalized, None, maxeval=maxeval)
 
+    def mes(self, x, ystar, want_grad=False, want_posterior=False):
+        """Max-value entropy search at the rows of x (hbegp_mes_*), in the normalised y space of a minimised function: the
+        information an observation is expected to give about the VALUE of the global minimum, from the sampled minimum values
+        ystar [S] (PosteriorPaths.minimize's f_best, or the row minima of sample_posterior over a grid; S <= MES_MAX_SAMPLES).
+        Returns (mes[m] float64 >= 0, best) -- best the last index of the maximum, -1 for m = 0 -- then grad[m, d] with want_grad,
+        then (mean[m], var[m]) with want_posterior: predict()'s batched numbers bit for bit (predict_with_gradient()'s with
+        want_grad).  A sigma = 0 row has mes = 0 and a zero gradient."""
+        x = _lib.as_c(np.asarray(x, dtype=self.dtype).reshape(-1, self.d), self.dtype)
+        ystar = _lib.as_c(np.asarray(ystar, dtype=np.float64).reshape(-1), np.float64)
+        m = x.shape[0]
+        val = np.zeros(m)
+        best = C.c_int(-1)
+        grad = np.zeros((m, self.d), dtype=self.dtype) if want_grad else None
+        mean = np.zeros(m, dtype=self.dtype) if want_posterior else None
+        var = np.zeros(m, dtype=self.dtype) if want_posterior else None
+        fn = getattr(_lib.load(), f"hbegp_mes_{self._sfx}")
+        _lib.check(fn(self._h, _lib.aptr(x), m, _lib.dptr(ystar), len(ystar), _lib.dptr(val), _lib.aptr(grad), C.byref(best),
+                      _lib.aptr(mean), _lib.aptr(var)))
+        out = (val, best.value)
+        if want_grad:
+            out += (grad,)
+        if want_posterior:
+            out += (mean, var)
+        return out
+
+    def maximize_mes(self, starts, lo, hi, ystar, maxeval=150):
+        """R bounded L-BFGS runs maximising mes() over the box (hbegp_maximize_mes_*), one batched gradient predict per round.
+        starts: [R, d] inside [lo, hi].  Returns (x[R, d], mes[R], nevals[R]): each run's best point, never worse than its start;
+        mes(x, ystar) reproduces the values bit for bit."""
+        starts = _lib.as_c(np.atleast_2d(starts), self.dtype)
+        assert starts.shape[1] == self.d
+        R = starts.shape[0]
+        lo = _lib.as_c(lo, np.float64)
+        hi = _lib.as_c(hi, np.float64)
+        assert lo.shape == (self.d,) and hi.shape == (self.d,)
+        ystar = _lib.as_c(np.asarray(ystar, dtype=np.float64).reshape(-1), np.float64)
+        x = np.zeros((R, self.d), dtype=self.dtype)
+        val = np.zeros(R)
+        nevals = np.zeros(R, dtype=np.int32)
+        fn = getattr(_lib.load(), f"hbegp_maximize_mes_{self._sfx}")
+        _lib.check(fn(self._h, _lib.aptr(starts), R, _lib.dptr(lo), _lib.dptr(hi), _lib.dptr(ystar), len(ystar), int(maxeval),
+                      _lib.aptr(x), _lib.dptr(val), nevals.ctypes.data_as(C.POINTER(C.c_int))))
+        return x, val, nevals
+
     def predict_cov(self, x, jitter=0.0):
         """Joint posterior at the query points (hbegp_predict_cov_*): returns (mean[m], cov[m, m]) in the normalised y space,
         cov = K** + (1e-5 + jitter) I - K*^T K^-1 K* (unclamped; its diagonal is predict()'s variance before clamping)."""

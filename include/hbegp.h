@@ -524,6 +524,49 @@ int hbegp_maximize_log_constrained_ei_f32(hbegp_model* objective, hbegp_model* c
                                           int S, const double* lo, const double* hi, double fmin_normalized, const double* limits,
                                           int maxeval, float* x_out, double* lcei_out, int* nevals_out);
 
+/* Max-value entropy search (MES: Wang & Jegelka, ICML 2017) under ONE model, for a minimised function: the information a noise-free
+ * observation at a candidate is expected to give about the VALUE of the global minimum, from S samples y*_s of that value (the
+ * f_best of hbegp_paths_minimize_*, or the row minima of hbegp_sample_posterior_* over a grid), in the model's normalised y space.
+ * The posterior N(mu, sigma^2) is the latent one of hbegp_predict_* (variance without s2, clamped at 0).  ystar[S] is always
+ * double, 1 <= S <= HBEGP_MES_MAX_SAMPLES.  With gamma_s = (mu - y*_s) / sigma clamped to +-1.7e308 and lambda = phi / Phi:
+ *   t(g)  = g lambda(g) / 2 - log Phi(g)                     t'(g) = -(lambda / 2) (1 + g^2 + g lambda)
+ *   mes   = (1/S) sum_s t(gamma_s)  >= 0                     -- lane l of a wave adds s = l, l + 64, .. in ascending s, the 64
+ *                                                               partial sums go through a fixed butterfly, then the 1/S
+ *   d mes / d mu = (1/S) sum t'(gamma_s) / sigma,    d mes / d sigma = -(1/S) sum gamma_s t'(gamma_s) / sigma
+ *   grad[j][i] = d mes / d mu * dmean[j][i] + d mes / d sigma * dvar[j][i] / (2 sigma),
+ * dmean and dvar being hbegp_predict_grad_*'s.  "sigma = 0" means !(sigma > 2.220446049250313e-16): mes = 0 and every partial is 0
+ * (a point the model is certain about carries no information).  Evaluation, fp64 for both element types, with lcei's branch points:
+ * for g > -1 the direct forms (Phi(-|g|) = erfc(|g| / sqrt 2) / 2, log Phi by log up to 0 and log1p(-Phi(-g)) above; g lambda and
+ * t' count as 0 where phi has underflowed).  For g = -a <= -1 both terms of t grow like a^2 / 2 and cancel to O(log a); with
+ * au = a sqrt(pi/2) erfcx(a / sqrt 2) and b = 1 - au:  w = a^2 b / au,  t = -w / 2 + log sqrt(2 pi) + (log a - log au),
+ * t' = -(a / au) (1 - w) / 2.  From a = 25 on, au, b / x and (au - b / x) / x (x = 1 / a^2) come from ten-term asymptotic series,
+ * w = (b / x) / au and 1 - w = x ((au - b / x) / x) / au; a^2 is never formed.  Against 60 digits the value is good to 5e-14
+ * max(1, |t|) and t' to 1e-10 relative (worst just below a = 25, where 1 - w cancels about a^4 eps); for g > 8 the value is below
+ * 1e-14 with a relative error of up to 0.5 %.  There are no atomics: a row's bits depend only on its own (mu, sigma^2, dmean, dvar)
+ * and on ystar in the order given -- not on m, on the row's position, or on whether a gradient was asked for.
+ * mes[m] (required for m > 0); grad[m*d] (may be NULL: no gradient launch); best (may be NULL): the LAST index of the maximum of mes
+ * (a NaN never wins; -1 for m = 0); mean[m], var[m] (each may be NULL): bit for bit what hbegp_predict_* returns on its batched
+ * path (m > 16), or hbegp_predict_grad_* with a gradient.  A NaN coordinate gives NaN in that row of mes and grad only.  m = 0 is
+ * a no-op with best = -1.  Calls are serialised per model, like predict.
+ * HBEGP_EINVAL, before any device call and without writing anything: a NULL model, a model of the other element type, m < 0, a NULL
+ * Xs or mes with m > 0, S < 1 or S > HBEGP_MES_MAX_SAMPLES, a NULL ystar or a ystar that is not finite.  HBEGP_ENOMEM: m beyond
+ * the device's memory. */
+#define HBEGP_MES_MAX_SAMPLES 1024 /* = HBEGP_PATHS_MAX_PATHS */
+int hbegp_mes_f64(hbegp_model* model, const double* Xs, int m, const double* ystar, int S, double* mes, double* grad, int* best,
+                  double* mean, double* var);
+int hbegp_mes_f32(hbegp_model* model, const float* Xs, int m, const double* ystar, int S, double* mes, float* grad, int* best,
+                  float* mean, float* var);
+/* R bounded L-BFGS runs maximising hbegp_mes_* over the box lo <= x <= hi, in lockstep: every round is one hbegp_mes_* with a
+ * gradient at the points of the unfinished runs.  starts[R*d] inside the box; x_out[R*d], mes_out[R]: each run's best evaluated
+ * point, never worse than its start -- hbegp_mes_* at x_out reproduces mes_out bit for bit; nevals_out[R] (may be NULL) <= maxeval.
+ * A value or a gradient component that is not finite is a failed evaluation.  Refused with HBEGP_EINVAL before any device call:
+ * everything hbegp_mes_* refuses about the model, ystar and S, and everything hbegp_maximize_ei_* refuses about R (its S), the
+ * box, the starts, maxeval and the outputs. */
+int hbegp_maximize_mes_f64(hbegp_model* model, const double* starts, int R, const double* lo, const double* hi, const double* ystar,
+                           int S, int maxeval, double* x_out, double* mes_out, int* nevals_out);
+int hbegp_maximize_mes_f32(hbegp_model* model, const float* starts, int R, const double* lo, const double* hi, const double* ystar,
+                           int S, int maxeval, float* x_out, double* mes_out, int* nevals_out);
+
 /* Sensitivity of the posterior mean mu (hbegp_predict_*'s mean, normalised y space) to each feature, from the CALLER's sample
  * matrices in the feature coordinates the model was fitted on (the RNG stays on the caller side).  Both calls evaluate the mean at
  * base rows with ONE coordinate substituted,
@@ -716,6 +759,11 @@ int hbegp_debug_cei_phases(int enable, double* phase_ms);
  * last timed hbegp_log_constrained_ei_* call -- the 1 + C predicts as above, the log-space kernel with the arg-max -- in
  * milliseconds; then enable != 0 makes this thread's later log-cEI calls timed.  A record of its own: cEI's is not touched. */
 int hbegp_debug_lcei_phases(int enable, double* phase_ms);
+/* ---- timing hook (tools/mes_bench.py): phase_ms[2] (may be NULL) receives the device time of the phases of the calling thread's
+ * last timed hbegp_mes_* call -- the predict (the uploads of the candidates and of ystar, the batched predict's launches and, with
+ * a gradient, the gradient's), the MES kernel with the arg-max -- in milliseconds; then enable != 0 makes this thread's later MES
+ * calls timed (the rounds of hbegp_maximize_mes_* too: the record holds the last one). */
+int hbegp_debug_mes_phases(int enable, double* phase_ms);
 /* ---- timing hook (tools/sens_bench.py): phase_ms[4] (may be NULL) receives the device time of the phases of the calling thread's
  * last timed hbegp_sobol_* / hbegp_main_effects_* call -- the upload (with the grid's scaling), the substituted means, the chunk and
  * row sums (both summed over the slabs), the final reduction with the downloads -- in milliseconds; then enable != 0 makes this

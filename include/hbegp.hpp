@@ -110,6 +110,13 @@ template <> struct Abi<double> {
                                          double fmin, const double* lim, int maxeval, double* x, double* v, int* ne) {
     return hbegp_maximize_log_constrained_ei_f64(o, cs, nc, st, s, lo, hi, fmin, lim, maxeval, x, v, ne);
   }
+  static int mes(hbegp_model* m, const double* xs, int cnt, const double* ys, int s, double* v, double* g, int* best, double* mean, double* var) {
+    return hbegp_mes_f64(m, xs, cnt, ys, s, v, g, best, mean, var);
+  }
+  static int maximize_mes(hbegp_model* m, const double* st, int r, const double* lo, const double* hi, const double* ys, int s, int maxeval,
+                          double* x, double* v, int* ne) {
+    return hbegp_maximize_mes_f64(m, st, r, lo, hi, ys, s, maxeval, x, v, ne);
+  }
   static int get(hbegp_model* m, double* t, double* a, double* ki) { return hbegp_model_get_f64(m, t, a, ki); }
 };
 template <> struct Abi<float> {
@@ -179,6 +186,13 @@ template <> struct Abi<float> {
   static int maximize_log_constrained_ei(hbegp_model* o, hbegp_model* const* cs, int nc, const float* st, int s, const double* lo, const double* hi,
                                          double fmin, const double* lim, int maxeval, float* x, double* v, int* ne) {
     return hbegp_maximize_log_constrained_ei_f32(o, cs, nc, st, s, lo, hi, fmin, lim, maxeval, x, v, ne);
+  }
+  static int mes(hbegp_model* m, const float* xs, int cnt, const double* ys, int s, double* v, float* g, int* best, float* mean, float* var) {
+    return hbegp_mes_f32(m, xs, cnt, ys, s, v, g, best, mean, var);
+  }
+  static int maximize_mes(hbegp_model* m, const float* st, int r, const double* lo, const double* hi, const double* ys, int s, int maxeval,
+                          float* x, double* v, int* ne) {
+    return hbegp_maximize_mes_f32(m, st, r, lo, hi, ys, s, maxeval, x, v, ne);
   }
   static int get(hbegp_model* m, double* t, float* a, float* ki) { return hbegp_model_get_f32(m, t, a, ki); }
 };
@@ -393,6 +407,22 @@ void maximize_log_constrained_ei(const FittedKernel<A>& objective, const std::ve
   for (const auto* c : constraints) cs.push_back(c ? c->handle() : nullptr);
   check(detail::Abi<A>::maximize_log_constrained_ei(objective.handle(), cs.data(), (int)cs.size(), starts, S, lo, hi, fmin, limits, maxeval,
                                                     x_out, lcei_out, nevals));
+}
+
+// Max-value entropy search at xs[m*d] under one minimised model (hbegp_mes_*): the information an observation is expected to give
+// about the value of the global minimum, from S sampled minimum values ystar[S] (normalised y space; PathsT::minimize's f_best, or
+// the row minima of sample_posterior over a grid).  mes[m] >= 0; grad[m*d], best (the last index of the maximum), mean[m], var[m]
+// may be nullptr
+template <typename A>
+void mes(const FittedKernel<A>& model, const A* xs, int m, const double* ystar, int S, double* mes_out, A* grad = nullptr,
+         int* best = nullptr, A* mean = nullptr, A* var = nullptr) {
+  check(detail::Abi<A>::mes(model.handle(), xs, m, ystar, S, mes_out, grad, best, mean, var));
+}
+// R bounded L-BFGS ascents of that MES from starts[R*d] inside [lo, hi]; x_out[R*d], mes_out[R], nevals[R] (may be nullptr)
+template <typename A>
+void maximize_mes(const FittedKernel<A>& model, const A* starts, int R, const double* lo, const double* hi, const double* ystar, int S,
+                  int maxeval, A* x_out, double* mes_out, int* nevals = nullptr) {
+  check(detail::Abi<A>::maximize_mes(model.handle(), starts, R, lo, hi, ystar, S, maxeval, x_out, mes_out, nevals));
 }
 
 // RAII owner of an hbegp_paths handle (FittedKernel::sample_paths); it keeps its model alive

@@ -203,6 +203,24 @@ extern "C" {
     ) -> c_int;
     #[allow(dead_code)]
     fn hbegp_debug_lcei_phases(enable: c_int, phase_ms: *mut c_double) -> c_int;
+    fn hbegp_mes_f64(
+        model: *mut HbegpModel, xs: *const c_double, m: c_int, ystar: *const c_double, s: c_int, mes: *mut c_double, grad: *mut c_double,
+        best: *mut c_int, mean: *mut c_double, var: *mut c_double,
+    ) -> c_int;
+    fn hbegp_maximize_mes_f64(
+        model: *mut HbegpModel, starts: *const c_double, r: c_int, lo: *const c_double, hi: *const c_double, ystar: *const c_double,
+        s: c_int, maxeval: c_int, x_out: *mut c_double, mes_out: *mut c_double, nevals_out: *mut c_int,
+    ) -> c_int;
+    fn hbegp_mes_f32(
+        model: *mut HbegpModel, xs: *const c_float, m: c_int, ystar: *const c_double, s: c_int, mes: *mut c_double, grad: *mut c_float,
+        best: *mut c_int, mean: *mut c_float, var: *mut c_float,
+    ) -> c_int;
+    fn hbegp_maximize_mes_f32(
+        model: *mut HbegpModel, starts: *const c_float, r: c_int, lo: *const c_double, hi: *const c_double, ystar: *const c_double,
+        s: c_int, maxeval: c_int, x_out: *mut c_float, mes_out: *mut c_double, nevals_out: *mut c_int,
+    ) -> c_int;
+    #[allow(dead_code)]
+    fn hbegp_debug_mes_phases(enable: c_int, phase_ms: *mut c_double) -> c_int;
     fn hbegp_noisy_ei_f64(
         model: *mut HbegpModel, xs: *const c_double, m: c_int, mb: c_int, z: *const c_double, s: c_int, jitter: c_double,
         nei: *mut c_double, best: *mut c_int, fmin_draws: *mut c_double, rho: *mut c_double, info: *mut c_int,
@@ -361,6 +379,18 @@ pub trait GpuScalar: Scalar + sealed::Sealed {
         hi: *const f64, fmin_normalized: f64, limits: *const f64, maxeval: c_int, x_out: *mut Self, cei_out: *mut f64,
         nevals_out: *mut c_int,
     ) -> c_int;
+    /// `hbegp_mes_*`
+    #[allow(clippy::too_many_arguments)]
+    unsafe fn ffi_mes(
+        model: *mut HbegpModel, xs: *const Self, m: c_int, ystar: *const f64, s: c_int, mes: *mut f64, grad: *mut Self,
+        best: *mut c_int, mean: *mut Self, var: *mut Self,
+    ) -> c_int;
+    /// `hbegp_maximize_mes_*`
+    #[allow(clippy::too_many_arguments)]
+    unsafe fn ffi_maximize_mes(
+        model: *mut HbegpModel, starts: *const Self, r: c_int, lo: *const f64, hi: *const f64, ystar: *const f64, s: c_int,
+        maxeval: c_int, x_out: *mut Self, mes_out: *mut f64, nevals_out: *mut c_int,
+    ) -> c_int;
     /// `hbegp_noisy_ei_*`
     #[allow(clippy::too_many_arguments)]
     unsafe fn ffi_noisy_ei(
@@ -474,6 +504,18 @@ impl GpuScalar for f64 {
     ) -> c_int {
         hbegp_maximize_log_constrained_ei_f64(objective, constraints, n_con, starts, s, lo, hi, fmin_normalized, limits, maxeval,
                                               x_out, cei_out, nevals_out)
+    }
+    unsafe fn ffi_mes(
+        model: *mut HbegpModel, xs: *const f64, m: c_int, ystar: *const f64, s: c_int, mes: *mut f64, grad: *mut f64,
+        best: *mut c_int, mean: *mut f64, var: *mut f64,
+    ) -> c_int {
+        hbegp_mes_f64(model, xs, m, ystar, s, mes, grad, best, mean, var)
+    }
+    unsafe fn ffi_maximize_mes(
+        model: *mut HbegpModel, starts: *const f64, r: c_int, lo: *const f64, hi: *const f64, ystar: *const f64, s: c_int,
+        maxeval: c_int, x_out: *mut f64, mes_out: *mut f64, nevals_out: *mut c_int,
+    ) -> c_int {
+        hbegp_maximize_mes_f64(model, starts, r, lo, hi, ystar, s, maxeval, x_out, mes_out, nevals_out)
     }
     unsafe fn ffi_noisy_ei(
         model: *mut HbegpModel, xs: *const f64, m: c_int, mb: c_int, z: *const f64, s: c_int, jitter: f64, nei: *mut f64,
@@ -590,6 +632,18 @@ impl GpuScalar for f32 {
     ) -> c_int {
         hbegp_maximize_log_constrained_ei_f32(objective, constraints, n_con, starts, s, lo, hi, fmin_normalized, limits, maxeval,
                                               x_out, cei_out, nevals_out)
+    }
+    unsafe fn ffi_mes(
+        model: *mut HbegpModel, xs: *const f32, m: c_int, ystar: *const f64, s: c_int, mes: *mut f64, grad: *mut f32,
+        best: *mut c_int, mean: *mut f32, var: *mut f32,
+    ) -> c_int {
+        hbegp_mes_f32(model, xs, m, ystar, s, mes, grad, best, mean, var)
+    }
+    unsafe fn ffi_maximize_mes(
+        model: *mut HbegpModel, starts: *const f32, r: c_int, lo: *const f64, hi: *const f64, ystar: *const f64, s: c_int,
+        maxeval: c_int, x_out: *mut f32, mes_out: *mut f64, nevals_out: *mut c_int,
+    ) -> c_int {
+        hbegp_maximize_mes_f32(model, starts, r, lo, hi, ystar, s, maxeval, x_out, mes_out, nevals_out)
     }
     unsafe fn ffi_noisy_ei(
         model: *mut HbegpModel, xs: *const f32, m: c_int, mb: c_int, z: *const f32, s: c_int, jitter: f64, nei: *mut f64,
@@ -1018,6 +1072,48 @@ impl<A: GpuScalar> SurrogateModelGpu<A> {
             panic!("hbegp_maximize_log_constrained_ei failed: {}", last_error());
         }
         (x_out, lcei, nevals)
+    }
+
+    /// Max-value entropy search (`hbegp_mes_*`; Wang & Jegelka 2017) at the rows of `x`, in the normalised y space of a minimised
+    /// function: the information an observation is expected to give about the VALUE of the global minimum, from the sampled minimum
+    /// values `ystar` [S] (`PosteriorPaths::minimize`'s f_best, or the row minima of `sample_posterior` over a grid; S <= 1024).
+    /// Stable where a candidate's mean lies far below a sample in units of sigma.  Returns (mes [m] >= 0, best = the last index of
+    /// its maximum, None without rows).  Opt-in.
+    pub fn mes_normalized(&self, x: ArrayView2<A>, ystar: &[f64]) -> (Vec<f64>, Option<usize>) {
+        let (m, _d) = x.dim();
+        let x = x.as_standard_layout();
+        let mut mes = vec![0.0f64; m];
+        let mut best: c_int = -1;
+        let mes_ptr = if m > 0 { mes.as_mut_ptr() } else { std::ptr::null_mut() };
+        let rc = unsafe {
+            A::ffi_mes(self.handle, x.as_ptr(), m as c_int, ystar.as_ptr(), ystar.len() as c_int, mes_ptr, std::ptr::null_mut(),
+                       &mut best, std::ptr::null_mut(), std::ptr::null_mut())
+        };
+        if rc != HBEGP_OK {
+            panic!("hbegp_mes failed: {}", last_error());
+        }
+        (mes, usize::try_from(best).ok())
+    }
+
+    /// Bounded L-BFGS ascents of `mes_normalized` from every row of `starts` inside [lo, hi] (`hbegp_maximize_mes_*`, all runs in
+    /// lockstep on the device model).  Returns (x [R, d] row-major, mes [R], evaluations [R]): each run's best point, never worse
+    /// than its start.  Opt-in.
+    pub fn maximize_mes(&self, starts: ArrayView2<A>, lo: &[f64], hi: &[f64], ystar: &[f64], maxeval: usize)
+        -> (Vec<A>, Vec<f64>, Vec<c_int>) {
+        let (r, d) = starts.dim();
+        assert!(lo.len() == d && hi.len() == d, "one bound pair per feature");
+        let starts = starts.as_standard_layout();
+        let mut x_out = vec![A::zero(); r * d];
+        let mut mes = vec![0.0f64; r];
+        let mut nevals = vec![0 as c_int; r];
+        let rc = unsafe {
+            A::ffi_maximize_mes(self.handle, starts.as_ptr(), r as c_int, lo.as_ptr(), hi.as_ptr(), ystar.as_ptr(),
+                                ystar.len() as c_int, maxeval as c_int, x_out.as_mut_ptr(), mes.as_mut_ptr(), nevals.as_mut_ptr())
+        };
+        if rc != HBEGP_OK {
+            panic!("hbegp_maximize_mes failed: {}", last_error());
+        }
+        (x_out, mes, nevals)
     }
 
     /// Noisy expected improvement over a candidate set (`hbegp_noisy_ei_*`; Letham, Karrer, Ottoni, Bakshy 2019): EI of every row

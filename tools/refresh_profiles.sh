@@ -48,3 +48,5 @@ rm -rf "$OUT/c5"
 cd "$ROOT"
 echo "[extra] log-space constrained EI beside cEI (profiles/lcei_bench.txt: prepend its header by hand)"
 python3 "$ROOT/tools/lcei_bench.py" --reps 3 > "$OUT/lcei_bench.txt" 2>&1
+echo "[extra] max-value entropy search: phases beside the host (profiles/mes_bench.txt: prepend its header by hand)"
+python3 "$ROOT/tools/mes_bench.py" --reps 3 > "$OUT/mes_bench.txt" 2>&1
