@@ -48,10 +48,11 @@ def tol_of(dtype):
 DATA_SEED = {(33, 90): 125}
 
 
-def inputs(d, n, dtype):
+def inputs(d, n, dtype, seed=None):
     """(X, y, theta) of a case -- tests/test_gpu_model_kinds.py::_extend's recipe: the same correlation range in every d; the
-    noise is 1e-2 x the amplitude in f64 and the amplitude in f32 (cond(K) <= n + 1, the regime of every f32 posterior test)."""
-    rng = np.random.default_rng(DATA_SEED.get((d, n), n + d))
+    noise is 1e-2 x the amplitude in f64 and the amplitude in f32 (cond(K) <= n + 1, the regime of every f32 posterior test).
+    `seed`: another table's data seed (tests/small_regime_cases.py) in place of this one's."""
+    rng = np.random.default_rng(DATA_SEED.get((d, n), n + d) if seed is None else seed)
     X = rng.uniform(0, 1, (n, d))
     y = np.sin(3 * X).sum(axis=1) + 0.1 * rng.standard_normal(n)
     ratio = 1e-2 if np.dtype(dtype) == np.float64 else 1.0

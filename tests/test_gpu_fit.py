@@ -305,29 +305,40 @@ def test_extend_repeats_the_fits_own_evaluation_bit_for_bit(n, dtype, n_restarts
     ex.release()
 
 
-def _replay_on_host_state_machine(tr, w, starts, maxeval, fixed_work):
+def replay_on_host_state_machine(tr, theta0, starts, lnlo, lnhi, maxeval, fixed_work):
+    """Every run of a traced fit replayed on the host state machine (hbegp_debug_lbfgs_replay), in both directions.  A run's L
+    recorded evaluations are followed by one dummy evaluation (f = +inf, a zero gradient) and passed as L + 1: the hook hands
+    out request i + 1 only if lbfgs_advance wanted another point after evaluation i, so n_requested is L + 1 exactly when the
+    host would have gone on after the device's last evaluation, and below L when it would have stopped before it.  Asserts
+    n_requested == L (the host stops exactly where the device stopped) and, in fixed-work mode, L == maxeval; returns the worst
+    |theta_host - theta_dev| / max(1, |theta|) over the L requests of every run, and the runs' lengths."""
     import ctypes as C
 
     from hbetune_rs_amd import _lib
 
     lib = _lib.load()
-    p = len(w["theta0"])
-    lnlo, lnhi = np.log(w["lo"]), np.log(w["hi"])
-    worst = 0.0
+    p = len(theta0)
+    lnlo, lnhi = np.ascontiguousarray(lnlo, dtype=np.float64), np.ascontiguousarray(lnhi, dtype=np.float64)
+    worst, lengths = 0.0, []
     for r in sorted(set(tr["run"].tolist())):
         idx = np.nonzero(tr["run"] == r)[0]
+        L = len(idx)
         th = np.ascontiguousarray(tr["theta"][idx])
-        f = np.ascontiguousarray(np.where(np.isfinite(tr["lml"][idx]), -tr["lml"][idx], np.inf))
-        g = np.ascontiguousarray(-tr["grad"][idx])
-        x0 = np.ascontiguousarray(w["theta0"] if r == 0 else starts[r - 1], dtype=np.float64)
-        req = np.zeros((len(idx), p))
+        f = np.ascontiguousarray(np.concatenate([np.where(np.isfinite(tr["lml"][idx]), -tr["lml"][idx], np.inf), [np.inf]]))
+        g = np.ascontiguousarray(np.concatenate([-tr["grad"][idx], np.zeros((1, p))]))
+        x0 = np.ascontiguousarray(theta0 if r == 0 else starts[r - 1], dtype=np.float64)
+        req = np.zeros((L + 1, p))
         nreq = C.c_int(0)
-        rc = lib.hbegp_debug_lbfgs_replay(p, _lib.dptr(x0), _lib.dptr(np.ascontiguousarray(lnlo)), _lib.dptr(np.ascontiguousarray(lnhi)), maxeval, 0,
-                                          1 if fixed_work else 0, len(idx), _lib.dptr(f), _lib.dptr(g), _lib.dptr(req), C.byref(nreq))
+        rc = lib.hbegp_debug_lbfgs_replay(p, _lib.dptr(x0), _lib.dptr(lnlo), _lib.dptr(lnhi), maxeval, 0, 1 if fixed_work else 0, L + 1,
+                                          _lib.dptr(f), _lib.dptr(g), _lib.dptr(req), C.byref(nreq))
         assert rc == 0
-        assert nreq.value == len(idx), (r, nreq.value, len(idx))  # the host would have stopped where the device stopped
-        worst = max(worst, float(np.max(np.abs(req - th) / np.maximum(1.0, np.abs(th)))))
-    return worst
+        assert nreq.value >= L, f"run {r}: the host stops after {nreq.value} evaluations, the device went on to {L}"
+        assert nreq.value == L, f"run {r}: the device stopped after {L} evaluations where the host asks for another point"
+        if fixed_work:
+            assert L == maxeval, (r, L, maxeval)
+        worst = max(worst, float(np.max(np.abs(req[:L] - th) / np.maximum(1.0, np.abs(th)))))
+        lengths.append(L)
+    return worst, lengths
 
 
 @pytest.mark.parametrize("n,cfg,dtype,fixed_work", [(100, "C2", np.float64, False), (128, "M", np.float64, True), (64, "C1", np.float64, False),
@@ -435,8 +446,9 @@ def test_persistent_fit_kernel_for_the_reference_regime(n, cfg, dtype, fixed_wor
     # (theta_i, f_i, g_i) are fed to lbfgs_advance on the host, which must ask for the very points the device went on to
     # evaluate -- start point, line-search trials, bound hits, failed evaluations (+inf), and in fixed-work mode the repeats at
     # the incumbent.  Same method, sums in another order: 1e-9 of max(1, |theta|) per step (the host's state follows its own
-    # iterates, so a difference would compound).
-    worst_step = _replay_on_host_state_machine(tr, w, starts, maxeval, fixed_work)
+    # iterates, so a difference would compound) -- and after the device's last evaluation of a run the host wants no further
+    # point: it stops exactly where the device stopped (asserted inside the helper).
+    worst_step, _ = replay_on_host_state_machine(tr, w["theta0"], starts, np.log(w["lo"]), np.log(w["hi"]), maxeval, fixed_work)
     print(f"device optimiser vs host state machine: worst |theta_dev - theta_host| / max(1, |theta|) over {len(tr['lml'])} evaluations {worst_step:.2e}")
     assert worst_step <= 1e-9
     lml_dev, n_dev = fk.lml, fk.n_evals
