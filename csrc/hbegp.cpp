@@ -2054,6 +2054,15 @@ static void predict_grad_reserve(hbegp_model* m, int mp) {
   m->dvar = m->palloc(sizeof(T) * (size_t)mp * m->d);
   m->cap_g = mp;
 }
+// What those arrays take for `rows` padded candidate rows, with or without the gradient's, as a double: a call counts its bytes with
+// this before it takes anything, so that a size far beyond the device is ENOMEM, not an overflow.
+static double padded_rows(double cnt) { return std::ceil(std::max(1.0, cnt) / NB) * NB; }
+template <typename T>
+static double predict_bytes(const hbegp_model* m, double rows, bool want_grad) {
+  const int d = m->d;
+  return (double)sizeof(T) * ((2.0 + (want_grad ? 2.0 * d : 0.0)) * rows * m->np + rows * (d + 2) + (want_grad ? 2.0 * rows * d : 0.0)) +
+         8.0 * (want_grad ? (double)pred_grad_chunks(m->n) * rows * d : 0.0);
+}
 // W = G X^T on the model stream, the candidates in m->Xs: G = dKstar/dx* (d matrices [mp x np] stacked into one operand), then the
 // triangular tile GEMM that makes Q = Kstar X^T.  Row k mp + i of W is L^-1 dk*_i / dx*_i,k.
 template <typename T>
@@ -2637,6 +2646,171 @@ static int model_maximize_ei(hbegp_model* m, const T* starts, int S, const doubl
   return lockstep_optimize<T, LbfgsState>(starts, S, d, lo, hi, lockstep_options(maxeval, true), eval, x_out, ei_out, nevals_out);
 }
 
+// ---- acquisition functions of K independent models' marginal posteriors: EHVI, cEI, log-cEI, MES -------------
+
+// the mutexes of K models, taken in the order of the models' addresses: calls that name the same models in any order cannot wait
+// for each other
+struct ModelsLock {
+  std::vector<std::unique_lock<std::mutex>> locks;
+  ModelsLock(hbegp_model* const* M, int K) {
+    std::vector<hbegp_model*> order(M, M + K);
+    std::sort(order.begin(), order.end(), std::less<hbegp_model*>());
+    locks.reserve((size_t)K);
+    for (hbegp_model* m : order) locks.emplace_back(m->mu);
+  }
+};
+
+// the events M[0]'s stream waits on, one per further model, for the length of one C call (a maximiser's rounds share them)
+struct JoinEvents {
+  std::vector<hipEvent_t> ev;
+  JoinEvents() = default;  // one model: nothing to join, no device call
+  JoinEvents(int dev, int n) {
+    HIPCHECK(hipSetDevice(dev));
+    ev.reserve((size_t)n);
+    for (int k = 0; k < n; ++k) {
+      hipEvent_t e = nullptr;
+      HIPCHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+      ev.push_back(e);
+    }
+  }
+  ~JoinEvents() {
+    for (auto& e : ev) (void)hipEventDestroy(e);
+  }
+  JoinEvents(const JoinEvents&) = delete;
+  JoinEvents& operator=(const JoinEvents&) = delete;
+};
+
+// what marginal_acquisition hands the entry point's launch, all of it on the device
+template <typename T>
+struct MarginalCall {
+  CeiArgs<T> p;          // K and the K posteriors: mean / var [cnt], dmean / dvar [cnt][d] (null without a gradient); thr is the launch's
+  int cnt, d, want_grad;
+  const double* params;  // the uploaded parameters
+  double* val;           // [n_val][cnt], the first cnt the acquisition value the arg-max runs over
+  T* grad;               // [cnt][d] (null without a gradient)
+  int* best;
+  hipStream_t s;         // M[0]'s stream
+};
+
+// An acquisition function at cnt >= 1 candidates that reads nothing of the K models (M[0] first) but each one's marginal posterior
+// at every candidate.  The call's bytes are counted before anything is taken (an m far beyond the device is ENOMEM, not an
+// overflow; what_fmt names the call over (cnt, K)), then all K mutexes are taken (ModelsLock).  Each model's upload and predict
+// launches -- hbegp_predict's batched ones, or hbegp_predict_grad's with a gradient, in their order -- go to its own stream; every
+// further model's stream records its event (join: K - 1 of them); M[0]'s stream also uploads params [n_params] (thresholds, y*;
+// may be empty) behind its candidates -- ahead of its launches: a copy behind them would wait for them, and with one model nothing
+// hides that -- waits for all the events and runs launch(MarginalCall) -- the entry point's kernel and the arg-max -- and every copy
+// back: vals (n_val = vals.size() arrays of cnt, each may be null but the first), best, grad (null: no gradient is computed) and
+// mean_out / var_out [cnt][K] (may be null): the K posteriors of a row, M[0]'s first.  Parameters and outputs are borrowed for the
+// call (CallScratch) and go back cleared; each is written in full before it is read.
+// The marks of a timed call: EHVI, whose record is each model's own interval and then the kernel's, marks around every model's
+// upload and launches on that model's stream (2 k, 2 k + 1); the others, whose record runs from before M[0]'s upload to the join and
+// then over the kernel, mark before M[0]'s upload alone.  Both then mark behind the join and behind the arg-max on M[0]'s stream.
+template <typename T, class Launch>
+static int marginal_acquisition(hbegp_model* const* M, int K, const T* Xs, int cnt, const JoinEvents& join, PhaseKind kind,
+                                const char* what_fmt, const double* params, size_t n_params, std::initializer_list<double*> vals,
+                                T* grad, int* best, T* mean_out, T* var_out, Launch&& launch) {
+  const bool want_grad = grad != nullptr;
+  const int d = M[0]->d;
+  const size_t n_val = vals.size();
+  const double rows = padded_rows((double)cnt);
+  double need = 8.0 * n_val * cnt + 8.0 * n_params + (want_grad ? (double)sizeof(T) * cnt * d : 0.0);
+  for (int k = 0; k < K; ++k) need += predict_bytes<T>(M[k], rows, want_grad);
+  if (need > 1e15 || rows > (double)(1 << 30)) {
+    char what[96];
+    snprintf(what, sizeof(what), what_fmt, cnt, K);
+    return fail(HBEGP_ENOMEM, "%s needs %.3g bytes of device memory", what, need);
+  }
+  ModelsLock lock(M, K);
+  HIPCHECK(hipSetDevice(M[0]->dev));
+  const int mp = round_up(cnt, NB);
+  for (int k = 0; k < K; ++k) {
+    if (want_grad) predict_grad_reserve<T>(M[k], mp);
+    else predict_batched_reserve<T>(M[k], mp);
+  }
+  hipStream_t s0 = M[0]->stream;
+  CallScratch ws{M[0]->dev, s0, {}};
+  MarginalCall<T> c{};
+  c.cnt = cnt;
+  c.d = d;
+  c.want_grad = want_grad ? 1 : 0;
+  c.s = s0;
+  double* dparams = n_params ? static_cast<double*>(ws.get(sizeof(double) * n_params)) : nullptr;
+  c.params = dparams;
+  c.val = static_cast<double*>(ws.get(sizeof(double) * n_val * (size_t)cnt));
+  c.best = static_cast<int*>(ws.get(sizeof(int)));
+  c.grad = want_grad ? static_cast<T*>(ws.get(sizeof(T) * (size_t)cnt * d)) : nullptr;
+  const bool per_model = kind == PH_EHVI;  // the record times every model's stream, not M[0]'s alone
+  PhaseClock clk(t_phase[kind].on, 2 * (size_t)K + 2);
+  c.p.K = K;
+  for (int k = 0; k < K; ++k) {
+    hbegp_model* m = M[k];
+    hipStream_t s = m->stream;
+    if (per_model || k == 0) clk.mark(s);
+    HIPCHECK(hipMemcpyAsync(m->Xs, Xs, sizeof(T) * (size_t)cnt * d, hipMemcpyHostToDevice, s));
+    if (k == 0 && n_params) HIPCHECK(hipMemcpyAsync(dparams, params, sizeof(double) * n_params, hipMemcpyHostToDevice, s0));
+    predict_batched_launches<T>(m, cnt, mp, true);
+    if (want_grad) predict_grad_launches<T>(m, cnt, mp, true, true);
+    CHECK_LAUNCHES();
+    if (per_model) clk.mark(s);
+    if (k > 0) HIPCHECK(hipEventRecord(join.ev[(size_t)k - 1], s));
+    c.p.mean[k] = static_cast<const T*>(m->mean);
+    c.p.var[k] = static_cast<const T*>(m->var);
+    c.p.dmean[k] = want_grad ? static_cast<const T*>(m->dmean) : nullptr;  // (not read without a gradient)
+    c.p.dvar[k] = want_grad ? static_cast<const T*>(m->dvar) : nullptr;
+  }
+  for (int k = 1; k < K; ++k) HIPCHECK(hipStreamWaitEvent(s0, join.ev[(size_t)k - 1], 0));
+  const int joined = clk.marks();
+  clk.mark(s0);
+  launch(c);
+  clk.mark(s0);
+  CHECK_LAUNCHES();
+  int hbest = -1;
+  std::vector<T> hm, hv;
+  size_t at = 0;
+  for (double* v : vals) {
+    if (v) HIPCHECK(hipMemcpyAsync(v, c.val + at * cnt, sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost, s0));
+    ++at;
+  }
+  HIPCHECK(hipMemcpyAsync(&hbest, c.best, sizeof(int), hipMemcpyDeviceToHost, s0));
+  if (want_grad) HIPCHECK(hipMemcpyAsync(grad, c.grad, sizeof(T) * (size_t)cnt * d, hipMemcpyDeviceToHost, s0));
+  if (mean_out) {
+    hm.resize((size_t)K * cnt);
+    for (int k = 0; k < K; ++k)
+      HIPCHECK(hipMemcpyAsync(hm.data() + (size_t)k * cnt, M[k]->mean, sizeof(T) * (size_t)cnt, hipMemcpyDeviceToHost, s0));
+  }
+  if (var_out) {
+    hv.resize((size_t)K * cnt);
+    for (int k = 0; k < K; ++k)
+      HIPCHECK(hipMemcpyAsync(hv.data() + (size_t)k * cnt, M[k]->var, sizeof(T) * (size_t)cnt, hipMemcpyDeviceToHost, s0));
+  }
+  HIPCHECK(hipStreamSynchronize(s0));  // behind the events: every further model's stream has finished this call's work too
+  if (best) *best = hbest;
+  for (int k = 0; k < K; ++k)
+    for (int i = 0; i < cnt; ++i) {
+      if (mean_out) mean_out[(size_t)K * i + k] = hm[(size_t)k * cnt + i];
+      if (var_out) var_out[(size_t)K * i + k] = hv[(size_t)k * cnt + i];
+    }
+  if (clk.on()) {
+    double* ms = t_phase[kind].ms;
+    if (per_model)
+      for (int k = 0; k < K; ++k) ms[k] = clk.elapsed_ms(2 * k, 2 * k + 1);
+    else ms[0] = clk.elapsed_ms(0, joined);
+    ms[per_model ? K : 1] = clk.elapsed_ms(joined, joined + 1);
+  }
+  return HBEGP_OK;
+}
+
+// S bounded L-BFGS runs on the negative of such a function in lockstep (lockstep.hpp), as model_maximize_ei: every round is ONE call
+// of rows(xs, cnt, val, gr) -- the entry point's call with a gradient: one batched gradient predict per model, then its kernel.
+// Each run returns the best point it evaluated; a value or a gradient component that is not finite is a failed evaluation (in
+// log space a row at -inf is one).
+template <typename T, class Rows>
+static int maximize_marginal(const T* starts, int S, int d, const double* lo, const double* hi, int maxeval, Rows rows, T* x_out,
+                             double* f_out, int* nevals_out) {
+  return lockstep_optimize<T, LbfgsState>(starts, S, d, lo, hi, lockstep_options(maxeval, true), finite_gradient_eval<T>(S, d, rows), x_out,
+                                          f_out, nevals_out);
+}
+
 // ---- expected hypervolume improvement of two independent objectives (hbegp_ehvi / hbegp_maximize_ehvi) ----------
 
 // The caller's front reduced to the non-dominated points strictly inside the reference box, a ascending (so b descends), as the
@@ -2667,341 +2841,52 @@ static int ehvi_thresholds(const double* front, int P, const double* ref, std::v
   return ns;
 }
 
-// EHVI at cnt >= 1 candidates.  Both models' mutexes are taken in the order of their addresses (two calls with the models in either
-// order cannot wait for each other).  Each model's predict launches -- hbegp_predict's batched ones, or hbegp_predict_grad's with a
-// gradient, in their order -- go to its own stream; the stream of objective 0 then waits for an event behind objective 1's launches
-// and runs the EHVI kernel and every copy back.  Thresholds and outputs are borrowed for the call (CallScratch) and go back cleared.
-// mean_out / var_out [cnt][2] (may be null): the two posteriors interleaved.
+// EHVI at cnt >= 1 candidates: marginal_acquisition over the two objectives' models, the thresholds its parameters
 template <typename T>
-static int model_ehvi(hbegp_model* const* M, const T* Xs, int cnt, const std::vector<double>& thr, int ns, hipEvent_t ev_join, double* ehvi,
-                      T* grad, int* best, T* mean_out, T* var_out) {
-  const bool want_grad = grad != nullptr;
-  const int d = M[0]->d;
-  // everything the call takes, counted before anything is taken: an m far beyond the device is ENOMEM, not an overflow
-  const double rows = std::ceil(std::max(1.0, (double)cnt) / NB) * NB;
-  double need = 8.0 * cnt + 16.0 * ns + (want_grad ? (double)sizeof(T) * cnt * d : 0.0);
-  for (int k = 0; k < 2; ++k)
-    need += (double)sizeof(T) * ((2.0 + (want_grad ? 2.0 * d : 0.0)) * rows * M[k]->np + rows * (d + 2) + (want_grad ? 2.0 * rows * d : 0.0)) +
-            8.0 * (want_grad ? (double)pred_grad_chunks(M[k]->n) * rows * d : 0.0);
-  if (need > 1e15 || rows > (double)(1 << 30))
-    return fail(HBEGP_ENOMEM, "EHVI at %d points needs %.3g bytes of device memory", cnt, need);
-  hbegp_model* first = M[0];
-  hbegp_model* second = M[1];
-  if (std::less<hbegp_model*>()(second, first)) std::swap(first, second);
-  std::lock_guard<std::mutex> lock_a(first->mu);
-  std::lock_guard<std::mutex> lock_b(second->mu);
-  HIPCHECK(hipSetDevice(M[0]->dev));
-  const int mp = round_up(cnt, NB);
-  for (int k = 0; k < 2; ++k) {
-    if (want_grad) predict_grad_reserve<T>(M[k], mp);
-    else predict_batched_reserve<T>(M[k], mp);
-  }
-  hipStream_t s0 = M[0]->stream, s1 = M[1]->stream;
-  CallScratch ws{M[0]->dev, s0, {}};
-  double* dthr = static_cast<double*>(ws.get(sizeof(double) * 2 * (size_t)ns));
-  double* dval = static_cast<double*>(ws.get(sizeof(double) * (size_t)cnt));
-  int* dbest = static_cast<int*>(ws.get(sizeof(int)));
-  T* dg = want_grad ? static_cast<T*>(ws.get(sizeof(T) * (size_t)cnt * d)) : nullptr;
-  PhaseClock clk(t_phase[PH_EHVI].on, 6);  // marks 2 k, 2 k + 1: around model k's predict; 4, 5: around the EHVI kernels
-  for (int k = 0; k < 2; ++k) {
-    hbegp_model* m = M[k];
-    hipStream_t s = m->stream;
-    clk.mark(s);
-    HIPCHECK(hipMemcpyAsync(m->Xs, Xs, sizeof(T) * (size_t)cnt * d, hipMemcpyHostToDevice, s));
-    predict_batched_launches<T>(m, cnt, mp, true);
-    if (want_grad) predict_grad_launches<T>(m, cnt, mp, true, true);
-    CHECK_LAUNCHES();
-    clk.mark(s);
-  }
-  HIPCHECK(hipEventRecord(ev_join, s1));
-  HIPCHECK(hipMemcpyAsync(dthr, thr.data(), sizeof(double) * 2 * (size_t)ns, hipMemcpyHostToDevice, s0));
-  HIPCHECK(hipStreamWaitEvent(s0, ev_join, 0));
-  clk.mark(s0);
-  const T* g0m = want_grad ? static_cast<const T*>(M[0]->dmean) : nullptr;  // (not read without a gradient)
-  const T* g0v = want_grad ? static_cast<const T*>(M[0]->dvar) : nullptr;
-  const T* g1m = want_grad ? static_cast<const T*>(M[1]->dmean) : nullptr;
-  const T* g1v = want_grad ? static_cast<const T*>(M[1]->dvar) : nullptr;
-  launch_ehvi<T>(static_cast<const T*>(M[0]->mean), static_cast<const T*>(M[0]->var), g0m, g0v, static_cast<const T*>(M[1]->mean),
-                 static_cast<const T*>(M[1]->var), g1m, g1v, cnt, d, dthr, ns, want_grad ? 1 : 0, dval, dg, dbest, s0);
-  clk.mark(s0);
-  CHECK_LAUNCHES();
-  int hbest = -1;
-  std::vector<T> hm, hv;
-  HIPCHECK(hipMemcpyAsync(ehvi, dval, sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost, s0));
-  HIPCHECK(hipMemcpyAsync(&hbest, dbest, sizeof(int), hipMemcpyDeviceToHost, s0));
-  if (want_grad) HIPCHECK(hipMemcpyAsync(grad, dg, sizeof(T) * (size_t)cnt * d, hipMemcpyDeviceToHost, s0));
-  if (mean_out) {
-    hm.resize(2 * (size_t)cnt);
-    for (int k = 0; k < 2; ++k)
-      HIPCHECK(hipMemcpyAsync(hm.data() + (size_t)k * cnt, M[k]->mean, sizeof(T) * (size_t)cnt, hipMemcpyDeviceToHost, s0));
-  }
-  if (var_out) {
-    hv.resize(2 * (size_t)cnt);
-    for (int k = 0; k < 2; ++k)
-      HIPCHECK(hipMemcpyAsync(hv.data() + (size_t)k * cnt, M[k]->var, sizeof(T) * (size_t)cnt, hipMemcpyDeviceToHost, s0));
-  }
-  HIPCHECK(hipStreamSynchronize(s0));  // behind the event: objective 1's stream has finished this call's work too
-  if (best) *best = hbest;
-  for (int k = 0; k < 2; ++k)
-    for (int i = 0; i < cnt; ++i) {
-      if (mean_out) mean_out[2 * (size_t)i + k] = hm[(size_t)k * cnt + i];
-      if (var_out) var_out[2 * (size_t)i + k] = hv[(size_t)k * cnt + i];
-    }
-  if (clk.on())
-    for (int i = 0; i < 3; ++i) t_phase[PH_EHVI].ms[i] = clk.elapsed_ms(2 * i, 2 * i + 1);
-  return HBEGP_OK;
-}
-
-// the event objective 0's stream waits on, for the length of one C call
-struct EhviJoin {
-  hipEvent_t ev = nullptr;
-  explicit EhviJoin(int dev) {
-    HIPCHECK(hipSetDevice(dev));
-    HIPCHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-  }
-  ~EhviJoin() {
-    if (ev) (void)hipEventDestroy(ev);
-  }
-};
-
-// S bounded L-BFGS runs on -EHVI in lockstep (lockstep.hpp), as model_maximize_ei: every round is ONE model_ehvi with a gradient
-// (one batched gradient predict per model, then the EHVI kernel).  Each run returns the best point it evaluated; a value or a
-// gradient component that is not finite is a failed evaluation.
-template <typename T>
-static int model_maximize_ehvi(hbegp_model* const* M, const T* starts, int S, const double* lo, const double* hi,
-                               const std::vector<double>& thr, int ns, int maxeval, T* x_out, double* ehvi_out, int* nevals_out) {
-  const int d = M[0]->d;
-  EhviJoin join(M[0]->dev);
-  std::vector<T> gr((size_t)S * d);
-  auto eval = [&](const T* xs, const int*, int cnt, double* val, double* grad, char* ok) {
-    const int rc = model_ehvi<T>(M, xs, cnt, thr, ns, join.ev, val, gr.data(), nullptr, nullptr, nullptr);
-    if (rc != HBEGP_OK) return rc;
-    for (int i = 0; i < cnt; ++i) {
-      ok[i] = std::isfinite(val[i]);
-      for (int k = 0; k < d; ++k) {
-        grad[(size_t)i * d + k] = (double)gr[(size_t)i * d + k];
-        ok[i] = ok[i] && std::isfinite(grad[(size_t)i * d + k]);
-      }
-    }
-    return (int)HBEGP_OK;
-  };
-  return lockstep_optimize<T, LbfgsState>(starts, S, d, lo, hi, lockstep_options(maxeval, true), eval, x_out, ehvi_out, nevals_out);
+static int model_ehvi(hbegp_model* const* M, const T* Xs, int cnt, const std::vector<double>& thr, int ns, const JoinEvents& join,
+                      double* ehvi, T* grad, int* best, T* mean_out, T* var_out) {
+  return marginal_acquisition<T>(M, 2, Xs, cnt, join, PH_EHVI, "EHVI at %d points", thr.data(), 2 * (size_t)ns, {ehvi}, grad, best, mean_out,
+                                 var_out, [&](const MarginalCall<T>& c) {
+                                   launch_ehvi<T>(c.p.mean[0], c.p.var[0], c.p.dmean[0], c.p.dvar[0], c.p.mean[1], c.p.var[1], c.p.dmean[1],
+                                                  c.p.dvar[1], cnt, c.d, c.params, ns, c.want_grad, c.val, c.grad, c.best, c.s);
+                                 });
 }
 
 // ---- constrained expected improvement over an objective and C constraint models (hbegp_constrained_ei /
 // hbegp_maximize_constrained_ei) ----------------------------------------------------------------------------
 
-// the events the objective's stream waits on, one per constraint model, for the length of one C call
-struct CeiJoin {
-  std::vector<hipEvent_t> ev;
-  CeiJoin(int dev, int n_con) {
-    HIPCHECK(hipSetDevice(dev));
-    ev.reserve((size_t)n_con);
-    for (int k = 0; k < n_con; ++k) {
-      hipEvent_t e = nullptr;
-      HIPCHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      ev.push_back(e);
-    }
-  }
-  ~CeiJoin() {
-    for (auto& e : ev) (void)hipEventDestroy(e);
-  }
-  CeiJoin(const CeiJoin&) = delete;
-  CeiJoin& operator=(const CeiJoin&) = delete;
-};
-
-// cEI at cnt >= 1 candidates under K = 1 + C models, M[0] the objective: model_ehvi's call pattern over a variable number of
-// models.  All K mutexes are taken in the order of the models' addresses (calls that name the same models in any order cannot wait
-// for each other).  Each model's upload and predict launches -- hbegp_predict's batched ones, or hbegp_predict_grad's with a
-// gradient, in their order -- go to its own stream; every constraint's stream records its own event, the objective's stream waits
-// for all of them and runs the cEI kernel, the arg-max and every copy back.  thr[0] = fmin, thr[k] = limits[k - 1] travel in the
-// kernel's arguments; the outputs are borrowed for the call (CallScratch) and go back cleared.  mean_out / var_out [cnt][K] (may be
-// null): the K posteriors of a row, the objective first.  log_space (hbegp_log_constrained_ei) changes the
-// kernel that follows the join -- lcei_kernel: cei / ei / pof receive lcei / lei / lpof -- and the phase record, nothing else.
+// cEI at cnt >= 1 candidates under K = 1 + C models, M[0] the objective: marginal_acquisition without parameters -- thr[0] = fmin,
+// thr[k] = limits[k - 1] travel in the kernel's arguments -- and with three values, cei | ei | pof.  log_space
+// (hbegp_log_constrained_ei) changes the kernel that follows the join -- lcei_kernel: cei / ei / pof receive
+// lcei / lei / lpof -- and the phase record, nothing else.
 template <typename T>
-static int model_constrained_ei(hbegp_model* const* M, int K, const T* Xs, int cnt, const double* thr, const CeiJoin& join, double* cei,
-                                T* grad, int* best, double* ei, double* pof, T* mean_out, T* var_out, bool log_space = false) {
-  const PhaseKind kind = log_space ? PH_LCEI : PH_CEI;
-  const bool want_grad = grad != nullptr;
-  const int d = M[0]->d;
-  // everything the call takes, counted before anything is taken: an m far beyond the device is ENOMEM, not an overflow
-  const double rows = std::ceil(std::max(1.0, (double)cnt) / NB) * NB;
-  double need = 3.0 * 8.0 * cnt + (want_grad ? (double)sizeof(T) * cnt * d : 0.0);
-  for (int k = 0; k < K; ++k)
-    need += (double)sizeof(T) * ((2.0 + (want_grad ? 2.0 * d : 0.0)) * rows * M[k]->np + rows * (d + 2) + (want_grad ? 2.0 * rows * d : 0.0)) +
-            8.0 * (want_grad ? (double)pred_grad_chunks(M[k]->n) * rows * d : 0.0);
-  if (need > 1e15 || rows > (double)(1 << 30))
-    return fail(HBEGP_ENOMEM, "constrained EI at %d points under %d models needs %.3g bytes of device memory", cnt, K, need);
-  std::vector<hbegp_model*> order(M, M + K);
-  std::sort(order.begin(), order.end(), std::less<hbegp_model*>());
-  std::vector<std::unique_lock<std::mutex>> locks;
-  locks.reserve((size_t)K);
-  for (hbegp_model* m : order) locks.emplace_back(m->mu);
-  HIPCHECK(hipSetDevice(M[0]->dev));
-  const int mp = round_up(cnt, NB);
-  for (int k = 0; k < K; ++k) {
-    if (want_grad) predict_grad_reserve<T>(M[k], mp);
-    else predict_batched_reserve<T>(M[k], mp);
-  }
-  hipStream_t s0 = M[0]->stream;
-  CallScratch ws{M[0]->dev, s0, {}};
-  double* dval = static_cast<double*>(ws.get(sizeof(double) * 3 * (size_t)cnt));  // cei | ei | pof
-  int* dbest = static_cast<int*>(ws.get(sizeof(int)));
-  T* dg = want_grad ? static_cast<T*>(ws.get(sizeof(T) * (size_t)cnt * d)) : nullptr;
-  PhaseClock clk(t_phase[kind].on, 3);  // all on the objective's stream: before its upload, behind the join, behind the arg-max
-  clk.mark(s0);
-  for (int k = 0; k < K; ++k) {
-    hbegp_model* m = M[k];
-    hipStream_t s = m->stream;
-    HIPCHECK(hipMemcpyAsync(m->Xs, Xs, sizeof(T) * (size_t)cnt * d, hipMemcpyHostToDevice, s));
-    predict_batched_launches<T>(m, cnt, mp, true);
-    if (want_grad) predict_grad_launches<T>(m, cnt, mp, true, true);
-    CHECK_LAUNCHES();
-    if (k > 0) HIPCHECK(hipEventRecord(join.ev[(size_t)k - 1], s));
-  }
-  for (int k = 1; k < K; ++k) HIPCHECK(hipStreamWaitEvent(s0, join.ev[(size_t)k - 1], 0));
-  clk.mark(s0);
-  CeiArgs<T> a{};
-  a.K = K;
-  for (int k = 0; k < K; ++k) {
-    a.mean[k] = static_cast<const T*>(M[k]->mean);
-    a.var[k] = static_cast<const T*>(M[k]->var);
-    a.dmean[k] = want_grad ? static_cast<const T*>(M[k]->dmean) : nullptr;  // (not read without a gradient)
-    a.dvar[k] = want_grad ? static_cast<const T*>(M[k]->dvar) : nullptr;
-    a.thr[k] = thr[k];
-  }
-  if (log_space) launch_lcei<T>(a, cnt, d, want_grad ? 1 : 0, dval, dval + cnt, dval + 2 * (size_t)cnt, dg, dbest, s0);
-  else launch_cei<T>(a, cnt, d, want_grad ? 1 : 0, dval, dval + cnt, dval + 2 * (size_t)cnt, dg, dbest, s0);
-  clk.mark(s0);
-  CHECK_LAUNCHES();
-  int hbest = -1;
-  std::vector<T> hm, hv;
-  HIPCHECK(hipMemcpyAsync(cei, dval, sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost, s0));
-  if (ei) HIPCHECK(hipMemcpyAsync(ei, dval + cnt, sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost, s0));
-  if (pof) HIPCHECK(hipMemcpyAsync(pof, dval + 2 * (size_t)cnt, sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost, s0));
-  HIPCHECK(hipMemcpyAsync(&hbest, dbest, sizeof(int), hipMemcpyDeviceToHost, s0));
-  if (want_grad) HIPCHECK(hipMemcpyAsync(grad, dg, sizeof(T) * (size_t)cnt * d, hipMemcpyDeviceToHost, s0));
-  if (mean_out) {
-    hm.resize((size_t)K * cnt);
-    for (int k = 0; k < K; ++k)
-      HIPCHECK(hipMemcpyAsync(hm.data() + (size_t)k * cnt, M[k]->mean, sizeof(T) * (size_t)cnt, hipMemcpyDeviceToHost, s0));
-  }
-  if (var_out) {
-    hv.resize((size_t)K * cnt);
-    for (int k = 0; k < K; ++k)
-      HIPCHECK(hipMemcpyAsync(hv.data() + (size_t)k * cnt, M[k]->var, sizeof(T) * (size_t)cnt, hipMemcpyDeviceToHost, s0));
-  }
-  HIPCHECK(hipStreamSynchronize(s0));  // behind the events: every constraint's stream has finished this call's work too
-  if (best) *best = hbest;
-  for (int k = 0; k < K; ++k)
-    for (int i = 0; i < cnt; ++i) {
-      if (mean_out) mean_out[(size_t)K * i + k] = hm[(size_t)k * cnt + i];
-      if (var_out) var_out[(size_t)K * i + k] = hv[(size_t)k * cnt + i];
-    }
-  clk.store(kind, 2);
-  return HBEGP_OK;
-}
-
-// S bounded L-BFGS runs on -cEI in lockstep (lockstep.hpp), as model_maximize_ehvi: every round is ONE model_constrained_ei with a
-// gradient (one batched gradient predict per model, then the cEI kernel).  Each run returns the best point it evaluated; a value or
-// a gradient component that is not finite is a failed evaluation (in log space a row at -inf is one).
-template <typename T>
-static int model_maximize_constrained_ei(hbegp_model* const* M, int K, const T* starts, int S, const double* lo, const double* hi,
-                                         const double* thr, int maxeval, T* x_out, double* cei_out, int* nevals_out,
-                                         bool log_space = false) {
-  const int d = M[0]->d;
-  CeiJoin join(M[0]->dev, K - 1);
-  std::vector<T> gr((size_t)S * d);
-  auto eval = [&](const T* xs, const int*, int cnt, double* val, double* grad, char* ok) {
-    const int rc = model_constrained_ei<T>(M, K, xs, cnt, thr, join, val, gr.data(), nullptr, nullptr, nullptr, nullptr, nullptr, log_space);
-    if (rc != HBEGP_OK) return rc;
-    for (int i = 0; i < cnt; ++i) {
-      ok[i] = std::isfinite(val[i]);
-      for (int k = 0; k < d; ++k) {
-        grad[(size_t)i * d + k] = (double)gr[(size_t)i * d + k];
-        ok[i] = ok[i] && std::isfinite(grad[(size_t)i * d + k]);
-      }
-    }
-    return (int)HBEGP_OK;
-  };
-  return lockstep_optimize<T, LbfgsState>(starts, S, d, lo, hi, lockstep_options(maxeval, true), eval, x_out, cei_out, nevals_out);
+static int model_constrained_ei(hbegp_model* const* M, int K, const T* Xs, int cnt, const double* thr, const JoinEvents& join, double* cei,
+                                T* grad, int* best, double* ei, double* pof, T* mean_out, T* var_out, bool log_space) {
+  return marginal_acquisition<T>(M, K, Xs, cnt, join, log_space ? PH_LCEI : PH_CEI, "constrained EI at %d points under %d models", nullptr, 0,
+                                 {cei, ei, pof}, grad, best, mean_out, var_out, [&](const MarginalCall<T>& c) {
+                                   CeiArgs<T> a = c.p;
+                                   std::copy(thr, thr + K, a.thr);
+                                   double* v = c.val;
+                                   if (log_space) launch_lcei<T>(a, cnt, c.d, c.want_grad, v, v + cnt, v + 2 * (size_t)cnt, c.grad, c.best, c.s);
+                                   else launch_cei<T>(a, cnt, c.d, c.want_grad, v, v + cnt, v + 2 * (size_t)cnt, c.grad, c.best, c.s);
+                                 });
 }
 
 // ---- max-value entropy search (hbegp_mes / hbegp_maximize_mes) ----------------------------------------------
 
-// MES at cnt >= 1 candidates under ONE model and S sampled minimum values: the candidates' and y*'s uploads, the batched predict's
-// launches (hbegp_predict's, or hbegp_predict_grad's with a gradient, in their order), then mes_kernel and the arg-max, all on the
-// model's stream under the model's mutex.  The outputs and y* are borrowed for the call (CallScratch) and go back cleared; each is
-// written in full before it is read: y* by its upload, mes [cnt] and the gradient [cnt][d] by mes_kernel, best by the arg-max.
+// MES at cnt >= 1 candidates under ONE model and S sampled minimum values: marginal_acquisition over that model (nothing to join:
+// all of it runs on the model's stream under the model's mutex), y* its parameters
 template <typename T>
 static int model_mes(hbegp_model* m, const T* Xs, int cnt, const double* ystar, int S, double* mes, T* grad, int* best, T* mean_out,
                      T* var_out) {
-  const bool want_grad = grad != nullptr;
-  const int d = m->d;
-  // everything the call takes, counted before anything is taken: an m far beyond the device is ENOMEM, not an overflow
-  const double rows = std::ceil(std::max(1.0, (double)cnt) / NB) * NB;
-  const double need = 8.0 * cnt + 8.0 * S + (want_grad ? (double)sizeof(T) * cnt * d : 0.0) +
-                      (double)sizeof(T) * ((2.0 + (want_grad ? 2.0 * d : 0.0)) * rows * m->np + rows * (d + 2) + (want_grad ? 2.0 * rows * d : 0.0)) +
-                      8.0 * (want_grad ? (double)pred_grad_chunks(m->n) * rows * d : 0.0);
-  if (need > 1e15 || rows > (double)(1 << 30))
-    return fail(HBEGP_ENOMEM, "max-value entropy search at %d points needs %.3g bytes of device memory", cnt, need);
-  std::lock_guard<std::mutex> lock(m->mu);
-  HIPCHECK(hipSetDevice(m->dev));
-  const int mp = round_up(cnt, NB);
-  if (want_grad) predict_grad_reserve<T>(m, mp);
-  else predict_batched_reserve<T>(m, mp);
-  hipStream_t s = m->stream;
-  CallScratch ws{m->dev, s, {}};
-  double* dval = static_cast<double*>(ws.get(sizeof(double) * (size_t)cnt));
-  double* dys = static_cast<double*>(ws.get(sizeof(double) * (size_t)S));
-  int* dbest = static_cast<int*>(ws.get(sizeof(int)));
-  T* dg = want_grad ? static_cast<T*>(ws.get(sizeof(T) * (size_t)cnt * d)) : nullptr;
-  PhaseClock clk(t_phase[PH_MES].on, 3);  // before the uploads, behind the predict's launches, behind the arg-max
-  clk.mark(s);
-  HIPCHECK(hipMemcpyAsync(m->Xs, Xs, sizeof(T) * (size_t)cnt * d, hipMemcpyHostToDevice, s));
-  HIPCHECK(hipMemcpyAsync(dys, ystar, sizeof(double) * (size_t)S, hipMemcpyHostToDevice, s));
-  predict_batched_launches<T>(m, cnt, mp, true);
-  if (want_grad) predict_grad_launches<T>(m, cnt, mp, true, true);
-  CHECK_LAUNCHES();
-  clk.mark(s);
-  launch_mes<T>(static_cast<const T*>(m->mean), static_cast<const T*>(m->var), want_grad ? static_cast<const T*>(m->dmean) : nullptr,
-                want_grad ? static_cast<const T*>(m->dvar) : nullptr, cnt, d, dys, S, want_grad ? 1 : 0, dval, dg, dbest, s);
-  clk.mark(s);
-  CHECK_LAUNCHES();
-  int hbest = -1;
-  HIPCHECK(hipMemcpyAsync(mes, dval, sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost, s));
-  HIPCHECK(hipMemcpyAsync(&hbest, dbest, sizeof(int), hipMemcpyDeviceToHost, s));
-  if (want_grad) HIPCHECK(hipMemcpyAsync(grad, dg, sizeof(T) * (size_t)cnt * d, hipMemcpyDeviceToHost, s));
-  if (mean_out) HIPCHECK(hipMemcpyAsync(mean_out, m->mean, sizeof(T) * (size_t)cnt, hipMemcpyDeviceToHost, s));
-  if (var_out) HIPCHECK(hipMemcpyAsync(var_out, m->var, sizeof(T) * (size_t)cnt, hipMemcpyDeviceToHost, s));
-  HIPCHECK(hipStreamSynchronize(s));
-  if (best) *best = hbest;
-  clk.store(PH_MES, 2);
-  return HBEGP_OK;
+  const JoinEvents none;
+  return marginal_acquisition<T>(&m, 1, Xs, cnt, none, PH_MES, "max-value entropy search at %d points", ystar, (size_t)S, {mes}, grad, best,
+                                 mean_out, var_out, [&](const MarginalCall<T>& c) {
+                                   launch_mes<T>(c.p.mean[0], c.p.var[0], c.p.dmean[0], c.p.dvar[0], cnt, c.d, c.params, S, c.want_grad, c.val,
+                                                 c.grad, c.best, c.s);
+                                 });
 }
 
-// R bounded L-BFGS runs on -MES in lockstep (lockstep.hpp), as model_maximize_constrained_ei: every round is ONE model_mes with a
-// gradient.  Each run returns the best point it evaluated; a value or a gradient component that is not finite is a failed
-// evaluation.
-template <typename T>
-static int model_maximize_mes(hbegp_model* m, const T* starts, int R, const double* lo, const double* hi, const double* ystar, int S,
-                              int maxeval, T* x_out, double* mes_out, int* nevals_out) {
-  const int d = m->d;
-  std::vector<T> gr((size_t)R * d);
-  auto eval = [&](const T* xs, const int*, int cnt, double* val, double* grad, char* ok) {
-    const int rc = model_mes<T>(m, xs, cnt, ystar, S, val, gr.data(), nullptr, nullptr, nullptr);
-    if (rc != HBEGP_OK) return rc;
-    for (int i = 0; i < cnt; ++i) {
-      ok[i] = std::isfinite(val[i]);
-      for (int k = 0; k < d; ++k) {
-        grad[(size_t)i * d + k] = (double)gr[(size_t)i * d + k];
-        ok[i] = ok[i] && std::isfinite(grad[(size_t)i * d + k]);
-      }
-    }
-    return (int)HBEGP_OK;
-  };
-  return lockstep_optimize<T, LbfgsState>(starts, R, d, lo, hi, lockstep_options(maxeval, true), eval, x_out, mes_out, nevals_out);
-}
 
 // Batch expected improvement by Monte Carlo (hbegp_qei) for B batches of q points: the B q points go through the batched predict's
 // launches (Kstar, mean, Q) and, with a gradient, the gradient's (dmean; G and W = G X^T), in the order hbegp_predict_grad issues
@@ -3015,9 +2900,8 @@ static int model_qei(hbegp_model* m, const T* Xb, int B, int q, const T* z, int 
   const bool want_grad = grad != nullptr;
   const int d = m->d;
   // everything the call borrows, counted before anything is taken: a B far beyond the device is ENOMEM, not an overflow
-  const double rows = round_up(std::max(1.0, (double)B * q), (double)NB);
-  const double need = (double)sizeof(T) * ((2.0 + (want_grad ? 2.0 * d : 0.0)) * rows * m->np + (double)S * q + rows * (d + 2)) +
-                      8.0 * (want_grad ? (double)pred_grad_chunks(m->n) * rows * d : 0.0) + 12.0 * B;
+  const double rows = padded_rows((double)B * q);
+  const double need = predict_bytes<T>(m, rows, want_grad) + (double)sizeof(T) * S * q + 12.0 * B;
   if (need > 1e15 || rows > (double)(1 << 30))
     return fail(HBEGP_ENOMEM, "qEI of %d batches of %d points needs %.3g bytes of device memory", B, q, need);
   const int cnt = B * q;
@@ -4658,8 +4542,8 @@ static int do_ehvi(hbegp_model* const* models, int n_obj, const T* Xs, int m, co
   GUARD_BEGIN
   std::vector<double> thr;
   const int ns = ehvi_thresholds(front, P, ref, &thr);
-  EhviJoin join(models[0]->dev);
-  return model_ehvi<T>(models, Xs, m, thr, ns, join.ev, ehvi, grad, best, mean, var);
+  JoinEvents join(models[0]->dev, 1);
+  return model_ehvi<T>(models, Xs, m, thr, ns, join, ehvi, grad, best, mean, var);
   GUARD_END
 }
 template <typename T>
@@ -4671,7 +4555,11 @@ static int do_maximize_ehvi(hbegp_model* const* models, int n_obj, const T* star
   GUARD_BEGIN
   std::vector<double> thr;
   const int ns = ehvi_thresholds(front, P, ref, &thr);
-  return model_maximize_ehvi<T>(models, starts, S, lo, hi, thr, ns, maxeval, x_out, ehvi_out, nevals_out);
+  JoinEvents join(models[0]->dev, 1);
+  return maximize_marginal<T>(
+      starts, S, models[0]->d, lo, hi, maxeval,
+      [&](const T* xs, int cnt, double* val, T* gr) { return model_ehvi<T>(models, xs, cnt, thr, ns, join, val, gr, nullptr, nullptr, nullptr); },
+      x_out, ehvi_out, nevals_out);
   GUARD_END
 }
 extern "C" {
@@ -4739,7 +4627,7 @@ static int do_cei(hbegp_model* objective, hbegp_model* const* constraints, int n
   if (m > 0 && (!Xs || !cei)) return fail(HBEGP_EINVAL, log_space ? "Xs/lcei is NULL" : "Xs/cei is NULL");
   if (best) *best = -1;
   if (m == 0) return HBEGP_OK;
-  CeiJoin join(objective->dev, n_con);
+  JoinEvents join(objective->dev, n_con);
   return model_constrained_ei<T>(M.data(), 1 + n_con, Xs, m, thr.data(), join, cei, grad, best, ei, pof, mean, var, log_space);
   GUARD_END
 }
@@ -4753,8 +4641,14 @@ static int do_maximize_cei(hbegp_model* objective, hbegp_model* const* constrain
   std::vector<double> thr;
   if (int rc = check_cei_models<T>(objective, constraints, n_con, fmin, limits, &M, &thr)) return rc;
   if (int rc = check_maximize_ei<T>(objective, starts, S, lo, hi, 0.0, maxeval, x_out, cei_out)) return rc;
-  return model_maximize_constrained_ei<T>(M.data(), 1 + n_con, starts, S, lo, hi, thr.data(), maxeval, x_out, cei_out, nevals_out,
-                                          log_space);
+  JoinEvents join(objective->dev, n_con);
+  return maximize_marginal<T>(
+      starts, S, objective->d, lo, hi, maxeval,
+      [&](const T* xs, int cnt, double* val, T* gr) {
+        return model_constrained_ei<T>(M.data(), 1 + n_con, xs, cnt, thr.data(), join, val, gr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                       log_space);
+      },
+      x_out, cei_out, nevals_out);
   GUARD_END
 }
 extern "C" {
@@ -4835,7 +4729,10 @@ static int do_maximize_mes(hbegp_model* model, const T* starts, int R, const dou
   if (int rc = check_mes<T>(model, ystar, S)) return rc;
   if (int rc = check_maximize_ei<T>(model, starts, R, lo, hi, 0.0, maxeval, x_out, mes_out)) return rc;
   GUARD_BEGIN
-  return model_maximize_mes<T>(model, starts, R, lo, hi, ystar, S, maxeval, x_out, mes_out, nevals_out);
+  return maximize_marginal<T>(
+      starts, R, model->d, lo, hi, maxeval,
+      [&](const T* xs, int cnt, double* val, T* gr) { return model_mes<T>(model, xs, cnt, ystar, S, val, gr, nullptr, nullptr, nullptr); }, x_out,
+      mes_out, nevals_out);
   GUARD_END
 }
 extern "C" {

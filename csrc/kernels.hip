@@ -4498,7 +4498,9 @@ __device__ __noinline__ EhviG ehvi_g(double t, double mu, double sd) {
   return r;
 }
 
-__device__ __forceinline__ double ehvi_wave_sum(double v) {
+// the sum over the 64 lanes through one xor butterfly, the result in every lane: a fixed tree, so every lane ends with the same bits
+// (ehvi_kernel, mes_kernel)
+__device__ __forceinline__ double wave_xor_sum(double v) {
 #pragma unroll
   for (int off = 1; off < 64; off <<= 1) v += __shfl_xor(v, off, 64);
   return v;
@@ -4554,11 +4556,11 @@ __global__ void __launch_bounds__(64 * EHVI_WAVES) ehvi_kernel(const T* __restri
       s4 += dg * h.pdf;                     // d/dsigma_2
     }
   }
-  s0 = ehvi_wave_sum(s0);
-  s1 = ehvi_wave_sum(s1);
-  s2 = ehvi_wave_sum(s2);
-  s3 = ehvi_wave_sum(s3);
-  s4 = ehvi_wave_sum(s4);
+  s0 = wave_xor_sum(s0);
+  s1 = wave_xor_sum(s1);
+  s2 = wave_xor_sum(s2);
+  s3 = wave_xor_sum(s3);
+  s4 = wave_xor_sum(s4);
   const double nan = __longlong_as_double(0x7ff8000000000000LL);
   if (lane == 0) ehvi[j] = bad ? nan : s0;
   if (want_grad && lane < d) {
@@ -4573,9 +4575,9 @@ __global__ void __launch_bounds__(64 * EHVI_WAVES) ehvi_kernel(const T* __restri
   }
 }
 
-// best = the LAST index of the maximum of v[0 .. m) through a fixed LDS tree (kg_epilogue_kernel's rule); a NaN never wins,
-// -1 where no entry is a number
-__global__ void __launch_bounds__(BSEL_THREADS) ehvi_best_kernel(const double* __restrict__ v, int m, int* __restrict__ res) {
+// The arg-max of the marginal acquisition functions (EHVI, cEI, log-cEI, MES): best = the LAST index of the maximum of v[0 .. m)
+// through a fixed LDS tree (kg_epilogue_kernel's rule); a NaN never wins, -1 where no entry is a number
+__global__ void __launch_bounds__(BSEL_THREADS) argmax_last_kernel(const double* __restrict__ v, int m, int* __restrict__ res) {
   __shared__ double sv[BSEL_THREADS];
   __shared__ int si[BSEL_THREADS];
   const int tid = threadIdx.x;
@@ -4599,6 +4601,9 @@ __global__ void __launch_bounds__(BSEL_THREADS) ehvi_best_kernel(const double* _
   }
   if (tid == 0) res[0] = si[0];
 }
+static void launch_argmax_last(const double* v, int m, int* best, hipStream_t s) {
+  hipLaunchKernelGGL(argmax_last_kernel, dim3(1), dim3(BSEL_THREADS), 0, s, v, m, best);
+}
 
 template <typename T>
 void launch_ehvi(const T* mean1, const T* var1, const T* dmean1, const T* dvar1, const T* mean2, const T* var2, const T* dmean2,
@@ -4611,7 +4616,7 @@ void launch_ehvi(const T* mean1, const T* var1, const T* dmean1, const T* dvar1,
   else
     hipLaunchKernelGGL((ehvi_kernel<T, false>), grid, block, 0, s, mean1, var1, dmean1, dvar1, mean2, var2, dmean2, dvar2, m, d, thr, ns,
                        want_grad, ehvi, grad);
-  hipLaunchKernelGGL(ehvi_best_kernel, dim3(1), dim3(BSEL_THREADS), 0, s, ehvi, m, best);
+  launch_argmax_last(ehvi, m, best, s);
 }
 template void launch_ehvi<double>(const double*, const double*, const double*, const double*, const double*, const double*, const double*,
                                   const double*, int, int, const double*, int, int, double*, double*, int*, hipStream_t);
@@ -4706,7 +4711,7 @@ void launch_cei(const CeiArgs<T>& a, int m, int d, int want_grad, double* cei, d
                 hipStream_t s) {
   const dim3 grid((unsigned)((m + CEI_WAVES - 1) / CEI_WAVES)), block(64 * CEI_WAVES);
   hipLaunchKernelGGL((cei_kernel<T>), grid, block, 0, s, a, m, d, want_grad, cei, ei, pof, grad);
-  hipLaunchKernelGGL(ehvi_best_kernel, dim3(1), dim3(BSEL_THREADS), 0, s, cei, m, best);
+  launch_argmax_last(cei, m, best, s);
 }
 template void launch_cei<double>(const CeiArgs<double>&, int, int, int, double*, double*, double*, double*, int*, hipStream_t);
 template void launch_cei<float>(const CeiArgs<float>&, int, int, int, double*, double*, double*, float*, int*, hipStream_t);
@@ -4733,6 +4738,25 @@ constexpr double LCEI_SERIES_A = 25.0;
 struct LceiTerm {
   double v, pm, ps;  // the log-term and its partials w.r.t. mu and sigma
 };
+// The Mills-ratio pieces at a >= 1 for lcei_term and mes_term: au = a u and bx = b / x.  Below the switch point au comes from erfcx
+// and b itself sits in bx with x = 1; from there on x = 1 / a^2 and both come from the series.
+struct MillsPieces {
+  double x, au, bx;
+};
+__device__ __forceinline__ MillsPieces mills_pieces(double a) {
+  MillsPieces r;
+  r.x = 1.0;
+  if (a < LCEI_SERIES_A) {
+    r.au = a * (1.2533141373155003 * erfcx(a / 1.4142135623730951));
+    r.bx = 1.0 - r.au;
+  } else {
+    r.x = 1.0 / a / a;  // (a * a may overflow where 1 / a / a only underflows)
+    const double x = r.x;
+    r.au = 1.0 + x * (-1.0 + x * (3.0 + x * (-15.0 + x * (105.0 + x * (-945.0 + x * (10395.0 + x * (-135135.0 + x * (2027025.0 + x * -34459425.0))))))));
+    r.bx = 1.0 + x * (-3.0 + x * (15.0 + x * (-105.0 + x * (945.0 + x * (-10395.0 + x * (135135.0 + x * (-2027025.0 + x * (34459425.0 + x * -654729075.0))))))));
+  }
+  return r;
+}
 // not inlined: erfcx's, log's and exp's fp64 coefficients, once per lane
 __device__ __noinline__ LceiTerm lcei_term(double t, double mu, double sd, int objective) {
   const double inf = __longlong_as_double(0x7ff0000000000000LL);
@@ -4768,17 +4792,8 @@ __device__ __noinline__ LceiTerm lcei_term(double t, double mu, double sd, int o
     }
   } else {
     const double a = -z;
-    double au, bx;  // a u and b / x; below the switch point b itself sits in bx with x = 1
-    double x = 1.0;
-    if (a < LCEI_SERIES_A) {
-      au = a * (1.2533141373155003 * erfcx(a / 1.4142135623730951));
-      bx = 1.0 - au;
-    } else {
-      x = 1.0 / a / a;  // (a * a may overflow where 1 / a / a only underflows)
-      au = 1.0 + x * (-1.0 + x * (3.0 + x * (-15.0 + x * (105.0 + x * (-945.0 + x * (10395.0 + x * (-135135.0 + x * (2027025.0 + x * -34459425.0))))))));
-      bx = 1.0 + x * (-3.0 + x * (15.0 + x * (-105.0 + x * (945.0 + x * (-10395.0 + x * (135135.0 + x * (-2027025.0 + x * (34459425.0 + x * -654729075.0))))))));
-    }
-    // u = au / a, b = x bx
+    const MillsPieces q = mills_pieces(a);
+    const double x = q.x, au = q.au, bx = q.bx;  // u = au / a, b = x bx
     const double base = -0.5 * a * a - 0.91893853320467274;
     if (objective) {
       lf = base + (log(bx) + log(x));
@@ -4852,7 +4867,7 @@ void launch_lcei(const CeiArgs<T>& a, int m, int d, int want_grad, double* lcei,
                  hipStream_t s) {
   const dim3 grid((unsigned)((m + CEI_WAVES - 1) / CEI_WAVES)), block(64 * CEI_WAVES);
   hipLaunchKernelGGL((lcei_kernel<T>), grid, block, 0, s, a, m, d, want_grad, lcei, lei, lpof, grad);
-  hipLaunchKernelGGL(ehvi_best_kernel, dim3(1), dim3(BSEL_THREADS), 0, s, lcei, m, best);
+  launch_argmax_last(lcei, m, best, s);
 }
 template void launch_lcei<double>(const CeiArgs<double>&, int, int, int, double*, double*, double*, double*, int*, hipStream_t);
 template void launch_lcei<float>(const CeiArgs<float>&, int, int, int, double*, double*, double*, float*, int*, hipStream_t);
@@ -4863,7 +4878,7 @@ template void launch_lcei<float>(const CeiArgs<float>&, int, int, int, double*, 
 //   t'(g) = -(lambda / 2) (1 + g^2 + g lambda),   d mes / d mu = (1/S) sum t' / sigma,   d mes / d sigma = -(1/S) sum g t' / sigma.
 // One WAVE per candidate, CEI_WAVES candidates per workgroup; y* is staged once per workgroup in the LDS when S fits
 // (S <= MES_LDS_SAMPLES: every call through the C ABI), else read from global memory.  Lane l evaluates mes_term for
-// s = l, l + 64, .. in ascending s and keeps three partial sums (t, t', g t'), which go through ehvi_wave_sum's fixed butterfly and
+// s = l, l + 64, .. in ascending s and keeps three partial sums (t, t', g t'), which go through wave_xor_sum's fixed butterfly and
 // are then scaled by 1/S; every lane holds the same three totals, so the lanes stride over the features without another shuffle.
 // All of it in fp64 for both element types, with or without a gradient, no atomics: a candidate's bits depend on nothing but its
 // own posterior and the y* array in the order given.  sigma = 0: mes = 0 with a zero gradient.  A NaN in the posterior gives NaN
@@ -4896,15 +4911,13 @@ __device__ __noinline__ MesTerm mes_term(double g) {
     r.dt = pdf > 0.0 ? -0.5 * lam * (1.0 + g * g + gl) : 0.0;
   } else {
     const double a = -g;
+    const MillsPieces q = mills_pieces(a);
+    const double x = q.x, au = q.au, bx = q.bx;
     if (a < LCEI_SERIES_A) {
-      const double au = a * (1.2533141373155003 * erfcx(a / 1.4142135623730951));
-      const double w = a * a * (1.0 - au) / au;
+      const double w = a * a * bx / au;  // (bx = 1 - au here)
       r.t = -0.5 * w + 0.91893853320467274 + (log(a) - log(au));
       r.dt = -(a / au) * (1.0 - w) / 2.0;
     } else {
-      const double x = 1.0 / a / a;  // (a * a may overflow where 1 / a / a only underflows)
-      const double au = 1.0 + x * (-1.0 + x * (3.0 + x * (-15.0 + x * (105.0 + x * (-945.0 + x * (10395.0 + x * (-135135.0 + x * (2027025.0 + x * -34459425.0))))))));
-      const double bx = 1.0 + x * (-3.0 + x * (15.0 + x * (-105.0 + x * (945.0 + x * (-10395.0 + x * (135135.0 + x * (-2027025.0 + x * (34459425.0 + x * -654729075.0))))))));
       const double dq = 2.0 + x * (-12.0 + x * (90.0 + x * (-840.0 + x * (9450.0 + x * (-124740.0 + x * (1891890.0 + x * (-32432400.0 + x * 620269650.0)))))));  // (au - bx) / x
       r.t = -bx / (2.0 * au) + 0.91893853320467274 + (log(a) - log(au));
       r.dt = -(a / au) * (x * dq / au) / 2.0;
@@ -4944,9 +4957,9 @@ __global__ void __launch_bounds__(64 * CEI_WAVES) mes_kernel(const T* __restrict
         s2 += g * r.dt;
       }
     }
-  s0 = ehvi_wave_sum(s0);  // the whole wave is here: `live` is uniform and the loop has ended for every lane
-  s1 = ehvi_wave_sum(s1);
-  s2 = ehvi_wave_sum(s2);
+  s0 = wave_xor_sum(s0);  // the whole wave is here: `live` is uniform and the loop has ended for every lane
+  s1 = wave_xor_sum(s1);
+  s2 = wave_xor_sum(s2);
   const double nan = __longlong_as_double(0x7ff8000000000000LL);
   if (lane == 0) mes[j] = bad ? nan : s0 / (double)S;
   if (!want_grad) return;
@@ -4968,7 +4981,7 @@ void launch_mes(const T* mean, const T* var, const T* dmean, const T* dvar, int 
     hipLaunchKernelGGL((mes_kernel<T, true>), grid, block, 0, s, mean, var, dmean, dvar, m, d, ystar, S, want_grad, mes, grad);
   else
     hipLaunchKernelGGL((mes_kernel<T, false>), grid, block, 0, s, mean, var, dmean, dvar, m, d, ystar, S, want_grad, mes, grad);
-  hipLaunchKernelGGL(ehvi_best_kernel, dim3(1), dim3(BSEL_THREADS), 0, s, mes, m, best);
+  launch_argmax_last(mes, m, best, s);
 }
 template void launch_mes<double>(const double*, const double*, const double*, const double*, int, int, const double*, int, int, double*,
                                  double*, int*, hipStream_t);

@@ -96,4 +96,28 @@ int lockstep_optimize(const T* starts, int R, int nvar, const double* lo, const 
   return 0;
 }
 
+// The evaluator of an optimiser whose batched call hands back fp64 values and gradient rows of type T (hbegp.cpp: maximize_ehvi,
+// maximize_constrained_ei, maximize_mes):
+//     int rows(const T* xs /*[cnt][nvar]*/, int cnt, double* val /*[cnt]*/, T* gr /*[cnt][nvar]*/)
+// The gradient rows are converted to double (exact for float and double), and an evaluation is ok iff its value and every
+// component of its gradient row are finite.  A return of rows other than 0 is handed on and nothing else is touched.  R: the most
+// rows a round can have.
+template <class T, class Rows>
+auto finite_gradient_eval(int R, int nvar, Rows rows) {
+  return [rows, nvar, gr = std::vector<T>((size_t)R * (size_t)nvar)](const T* xs, const int*, int cnt, double* val, double* grad,
+                                                                      char* ok) mutable -> int {
+    if (const int rc = rows(xs, cnt, val, gr.data())) return rc;
+    const size_t n = (size_t)nvar;
+    for (int i = 0; i < cnt; ++i) {
+      bool finite = std::isfinite(val[i]);
+      for (size_t k = 0; k < n; ++k) {
+        grad[i * n + k] = (double)gr[i * n + k];
+        finite = finite && std::isfinite(grad[i * n + k]);
+      }
+      ok[i] = finite ? 1 : 0;
+    }
+    return 0;
+  };
+}
+
 }  // namespace hbegp

@@ -7,6 +7,7 @@
 //   * a run whose every evaluation fails keeps its start and the failure value (+inf, -inf when maximising);
 //   * the gradient of a failed evaluation is poisoned (NaN in one pass, 1e300 in the other): nothing depends on it;
 //   * an evaluator that returns a status in round 2 ends the call with that status, and is not called again.
+// And finite_gradient_eval, the evaluator of the maximisers whose batched call returns T gradient rows (adaptor_case below).
 // Build + run (CPU): g++ -O1 -g -std=c++17 -ffp-contract=off -fsanitize=address,undefined -Icsrc tests/cpp/test_lockstep.cpp -o build/test_lockstep && build/test_lockstep
 #include <cmath>
 #include <cstdint>
@@ -246,7 +247,78 @@ static void status_case() {
   printf("status in round 2: rc %d after %d calls %s\n", rc, calls, same ? "same: yes" : "DIFFERENT");
 }
 
+// finite_gradient_eval: the evaluator around a batched call that returns fp64 values and gradient rows of type T.  Row i of a case
+// is of kind (first + i) % 7: clean; the value NaN, +inf, -inf; the LAST gradient component alone NaN, +inf, -inf.  Only the clean
+// row is ok; every gradient component arrives as the double of the T the call wrote (exactly: the way back gives the same T bits),
+// the values stay as the call wrote them, the call sees the driver's xs and cnt, nothing behind row cnt is written, and a status
+// of the call is handed on with nothing written at all.
+static int g_adaptor_cases = 0, g_adaptor_problems = 0;
+
+template <typename T>
+static void adaptor_case(const char* name, int d, int cnt, int first) {
+  const int R = cnt + 2;  // the buffers hold more rows than the round has
+  const double sentinel = -7.25;
+  std::vector<T> xs((size_t)R * d, (T)0.5), wrote((size_t)cnt * d);
+  std::vector<double> wrote_val(cnt);
+  const T* seen_xs = nullptr;
+  int seen_cnt = -1, status = 0;
+  auto rows = [&](const T* x, int c, double* val, T* gr) {
+    seen_xs = x;
+    seen_cnt = c;
+    if (status) return status;
+    for (int i = 0; i < c; ++i) {
+      const int kind = (first + i) % 7;
+      val[i] = kind == 1 ? (double)NAN : kind == 2 ? (double)INFINITY : kind == 3 ? -(double)INFINITY : 0.3 * (i + 1);
+      for (int k = 0; k < d; ++k) gr[(size_t)i * d + k] = (T)(0.1 * (i + 1) - 0.7 * k);  // not representable: the float rounds
+      T& last = gr[(size_t)i * d + d - 1];
+      if (kind == 4) last = (T)NAN;
+      if (kind == 5) last = (T)INFINITY;
+      if (kind == 6) last = -(T)INFINITY;
+    }
+    std::copy(val, val + c, wrote_val.begin());
+    std::copy(gr, gr + (size_t)c * d, wrote.begin());
+    return 0;
+  };
+  auto eval = finite_gradient_eval<T>(R, d, rows);
+  bool good = true;
+  for (int pass = 0; pass < 2; ++pass) {  // the second pass: the call refuses
+    status = pass ? 42 : 0;
+    std::vector<double> val(R, sentinel), grad((size_t)R * d, sentinel);
+    std::vector<char> ok(R, 9);
+    const int rc = eval(xs.data(), nullptr, cnt, val.data(), grad.data(), ok.data());
+    good = good && rc == status && seen_xs == xs.data() && seen_cnt == cnt;
+    const int written = pass ? 0 : cnt;
+    for (int i = 0; i < written; ++i) {
+      good = good && ok[i] == ((first + i) % 7 == 0 ? 1 : 0) && memcmp(&val[i], &wrote_val[i], sizeof(double)) == 0;
+      for (int k = 0; k < d; ++k) {
+        const double g = grad[(size_t)i * d + k];
+        const T w = wrote[(size_t)i * d + k], back = (T)g;
+        good = good && (std::isnan(w) ? std::isnan(g) : (g == (double)w && memcmp(&back, &w, sizeof(T)) == 0));
+      }
+    }
+    for (int i = written; i < R; ++i) {
+      good = good && ok[i] == 9 && val[i] == sentinel;
+      for (int k = 0; k < d; ++k) good = good && grad[(size_t)i * d + k] == sentinel;
+    }
+  }
+  ++g_adaptor_cases;
+  if (!good) ++g_adaptor_problems;
+  printf("adaptor %s d %d cnt %d first kind %d %s\n", name, d, cnt, first, good ? "adaptor: ok" : "adaptor: WRONG");
+}
+
 int main() {
+  for (int d : {1, 2, 5})
+    for (int first = 0; first < 7; ++first) {  // cnt = 1: every kind alone
+      adaptor_case<double>("f64", d, 1, first);
+      adaptor_case<float>("f32", d, 1, first);
+    }
+  for (int d : {1, 2, 5})
+    for (int first : {0, 3}) {  // every kind in one round, a clean row first and in the middle
+      adaptor_case<double>("f64", d, 9, first);
+      adaptor_case<float>("f32", d, 9, first);
+    }
+  printf("%d adaptor cases, %d problems\n", g_adaptor_cases, g_adaptor_problems);
+  if (g_adaptor_problems) ++g_problems;
   Counts cn;
   uint64_t seed = 20251019;
   for (int kind = 0; kind < 2; ++kind)
