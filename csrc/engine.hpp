@@ -304,6 +304,33 @@ void launch_cei(const CeiArgs<T>& a, int m, int d, int want_grad, double* cei, d
 // lpof = sum_k log F_k from stable forms, the gradient of lcei, *best = the last index of the maximum of lcei.
 template <typename T>
 void launch_lcei(const CeiArgs<T>& a, int m, int d, int want_grad, double* lcei, double* lei, double* lpof, T* grad, int* best, hipStream_t s);
+// expected hypervolume improvement of 2 .. 4 independent objectives over a box decomposition of the free region (hbegp_ehvi_nd;
+// ehvi_nd_kernel: one wave per candidate).  a.K = n_obj models: mean / var [m] and, with want_grad, dmean / dvar
+// [m][d] (a.thr is not read).  thr [g.nt] on the device: objective k's thresholds at g.off[k] .. g.off[k] + g.T[k] - 1, entry 0 standing
+// for -inf (never evaluated), the last one r_k.  boxes [g.n_boxes][2 n_obj] ints on the device: per objective (l, u), each g.off[k] +
+// its index into objective k's thresholds.  Per candidate the kernel first fills a table of (G, Phi, phi) at every threshold -- 24
+// bytes per entry, g.nt entries -- and then sums over the boxes by lookup.  Where the table lives is the call's regime, decided by
+// g.nt alone:
+//   nt <= EHVI_ND_LDS4_ENTRIES   in the LDS, EHVI_ND_WAVES candidates per workgroup (their tables fit the 64 KiB default)
+//   nt <= EHVI_ND_LDS1_ENTRIES   in the LDS, one candidate per workgroup (one table in the workgroup's 160 KiB)
+//   beyond                       in `scratch` [m][nt][3] doubles on the device (null in the two LDS regimes)
+// A candidate's arithmetic is the same in all three.  Out: ehvi[m] (fp64), grad[m][d] (want_grad), *best = the last index of the
+// maximum of ehvi (NaN never wins; m >= 1).
+constexpr int EHVI_ND_MAX_OBJ = 4;
+constexpr int EHVI_ND_WAVES = 4;
+constexpr int EHVI_ND_LDS4_ENTRIES = 65536 / (24 * EHVI_ND_WAVES);  // 682
+constexpr int EHVI_ND_LDS1_ENTRIES = 163840 / 24;                    // 6826
+constexpr size_t ehvi_nd_lds_bytes(int nt, int waves) { return 24 * (size_t)nt * waves; }
+struct EhviNdGeom {
+  int n_obj;
+  int T[EHVI_ND_MAX_OBJ];    // thresholds per objective, -inf and r_k included
+  int off[EHVI_ND_MAX_OBJ];  // where they start in thr and in the table
+  int nt;                    // their sum
+  int n_boxes;
+};
+template <typename T>
+void launch_ehvi_nd(const CeiArgs<T>& a, int m, int d, const double* thr, const int* boxes, const EhviNdGeom& g, double* scratch,
+                    int want_grad, double* ehvi, T* grad, int* best, hipStream_t s);
 // max-value entropy search (hbegp_mes; mes_kernel: one wave per candidate): mean, var [m] and, with want_grad, dmean, dvar [m][d] of
 // ONE model; ystar [S] on the device, S >= 1.  Out: mes[m], grad[m][d] (want_grad), *best = the last index of the maximum of mes.
 template <typename T>

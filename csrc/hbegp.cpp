@@ -2144,10 +2144,10 @@ struct CallScratch {
 // ---- phase times of the posterior-side calls (hbegp_debug_*_phases) ----------------------------------------------------------
 // One record per kind and calling thread: whether the thread's calls of that kind are timed, and the phase times (ms) of its last
 // timed call of that kind that reached its end.
-enum PhaseKind { PH_POSTERIOR, PH_SELECT, PH_KG, PH_NEI, PH_SENS, PH_EHVI, PH_QEI, PH_LOO, PH_PATHS, PH_CEI, PH_LCEI, PH_MES, PH_KINDS };
+enum PhaseKind { PH_POSTERIOR, PH_SELECT, PH_KG, PH_NEI, PH_SENS, PH_EHVI, PH_QEI, PH_LOO, PH_PATHS, PH_CEI, PH_LCEI, PH_MES, PH_EHVI_ND, PH_KINDS };
 struct PhaseRecord {
   bool on = false;
-  double ms[4] = {0, 0, 0, 0};
+  double ms[5] = {0, 0, 0, 0, 0};
 };
 static thread_local PhaseRecord t_phase[PH_KINDS];
 
@@ -2215,6 +2215,7 @@ class PhaseClock {
 //   cei        the K predicts (the objective's upload .. the join of the K streams), the cEI kernel with the arg-max
 //   lcei       as cei, the second phase being the log-space kernel with the arg-max
 //   mes        the predict (the uploads .. the last predict or gradient launch), the MES kernel with the arg-max
+//   ehvi_nd    as ehvi with n_obj predicts: each objective's predict on its model's stream, then the box kernel with the arg-max
 
 // Sigma = K** + noise I - Q Q^T at the candidates into W (lower tiles; m_p x m_p, kmat's identity padding): the candidates'
 // upload, the batched predict's launches (Kstar, the mean, Q = Kstar X^T; the variance too, unused), then kmat_kernel over
@@ -2646,7 +2647,7 @@ static int model_maximize_ei(hbegp_model* m, const T* starts, int S, const doubl
   return lockstep_optimize<T, LbfgsState>(starts, S, d, lo, hi, lockstep_options(maxeval, true), eval, x_out, ei_out, nevals_out);
 }
 
-// ---- acquisition functions of K independent models' marginal posteriors: EHVI, cEI, log-cEI, MES -------------
+// ---- acquisition functions of K independent models' marginal posteriors: EHVI, cEI, log-cEI, MES, EHVI over boxes
 
 // the mutexes of K models, taken in the order of the models' addresses: calls that name the same models in any order cannot wait
 // for each other
@@ -2686,6 +2687,8 @@ struct MarginalCall {
   CeiArgs<T> p;          // K and the K posteriors: mean / var [cnt], dmean / dvar [cnt][d] (null without a gradient); thr is the launch's
   int cnt, d, want_grad;
   const double* params;  // the uploaded parameters
+  const void* bytes;     // the uploaded byte parameters (null without any)
+  void* scratch;         // the call's device scratch (null without any; its contents are whatever the pool block held)
   double* val;           // [n_val][cnt], the first cnt the acquisition value the arg-max runs over
   T* grad;               // [cnt][d] (null without a gradient)
   int* best;
@@ -2705,15 +2708,22 @@ struct MarginalCall {
 // The marks of a timed call: EHVI, whose record is each model's own interval and then the kernel's, marks around every model's
 // upload and launches on that model's stream (2 k, 2 k + 1); the others, whose record runs from before M[0]'s upload to the join and
 // then over the kernel, mark before M[0]'s upload alone.  Both then mark behind the join and behind the arg-max on M[0]'s stream.
+// A call may also upload byte parameters (x.bytes [x.n_bytes]: EHVI over boxes' index list, behind params on M[0]'s stream) and borrow
+// x.scratch_bytes of device scratch for its kernel; a call without either issues exactly the copies and launches described above.
+struct MarginalExtra {
+  const void* bytes = nullptr;
+  size_t n_bytes = 0;
+  double scratch_bytes = 0.0;  // a double: counted before anything is taken, it may be far beyond the device
+};
 template <typename T, class Launch>
 static int marginal_acquisition(hbegp_model* const* M, int K, const T* Xs, int cnt, const JoinEvents& join, PhaseKind kind,
-                                const char* what_fmt, const double* params, size_t n_params, std::initializer_list<double*> vals,
-                                T* grad, int* best, T* mean_out, T* var_out, Launch&& launch) {
+                                const char* what_fmt, const double* params, size_t n_params, const MarginalExtra& x,
+                                std::initializer_list<double*> vals, T* grad, int* best, T* mean_out, T* var_out, Launch&& launch) {
   const bool want_grad = grad != nullptr;
   const int d = M[0]->d;
   const size_t n_val = vals.size();
   const double rows = padded_rows((double)cnt);
-  double need = 8.0 * n_val * cnt + 8.0 * n_params + (want_grad ? (double)sizeof(T) * cnt * d : 0.0);
+  double need = 8.0 * n_val * cnt + 8.0 * n_params + (want_grad ? (double)sizeof(T) * cnt * d : 0.0) + (double)x.n_bytes + x.scratch_bytes;
   for (int k = 0; k < K; ++k) need += predict_bytes<T>(M[k], rows, want_grad);
   if (need > 1e15 || rows > (double)(1 << 30)) {
     char what[96];
@@ -2736,10 +2746,13 @@ static int marginal_acquisition(hbegp_model* const* M, int K, const T* Xs, int c
   c.s = s0;
   double* dparams = n_params ? static_cast<double*>(ws.get(sizeof(double) * n_params)) : nullptr;
   c.params = dparams;
+  void* dbytes = x.n_bytes ? ws.get(x.n_bytes) : nullptr;
+  c.bytes = dbytes;
+  c.scratch = x.scratch_bytes > 0.0 ? ws.get((size_t)x.scratch_bytes) : nullptr;
   c.val = static_cast<double*>(ws.get(sizeof(double) * n_val * (size_t)cnt));
   c.best = static_cast<int*>(ws.get(sizeof(int)));
   c.grad = want_grad ? static_cast<T*>(ws.get(sizeof(T) * (size_t)cnt * d)) : nullptr;
-  const bool per_model = kind == PH_EHVI;  // the record times every model's stream, not M[0]'s alone
+  const bool per_model = kind == PH_EHVI || kind == PH_EHVI_ND;  // the record times every model's stream, not M[0]'s alone
   PhaseClock clk(t_phase[kind].on, 2 * (size_t)K + 2);
   c.p.K = K;
   for (int k = 0; k < K; ++k) {
@@ -2748,6 +2761,7 @@ static int marginal_acquisition(hbegp_model* const* M, int K, const T* Xs, int c
     if (per_model || k == 0) clk.mark(s);
     HIPCHECK(hipMemcpyAsync(m->Xs, Xs, sizeof(T) * (size_t)cnt * d, hipMemcpyHostToDevice, s));
     if (k == 0 && n_params) HIPCHECK(hipMemcpyAsync(dparams, params, sizeof(double) * n_params, hipMemcpyHostToDevice, s0));
+    if (k == 0 && x.n_bytes) HIPCHECK(hipMemcpyAsync(dbytes, x.bytes, x.n_bytes, hipMemcpyHostToDevice, s0));
     predict_batched_launches<T>(m, cnt, mp, true);
     if (want_grad) predict_grad_launches<T>(m, cnt, mp, true, true);
     CHECK_LAUNCHES();
@@ -2796,8 +2810,18 @@ static int marginal_acquisition(hbegp_model* const* M, int K, const T* Xs, int c
       for (int k = 0; k < K; ++k) ms[k] = clk.elapsed_ms(2 * k, 2 * k + 1);
     else ms[0] = clk.elapsed_ms(0, joined);
     ms[per_model ? K : 1] = clk.elapsed_ms(joined, joined + 1);
+    if (kind == PH_EHVI_ND)
+      for (int k = K + 1; k < 5; ++k) ms[k] = 0.0;  // a record of n_obj + 1 phases: nothing of an earlier call with more objectives stays
   }
   return HBEGP_OK;
+}
+// the call without byte parameters or scratch (EHVI, cEI, log-cEI, MES)
+template <typename T, class Launch>
+static int marginal_acquisition(hbegp_model* const* M, int K, const T* Xs, int cnt, const JoinEvents& join, PhaseKind kind,
+                                const char* what_fmt, const double* params, size_t n_params, std::initializer_list<double*> vals,
+                                T* grad, int* best, T* mean_out, T* var_out, Launch&& launch) {
+  return marginal_acquisition<T>(M, K, Xs, cnt, join, kind, what_fmt, params, n_params, MarginalExtra{}, vals, grad, best, mean_out, var_out,
+                                 launch);
 }
 
 // S bounded L-BFGS runs on the negative of such a function in lockstep (lockstep.hpp), as model_maximize_ei: every round is ONE call
@@ -2849,6 +2873,178 @@ static int model_ehvi(hbegp_model* const* M, const T* Xs, int cnt, const std::ve
                                  var_out, [&](const MarginalCall<T>& c) {
                                    launch_ehvi<T>(c.p.mean[0], c.p.var[0], c.p.dmean[0], c.p.dvar[0], c.p.mean[1], c.p.var[1], c.p.dmean[1],
                                                   c.p.dvar[1], cnt, c.d, c.params, ns, c.want_grad, c.val, c.grad, c.best, c.s);
+                                 });
+}
+
+// ---- expected hypervolume improvement of 2 .. 4 independent objectives (hbegp_ehvi_nd / hbegp_maximize_ehvi_nd) ---
+
+// What one C call makes of its front, once, on the host (a maximiser's rounds share it): objective k's thresholds thr[k] = -inf, the
+// distinct k-th coordinates of the reduced front ascending, r_k; and the disjoint boxes [l, u) whose union is the part of (-inf, r)
+// that no front point weakly dominates, per box (l_0, u_0, l_1, u_1, ..) as indices into the thresholds (0 = -inf).
+struct EhviNdPlan {
+  int n_obj = 0;
+  std::vector<double> thr[EHVI_ND_MAX_OBJ];
+  std::vector<int> boxes;
+  size_t n_boxes = 0;
+};
+typedef std::array<int, EHVI_ND_MAX_OBJ> EhviNdPt;
+
+// The non-dominated ones among distinct points, looking at the coordinates k0 .. M - 1 only, sorted by those coordinates
+// lexicographically: a canonical form of the set.  A point is dropped when another one is <= it in every coordinate looked at (so
+// of points equal there one stays).  Sorted, only an earlier point can dominate a later one; with two coordinates that is "the
+// second coordinate is not below the running minimum", with one only the first point stays.
+template <typename P>
+static void ehvi_nd_reduce(std::vector<P>* pts, int k0, int M) {
+  auto less = [&](const P& a, const P& b) {
+    for (int k = k0; k < M; ++k)
+      if (a[k] != b[k]) return a[k] < b[k];
+    return false;
+  };
+  std::sort(pts->begin(), pts->end(), less);
+  std::vector<P> keep;
+  for (const P& p : *pts) {
+    bool dominated = false;
+    if (M - k0 <= 2) {
+      dominated = !keep.empty() && (M - k0 == 1 || !(p[M - 1] < keep.back()[M - 1]));
+    } else {
+      for (const P& q : keep) {
+        bool le = true;
+        for (int k = k0; k < M && le; ++k) le = q[k] <= p[k];
+        if (le) { dominated = true; break; }
+      }
+    }
+    if (!dominated) keep.push_back(p);
+  }
+  pts->swap(keep);
+}
+
+// The sweep over objective k of points that are reduced in the objectives k .. M - 1 (as ranks: indices into the thresholds): the
+// slab below the lowest k-th coordinate holds no point, the slab from the s-th distinct coordinate to the next one (the last: to
+// r_k) the points up to the s-th; each slab's points are projected onto the objectives behind k, reduced and swept in turn.  With
+// one objective left the free region is (-inf, the lowest coordinate); with two, the slabs of the points sorted by the first are
+// the free strips directly (the second coordinate descends).  box holds the (l, u) of the objectives before k.  False once the
+// boxes would pass cap.
+static bool ehvi_nd_sweep(int k, int M, const std::vector<EhviNdPt>& pts, const int* top, int* box, EhviNdPlan* plan, size_t cap) {
+  auto emit = [&]() {
+    if (plan->n_boxes == cap) return false;
+    plan->boxes.insert(plan->boxes.end(), box, box + 2 * M);
+    ++plan->n_boxes;
+    return true;
+  };
+  if (k == M - 1) {
+    int u = top[k];
+    for (const EhviNdPt& p : pts) u = std::min(u, p[k]);
+    box[2 * k] = 0;
+    box[2 * k + 1] = u;
+    return emit();
+  }
+  const size_t n = pts.size();  // sorted by (k, k + 1, ..): ehvi_nd_reduce's order
+  if (k == M - 2) {
+    for (size_t s = 0; s <= n; ++s) {
+      box[2 * k] = s ? pts[s - 1][k] : 0;
+      box[2 * k + 1] = s < n ? pts[s][k] : top[k];
+      box[2 * k + 2] = 0;
+      box[2 * k + 3] = s ? pts[s - 1][k + 1] : top[k + 1];
+      if (!emit()) return false;
+    }
+    return true;
+  }
+  std::vector<EhviNdPt> proj;  // the reduced projection of the points [0, s): the previous slab's with the new points, reduced again
+  size_t taken = 0;
+  for (size_t s = 0; s <= n;) {  // the points [0, s) lie at or below the slab's lower edge
+    size_t e = s;                // the slab's upper edge: the next distinct coordinate
+    if (s < n)
+      while (e < n && pts[e][k] == pts[s][k]) ++e;
+    box[2 * k] = s ? pts[s - 1][k] : 0;
+    box[2 * k + 1] = s < n ? pts[s][k] : top[k];
+    if (s > taken) {
+      proj.insert(proj.end(), pts.begin() + (long)taken, pts.begin() + (long)s);
+      taken = s;
+      ehvi_nd_reduce(&proj, k + 1, M);
+    }
+    if (!ehvi_nd_sweep(k + 1, M, proj, top, box, plan, cap)) return false;
+    if (s == n) break;
+    s = e;
+  }
+  return true;
+}
+
+// The plan of a front [P][M] below ref: the front reduced to its distinct non-dominated points strictly inside the box -- the result
+// depends on that set only -- then the thresholds and the sweep.  HBEGP_ENOMEM past HBEGP_EHVI_ND_MAX_BOXES boxes.
+static int ehvi_nd_plan(const double* front, int P, int M, const double* ref, EhviNdPlan* plan) {
+  typedef std::array<double, EHVI_ND_MAX_OBJ> Pt;
+  std::vector<Pt> pts;
+  pts.reserve((size_t)P);
+  for (int i = 0; i < P; ++i) {
+    Pt p{};
+    bool inside = true;
+    for (int k = 0; k < M; ++k) {
+      p[k] = front[(size_t)M * i + k];
+      inside = inside && p[k] < ref[k];
+    }
+    if (inside) pts.push_back(p);
+  }
+  ehvi_nd_reduce(&pts, 0, M);
+  plan->n_obj = M;
+  plan->boxes.clear();
+  plan->n_boxes = 0;
+  int top[EHVI_ND_MAX_OBJ];
+  for (int k = 0; k < M; ++k) {
+    std::vector<double>& t = plan->thr[k];
+    t.clear();
+    for (const Pt& p : pts) t.push_back(p[k]);
+    std::sort(t.begin(), t.end());
+    t.erase(std::unique(t.begin(), t.end()), t.end());
+    t.insert(t.begin(), -std::numeric_limits<double>::infinity());
+    t.push_back(ref[k]);
+    top[k] = (int)t.size() - 1;
+  }
+  std::vector<EhviNdPt> ranks(pts.size());
+  for (size_t i = 0; i < pts.size(); ++i) {
+    ranks[i] = EhviNdPt{};
+    for (int k = 0; k < M; ++k)
+      ranks[i][k] = (int)(std::lower_bound(plan->thr[k].begin() + 1, plan->thr[k].end(), pts[i][k]) - plan->thr[k].begin());
+  }
+  int box[2 * EHVI_ND_MAX_OBJ];
+  if (!ehvi_nd_sweep(0, M, ranks, top, box, plan, (size_t)HBEGP_EHVI_ND_MAX_BOXES))
+    return fail(HBEGP_ENOMEM, "the front's free region splits into more than %d boxes (%d objectives, %d non-dominated points)",
+                HBEGP_EHVI_ND_MAX_BOXES, M, (int)pts.size());
+  return HBEGP_OK;
+}
+
+// what the kernel reads of a plan: the thresholds in one array, the boxes' indices moved to each objective's place in it
+struct EhviNdUpload {
+  EhviNdGeom g{};
+  std::vector<double> thr;
+  std::vector<int> boxes;
+  explicit EhviNdUpload(const EhviNdPlan& plan) {
+    const int M = plan.n_obj;
+    g.n_obj = M;
+    for (int k = 0; k < M; ++k) {
+      g.T[k] = (int)plan.thr[k].size();
+      g.off[k] = (int)thr.size();
+      thr.insert(thr.end(), plan.thr[k].begin(), plan.thr[k].end());
+    }
+    g.nt = (int)thr.size();
+    g.n_boxes = (int)plan.n_boxes;
+    boxes = plan.boxes;
+    for (size_t i = 0; i < boxes.size(); ++i) boxes[i] += g.off[(i % (2 * (size_t)M)) / 2];
+  }
+};
+
+// EHVI over boxes at cnt >= 1 candidates: marginal_acquisition over the n_obj objectives' models, the thresholds its parameters, the
+// boxes its byte parameters, the table of a front past the LDS regimes its scratch
+template <typename T>
+static int model_ehvi_nd(hbegp_model* const* M, const T* Xs, int cnt, const EhviNdUpload& u, const JoinEvents& join, double* ehvi, T* grad,
+                         int* best, T* mean_out, T* var_out) {
+  MarginalExtra x;
+  x.bytes = u.boxes.data();
+  x.n_bytes = sizeof(int) * u.boxes.size();
+  x.scratch_bytes = u.g.nt > EHVI_ND_LDS1_ENTRIES ? 24.0 * u.g.nt * cnt : 0.0;
+  return marginal_acquisition<T>(M, u.g.n_obj, Xs, cnt, join, PH_EHVI_ND, "EHVI over boxes at %d points under %d models", u.thr.data(),
+                                 u.thr.size(), x, {ehvi}, grad, best, mean_out, var_out, [&](const MarginalCall<T>& c) {
+                                   launch_ehvi_nd<T>(c.p, cnt, c.d, c.params, static_cast<const int*>(c.bytes), u.g,
+                                                     static_cast<double*>(c.scratch), c.want_grad, c.val, c.grad, c.best, c.s);
                                  });
 }
 
@@ -4580,6 +4776,118 @@ int hbegp_maximize_ehvi_f32(hbegp_model* const* models, int n_obj, const float* 
   return do_maximize_ehvi<float>(models, n_obj, starts, S, lo, hi, front, P, ref, maxeval, x_out, ehvi_out, nevals_out);
 }
 int hbegp_debug_ehvi_phases(int enable, double* phase_ms) { return debug_phases(PH_EHVI, 3, enable, phase_ms); }
+}  // extern "C"
+
+// argument checks of hbegp_ehvi_nd_* / hbegp_maximize_ehvi_nd_* / hbegp_debug_ehvi_boxes that need no model
+static int check_ehvi_nd_front(int n_obj, const double* front, int P, const double* ref) {
+  if (n_obj < 2 || n_obj > EHVI_ND_MAX_OBJ) return fail(HBEGP_EINVAL, "n_obj must be 2, 3 or 4 (got %d)", n_obj);
+  if (P < 0) return fail(HBEGP_EINVAL, "P must be >= 0 (got %d)", P);
+  if (!ref) return fail(HBEGP_EINVAL, "ref is NULL");
+  if (P > 0 && !front) return fail(HBEGP_EINVAL, "front is NULL");
+  for (int k = 0; k < n_obj; ++k)
+    if (!std::isfinite(ref[k])) return fail(HBEGP_EINVAL, "non-finite reference point");
+  for (size_t i = 0; i < (size_t)n_obj * (size_t)P; ++i)
+    if (!std::isfinite(front[i])) return fail(HBEGP_EINVAL, "non-finite front value (point %d)", (int)(i / (size_t)n_obj));
+  return HBEGP_OK;
+}
+// the checks of the models, as check_ehvi_models' with n_obj of them
+template <typename T>
+static int check_ehvi_nd_models(hbegp_model* const* models, int n_obj) {
+  if (!models) return fail(HBEGP_EINVAL, "models is NULL");
+  for (int k = 0; k < n_obj; ++k)
+    if (!models[k]) return fail(HBEGP_EINVAL, "NULL model");
+  for (int k = 0; k < n_obj; ++k)
+    for (int i = 0; i < k; ++i)
+      if (models[i] == models[k]) return fail(HBEGP_EINVAL, "the same model was passed for objectives %d and %d", i, k);
+  for (int k = 0; k < n_obj; ++k)
+    if (models[k]->is_f32 != (sizeof(T) == 4)) return fail(HBEGP_EINVAL, "model %d holds %s data", k, models[k]->is_f32 ? "f32" : "f64");
+  for (int k = 1; k < n_obj; ++k) {
+    if (models[0]->d != models[k]->d) return fail(HBEGP_EINVAL, "the models differ in d (%d and %d)", models[0]->d, models[k]->d);
+    if (models[0]->dev != models[k]->dev)
+      return fail(HBEGP_EINVAL, "the models live on different devices (%d and %d)", models[0]->dev, models[k]->dev);
+  }
+  return HBEGP_OK;
+}
+// Everything is refused before any device call: the arguments that need no model, then the front's decomposition (ENOMEM past the
+// box cap), then the models.
+template <typename T>
+static int do_ehvi_nd(hbegp_model* const* models, int n_obj, const T* Xs, int m, const double* front, int P, const double* ref,
+                      double* ehvi, T* grad, int* best, T* mean, T* var) {
+  if (m < 0) return fail(HBEGP_EINVAL, "m must be >= 0 (got %d)", m);
+  if (int rc = check_ehvi_nd_front(n_obj, front, P, ref)) return rc;
+  GUARD_BEGIN
+  EhviNdPlan plan;
+  if (int rc = ehvi_nd_plan(front, P, n_obj, ref, &plan)) return rc;
+  if (int rc = check_ehvi_nd_models<T>(models, n_obj)) return rc;
+  if (m > 0 && (!Xs || !ehvi)) return fail(HBEGP_EINVAL, "Xs/ehvi is NULL");
+  if (best) *best = -1;
+  if (m == 0) return HBEGP_OK;
+  const EhviNdUpload up(plan);
+  JoinEvents join(models[0]->dev, n_obj - 1);
+  return model_ehvi_nd<T>(models, Xs, m, up, join, ehvi, grad, best, mean, var);
+  GUARD_END
+}
+template <typename T>
+static int do_maximize_ehvi_nd(hbegp_model* const* models, int n_obj, const T* starts, int S, const double* lo, const double* hi,
+                               const double* front, int P, const double* ref, int maxeval, T* x_out, double* ehvi_out, int* nevals_out) {
+  if (S < 1) return fail(HBEGP_EINVAL, "S must be >= 1 (got %d)", S);
+  if (int rc = check_ehvi_nd_front(n_obj, front, P, ref)) return rc;
+  GUARD_BEGIN
+  EhviNdPlan plan;
+  if (int rc = ehvi_nd_plan(front, P, n_obj, ref, &plan)) return rc;
+  if (int rc = check_ehvi_nd_models<T>(models, n_obj)) return rc;
+  if (int rc = check_maximize_ei<T>(models[0], starts, S, lo, hi, 0.0, maxeval, x_out, ehvi_out)) return rc;
+  const EhviNdUpload up(plan);
+  JoinEvents join(models[0]->dev, n_obj - 1);
+  return maximize_marginal<T>(
+      starts, S, models[0]->d, lo, hi, maxeval,
+      [&](const T* xs, int cnt, double* val, T* gr) { return model_ehvi_nd<T>(models, xs, cnt, up, join, val, gr, nullptr, nullptr, nullptr); },
+      x_out, ehvi_out, nevals_out);
+  GUARD_END
+}
+extern "C" {
+int hbegp_ehvi_nd_f64(hbegp_model* const* models, int n_obj, const double* Xs, int m, const double* front, int P, const double* ref,
+                      double* ehvi, double* grad, int* best, double* mean, double* var) {
+  return do_ehvi_nd<double>(models, n_obj, Xs, m, front, P, ref, ehvi, grad, best, mean, var);
+}
+int hbegp_ehvi_nd_f32(hbegp_model* const* models, int n_obj, const float* Xs, int m, const double* front, int P, const double* ref,
+                      double* ehvi, float* grad, int* best, float* mean, float* var) {
+  return do_ehvi_nd<float>(models, n_obj, Xs, m, front, P, ref, ehvi, grad, best, mean, var);
+}
+int hbegp_maximize_ehvi_nd_f64(hbegp_model* const* models, int n_obj, const double* starts, int S, const double* lo, const double* hi,
+                               const double* front, int P, const double* ref, int maxeval, double* x_out, double* ehvi_out,
+                               int* nevals_out) {
+  return do_maximize_ehvi_nd<double>(models, n_obj, starts, S, lo, hi, front, P, ref, maxeval, x_out, ehvi_out, nevals_out);
+}
+int hbegp_maximize_ehvi_nd_f32(hbegp_model* const* models, int n_obj, const float* starts, int S, const double* lo, const double* hi,
+                               const double* front, int P, const double* ref, int maxeval, float* x_out, double* ehvi_out,
+                               int* nevals_out) {
+  return do_maximize_ehvi_nd<float>(models, n_obj, starts, S, lo, hi, front, P, ref, maxeval, x_out, ehvi_out, nevals_out);
+}
+int hbegp_debug_ehvi_nd_phases(int enable, double* phase_ms) { return debug_phases(PH_EHVI_ND, 5, enable, phase_ms); }
+int hbegp_debug_ehvi_boxes(const double* front, int P, int n_obj, const double* ref, int* thr_count, double* thr, int thr_cap, int* n_boxes,
+                           int* boxes, int box_cap) {
+  if (int rc = check_ehvi_nd_front(n_obj, front, P, ref)) return rc;
+  if (thr_cap < 0 || box_cap < 0) return fail(HBEGP_EINVAL, "thr_cap and box_cap must be >= 0 (got %d and %d)", thr_cap, box_cap);
+  if (!thr_count || !n_boxes) return fail(HBEGP_EINVAL, "thr_count/n_boxes is NULL");
+  if ((thr_cap > 0 && !thr) || (box_cap > 0 && !boxes)) return fail(HBEGP_EINVAL, "thr/boxes is NULL with a cap > 0");
+  GUARD_BEGIN
+  EhviNdPlan plan;
+  if (int rc = ehvi_nd_plan(front, P, n_obj, ref, &plan)) return rc;
+  size_t nt = 0;
+  for (int k = 0; k < n_obj; ++k) {
+    thr_count[k] = (int)plan.thr[k].size();
+    nt += plan.thr[k].size();
+  }
+  *n_boxes = (int)plan.n_boxes;
+  if (thr_cap == 0 && box_cap == 0) return HBEGP_OK;
+  if ((size_t)thr_cap < nt || (size_t)box_cap < plan.n_boxes)
+    return fail(HBEGP_EINVAL, "the caps (%d thresholds, %d boxes) are below the counts (%d, %d)", thr_cap, box_cap, (int)nt, (int)plan.n_boxes);
+  for (int k = 0; k < n_obj; ++k) thr = std::copy(plan.thr[k].begin(), plan.thr[k].end(), thr);
+  std::copy(plan.boxes.begin(), plan.boxes.end(), boxes);
+  return HBEGP_OK;
+  GUARD_END
+}
 }  // extern "C"
 
 // argument checks of hbegp_constrained_ei_* / hbegp_maximize_constrained_ei_*: everything is refused before any device call, the

@@ -4624,6 +4624,130 @@ template void launch_ehvi<float>(const float*, const float*, const float*, const
                                  const float*, int, int, const double*, int, int, double*, float*, int*, hipStream_t);
 
 // =================================================================================================================
+// expected hypervolume improvement of M = 2 .. 4 independent objectives (hbegp.cpp: model_ehvi_nd).  The host
+// splits the part of (-inf, r) that no front point weakly dominates into disjoint boxes [l_j, u_j), every l_jk and u_jk one of
+// objective k's thresholds (entry 0 = -inf, then the front's distinct coordinates, then r_k).  With ehvi_g's G, Phi, phi,
+//   EHVI = sum_j prod_k dG_jk,   dG_jk = G_k(u_jk) - G_k(l_jk),   G_k(-inf) = 0,
+//   d/dmu_k = -sum_j [Phi_k(u) - Phi_k(l)] prod_{i != k} dG_ji,   d/dsigma_k = sum_j [phi_k(u) - phi_k(l)] prod_{i != k} dG_ji.
+// One WAVE per candidate.  Phase A: the lanes run over objective k's thresholds and store ehvi_g(thr, mu_k, sigma_k) -- all of the
+// call's erfc and exp -- into the candidate's table (entry 0 of every objective is (0, 0, 0)).  Phase B: lane l takes the boxes
+// l, l + 64, .. in ascending order, looks its 2 M entries up, and adds into 1 + 2 M sums: the value takes max(dG, 0) (G is monotone:
+// a negative difference is rounding), the products of the partials the differences as they are, every product in ascending k.  The
+// sums go through wave_xor_sum; lane k < d forms grad[j][k] by the chain rule as ehvi_kernel does.  fp64 for both element types, the
+// 1 + 2 M sums with or without a gradient: a candidate's bits depend on its own posteriors, the thresholds and the boxes only.
+// LDS = true: the table is this wave's slice of the dynamic LDS (blockDim.x / 64 candidates per workgroup: EHVI_ND_WAVES, or one
+// with the whole LDS); false: its rows of `scratch`.  Every wave reaches the one barrier between the phases (a wave past m only
+// waits there); the box indices are read by every wave and stay in the L2.
+// =================================================================================================================
+template <typename T, int M, bool LDS>
+__global__ void __launch_bounds__(64 * EHVI_ND_WAVES) ehvi_nd_kernel(const CeiArgs<T> a, int m, int d, const double* __restrict__ thr,
+                                                                     const int* __restrict__ boxes, const EhviNdGeom g, double* scratch,
+                                                                     int want_grad, double* __restrict__ ehvi, T* __restrict__ grad) {
+  extern __shared__ __align__(16) char smem_raw[];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int j = blockIdx.x * (blockDim.x >> 6) + wave;
+  const bool live = j < m;
+  const int jj = live ? j : 0;
+  double* tab = LDS ? reinterpret_cast<double*>(smem_raw) + 3 * (size_t)g.nt * wave : scratch + 3 * (size_t)g.nt * jj;
+  double mu[M], sd[M];
+  bool bad = false;
+#pragma unroll
+  for (int k = 0; k < M; ++k) {
+    mu[k] = (double)a.mean[k][jj];
+    const double v = (double)a.var[k][jj];
+    sd[k] = sqrt(v);
+    bad = bad || (mu[k] != mu[k]) || (v != v);
+  }
+  if (live) {
+#pragma unroll
+    for (int k = 0; k < M; ++k) {
+      const double* t = thr + g.off[k];
+      double* e = tab + 3 * (size_t)g.off[k];
+      for (int i = lane; i < g.T[k]; i += 64) {
+        EhviG r = {0.0, 0.0, 0.0};
+        if (i > 0) r = ehvi_g(t[i], mu[k], sd[k]);
+        e[3 * i] = r.g;
+        e[3 * i + 1] = r.cdf;
+        e[3 * i + 2] = r.pdf;
+      }
+    }
+  }
+  __syncthreads();
+  if (!live) return;  // whole waves leave, behind the only barrier
+  double s[1 + 2 * M];
+#pragma unroll
+  for (int q = 0; q < 1 + 2 * M; ++q) s[q] = 0.0;
+  for (int b = lane; b < g.n_boxes; b += 64) {
+    const int* bx = boxes + (size_t)b * (2 * M);
+    double dg[M], dc[M], dp[M];
+#pragma unroll
+    for (int k = 0; k < M; ++k) {
+      const double* lo = tab + 3 * (size_t)bx[2 * k];
+      const double* up = tab + 3 * (size_t)bx[2 * k + 1];
+      dg[k] = up[0] - lo[0];
+      dc[k] = lo[1] - up[1];  // d dG / d mu
+      dp[k] = up[2] - lo[2];  // d dG / d sigma
+    }
+    double v = fmax(dg[0], 0.0);
+#pragma unroll
+    for (int k = 1; k < M; ++k) v *= fmax(dg[k], 0.0);
+    s[0] += v;
+#pragma unroll
+    for (int k = 0; k < M; ++k) {
+      double others = 1.0;
+#pragma unroll
+      for (int i = 0; i < M; ++i)
+        if (i != k) others *= dg[i];
+      s[1 + 2 * k] += dc[k] * others;
+      s[2 + 2 * k] += dp[k] * others;
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < 1 + 2 * M; ++q) s[q] = wave_xor_sum(s[q]);
+  const double nan = __longlong_as_double(0x7ff8000000000000LL);
+  if (lane == 0) ehvi[j] = bad ? nan : s[0];
+  if (want_grad && lane < d) {
+    const size_t e = (size_t)j * d + lane;
+    double gr = 0.0;
+#pragma unroll
+    for (int k = 0; k < M; ++k) {
+      const double ds = sd[k] > 2.220446049250313e-16 ? (double)a.dvar[k][e] / (2.0 * sd[k]) : 0.0;
+      gr += s[1 + 2 * k] * (double)a.dmean[k][e];
+      gr += s[2 + 2 * k] * ds;
+    }
+    grad[e] = bad ? (T)nan : (T)gr;
+  }
+}
+
+template <typename T, int M>
+static void launch_ehvi_nd_m(const CeiArgs<T>& a, int m, int d, const double* thr, const int* boxes, const EhviNdGeom& g, double* scratch,
+                             int want_grad, double* ehvi, T* grad, hipStream_t s) {
+  if (g.nt <= EHVI_ND_LDS4_ENTRIES) {
+    const dim3 grid((unsigned)((m + EHVI_ND_WAVES - 1) / EHVI_ND_WAVES)), block(64 * EHVI_ND_WAVES);
+    hipLaunchKernelGGL((ehvi_nd_kernel<T, M, true>), grid, block, ehvi_nd_lds_bytes(g.nt, EHVI_ND_WAVES), s, a, m, d, thr, boxes, g, nullptr,
+                       want_grad, ehvi, grad);
+  } else if (g.nt <= EHVI_ND_LDS1_ENTRIES) {
+    hipLaunchKernelGGL((ehvi_nd_kernel<T, M, true>), dim3((unsigned)m), dim3(64), ehvi_nd_lds_bytes(g.nt, 1), s, a, m, d, thr, boxes, g,
+                       nullptr, want_grad, ehvi, grad);
+  } else {
+    const dim3 grid((unsigned)((m + EHVI_ND_WAVES - 1) / EHVI_ND_WAVES)), block(64 * EHVI_ND_WAVES);
+    hipLaunchKernelGGL((ehvi_nd_kernel<T, M, false>), grid, block, 0, s, a, m, d, thr, boxes, g, scratch, want_grad, ehvi, grad);
+  }
+}
+template <typename T>
+void launch_ehvi_nd(const CeiArgs<T>& a, int m, int d, const double* thr, const int* boxes, const EhviNdGeom& g, double* scratch,
+                    int want_grad, double* ehvi, T* grad, int* best, hipStream_t s) {
+  if (g.n_obj == 2) launch_ehvi_nd_m<T, 2>(a, m, d, thr, boxes, g, scratch, want_grad, ehvi, grad, s);
+  else if (g.n_obj == 3) launch_ehvi_nd_m<T, 3>(a, m, d, thr, boxes, g, scratch, want_grad, ehvi, grad, s);
+  else launch_ehvi_nd_m<T, 4>(a, m, d, thr, boxes, g, scratch, want_grad, ehvi, grad, s);
+  launch_argmax_last(ehvi, m, best, s);
+}
+template void launch_ehvi_nd<double>(const CeiArgs<double>&, int, int, const double*, const int*, const EhviNdGeom&, double*, int, double*,
+                                     double*, int*, hipStream_t);
+template void launch_ehvi_nd<float>(const CeiArgs<float>&, int, int, const double*, const int*, const EhviNdGeom&, double*, int, double*,
+                                    float*, int*, hipStream_t);
+
+// =================================================================================================================
 // constrained expected improvement over K = 1 + C independent models (hbegp.cpp: model_constrained_ei):
 //   cEI = EI_0 prod_{k=1..C} F_k,   EI_0 = G_0(fmin) (ehvi_g's G; 1 for fmin = +inf),   F_k = Phi((t_k - mu_k) / sigma_k).
 // One WAVE per candidate, CEI_WAVES candidates per workgroup.  Lane k < K evaluates ehvi_g for model k once and keeps its factor
@@ -5011,6 +5135,15 @@ void init_kernels() {
   set_lds_attr(reinterpret_cast<const void*>(&qei_batch_kernel<float>), (int)qei_lds_bytes(QEI_MAXQ, MAXD), "qei_batch_kernel<f32>: dynamic LDS limit");
   set_lds_attr(reinterpret_cast<const void*>(&kg_kernel<double>), (int)kg_lds_bytes(KG_LDS_ROWS), "kg_kernel<f64>: dynamic LDS limit");
   set_lds_attr(reinterpret_cast<const void*>(&kg_kernel<float>), (int)kg_lds_bytes(KG_LDS_ROWS), "kg_kernel<f32>: dynamic LDS limit");
+  {
+    const int nd = (int)ehvi_nd_lds_bytes(EHVI_ND_LDS1_ENTRIES, 1);
+    set_lds_attr(reinterpret_cast<const void*>(&ehvi_nd_kernel<double, 2, true>), nd, "ehvi_nd_kernel<f64, 2>: dynamic LDS limit");
+    set_lds_attr(reinterpret_cast<const void*>(&ehvi_nd_kernel<double, 3, true>), nd, "ehvi_nd_kernel<f64, 3>: dynamic LDS limit");
+    set_lds_attr(reinterpret_cast<const void*>(&ehvi_nd_kernel<double, 4, true>), nd, "ehvi_nd_kernel<f64, 4>: dynamic LDS limit");
+    set_lds_attr(reinterpret_cast<const void*>(&ehvi_nd_kernel<float, 2, true>), nd, "ehvi_nd_kernel<f32, 2>: dynamic LDS limit");
+    set_lds_attr(reinterpret_cast<const void*>(&ehvi_nd_kernel<float, 3, true>), nd, "ehvi_nd_kernel<f32, 3>: dynamic LDS limit");
+    set_lds_attr(reinterpret_cast<const void*>(&ehvi_nd_kernel<float, 4, true>), nd, "ehvi_nd_kernel<f32, 4>: dynamic LDS limit");
+  }
   init_dag_kernels();
   const int lb = 163840;
   // kmat / gradtrace: 2 d 64 elements of dynamic LDS (64 KiB at d = 64 in f64) beside ~21 KiB of static LDS

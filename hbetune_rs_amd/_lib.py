@@ -16,6 +16,7 @@ EINVAL, EHIP, ENODEV, ENOMEM = -1, -2, -3, -4
 PATHS_MAX_FEATURES, PATHS_MAX_PATHS = 16384, 1024  # HBEGP_PATHS_MAX_* of include/hbegp.h
 CEI_MAX_CONSTRAINTS = 8  # HBEGP_CEI_MAX_CONSTRAINTS of include/hbegp.h
 MES_MAX_SAMPLES = 1024  # HBEGP_MES_MAX_SAMPLES of include/hbegp.h
+EHVI_ND_MAX_BOXES = 1048576  # HBEGP_EHVI_ND_MAX_BOXES of include/hbegp.h
 
 
 class HbegpError(RuntimeError):
@@ -113,6 +114,13 @@ SIGNATURES = {
                                           _ip]),
     "hbegp_maximize_ehvi_f32": (C.c_int, [C.POINTER(_vp), C.c_int, _fp, C.c_int, _dp, _dp, _dp, C.c_int, _dp, C.c_int, _fp, _dp,
                                           _ip]),
+    "hbegp_ehvi_nd_f64": (C.c_int, [C.POINTER(_vp), C.c_int, _dp, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _ip, _dp, _dp]),
+    "hbegp_ehvi_nd_f32": (C.c_int, [C.POINTER(_vp), C.c_int, _fp, C.c_int, _dp, C.c_int, _dp, _dp, _fp, _ip, _fp, _fp]),
+    "hbegp_maximize_ehvi_nd_f64": (C.c_int, [C.POINTER(_vp), C.c_int, _dp, C.c_int, _dp, _dp, _dp, C.c_int, _dp, C.c_int, _dp, _dp,
+                                             _ip]),
+    "hbegp_maximize_ehvi_nd_f32": (C.c_int, [C.POINTER(_vp), C.c_int, _fp, C.c_int, _dp, _dp, _dp, C.c_int, _dp, C.c_int, _fp, _dp,
+                                             _ip]),
+    "hbegp_debug_ehvi_boxes": (C.c_int, [_dp, C.c_int, C.c_int, _dp, _ip, _dp, C.c_int, _ip, _ip, C.c_int]),
     "hbegp_constrained_ei_f64": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, _dp, C.c_int, C.c_double, _dp, _dp, _dp, _ip, _dp, _dp, _dp,
                                            _dp]),
     "hbegp_constrained_ei_f32": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, _fp, C.c_int, C.c_double, _dp, _dp, _fp, _ip, _dp, _dp, _fp,
@@ -167,6 +175,7 @@ SIGNATURES = {
     "hbegp_debug_nei_phases": (C.c_int, [C.c_int, _dp]),
     "hbegp_debug_sens_phases": (C.c_int, [C.c_int, _dp]),
     "hbegp_debug_ehvi_phases": (C.c_int, [C.c_int, _dp]),
+    "hbegp_debug_ehvi_nd_phases": (C.c_int, [C.c_int, _dp]),
     "hbegp_debug_cei_phases": (C.c_int, [C.c_int, _dp]),
     "hbegp_debug_lcei_phases": (C.c_int, [C.c_int, _dp]),
     "hbegp_debug_mes_phases": (C.c_int, [C.c_int, _dp]),

@@ -797,6 +797,157 @@ def acquire_by_ehvi(candidates, models, k, front=None, ref=None, ctx=None):
     return np.array(idx, dtype=np.int64), proj, np.array(vals, dtype=np.float64), np.array(hvs, dtype=np.float64)
 
 
+# Expected hypervolume improvement of two to four objectives (opt-in; nothing the estimator suggests by default uses it).
+def pareto_front_nd(y):
+    """The non-dominated rows of y [N, M] when every column is minimised, sorted lexicographically; duplicates appear once.  A row
+    is dominated when another row is <= it in every column.  float64 [P, M]."""
+    y = np.asarray(y, dtype=np.float64)
+    if y.ndim != 2:
+        raise ValueError("y must be [N, M]")
+    if len(y) == 0:
+        return y.copy()
+    y = np.unique(y, axis=0)  # sorted lexicographically: only an earlier row can dominate a later one
+    keep = []
+    for i in range(len(y)):
+        if not any((y[j] <= y[i]).all() for j in keep):
+            keep.append(i)
+    return y[keep]
+
+
+def hypervolume_nd(front, ref):
+    """The volume that the points of front [..., P, M] dominate inside the box below ref [M], every objective minimised, exactly,
+    by slicing: the points sorted by the last objective, each slice between two consecutive values has the depth of their
+    difference and the (M - 1)-dimensional hypervolume of the points at or before it; M = 2 is hypervolume_2d, M = 1 the length
+    below ref.  Points need not be non-dominated, nor inside the box.  A leading shape is a batch of fronts: returns a float, or an
+    array of that shape."""
+    f = np.asarray(front, dtype=np.float64)
+    r = np.asarray(ref, dtype=np.float64).reshape(-1)
+    M = len(r)
+    if f.size == 0:
+        return 0.0 if f.ndim <= 2 else np.zeros(f.shape[:-2])
+    if f.shape[-1] != M:
+        raise ValueError("front and ref differ in the number of objectives")
+    if M == 1:
+        hv = np.maximum(r[0] - f[..., 0].min(axis=-1), 0.0)
+    elif M == 2:
+        hv = hypervolume_2d(f, r)
+    else:
+        f = np.minimum(f, r)
+        order = np.argsort(f[..., -1], axis=-1, kind="stable")
+        f = np.take_along_axis(f, order[..., None], axis=-2)
+        z = f[..., -1]
+        depth = np.concatenate([z[..., 1:], np.full(z.shape[:-1] + (1,), r[-1])], axis=-1) - z
+        hv = 0.0
+        for i in range(f.shape[-2]):
+            hv = hv + depth[..., i] * hypervolume_nd(f[..., :i + 1, :-1], r[:-1])
+    return float(hv) if np.ndim(hv) == 0 else hv
+
+
+def default_reference_point_nd(front):
+    """default_reference_point's rule for front [P >= 1, M]: per objective the worst value plus 10 % of the front's range there;
+    where the range is 0 plus 10 % of max(1, |value|)."""
+    f = np.asarray(front, dtype=np.float64)
+    if f.ndim != 2 or len(f) < 1:
+        raise ValueError("an empty front has no default reference point")
+    worst, span = f.max(axis=0), f.max(axis=0) - f.min(axis=0)
+    return worst + 0.1 * np.where(span > 0, span, np.maximum(1.0, np.abs(worst)))
+
+
+def _ehvi_nd_normalized(models, front, ref):
+    """front [P, M] and ref [M] in y units -> each column through that model's YNormalize (float64), M = len(models) in 2 .. 4."""
+    M = len(models)
+    if not 2 <= M <= 4:
+        raise ValueError("EHVI over boxes takes two, three or four models")
+    f = np.asarray(front if front is not None else [], dtype=np.float64).reshape(-1, M)
+    r = np.asarray(ref, dtype=np.float64).reshape(M)
+    fn = np.stack([np.asarray(mo.y_norm.project_into_normalized(f[:, k]), dtype=np.float64) for k, mo in enumerate(models)], axis=1)
+    rn = np.array([float(mo.y_norm.project_into_normalized(r[k:k + 1])[0]) for k, mo in enumerate(models)])
+    return fn, rn
+
+
+def ehvi_nd_a(models, x, front, ref):
+    """EHVI of the rows of x [m, d] under two, three or four SurrogateModelGPRs (objective 0 first), all minimised and taken as
+    independent (gpr.ehvi_nd).  front [P, M] and ref [M] are in y units; each column goes through that model's y projection, and
+    the VOLUME is measured in the models' normalised units, as ehvi_a's area is.  Returns (ehvi[m] float64, best): best the last
+    index of the maximum, -1 without rows."""
+    fn, rn = _ehvi_nd_normalized(models, front, ref)
+    return gpr.ehvi_nd([mo.fitted for mo in models], np.asarray(x, dtype=models[0].dtype), fn, rn)
+
+
+def maximize_ehvi_nd(models, starts, bounds, front, ref, maxeval=150):
+    """Bounded L-BFGS ascents of ehvi_nd_a from every row of `starts` (the box: `bounds` = [(lo, hi)] per feature), all runs in
+    lockstep on the device models (gpr.maximize_ehvi_nd).  front and ref in y units.  Returns (x[S, d], ehvi[S], nevals[S])."""
+    fn, rn = _ehvi_nd_normalized(models, front, ref)
+    return gpr.maximize_ehvi_nd([mo.fitted for mo in models], np.asarray(starts, dtype=models[0].dtype), bounds, fn, rn, maxeval=maxeval)
+
+
+def _ehvi_nd_default_front(models):
+    """pareto_front_nd of the models' training targets in y units; the models must have been trained on the very same rows."""
+    fks = [mo.fitted for mo in models]
+    xs = [fk.x_train for fk in fks]
+    if any(x is None for x in xs) or any(fk.y_train is None for fk in fks):
+        raise ValueError("the models do not hold their training rows: pass a front")
+    if any(x.shape != xs[0].shape or x.tobytes() != xs[0].tobytes() for x in xs[1:]):
+        raise ValueError("the models were not trained on the same rows: pass a front")
+    y = [np.asarray(mo.y_norm.project_location_from_normalized(np.asarray(mo.fitted.y_train)), dtype=np.float64) for mo in models]
+    return pareto_front_nd(np.stack(y, axis=1))
+
+
+def acquire_by_ehvi_nd(candidates, models, k, front=None, ref=None, ctx=None):
+    """acquire_by_ehvi for two, three or four minimised objectives: k distinct rows of the candidate set [m, n_features], each the
+    row of largest EHVI (gpr.ehvi_nd) under the SurrogateModelGPRs `models`.  After a pick ALL surrogates are conditioned on the
+    kriging-believer fantasy (x_pick, that model's posterior mean) through extend_with at the same theta, and the believed point
+    joins the front.  front [P, M] and ref [M] are in y units.  Without a front: pareto_front_nd of the models' training targets,
+    which needs models trained on the very same rows (else ValueError).  Without a ref: default_reference_point_nd of the front.
+    Returns (idx[k] int64, the projected means [k, M] of the picks at the time they were picked, ehvi[k] and the believed
+    hypervolume hv[k] after each pick, both in the normalised units of ehvi_nd_a).  The models' own `fitted` handles are left as
+    they were."""
+    M = len(models)
+    if not 2 <= M <= 4:
+        raise ValueError("EHVI over boxes takes two, three or four models")
+    dtype = models[0].dtype
+    c = np.asarray(candidates, dtype=dtype)
+    if c.ndim != 2:
+        raise ValueError("candidates must be [m, n_features]")
+    k = int(k)
+    if not 0 <= k <= c.shape[0]:
+        raise ValueError("k must lie in [0, number of rows]")
+    if front is None:
+        front = _ehvi_nd_default_front(models)
+    if ref is None:
+        ref = default_reference_point_nd(front)
+    fn, rn = _ehvi_nd_normalized(models, front, ref)
+    fks = [mo.fitted for mo in models]
+    data = [(fk.x_train, fk.y_train) for fk in fks]
+    if k > 1 and any(X is None or y is None for X, y in data):
+        raise ValueError("the models do not hold their training rows: they cannot be conditioned on a fantasy")
+    avail = list(range(c.shape[0]))
+    idx, means, vals, hvs = [], [], [], []
+    try:
+        for t in range(k):
+            val, best, mean, _ = gpr.ehvi_nd(fks, c[avail], fn, rn, want_posterior=True)
+            idx.append(avail.pop(best))
+            means.append(mean[best])
+            vals.append(val[best])
+            fn = np.vstack([fn, np.asarray(mean[best], dtype=np.float64)[None, :]])
+            hvs.append(hypervolume_nd(fn, rn))
+            if t + 1 < k:
+                for o in range(M):
+                    X, y = data[o]
+                    data[o] = (np.vstack([X, c[idx[-1]:idx[-1] + 1]]), np.concatenate([y, mean[best, o:o + 1]]))
+                    nxt = fks[o].extend_with(*data[o], ctx=ctx)
+                    if fks[o] is not models[o].fitted:
+                        fks[o].release()
+                    fks[o] = nxt
+    finally:
+        for o in range(M):
+            if fks[o] is not models[o].fitted:
+                fks[o].release()
+    means = np.array(means, dtype=dtype).reshape(-1, M)
+    proj = np.stack([models[o].y_norm.project_location_from_normalized(means[:, o]) for o in range(M)], axis=1)
+    return np.array(idx, dtype=np.int64), proj, np.array(vals, dtype=np.float64), np.array(hvs, dtype=np.float64)
+
+
 # Constrained expected improvement (opt-in; nothing the estimator suggests by default uses it).
 def feasible_fmin(y, g, limits):
     """The smallest objective y[i] among the rows whose constraint values all hold, g[i, k] <= limits[k] (a row exactly on a limit

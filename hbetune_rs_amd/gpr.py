@@ -785,6 +785,83 @@ def maximize_ehvi(models, starts, bounds, front, ref, maxeval=150):
     return x, val, nevals
 
 
+def _ehvi_nd_args(models, front, ref):
+    """(models, handle array, suffix, dtype, d, front [P, n_obj] float64, ref [n_obj] float64) of an n_obj-objective call."""
+    models = list(models)
+    n_obj = max(len(models), 1)
+    handles = (C.c_void_p * n_obj)(*[fk._h for fk in models])
+    fk = models[0]
+    front = _lib.as_c(np.asarray(front if front is not None else [], dtype=np.float64).reshape(-1, n_obj), np.float64)
+    ref = _lib.as_c(np.asarray(ref, dtype=np.float64).reshape(n_obj), np.float64)
+    return models, handles, fk._sfx, fk.dtype, fk.d, front, ref
+
+
+def ehvi_nd(models, x, front, ref, want_grad=False, want_posterior=False):
+    """Expected hypervolume improvement of n_obj = len(models) = 2, 3 or 4 minimised objectives (hbegp_ehvi_nd_*), in the models'
+    normalised y spaces: models = (objective 0, ..), FittedKernels of the same d, element type and device, taken as independent;
+    front [P, n_obj] the points reached so far, in any order (dominated points, duplicates and points outside the box change
+    nothing); ref [n_obj] the reference point.  Returns what ehvi() returns, with mean[m, n_obj] and var[m, n_obj].  A front whose
+    free region splits into more than _lib.EHVI_ND_MAX_BOXES boxes is refused (HbegpError, ENOMEM)."""
+    models, handles, sfx, dtype, d, front, ref = _ehvi_nd_args(models, front, ref)
+    n_obj = len(models)
+    x = _lib.as_c(np.asarray(x, dtype=dtype).reshape(-1, d), dtype)
+    m = x.shape[0]
+    val = np.zeros(m)
+    best = C.c_int(-1)
+    grad = np.zeros((m, d), dtype=dtype) if want_grad else None
+    mean = np.zeros((m, n_obj), dtype=dtype) if want_posterior else None
+    var = np.zeros((m, n_obj), dtype=dtype) if want_posterior else None
+    fn = getattr(_lib.load(), f"hbegp_ehvi_nd_{sfx}")
+    _lib.check(fn(handles, n_obj, _lib.aptr(x), m, _lib.dptr(front), front.shape[0], _lib.dptr(ref), _lib.dptr(val),
+                  _lib.aptr(grad), C.byref(best), _lib.aptr(mean), _lib.aptr(var)))
+    out = (val, best.value)
+    if want_grad:
+        out += (grad,)
+    if want_posterior:
+        out += (mean, var)
+    return out
+
+
+def maximize_ehvi_nd(models, starts, bounds, front, ref, maxeval=150):
+    """S bounded L-BFGS runs maximising ehvi_nd() over the box (hbegp_maximize_ehvi_nd_*), one batched gradient predict per model
+    and round; the front is decomposed once.  starts: [S, d] inside the box; bounds: d pairs (lo, hi).  Returns (x[S, d], ehvi[S],
+    nevals[S]): each run's best point, never worse than its start; ehvi_nd(models, x, front, ref) reproduces the values bit for
+    bit."""
+    models, handles, sfx, dtype, d, front, ref = _ehvi_nd_args(models, front, ref)
+    starts = _lib.as_c(np.atleast_2d(starts), dtype)
+    assert starts.shape[1] == d
+    S = starts.shape[0]
+    bounds = np.asarray(bounds, dtype=np.float64).reshape(d, 2)
+    lo = _lib.as_c(bounds[:, 0], np.float64)
+    hi = _lib.as_c(bounds[:, 1], np.float64)
+    x = np.zeros((S, d), dtype=dtype)
+    val = np.zeros(S)
+    nevals = np.zeros(S, dtype=np.int32)
+    fn = getattr(_lib.load(), f"hbegp_maximize_ehvi_nd_{sfx}")
+    _lib.check(fn(handles, len(models), _lib.aptr(starts), S, _lib.dptr(lo), _lib.dptr(hi), _lib.dptr(front), front.shape[0],
+                  _lib.dptr(ref), int(maxeval), _lib.aptr(x), _lib.dptr(val), nevals.ctypes.data_as(C.POINTER(C.c_int))))
+    return x, val, nevals
+
+
+def ehvi_boxes(front, ref):
+    """The box decomposition hbegp_ehvi_nd_* sums over (hbegp_debug_ehvi_boxes; host only, no device): front [P, n_obj], ref [n_obj].
+    Returns (thr, boxes): thr a list of n_obj float64 arrays -- -inf, the reduced front's distinct coordinates ascending, r_k -- and
+    boxes [n_boxes, n_obj, 2] int32, per box and objective the indices (l, u) into thr[k] (0 = -inf)."""
+    ref = _lib.as_c(np.asarray(ref, dtype=np.float64).reshape(-1), np.float64)
+    n_obj = len(ref)
+    front = _lib.as_c(np.asarray(front if front is not None else [], dtype=np.float64).reshape(-1, max(n_obj, 1)), np.float64)
+    fn = _lib.load().hbegp_debug_ehvi_boxes
+    ip = C.POINTER(C.c_int)
+    counts = np.zeros(max(n_obj, 1), dtype=np.int32)
+    nb = C.c_int(0)
+    _lib.check(fn(_lib.dptr(front), front.shape[0], n_obj, _lib.dptr(ref), counts.ctypes.data_as(ip), None, 0, C.byref(nb), None, 0))
+    thr = np.zeros(int(counts.sum()))
+    boxes = np.zeros((nb.value, n_obj, 2), dtype=np.int32)
+    _lib.check(fn(_lib.dptr(front), front.shape[0], n_obj, _lib.dptr(ref), counts.ctypes.data_as(ip), _lib.dptr(thr), len(thr),
+                  C.byref(nb), boxes.ctypes.data_as(ip), nb.value))
+    return np.split(thr, np.cumsum(counts)[:-1]), boxes
+
+
 def _cei_args(objective, constraints, limits):
     """(constraints as a list, their handle array, limits [C] float64) of a constrained-EI call."""
     constraints = list(constraints)

@@ -419,6 +419,46 @@ int hbegp_maximize_ehvi_f32(hbegp_model* const* models, int n_obj, const float* 
                             const double* front, int P, const double* ref, int maxeval, float* x_out, double* ehvi_out,
                             int* nevals_out);
 
+/* Expected hypervolume improvement of n_obj = 2, 3 or 4 objectives, all minimised, each modelled by its own model; the posteriors
+ * are taken as independent.  Everything hbegp_ehvi_* says about the models (models[n_obj], objective 0 first; they share d, the
+ * element type and the device and may differ in n and nu), the normalised y spaces, the posterior N(mu_k, sigma_k^2) at a row,
+ * "sigma = 0", h's evaluation, fp64 arithmetic in a fixed order without atomics, NaN rows, best, m = 0, the locking order, the
+ * per-model streams and borrowed device memory holds here with "two" read as n_obj.  ref[n_obj] is the reference point r,
+ * front[P*n_obj] the caller's points in any order (row i holds its n_obj coordinates), both always double.  The library reduces the
+ * front on the host to its distinct non-dominated points strictly inside the box (every coordinate below r_k) -- the result depends
+ * on that SET only: the order of the points, duplicates, dominated points and points outside the box change no bit -- and splits
+ * the part of (-inf, r) that no front point weakly dominates into disjoint boxes [l_j, u_j), each l_jk -inf or a k-th coordinate
+ * of the front, each u_jk such a coordinate or r_k (a sweep over the objectives in their order: hbegp_debug_ehvi_boxes).  With
+ * G_k(t) = E[(t - Y_k)^+] = sigma_k h((t - mu_k) / sigma_k) and G_k(-inf) = 0,
+ *   ehvi = sum_j prod_k [G_k(u_jk) - G_k(l_jk)] >= 0
+ * is the expected volume, inside the box, that the point would add to what the front dominates; P = 0 gives prod_k G_k(r_k).  The
+ * partials follow from dG/dmu = -Phi(z), dG/dsigma = phi(z) in the same sum, grad[m*d] (may be NULL: no gradient launch) through
+ * hbegp_predict_grad_*'s dmean and dvar.  n_obj = 2 gives the quantity of hbegp_ehvi_* by another sum: equal within rounding, not
+ * bit for bit.  A row's bits depend neither on m, nor on its position, nor on whether a gradient was asked for.
+ * ehvi[m] (required for m > 0); best (may be NULL); mean[m*n_obj], var[m*n_obj] (each may be NULL): row j holds objective 0 first,
+ * bit for bit hbegp_predict_*'s (batched path) or hbegp_predict_grad_*'s numbers.
+ * HBEGP_EINVAL (before any device call) for n_obj outside 2 .. 4, m < 0, P < 0, a NULL ref, a NULL front with P > 0, a non-finite
+ * front or ref value, a NULL model, a model named twice, models of different d, element type or device, a model of the other
+ * element type, a NULL Xs or ehvi with m > 0.  HBEGP_ENOMEM, also before any device call, for a front whose free region splits
+ * into more than HBEGP_EHVI_ND_MAX_BOXES boxes (their number grows like P^(n_obj - 1)), and for work that does not fit in device
+ * memory.  The cap keeps the index list of a call, 8 n_obj bytes per box, at 32 MiB at the most. */
+#define HBEGP_EHVI_ND_MAX_BOXES 1048576
+int hbegp_ehvi_nd_f64(hbegp_model* const* models, int n_obj, const double* Xs, int m, const double* front, int P, const double* ref,
+                      double* ehvi, double* grad, int* best, double* mean, double* var);
+int hbegp_ehvi_nd_f32(hbegp_model* const* models, int n_obj, const float* Xs, int m, const double* front, int P, const double* ref,
+                      double* ehvi, float* grad, int* best, float* mean, float* var);
+/* S bounded L-BFGS runs maximising hbegp_ehvi_nd_* over the box [lo, hi] in lockstep, with the contract of hbegp_maximize_ehvi_*:
+ * every round is one batched gradient predict per model over the runs still going and the box kernel with its gradient; the
+ * front is decomposed once for all rounds.  hbegp_ehvi_nd_* at x_out reproduces ehvi_out bit for bit; nevals_out[S] (may be NULL)
+ * <= maxeval.  HBEGP_EINVAL / HBEGP_ENOMEM for everything hbegp_ehvi_nd_* refuses about n_obj, front, ref and models, and
+ * HBEGP_EINVAL for S < 1, a NULL starts / lo / hi / x_out / ehvi_out, maxeval < 1, lo > hi or a start outside the box. */
+int hbegp_maximize_ehvi_nd_f64(hbegp_model* const* models, int n_obj, const double* starts, int S, const double* lo, const double* hi,
+                               const double* front, int P, const double* ref, int maxeval, double* x_out, double* ehvi_out,
+                               int* nevals_out);
+int hbegp_maximize_ehvi_nd_f32(hbegp_model* const* models, int n_obj, const float* starts, int S, const double* lo, const double* hi,
+                               const double* front, int P, const double* ref, int maxeval, float* x_out, double* ehvi_out,
+                               int* nevals_out);
+
 /* Constrained expected improvement (cEI; Gardner et al. 2014, Gelbart et al. 2014): the expected improvement of a minimised objective
  * times the probability that C constraints g_k(x) <= t_k hold, each quantity modelled by its own model; the 1 + C posteriors are
  * taken as independent.  Everything is in each model's own normalised y space.  Model 0 is `objective`, models 1 .. C are
@@ -751,6 +791,19 @@ int hbegp_debug_nei_phases(int enable, double* phase_ms);
  * last timed hbegp_ehvi_* call -- objective 0's predict and objective 1's (each with its upload, on its own stream: they overlap),
  * the EHVI kernel with the arg-max -- in milliseconds; then enable != 0 makes this thread's later EHVI calls timed. */
 int hbegp_debug_ehvi_phases(int enable, double* phase_ms);
+/* ---- timing hook (tools/ehvi_nd_bench.py): phase_ms[5] (may be NULL) receives the device time of the phases of the calling
+ * thread's last timed hbegp_ehvi_nd_* call -- objective 0's predict .. objective n_obj - 1's (each with its upload, on its own
+ * stream: they overlap), then the box kernel with the arg-max; the entries behind these n_obj + 1 are 0 -- in milliseconds; then
+ * enable != 0 makes this thread's later hbegp_ehvi_nd_* calls timed. */
+int hbegp_debug_ehvi_nd_phases(int enable, double* phase_ms);
+/* ---- the box decomposition of hbegp_ehvi_nd_*, on the host alone (no device is touched; for the tests of the decomposition).
+ * front[P*n_obj], ref[n_obj] and their refusals as there.  thr_count[n_obj] receives the number of thresholds per objective:
+ * -inf, the distinct coordinates of the reduced front ascending, r_k; *n_boxes the number of boxes.  With thr_cap = box_cap = 0
+ * nothing else is written.  Otherwise thr[thr_cap] receives the thresholds, objective 0's first, and boxes[box_cap * 2 * n_obj]
+ * per box and objective (l, u) as indices into that objective's thresholds (0 = -inf), in the order the kernel sums them;
+ * HBEGP_EINVAL when a cap is below its count.  HBEGP_ENOMEM past HBEGP_EHVI_ND_MAX_BOXES boxes. */
+int hbegp_debug_ehvi_boxes(const double* front, int P, int n_obj, const double* ref, int* thr_count, double* thr, int thr_cap,
+                           int* n_boxes, int* boxes, int box_cap);
 /* ---- timing hook (tools/cei_bench.py): phase_ms[2] (may be NULL) receives the device time of the phases of the calling thread's
  * last timed hbegp_constrained_ei_* call -- the 1 + C predicts (from the objective's upload to the join of the streams: they
  * overlap), the cEI kernel with the arg-max -- in milliseconds; then enable != 0 makes this thread's later cEI calls timed. */

@@ -94,6 +94,12 @@ template <> struct Abi<double> {
                            const double* ref, int maxeval, double* x, double* v, int* ne) {
     return hbegp_maximize_ehvi_f64(ms, no, st, s, lo, hi, front, P, ref, maxeval, x, v, ne);
   }
+  static int ehvi_nd(hbegp_model* const* ms, int no, const double* xs, int m, const double* front, int P, const double* ref, double* v, double* g,
+                     int* best, double* mean, double* var) { return hbegp_ehvi_nd_f64(ms, no, xs, m, front, P, ref, v, g, best, mean, var); }
+  static int maximize_ehvi_nd(hbegp_model* const* ms, int no, const double* st, int s, const double* lo, const double* hi, const double* front,
+                              int P, const double* ref, int maxeval, double* x, double* v, int* ne) {
+    return hbegp_maximize_ehvi_nd_f64(ms, no, st, s, lo, hi, front, P, ref, maxeval, x, v, ne);
+  }
   static int constrained_ei(hbegp_model* o, hbegp_model* const* cs, int nc, const double* xs, int m, double fmin, const double* lim, double* v, double* g,
                             int* best, double* ei, double* pof, double* mean, double* var) {
     return hbegp_constrained_ei_f64(o, cs, nc, xs, m, fmin, lim, v, g, best, ei, pof, mean, var);
@@ -170,6 +176,12 @@ template <> struct Abi<float> {
   static int maximize_ehvi(hbegp_model* const* ms, int no, const float* st, int s, const double* lo, const double* hi, const double* front, int P,
                            const double* ref, int maxeval, float* x, double* v, int* ne) {
     return hbegp_maximize_ehvi_f32(ms, no, st, s, lo, hi, front, P, ref, maxeval, x, v, ne);
+  }
+  static int ehvi_nd(hbegp_model* const* ms, int no, const float* xs, int m, const double* front, int P, const double* ref, double* v, float* g,
+                     int* best, float* mean, float* var) { return hbegp_ehvi_nd_f32(ms, no, xs, m, front, P, ref, v, g, best, mean, var); }
+  static int maximize_ehvi_nd(hbegp_model* const* ms, int no, const float* st, int s, const double* lo, const double* hi, const double* front,
+                              int P, const double* ref, int maxeval, float* x, double* v, int* ne) {
+    return hbegp_maximize_ehvi_nd_f32(ms, no, st, s, lo, hi, front, P, ref, maxeval, x, v, ne);
   }
   static int constrained_ei(hbegp_model* o, hbegp_model* const* cs, int nc, const float* xs, int m, double fmin, const double* lim, double* v, float* g,
                             int* best, double* ei, double* pof, float* mean, float* var) {
@@ -359,6 +371,22 @@ void maximize_ehvi(const FittedKernel<A>& obj0, const FittedKernel<A>& obj1, con
                    const double* front, int P, const double* ref, int maxeval, A* x_out, double* ehvi_out, int* nevals = nullptr) {
   hbegp_model* ms[2] = {obj0.handle(), obj1.handle()};
   check(detail::Abi<A>::maximize_ehvi(ms, 2, starts, S, lo, hi, front, P, ref, maxeval, x_out, ehvi_out, nevals));
+}
+// The same for n_obj = 2, 3 or 4 objectives, objs[n_obj] pointing at their FittedKernels (objective 0 first): front[P*n_obj],
+// ref[n_obj], mean[m*n_obj], var[m*n_obj].  A front whose free region splits into more than HBEGP_EHVI_ND_MAX_BOXES boxes throws.
+template <typename A>
+void ehvi_nd(const FittedKernel<A>* const* objs, int n_obj, const A* xs, int m, const double* front, int P, const double* ref,
+             double* ehvi_out, A* grad = nullptr, int* best = nullptr, A* mean = nullptr, A* var = nullptr) {
+  hbegp_model* ms[4] = {nullptr, nullptr, nullptr, nullptr};
+  for (int k = 0; k < n_obj && k < 4; ++k) ms[k] = objs[k]->handle();
+  check(detail::Abi<A>::ehvi_nd(ms, n_obj, xs, m, front, P, ref, ehvi_out, grad, best, mean, var));
+}
+template <typename A>
+void maximize_ehvi_nd(const FittedKernel<A>* const* objs, int n_obj, const A* starts, int S, const double* lo, const double* hi,
+                      const double* front, int P, const double* ref, int maxeval, A* x_out, double* ehvi_out, int* nevals = nullptr) {
+  hbegp_model* ms[4] = {nullptr, nullptr, nullptr, nullptr};
+  for (int k = 0; k < n_obj && k < 4; ++k) ms[k] = objs[k]->handle();
+  check(detail::Abi<A>::maximize_ehvi_nd(ms, n_obj, starts, S, lo, hi, front, P, ref, maxeval, x_out, ehvi_out, nevals));
 }
 
 // Constrained expected improvement at xs[m*d]: the EI of the minimised `objective` below fmin (normalised y space; +infinity: no

@@ -159,6 +159,14 @@ extern "C" {
         models: *const *mut HbegpModel, n_obj: c_int, xs: *const c_float, m: c_int, front: *const c_double, p: c_int,
         reference: *const c_double, ehvi: *mut c_double, grad: *mut c_float, best: *mut c_int, mean: *mut c_float, var: *mut c_float,
     ) -> c_int;
+    fn hbegp_ehvi_nd_f64(
+        models: *const *mut HbegpModel, n_obj: c_int, xs: *const c_double, m: c_int, front: *const c_double, p: c_int,
+        reference: *const c_double, ehvi: *mut c_double, grad: *mut c_double, best: *mut c_int, mean: *mut c_double, var: *mut c_double,
+    ) -> c_int;
+    fn hbegp_ehvi_nd_f32(
+        models: *const *mut HbegpModel, n_obj: c_int, xs: *const c_float, m: c_int, front: *const c_double, p: c_int,
+        reference: *const c_double, ehvi: *mut c_double, grad: *mut c_float, best: *mut c_int, mean: *mut c_float, var: *mut c_float,
+    ) -> c_int;
     fn hbegp_constrained_ei_f64(
         objective: *mut HbegpModel, constraints: *const *mut HbegpModel, n_con: c_int, xs: *const c_double, m: c_int,
         fmin_normalized: c_double, limits: *const c_double, cei: *mut c_double, grad: *mut c_double, best: *mut c_int,
@@ -351,6 +359,12 @@ pub trait GpuScalar: Scalar + sealed::Sealed {
         models: *const *mut HbegpModel, n_obj: c_int, xs: *const Self, m: c_int, front: *const f64, p: c_int, reference: *const f64,
         ehvi: *mut f64, grad: *mut Self, best: *mut c_int, mean: *mut Self, var: *mut Self,
     ) -> c_int;
+    /// `hbegp_ehvi_nd_*`
+    #[allow(clippy::too_many_arguments)]
+    unsafe fn ffi_ehvi_nd(
+        models: *const *mut HbegpModel, n_obj: c_int, xs: *const Self, m: c_int, front: *const f64, p: c_int, reference: *const f64,
+        ehvi: *mut f64, grad: *mut Self, best: *mut c_int, mean: *mut Self, var: *mut Self,
+    ) -> c_int;
     /// `hbegp_constrained_ei_*`
     #[allow(clippy::too_many_arguments)]
     unsafe fn ffi_constrained_ei(
@@ -474,6 +488,12 @@ impl GpuScalar for f64 {
         ehvi: *mut f64, grad: *mut f64, best: *mut c_int, mean: *mut f64, var: *mut f64,
     ) -> c_int {
         hbegp_ehvi_f64(models, n_obj, xs, m, front, p, reference, ehvi, grad, best, mean, var)
+    }
+    unsafe fn ffi_ehvi_nd(
+        models: *const *mut HbegpModel, n_obj: c_int, xs: *const f64, m: c_int, front: *const f64, p: c_int, reference: *const f64,
+        ehvi: *mut f64, grad: *mut f64, best: *mut c_int, mean: *mut f64, var: *mut f64,
+    ) -> c_int {
+        hbegp_ehvi_nd_f64(models, n_obj, xs, m, front, p, reference, ehvi, grad, best, mean, var)
     }
     unsafe fn ffi_constrained_ei(
         objective: *mut HbegpModel, constraints: *const *mut HbegpModel, n_con: c_int, xs: *const f64, m: c_int, fmin_normalized: f64,
@@ -602,6 +622,12 @@ impl GpuScalar for f32 {
         ehvi: *mut f64, grad: *mut f32, best: *mut c_int, mean: *mut f32, var: *mut f32,
     ) -> c_int {
         hbegp_ehvi_f32(models, n_obj, xs, m, front, p, reference, ehvi, grad, best, mean, var)
+    }
+    unsafe fn ffi_ehvi_nd(
+        models: *const *mut HbegpModel, n_obj: c_int, xs: *const f32, m: c_int, front: *const f64, p: c_int, reference: *const f64,
+        ehvi: *mut f64, grad: *mut f32, best: *mut c_int, mean: *mut f32, var: *mut f32,
+    ) -> c_int {
+        hbegp_ehvi_nd_f32(models, n_obj, xs, m, front, p, reference, ehvi, grad, best, mean, var)
     }
     unsafe fn ffi_constrained_ei(
         objective: *mut HbegpModel, constraints: *const *mut HbegpModel, n_con: c_int, xs: *const f32, m: c_int, fmin_normalized: f64,
@@ -969,6 +995,37 @@ impl<A: GpuScalar> SurrogateModelGpu<A> {
         };
         if rc != HBEGP_OK {
             panic!("hbegp_ehvi failed: {}", last_error());
+        }
+        (ehvi, usize::try_from(best).ok())
+    }
+
+    /// Expected hypervolume improvement of two to four minimised objectives (`hbegp_ehvi_nd_*`): `self` models objective 0, `others`
+    /// the objectives 1 .. (one to three models of the same features, element type and device; the posteriors are taken as
+    /// independent).  `front` [P, n_obj] and `reference` [n_obj] are in the models' NORMALISED y spaces, as in `ehvi_normalized`; the
+    /// volume is measured in normalised units.  The library splits the free region into boxes on the host and refuses a front that
+    /// needs more than `HBEGP_EHVI_ND_MAX_BOXES` of them.  Returns (ehvi [m], best = the last index of its maximum, None without
+    /// rows).  Opt-in.
+    pub fn ehvi_nd_normalized(&self, others: &[&Self], x: ArrayView2<A>, front: ArrayView2<f64>, reference: &[f64]) -> (Vec<f64>, Option<usize>) {
+        let n_obj = 1 + others.len();
+        assert!((2..=4).contains(&n_obj), "EHVI over boxes takes two, three or four models");
+        assert!(reference.len() == n_obj, "reference must hold one value per objective");
+        let (m, _d) = x.dim();
+        let (p, cols) = front.dim();
+        assert!(p == 0 || cols == n_obj, "front must be [P, n_obj]");
+        let x = x.as_standard_layout();
+        let front = front.as_standard_layout();
+        let mut models = vec![self.handle];
+        models.extend(others.iter().map(|o| o.handle));
+        let mut ehvi = vec![0.0f64; m];
+        let mut best: c_int = -1;
+        let ehvi_ptr = if m > 0 { ehvi.as_mut_ptr() } else { std::ptr::null_mut() };
+        let front_ptr = if p > 0 { front.as_ptr() } else { std::ptr::null() };
+        let rc = unsafe {
+            A::ffi_ehvi_nd(models.as_ptr(), n_obj as c_int, x.as_ptr(), m as c_int, front_ptr, p as c_int, reference.as_ptr(), ehvi_ptr,
+                           std::ptr::null_mut(), &mut best, std::ptr::null_mut(), std::ptr::null_mut())
+        };
+        if rc != HBEGP_OK {
+            panic!("hbegp_ehvi_nd failed: {}", last_error());
         }
         (ehvi, usize::try_from(best).ok())
     }
