@@ -36,6 +36,7 @@
 #include "lbfgsb.hpp"
 #include "lbfgs_step.hpp"
 #include "lockstep.hpp"
+#include "slot_share.hpp"
 
 
 using namespace hbegp;
@@ -715,6 +716,8 @@ constexpr int DAG_MAX_VARIANTS = 4;  // task-queue launches sized for 1..4 busy 
 // threads fitting side by side on one context -- replicas).  Sized for 6 / 12 / 24 runs in flight.
 constexpr int DAG_CROWD_LEVELS = 3;
 constexpr int DAG_CROWD_BUSY[DAG_CROWD_LEVELS] = {6, 12, 24};
+// ... and, behind those, the two unequal shares of a fit whose runs have drifted apart (slot_share.hpp): lead, then lag
+constexpr int DAG_SHARE_VARIANTS = 2;
 constexpr int MAX_DEVS = 64;
 // What a task-queue plan is built from: Problem::init keeps the plans it builds by this key
 struct DagPlanKey {
@@ -723,6 +726,7 @@ struct DagPlanKey {
   bool operator<(const DagPlanKey& o) const { return tie() < o.tie(); }
 };
 static std::atomic<int> g_dev_busy[MAX_DEVS];  // optimiser runs in flight per device id, over all fits of the process
+static std::atomic<int> g_dev_fits[MAX_DEVS];  // fits in flight per device id, from the moment they are called (hbegp_debug_fits_in_flight)
 
 // What the leave-one-out tail (loo_tail, below the model) reads: the results an evaluation left on the device.  Kinv is read on and
 // below the diagonal only (a slot's buffer is not mirrored), P may be a pinned host block.
@@ -758,7 +762,7 @@ struct Slot {
   size_t small_slab_bytes = 0;
   void* host_slab = nullptr;    // one pooled pinned block behind hP, hOut
   size_t host_slab_bytes = 0;
-  hipGraphExec_t graph[DAG_MAX_VARIANTS + 1 + DAG_CROWD_LEVELS][2][4] = {};  // [task-queue variant][target][EvalMode]
+  hipGraphExec_t graph[DAG_MAX_VARIANTS + 1 + DAG_CROWD_LEVELS + DAG_SHARE_VARIANTS][2][4] = {};  // [task-queue variant][target][EvalMode]
   // capture state (fit.rs:116-125)
   int best_idx = -1;  // which ping-pong buffer holds the best evaluation so far
   double best_lml = -std::numeric_limits<double>::infinity();
@@ -816,6 +820,18 @@ struct Problem : ProblemBase {
   std::unique_ptr<std::atomic<int>[]> busy_slots_;  // per device: slots inside an optimiser run (0: not known -> all of them)
   int dag_ntasks = 0, dag_nwg = 0;          // dag_nwg: workgroups of the default variant (all slots busy)
   int dag_nvar_ = 1, dag_ncrowd_ = 0;       // variants [1..dag_nvar_] for this fit's own busy slots, then dag_ncrowd_ crowded-device levels
+  // Unequal shares (slot_share.hpp; HBEGP_RUN_BALANCE, read when the problem is created): variants [nvar + ncrowd + 1] = lead and
+  // [+ 2] = lag, 0 = none built.  A fit tells the problem which devices run one optimiser run per slot (balance_dev_) and keeps
+  // every slot's progress (slot_running_ / slot_done_, [device * n_slots + slot]); variant_now asks the policy with them.
+  int dag_nshare_ = 0;
+  int share_hyst_ = SLOT_SHARE_HYSTERESIS;
+  int slot_maxeval_ = 0;
+  std::vector<int> share_force_;            // HBEGP_RUN_BALANCE_FORCE: the class of every slot, pinned (tests)
+  std::vector<char> balance_dev_;           // per device
+  std::unique_ptr<std::atomic<int>[]> slot_running_, slot_done_;
+  // set for good by the first evaluation that finds another fit in flight on its device: such a fit keeps even shares to its
+  // end, also after the other fit has left (several fits on a context: the crowded-device levels are their rule)
+  mutable std::atomic<int> not_alone_{0};
   unsigned long long dag_wait_ticks_ = 200000000ull;  // bound of one dependency wait (100 MHz ticks), see init()
   size_t dag_ctrl_bytes = 0;                // one region of control words (queue head + counters)
   // A lazy fit's slots hold two regions: the second is the K^-1-only queue's.  The first kernel of every evaluation clears both
@@ -1075,15 +1091,46 @@ struct Problem : ProblemBase {
         // same tasks, same bits -- fewer workgroups per launch, so that all the launches in flight are resident)
         dag_nvar_ = nvar;
         dag_ncrowd_ = (adapt && n_slots > 1) ? DAG_CROWD_LEVELS : 0;
-        dag_var.assign(nvar + 1 + dag_ncrowd_, DagVariant());
-        for (int v = 1; v <= nvar + dag_ncrowd_; ++v) {
+        // [nvar + ncrowd + 1], [+ 2]: the lead and the lag share of a fit whose runs have drifted apart (slot_share.hpp) -- again the
+        // same tasks and bits, ordered for another workgroup count.  Only where the policy can ever be asked: several slots, and the
+        // busy-count variants in use.  HBEGP_RUN_BALANCE=0: none are built and variant_now is what it was.
+        int share_wg[DAG_SHARE_VARIANTS] = {slot_share_lead_wg(dag_nwg, n_slots, cus), slot_share_lag_wg(dag_nwg, n_slots, cus)};
+        if (const char* wgs = getenv("HBEGP_RUN_BALANCE_WG")) {
+          int a = 0, b = 0;
+          if (sscanf(wgs, "%d,%d", &a, &b) == 2 && a > 0 && b > 0) { share_wg[0] = std::min(a, cus); share_wg[1] = std::min(b, cus); }
+        }
+        const char* share_force = getenv("HBEGP_RUN_BALANCE_FORCE");
+        share_force_.clear();
+        if (share_force && *share_force) {
+          for (const char* q = share_force; *q;) {
+            const size_t len = strcspn(q, ",");
+            share_force_.push_back(strncmp(q, "lag", 3) == 0 ? SLOT_SHARE_LAG : (strncmp(q, "lead", 4) == 0 ? SLOT_SHARE_LEAD : SLOT_SHARE_EVEN));
+            q += len;
+            if (*q == ',') ++q;
+          }
+          share_force_.resize(n_slots, SLOT_SHARE_EVEN);
+        }
+        share_hyst_ = std::max(0, env_int("HBEGP_RUN_BALANCE_HYST", SLOT_SHARE_HYSTERESIS));
+        dag_nshare_ = (adapt && n_slots > 1 && (env_int("HBEGP_RUN_BALANCE", np / NB >= SLOT_SHARE_MIN_BLOCKS ? 1 : 0) != 0 || !share_force_.empty())) ? DAG_SHARE_VARIANTS : 0;
+        if (dag_nshare_) {
+          balance_dev_.assign(c->devs.size(), 0);
+          slot_running_.reset(new std::atomic<int>[c->devs.size() * n_slots]);
+          slot_done_.reset(new std::atomic<int>[c->devs.size() * n_slots]);
+          for (size_t i = 0; i < c->devs.size() * n_slots; ++i) { slot_running_[i].store(0); slot_done_[i].store(0); }
+        }
+        dag_var.assign(nvar + 1 + dag_ncrowd_ + dag_nshare_, DagVariant());
+        for (int v = 1; v <= nvar + dag_ncrowd_ + dag_nshare_; ++v) {
           DagVariant& var = dag_var[v];
           std::shared_ptr<const DagPlan> pv = cached;
           var.nwg = dag_nwg;
           if (v != nvar && adapt) {
-            const int busy = v < nvar ? v : DAG_CROWD_BUSY[v - nvar - 1];
-            var.nwg = std::min(share_of(busy), dag_ntasks);
-            if (v > nvar) var.nwg = std::min(var.nwg, dag_nwg);
+            if (v > nvar + dag_ncrowd_) {
+              var.nwg = std::min(share_wg[v - nvar - dag_ncrowd_ - 1], dag_ntasks);
+            } else {
+              const int busy = v < nvar ? v : DAG_CROWD_BUSY[v - nvar - 1];
+              var.nwg = std::min(share_of(busy), dag_ntasks);
+              if (v > nvar) var.nwg = std::min(var.nwg, dag_nwg);
+            }
             pv = plan_for(var.nwg);
             if (pv->tasks.size() != plan.tasks.size()) { pv = cached; var.nwg = dag_nwg; }  // cannot happen: same task set
           }
@@ -1179,7 +1226,7 @@ struct Problem : ProblemBase {
       (void)hipSetDevice(ctx->devs[di]);
       for (auto& s : slots[di]) {
         if (s.stream) (void)hipStreamSynchronize(s.stream);
-        for (int v = 0; v <= DAG_MAX_VARIANTS + DAG_CROWD_LEVELS; ++v)
+        for (int v = 0; v <= DAG_MAX_VARIANTS + DAG_CROWD_LEVELS + DAG_SHARE_VARIANTS; ++v)
           for (int a = 0; a < 2; ++a)
             for (int b = 0; b < 4; ++b)
               if (s.graph[v][a][b]) (void)hipGraphExecDestroy(s.graph[v][a][b]);
@@ -1544,7 +1591,10 @@ struct Problem : ProblemBase {
 
   // The task-queue variant for an evaluation that starts now on device di: sized for the slots that are inside an optimiser
   // run at this moment (a fit keeps the count; outside a fit every slot is assumed busy).
-  int variant_now(size_t di) const {
+  // si >= 0: the slot that starts the evaluation, inside a fit's optimiser run -- the one caller for which the share policy
+  // (slot_share.hpp) is asked, and only when every slot of the problem is busy on the device, each with a run of its own, and the
+  // device is not crowded.  Everything else gets the busy-count / crowded-device variant as ever.
+  int variant_now(size_t di, int si = -1) const {
     if (!dag_ || dag_var.size() < 2) return 1;
     const int nvar = dag_nvar_;
     const int busy = busy_slots_ ? busy_slots_[di].load(std::memory_order_relaxed) : 0;
@@ -1558,12 +1608,35 @@ struct Problem : ProblemBase {
         return nvar + 1 + l;
       }
     }
+    if (si >= 0 && dag_nshare_ > 0 && ctx->devs[di] < MAX_DEVS && g_dev_fits[ctx->devs[di]].load(std::memory_order_relaxed) > 1)
+      not_alone_.store(1, std::memory_order_relaxed);
+    if (si >= 0 && dag_nshare_ > 0 && busy == n_slots && n_slots >= 2 && n_slots <= SLOT_SHARE_MAX_SLOTS && balance_dev_[di] &&
+        !not_alone_.load(std::memory_order_relaxed)) {
+      int share[SLOT_SHARE_MAX_SLOTS];
+      if (!share_force_.empty()) {
+        for (int i = 0; i < n_slots; ++i) share[i] = share_force_[i];
+      } else {
+        int running[SLOT_SHARE_MAX_SLOTS], done[SLOT_SHARE_MAX_SLOTS], cap[SLOT_SHARE_MAX_SLOTS];
+        for (int i = 0; i < n_slots; ++i) {
+          running[i] = slot_running_[di * n_slots + i].load(std::memory_order_relaxed);
+          done[i] = slot_done_[di * n_slots + i].load(std::memory_order_relaxed);
+          cap[i] = slot_maxeval_;
+        }
+        slot_shares(n_slots, running, done, cap, share_hyst_, share);
+      }
+      if (share[si] != SLOT_SHARE_EVEN) return nvar + dag_ncrowd_ + (share[si] == SLOT_SHARE_LEAD ? 1 : 2);
+    }
     return busy <= 0 ? nvar : std::min(busy, nvar);
+  }
+  // SLOT_SHARE_LEAD / _LAG when variant v is one of the two unequal shares, SLOT_SHARE_EVEN otherwise
+  int share_of_variant(int v) const {
+    if (!dag_ || dag_nshare_ <= 0 || v <= dag_nvar_ + dag_ncrowd_) return SLOT_SHARE_EVEN;
+    return v == dag_nvar_ + dag_ncrowd_ + 1 ? SLOT_SHARE_LEAD : SLOT_SHARE_LAG;
   }
   // Run one evaluation on (device index di, slot si) into ping-pong buffer `target`; blocks until the result is on the host.
   // mode: EvalMode (a bool converts as it always meant: false = lml + K^-1, true = the whole evaluation).  EVAL_GRAD_ONLY continues
   // the slot's last EVAL_LML_ONLY evaluation (same target, parameters still in dP): *lml is not touched, grad must not be null.
-  int run_eval(size_t di, int si, int target, int mode, bool use_graph, double* lml, double* grad) {
+  int run_eval(size_t di, int si, int target, int mode, bool use_graph, double* lml, double* grad, bool in_run = false) {
     Slot<T>& s = slots[di][si];
     HIPCHECK(hipSetDevice(s.dev));
     static const bool graphs_on = env_int("HBEGP_NO_GRAPH", 0) == 0;
@@ -1576,7 +1649,7 @@ struct Problem : ProblemBase {
       reinterpret_cast<volatile unsigned long long*>(&s.hOut->seq)[0] = 0;
       std::atomic_thread_fence(std::memory_order_seq_cst);
     } else {
-      s.dag_variant = variant_now(di);
+      s.dag_variant = variant_now(di, in_run ? si : -1);
       s.hP->seq = ++s.seq;
     }
     const auto t_launch = std::chrono::steady_clock::now();
@@ -3514,8 +3587,15 @@ static int check_paths_minimize(hbegp_paths* paths, const T* starts, int R, cons
 // stays zero / NULL.  Nothing is read or written beyond min(struct_size, sizeof).
 // What the calling thread's most recent fit did (hbegp_last_fit_stats): evaluations, failed ones, and the line-search trials
 // that ended after their first phase (lml only: no K^-1, no gradient).
-struct LastFitStats { int n_evals, n_not_pd, n_lml_only; };
-static thread_local LastFitStats g_last_fit_stats = {0, 0, 0};
+// Per optimiser run (the first HBEGP_STATS_MAX_RUNS of them): when its last evaluation was over, in ms since the fit was called,
+// and what it launched -- whole evaluations, first phases that stayed alone, first phases followed by a second one, and how many of
+// its evaluations ran with a lead / a lag share of the compute units (slot_share.hpp).
+struct RunStats { double end_ms = 0; int fused = 0, lml_only = 0, phase2 = 0, lead = 0, lag = 0; };
+struct LastFitStats {
+  int n_evals = 0, n_not_pd = 0, n_lml_only = 0, n_runs = 0;
+  RunStats run[HBEGP_STATS_MAX_RUNS];
+};
+static thread_local LastFitStats g_last_fit_stats;
 
 static int read_fit_options(const hbegp_fit_options* in, hbegp_fit_options* out) {
   *out = hbegp_fit_options{};
@@ -3540,7 +3620,7 @@ static int do_fit(hbegp_ctx* ctx, const T* X, const T* y, int n, int d, double n
                   const double* hi, const double* starts, int n_restarts, const hbegp_fit_options* opt_in,
                   double* theta_best, double* lml_best, hbegp_model** model_out, bool loo = false) {
   hbegp_fit_options opt{};
-  g_last_fit_stats = {0, 0, 0};  // a fit that fails leaves zeros, not the previous fit's numbers
+  g_last_fit_stats = LastFitStats{};  // a fit that fails leaves zeros, not the previous fit's numbers
   if (int e = read_fit_options(opt_in, &opt)) return e;
   if (opt.maxeval <= 0) opt.maxeval = 150;
   const int p = d + 2;
@@ -3561,6 +3641,13 @@ static int do_fit(hbegp_ctx* ctx, const T* X, const T* y, int n, int d, double n
     for (int di = 0; di < ndev; ++di) n_slots = std::max(n_slots, runs_on[di]);
   static const int timing = env_int("HBEGP_TIMING", 0);
   const auto tf0 = std::chrono::steady_clock::now();
+  auto since_start_ms = [tf0] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tf0).count(); };
+  std::vector<RunStats> run_stats(nruns);  // every run is written by the one thread that drives it
+  struct FitsInFlight {  // counted from here on, not from the first evaluation: a second fit sees this one while it still sets up
+    const hbegp_ctx* c;
+    explicit FitsInFlight(const hbegp_ctx* cc) : c(cc) { for (int dev : c->devs) if (dev < MAX_DEVS) g_dev_fits[dev].fetch_add(1); }
+    ~FitsInFlight() { for (int dev : c->devs) if (dev < MAX_DEVS) g_dev_fits[dev].fetch_sub(1); }
+  } fits_in_flight(ctx);
   // like_fit: the evaluation path (launches / task queue) is a function of n alone, also for a fit with one slot per device
   // (n_restarts = 0, or no more runs than devices): `extend` at the fitted theta then repeats the fit's own evaluation bit for bit
   SmallArrival arrival;  // other threads' small fits wait (briefly) for this one's runs before they launch: SmallBatcher
@@ -3721,7 +3808,11 @@ static int do_fit(hbegp_ctx* ctx, const T* X, const T* y, int n, int d, double n
         }
         std::atomic_thread_fence(std::memory_order_acquire);
       };
-      for (int r = 0; r < nruns; ++r) wait_run(r, ws[r].di);
+      for (int r = 0; r < nruns; ++r) {
+        wait_run(r, ws[r].di);
+        run_stats[r].end_ms = since_start_ms();  // (when the host saw the run's word: the runs are waited for in run order)
+        run_stats[r].fused = hruns[r].res.n_evals;
+      }
       runs_over = true;
       int total_evals = 0, total_not_pd = 0, trace_n = 0;
       for (int r = 0; r < nruns; ++r) {
@@ -3752,7 +3843,9 @@ static int do_fit(hbegp_ctx* ctx, const T* X, const T* y, int n, int d, double n
       if (opt.trace_count) *opt.trace_count = trace_n;
       if (opt.n_evals) *opt.n_evals = total_evals;
       if (opt.n_not_pd) *opt.n_not_pd = total_not_pd;
-      g_last_fit_stats = {total_evals, total_not_pd, 0};  // the persistent kernel evaluates every point whole
+      g_last_fit_stats.n_evals = total_evals;
+      g_last_fit_stats.n_not_pd = total_not_pd;
+      g_last_fit_stats.n_lml_only = 0;  // the persistent kernel evaluates every point whole
       n_evals.store(total_evals);
     } catch (...) {
       for (int di = 0; di < ndev && di < (int)prob.slots.size(); ++di) {  // let the launched kernels finish before their workspaces go
@@ -3768,6 +3861,12 @@ static int do_fit(hbegp_ctx* ctx, const T* X, const T* y, int n, int d, double n
   // how many slots of each device are inside an optimiser run: the task-queue launches are sized for that (Problem::DagVariant)
   if (prob.busy_slots_)
     for (int di = 0; di < ndev; ++di) prob.busy_slots_[di].store(std::min(runs_on[di], max_conc));
+  // unequal shares (slot_share.hpp) only on devices where every slot drives ONE run: a slot that takes several runs in turn (8 runs
+  // over 3 slots) has no single progress count to compare
+  if (prob.dag_nshare_ > 0) {
+    prob.slot_maxeval_ = opt.maxeval;
+    for (int di = 0; di < ndev; ++di) prob.balance_dev_[di] = runs_on[di] <= max_conc && runs_on[di] == prob.n_slots;
+  }
   auto worker = [&](int di, int si) {
     struct Leave {
       std::atomic<int>* busy;
@@ -3790,6 +3889,12 @@ static int do_fit(hbegp_ctx* ctx, const T* X, const T* y, int n, int d, double n
         if (r == 0) for (int i = 0; i < p; ++i) x[i] = theta0[i];
         else for (int i = 0; i < p; ++i) x[i] = starts[(size_t)(r - 1) * p + i];
         int eval_idx = 0;
+        RunStats& rs = run_stats[r];
+        std::atomic<int>* progress = prob.dag_nshare_ > 0 ? &prob.slot_done_[(size_t)di * prob.n_slots + si] : nullptr;
+        if (progress) {
+          progress->store(0, std::memory_order_relaxed);
+          prob.slot_running_[(size_t)di * prob.n_slots + si].store(1, std::memory_order_relaxed);
+        }
         // trial: the evaluation is a line-search trial of `ls` (lbfgs_is_trial) and the problem evaluates those lazily -- the lml
         // first; K^-1 and the gradient only if lbfgs_advance will read the gradient (the Armijo test accepts the value:
         // lbfgs_trial_accepted) or the capture rule below will keep the evaluation (a new best lml: a rejected trial can lie
@@ -3801,7 +3906,7 @@ static int do_fit(hbegp_ctx* ctx, const T* X, const T* y, int n, int d, double n
           double lml;
           int st;
           if (ls) {
-            st = prob.run_eval((size_t)di, si, target, Problem<T>::EVAL_LML_ONLY, true, &lml, nullptr);
+            st = prob.run_eval((size_t)di, si, target, Problem<T>::EVAL_LML_ONLY, true, &lml, nullptr, true);
             const bool new_best = st == HBEGP_OK && (s.best_idx < 0 || lml > s.best_lml);
             if (st == HBEGP_OK && (new_best || lbfgs_trial_accepted(*ls, -lml))) {
               // (a gradient that is not finite fails the whole evaluation here as in the fused form: +inf, never captured.  The one
@@ -3809,19 +3914,26 @@ static int do_fit(hbegp_ctx* ctx, const T* X, const T* y, int n, int d, double n
               // rejected and not a new best, keeps its finite lml and is not counted in n_not_pd -- its gradient is never formed)
               st = prob.run_eval((size_t)di, si, target, Problem<T>::EVAL_GRAD_ONLY, true, nullptr, grad);
               if (st != HBEGP_OK) lml = -std::numeric_limits<double>::infinity();
+              rs.phase2++;
             } else {
               for (int j = 0; j < p; ++j) grad[j] = 0.0;  // never read
               n_lml_only.fetch_add(1);
+              rs.lml_only++;
             }
           } else {
-            st = prob.run_eval((size_t)di, si, target, !loo, true, &lml, loo ? nullptr : grad);
+            st = prob.run_eval((size_t)di, si, target, !loo, true, &lml, loo ? nullptr : grad, true);
+            rs.fused++;
           }
+          const int share = prob.share_of_variant(s.dag_variant);
+          if (share == SLOT_SHARE_LEAD) rs.lead++;
+          if (share == SLOT_SHARE_LAG) rs.lag++;
           if (loo) {
             if (st == HBEGP_OK) st = prob.loo_on_slot((size_t)di, si, &lml, grad);
             else for (int j = 0; j < p; ++j) grad[j] = 0.0;
             if (st != HBEGP_OK && st != HBEGP_NOT_PD) throw std::runtime_error(g_last_error);
           }
           const int my_eval = eval_idx++;
+          if (progress) progress->store(eval_idx, std::memory_order_relaxed);
           n_evals.fetch_add(1);
           if (st != HBEGP_OK) n_not_pd.fetch_add(1);
           if (opt.trace_cap > 0) {
@@ -3860,6 +3972,8 @@ static int do_fit(hbegp_ctx* ctx, const T* X, const T* y, int n, int d, double n
           const double f = obj(lbfgs_request(*ls), g.data(), trial ? ls.get() : nullptr);
           if (!lbfgs_advance(*ls, f, g.data())) break;
         }
+        rs.end_ms = since_start_ms();
+        if (progress) prob.slot_running_[(size_t)di * prob.n_slots + si].store(0, std::memory_order_relaxed);
       }
     } catch (const HipError& he) {
       hip_fail(he);
@@ -3901,9 +4015,18 @@ static int do_fit(hbegp_ctx* ctx, const T* X, const T* y, int n, int d, double n
   if (opt.trace_count) *opt.trace_count = trace_n;
   if (opt.n_evals) *opt.n_evals = n_evals.load();
   if (opt.n_not_pd) *opt.n_not_pd = n_not_pd.load();
-  g_last_fit_stats = {n_evals.load(), n_not_pd.load(), n_lml_only.load()};
+  g_last_fit_stats.n_evals = n_evals.load();
+  g_last_fit_stats.n_not_pd = n_not_pd.load();
+  g_last_fit_stats.n_lml_only = n_lml_only.load();
   if (!err.empty()) return fail(HBEGP_EHIP, "%s", err.c_str());
   }  // host-driven optimiser runs
+
+  g_last_fit_stats.n_runs = std::min(nruns, (int)HBEGP_STATS_MAX_RUNS);
+  for (int r = 0; r < g_last_fit_stats.n_runs; ++r) g_last_fit_stats.run[r] = run_stats[r];
+  if (timing)
+    for (int r = 0; r < nruns; ++r)
+      fprintf(stderr, "fit: run %d ended at %.2f ms: %d fused, %d lml-only, %d two-phase evaluations; %d with a lead share, %d with a lag share\n", r,
+              run_stats[r].end_ms, run_stats[r].fused, run_stats[r].lml_only, run_stats[r].phase2, run_stats[r].lead, run_stats[r].lag);
 
   // global arg-max over the per-slot captures, ties -> lowest (run, eval)
   int bdi = -1, bsi = -1;
@@ -5175,6 +5298,13 @@ int hbegp_last_fit_stats(hbegp_fit_stats* out) {
   full.n_evals = g_last_fit_stats.n_evals;
   full.n_not_pd = g_last_fit_stats.n_not_pd;
   full.n_lml_only = g_last_fit_stats.n_lml_only;
+  full.n_runs = g_last_fit_stats.n_runs;
+  for (int r = 0; r < full.n_runs; ++r) {
+    const RunStats& rs = g_last_fit_stats.run[r];
+    full.run_end_ms[r] = rs.end_ms;
+    full.run_fused[r] = rs.fused; full.run_lml_only[r] = rs.lml_only; full.run_phase2[r] = rs.phase2;
+    full.run_lead[r] = rs.lead; full.run_lag[r] = rs.lag;
+  }
   memcpy(out, &full, std::min(out->struct_size, sizeof(full)));  // nothing beyond the caller's struct is written
   return HBEGP_OK;
 }
@@ -5216,6 +5346,22 @@ int hbegp_debug_lbfgs_decisions(int n, const double* x0, const double* lo, const
   GUARD_BEGIN
   return lbfgs_replay_impl(n, x0, lo, hi, maxeval, memory, fixed_work, count, f, g, requested, trial, accepted, took, n_requested);
   GUARD_END
+}
+
+// The share policy of a fit's slots as it is (slot_share.hpp), for the tests.  hysteresis < 0: the default.  lead_wg / lag_wg (may
+// be NULL): the launch sizes the defaults give for `even_wg` workgroups per even launch on `cus` compute units.
+int hbegp_debug_slot_shares(int n_slots, const int* running, const int* done, const int* maxeval, int hysteresis, int* share, int even_wg,
+                            int cus, int* lead_wg, int* lag_wg) {
+  if (n_slots < 1 || !running || !done || !maxeval || !share) return fail(HBEGP_EINVAL, "bad argument");
+  slot_shares(n_slots, running, done, maxeval, hysteresis < 0 ? SLOT_SHARE_HYSTERESIS : hysteresis, share);
+  if (lead_wg) *lead_wg = slot_share_lead_wg(even_wg, n_slots, cus);
+  if (lag_wg) *lag_wg = slot_share_lag_wg(even_wg, n_slots, cus);
+  return HBEGP_OK;
+}
+
+// Fits in flight on a device id, counted from the moment hbegp_fit_* is called (tests: start a second fit beside a first one).
+int hbegp_debug_fits_in_flight(int device_id) {
+  return device_id >= 0 && device_id < MAX_DEVS ? g_dev_fits[device_id].load() : 0;
 }
 
 // The three queues of a task-queue evaluation for the tests: which = 0 the full plan (with the K^-1 tiles), 1 the plan without

@@ -17,6 +17,7 @@ PATHS_MAX_FEATURES, PATHS_MAX_PATHS = 16384, 1024  # HBEGP_PATHS_MAX_* of includ
 CEI_MAX_CONSTRAINTS = 8  # HBEGP_CEI_MAX_CONSTRAINTS of include/hbegp.h
 MES_MAX_SAMPLES = 1024  # HBEGP_MES_MAX_SAMPLES of include/hbegp.h
 EHVI_ND_MAX_BOXES = 1048576  # HBEGP_EHVI_ND_MAX_BOXES of include/hbegp.h
+STATS_MAX_RUNS = 16  # HBEGP_STATS_MAX_RUNS of include/hbegp.h
 
 
 class HbegpError(RuntimeError):
@@ -51,7 +52,10 @@ class FitOptions(C.Structure):
 class FitStats(C.Structure):
     """hbegp_fit_stats; `struct_size` is filled in by __init__ (the library writes min(struct_size, its own size))."""
 
-    _fields_ = [("struct_size", C.c_size_t), ("n_evals", C.c_int), ("n_not_pd", C.c_int), ("n_lml_only", C.c_int)]
+    _fields_ = [("struct_size", C.c_size_t), ("n_evals", C.c_int), ("n_not_pd", C.c_int), ("n_lml_only", C.c_int), ("n_runs", C.c_int),
+                ("run_end_ms", C.c_double * STATS_MAX_RUNS), ("run_fused", C.c_int * STATS_MAX_RUNS),
+                ("run_lml_only", C.c_int * STATS_MAX_RUNS), ("run_phase2", C.c_int * STATS_MAX_RUNS),
+                ("run_lead", C.c_int * STATS_MAX_RUNS), ("run_lag", C.c_int * STATS_MAX_RUNS)]
 
     def __init__(self, *a, **k):
         super().__init__(*a, **k)
@@ -191,6 +195,8 @@ SIGNATURES = {
     "hbegp_debug_lbfgs_decisions": (C.c_int, [C.c_int, _dp, _dp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _ip, _ip, _ip, _ip]),
     "hbegp_debug_dag_queues": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip, _ip, C.c_int, C.c_char_p,
                                          C.c_int]),
+    "hbegp_debug_slot_shares": (C.c_int, [C.c_int, _ip, _ip, _ip, C.c_int, _ip, C.c_int, C.c_int, _ip, _ip]),
+    "hbegp_debug_fits_in_flight": (C.c_int, [C.c_int]),
     "hbegp_debug_dag_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip, _ip, _ip, _dp, _dp, _dp, C.c_char_p,
                                        C.c_int]),
     "hbegp_minimize_by_gradient": (C.c_double, [OBJECTIVE_FN, _vp, _dp, _dp, _dp, C.c_int, C.c_int]),

@@ -273,6 +273,11 @@ class FittedKernel:
         stats = _lib.FitStats()
         _lib.check(lib.hbegp_last_fit_stats(C.byref(stats)))  # this thread's fit, the one above
         fk.n_lml_only = stats.n_lml_only
+        # per optimiser run (hbegp_fit_stats): when its last evaluation was over, in ms since the fit was called, and what it launched
+        k = stats.n_runs
+        fk.run_end_ms = np.array(stats.run_end_ms[:k], dtype=np.float64)
+        fk.run_counts = {name: np.array(getattr(stats, "run_" + name)[:k], dtype=np.int64)
+                         for name in ("fused", "lml_only", "phase2", "lead", "lag")}
         fk.theta_best = theta_best
         if symbol == "hbegp_fit_loo":
             fk.loo_best = lml_best.value

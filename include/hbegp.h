@@ -187,11 +187,25 @@ typedef struct hbegp_fit_options {
  * lml alone -- line-search trials that the optimiser rejected and the capture rule did not keep, so that nobody would have read
  * their K^-1 or gradient (0 with HBEGP_LAZY_GRAD=0, for fits of at most 128 rows, leave-one-out fits, and fits that trace
  * gradients). */
+#define HBEGP_STATS_MAX_RUNS 16
 typedef struct hbegp_fit_stats {
   size_t struct_size;
   int n_evals;
   int n_not_pd;
   int n_lml_only;
+  /* Per optimiser run, for the first n_runs = min(1 + n_restarts, HBEGP_STATS_MAX_RUNS) runs.  run_end_ms: wall time from the call
+   * of the fit to the end of the run's last evaluation (fits of at most 128 rows: to the moment the host saw the run's result; the
+   * runs are waited for in run order).  run_fused: evaluations launched whole; run_lml_only: line-search trials that ended after
+   * their first phase; run_phase2: trials whose second phase (K^-1 and the gradient) ran.  run_lead / run_lag: evaluations among
+   * those that ran with a lead / a lag share of the compute units (HBEGP_RUN_BALANCE); 0 where every launch had
+   * the even share. */
+  int n_runs;
+  double run_end_ms[HBEGP_STATS_MAX_RUNS];
+  int run_fused[HBEGP_STATS_MAX_RUNS];
+  int run_lml_only[HBEGP_STATS_MAX_RUNS];
+  int run_phase2[HBEGP_STATS_MAX_RUNS];
+  int run_lead[HBEGP_STATS_MAX_RUNS];
+  int run_lag[HBEGP_STATS_MAX_RUNS];
 } hbegp_fit_stats;
 #define HBEGP_FIT_STATS_INIT { sizeof(hbegp_fit_stats) }
 int hbegp_last_fit_stats(hbegp_fit_stats* out);
@@ -764,6 +778,15 @@ int hbegp_debug_lbfgs_decisions(int n, const double* x0, const double* lo, const
  * as in hbegp_debug_dag_plan. */
 int hbegp_debug_dag_queues(int nblocks, int bk, int small_h, int nwg, int fine, int big128, int which, int* ntasks, int* tasks, int cap,
                            char* err, int errlen);
+
+/* ---- test hooks (host only, no GPU): the share policy of a fit's slots (csrc/slot_share.hpp).  Per slot of one
+ * problem on one device: running[i] != 0 while the slot is inside an optimiser run, done[i] the evaluations that run has completed,
+ * maxeval[i] its cap.  share[i] receives 0 (even), 1 (lead) or 2 (lag).  hysteresis < 0: the library's default.  lead_wg / lag_wg
+ * (may be NULL): the default workgroup counts of a lead / lag launch where an even launch has even_wg workgroups on cus compute
+ * units.  hbegp_debug_fits_in_flight: hbegp_fit_* / hbegp_fit_loo_* calls in flight on a device id, counted from the call on. */
+int hbegp_debug_slot_shares(int n_slots, const int* running, const int* done, const int* maxeval, int hysteresis, int* share, int even_wg,
+                            int cus, int* lead_wg, int* lag_wg);
+int hbegp_debug_fits_in_flight(int device_id);
 
 /* ---- test hook (tests/test_gpu_pool_hygiene.py): how many blocks of the device pool, and how many bytes, have been filled on
  * hand-out under HBEGP_POOL_POISON (1: the word 0x40490FDB, finite in both element types; 2: 0x7FF80000, a quiet NaN in both)
