@@ -4,8 +4,10 @@ every wait for a full count, no unordered access to a tile of W1/W2 -- and the c
 import ctypes as C
 import os
 
+import numpy as np
 import pytest
 
+import big128_cases as BC
 from hbetune_rs_amd import _lib
 
 
@@ -146,15 +148,72 @@ def test_plan_builder_and_optimiser_are_clean_under_sanitizers(tmp_path):
 
 @pytest.mark.parametrize("nb", [2, 3, 5, 8, 16, 24, 32, 33, 48])
 def test_plans_with_128x128_tiles_are_sound(nb, monkeypatch):
-    # HBEGP_DAG_BIG128: the deep products without beta = 1 as 128x128 tiles (round 4; the default for multi-slot problems from 32
-    # blocks on): fewer tasks, the same flops, sound in every plan -- and never a beta = 1 task of that kind (the checker rejects one)
+    # HBEGP_DAG_BIG128 = 1: the deep products without beta = 1 as 128x128 tiles; 2 (the default for a fit's slots from 32 blocks on and
+    # for any problem from 64): the beta = 1 products too, whose old values the tile fetches in its epilogue.  Fewer tasks, the same
+    # flops, sound in every plan -- and never a 128x128 task that continues a sum (DAGF_CINIT: the checker rejects one)
     _, base = plan(nb, 16, 4, 96, 1 | 4 | 8)
-    monkeypatch.setenv("HBEGP_DAG_BIG128", "1")
-    for bk in (16, 32):
-        for small_h, nwg, fine in [(4, 96, 1 | 4 | 8), (4, 256, 1 | 4 | 8 | 16), (8, 85, 1 | 4), (0, 3, 1 | 4 | 8)]:
-            rc, info = plan(nb, bk, small_h, nwg, fine)
-            assert rc == 0, (nb, bk, small_h, nwg, fine, info["err"])
-            assert info["gflop"] == pytest.approx(base["gflop"], rel=1e-12)
-    if nb >= 8:
-        _, big = plan(nb, 16, 4, 96, 1 | 4 | 8)
-        assert big["ntasks"] < base["ntasks"]
+    fewer = base["ntasks"]
+    for big128 in (1, 2):
+        monkeypatch.setenv("HBEGP_DAG_BIG128", str(big128))
+        for bk in (16, 32):
+            for small_h, nwg, fine in [(4, 96, 1 | 4 | 8), (4, 256, 1 | 4 | 8 | 16), (8, 85, 1 | 4), (0, 3, 1 | 4 | 8)]:
+                rc, info = plan(nb, bk, small_h, nwg, fine)
+                assert rc == 0, (nb, big128, bk, small_h, nwg, fine, info["err"])
+                assert info["gflop"] == pytest.approx(base["gflop"], rel=1e-12)
+        if nb >= 8:
+            _, big = plan(nb, 16, 4, 96, 1 | 4 | 8)
+            assert big["ntasks"] < fewer  # 1: fewer tasks than 128x64 tiles alone; 2: fewer again
+            fewer = big["ntasks"]
+
+
+def queue(nb, bk, small_h, nwg, fine, big128, which):
+    lib = _lib.load()
+    nt = C.c_int()
+    err = C.create_string_buffer(400)
+    cap = 40000
+    tasks = np.zeros((cap, 6), dtype=np.int32)
+    rc = lib.hbegp_debug_dag_queues(nb, bk, small_h, nwg, fine, big128, which, C.byref(nt), tasks.ctypes.data_as(C.POINTER(C.c_int)), cap, err, 400)
+    assert nt.value <= cap
+    return rc, tasks[: nt.value].copy(), err.value.decode()
+
+
+@pytest.mark.parametrize("case,several_slots", [pytest.param(c, m, id=f"{c[0][0]}-n{c[1]}-{'fit' if m else 'one'}") for c, m in BC.PLANNED])
+def test_the_forced_gpu_cases_hold_128x128_tiles_of_every_class_they_claim(case, several_slots):
+    # What the device cannot assert: that the small problems tests/test_gpu_big128.py forces really run the tile.  Each of its
+    # configurations with its own (blocks, stage depth, small_h, fine bits), at the launch sizes it uses (all workgroups of one slot,
+    # a fit's even / lead / lag shares, the forced 3, 40 and 128): the full queue and the two queues of a trial evaluated in two
+    # phases pass the checker and hold at least one 128x128 task of every claimed class; BIG128 = 1 has the same tasks without
+    # beta = 1, and BIG128 = 0 none at all.
+    (name, _, small_h, _), n, dtypes, want = case
+    nb, fine = BC.blocks(n), BC.fine_bits(case[0], several_slots)
+    for dtype in dtypes:
+        bk = BC.stage_depth(dtype)
+        sets = {}
+        for nwg in (256, 96, 72, 128, 3, 40):
+            for which in (0, 1, 2):
+                rc, tasks, err = queue(nb, bk, small_h, nwg, fine, 2, which)
+                assert rc == 0, (name, n, dtype, nwg, which, err)
+                got = BC.classes(tasks)
+                for cls in BC.claimed(want, which):
+                    assert got[cls] > 0, (name, n, dtype, nwg, which, cls, got)
+                # the launch size orders the queue, it does not choose the tiles
+                assert sets.setdefault(which, got) == got, (name, n, dtype, nwg, which)
+        for which in (0, 1, 2):
+            rc, one, err = queue(nb, bk, small_h, 96, fine, 1, which)
+            assert rc == 0, (name, n, dtype, which, err)
+            got = BC.classes(one)
+            assert got["ACC"] == 0 and got["all"] == sets[which]["all"] - sets[which]["ACC"], (name, n, dtype, which, got)
+            rc, none, err = queue(nb, bk, small_h, 96, fine, 0, which)
+            assert rc == 0 and BC.classes(none)["all"] == 0, (name, n, dtype, which, err)
+
+
+def test_the_issue_table_of_128x128_task_counts():
+    # the counts the cases were chosen by (f64, 96 workgroups, one slot): 128x128 tasks, then those with beta = 1, alpha = -1, an
+    # operand read along rows, and the K^-1 tiles -- 6 blocks is the smallest size with every class, 17 the first at which the
+    # recursion with small nodes of 8 blocks has such tiles outside K^-1
+    table = [(BC.RL_DC, 4, (11, 2, 2, 6, 6)), (BC.RL_DC, 6, (38, 13, 13, 15, 15)), (BC.RL_DC, 9, (149, 49, 65, 72, 36)), (BC.RL_PROG, 6, (68, 13, 28, 45, 15)),
+             (BC.REC_8, 16, (120, 0, 0, 120, 120)), (BC.REC_8, 17, (372, 36, 100, 272, 136)), (BC.REC_0, 6, (51, 5, 13, 38, 15))]
+    for p, nb, want in table:
+        rc, tasks, err = queue(nb, 16, p[2], 96, p[3], 2, 0)
+        got = BC.classes(tasks)
+        assert rc == 0 and (got["all"], got["ACC"], got["NEG"], got["KM"], got["CKINV"]) == want, (p[0], nb, got, err)
