@@ -336,6 +336,12 @@ void launch_ehvi_nd(const CeiArgs<T>& a, int m, int d, const double* thr, const 
 template <typename T>
 void launch_mes(const T* mean, const T* var, const T* dmean, const T* dvar, int m, int d, const double* ystar, int S, int want_grad,
                 double* mes, T* grad, int* best, hipStream_t s);
+// the confidence bound mu + kappa sigma (hbegp_confidence_bound; cb_kernel: 2^ceil(log2 d) lanes per candidate):
+// mean, var [m] and, with want_grad, dmean, dvar [m][d] of ONE model; kappa travels in the kernel's arguments.  Out: cb[m],
+// grad[m][d] (want_grad), *best = the FIRST index of the minimum of cb (argmin_first_kernel; NaN never wins; m >= 1).
+template <typename T>
+void launch_cb(const T* mean, const T* var, const T* dmean, const T* dvar, int m, int d, double kappa, int want_grad, double* cb, T* grad,
+               int* best, hipStream_t s);
 // batch expected improvement by Monte Carlo (hbegp_qei; qei_batch_kernel: one workgroup per batch of q points).  Rows b q .. b q + q - 1
 // of Xs [B q][d], Q [mp][np], mean, dmean [mp][d] and W [d][mp][np] (W and dmean are read only with want_grad); z [S][q] shared by
 // the batches; noise = 1e-5 + jitter.  Out: qei[B], grad[B q][d] (want_grad), info[B] (0, or 1 + the column whose pivot failed).

@@ -2217,7 +2217,7 @@ struct CallScratch {
 // ---- phase times of the posterior-side calls (hbegp_debug_*_phases) ----------------------------------------------------------
 // One record per kind and calling thread: whether the thread's calls of that kind are timed, and the phase times (ms) of its last
 // timed call of that kind that reached its end.
-enum PhaseKind { PH_POSTERIOR, PH_SELECT, PH_KG, PH_NEI, PH_SENS, PH_EHVI, PH_QEI, PH_LOO, PH_PATHS, PH_CEI, PH_LCEI, PH_MES, PH_EHVI_ND, PH_KINDS };
+enum PhaseKind { PH_POSTERIOR, PH_SELECT, PH_KG, PH_NEI, PH_SENS, PH_EHVI, PH_QEI, PH_LOO, PH_PATHS, PH_CEI, PH_LCEI, PH_MES, PH_EHVI_ND, PH_CB, PH_KINDS };
 struct PhaseRecord {
   bool on = false;
   double ms[5] = {0, 0, 0, 0, 0};
@@ -2289,6 +2289,7 @@ class PhaseClock {
 //   lcei       as cei, the second phase being the log-space kernel with the arg-max
 //   mes        the predict (the uploads .. the last predict or gradient launch), the MES kernel with the arg-max
 //   ehvi_nd    as ehvi with n_obj predicts: each objective's predict on its model's stream, then the box kernel with the arg-max
+//   cb         as mes: the predict, the confidence-bound kernel with the arg-min
 
 // Sigma = K** + noise I - Q Q^T at the candidates into W (lower tiles; m_p x m_p, kmat's identity padding): the candidates'
 // upload, the batched predict's launches (Kstar, the mean, Q = Kstar X^T; the variance too, unused), then kmat_kernel over
@@ -2907,6 +2908,26 @@ static int maximize_marginal(const T* starts, int S, int d, const double* lo, co
   return lockstep_optimize<T, LbfgsState>(starts, S, d, lo, hi, lockstep_options(maxeval, true), finite_gradient_eval<T>(S, d, rows), x_out,
                                           f_out, nevals_out);
 }
+// The same runs on the function itself (hbegp_minimize_confidence_bound): maximize = false is the driver's only difference.
+// nan_start[r] != 0 marks a run whose start has a NaN coordinate: lbfgs_begin would clip that coordinate to lo and the run would
+// set off from a point the caller never named, so every evaluation of such a run counts as failed -- it ends after one, keeps
+// its start and reports +inf; the other runs never see it.
+template <typename T, class Rows>
+static int minimize_marginal(const T* starts, int S, int d, const double* lo, const double* hi, int maxeval, Rows rows, T* x_out,
+                             double* f_out, int* nevals_out) {
+  std::vector<char> nan_start((size_t)S, 0);
+  for (int r = 0; r < S; ++r)
+    for (int k = 0; k < d; ++k)
+      if (starts[(size_t)r * d + k] != starts[(size_t)r * d + k]) nan_start[r] = 1;
+  auto inner = finite_gradient_eval<T>(S, d, rows);
+  auto eval = [&](const T* xs, const int* runs, int cnt, double* val, double* grad, char* ok) mutable -> int {
+    if (const int rc = inner(xs, runs, cnt, val, grad, ok)) return rc;
+    for (int i = 0; i < cnt; ++i)
+      if (nan_start[runs[i]]) ok[i] = 0;
+    return 0;
+  };
+  return lockstep_optimize<T, LbfgsState>(starts, S, d, lo, hi, lockstep_options(maxeval, false), eval, x_out, f_out, nevals_out);
+}
 
 // ---- expected hypervolume improvement of two independent objectives (hbegp_ehvi / hbegp_maximize_ehvi) ----------
 
@@ -3156,6 +3177,19 @@ static int model_mes(hbegp_model* m, const T* Xs, int cnt, const double* ystar, 
                                  });
 }
 
+// ---- the confidence bound mu + kappa sigma (hbegp_confidence_bound / hbegp_minimize_confidence_bound) -----------
+
+// The bound at cnt >= 1 candidates under ONE model: marginal_acquisition over that model without parameters -- kappa travels in the
+// kernel's arguments, as cEI's thresholds do -- and *best the FIRST index of the minimum
+template <typename T>
+static int model_cb(hbegp_model* m, const T* Xs, int cnt, double kappa, double* cb, T* grad, int* best, T* mean_out, T* var_out) {
+  const JoinEvents none;
+  return marginal_acquisition<T>(&m, 1, Xs, cnt, none, PH_CB, "the confidence bound at %d points", nullptr, 0, {cb}, grad, best, mean_out,
+                                 var_out, [&](const MarginalCall<T>& c) {
+                                   launch_cb<T>(c.p.mean[0], c.p.var[0], c.p.dmean[0], c.p.dvar[0], cnt, c.d, kappa, c.want_grad, c.val, c.grad,
+                                                c.best, c.s);
+                                 });
+}
 
 // Batch expected improvement by Monte Carlo (hbegp_qei) for B batches of q points: the B q points go through the batched predict's
 // launches (Kstar, mean, Q) and, with a gradient, the gradient's (dmean; G and W = G X^T), in the order hbegp_predict_grad issues
@@ -5184,6 +5218,72 @@ int hbegp_maximize_mes_f32(hbegp_model* model, const float* starts, int R, const
   return do_maximize_mes<float>(model, starts, R, lo, hi, ystar, S, maxeval, x_out, mes_out, nevals_out);
 }
 int hbegp_debug_mes_phases(int enable, double* phase_ms) { return debug_phases(PH_MES, 2, enable, phase_ms); }
+}  // extern "C"
+
+// argument checks of hbegp_confidence_bound_* / hbegp_minimize_confidence_bound_*: everything is refused before any device call,
+// the checks that need no model first, so that each one has its own message whatever else is wrong
+template <typename T>
+static int check_cb_model(hbegp_model* model) {
+  if (!model) return fail(HBEGP_EINVAL, "NULL model");
+  if (model->is_f32 != (sizeof(T) == 4)) return fail(HBEGP_EINVAL, "model holds %s data", model->is_f32 ? "f32" : "f64");
+  return HBEGP_OK;
+}
+template <typename T>
+static int do_cb(hbegp_model* model, const T* Xs, int m, double kappa, double* cb, T* grad, int* best, T* mean, T* var) {
+  if (!std::isfinite(kappa)) return fail(HBEGP_EINVAL, "kappa is not finite");
+  if (m < 0) return fail(HBEGP_EINVAL, "m must be >= 0 (got %d)", m);
+  if (m > 0 && (!Xs || !cb)) return fail(HBEGP_EINVAL, "Xs/cb is NULL");
+  if (int rc = check_cb_model<T>(model)) return rc;
+  if (best) *best = -1;
+  if (m == 0) return HBEGP_OK;
+  GUARD_BEGIN
+  return model_cb<T>(model, Xs, m, kappa, cb, grad, best, mean, var);
+  GUARD_END
+}
+// hbegp_maximize_ei_*'s checks of S, the box, maxeval and the outputs (the box's order and the starts' places need the model's d, so
+// they follow the model's check); a start has to lie inside the box unless one of its coordinates is a NaN (that run fails alone:
+// minimize_marginal)
+template <typename T>
+static int do_minimize_cb(hbegp_model* model, const T* starts, int S, const double* lo, const double* hi, double kappa, int maxeval, T* x_out,
+                          double* cb_out, int* nevals_out) {
+  if (S < 1) return fail(HBEGP_EINVAL, "S must be >= 1 (got %d)", S);
+  if (!std::isfinite(kappa)) return fail(HBEGP_EINVAL, "kappa is not finite");
+  if (!starts || !lo || !hi || !x_out || !cb_out) return fail(HBEGP_EINVAL, "starts/lo/hi/x_out/cb_out is NULL");
+  if (maxeval < 1) return fail(HBEGP_EINVAL, "maxeval must be >= 1 (got %d)", maxeval);
+  if (int rc = check_cb_model<T>(model)) return rc;
+  const int d = model->d;
+  for (int k = 0; k < d; ++k)
+    if (!(lo[k] <= hi[k])) return fail(HBEGP_EINVAL, "lo[%d] > hi[%d] (%g > %g)", k, k, lo[k], hi[k]);
+  for (int r = 0; r < S; ++r)
+    for (int k = 0; k < d; ++k) {
+      const double v = (double)starts[(size_t)r * d + k];
+      if (v < lo[k] || v > hi[k]) return fail(HBEGP_EINVAL, "start %d lies outside the box (feature %d: %g)", r, k, v);
+    }
+  GUARD_BEGIN
+  return minimize_marginal<T>(
+      starts, S, d, lo, hi, maxeval,
+      [&](const T* xs, int cnt, double* val, T* gr) { return model_cb<T>(model, xs, cnt, kappa, val, gr, nullptr, nullptr, nullptr); }, x_out,
+      cb_out, nevals_out);
+  GUARD_END
+}
+extern "C" {
+int hbegp_confidence_bound_f64(hbegp_model* model, const double* Xs, int m, double kappa, double* cb, double* grad, int* best, double* mean,
+                               double* var) {
+  return do_cb<double>(model, Xs, m, kappa, cb, grad, best, mean, var);
+}
+int hbegp_confidence_bound_f32(hbegp_model* model, const float* Xs, int m, double kappa, double* cb, float* grad, int* best, float* mean,
+                               float* var) {
+  return do_cb<float>(model, Xs, m, kappa, cb, grad, best, mean, var);
+}
+int hbegp_minimize_confidence_bound_f64(hbegp_model* model, const double* starts, int S, const double* lo, const double* hi, double kappa,
+                                        int maxeval, double* x_out, double* cb_out, int* nevals_out) {
+  return do_minimize_cb<double>(model, starts, S, lo, hi, kappa, maxeval, x_out, cb_out, nevals_out);
+}
+int hbegp_minimize_confidence_bound_f32(hbegp_model* model, const float* starts, int S, const double* lo, const double* hi, double kappa,
+                                        int maxeval, float* x_out, double* cb_out, int* nevals_out) {
+  return do_minimize_cb<float>(model, starts, S, lo, hi, kappa, maxeval, x_out, cb_out, nevals_out);
+}
+int hbegp_debug_cb_phases(int enable, double* phase_ms) { return debug_phases(PH_CB, 2, enable, phase_ms); }
 }  // extern "C"
 
 // argument checks of hbegp_sobol_* / hbegp_main_effects_*: everything is refused before any device call, the checks that need no

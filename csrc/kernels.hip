@@ -5112,6 +5112,88 @@ template void launch_mes<double>(const double*, const double*, const double*, co
 template void launch_mes<float>(const float*, const float*, const float*, const float*, int, int, const double*, int, int, double*,
                                 float*, int*, hipStream_t);
 
+// =================================================================================================================
+// the confidence bound of ONE model (hbegp.cpp: model_cb):
+//   cb = mu + kappa sigma,   grad[i] = dmean[i] + kappa (dvar[i] / (2 sigma)),   sigma = sqrt(var)
+// The sigma term is dropped -- never divided -- where !(sigma > 2.220446049250313e-16) and where kappa = 0: cb = mu widened, grad =
+// dmean's bits.  There is no sum over anything, so a wave per candidate (mes_kernel's mapping) would leave 64 - d lanes idle: a row
+// gets L = 2^shift lanes, the smallest power of two >= d (1 without a gradient), and a workgroup of CB_THREADS lanes covers
+// CB_THREADS / L consecutive rows -- lane (r, i) reads element r d + i of dmean and dvar, so a wave's loads cover one contiguous
+// range, and at least half the lanes work.  Every lane of a row reads the row's mu and var (one cache line for the group) and forms
+// sigma itself; lane i = 0 stores cb.  Every operation is a single rounded fp64 one (no contraction), the same with and without a
+// gradient: a row's bits depend on its own (mu, var, dmean, dvar) and kappa alone.  A NaN in mu or var gives NaN in cb and the row.
+// =================================================================================================================
+constexpr int CB_THREADS = 256;
+
+template <typename T>
+__global__ void __launch_bounds__(CB_THREADS) cb_kernel(const T* __restrict__ mean, const T* __restrict__ var,
+                                                        const T* __restrict__ dmean, const T* __restrict__ dvar, int m, int d, int shift,
+                                                        double kappa, int want_grad, double* __restrict__ cb, T* __restrict__ grad) {
+#pragma clang fp contract(off)  // every product and sum below is rounded on its own (HIP's default would fuse them)
+  const int L = 1 << shift;
+  const long long j = (long long)blockIdx.x * (CB_THREADS >> shift) + (threadIdx.x >> shift);
+  const int i0 = threadIdx.x & (L - 1);
+  if (j >= m) return;
+  const double mu = (double)mean[j], v = (double)var[j];
+  const double sd = sqrt(v);
+  const bool bad = (mu != mu) || (v != v);
+  const bool live = sd > 2.220446049250313e-16 && kappa != 0.0;
+  const double nan = __longlong_as_double(0x7ff8000000000000LL);
+  if (i0 == 0) cb[j] = bad ? nan : (live ? mu + kappa * sd : mu);
+  if (!want_grad) return;
+  const double two_sd = 2.0 * sd;
+  for (int i = i0; i < d; i += L) {
+    const size_t x = (size_t)j * d + i;
+    const double dm = (double)dmean[x];
+    const double g = live ? dm + kappa * ((double)dvar[x] / two_sd) : dm;
+    grad[x] = bad ? (T)nan : (T)g;
+  }
+}
+
+// The arg-min of the confidence bound: best = the FIRST index of the minimum of v[0 .. m) through argmax_last_kernel's fixed LDS
+// tree with the order turned round; a NaN never wins, -1 where no entry is a number.  First, because the reference replaces its
+// suggestion only on a strictly lower bound.
+__global__ void __launch_bounds__(BSEL_THREADS) argmin_first_kernel(const double* __restrict__ v, int m, int* __restrict__ res) {
+  __shared__ double sv[BSEL_THREADS];
+  __shared__ int si[BSEL_THREADS];
+  const int tid = threadIdx.x;
+  double best = 0.0;
+  int bi = -1;
+  for (int i = tid; i < m; i += BSEL_THREADS) {
+    const double e = v[i];
+    if (e == e && (bi < 0 || e < best)) { best = e; bi = i; }  // ascending i: an equal value stays at the earlier index
+  }
+  sv[tid] = best;
+  si[tid] = bi;
+  __syncthreads();
+#pragma unroll 1
+  for (int w = BSEL_THREADS / 2; w > 0; w >>= 1) {
+    if (tid < w) {
+      const double o = sv[tid + w];
+      const int oi = si[tid + w];
+      if (oi >= 0 && (si[tid] < 0 || o < sv[tid] || (o == sv[tid] && oi < si[tid]))) { sv[tid] = o; si[tid] = oi; }
+    }
+    __syncthreads();
+  }
+  if (tid == 0) res[0] = si[0];
+}
+
+template <typename T>
+void launch_cb(const T* mean, const T* var, const T* dmean, const T* dvar, int m, int d, double kappa, int want_grad, double* cb, T* grad,
+               int* best, hipStream_t s) {
+  int shift = 0;
+  if (want_grad)
+    while ((1 << shift) < d && (1 << shift) < 64) ++shift;
+  const int rows = CB_THREADS >> shift;
+  hipLaunchKernelGGL((cb_kernel<T>), dim3((unsigned)((m + rows - 1) / rows)), dim3(CB_THREADS), 0, s, mean, var, dmean, dvar, m, d, shift,
+                     kappa, want_grad, cb, grad);
+  hipLaunchKernelGGL(argmin_first_kernel, dim3(1), dim3(BSEL_THREADS), 0, s, cb, m, best);
+}
+template void launch_cb<double>(const double*, const double*, const double*, const double*, int, int, double, int, double*, double*, int*,
+                                hipStream_t);
+template void launch_cb<float>(const float*, const float*, const float*, const float*, int, int, double, int, double*, float*, int*,
+                               hipStream_t);
+
 // Per-device one-time setup: kernels that use more than 64 KiB of dynamic LDS need the attribute raised.  Called from
 // hbegp_ctx_create() for every device, before any stream capture.
 static void init_dag_kernels();  // dag_kernel.inc.hpp (end of this file)

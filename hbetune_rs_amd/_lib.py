@@ -145,6 +145,10 @@ SIGNATURES = {
     "hbegp_mes_f32": (C.c_int, [_vp, _fp, C.c_int, _dp, C.c_int, _dp, _fp, _ip, _fp, _fp]),
     "hbegp_maximize_mes_f64": (C.c_int, [_vp, _dp, C.c_int, _dp, _dp, _dp, C.c_int, C.c_int, _dp, _dp, _ip]),
     "hbegp_maximize_mes_f32": (C.c_int, [_vp, _fp, C.c_int, _dp, _dp, _dp, C.c_int, C.c_int, _fp, _dp, _ip]),
+    "hbegp_confidence_bound_f64": (C.c_int, [_vp, _dp, C.c_int, C.c_double, _dp, _dp, _ip, _dp, _dp]),
+    "hbegp_confidence_bound_f32": (C.c_int, [_vp, _fp, C.c_int, C.c_double, _dp, _fp, _ip, _fp, _fp]),
+    "hbegp_minimize_confidence_bound_f64": (C.c_int, [_vp, _dp, C.c_int, _dp, _dp, C.c_double, C.c_int, _dp, _dp, _ip]),
+    "hbegp_minimize_confidence_bound_f32": (C.c_int, [_vp, _fp, C.c_int, _dp, _dp, C.c_double, C.c_int, _fp, _dp, _ip]),
     "hbegp_sobol_f64": (C.c_int, [_vp, _dp, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "hbegp_sobol_f32": (C.c_int, [_vp, _fp, _fp, C.c_int, _dp, _dp, _dp, _dp, _fp, _fp, _fp]),
     "hbegp_main_effects_f64": (C.c_int, [_vp, _dp, C.c_int, _dp, C.c_int, _dp, _dp]),
@@ -183,6 +187,7 @@ SIGNATURES = {
     "hbegp_debug_cei_phases": (C.c_int, [C.c_int, _dp]),
     "hbegp_debug_lcei_phases": (C.c_int, [C.c_int, _dp]),
     "hbegp_debug_mes_phases": (C.c_int, [C.c_int, _dp]),
+    "hbegp_debug_cb_phases": (C.c_int, [C.c_int, _dp]),
     "hbegp_debug_pool_poisoned": (C.c_int, [C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "hbegp_model_info": (C.c_int, [_vp, _ip, _ip, _ip, _dp, _dp]),
     "hbegp_model_get_f64": (C.c_int, [_vp, _dp, _dp, _dp]),

@@ -247,6 +247,22 @@ class SurrogateModelGPR:
         q = self.y_norm.project_location_from_normalized(qn)
         return SummaryStatistics(mean, std, cv, (q[0], q[1], q[2]))
 
+    def predict_statistics_a(self, x):
+        """predict_statistics at every row of x [m, d]: ONE predict for all rows, the quartiles as mu + z_p sigma on the host.
+        Returns a list of m SummaryStatistics, row by row the numbers the scalar method gives."""
+        from scipy.special import ndtri
+
+        m, v = self._predict_norm(np.asarray(x, dtype=self.dtype).reshape(-1, self.fitted.d))
+        mean = self.y_norm.project_mean_from_normalized(m, v)
+        std = self.y_norm.project_std_from_normalized(m, v)
+        cv = self.y_norm.project_cv_from_normalized(m, v)
+        mean_n, std_n = m.astype(np.float64), np.sqrt(v).astype(np.float64)
+        z = np.array([float(ndtri(p)) for p in (0.25, 0.5, 0.75)])
+        qn = mean_n[:, None] + std_n[:, None] * z[None, :]
+        qn = np.where((np.abs(std_n) <= np.finfo(float).eps)[:, None], mean_n[:, None], qn).astype(self.dtype)
+        q = self.y_norm.project_location_from_normalized(qn)
+        return [SummaryStatistics(mean[i], std[i], cv[i], (q[i, 0], q[i, 1], q[i, 2])) for i in range(len(m))]
+
     def predict_mean_ei_a(self, x, fmin):  # gpr.rs:179-212
         m, v = self._predict_norm(x)
         fmin_n = float(self.y_norm.project_into_normalized(np.array([fmin], dtype=self.dtype))[0])
@@ -412,6 +428,18 @@ class SurrogateModelGPR:
         lo = np.array([b[0] for b in bounds], dtype=np.float64)
         hi = np.array([b[1] for b in bounds], dtype=np.float64)
         return self.fitted.maximize_mes(np.asarray(starts, dtype=self.dtype), lo, hi, ystar, maxeval=maxeval)
+
+    def minimize_confidence_bound(self, starts, bounds, cb, maxeval=150):
+        """Bounded L-BFGS descent of the confidence bound mean + cb * std from every row of `starts` (the box: `bounds` = [(lo, hi)]
+        per feature), all runs in lockstep on the device model (FittedKernel.minimize_confidence_bound): the device alternative to
+        the BOBYQA loop of the reference's suggest_optimum (minimize.rs:598-610).  The runs work on the NORMALISED bound:
+        project_location_from_normalized is strictly increasing for the linear and for the logarithmic projection, so the point
+        that minimises the normalised bound minimises predict_confidence_bound too.  Returns (x[S, d], bound[S], nevals[S]), the
+        bound PROJECTED like predict_confidence_bound's (float64)."""
+        lo = np.array([b[0] for b in bounds], dtype=np.float64)
+        hi = np.array([b[1] for b in bounds], dtype=np.float64)
+        x, val, nevals = self.fitted.minimize_confidence_bound(np.asarray(starts, dtype=self.dtype), lo, hi, float(cb), maxeval=maxeval)
+        return x, self.y_norm.project_location_from_normalized(val), nevals
 
     # Sensitivity of the surrogate to its features (opt-in; nothing the estimator suggests by default uses it).
     def _uniform_rows(self, n_samples, rng, bounds):
@@ -1229,6 +1257,60 @@ def find_best_individual_by_confidence_bound(features, model, confidence_bound):
         if ucb[i] < ucb[best]:
             best = i
     return best, model.predict_mean(features[best])
+
+
+def suggest_optimum(features, model, confidence_bound=1.0, bounds=None, n_starts=1, maxeval=150):
+    """minimize.rs:588-621, up to the validation samples, over a feature array [n, d]: the individual with the lowest confidence
+    bound (find_best_individual_by_confidence_bound), then the minimisation of the bound over the box from that individual --
+    the model's lockstep bounded L-BFGS on the exact gradient (model.minimize_confidence_bound) where the reference runs BOBYQA
+    over 150 single-point predicts -- then mean and EI at the minimiser (model.predict_mean_ei) against `suggestion_y`, the start
+    individual's predicted mean.  `bounds` = [(lo, hi)] per feature, default the unit box the reference uses.  With n_starts > 1
+    the individuals with the next-lowest bounds at distinct points start runs 1 .. n_starts - 1 (fewer where the population holds
+    fewer distinct points); the lowest run is returned, ties to the lower run index.  Run 0 starts at the scan's winner and a run
+    is never worse than its start, so the suggestion's bound is at most that individual's, whatever n_starts is.
+    Returns (x[d], bound, mean, ei, start): the suggestion, its projected bound (float64), its projected mean, its EI and the index
+    of the scan's winner.  The reference sends every point BOBYQA tries through the design space and back, which snaps integer
+    parameters; this function works in the continuous feature box and leaves the snapping of x to the caller.  Running the
+    validation samples, extend and the final predict_statistics stay with the caller."""
+    features = np.asarray(features)
+    start, suggestion_y = find_best_individual_by_confidence_bound(features, model, confidence_bound)
+    d = features.shape[1]
+    if bounds is None:
+        bounds = [(0.0, 1.0)] * d
+    lo = np.array([b[0] for b in bounds], dtype=np.float64)
+    hi = np.array([b[1] for b in bounds], dtype=np.float64)
+    rows = [start]
+    if int(n_starts) > 1:
+        ucb = np.asarray(model.predict_confidence_bound_a(features, confidence_bound))
+        for i in np.argsort(ucb, kind="stable"):
+            if len(rows) < int(n_starts) and not any((features[i] == features[r]).all() for r in rows):
+                rows.append(int(i))
+    x, bound, _ = model.minimize_confidence_bound(_starts_in_box(features[rows], lo, hi, model.dtype), bounds, confidence_bound, maxeval=maxeval)
+    run = 0
+    for r in range(1, len(rows)):
+        if bound[r] < bound[run]:
+            run = r
+    mean, ei = model.predict_mean_ei(x[run], suggestion_y)
+    return x[run], bound[run], mean, ei, start
+
+
+def acquire_by_confidence_bound(candidates, model, k, cb):
+    """The k rows of `candidates` [m, n_features] with the lowest confidence bound mean + cb * std
+    (model.predict_confidence_bound_a: one batched predict), lowest first, equal bounds in the order of their indices (a stable
+    sort); a NaN bound raises.  cb > 0 prefers points that are good even pessimistically, cb < 0 is GP-LCB (Srinivas et al.
+    2010): optimism in the face of uncertainty.  Opt-in: nothing the estimator suggests by default calls it.
+    Returns (idx[k] int64, bound[k])."""
+    c = np.asarray(candidates)
+    if c.ndim != 2:
+        raise ValueError("candidates must be [m, n_features]")
+    k = int(k)
+    if not 0 <= k <= c.shape[0]:
+        raise ValueError("k must lie in [0, m]")
+    bound = np.asarray(model.predict_confidence_bound_a(c, cb))
+    if np.isnan(bound).any():
+        raise ValueError("confidence bounds should be comparable")
+    idx = np.argsort(bound, kind="stable")[:k].astype(np.int64)
+    return idx, bound[idx]
 
 
 class EstimatorGPR:

@@ -442,6 +442,48 @@ class FittedKernel:
                       _lib.aptr(x), _lib.dptr(val), nevals.ctypes.data_as(C.POINTER(C.c_int))))
         return x, val, nevals
 
+    def confidence_bound(self, x, kappa, want_grad=False, want_posterior=False):
+        """The confidence bound mu + kappa sigma at the rows of x (hbegp_confidence_bound_*), in the normalised y space: kappa > 0
+        is the reference's predict_confidence_bound, kappa < 0 GP-LCB, kappa = 0 the mean.  Returns (cb[m] float64, best) -- best the
+        FIRST index of the minimum, -1 for m = 0 or where every row is NaN -- then grad[m, d] with want_grad, then (mean[m], var[m])
+        with want_posterior: predict()'s batched numbers bit for bit (predict_with_gradient()'s with want_grad).  A sigma = 0 row has
+        cb = mean and grad = dmean."""
+        x = _lib.as_c(np.asarray(x, dtype=self.dtype).reshape(-1, self.d), self.dtype)
+        m = x.shape[0]
+        val = np.zeros(m)
+        best = C.c_int(-1)
+        grad = np.zeros((m, self.d), dtype=self.dtype) if want_grad else None
+        mean = np.zeros(m, dtype=self.dtype) if want_posterior else None
+        var = np.zeros(m, dtype=self.dtype) if want_posterior else None
+        fn = getattr(_lib.load(), f"hbegp_confidence_bound_{self._sfx}")
+        _lib.check(fn(self._h, _lib.aptr(x), m, float(kappa), _lib.dptr(val), _lib.aptr(grad), C.byref(best), _lib.aptr(mean),
+                      _lib.aptr(var)))
+        out = (val, best.value)
+        if want_grad:
+            out += (grad,)
+        if want_posterior:
+            out += (mean, var)
+        return out
+
+    def minimize_confidence_bound(self, starts, lo, hi, kappa, maxeval=150):
+        """S bounded L-BFGS runs minimising confidence_bound() over the box (hbegp_minimize_confidence_bound_*), one batched gradient
+        predict per round.  starts: [S, d] inside [lo, hi].  Returns (x[S, d], cb[S], nevals[S]): each run's best point, never worse
+        than its start; confidence_bound(x, kappa) reproduces the values bit for bit.  A start with a NaN coordinate fails its own
+        run alone: it comes back as it is with cb = +inf."""
+        starts = _lib.as_c(np.atleast_2d(starts), self.dtype)
+        assert starts.shape[1] == self.d
+        S = starts.shape[0]
+        lo = _lib.as_c(lo, np.float64)
+        hi = _lib.as_c(hi, np.float64)
+        assert lo.shape == (self.d,) and hi.shape == (self.d,)
+        x = np.zeros((S, self.d), dtype=self.dtype)
+        val = np.zeros(S)
+        nevals = np.zeros(S, dtype=np.int32)
+        fn = getattr(_lib.load(), f"hbegp_minimize_confidence_bound_{self._sfx}")
+        _lib.check(fn(self._h, _lib.aptr(starts), S, _lib.dptr(lo), _lib.dptr(hi), float(kappa), int(maxeval), _lib.aptr(x),
+                      _lib.dptr(val), nevals.ctypes.data_as(C.POINTER(C.c_int))))
+        return x, val, nevals
+
     def predict_cov(self, x, jitter=0.0):
         """Joint posterior at the query points (hbegp_predict_cov_*): returns (mean[m], cov[m, m]) in the normalised y space,
         cov = K** + (1e-5 + jitter) I - K*^T K^-1 K* (unclamped; its diagonal is predict()'s variance before clamping)."""

@@ -621,6 +621,41 @@ int hbegp_maximize_mes_f64(hbegp_model* model, const double* starts, int R, cons
 int hbegp_maximize_mes_f32(hbegp_model* model, const float* starts, int R, const double* lo, const double* hi, const double* ystar,
                            int S, int maxeval, float* x_out, double* mes_out, int* nevals_out);
 
+/* The confidence bound of ONE model, cb = mu + kappa sigma, in the model's normalised y space: the reference's
+ * predict_confidence_bound (kappa > 0: the pessimistic value suggest_optimum minimises) and, with kappa < 0, GP-LCB (Srinivas et
+ * al., ICML 2010).  The posterior N(mu, sigma^2) is the latent one of hbegp_predict_* (variance without s2, clamped at 0).
+ *   cb[j]      = mu + kappa sigma                                 sigma = sqrt(var), stored as double
+ *   grad[j][i] = dmean[j][i] + kappa (dvar[j][i] / (2 sigma))     rounded to the element type once
+ * dmean and dvar being hbegp_predict_grad_*'s.  Every operation is one correctly rounded fp64 operation for both element types
+ * (no fused multiply-add), so the two lines above, evaluated in double on the returned posteriors, give the same bits.
+ * "sigma = 0" means !(sigma > 2.220446049250313e-16): cb = mu and grad = dmean, the sigma term is dropped and never divided.
+ * kappa = 0 drops it too: cb is mean widened to double and grad holds dmean's bits.  There are no atomics: a row's bits depend only on
+ * its own (mu, sigma^2, dmean, dvar) and kappa -- not on m, on the row's position, or on whether a gradient was asked for.
+ * cb[m] (required for m > 0); grad[m*d] (may be NULL: no gradient launch); best (may be NULL): the FIRST index of the minimum of cb
+ * (a NaN never wins; -1 for m = 0 and where every row is NaN) -- first, because the reference replaces its suggestion only on a
+ * strictly lower bound; mean[m], var[m] (each may be NULL): bit for bit what hbegp_predict_* returns on its batched path (m > 16),
+ * or hbegp_predict_grad_* with a gradient.  A NaN coordinate gives NaN in that row of cb and grad only.  m = 0 is a no-op with
+ * best = -1.  Calls are serialised per model, like predict.
+ * HBEGP_EINVAL, before any device call and without writing anything: a kappa that is not finite (either sign and 0 are valid), a
+ * NULL model, a model of the other element type, m < 0, a NULL Xs or cb with m > 0.  HBEGP_ENOMEM: m beyond the device's memory. */
+int hbegp_confidence_bound_f64(hbegp_model* model, const double* Xs, int m, double kappa, double* cb, double* grad, int* best,
+                               double* mean, double* var);
+int hbegp_confidence_bound_f32(hbegp_model* model, const float* Xs, int m, double kappa, double* cb, float* grad, int* best, float* mean,
+                               float* var);
+/* S bounded L-BFGS runs MINIMISING hbegp_confidence_bound_* over the box lo <= x <= hi, in lockstep: every round is one
+ * hbegp_confidence_bound_* with a gradient at the points of the unfinished runs (the device alternative to the reference's 150
+ * single-point BOBYQA evaluations in suggest_optimum).  starts[S*d] inside the box; x_out[S*d], cb_out[S]: each run's best
+ * evaluated point, never worse than its start -- hbegp_confidence_bound_* at x_out reproduces cb_out bit for bit; nevals_out[S]
+ * (may be NULL) <= maxeval.  A value or a gradient component that is not finite is a failed evaluation.  A start with a NaN
+ * coordinate is admitted and fails its own run alone: that run returns its start, cb_out = +inf and one evaluation, the others
+ * what they return without it.  Refused with HBEGP_EINVAL before any device call: everything hbegp_confidence_bound_* refuses
+ * about the model and kappa, and everything hbegp_maximize_ei_* refuses about S, the box, starts outside it, maxeval and the
+ * outputs. */
+int hbegp_minimize_confidence_bound_f64(hbegp_model* model, const double* starts, int S, const double* lo, const double* hi, double kappa,
+                                        int maxeval, double* x_out, double* cb_out, int* nevals_out);
+int hbegp_minimize_confidence_bound_f32(hbegp_model* model, const float* starts, int S, const double* lo, const double* hi, double kappa,
+                                        int maxeval, float* x_out, double* cb_out, int* nevals_out);
+
 /* Sensitivity of the posterior mean mu (hbegp_predict_*'s mean, normalised y space) to each feature, from the CALLER's sample
  * matrices in the feature coordinates the model was fitted on (the RNG stays on the caller side).  Both calls evaluate the mean at
  * base rows with ONE coordinate substituted,
@@ -840,6 +875,11 @@ int hbegp_debug_lcei_phases(int enable, double* phase_ms);
  * a gradient, the gradient's), the MES kernel with the arg-max -- in milliseconds; then enable != 0 makes this thread's later MES
  * calls timed (the rounds of hbegp_maximize_mes_* too: the record holds the last one). */
 int hbegp_debug_mes_phases(int enable, double* phase_ms);
+/* ---- timing hook (tools/cb_bench.py): phase_ms[2] (may be NULL) receives the device time of the phases of the calling thread's
+ * last timed hbegp_confidence_bound_* call -- the predict (the upload of the candidates, the batched predict's launches and, with a
+ * gradient, the gradient's), the confidence-bound kernel with the arg-min -- in milliseconds; then enable != 0 makes this thread's
+ * later calls timed (the rounds of hbegp_minimize_confidence_bound_* too: the record holds the last one). */
+int hbegp_debug_cb_phases(int enable, double* phase_ms);
 /* ---- timing hook (tools/sens_bench.py): phase_ms[4] (may be NULL) receives the device time of the phases of the calling thread's
  * last timed hbegp_sobol_* / hbegp_main_effects_* call -- the upload (with the grid's scaling), the substituted means, the chunk and
  * row sums (both summed over the slabs), the final reduction with the downloads -- in milliseconds; then enable != 0 makes this

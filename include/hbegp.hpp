@@ -123,6 +123,13 @@ template <> struct Abi<double> {
                           double* x, double* v, int* ne) {
     return hbegp_maximize_mes_f64(m, st, r, lo, hi, ys, s, maxeval, x, v, ne);
   }
+  static int confidence_bound(hbegp_model* m, const double* xs, int cnt, double kappa, double* v, double* g, int* best, double* mean, double* var) {
+    return hbegp_confidence_bound_f64(m, xs, cnt, kappa, v, g, best, mean, var);
+  }
+  static int minimize_confidence_bound(hbegp_model* m, const double* st, int s, const double* lo, const double* hi, double kappa, int maxeval,
+                                       double* x, double* v, int* ne) {
+    return hbegp_minimize_confidence_bound_f64(m, st, s, lo, hi, kappa, maxeval, x, v, ne);
+  }
   static int get(hbegp_model* m, double* t, double* a, double* ki) { return hbegp_model_get_f64(m, t, a, ki); }
 };
 template <> struct Abi<float> {
@@ -205,6 +212,13 @@ template <> struct Abi<float> {
   static int maximize_mes(hbegp_model* m, const float* st, int r, const double* lo, const double* hi, const double* ys, int s, int maxeval,
                           float* x, double* v, int* ne) {
     return hbegp_maximize_mes_f32(m, st, r, lo, hi, ys, s, maxeval, x, v, ne);
+  }
+  static int confidence_bound(hbegp_model* m, const float* xs, int cnt, double kappa, double* v, float* g, int* best, float* mean, float* var) {
+    return hbegp_confidence_bound_f32(m, xs, cnt, kappa, v, g, best, mean, var);
+  }
+  static int minimize_confidence_bound(hbegp_model* m, const float* st, int s, const double* lo, const double* hi, double kappa, int maxeval,
+                                       float* x, double* v, int* ne) {
+    return hbegp_minimize_confidence_bound_f32(m, st, s, lo, hi, kappa, maxeval, x, v, ne);
   }
   static int get(hbegp_model* m, double* t, float* a, float* ki) { return hbegp_model_get_f32(m, t, a, ki); }
 };
@@ -451,6 +465,21 @@ template <typename A>
 void maximize_mes(const FittedKernel<A>& model, const A* starts, int R, const double* lo, const double* hi, const double* ystar, int S,
                   int maxeval, A* x_out, double* mes_out, int* nevals = nullptr) {
   check(detail::Abi<A>::maximize_mes(model.handle(), starts, R, lo, hi, ystar, S, maxeval, x_out, mes_out, nevals));
+}
+
+// The confidence bound mu + kappa sigma at xs[m*d] under one model (hbegp_confidence_bound_*; normalised y space): kappa > 0 is the
+// reference's predict_confidence_bound, kappa < 0 GP-LCB.  cb[m]; grad[m*d], best (the FIRST index of the minimum), mean[m], var[m]
+// may be nullptr
+template <typename A>
+void confidence_bound(const FittedKernel<A>& model, const A* xs, int m, double kappa, double* cb, A* grad = nullptr, int* best = nullptr,
+                      A* mean = nullptr, A* var = nullptr) {
+  check(detail::Abi<A>::confidence_bound(model.handle(), xs, m, kappa, cb, grad, best, mean, var));
+}
+// S bounded L-BFGS descents of that bound from starts[S*d] inside [lo, hi]; x_out[S*d], cb_out[S], nevals[S] (may be nullptr)
+template <typename A>
+void minimize_confidence_bound(const FittedKernel<A>& model, const A* starts, int S, const double* lo, const double* hi, double kappa,
+                               int maxeval, A* x_out, double* cb_out, int* nevals = nullptr) {
+  check(detail::Abi<A>::minimize_confidence_bound(model.handle(), starts, S, lo, hi, kappa, maxeval, x_out, cb_out, nevals));
 }
 
 // RAII owner of an hbegp_paths handle (FittedKernel::sample_paths); it keeps its model alive

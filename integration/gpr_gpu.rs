@@ -229,6 +229,14 @@ extern "C" {
     ) -> c_int;
     #[allow(dead_code)]
     fn hbegp_debug_mes_phases(enable: c_int, phase_ms: *mut c_double) -> c_int;
+    fn hbegp_minimize_confidence_bound_f64(
+        model: *mut HbegpModel, starts: *const c_double, s: c_int, lo: *const c_double, hi: *const c_double, kappa: c_double,
+        maxeval: c_int, x_out: *mut c_double, cb_out: *mut c_double, nevals_out: *mut c_int,
+    ) -> c_int;
+    fn hbegp_minimize_confidence_bound_f32(
+        model: *mut HbegpModel, starts: *const c_float, s: c_int, lo: *const c_double, hi: *const c_double, kappa: c_double,
+        maxeval: c_int, x_out: *mut c_float, cb_out: *mut c_double, nevals_out: *mut c_int,
+    ) -> c_int;
     fn hbegp_noisy_ei_f64(
         model: *mut HbegpModel, xs: *const c_double, m: c_int, mb: c_int, z: *const c_double, s: c_int, jitter: c_double,
         nei: *mut c_double, best: *mut c_int, fmin_draws: *mut c_double, rho: *mut c_double, info: *mut c_int,
@@ -405,6 +413,12 @@ pub trait GpuScalar: Scalar + sealed::Sealed {
         model: *mut HbegpModel, starts: *const Self, r: c_int, lo: *const f64, hi: *const f64, ystar: *const f64, s: c_int,
         maxeval: c_int, x_out: *mut Self, mes_out: *mut f64, nevals_out: *mut c_int,
     ) -> c_int;
+    /// `hbegp_minimize_confidence_bound_*`
+    #[allow(clippy::too_many_arguments)]
+    unsafe fn ffi_minimize_confidence_bound(
+        model: *mut HbegpModel, starts: *const Self, s: c_int, lo: *const f64, hi: *const f64, kappa: f64, maxeval: c_int,
+        x_out: *mut Self, cb_out: *mut f64, nevals_out: *mut c_int,
+    ) -> c_int;
     /// `hbegp_noisy_ei_*`
     #[allow(clippy::too_many_arguments)]
     unsafe fn ffi_noisy_ei(
@@ -536,6 +550,12 @@ impl GpuScalar for f64 {
         maxeval: c_int, x_out: *mut f64, mes_out: *mut f64, nevals_out: *mut c_int,
     ) -> c_int {
         hbegp_maximize_mes_f64(model, starts, r, lo, hi, ystar, s, maxeval, x_out, mes_out, nevals_out)
+    }
+    unsafe fn ffi_minimize_confidence_bound(
+        model: *mut HbegpModel, starts: *const f64, s: c_int, lo: *const f64, hi: *const f64, kappa: f64, maxeval: c_int,
+        x_out: *mut f64, cb_out: *mut f64, nevals_out: *mut c_int,
+    ) -> c_int {
+        hbegp_minimize_confidence_bound_f64(model, starts, s, lo, hi, kappa, maxeval, x_out, cb_out, nevals_out)
     }
     unsafe fn ffi_noisy_ei(
         model: *mut HbegpModel, xs: *const f64, m: c_int, mb: c_int, z: *const f64, s: c_int, jitter: f64, nei: *mut f64,
@@ -670,6 +690,12 @@ impl GpuScalar for f32 {
         maxeval: c_int, x_out: *mut f32, mes_out: *mut f64, nevals_out: *mut c_int,
     ) -> c_int {
         hbegp_maximize_mes_f32(model, starts, r, lo, hi, ystar, s, maxeval, x_out, mes_out, nevals_out)
+    }
+    unsafe fn ffi_minimize_confidence_bound(
+        model: *mut HbegpModel, starts: *const f32, s: c_int, lo: *const f64, hi: *const f64, kappa: f64, maxeval: c_int,
+        x_out: *mut f32, cb_out: *mut f64, nevals_out: *mut c_int,
+    ) -> c_int {
+        hbegp_minimize_confidence_bound_f32(model, starts, s, lo, hi, kappa, maxeval, x_out, cb_out, nevals_out)
     }
     unsafe fn ffi_noisy_ei(
         model: *mut HbegpModel, xs: *const f32, m: c_int, mb: c_int, z: *const f32, s: c_int, jitter: f64, nei: *mut f64,
@@ -1171,6 +1197,33 @@ impl<A: GpuScalar> SurrogateModelGpu<A> {
             panic!("hbegp_maximize_mes failed: {}", last_error());
         }
         (x_out, mes, nevals)
+    }
+
+    /// Bounded L-BFGS descents of the confidence bound mean + `confidence_bound` * std, in the NORMALISED y space, from every row
+    /// of `starts` inside [lo, hi] (`hbegp_minimize_confidence_bound_*`, all runs in lockstep on the device model, the exact
+    /// gradient from the posterior gradients).  Returns (x [S, d] row-major, bound [S] normalised, evaluations [S]): each run's
+    /// best point, never worse than its start.  `project_location_from_normalized` is strictly increasing, so the point that
+    /// minimises the normalised bound minimises `predict_confidence_bound`; project the returned bound with it.
+    /// A maintainer may call this from `suggest_optimum` (minimize.rs:598-610) in place of the BOBYQA loop over 150 single-point
+    /// `predict_confidence_bound` calls: start it at `suggestion_features` with the unit box, then snap the result through
+    /// `project_from_features` / `project_into_features` once -- the reference does that inside every BOBYQA evaluation, this
+    /// minimiser works in the continuous feature box.  Opt-in: nothing calls it by default.
+    pub fn minimize_confidence_bound(&self, starts: ArrayView2<A>, lo: &[f64], hi: &[f64], confidence_bound: f64, maxeval: usize)
+        -> (Vec<A>, Vec<f64>, Vec<c_int>) {
+        let (s, d) = starts.dim();
+        assert!(lo.len() == d && hi.len() == d, "one bound pair per feature");
+        let starts = starts.as_standard_layout();
+        let mut x_out = vec![A::zero(); s * d];
+        let mut bound = vec![0.0f64; s];
+        let mut nevals = vec![0 as c_int; s];
+        let rc = unsafe {
+            A::ffi_minimize_confidence_bound(self.handle, starts.as_ptr(), s as c_int, lo.as_ptr(), hi.as_ptr(), confidence_bound,
+                                             maxeval as c_int, x_out.as_mut_ptr(), bound.as_mut_ptr(), nevals.as_mut_ptr())
+        };
+        if rc != HBEGP_OK {
+            panic!("hbegp_minimize_confidence_bound failed: {}", last_error());
+        }
+        (x_out, bound, nevals)
     }
 
     /// Noisy expected improvement over a candidate set (`hbegp_noisy_ei_*`; Letham, Karrer, Ottoni, Bakshy 2019): EI of every row

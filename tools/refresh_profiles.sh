@@ -50,3 +50,5 @@ echo "[extra] log-space constrained EI beside cEI (profiles/lcei_bench.txt: prep
 python3 "$ROOT/tools/lcei_bench.py" --reps 3 > "$OUT/lcei_bench.txt" 2>&1
 echo "[extra] max-value entropy search: phases beside the host (profiles/mes_bench.txt: prepend its header by hand)"
 python3 "$ROOT/tools/mes_bench.py" --reps 3 > "$OUT/mes_bench.txt" 2>&1
+echo "[extra] the confidence bound: phases beside the host, the minimiser beside 150 single-point bounds (profiles/cb_bench.txt: prepend its header by hand)"
+python3 "$ROOT/tools/cb_bench.py" --reps 5 > "$OUT/cb_bench.txt" 2>&1
