@@ -157,7 +157,8 @@ template <typename T>
 void launch_gemm(const GemmLaunch& g, int tile, hipStream_t s);  // tile in {32, 64, 128}
 
 template <typename T>
-void launch_kmat(const T* X, int n, int d, int np, int nu2, const EvalParams* P, T* W, const int* info, hipStream_t s,
+// rv (may be null): known noise variances of the n rows, added to the diagonal entries of rows < n -- K = c Matern + diag(s2 + v)
+void launch_kmat(const T* X, const T* rv, int n, int d, int np, int nu2, const EvalParams* P, T* W, const int* info, hipStream_t s,
                  const EvalPrologue* pro = nullptr);
 
 // Factor the 128x128 diagonal block `blk` of W1 (lower) in place -> X_blk = L_blk^-1 into W2's block, diag(L) -> ldiag.
@@ -360,8 +361,8 @@ void launch_qei_batch(const T* Xs, int B, int q, int d, const T* Q, const T* W, 
 // posterior sample paths (hbegp_paths_*; kernels.hip: paths_project_kernel, paths_eval_kernel).  omT [d][F] = om0^T / ell, phase [F],
 // Wf [S][F] are fp64 for both element types; Vt, Rt [Sp][np] hold one path per row (the tile GEMMs' operand layout).
 //   scale_omega: omT from the caller's unit-length-scale om0 [F][d]
-//   project:     Rt[s][i] = y_i - sqrt(2c/F) sum_j Wf[s][j] cos(om_j . x_i + b_j) - sqrt(sigma^2) eps[s][i] (eps [S][n] or null), zero
-//                padding; part: paths_project_chunks(F, n, S) * S * n doubles
+//   project:     Rt[s][i] = y_i - sqrt(2c/F) sum_j Wf[s][j] cos(om_j . x_i + b_j) - sqrt(sigma^2 + v_i) eps[s][i] (eps [S][n] or null;
+//                v = rv [n] or null: the model's known row variances), zero padding; part: paths_project_chunks(F, n, S) * S * n doubles
 //   eval:        f [S][m], df [S][m][d] (want_grad) at Xs [m][d] (per_path = 0) or [S][m][d] (per_path = 1);
 //                part: paths_eval_chunks(n, F) * S * m * (d + 1) doubles
 int paths_project_chunks(int F, int n, int S, int* fch_out = nullptr);
@@ -370,7 +371,7 @@ template <typename T>
 void launch_paths_scale_omega(const T* om0, int F, int d, const EvalParams* P, double* omT, hipStream_t s);
 template <typename T>
 void launch_paths_project(const T* X, int n, int d, int np, const double* omT, const double* phase, int F, const double* Wf, int S, int Sp,
-                          const T* y, const T* eps, const EvalParams* P, double* part, T* Rt, hipStream_t s);
+                          const T* y, const T* eps, const T* rv, const EvalParams* P, double* part, T* Rt, hipStream_t s);
 template <typename T>
 void launch_paths_eval(const T* Xs, int m, int per_path, int S, const T* X, int n, int d, int np, int nu2, const EvalParams* P, const T* Vt,
                        const double* omT, const double* phase, const double* Wf, int F, int want_grad, double* part, T* f, T* df,
@@ -399,8 +400,10 @@ struct SmallEval {
   EvalOut* hout;   // where the results go: the slot's pinned host block (written by the kernel itself: no copy node) or `out`
   int mode;
 };
+// rv (may be null): known noise variances of the n rows, in the element type of X.  It travels beside SmallEval, not inside it: the
+// descriptor a run of small_fit_kernel copies to its stack for every evaluation keeps its size.
 template <typename T>
-void launch_small_eval(const SmallEval& g, int nu2, hipStream_t s);
+void launch_small_eval(const SmallEval& g, const void* rv, int nu2, hipStream_t s);
 
 // One optimiser run of a fit of at most 128 rows in ONE launch (kernels.hip: small_fit_kernel): the evaluation above in a loop
 // with the bounded L-BFGS step and the fit's objective wrapper (clamping, failed evaluations, capture of the best) on the device.
@@ -434,6 +437,8 @@ struct SmallFit {
   double* trace_lml;         // [trace_cap]
   double* trace_grad;        // [trace_cap][p]
   int trace_cap;
+  const void* rv;            // known noise variances of the run's n rows (element type of X; null: none): every run of a shared launch
+                             // carries its own
 };
 // fs_dev: device array of nruns descriptors; run r is workgroup r of one launch
 template <typename T>

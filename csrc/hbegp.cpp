@@ -795,6 +795,7 @@ struct hbegp_problem {
 template <typename T>
 struct Problem : ProblemBase {
   std::vector<T*> Xd, yd;                 // per device
+  std::vector<T*> rvd;                    // per device: the rows' known noise variances, n entries (null: none) -- K = c Matern + diag(s2 + v)
   std::vector<std::vector<Slot<T>>> slots;  // [device][slot]
   std::vector<std::vector<Sched>> scheds;   // [device][gemm launch ordinal]
   // device-scheduled factorisation (dag_kernel.inc.hpp): one plan per problem, the same on every device
@@ -877,20 +878,21 @@ struct Problem : ProblemBase {
   // single_shot: the problem runs one evaluation (extend): skip the static schedule tables, every GEMM launch is ad hoc
   // like_fit: choose the evaluation path (launches / task queue) as a fit of this size does, whatever the slot count --
   // `extend` then repeats the fit's own evaluation of a theta bit for bit
+  // rv: n known noise variances (validated by the caller: finite and >= 0 in T) or null; data like X and y, converted once
   Problem(hbegp_ctx* c, const T* X, const T* y, int n_, int d_, double nu, int n_slots_, bool single_shot = false, bool like_fit = false,
-          bool lazy_fit = false) {
+          bool lazy_fit = false, const double* rv = nullptr) {
     try {
       adhoc_ = single_shot;
       like_fit_ = like_fit;
       lazy_ = lazy_fit && env_int("HBEGP_LAZY_GRAD", 1) != 0;
-      init(c, X, y, n_, d_, nu, n_slots_);
+      init(c, X, y, n_, d_, nu, n_slots_, rv);
     } catch (...) {
       release();  // a constructor that throws never runs the destructor: give back what was allocated so far
       throw;
     }
   }
 
-  void init(hbegp_ctx* c, const T* X, const T* y, int n_, int d_, double nu, int n_slots_) {
+  void init(hbegp_ctx* c, const T* X, const T* y, int n_, int d_, double nu, int n_slots_, const double* rv) {
     ctx = c; n = n_; d = d_; np = round_up(n_, NB); n_slots = n_slots_;
     nu2 = std::isinf(nu) ? 0 : (int)std::lround(2 * nu);  // 0 = squared exponential (nu = infinity)
     is_f32 = sizeof(T) == 4;
@@ -906,6 +908,9 @@ struct Problem : ProblemBase {
     const size_t nn = (size_t)np * np;
     Xd.assign(c->devs.size(), nullptr);
     yd.assign(c->devs.size(), nullptr);
+    rvd.assign(c->devs.size(), nullptr);
+    std::vector<T> rv_t;  // the source of asynchronous copies: alive until every device's stream has been waited for below
+    if (rv) rv_t.assign(rv, rv + n_);
     slots.resize(c->devs.size());
     for (size_t di = 0; di < c->devs.size(); ++di) {
       HIPCHECK(hipSetDevice(c->devs[di]));
@@ -922,6 +927,10 @@ struct Problem : ProblemBase {
       HIPCHECK(hipMemsetAsync(yd[di], 0, sizeof(T) * np, st0));
       HIPCHECK(hipMemcpyAsync(Xd[di], X, sizeof(T) * (size_t)n * d, hipMemcpyHostToDevice, st0));
       HIPCHECK(hipMemcpyAsync(yd[di], y, sizeof(T) * n, hipMemcpyHostToDevice, st0));
+      if (rv) {
+        rvd[di] = palloc<T>(c->devs[di], n);
+        HIPCHECK(hipMemcpyAsync(rvd[di], rv_t.data(), sizeof(T) * n, hipMemcpyHostToDevice, st0));
+      }
       for (auto& s : slots[di]) {
         bool fresh1 = false, fresh2 = false, fk = false;
         s.W1 = static_cast<T*>(g_pool.get(s.dev, sizeof(T) * nn, &fresh1));
@@ -1245,6 +1254,7 @@ struct Problem : ProblemBase {
     dag_var.clear();
     Xd.clear();
     yd.clear();
+    rvd.clear();
   }
 
   // The GEMMs of an evaluation of the launch path are issued by this dispatcher: the i-th launch by the i-th static schedule
@@ -1367,7 +1377,7 @@ struct Problem : ProblemBase {
     // captured graph of an evaluation is ONE node (no parameter copy, no reset kernel, no result copy -- each was ~2-5 us of
     // a 57 us evaluation).
     g.P = s.hP; g.hout = s.hOut;
-    launch_small_eval<T>(g, nu2, s.stream);
+    launch_small_eval<T>(g, rvd[di], nu2, s.stream);
   }
 
   // What one enqueued evaluation computes.  The first two are what `want_grad` = false / true always were (the index of the
@@ -1410,13 +1420,13 @@ struct Problem : ProblemBase {
         s.ctrl_cleared = true;
       }
       if (tm) tm->begin(PhaseTimer::KMAT);
-      launch_kmat<T>(Xd[di], n, d, np, nu2, s.hP, s.W1, info, s.stream, &pro);
+      launch_kmat<T>(Xd[di], rvd[di], n, d, np, nu2, s.hP, s.W1, info, s.stream, &pro);
       if (tm) tm->end();
     } else {
       HIPCHECK(hipMemcpyAsync(s.dP, s.hP, sizeof(EvalParams), hipMemcpyHostToDevice, s.stream));
       launch_reset_out(s.dOut, s.stream);
       if (tm) tm->begin(PhaseTimer::KMAT);
-      launch_kmat<T>(Xd[di], n, d, np, nu2, s.dP, s.W1, info, s.stream);
+      launch_kmat<T>(Xd[di], rvd[di], n, d, np, nu2, s.dP, s.W1, info, s.stream);
       if (tm) tm->end();
     }
     if (dag_) launch_queue(s, di, s.Kinv[target], tm, dag_lauum_ ? part : 0);
@@ -1505,7 +1515,7 @@ struct Problem : ProblemBase {
       HIPCHECK(hipStreamSynchronize(s.stream));
       return s.hOut->info != 0 ? HBEGP_NOT_PD : HBEGP_OK;
     }
-    launch_kmat<T>(Xd[di], n, d, np, nu2, s.dP, s.W1, &s.dOut->info, s.stream);
+    launch_kmat<T>(Xd[di], rvd[di], n, d, np, nu2, s.dP, s.W1, &s.dOut->info, s.stream);
     // the captured K^-1 stays as it is; the recursion's launches are the first ones of eval_gemms, whose schedules they take
     const int nb = np / NB;
     if (dag_) launch_queue(s, di, nullptr, nullptr);
@@ -1526,7 +1536,8 @@ struct Problem : ProblemBase {
   //   [X11 0; X21 X22]:  T = A21 X11^T,  A22 -= T T^T,  U = T X11,  chol_inv(A22),  X21 = -X22 U          O(n^2 k)
   //   K^-1 = [K11^-1 + X21^T X21, .; X22^T X21, X22^T X22]                                                   O(n^2 k)
   // Results go to ping-pong buffer 0 of slot (di, si).  Returns HBEGP_EINVAL when nothing can be reused.
-  int extend_from(size_t di, int si, const T* pX, const T* pXinv, const T* pKinv, const T* pldiag, int pn, int pnp) {
+  // prv: the prior's known row variances (pn entries) or null; a side without them counts as zeros
+  int extend_from(size_t di, int si, const T* pX, const T* prv, const T* pXinv, const T* pKinv, const T* pldiag, int pn, int pnp) {
     Slot<T>& s = slots[di][si];
     HIPCHECK(hipSetDevice(s.dev));
     const int nb = np / NB, q0 = std::min(pn / NB, nb - 1);
@@ -1536,6 +1547,16 @@ struct Problem : ProblemBase {
     launch_reset_out(s.dOut, s.stream);
     // same leading rows?  (only the kept blocks matter, compare the whole prior prefix anyway)
     launch_prefix_differs<T>(Xd[di], pX, (size_t)pn * d, &s.dOut->n_warn, s.stream);
+    if (rvd[di] || prv) {
+      const T* zeros = nullptr;
+      if (!rvd[di] || !prv) {
+        // one side has no v: it is compared as zeros.  The block is the problem's (palloc): it lives until release(), past the launch
+        T* z = palloc<T>(s.dev, pn);
+        HIPCHECK(hipMemsetAsync(z, 0, sizeof(T) * pn, s.stream));
+        zeros = z;
+      }
+      launch_prefix_differs<T>(rvd[di] ? rvd[di] : zeros, prv ? prv : zeros, (size_t)pn, &s.dOut->n_warn, s.stream);
+    }
     CHECK_LAUNCHES();
     HIPCHECK(hipMemcpyAsync(s.hOut, s.dOut, sizeof(EvalOut), hipMemcpyDeviceToHost, s.stream));
     HIPCHECK(hipStreamSynchronize(s.stream));
@@ -1547,7 +1568,7 @@ struct Problem : ProblemBase {
     HIPCHECK(hipMemcpy2DAsync(s.W2, sizeof(T) * np, pXinv, sizeof(T) * pnp, sizeof(T) * w, w, hipMemcpyDeviceToDevice, s.stream));
     HIPCHECK(hipMemcpy2DAsync(s.Kinv[0], sizeof(T) * np, pKinv, sizeof(T) * pnp, sizeof(T) * w, w, hipMemcpyDeviceToDevice, s.stream));
     HIPCHECK(hipMemcpyAsync(s.ldiag, pldiag, sizeof(T) * w, hipMemcpyDeviceToDevice, s.stream));
-    launch_kmat<T>(Xd[di], n, d, np, nu2, s.dP, s.W1, info, s.stream);
+    launch_kmat<T>(Xd[di], rvd[di], n, d, np, nu2, s.dP, s.W1, info, s.stream);
     // a launch sequence other than the evaluation's: every GEMM ad hoc
     chol_inv_rec<T>(s.W1, s.W2, s.W2, np, 0, q0, nb, true, true, [&](GemmLaunch& g, int) { gemm_adhoc<T>(g, info, s.stream); },
                     leaf_step(s, nullptr));
@@ -1923,6 +1944,7 @@ struct hbegp_model {
   std::vector<double> theta;  // clamped, log space
   void *X = nullptr, *alpha = nullptr, *Kinv = nullptr;  // device
   void* y = nullptr;     // the (normalised) targets, n entries: the residual of a sample path (hbegp_paths_create) starts from them
+  void* rv = nullptr;    // the rows' known noise variances, n entries in the element type (null: none)
   void* Xinv = nullptr;  // L^-1 (lower), for the predictive variance as c + 1e-5 - |L^-1 k*|^2
   void* ldiag = nullptr; // diag(L), np entries (incremental extend needs the log-determinant of the kept part)
   size_t kinv_bytes = 0;
@@ -1988,6 +2010,7 @@ static hbegp_model* make_model(Problem<T>& prob, size_t di, int si, const double
   m->X = m->palloc(sizeof(T) * (size_t)prob.n * prob.d);
   m->alpha = m->palloc(sizeof(T) * prob.np);
   m->y = m->palloc(sizeof(T) * prob.n);
+  if (prob.rvd[di]) m->rv = m->palloc(sizeof(T) * prob.n);
   { bool fr; m->Kinv = g_pool.get(m->dev, sizeof(T) * nn, &fr); m->Xinv = g_pool.get(m->dev, sizeof(T) * nn, &fr); m->kinv_bytes = sizeof(T) * nn; }
   m->dP = static_cast<EvalParams*>(m->palloc(sizeof(EvalParams)));
   m->dOut = static_cast<EvalOut*>(m->palloc(sizeof(EvalOut)));
@@ -2016,6 +2039,7 @@ static hbegp_model* make_model(Problem<T>& prob, size_t di, int si, const double
   HIPCHECK(hipMemcpyAsync(m->X, prob.Xd[di], sizeof(T) * (size_t)prob.n * prob.d, hipMemcpyDeviceToDevice, m->stream));
   HIPCHECK(hipMemcpyAsync(m->alpha, s.alpha[b], sizeof(T) * prob.np, hipMemcpyDeviceToDevice, m->stream));
   HIPCHECK(hipMemcpyAsync(m->y, prob.yd[di], sizeof(T) * prob.n, hipMemcpyDeviceToDevice, m->stream));
+  if (m->rv) HIPCHECK(hipMemcpyAsync(m->rv, prob.rvd[di], sizeof(T) * prob.n, hipMemcpyDeviceToDevice, m->stream));
   HIPCHECK(hipMemcpyAsync(m->Kinv, s.Kinv[b], sizeof(T) * nn, hipMemcpyDeviceToDevice, m->stream));
   launch_symmetrize<T>(static_cast<T*>(m->Kinv), prob.np, m->stream);  // invc_into() returns the full matrix (fit.rs:60,168)
   CHECK_LAUNCHES();
@@ -2305,7 +2329,7 @@ static void posterior_sigma(hbegp_model* m, const T* Xs, int cnt, int mp, const 
   if (clk_q) clk_q->mark(s);
   HIPCHECK(hipMemcpyAsync(m->dPcov, m->dP, sizeof(EvalParams), hipMemcpyDeviceToDevice, s));
   HIPCHECK(hipMemcpyAsync(&m->dPcov->noise, noise, sizeof(double), hipMemcpyHostToDevice, s));
-  launch_kmat<T>(static_cast<T*>(m->Xs), cnt, m->d, mp, m->nu2, m->dPcov, W, info, s);
+  launch_kmat<T>(static_cast<T*>(m->Xs), nullptr, cnt, m->d, mp, m->nu2, m->dPcov, W, info, s);
   {
     // Sigma -= Q Q^T (lower tiles), contraction over the training points
     GemmLaunch g{};
@@ -3449,7 +3473,7 @@ static int paths_create(hbegp_model* m, const T* omega0, const T* phase, const T
   HIPCHECK(hipMemsetAsync(m->dOut, 0, sizeof(EvalOut), s));
   launch_paths_scale_omega<T>(om0, F, d, m->dP, p->omT, s);
   clk.mark(s);
-  launch_paths_project<T>(static_cast<T*>(m->X), n, d, np, p->omT, p->phase, F, p->Wf, S, Sp, static_cast<T*>(m->y), deps, m->dP, part, Rt, s);
+  launch_paths_project<T>(static_cast<T*>(m->X), n, d, np, p->omT, p->phase, F, p->Wf, S, Sp, static_cast<T*>(m->y), deps, static_cast<const T*>(m->rv), m->dP, part, Rt, s);
   clk.mark(s);
   {
     // v = L^-T (L^-1 r) for all paths, one path per row: T1 = R^T X^T (X = L^-1 lower: k <= j, as Q = Kstar X^T), then
@@ -3643,15 +3667,15 @@ static int read_fit_options(const hbegp_fit_options* in, hbegp_fit_options* out)
 }
 
 template <typename T>
-static int do_extend(hbegp_ctx* ctx, const T* X, const T* y, int n, int d, double nu, const double* theta, const double* lo,
-                     const double* hi, hbegp_model** model_out);
+static int do_extend(hbegp_ctx* ctx, const T* X, const T* y, const double* rv, int n, int d, double nu, const double* theta,
+                     const double* lo, const double* hi, hbegp_model** model_out);
 
 // loo: the objective is the leave-one-out log pseudo-likelihood (hbegp_fit_loo_*) -- every evaluation is the slot's normal one
 // without the lml gradient plus the leave-one-out tail on its results, always under the host-driven optimiser, and the model
 // is `extend` at the captured theta.  Nothing else differs; loo = false is the fit as it always was.
 template <typename T>
-static int do_fit(hbegp_ctx* ctx, const T* X, const T* y, int n, int d, double nu, const double* theta0, const double* lo,
-                  const double* hi, const double* starts, int n_restarts, const hbegp_fit_options* opt_in,
+static int do_fit(hbegp_ctx* ctx, const T* X, const T* y, const double* rv, int n, int d, double nu, const double* theta0,
+                  const double* lo, const double* hi, const double* starts, int n_restarts, const hbegp_fit_options* opt_in,
                   double* theta_best, double* lml_best, hbegp_model** model_out, bool loo = false) {
   hbegp_fit_options opt{};
   g_last_fit_stats = LastFitStats{};  // a fit that fails leaves zeros, not the previous fit's numbers
@@ -3703,7 +3727,7 @@ static int do_fit(hbegp_ctx* ctx, const T* X, const T* y, int n, int d, double n
   if (host_serial) host_lk.lock();
   const auto th0 = std::chrono::steady_clock::now();  // (HBEGP_TIMING: how long the turns are)
   double held_ms = 0;
-  Problem<T> prob(ctx, X, y, n, d, nu, n_slots, false, true, !loo);
+  Problem<T> prob(ctx, X, y, n, d, nu, n_slots, false, true, !loo, rv);
   const auto tf1 = std::chrono::steady_clock::now();
   if (!(small_fit && prob.small_)) arrival.arrived();
   if (!(small_fit && prob.small_) && host_lk.owns_lock()) host_lk.unlock();
@@ -3782,7 +3806,7 @@ static int do_fit(hbegp_ctx* ctx, const T* X, const T* y, int n, int d, double n
         memcpy(box + p, lo, sizeof(double) * p);
         memcpy(box + 2 * p, hi, sizeof(double) * p);
         SmallFit f{};
-        f.ev.X = prob.Xd[w.di]; f.ev.y = prob.yd[w.di]; f.ev.n = n; f.ev.d = d; f.ev.P = s.dP;
+        f.ev.X = prob.Xd[w.di]; f.ev.y = prob.yd[w.di]; f.rv = prob.rvd[w.di]; f.ev.n = n; f.ev.d = d; f.ev.P = s.dP;
         f.ev.W2 = s.W2; f.ev.ldiag = s.ldiag; f.ev.out = s.dOut; f.ev.hout = s.dOut;
         f.Kinv[0] = s.Kinv[0]; f.Kinv[1] = s.Kinv[1]; f.alpha[0] = s.alpha[0]; f.alpha[1] = s.alpha[1];
         // L^-1 and diag(L) ping-pong too: the captured evaluation's factor survives the run, the model takes it as it is (no
@@ -4092,7 +4116,7 @@ static int do_fit(hbegp_ctx* ctx, const T* X, const T* y, int n, int d, double n
     // the model is what `extend` gives at theta_best, bit for bit: built through that very path, once the fit's slots are back
     // in the pool
     prob.release();
-    return model_out ? do_extend<T>(ctx, X, y, n, d, nu, th.data(), nullptr, nullptr, model_out) : HBEGP_OK;
+    return model_out ? do_extend<T>(ctx, X, y, rv, n, d, nu, th.data(), nullptr, nullptr, model_out) : HBEGP_OK;
   }
   const auto tf2 = std::chrono::steady_clock::now();
   if (host_serial && prob.small_ && !host_lk.owns_lock()) host_lk.lock();
@@ -4113,8 +4137,8 @@ static int do_fit(hbegp_ctx* ctx, const T* X, const T* y, int n, int d, double n
 }
 
 template <typename T>
-static int do_extend(hbegp_ctx* ctx, const T* X, const T* y, int n, int d, double nu, const double* theta, const double* lo,
-                     const double* hi, hbegp_model** model_out) {
+static int do_extend(hbegp_ctx* ctx, const T* X, const T* y, const double* rv, int n, int d, double nu, const double* theta,
+                     const double* lo, const double* hi, hbegp_model** model_out) {
   hbegp_ctx one;
   one.devs = {ctx->devs[0]};
   // One order of operations for one theta: the evaluation runs the way a fit's evaluations do at this size -- through the task
@@ -4122,7 +4146,7 @@ static int do_extend(hbegp_ctx* ctx, const T* X, const T* y, int n, int d, doubl
   // arithmetic does not depend on how the launch is scheduled).
   const int dag_env = env_int("HBEGP_DAG", -1);
   const bool queue_like_fit = (dag_env < 0 ? round_up(n, NB) / NB >= env_int("HBEGP_DAG_MIN_BLOCKS", DAG_MIN_BLOCKS_FIT) : dag_env != 0) && round_up(n, NB) / NB >= 2;
-  Problem<T> prob(&one, X, y, n, d, nu, 1, !queue_like_fit, true);
+  Problem<T> prob(&one, X, y, n, d, nu, 1, !queue_like_fit, true, false, rv);
   const int p = d + 2;
   Slot<T>& s = prob.slots[0][0];
   theta_to_params(theta, lo, hi, d, s.hP);
@@ -4146,30 +4170,30 @@ static int do_extend(hbegp_ctx* ctx, const T* X, const T* y, int n, int d, doubl
 // data the last model was built from): same theta, incremental factorisation; falls back to the full path when the
 // prefix does not match or is shorter than one 128-block.
 template <typename T>
-static int do_extend_from(hbegp_ctx* ctx, hbegp_model* prior, const T* X, const T* y, int n, hbegp_model** model_out,
+static int do_extend_from(hbegp_ctx* ctx, hbegp_model* prior, const T* X, const T* y, const double* rv, int n, hbegp_model** model_out,
                           int* incremental) {
   if (incremental) *incremental = 0;
   const int d = prior->d, p = d + 2;
   const double nu = prior->nu2 == 0 ? std::numeric_limits<double>::infinity() : prior->nu2 / 2.0;
   if (prior->dev != ctx->devs[0] || n < prior->n || prior->n < NB || !prior->ldiag)
-    return do_extend<T>(ctx, X, y, n, d, nu, prior->theta.data(), nullptr, nullptr, model_out);
+    return do_extend<T>(ctx, X, y, rv, n, d, nu, prior->theta.data(), nullptr, nullptr, model_out);
   hbegp_ctx one;
   one.devs = {ctx->devs[0]};
   static const int timing = env_int("HBEGP_TIMING", 0);
   auto now = [] { return std::chrono::steady_clock::now(); };
   auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
   const auto t0 = now();
-  Problem<T> prob(&one, X, y, n, d, nu, 1, true);
+  Problem<T> prob(&one, X, y, n, d, nu, 1, true, false, false, rv);
   const auto t1 = now();
   Slot<T>& s = prob.slots[0][0];
   theta_to_params(prior->theta.data(), nullptr, nullptr, d, s.hP);
   int st;
   {
     std::lock_guard<std::mutex> lock(prior->mu);
-    st = prob.extend_from(0, 0, static_cast<const T*>(prior->X), static_cast<const T*>(prior->Xinv),
+    st = prob.extend_from(0, 0, static_cast<const T*>(prior->X), static_cast<const T*>(prior->rv), static_cast<const T*>(prior->Xinv),
                           static_cast<const T*>(prior->Kinv), static_cast<const T*>(prior->ldiag), prior->n, prior->np);
   }
-  if (st == HBEGP_EINVAL) return do_extend<T>(ctx, X, y, n, d, nu, prior->theta.data(), nullptr, nullptr, model_out);
+  if (st == HBEGP_EINVAL) return do_extend<T>(ctx, X, y, rv, n, d, nu, prior->theta.data(), nullptr, nullptr, model_out);
   if (st != HBEGP_OK) return fail(HBEGP_NOT_PD, "Kernel matrix must be invertible.");  // fit.rs:55
   s.best_idx = 0;
   if (incremental) *incremental = 1;
@@ -4375,7 +4399,7 @@ static int problem_kmat(hbegp_problem* prob, int dev, int slot, const double* th
   theta_to_params(theta, lo, hi, p->d, s.hP);
   HIPCHECK(hipMemcpyAsync(s.dP, s.hP, sizeof(EvalParams), hipMemcpyHostToDevice, s.stream));
   launch_reset_out(s.dOut, s.stream);
-  launch_kmat<T>(p->Xd[dev], p->n, p->d, p->np, p->nu2, s.dP, s.W1, &s.dOut->info, s.stream);
+  launch_kmat<T>(p->Xd[dev], p->rvd[dev], p->n, p->d, p->np, p->nu2, s.dP, s.W1, &s.dOut->info, s.stream);
   CHECK_LAUNCHES();
   const int n = p->n, np = p->np;
   std::vector<T> tmp((size_t)np * np);
@@ -4406,7 +4430,7 @@ int hbegp_fit_f64(hbegp_ctx* ctx, const double* X, const double* y, int n, int d
   if (int e = check_args(ctx, X, y, n, d, nu)) return e;
   if (!theta0 || !lo || !hi || (n_restarts > 0 && !starts)) return fail(HBEGP_EINVAL, "theta0/lo/hi/starts is NULL");
   GUARD_BEGIN
-  return do_fit<double>(ctx, X, y, n, d, nu, theta0, lo, hi, starts, n_restarts, opt, theta_best, lml_best, model);
+  return do_fit<double>(ctx, X, y, nullptr, n, d, nu, theta0, lo, hi, starts, n_restarts, opt, theta_best, lml_best, model);
   GUARD_END
 }
 int hbegp_fit_f32(hbegp_ctx* ctx, const float* X, const float* y, int n, int d, double nu, const double* theta0,
@@ -4419,7 +4443,7 @@ int hbegp_fit_f32(hbegp_ctx* ctx, const float* X, const float* y, int n, int d, 
   if (int e = check_args(ctx, X, y, n, d, nu)) return e;
   if (!theta0 || !lo || !hi || (n_restarts > 0 && !starts)) return fail(HBEGP_EINVAL, "theta0/lo/hi/starts is NULL");
   GUARD_BEGIN
-  return do_fit<float>(ctx, X, y, n, d, nu, theta0, lo, hi, starts, n_restarts, opt, theta_best, lml_best, model);
+  return do_fit<float>(ctx, X, y, nullptr, n, d, nu, theta0, lo, hi, starts, n_restarts, opt, theta_best, lml_best, model);
   GUARD_END
 }
 
@@ -4433,7 +4457,7 @@ int hbegp_fit_loo_f64(hbegp_ctx* ctx, const double* X, const double* y, int n, i
   if (int e = check_args(ctx, X, y, n, d, nu)) return e;
   if (!theta0 || !lo || !hi || (n_restarts > 0 && !starts)) return fail(HBEGP_EINVAL, "NULL theta0/lo/hi/starts");
   GUARD_BEGIN
-  return do_fit<double>(ctx, X, y, n, d, nu, theta0, lo, hi, starts, n_restarts, opt, theta_best, loo_best, model, true);
+  return do_fit<double>(ctx, X, y, nullptr, n, d, nu, theta0, lo, hi, starts, n_restarts, opt, theta_best, loo_best, model, true);
   GUARD_END
 }
 int hbegp_fit_loo_f32(hbegp_ctx* ctx, const float* X, const float* y, int n, int d, double nu, const double* theta0,
@@ -4446,7 +4470,7 @@ int hbegp_fit_loo_f32(hbegp_ctx* ctx, const float* X, const float* y, int n, int
   if (int e = check_args(ctx, X, y, n, d, nu)) return e;
   if (!theta0 || !lo || !hi || (n_restarts > 0 && !starts)) return fail(HBEGP_EINVAL, "NULL theta0/lo/hi/starts");
   GUARD_BEGIN
-  return do_fit<float>(ctx, X, y, n, d, nu, theta0, lo, hi, starts, n_restarts, opt, theta_best, loo_best, model, true);
+  return do_fit<float>(ctx, X, y, nullptr, n, d, nu, theta0, lo, hi, starts, n_restarts, opt, theta_best, loo_best, model, true);
   GUARD_END
 }
 
@@ -4455,7 +4479,7 @@ int hbegp_extend_f64(hbegp_ctx* ctx, const double* X, const double* y, int n, in
   if (int e = check_args(ctx, X, y, n, d, nu)) return e;
   if (!theta) return fail(HBEGP_EINVAL, "theta is NULL");
   GUARD_BEGIN
-  return do_extend<double>(ctx, X, y, n, d, nu, theta, lo, hi, model);
+  return do_extend<double>(ctx, X, y, nullptr, n, d, nu, theta, lo, hi, model);
   GUARD_END
 }
 int hbegp_extend_f32(hbegp_ctx* ctx, const float* X, const float* y, int n, int d, double nu, const double* theta,
@@ -4463,7 +4487,7 @@ int hbegp_extend_f32(hbegp_ctx* ctx, const float* X, const float* y, int n, int 
   if (int e = check_args(ctx, X, y, n, d, nu)) return e;
   if (!theta) return fail(HBEGP_EINVAL, "theta is NULL");
   GUARD_BEGIN
-  return do_extend<float>(ctx, X, y, n, d, nu, theta, lo, hi, model);
+  return do_extend<float>(ctx, X, y, nullptr, n, d, nu, theta, lo, hi, model);
   GUARD_END
 }
 
@@ -4472,8 +4496,9 @@ int hbegp_extend_from_f64(hbegp_ctx* ctx, hbegp_model* prior, const double* X, c
   if (!ctx || !prior || !X || !y) return fail(HBEGP_EINVAL, "ctx/prior/X/y is NULL");
   if (prior->is_f32) return fail(HBEGP_EINVAL, "prior model holds f32 data");
   if (n < 1) return fail(HBEGP_EINVAL, "n must be >= 1 (got %d)", n);
+  if (prior->rv) return fail(HBEGP_EINVAL, "the prior model carries row variances: extend it with hbegp_extend_from_rv_*");
   GUARD_BEGIN
-  return do_extend_from<double>(ctx, prior, X, y, n, model, incremental);
+  return do_extend_from<double>(ctx, prior, X, y, nullptr, n, model, incremental);
   GUARD_END
 }
 int hbegp_extend_from_f32(hbegp_ctx* ctx, hbegp_model* prior, const float* X, const float* y, int n, hbegp_model** model,
@@ -4481,8 +4506,9 @@ int hbegp_extend_from_f32(hbegp_ctx* ctx, hbegp_model* prior, const float* X, co
   if (!ctx || !prior || !X || !y) return fail(HBEGP_EINVAL, "ctx/prior/X/y is NULL");
   if (!prior->is_f32) return fail(HBEGP_EINVAL, "prior model holds f64 data");
   if (n < 1) return fail(HBEGP_EINVAL, "n must be >= 1 (got %d)", n);
+  if (prior->rv) return fail(HBEGP_EINVAL, "the prior model carries row variances: extend it with hbegp_extend_from_rv_*");
   GUARD_BEGIN
-  return do_extend_from<float>(ctx, prior, X, y, n, model, incremental);
+  return do_extend_from<float>(ctx, prior, X, y, nullptr, n, model, incremental);
   GUARD_END
 }
 
@@ -4504,6 +4530,135 @@ int hbegp_predict_f32(hbegp_model* model, const float* Xs, int m, float* mean, f
 }
 
 }  // extern "C"
+// ---- known per-row noise variances (hbegp.h: "row variances"): the entry points above with `rv` behind y ---------------------
+// Refused before any device call: a variance that is negative or not finite (in the element type it is converted to).
+template <typename T>
+static int check_rv(const double* rv, int n) {
+  if (!rv) return HBEGP_OK;
+  for (int i = 0; i < n; ++i)
+    if (!(rv[i] >= 0.0) || !std::isfinite((T)rv[i]))
+      return fail(HBEGP_EINVAL, "rv[%d] = %g: a row variance must be finite and >= 0", i, rv[i]);
+  return HBEGP_OK;
+}
+template <typename T>
+static int problem_create_rv(hbegp_ctx* ctx, const T* X, const T* y, const double* rv, int n, int d, double nu, int n_slots,
+                             hbegp_problem** out) {
+  if (int e = check_args(ctx, X, y, n, d, nu)) return e;
+  if (!out || n_slots < 1) return fail(HBEGP_EINVAL, "bad out/n_slots");
+  if (int e = check_rv<T>(rv, n)) return e;
+  GUARD_BEGIN
+  std::unique_ptr<hbegp_problem> p(new hbegp_problem());
+  p->impl.reset(new Problem<T>(ctx, X, y, n, d, nu, n_slots, false, false, false, rv));
+  *out = p.release();
+  return HBEGP_OK;
+  GUARD_END
+}
+template <typename T>
+static int fit_rv(hbegp_ctx* ctx, const T* X, const T* y, const double* rv, int n, int d, double nu, const double* theta0, const double* lo,
+                  const double* hi, const double* starts, int n_restarts, const hbegp_fit_options* opt, double* theta_best, double* best,
+                  hbegp_model** model, bool loo) {
+  {
+    hbegp_fit_options probe;
+    if (int e = read_fit_options(opt, &probe)) return e;  // the order of the plain entry points: options, arguments, then rv
+  }
+  if (int e = check_args(ctx, X, y, n, d, nu)) return e;
+  if (!theta0 || !lo || !hi || (n_restarts > 0 && !starts)) return fail(HBEGP_EINVAL, "theta0/lo/hi/starts is NULL");
+  if (int e = check_rv<T>(rv, n)) return e;
+  GUARD_BEGIN
+  return do_fit<T>(ctx, X, y, rv, n, d, nu, theta0, lo, hi, starts, n_restarts, opt, theta_best, best, model, loo);
+  GUARD_END
+}
+template <typename T>
+static int extend_rv(hbegp_ctx* ctx, const T* X, const T* y, const double* rv, int n, int d, double nu, const double* theta,
+                     const double* lo, const double* hi, hbegp_model** model) {
+  if (int e = check_args(ctx, X, y, n, d, nu)) return e;
+  if (!theta) return fail(HBEGP_EINVAL, "theta is NULL");
+  if (int e = check_rv<T>(rv, n)) return e;
+  GUARD_BEGIN
+  return do_extend<T>(ctx, X, y, rv, n, d, nu, theta, lo, hi, model);
+  GUARD_END
+}
+template <typename T>
+static int extend_from_rv(hbegp_ctx* ctx, hbegp_model* prior, const T* X, const T* y, const double* rv, int n, hbegp_model** model,
+                          int* incremental) {
+  if (!ctx || !prior || !X || !y) return fail(HBEGP_EINVAL, "ctx/prior/X/y is NULL");
+  if (prior->is_f32 != (sizeof(T) == 4)) return fail(HBEGP_EINVAL, prior->is_f32 ? "prior model holds f32 data" : "prior model holds f64 data");
+  if (n < 1) return fail(HBEGP_EINVAL, "n must be >= 1 (got %d)", n);
+  if (int e = check_rv<T>(rv, n)) return e;
+  // rv = NULL is the plain call, and the plain call refuses such a prior
+  if (!rv && prior->rv) return fail(HBEGP_EINVAL, "the prior model carries row variances: extend it with hbegp_extend_from_rv_* and the rows' rv");
+  GUARD_BEGIN
+  return do_extend_from<T>(ctx, prior, X, y, rv, n, model, incremental);
+  GUARD_END
+}
+extern "C" {
+int hbegp_problem_create_rv_f64(hbegp_ctx* ctx, const double* X, const double* y, const double* rv, int n, int d, double nu, int n_slots,
+                                hbegp_problem** out) {
+  return problem_create_rv<double>(ctx, X, y, rv, n, d, nu, n_slots, out);
+}
+int hbegp_problem_create_rv_f32(hbegp_ctx* ctx, const float* X, const float* y, const double* rv, int n, int d, double nu, int n_slots,
+                                hbegp_problem** out) {
+  return problem_create_rv<float>(ctx, X, y, rv, n, d, nu, n_slots, out);
+}
+int hbegp_fit_rv_f64(hbegp_ctx* ctx, const double* X, const double* y, const double* rv, int n, int d, double nu, const double* theta0,
+                     const double* lo, const double* hi, const double* starts, int n_restarts, const hbegp_fit_options* opt,
+                     double* theta_best, double* lml_best, hbegp_model** model) {
+  return fit_rv<double>(ctx, X, y, rv, n, d, nu, theta0, lo, hi, starts, n_restarts, opt, theta_best, lml_best, model, false);
+}
+int hbegp_fit_rv_f32(hbegp_ctx* ctx, const float* X, const float* y, const double* rv, int n, int d, double nu, const double* theta0,
+                     const double* lo, const double* hi, const double* starts, int n_restarts, const hbegp_fit_options* opt,
+                     double* theta_best, double* lml_best, hbegp_model** model) {
+  return fit_rv<float>(ctx, X, y, rv, n, d, nu, theta0, lo, hi, starts, n_restarts, opt, theta_best, lml_best, model, false);
+}
+int hbegp_fit_loo_rv_f64(hbegp_ctx* ctx, const double* X, const double* y, const double* rv, int n, int d, double nu, const double* theta0,
+                         const double* lo, const double* hi, const double* starts, int n_restarts, const hbegp_fit_options* opt,
+                         double* theta_best, double* loo_best, hbegp_model** model) {
+  return fit_rv<double>(ctx, X, y, rv, n, d, nu, theta0, lo, hi, starts, n_restarts, opt, theta_best, loo_best, model, true);
+}
+int hbegp_fit_loo_rv_f32(hbegp_ctx* ctx, const float* X, const float* y, const double* rv, int n, int d, double nu, const double* theta0,
+                         const double* lo, const double* hi, const double* starts, int n_restarts, const hbegp_fit_options* opt,
+                         double* theta_best, double* loo_best, hbegp_model** model) {
+  return fit_rv<float>(ctx, X, y, rv, n, d, nu, theta0, lo, hi, starts, n_restarts, opt, theta_best, loo_best, model, true);
+}
+int hbegp_extend_rv_f64(hbegp_ctx* ctx, const double* X, const double* y, const double* rv, int n, int d, double nu, const double* theta,
+                        const double* lo, const double* hi, hbegp_model** model) {
+  return extend_rv<double>(ctx, X, y, rv, n, d, nu, theta, lo, hi, model);
+}
+int hbegp_extend_rv_f32(hbegp_ctx* ctx, const float* X, const float* y, const double* rv, int n, int d, double nu, const double* theta,
+                        const double* lo, const double* hi, hbegp_model** model) {
+  return extend_rv<float>(ctx, X, y, rv, n, d, nu, theta, lo, hi, model);
+}
+int hbegp_extend_from_rv_f64(hbegp_ctx* ctx, hbegp_model* prior, const double* X, const double* y, const double* rv, int n,
+                             hbegp_model** model, int* incremental) {
+  return extend_from_rv<double>(ctx, prior, X, y, rv, n, model, incremental);
+}
+int hbegp_extend_from_rv_f32(hbegp_ctx* ctx, hbegp_model* prior, const float* X, const float* y, const double* rv, int n,
+                             hbegp_model** model, int* incremental) {
+  return extend_from_rv<float>(ctx, prior, X, y, rv, n, model, incremental);
+}
+int hbegp_model_row_variance(const hbegp_model* model, double* rv) {
+  if (!model) return fail(HBEGP_EINVAL, "NULL model");
+  if (!model->rv) return 0;
+  if (!rv) return 1;
+  GUARD_BEGIN
+  hbegp_model* m = const_cast<hbegp_model*>(model);
+  std::lock_guard<std::mutex> lock(m->mu);
+  HIPCHECK(hipSetDevice(m->dev));
+  const size_t n = (size_t)m->n;
+  if (m->is_f32) {
+    std::vector<float> tmp(n);
+    HIPCHECK(hipMemcpyAsync(tmp.data(), m->rv, sizeof(float) * n, hipMemcpyDeviceToHost, m->stream));
+    HIPCHECK(hipStreamSynchronize(m->stream));
+    for (size_t i = 0; i < n; ++i) rv[i] = (double)tmp[i];
+  } else {
+    HIPCHECK(hipMemcpyAsync(rv, m->rv, sizeof(double) * n, hipMemcpyDeviceToHost, m->stream));
+    HIPCHECK(hipStreamSynchronize(m->stream));
+  }
+  return 1;
+  GUARD_END
+}
+}  // extern "C"
+
 // argument checks of the gradient entry points: everything is refused before any device call
 template <typename T>
 static int check_predict_grad(hbegp_model* model, const T* Xs, int m, T* mean, T* var, T* dmean, T* dvar) {

@@ -5,6 +5,7 @@
 //  leaf_kernel   : 128x128 diagonal block: Cholesky + inverse of the factor, LDS resident, 16x16 diagonal
 //                  sub-blocks factored in one wavefront with lane broadcasts, the rest on MFMA.
 //  kmat_kernel   : K = c*Matern(X,X) + s2*I (lower tiles), matern_kernel.rs:37-81 + constant/product kernels + lml.rs:44.
+//                  With known per-row noise variances v (rv, hbegp.h "row variances"): K = c*Matern + diag(s2 + v).
 //  gradtrace     : 1/2 tr((aa^T - K^-1) dK/dtheta_j) for all j in one pass over K^-1 (lml.rs:62-70, matern_kernel.rs:83-135)
 //                  without the n x n x (d+1) tensor the reference materialises.
 //  trmv/finalize : alpha = X^T (X y), y^T alpha, sum log L_ii (lml.rs:54-59).
@@ -1042,6 +1043,13 @@ __device__ __forceinline__ T kmat_entry(T dist2, int nu2, T amp, T noise, bool d
   const T v = amp * matern_map<T>(sqrt_nonneg(dist2), nu2);  // product_kernel.rs:37 (k1 * k2)
   return diag ? v + noise : v;
 }
+// a diagonal entry of K with the row's known noise variance: (c k(0) + s2) + v_i, one more rounding.  rvi = 0 (no variances)
+// leaves the entry's bits as they are: it is positive.
+template <typename T>
+__device__ __forceinline__ T kmat_add_rv(T entry, T rvi) {
+#pragma clang fp contract(off)
+  return entry + rvi;
+}
 
 // the poison pattern run_eval looks for in outputs that were never written (a payload no arithmetic produces)
 __device__ __forceinline__ void poison_out(EvalOut* out, int t) {
@@ -1093,7 +1101,7 @@ __device__ __forceinline__ void read_xj4(const T* xj, int k, int tx, T (&b)[4]) 
 // NU2: the Matern order at compile time (no branch per entry); tiles that lie wholly inside the n x n matrix skip the
 // per-entry bounds tests.
 template <typename T, int NU2>
-__global__ void __launch_bounds__(256) kmat_kernel(const T* __restrict__ X, int n, int d, int np,
+__global__ void __launch_bounds__(256) kmat_kernel(const T* __restrict__ X, const T* __restrict__ rv, int n, int d, int np,
                                                    const EvalParams* __restrict__ P, T* __restrict__ W,
                                                    const int* info, EvalPrologue pro) {
   if (pro.dP) {
@@ -1146,14 +1154,23 @@ __global__ void __launch_bounds__(256) kmat_kernel(const T* __restrict__ X, int 
         }
     }
     const T amp = (T)sp[1], noise = (T)sp[0];
+    // rv (may be null): the rows' known noise variances.  In a diagonal tile the thread whose four columns hold row gi's diagonal
+    // entry (column ty + 16 r of the tile: tx = that >> 2, c = ty & 3) loads rv[gi] and adds it there; nobody else reads rv.
+    const bool dtile = li == lj;
+    const bool rv_tile = rv != nullptr && dtile;
     if (i0 + 64 <= n && j0 + 64 <= n) {
-      const bool dtile = li == lj;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int gi = i0 + ty + 16 * r;
         vec4 out;
 #pragma unroll
         for (int c = 0; c < 4; ++c) out[c] = kmat_entry<T>(acc[r][c], NU2, amp, noise, dtile && gi == j0 + tx * 4 + c);
+        if (rv_tile && ((ty + 16 * r) >> 2) == tx) {
+          const T rvi = rv[gi];
+#pragma unroll
+          for (int c = 0; c < 4; ++c)
+            if (c == (ty & 3)) out[c] = kmat_add_rv<T>(out[c], rvi);
+        }
         *reinterpret_cast<vec4*>(W + (size_t)gi * np + j0 + tx * 4) = out;
       }
       return;
@@ -1168,27 +1185,33 @@ __global__ void __launch_bounds__(256) kmat_kernel(const T* __restrict__ X, int 
         const T v = kmat_entry<T>(acc[r][c], NU2, amp, noise, gi == gj);
         out[c] = (gi < n && gj < n) ? v : ((gi == gj) ? T(1) : T(0));  // identity padding
       }
+      if (rv_tile && ((ty + 16 * r) >> 2) == tx && gi < n) {  // never the padding's ones, never rv at an index >= n
+        const T rvi = rv[gi];
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+          if (c == (ty & 3)) out[c] = kmat_add_rv<T>(out[c], rvi);
+      }
       *reinterpret_cast<vec4*>(W + (size_t)gi * np + j0 + tx * 4) = out;
     }
   }
 }
 
 template <typename T>
-void launch_kmat(const T* X, int n, int d, int np, int nu2, const EvalParams* P, T* W, const int* info, hipStream_t s,
+void launch_kmat(const T* X, const T* rv, int n, int d, int np, int nu2, const EvalParams* P, T* W, const int* info, hipStream_t s,
                  const EvalPrologue* pro) {
   const int nt = np / 64, ntiles = nt * (nt + 1) / 2;
   const size_t lds = (size_t)2 * d * 64 * sizeof(T);
   const dim3 grid(ntiles), block(256);
   const EvalPrologue pr = pro ? *pro : EvalPrologue{};
   switch (nu2) {
-    case 0: hipLaunchKernelGGL((kmat_kernel<T, 0>), grid, block, lds, s, X, n, d, np, P, W, info, pr); break;
-    case 1: hipLaunchKernelGGL((kmat_kernel<T, 1>), grid, block, lds, s, X, n, d, np, P, W, info, pr); break;
-    case 3: hipLaunchKernelGGL((kmat_kernel<T, 3>), grid, block, lds, s, X, n, d, np, P, W, info, pr); break;
-    default: hipLaunchKernelGGL((kmat_kernel<T, 5>), grid, block, lds, s, X, n, d, np, P, W, info, pr); break;
+    case 0: hipLaunchKernelGGL((kmat_kernel<T, 0>), grid, block, lds, s, X, rv, n, d, np, P, W, info, pr); break;
+    case 1: hipLaunchKernelGGL((kmat_kernel<T, 1>), grid, block, lds, s, X, rv, n, d, np, P, W, info, pr); break;
+    case 3: hipLaunchKernelGGL((kmat_kernel<T, 3>), grid, block, lds, s, X, rv, n, d, np, P, W, info, pr); break;
+    default: hipLaunchKernelGGL((kmat_kernel<T, 5>), grid, block, lds, s, X, rv, n, d, np, P, W, info, pr); break;
   }
 }
-template void launch_kmat<double>(const double*, int, int, int, int, const EvalParams*, double*, const int*, hipStream_t, const EvalPrologue*);
-template void launch_kmat<float>(const float*, int, int, int, int, const EvalParams*, float*, const int*, hipStream_t, const EvalPrologue*);
+template void launch_kmat<double>(const double*, const double*, int, int, int, int, const EvalParams*, double*, const int*, hipStream_t, const EvalPrologue*);
+template void launch_kmat<float>(const float*, const float*, int, int, int, int, const EvalParams*, float*, const int*, hipStream_t, const EvalPrologue*);
 
 // =================================================================================================================
 // alpha = K^-1 y through the explicit inverse factor: w = X y, alpha = X^T w;  lml pieces (lml.rs:54-59)
@@ -3374,14 +3397,18 @@ template void launch_predict_small<float>(const float*, int, const float*, int, 
 // (minimize.rs:118-120 keeps n at 100-200).  The five launches of the general path (kmat, diagonal block, trmv x2 + reductions,
 // K^-1 = X^T X, gradient) cost ~2 us of launch gap and one HBM round trip each -- more than their arithmetic at this size.
 // Here one workgroup keeps everything in the LDS:
-//   K = c Matern + s2 I      into the block image (the arithmetic of kmat_kernel, entry for entry; K never goes to HBM)
+//   K = c Matern + s2 I      into the block image (the arithmetic of kmat_kernel, entry for entry, the rows' rv on the diagonal
+//                            included; K never goes to HBM)
 //   L, X = L^-1              leaf_body on that image (X and diag(L) also go to HBM: the model keeps them)
 //   alpha = X^T (X y), lml   fp64 dot products against the image (X lives transposed in its strict upper blocks)
 //   K^-1 = X^T X             120 16x16x16 products on MFMA, into the lower blocks of the image (L is no longer needed) and to HBM
 //   g_j = 1/2 sum (alpha alpha^T - K^-1) o dK_j    the arithmetic of gradtrace_kernel, K^-1 and alpha read from the LDS
 // =================================================================================================================
+// rv_raw (may be null): the rows' known noise variances.  They travel beside the descriptor, not inside it: a run of
+// small_fit_kernel copies the descriptor to its stack for every evaluation, and eight more bytes there cost the fit without
+// variances 0.5 % of its rate at n = 128 (profiles/rv_bench.txt).
 template <typename TIO, int NU2>
-__device__ __forceinline__ void small_eval_body(const SmallEval& g, char* smem_raw) {
+__device__ __forceinline__ void small_eval_body(const SmallEval& g, const void* rv_raw, char* smem_raw) {
   using T = double;
   using C = Cfg<T>;
   using L = LeafGeom<T>;
@@ -3497,6 +3524,22 @@ __device__ __forceinline__ void small_eval_body(const SmallEval& g, char* smem_r
           }
         }
       }
+    if (rv_raw != nullptr) {
+      const TIO* rv = static_cast<const TIO*>(rv_raw);  // the rows' known noise variances: constant over a fit's evaluations
+      // kmat_kernel's rule: (c k(0) + s2) + v_i, added by the thread that wrote the entry -- in the diagonal tiles (0 and 2) the one
+      // whose four columns hold the row's own column (tx = (row within the tile) >> 2).  Rows >= n keep the padding's one.
+#pragma unroll
+      for (int r = 0; r < 2; ++r) {
+        const int li = ty + 16 * (2 * half + r);
+        if ((li >> 2) == tx) {
+#pragma unroll
+          for (int tile = 0; tile < 3; tile += 2) {
+            const int gi = tile_i0(tile) + li;
+            if (gi < n) As[gi * S + gi] = (T)kmat_add_rv<TIO>((TIO)As[gi * S + gi], rv[gi]);
+          }
+        }
+      }
+    }
     __syncthreads();
   }
   if (t == 0) g_leaf_stamps[201] = (long long)__builtin_readcyclecounter();
@@ -3765,9 +3808,9 @@ __device__ __forceinline__ void small_eval_body(const SmallEval& g, char* smem_r
 }
 
 template <typename TIO, int NU2>
-__global__ void __launch_bounds__(512, 2) small_eval_kernel(SmallEval g) {
+__global__ void __launch_bounds__(512, 2) small_eval_kernel(SmallEval g, const void* rv) {
   extern __shared__ __align__(16) char smem_raw[];
-  small_eval_body<TIO, NU2>(g, smem_raw);
+  small_eval_body<TIO, NU2>(g, rv, smem_raw);
 }
 
 // ---- the bounded L-BFGS step of lbfgs_step.hpp, one wavefront wide: lane i owns dimension i (the GP has at most 34 parameters
@@ -3976,8 +4019,8 @@ __device__ __forceinline__ bool wl_advance(WaveLbfgs& w, LbfgsState* st, int i, 
 // out-of-line copy of the evaluation for small_fit_kernel: a register allocation of its own (inlined into the loop the kernel
 // spilled 216 VGPRs)
 template <typename TIO, int NU2>
-__device__ __attribute__((noinline)) void small_eval_call(const SmallEval* g, char* smem_raw) {
-  small_eval_body<TIO, NU2>(*g, smem_raw);
+__device__ __attribute__((noinline)) void small_eval_call(const SmallEval* g, const void* rv, char* smem_raw) {
+  small_eval_body<TIO, NU2>(*g, rv, smem_raw);
 }
 
 // ---- a whole optimiser run in ONE launch (n <= 128): the evaluation above in a loop, with the bounded L-BFGS step and the fit's
@@ -4047,7 +4090,7 @@ __global__ void __launch_bounds__(512, 2) small_fit_kernel(const SmallFit* __res
       g.ldiag = f.ldiag[target];
     }
     g.mode = 7;
-    small_eval_call<TIO, NU2>(&g, smem_raw);
+    small_eval_call<TIO, NU2>(&g, f.rv, smem_raw);
     __threadfence();
     __syncthreads();
     if (wave == 0) {
@@ -4134,18 +4177,18 @@ template void launch_small_fit<double>(const SmallFit*, int, int, hipStream_t);
 template void launch_small_fit<float>(const SmallFit*, int, int, hipStream_t);
 
 template <typename T>
-void launch_small_eval(const SmallEval& g, int nu2, hipStream_t s) {
+void launch_small_eval(const SmallEval& g, const void* rv, int nu2, hipStream_t s) {
   const dim3 grid(1), block(512);
   const size_t lds = 163840;  // the whole LDS of a CU: the block image + the kernel's scratch
   switch (nu2) {
-    case 0: hipLaunchKernelGGL((small_eval_kernel<T, 0>), grid, block, lds, s, g); break;
-    case 1: hipLaunchKernelGGL((small_eval_kernel<T, 1>), grid, block, lds, s, g); break;
-    case 3: hipLaunchKernelGGL((small_eval_kernel<T, 3>), grid, block, lds, s, g); break;
-    default: hipLaunchKernelGGL((small_eval_kernel<T, 5>), grid, block, lds, s, g); break;
+    case 0: hipLaunchKernelGGL((small_eval_kernel<T, 0>), grid, block, lds, s, g, rv); break;
+    case 1: hipLaunchKernelGGL((small_eval_kernel<T, 1>), grid, block, lds, s, g, rv); break;
+    case 3: hipLaunchKernelGGL((small_eval_kernel<T, 3>), grid, block, lds, s, g, rv); break;
+    default: hipLaunchKernelGGL((small_eval_kernel<T, 5>), grid, block, lds, s, g, rv); break;
   }
 }
-template void launch_small_eval<double>(const SmallEval&, int, hipStream_t);
-template void launch_small_eval<float>(const SmallEval&, int, hipStream_t);
+template void launch_small_eval<double>(const SmallEval&, const void*, int, hipStream_t);
+template void launch_small_eval<float>(const SmallEval&, const void*, int, hipStream_t);
 
 // =================================================================================================================
 // posterior sample paths (hbegp_paths_*): pathwise conditioning on a random-Fourier-feature prior draw
@@ -4223,11 +4266,12 @@ __global__ void __launch_bounds__(256) paths_project_kernel(const T* __restrict_
   }
 }
 
-// R^T[s][i] = y_i - A sum_chunks part[c][s][i] - sqrt(sigma^2) eps[s][i] (eps may be null); zero for s >= S or i >= n
+// R^T[s][i] = y_i - A sum_chunks part[c][s][i] - sqrt(sigma^2 + v_i) eps[s][i] (eps may be null, v_i = 0 without rv); zero for s >= S or i >= n
 template <typename T>
 __global__ void __launch_bounds__(256) paths_project_finish_kernel(const double* __restrict__ part, int nch, int n, int np, int S, int F,
                                                                    const T* __restrict__ y, const T* __restrict__ eps,
-                                                                   const EvalParams* __restrict__ P, T* __restrict__ Rt) {
+                                                                   const T* __restrict__ rv, const EvalParams* __restrict__ P,
+                                                                   T* __restrict__ Rt) {
 #pragma clang fp contract(off)
   const int i = blockIdx.x * 256 + threadIdx.x, s = blockIdx.y;
   if (i >= np) return;
@@ -4236,7 +4280,8 @@ __global__ void __launch_bounds__(256) paths_project_finish_kernel(const double*
     double sm = 0.0;
     for (int c = 0; c < nch; ++c) sm += part[((size_t)c * S + s) * n + i];
     double v = (double)y[i] - sqrt(2.0 * P->amp / (double)F) * sm;
-    if (eps) v -= sqrt(P->noise) * (double)eps[(size_t)s * n + i];
+    // the noise draw of row i: its learned noise plus, where the model has them, its known variance (rv: n entries or null)
+    if (eps) v -= sqrt(rv ? P->noise + (double)rv[i] : P->noise) * (double)eps[(size_t)s * n + i];
     r = (T)v;
   }
   Rt[(size_t)s * np + i] = r;
@@ -4410,13 +4455,13 @@ void launch_paths_scale_omega(const T* om0, int F, int d, const EvalParams* P, d
 }
 template <typename T>
 void launch_paths_project(const T* X, int n, int d, int np, const double* omT, const double* phase, int F, const double* Wf, int S, int Sp,
-                          const T* y, const T* eps, const EvalParams* P, double* part, T* Rt, hipStream_t s) {
+                          const T* y, const T* eps, const T* rv, const EvalParams* P, double* part, T* Rt, hipStream_t s) {
   int fch = 0;
   const int nch = paths_project_chunks(F, n, S, &fch);
   const size_t lds = sizeof(double) * PP_FT * 64 + sizeof(T) * (size_t)d * 64;
   hipLaunchKernelGGL((paths_project_kernel<T>), dim3((n + 63) / 64, nch, (S + 63) / 64), dim3(256), lds, s, X, n, d, omT, phase, F, fch, Wf,
                      S, part);
-  hipLaunchKernelGGL((paths_project_finish_kernel<T>), dim3((np + 255) / 256, Sp), dim3(256), 0, s, part, nch, n, np, S, F, y, eps, P, Rt);
+  hipLaunchKernelGGL((paths_project_finish_kernel<T>), dim3((np + 255) / 256, Sp), dim3(256), 0, s, part, nch, n, np, S, F, y, eps, rv, P, Rt);
 }
 template <typename T>
 void launch_paths_eval(const T* Xs, int m, int per_path, int S, const T* X, int n, int d, int np, int nu2, const EvalParams* P, const T* Vt,
@@ -4445,7 +4490,7 @@ void launch_paths_eval(const T* Xs, int m, int per_path, int S, const T* X, int 
 #define PATHS_INST(T)                                                                                                                     \
   template void launch_paths_scale_omega<T>(const T*, int, int, const EvalParams*, double*, hipStream_t);                                  \
   template void launch_paths_project<T>(const T*, int, int, int, const double*, const double*, int, const double*, int, int, const T*,     \
-                                        const T*, const EvalParams*, double*, T*, hipStream_t);                                            \
+                                        const T*, const T*, const EvalParams*, double*, T*, hipStream_t);                                  \
   template void launch_paths_eval<T>(const T*, int, int, int, const T*, int, int, int, int, const EvalParams*, const T*, const double*,    \
                                      const double*, const double*, int, int, double*, T*, T*, hipStream_t);
 PATHS_INST(double)

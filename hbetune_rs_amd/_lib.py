@@ -205,6 +205,22 @@ SIGNATURES = {
     "hbegp_debug_dag_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip, _ip, _ip, _dp, _dp, _dp, C.c_char_p,
                                        C.c_int]),
     "hbegp_minimize_by_gradient": (C.c_double, [OBJECTIVE_FN, _vp, _dp, _dp, _dp, C.c_int, C.c_int]),
+    # known per-row noise variances: the plain signatures with `const double* rv` behind y
+    "hbegp_problem_create_rv_f64": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int, C.c_int, C.c_double, C.c_int, C.POINTER(_vp)]),
+    "hbegp_problem_create_rv_f32": (C.c_int, [_vp, _fp, _fp, _dp, C.c_int, C.c_int, C.c_double, C.c_int, C.POINTER(_vp)]),
+    "hbegp_fit_rv_f64": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int, C.c_int, C.c_double, _dp, _dp, _dp, _dp, C.c_int,
+                                   C.POINTER(FitOptions), _dp, _dp, C.POINTER(_vp)]),
+    "hbegp_fit_rv_f32": (C.c_int, [_vp, _fp, _fp, _dp, C.c_int, C.c_int, C.c_double, _dp, _dp, _dp, _dp, C.c_int,
+                                   C.POINTER(FitOptions), _dp, _dp, C.POINTER(_vp)]),
+    "hbegp_fit_loo_rv_f64": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int, C.c_int, C.c_double, _dp, _dp, _dp, _dp, C.c_int,
+                                       C.POINTER(FitOptions), _dp, _dp, C.POINTER(_vp)]),
+    "hbegp_fit_loo_rv_f32": (C.c_int, [_vp, _fp, _fp, _dp, C.c_int, C.c_int, C.c_double, _dp, _dp, _dp, _dp, C.c_int,
+                                       C.POINTER(FitOptions), _dp, _dp, C.POINTER(_vp)]),
+    "hbegp_extend_rv_f64": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int, C.c_int, C.c_double, _dp, _dp, _dp, C.POINTER(_vp)]),
+    "hbegp_extend_rv_f32": (C.c_int, [_vp, _fp, _fp, _dp, C.c_int, C.c_int, C.c_double, _dp, _dp, _dp, C.POINTER(_vp)]),
+    "hbegp_extend_from_rv_f64": (C.c_int, [_vp, _vp, _dp, _dp, _dp, C.c_int, C.POINTER(_vp), _ip]),
+    "hbegp_extend_from_rv_f32": (C.c_int, [_vp, _vp, _fp, _fp, _dp, C.c_int, C.POINTER(_vp), _ip]),
+    "hbegp_model_row_variance": (C.c_int, [_vp, _dp]),
 }
 
 _lib = None

@@ -60,6 +60,16 @@ class YNormalize:
             return (y - self.expected) / self.amplitude + y.dtype.type(FUDGE_MIN)
         return np.log(y - self.expected) / self.amplitude
 
+    def project_variance_into_normalized(self, y, y_variance):
+        """The variance of a measured y (of a mean of replicates: the variance of that mean) in the normalised space, for
+        FittedKernel's row_variance.  Linear: y_variance / amplitude^2, exact.  Logarithmic: first order (the delta method),
+        y_variance times the squared derivative of the projection, 1 / ((y - expected) amplitude)^2.  Not in the reference."""
+        y = np.asarray(y)
+        var = np.asarray(y_variance, dtype=np.float64)
+        if self.projection == "linear":
+            return var / float(self.amplitude) ** 2
+        return var / ((y.astype(np.float64) - float(self.expected)) * float(self.amplitude)) ** 2
+
     def project_location_from_normalized(self, y):  # :214-224
         y = np.asarray(y)
         if self.projection == "linear":
@@ -84,6 +94,32 @@ class YNormalize:
         if self.projection == "linear":
             return np.sqrt(variance) * self.amplitude / ((mean - mean.dtype.type(FUDGE_MIN)) * self.amplitude + self.expected)
         return np.sqrt(np.exp(variance * self.amplitude ** 2) - 1)
+
+
+def aggregate_replicates(x, y):
+    """Repeated measurements of the same configuration -> one row each: (x_unique [u, d] in order of first appearance, mean [u],
+    variance of that mean [u] float64, count [u]).  A row seen k >= 2 times: its unbiased sample variance / k.  A row seen once
+    has no variance of its own: it gets the pooled variance of the replicated rows (their within-row sums of squares over their
+    degrees of freedom; 0 where no row is replicated).  The result feeds EstimatorGPR.estimate(..., y_variance=): n and the n^3
+    work then follow the number of configurations, not of measurements."""
+    x = np.asarray(x)
+    y = np.asarray(y)
+    assert x.ndim == 2 and y.shape == (x.shape[0],)
+    _, first, inverse, counts = np.unique(x, axis=0, return_index=True, return_inverse=True, return_counts=True)
+    inverse = np.asarray(inverse).reshape(-1)
+    order = np.argsort(first, kind="stable")  # np.unique sorts the rows: back to the order of first appearance
+    rank = np.empty_like(order)
+    rank[order] = np.arange(len(order))
+    group = rank[inverse]
+    u = len(order)
+    counts = counts[order]
+    y64 = y.astype(np.float64)
+    mean = np.bincount(group, weights=y64, minlength=u) / counts
+    ss = np.bincount(group, weights=(y64 - mean[group]) ** 2, minlength=u)
+    dof = counts - 1
+    pooled = ss[dof > 0].sum() / dof[dof > 0].sum() if (dof > 0).any() else 0.0
+    var = np.where(dof > 0, ss / np.maximum(dof, 1) / counts, pooled)
+    return x[first[order]], mean.astype(y.dtype), var, counts
 
 
 def _norm_cdf(z):
@@ -1382,11 +1418,15 @@ class EstimatorGPR:
         hi = np.array([self._noise_bounds[1], a_hi] + [b[1] for b in self._length_scale_bounds])
         return theta0, lo, hi
 
-    def estimate(self, x, y, prior, rng):  # gpr.rs:238-291
+    def estimate(self, x, y, prior, rng, y_variance=None):  # gpr.rs:238-291
+        """y_variance (opt-in, not in the reference): the known noise variance of every y in y's own units -- for means of
+        replicates the variance of the mean (aggregate_replicates).  It is projected into the normalised space and rides on the
+        diagonal next to the learned noise (FittedKernel.new(..., row_variance=))."""
         x = np.asarray(x)
         y = np.asarray(y, dtype=x.dtype)
         assert y.shape == (x.shape[0],), f"expected y values for {x.shape[0]} observations"
         y_train, y_norm = YNormalize.new_project_into_normalized(y, self._y_projection, self._known_optimum)
+        row_variance = None if y_variance is None else y_norm.project_variance_into_normalized(y, y_variance)
         theta0, lo, hi = self._theta_and_bounds(prior, y_train)
         fork = rng.fork_random_state()  # gpr.rs:276
         p = len(theta0)
@@ -1398,17 +1438,29 @@ class EstimatorGPR:
         # the estimator's own nu only configures the default kernel
         nu = prior.fitted.nu if prior is not None else self._matern_nu
         fit = gpr.FittedKernel.new_by_loo if self._objective == "loo" else gpr.FittedKernel.new
-        fitted = fit(x, y_train.astype(x.dtype), theta0, lo, hi, starts, nu=nu, ctx=self.ctx)
+        if row_variance is None:
+            fitted = fit(x, y_train.astype(x.dtype), theta0, lo, hi, starts, nu=nu, ctx=self.ctx)
+        else:
+            fitted = fit(x, y_train.astype(x.dtype), theta0, lo, hi, starts, nu=nu, ctx=self.ctx, row_variance=row_variance)
         return SurrogateModelGPR(fitted, (lo[0], hi[0]), (lo[1], hi[1]), list(zip(lo[2:], hi[2:])), y_norm, x.dtype)
 
-    def extend(self, x, y, prior, rng=None):  # gpr.rs:293-337
+    def extend(self, x, y, prior, rng=None, y_variance=None):  # gpr.rs:293-337
+        """y_variance: as in `estimate`.  Without it the new model has no row variances, whatever the prior carried."""
         x = np.asarray(x)
         y = np.asarray(y, dtype=x.dtype)
         assert y.shape == (x.shape[0],), f"expected y values for {x.shape[0]} observations"
         y_train, y_norm = YNormalize.new_project_into_normalized(y, self._y_projection, self._known_optimum)
+        row_variance = None if y_variance is None else y_norm.project_variance_into_normalized(y, y_variance)
         lo = np.array([prior.noise_bounds[0], prior.amplitude_bounds[0]] + [b[0] for b in prior.length_scale_bounds])
         hi = np.array([prior.noise_bounds[1], prior.amplitude_bounds[1]] + [b[1] for b in prior.length_scale_bounds])
-        if prior.fitted.dtype == x.dtype:  # the kernel (incl. its nu) is the prior's (prior.kernel.clone(), gpr.rs:318-323)
+        if row_variance is not None:
+            if prior.fitted.dtype == x.dtype:
+                fitted = prior.fitted.extend_with(x, y_train.astype(x.dtype), ctx=self.ctx, row_variance=row_variance)
+            else:
+                fitted = gpr.FittedKernel.extend(x, y_train.astype(x.dtype), prior.fitted.theta, lo, hi, nu=prior.fitted.nu, ctx=self.ctx,
+                                                 row_variance=row_variance)
+        elif prior.fitted.dtype == x.dtype and getattr(prior.fitted, "row_variance", None) is None:
+            # the kernel (incl. its nu) is the prior's (prior.kernel.clone(), gpr.rs:318-323)
             # the caller appends its validation samples to the rows the prior was built on (minimize.rs:629-644): the engine
             # reuses the prior's factorisation for the unchanged leading rows (falls back by itself when they differ)
             fitted = prior.fitted.extend_with(x, y_train.astype(x.dtype), ctx=self.ctx)

@@ -62,10 +62,22 @@ def device_count():
     return _lib.load().hbegp_device_count()
 
 
+def _row_variance(row_variance, n):
+    """The caller's per-row noise variances as the C ABI takes them: float64 [n], or None."""
+    if row_variance is None:
+        return None
+    rv = _lib.as_c(np.asarray(row_variance, dtype=np.float64).reshape(-1), np.float64)
+    if rv.shape != (n,):
+        raise ValueError(f"row_variance must have one entry per training row ({n}), got {rv.shape}")
+    return rv
+
+
 class Problem:
     """X, y resident on the device; repeated lml/gradient evaluations (the optimiser's inner loop)."""
 
-    def __init__(self, x_train, y_train, nu=2.5, n_slots=1, ctx=None):
+    def __init__(self, x_train, y_train, nu=2.5, n_slots=1, ctx=None, row_variance=None):
+        """row_variance: known noise variances v_i >= 0 of the rows (normalised y scale), added to the diagonal next to the learned
+        noise: K = c Matern + diag(s2 + v)."""
         lib = _lib.load()
         self.ctx = ctx or default_context()
         self.dtype = np.dtype(x_train.dtype)
@@ -77,8 +89,14 @@ class Problem:
         self.p = self.d + 2
         self._sfx = sfx
         self._h = C.c_void_p()
-        create = getattr(lib, f"hbegp_problem_create_{sfx}")
-        _lib.check(create(self.ctx._h, _lib.aptr(self.x), _lib.aptr(self.y), self.n, self.d, float(nu), n_slots, C.byref(self._h)))
+        self.row_variance = _row_variance(row_variance, self.n)
+        if self.row_variance is None:
+            create = getattr(lib, f"hbegp_problem_create_{sfx}")
+            _lib.check(create(self.ctx._h, _lib.aptr(self.x), _lib.aptr(self.y), self.n, self.d, float(nu), n_slots, C.byref(self._h)))
+        else:
+            create = getattr(lib, f"hbegp_problem_create_rv_{sfx}")
+            _lib.check(create(self.ctx._h, _lib.aptr(self.x), _lib.aptr(self.y), _lib.dptr(self.row_variance), self.n, self.d, float(nu),
+                              n_slots, C.byref(self._h)))
 
     def close(self):
         if self._h:
@@ -197,6 +215,17 @@ class FittedKernel:
     def length_scale(self):
         return np.exp(self.theta[2:])
 
+    @property
+    def row_variance(self):
+        """The per-row noise variances the model works with (hbegp_model_row_variance), float64 [n] -- for a float32 model the
+        rounded values, widened; None for a model without them."""
+        lib = _lib.load()
+        if lib.hbegp_model_row_variance(self._h, None) != 1:
+            return None
+        out = np.zeros(self.n)
+        lib.hbegp_model_row_variance(self._h, _lib.dptr(out))
+        return out
+
     def device_params(self):
         """(noise, amplitude, length_scale) as the model's posterior queries use them (hbegp_model_debug_params): for a
         device-driven fit the captured evaluation's own numbers, which may differ from exp(theta) in the last bit."""
@@ -213,22 +242,27 @@ class FittedKernel:
         return alpha, kinv
 
     @staticmethod
-    def new(x_train, y_train, theta0, lo, hi, starts=None, nu=2.5, ctx=None, maxeval=150, fixed_work=False, trace=False):
+    def new(x_train, y_train, theta0, lo, hi, starts=None, nu=2.5, ctx=None, maxeval=150, fixed_work=False, trace=False,
+            row_variance=None):
         """FittedKernel::new (fit.rs:18-31, 71-176): 1 + len(starts) bounded L-BFGS runs, capture the best lml.
 
         trace=True records (theta, lml, gradient, run) of every evaluation; a fit that records gradients evaluates every
         line-search trial whole.  trace="lml" records (theta, lml, run) only and leaves the evaluation as an untraced fit's:
-        trials the optimiser rejects end after their lml (`n_lml_only` counts them; HBEGP_LAZY_GRAD=0 turns that off)."""
-        return FittedKernel._fit("hbegp_fit", x_train, y_train, theta0, lo, hi, starts, nu, ctx, maxeval, fixed_work, trace)
+        trials the optimiser rejects end after their lml (`n_lml_only` counts them; HBEGP_LAZY_GRAD=0 turns that off).
+
+        row_variance: known noise variances v_i >= 0 of the rows in the normalised y scale (hbegp_fit_rv_*): data, not a
+        hyper-parameter -- K = c Matern + diag(s2 + v), and s2 is still learned as the homoscedastic remainder."""
+        return FittedKernel._fit("hbegp_fit", x_train, y_train, theta0, lo, hi, starts, nu, ctx, maxeval, fixed_work, trace, row_variance)
 
     @staticmethod
-    def new_by_loo(x_train, y_train, theta0, lo, hi, starts=None, nu=2.5, ctx=None, maxeval=150, fixed_work=False, trace=False):
+    def new_by_loo(x_train, y_train, theta0, lo, hi, starts=None, nu=2.5, ctx=None, maxeval=150, fixed_work=False, trace=False,
+                   row_variance=None):
         """`new` with the leave-one-out log pseudo-likelihood as the objective (hbegp_fit_loo_*): the same runs, options and
         trace (trace["lml"] holds loo), capture of the best loo in `.loo_best`; the model is `extend` at the captured theta."""
-        return FittedKernel._fit("hbegp_fit_loo", x_train, y_train, theta0, lo, hi, starts, nu, ctx, maxeval, fixed_work, trace)
+        return FittedKernel._fit("hbegp_fit_loo", x_train, y_train, theta0, lo, hi, starts, nu, ctx, maxeval, fixed_work, trace, row_variance)
 
     @staticmethod
-    def _fit(symbol, x_train, y_train, theta0, lo, hi, starts, nu, ctx, maxeval, fixed_work, trace):
+    def _fit(symbol, x_train, y_train, theta0, lo, hi, starts, nu, ctx, maxeval, fixed_work, trace, row_variance=None):
         lib = _lib.load()
         ctx = ctx or default_context()
         dtype = np.dtype(x_train.dtype)
@@ -264,9 +298,13 @@ class FittedKernel:
         handle = C.c_void_p()
         theta_best = np.zeros(p)
         lml_best = C.c_double()
-        fit = getattr(lib, f"{symbol}_{sfx}")
-        _lib.check(fit(ctx._h, _lib.aptr(x), _lib.aptr(y), n, d, float(nu), _lib.dptr(theta0), _lib.dptr(lo), _lib.dptr(hi),
-                       _lib.dptr(starts_c), n_restarts, C.byref(opt), _lib.dptr(theta_best), C.byref(lml_best), C.byref(handle)))
+        rv = _row_variance(row_variance, n)
+        tail = (n, d, float(nu), _lib.dptr(theta0), _lib.dptr(lo), _lib.dptr(hi), _lib.dptr(starts_c), n_restarts, C.byref(opt),
+                _lib.dptr(theta_best), C.byref(lml_best), C.byref(handle))
+        if rv is None:
+            _lib.check(getattr(lib, f"{symbol}_{sfx}")(ctx._h, _lib.aptr(x), _lib.aptr(y), *tail))
+        else:
+            _lib.check(getattr(lib, f"{symbol}_rv_{sfx}")(ctx._h, _lib.aptr(x), _lib.aptr(y), _lib.dptr(rv), *tail))
         fk = FittedKernel(handle, dtype, n, d, nu)
         fk.x_train, fk.y_train = x, y
         fk.n_evals, fk.n_not_pd = n_evals.value, n_not_pd.value
@@ -289,8 +327,9 @@ class FittedKernel:
         return fk
 
     @staticmethod
-    def extend(x_train, y_train, theta, lo=None, hi=None, nu=2.5, ctx=None):
-        """FittedKernel::extend (fit.rs:33-68): one evaluation at fixed theta + K^-1.  Raises where the reference panics."""
+    def extend(x_train, y_train, theta, lo=None, hi=None, nu=2.5, ctx=None, row_variance=None):
+        """FittedKernel::extend (fit.rs:33-68): one evaluation at fixed theta + K^-1.  Raises where the reference panics.
+        row_variance: as in `new` (hbegp_extend_rv_*)."""
         lib = _lib.load()
         ctx = ctx or default_context()
         dtype = np.dtype(x_train.dtype)
@@ -302,17 +341,22 @@ class FittedKernel:
         lo = None if lo is None else _lib.as_c(lo, np.float64)
         hi = None if hi is None else _lib.as_c(hi, np.float64)
         handle = C.c_void_p()
-        ext = getattr(lib, f"hbegp_extend_{sfx}")
-        _lib.check(ext(ctx._h, _lib.aptr(x), _lib.aptr(y), n, d, float(nu), _lib.dptr(theta), _lib.dptr(lo), _lib.dptr(hi),
-                       C.byref(handle)))
+        rv = _row_variance(row_variance, n)
+        tail = (n, d, float(nu), _lib.dptr(theta), _lib.dptr(lo), _lib.dptr(hi), C.byref(handle))
+        if rv is None:
+            _lib.check(getattr(lib, f"hbegp_extend_{sfx}")(ctx._h, _lib.aptr(x), _lib.aptr(y), *tail))
+        else:
+            _lib.check(getattr(lib, f"hbegp_extend_rv_{sfx}")(ctx._h, _lib.aptr(x), _lib.aptr(y), _lib.dptr(rv), *tail))
         fk = FittedKernel(handle, dtype, n, d, nu)
         fk.x_train, fk.y_train = x, y
         return fk
 
-    def extend_with(self, x_train, y_train, ctx=None):
+    def extend_with(self, x_train, y_train, ctx=None, row_variance=None):
         """FittedKernel::extend (fit.rs:33-68) at this model's theta on data whose leading rows are this model's training
         rows (minimize.rs:629-644 appends the validation samples): reuses the factorisation of the kept 128-blocks, O(n^2 k)
-        instead of O(n^3).  Falls back to the full path when the prefix differs.  Sets `.incremental` on the result."""
+        instead of O(n^3).  Falls back to the full path when the prefix differs.  Sets `.incremental` on the result.
+        row_variance: the rows' known noise variances (hbegp_extend_from_rv_*); their prefix must equal this model's too (a
+        model without them counts as zeros).  A model that carries them needs the argument."""
         lib = _lib.load()
         ctx = ctx or default_context()
         x = _lib.as_c(x_train, self.dtype)
@@ -321,8 +365,13 @@ class FittedKernel:
         assert d == self.d
         handle = C.c_void_p()
         inc = C.c_int(0)
-        ext = getattr(lib, f"hbegp_extend_from_{self._sfx}")
-        _lib.check(ext(ctx._h, self._h, _lib.aptr(x), _lib.aptr(y), n, C.byref(handle), C.byref(inc)))
+        rv = _row_variance(row_variance, n)
+        if rv is None:
+            ext = getattr(lib, f"hbegp_extend_from_{self._sfx}")
+            _lib.check(ext(ctx._h, self._h, _lib.aptr(x), _lib.aptr(y), n, C.byref(handle), C.byref(inc)))
+        else:
+            ext = getattr(lib, f"hbegp_extend_from_rv_{self._sfx}")
+            _lib.check(ext(ctx._h, self._h, _lib.aptr(x), _lib.aptr(y), _lib.dptr(rv), n, C.byref(handle), C.byref(inc)))
         fk = FittedKernel(handle, self.dtype, n, d, self.nu)
         fk.x_train, fk.y_train = x, y
         fk.incremental = bool(inc.value)

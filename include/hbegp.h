@@ -255,6 +255,54 @@ int hbegp_extend_from_f64(hbegp_ctx* ctx, hbegp_model* prior, const double* X, c
 int hbegp_extend_from_f32(hbegp_ctx* ctx, hbegp_model* prior, const float* X, const float* y, int n, hbegp_model** model,
                           int* incremental);
 
+/* ---- row variances: known per-row noise on the diagonal (stochastic kriging) --------------------------
+ * A caller who repeats measurements holds, per row, a mean and the variance of that mean.  The `_rv` entry points take those
+ * variances as data: K = c Matern + diag(s2 + v_i), v_i = rv[i] >= 0 in the y-normalised scale.  theta, its order, bounds and
+ * clamping and p = d + 2 are unchanged; s2 is still learned, as the homoscedastic remainder.  A diagonal entry is formed as
+ * (c k(0) + s2) + v_i, each + rounded once, so v = 0 everywhere gives the bits of the call without rv.
+ *   rv       n doubles for both element types (like bounds and theta), converted once to the element type on upload.  NULL:
+ *            the `_rv` call is its plain counterpart, bit for bit.  A negative or non-finite rv[i] (non-finite also: after the
+ *            conversion to float) is HBEGP_EINVAL with the index in the message, before any device call; nothing is written.
+ *   problem  hbegp_problem_eval, _eval_loo, _get_* and _kmat_* of such a problem work with v on the diagonal.
+ *   fit      the signatures of hbegp_fit_* / hbegp_fit_loo_* / hbegp_extend_* with rv behind y; every path decision (single
+ *            launch up to 128 rows, launches, task queue) is taken as without rv.
+ *   extend_from  the incremental path runs only when the prefix of X, of y's rows and of v equals the prior's (a prior without
+ *            v counts as zeros), else the full path.  Plain hbegp_extend_from_* on a prior that carries v is HBEGP_EINVAL, and so
+ *            is hbegp_extend_from_rv_* with rv = NULL on such a prior: it is the plain call, refusals included.
+ * Everything downstream reads K^-1, L^-1 and alpha and is unchanged: predictions stay those of the latent function and exclude
+ * s2 and v.  What the model's v does change:
+ *   hbegp_paths_create_*   the noise draw of row i is sqrt(s2 + v_i) eps (a call without eps is unaffected);
+ *   hbegp_model_loo_*      var is that of the left-out noisy observation, 1 / K^-1_ii, which now contains s2 + v_i.
+ * What stays homoscedastic: hbegp_select_batch_*, hbegp_knowledge_gradient_* and hbegp_qei_* keep s2 alone as the noise of the
+ * observation they imagine at a NEW point (no v is known there). */
+int hbegp_problem_create_rv_f64(hbegp_ctx* ctx, const double* X, const double* y, const double* rv, int n, int d, double nu,
+                                int n_slots, hbegp_problem** out);
+int hbegp_problem_create_rv_f32(hbegp_ctx* ctx, const float* X, const float* y, const double* rv, int n, int d, double nu,
+                                int n_slots, hbegp_problem** out);
+int hbegp_fit_rv_f64(hbegp_ctx* ctx, const double* X, const double* y, const double* rv, int n, int d, double nu,
+                     const double* theta0, const double* lo, const double* hi, const double* starts, int n_restarts,
+                     const hbegp_fit_options* opt, double* theta_best, double* lml_best, hbegp_model** model);
+int hbegp_fit_rv_f32(hbegp_ctx* ctx, const float* X, const float* y, const double* rv, int n, int d, double nu,
+                     const double* theta0, const double* lo, const double* hi, const double* starts, int n_restarts,
+                     const hbegp_fit_options* opt, double* theta_best, double* lml_best, hbegp_model** model);
+int hbegp_fit_loo_rv_f64(hbegp_ctx* ctx, const double* X, const double* y, const double* rv, int n, int d, double nu,
+                         const double* theta0, const double* lo, const double* hi, const double* starts, int n_restarts,
+                         const hbegp_fit_options* opt, double* theta_best, double* loo_best, hbegp_model** model);
+int hbegp_fit_loo_rv_f32(hbegp_ctx* ctx, const float* X, const float* y, const double* rv, int n, int d, double nu,
+                         const double* theta0, const double* lo, const double* hi, const double* starts, int n_restarts,
+                         const hbegp_fit_options* opt, double* theta_best, double* loo_best, hbegp_model** model);
+int hbegp_extend_rv_f64(hbegp_ctx* ctx, const double* X, const double* y, const double* rv, int n, int d, double nu,
+                        const double* theta, const double* lo, const double* hi, hbegp_model** model);
+int hbegp_extend_rv_f32(hbegp_ctx* ctx, const float* X, const float* y, const double* rv, int n, int d, double nu,
+                        const double* theta, const double* lo, const double* hi, hbegp_model** model);
+int hbegp_extend_from_rv_f64(hbegp_ctx* ctx, hbegp_model* prior, const double* X, const double* y, const double* rv, int n,
+                             hbegp_model** model, int* incremental);
+int hbegp_extend_from_rv_f32(hbegp_ctx* ctx, hbegp_model* prior, const float* X, const float* y, const double* rv, int n,
+                             hbegp_model** model, int* incremental);
+/* 1 and, with rv != NULL, the n variances the model works with (for an f32 model the rounded values, widened); 0 for a model
+ * without them (rv is not written). */
+int hbegp_model_row_variance(const hbegp_model* model, double* rv);
+
 /* ---- model: mirrors predict() (predict.rs:7-52) and the FittedKernel fields -------------------------- */
 /* mean[m]; var[m] or NULL.  var = c + 1e-5 - rowsum((K* K^-1) o K*), negatives clamped to 0 (predict.rs:25-48);
  * it excludes s2 (the reference predicts the latent function).  *n_warn (may be NULL) = number of variances below

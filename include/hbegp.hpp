@@ -50,6 +50,14 @@ template <> struct Abi<double> {
   static int extend(hbegp_ctx* c, const double* x, const double* y, int n, int d, double nu, const double* t, const double* lo,
                     const double* hi, hbegp_model** m) { return hbegp_extend_f64(c, x, y, n, d, nu, t, lo, hi, m); }
   static int extend_from(hbegp_ctx* c, hbegp_model* p, const double* x, const double* y, int n, hbegp_model** m, int* inc) { return hbegp_extend_from_f64(c, p, x, y, n, m, inc); }
+  // the same with known per-row noise variances rv[n] behind y (hbegp.h: row variances)
+  static int fit_rv(hbegp_ctx* c, const double* x, const double* y, const double* rv, int n, int d, double nu, const double* t0, const double* lo,
+                    const double* hi, const double* st, int r, const hbegp_fit_options* o, double* tb, double* lb, hbegp_model** m) {
+    return hbegp_fit_rv_f64(c, x, y, rv, n, d, nu, t0, lo, hi, st, r, o, tb, lb, m);
+  }
+  static int extend_rv(hbegp_ctx* c, const double* x, const double* y, const double* rv, int n, int d, double nu, const double* t, const double* lo,
+                       const double* hi, hbegp_model** m) { return hbegp_extend_rv_f64(c, x, y, rv, n, d, nu, t, lo, hi, m); }
+  static int extend_from_rv(hbegp_ctx* c, hbegp_model* p, const double* x, const double* y, const double* rv, int n, hbegp_model** m, int* inc) { return hbegp_extend_from_rv_f64(c, p, x, y, rv, n, m, inc); }
   static int predict(hbegp_model* m, const double* xs, int k, double* mean, double* var, int* w) { return hbegp_predict_f64(m, xs, k, mean, var, w); }
   static int predict_grad(hbegp_model* m, const double* xs, int k, double* mean, double* var, double* dm, double* dv, int* w) {
     return hbegp_predict_grad_f64(m, xs, k, mean, var, dm, dv, w);
@@ -140,6 +148,14 @@ template <> struct Abi<float> {
   static int extend(hbegp_ctx* c, const float* x, const float* y, int n, int d, double nu, const double* t, const double* lo,
                     const double* hi, hbegp_model** m) { return hbegp_extend_f32(c, x, y, n, d, nu, t, lo, hi, m); }
   static int extend_from(hbegp_ctx* c, hbegp_model* p, const float* x, const float* y, int n, hbegp_model** m, int* inc) { return hbegp_extend_from_f32(c, p, x, y, n, m, inc); }
+  // the same with known per-row noise variances rv[n] behind y (hbegp.h: row variances)
+  static int fit_rv(hbegp_ctx* c, const float* x, const float* y, const double* rv, int n, int d, double nu, const double* t0, const double* lo,
+                    const double* hi, const double* st, int r, const hbegp_fit_options* o, double* tb, double* lb, hbegp_model** m) {
+    return hbegp_fit_rv_f32(c, x, y, rv, n, d, nu, t0, lo, hi, st, r, o, tb, lb, m);
+  }
+  static int extend_rv(hbegp_ctx* c, const float* x, const float* y, const double* rv, int n, int d, double nu, const double* t, const double* lo,
+                       const double* hi, hbegp_model** m) { return hbegp_extend_rv_f32(c, x, y, rv, n, d, nu, t, lo, hi, m); }
+  static int extend_from_rv(hbegp_ctx* c, hbegp_model* p, const float* x, const float* y, const double* rv, int n, hbegp_model** m, int* inc) { return hbegp_extend_from_rv_f32(c, p, x, y, rv, n, m, inc); }
   static int predict(hbegp_model* m, const float* xs, int k, float* mean, float* var, int* w) { return hbegp_predict_f32(m, xs, k, mean, var, w); }
   static int predict_grad(hbegp_model* m, const float* xs, int k, float* mean, float* var, float* dm, float* dv, int* w) {
     return hbegp_predict_grad_f32(m, xs, k, mean, var, dm, dv, w);
@@ -242,8 +258,10 @@ class FittedKernel {
   ~FittedKernel() { if (h_) hbegp_model_release(h_); }
 
   // fit.rs:18-31, 71-176.  theta0: log-space start [ln s2, ln c, ln ell..]; starts: n_restarts * p log-space start points.
+  // row_variance (here and in extend / extend_with; may be nullptr): n known noise variances of the rows in the normalised y scale,
+  // K = c Matern + diag(s2 + v) (hbegp.h: row variances); nullptr is the plain call.
   static FittedKernel new_(const Context& ctx, const A* x, const A* y, int n, int d, double nu, const std::vector<double>& theta0,
-                           const KernelBounds& b, const std::vector<double>& starts, int maxeval = 150) {
+                           const KernelBounds& b, const std::vector<double>& starts, int maxeval = 150, const double* row_variance = nullptr) {
     const int p = d + 2;
     if ((int)theta0.size() != p || (int)b.lo.size() != p || (int)b.hi.size() != p || starts.size() % p != 0)
       throw Error(HBEGP_EINVAL, "theta0 / bounds / starts have the wrong length");
@@ -251,31 +269,49 @@ class FittedKernel {
     opt.maxeval = maxeval;
     FittedKernel fk;
     fk.n_ = n; fk.d_ = d; fk.theta_.resize(p);
-    check(detail::Abi<A>::fit(ctx.get(), x, y, n, d, nu, theta0.data(), b.lo.data(), b.hi.data(), starts.empty() ? nullptr : starts.data(),
-                              (int)(starts.size() / p), &opt, fk.theta_.data(), &fk.lml_, &fk.h_));
+    const double* st = starts.empty() ? nullptr : starts.data();
+    const int nr = (int)(starts.size() / p);
+    check(row_variance ? detail::Abi<A>::fit_rv(ctx.get(), x, y, row_variance, n, d, nu, theta0.data(), b.lo.data(), b.hi.data(), st, nr, &opt,
+                                                fk.theta_.data(), &fk.lml_, &fk.h_)
+                       : detail::Abi<A>::fit(ctx.get(), x, y, n, d, nu, theta0.data(), b.lo.data(), b.hi.data(), st, nr, &opt, fk.theta_.data(),
+                                             &fk.lml_, &fk.h_));
     return fk;
   }
   // fit.rs:33-68
   static FittedKernel extend(const Context& ctx, const A* x, const A* y, int n, int d, double nu, const std::vector<double>& theta,
-                             const KernelBounds* b = nullptr) {
+                             const KernelBounds* b = nullptr, const double* row_variance = nullptr) {
     FittedKernel fk;
     fk.n_ = n; fk.d_ = d; fk.theta_.resize(d + 2);
-    check(detail::Abi<A>::extend(ctx.get(), x, y, n, d, nu, theta.data(), b ? b->lo.data() : nullptr, b ? b->hi.data() : nullptr, &fk.h_));
+    const double* lo = b ? b->lo.data() : nullptr;
+    const double* hi = b ? b->hi.data() : nullptr;
+    check(row_variance ? detail::Abi<A>::extend_rv(ctx.get(), x, y, row_variance, n, d, nu, theta.data(), lo, hi, &fk.h_)
+                       : detail::Abi<A>::extend(ctx.get(), x, y, n, d, nu, theta.data(), lo, hi, &fk.h_));
     check(detail::Abi<A>::get(fk.h_, fk.theta_.data(), nullptr, nullptr));
     check(hbegp_model_info(fk.h_, nullptr, nullptr, nullptr, nullptr, &fk.lml_));
     return fk;
   }
   // fit.rs:33-68 at this model's theta on data whose leading rows are this model's training rows (minimize.rs:629-644):
   // reuses the factorisation of the unchanged 128-blocks; *incremental (optional) tells whether it could
-  FittedKernel extend_with(const Context& ctx, const A* x, const A* y, int n, bool* incremental = nullptr) const {
+  // (a model that carries row variances needs row_variance here: their prefix must equal the model's too)
+  FittedKernel extend_with(const Context& ctx, const A* x, const A* y, int n, bool* incremental = nullptr,
+                           const double* row_variance = nullptr) const {
     FittedKernel fk;
     fk.n_ = n; fk.d_ = d_; fk.theta_.resize(d_ + 2);
     int inc = 0;
-    check(detail::Abi<A>::extend_from(ctx.get(), h_, x, y, n, &fk.h_, &inc));
+    check(row_variance ? detail::Abi<A>::extend_from_rv(ctx.get(), h_, x, y, row_variance, n, &fk.h_, &inc)
+                       : detail::Abi<A>::extend_from(ctx.get(), h_, x, y, n, &fk.h_, &inc));
     if (incremental) *incremental = inc != 0;
     check(detail::Abi<A>::get(fk.h_, fk.theta_.data(), nullptr, nullptr));
     check(hbegp_model_info(fk.h_, nullptr, nullptr, nullptr, nullptr, &fk.lml_));
     return fk;
+  }
+  // the model's row variances (n doubles; for an f32 model the rounded values, widened); empty for a model without them
+  std::vector<double> row_variance() const {
+    std::vector<double> rv;
+    if (hbegp_model_row_variance(h_, nullptr) != 1) return rv;
+    rv.resize((size_t)n_);
+    if (hbegp_model_row_variance(h_, rv.data()) != 1) throw Error(HBEGP_EHIP, hbegp_last_error());
+    return rv;
   }
   // predict.rs:7-52: mean (and variance when var != nullptr); returns the number of variances below -sqrt(1e-5)
   int predict(const A* xs, int m, A* mean, A* var) const {
