@@ -20,9 +20,11 @@
 //                                                                                            bumps Uall[N]
 //   X21(N)(i,j)    waits rowfinal(R, i) [X22 row i], Uall[N], Sall[N] (it overwrites T(i,j), read by SYRK and U)
 //                                                                                            bumps Xrow[N][i], Xall[N]
-// Queue order: a list schedule simulated on the host for the number of workgroups the launch will have (critical-path
-// priority, estimated task times); workgroups pull in that order, so tasks tend to be pulled when their inputs are ready.
-// Any topological order is deadlock-free for any number of resident workgroups; this one is also fast.
+// Queue order: a list schedule simulated on the host for a number of workers (critical-path priority, estimated task times);
+// workgroups pull in that order, so tasks tend to be pulled when their inputs are ready.  The number is the launch's workgroup
+// count unless the caller names another (order_wg: a launch that starts beside others has fewer compute units than workgroups
+// for a while; dag_default_order_wg, dag_plan_replay).  Any topological order is deadlock-free for any number of resident
+// workgroups; this one is also fast.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -51,29 +53,75 @@ struct DagPlan {
   double crit_us = 0;       // critical path of the graph under the same estimates
 };
 
+constexpr int DAG_ORDER_BY_LEVEL = -1;  // DagBuilder's order_wg: order the queue for no worker count (order_by_level)
+
+// What a queue of a problem is ordered for by default.  queue: 0 the fused evaluation, 1 the first phase of a two-phase trial
+// (no K^-1 tasks), 2 the K^-1 tasks alone; share: 0 an even launch (the busy-count and crowded-device variants are even
+// launches too), 1 the lead, 2 the lag launch of a fit whose runs have drifted apart (slot_share.hpp); nwg: the launch's
+// workgroups; even_wg: those of the problem's even launch.  0 = the launch's own count, which is what every queue was ordered for
+// before the two were separated.
+// Measured (config M, three slots; profiles/queue_order_workers.txt, profiles/queue_order_sweep.txt): an even launch of 96
+// workgroups holds 64 CUs for its first 0.4 ms and 96 from then on, a lead launch of 80 holds 64 for 0.2 ms and then 80 -- close
+// to their launch sizes, and every other order than the launch's own lost (even: 80 / 88 / 104 / by level +13 / +6 / +8 / +17 ms
+// of a 500 ms fit; lead: 64 - 96 +2).  The lag launch of 128 starts on the 96 CUs an even launch has and gets the other 32 when
+// the lead launches end, a third into its life: ordered for the even launch's count it is the one order that gains (-2.4 ms).
+// DAG_ORDER_MIN_BLOCKS: the size from which this was measured, and from which the recalibrated DagCosts apply.
+constexpr int DAG_ORDER_MIN_BLOCKS = 32;
+inline int dag_default_order_wg(int queue, int share, int nwg, int even_wg, int nblocks, int n_slots) {
+  (void)queue;  // (all three queues of a launch follow its share)
+  if (n_slots < 2 || nblocks < DAG_ORDER_MIN_BLOCKS) return 0;  // one slot, small problems: never measured to gain
+  if (share == 2 && even_wg > 0 && even_wg < nwg) return even_wg;
+  return 0;
+}
+
 struct DagGate {
   int cnt = -1, val = 0;  // cnt < 0: nothing to wait for
 };
 
-// estimated task times in microseconds (MI355X, one workgroup of 512 threads per CU; measured round 2)
+// Estimated task times in microseconds (MI355X, one workgroup of 512 threads per CU): a task's time from "counters complete" to
+// "results published" is fixed + rate x depth / 128, and a task that waits for a counter runs `signal` after the last bump was
+// published.  From the task traces a flagship fit keeps of its own launches (config M: n = 4096, d = 8, f64, three slots side by
+// side; tools/queue_workers.py, profiles/queue_order_trace_summary.txt: class medians over 192 launches, line fits weighted by
+// task count), except the 128x64 tile, which a fit with several slots does not use: from the single-evaluation trace
+// profiles/r05_task_trace_4096.txt (busy 12.12 us at depth 128, 133.12 us at depth 2048).
+// Until then (round 2): diagonal block 28.5, one fixed 1.5 for every tile kind, 3.9 / 7.9 / 15.0 / 1.5 per 128 for the 64x64 /
+// 128x64 / 128x128 / 32x64 tile, and 4.0 of signal latency -- in a trace of today's kernel a waiter runs 1.1 us after the bump
+// (1208 waits of a phase-1 launch, quartiles 0.94 / 1.29), and the next task of the SAME workgroup is staged before the
+// previous one is published (median hand-off -0.24 us).
+// The round-2 table stays in force below DAG_ORDER_MIN_BLOCKS blocks (DagCosts::round2): those queues are byte for byte what they
+// were.  The new table was calibrated on the 128x128 tiles of a 32-block fit, and fixed-work fits of n = 1024 / 2048 gained nothing
+// from queues ordered by it (66.4 -> 66.7, 146.3 -> 146.9 ms; profiles/queue_order_bench.txt).
 struct DagCosts {
-  // from task traces (tools/dag_trace.py, n=4096 f64): diagonal block 28.3 us; tile = 1.5 us + 3.9 (64x64) / 7.9 (128x64) us
-  // per 128 elements of contraction (81-84 % of one CU's fp64 MFMA peak); counter bump -> dependent task running ~4 us
-  double leaf = 28.5 + 4.0;
-  double overhead = 1.5 + 4.0;
-  double per128_big = 7.9;
-  double per128_small = 3.9;
-  double per128_big128 = 15.0;  // 128x128 tile
-  double per128_chain = 1.5;  // 32x64 one-shot tile: one dependent MFMA chain per wave
+  static DagCosts round2() {
+    DagCosts c;
+    c.signal = 4.0; c.leaf = 28.5;
+    c.fixed_small = c.fixed_big = c.fixed_big128 = c.fixed_chain = 1.5; c.acc_big128 = 0.0;
+    c.per128_big = 7.9; c.per128_small = 3.9; c.per128_big128 = c.per128_big128_km = 15.0; c.per128_chain = 1.5;
+    return c;
+  }
+  double signal = 1.1;          // last bump published -> waiting task running
+  double leaf = 26.3;           // diagonal block (3840 tasks: median 26.28, quartiles 25.92 / 26.72)
+  double fixed_small = 3.5;     // 64x64 tile: 3.38 (row-major operand) / 3.67 (beta = 1)
+  double fixed_big = 4.0;       // 128x64 tile
+  double fixed_big128 = 4.2;    // 128x128 tile: 19.16 us at depth 128, 4.18 + 14.99 per 128 over 47 depths
+  double acc_big128 = 1.8;      // ... with beta = 1: the old tile is fetched in the epilogue (5.94 + 15.05 per 128 over 5 depths)
+  double fixed_chain = 3.2;     // 32x64 one-shot tile: 4.48 us at depth 64, 5.72 / 5.44 at depth 128
+  double per128_big = 8.1;
+  double per128_small = 4.0;    // 3.96 (row-major operand, 76 depths) / 4.01 (beta = 1)
+  double per128_big128 = 15.0;
+  double per128_big128_km = 15.0;  // 128x128 tile with a row-major contraction operand (DAGF_AKM / DAGF_BKM): no slower (14.99)
+  double per128_chain = 2.5;    // one dependent MFMA chain per wave
 };
 
 class DagBuilder {
  public:
   // bk: contraction elements per pipeline stage (16 for f64, 32 for f32): ranges are whole stages
   // small_h: nodes whose halves are at most this many 128-blocks wide use 64x64 tiles (latency-bound products)
-  // nwg: workgroups the queue is ordered for (0: keep the recursion's order)
+  // nwg: workgroups the launch will have (0: keep the recursion's order)
   // fine: dependencies per block row (false: on whole subtrees)
-  DagBuilder(int bk, int small_h, int nwg = 0, bool fine = true) : bk_(bk), small_h_(small_h), nwg_(nwg), fine_(fine) {}
+  // order_wg: workers the queue is ordered for -- 0: nwg, as ever; DAG_ORDER_BY_LEVEL: for no count at all (order_by_level)
+  DagBuilder(int bk, int small_h, int nwg = 0, bool fine = true, int order_wg = 0)
+      : bk_(bk), small_h_(small_h), nwg_(nwg), order_wg_(order_wg == 0 ? nwg : order_wg), fine_(fine) {}
 
   // full = true: the kernel-matrix tiles in front of the recursion and the alpha / lml reductions behind it are tasks of the
   // same queue (whole matrix only: blo = 0, bhi = np / 128)
@@ -91,6 +139,7 @@ class DagBuilder {
   // carries the inverse (whole matrix only; the factor L lives in W3)
   DagPlan build(int blo, int bhi, bool lauum = false, bool rl = false) {
     plan_ = DagPlan();
+    cost_ = bhi - blo >= DAG_ORDER_MIN_BLOCKS ? DagCosts() : DagCosts::round2();
     top_lo_ = blo; top_hi_ = bhi;
     if (rl && blo == 0) {
       lauum_split_ = rl_lauum_split_;
@@ -102,7 +151,10 @@ class DagBuilder {
     if (plan_.totals.size() >= 0xffff) plan_.tasks.clear();  // counter ids are 16-bit: the caller falls back
     for (int tot : plan_.totals)
       if (tot > 0xffff) plan_.tasks.clear();
-    if (nwg_ > 0 && !plan_.tasks.empty()) order();
+    if (nwg_ > 0 && !plan_.tasks.empty()) {
+      if (order_wg_ < 0) order_by_level();
+      else order();
+    }
     return plan_;
   }
 
@@ -110,7 +162,7 @@ class DagBuilder {
   // in the big nodes, the block row next to the diagonal chain (the first row of T and of the Schur update, the last row of
   // X21) also uses 64x64 tiles: it sits on the critical path, where a tile's time counts
   static constexpr int crit_rows_ = 1;
-  int bk_, small_h_, nwg_;
+  int bk_, small_h_, nwg_, order_wg_;
   bool fine_;
   int rl_group_ = 32, rl_near_ = 1;
   bool rl_lauum_split_ = true;
@@ -238,7 +290,12 @@ class DagBuilder {
     t.row0 = tl.row0; t.col0 = tl.col0;
     t.kbeg = tl.ka / bk_ * bk_;
     t.kend = (tl.kb + bk_ - 1) / bk_ * bk_;
-    *cost_us = cost_.overhead + (t.kend - t.kbeg) / 128.0 * (tl.kind == DAG_GEMM_128x128 ? cost_.per128_big128 : (tl.kind == DAG_GEMM_128x64 ? cost_.per128_big : (tl.kind == DAG_GEMM_32x64 ? cost_.per128_chain : cost_.per128_small)));
+    const bool km = (op.flags & (DAGF_AKM | DAGF_BKM)) != 0;
+    double fixed = cost_.fixed_small, rate = cost_.per128_small;
+    if (tl.kind == DAG_GEMM_128x128) { fixed = cost_.fixed_big128 + ((op.flags & DAGF_ACC) ? cost_.acc_big128 : 0.0); rate = km ? cost_.per128_big128_km : cost_.per128_big128; }
+    if (tl.kind == DAG_GEMM_128x64) { fixed = cost_.fixed_big; rate = cost_.per128_big; }
+    if (tl.kind == DAG_GEMM_32x64) { fixed = cost_.fixed_chain; rate = cost_.per128_chain; }
+    *cost_us = cost_.signal + fixed + (t.kend - t.kbeg) / 128.0 * rate;
     return t;
   }
   static int count_row(const std::vector<Tile>& tiles, int bi) {
@@ -267,7 +324,7 @@ class DagBuilder {
       t.kind = DAG_LEAF;
       t.row0 = lo;
       const int c = new_counter();
-      push(t, {gate_of(lo)}, c, -1, cost_.leaf);
+      push(t, {gate_of(lo)}, c, -1, cost_.leaf + cost_.signal);
       plan_.n_leaf++;
       out.rowfin.assign(1, DagGate{c, 1});
       out.all = DagGate{c, 1};
@@ -461,7 +518,7 @@ class DagBuilder {
         t.kind = DAG_LEAF;
         t.row0 = k;
         const int c = new_counter();
-        push(t, {last_upd[k][k]}, c, -1, cost_.leaf);
+        push(t, {last_upd[k][k]}, c, -1, cost_.leaf + cost_.signal);
         plan_.n_leaf++;
         leafc[k] = DagGate{c, 1};
       }
@@ -671,13 +728,10 @@ class DagBuilder {
     return out;
   }
 
-  // Reorder the queue: simulate a list schedule with nwg_ workers, priority = longest remaining path.
-  void order() {
+  // bottom level of every task (its own time + the longest path behind it): the emission order is topological, so one
+  // reverse sweep does it
+  std::vector<double> bottom_levels() {
     const int nt = (int)plan_.tasks.size(), nc = (int)plan_.totals.size();
-    std::vector<std::vector<int>> waiters(nc);
-    for (int i = 0; i < nt; ++i)
-      for (int w = 0; w < plan_.tasks[i].nwait; ++w) waiters[plan_.tasks[i].wcnt[w]].push_back(i);
-    // bottom levels: the emission order is topological, so one reverse sweep does it
     std::vector<double> bl(nt, 0.0), blc(nc, 0.0);
     for (int i = nt - 1; i >= 0; --i) {
       const DagTask& t = plan_.tasks[i];
@@ -688,6 +742,20 @@ class DagBuilder {
       for (int w = 0; w < t.nwait; ++w) blc[t.wcnt[w]] = std::max(blc[t.wcnt[w]], bl[i]);
     }
     plan_.crit_us = *std::max_element(bl.begin(), bl.end());
+    return bl;
+  }
+
+  // Reorder the queue for no worker count at all: strictly by bottom level among the tasks whose predecessors are already in
+  // the queue (a priority topological sort).  sim_us is then the in-order replay of that queue on the launch's workgroups.
+  void order_by_level();
+
+  // Reorder the queue: simulate a list schedule with order_wg_ workers, priority = longest remaining path.
+  void order() {
+    const int nt = (int)plan_.tasks.size(), nc = (int)plan_.totals.size();
+    std::vector<std::vector<int>> waiters(nc);
+    for (int i = 0; i < nt; ++i)
+      for (int w = 0; w < plan_.tasks[i].nwait; ++w) waiters[plan_.tasks[i].wcnt[w]].push_back(i);
+    const std::vector<double> bl = bottom_levels();
     std::vector<int> count(nc, 0), missing(nt, 0);
     typedef std::pair<double, int> Pri;  // (bottom level, -index): highest first, earlier emission breaks ties
     std::priority_queue<Pri> ready;
@@ -702,7 +770,7 @@ class DagBuilder {
     std::vector<int> out_idx;      // original index of the task at each queue position
     std::vector<double> start(nt, 0.0);
     out_idx.reserve(nt);
-    int idle = nwg_;
+    int idle = order_wg_;
     double now = 0;
     while ((int)out.size() < nt) {
       while (idle > 0 && !ready.empty()) {
@@ -781,6 +849,73 @@ inline DagPlan dag_plan_kinv_only(const DagPlan& full) {
   out.sim_us = full.sim_us;    // bounds of the whole evaluation: only used to size the wait bound
   out.crit_us = full.crit_us;
   return out;
+}
+
+// The queue replayed the way the kernel executes it, under the planner's task times: `workers` workgroups each claim the next
+// index when free (strictly in queue order), the claimed task starts when its counters are complete and lasts its planner
+// cost.  A worker that has claimed a task whose counters are not complete holds its compute unit while it waits: wait_us is
+// that time summed over the workers, busy_us the tasks' own.  At workers == the count the queue was ordered for, the makespan
+// is the list schedule's (DagPlan::sim_us): the schedule only ever starts a task when it is ready and a worker is free, in
+// queue order.  Any topological order can be replayed (every bump a task waits for comes from an earlier index).
+struct DagReplay {
+  double makespan_us = 0, wait_us = 0, busy_us = 0;
+};
+inline DagReplay dag_plan_replay(const DagPlan& plan, int workers) {
+  DagReplay out;
+  const int nt = (int)plan.tasks.size(), nc = (int)plan.totals.size();
+  if (workers < 1 || nt == 0) return out;
+  std::vector<double> done(nc, 0.0);  // per counter: when the last of its bumps so far became visible
+  std::priority_queue<double, std::vector<double>, std::greater<double>> free_at;
+  for (int w = 0; w < std::min(workers, nt); ++w) free_at.push(0.0);
+  for (int i = 0; i < nt; ++i) {
+    const DagTask& t = plan.tasks[i];
+    const double claimed = free_at.top();
+    free_at.pop();
+    double start = claimed;
+    for (int w = 0; w < t.nwait; ++w) start = std::max(start, done[t.wcnt[w]]);
+    const double end = start + t.cost * 0.1;
+    for (int q = 0; q < DAG_MAXSIG; ++q)
+      if (t.sig[q] != DAG_NOSIG) done[t.sig[q]] = std::max(done[t.sig[q]], end);
+    out.wait_us += start - claimed;
+    out.busy_us += t.cost * 0.1;
+    out.makespan_us = std::max(out.makespan_us, end);
+    free_at.push(end);
+  }
+  return out;
+}
+
+inline void DagBuilder::order_by_level() {
+  const int nt = (int)plan_.tasks.size(), nc = (int)plan_.totals.size();
+  std::vector<std::vector<int>> waiters(nc);
+  for (int i = 0; i < nt; ++i)
+    for (int w = 0; w < plan_.tasks[i].nwait; ++w) waiters[plan_.tasks[i].wcnt[w]].push_back(i);
+  const std::vector<double> bl = bottom_levels();
+  std::vector<int> count(nc, 0), missing(nt, 0);
+  typedef std::pair<double, int> Pri;  // (bottom level, -index): highest first, earlier emission breaks ties
+  std::priority_queue<Pri> ready;
+  for (int i = 0; i < nt; ++i) {
+    missing[i] = plan_.tasks[i].nwait;
+    if (missing[i] == 0) ready.push({bl[i], -i});
+  }
+  std::vector<DagTask> out;
+  out.reserve(nt);
+  while (!ready.empty()) {
+    const int i = -ready.top().second;
+    ready.pop();
+    out.push_back(plan_.tasks[i]);
+    const DagTask& t = plan_.tasks[i];
+    for (int q = 0; q < DAG_MAXSIG; ++q) {
+      if (t.sig[q] == DAG_NOSIG) continue;
+      const int c = t.sig[q];
+      if (++count[c] == plan_.totals[c])
+        for (int wtr : waiters[c])
+          if (--missing[wtr] == 0) ready.push({bl[wtr], -wtr});
+    }
+  }
+  if ((int)out.size() == nt) {
+    plan_.tasks.swap(out);
+    plan_.sim_us = dag_plan_replay(plan_, nwg_).makespan_us;
+  }
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -722,7 +722,8 @@ constexpr int MAX_DEVS = 64;
 // What a task-queue plan is built from: Problem::init keeps the plans it builds by this key
 struct DagPlanKey {
   int blocks, bk, small_h, nwg, lauum, rl, rl_group, rl_near, lauum_split, chain32, prog, big128;
-  auto tie() const { return std::tie(blocks, bk, small_h, nwg, lauum, rl, rl_group, rl_near, lauum_split, chain32, prog, big128); }
+  int order_wg;  // workers the queue is ordered for where that is not nwg (0: nwg; DAG_ORDER_BY_LEVEL: no count)
+  auto tie() const { return std::tie(blocks, bk, small_h, nwg, lauum, rl, rl_group, rl_near, lauum_split, chain32, prog, big128, order_wg); }
   bool operator<(const DagPlanKey& o) const { return tie() < o.tie(); }
 };
 static std::atomic<int> g_dev_busy[MAX_DEVS];  // optimiser runs in flight per device id, over all fits of the process
@@ -755,6 +756,9 @@ struct Slot {
   EvalOut* dOut = nullptr;
   int* tickets = nullptr;    // [0] alpha / lml reduction, [1] gradient: "last workgroup finishes the launch's job" counters (zero between launches)
   unsigned long long* dag_trace = nullptr;  // HBEGP_DAG_TRACE: per-task time stamps of the last evaluation
+  // HBEGP_DAG_TRACE_EVALS: the traces of a fit's own launches, kept on the host until the problem is released (keep_fit_trace)
+  struct KeptTrace { unsigned long long seq; int part, variant, nwg; std::vector<unsigned long long> stamps; };
+  std::vector<KeptTrace> kept_traces;
   int* dag_ctrl = nullptr;   // queue head + dependency counters of the task-queue kernel (cleared before every launch)
   EvalParams* hP = nullptr;  // pinned
   EvalOut* hOut = nullptr;   // pinned
@@ -847,7 +851,7 @@ struct Problem : ProblemBase {
   // everything the lml needs first (EVAL_LML_ONLY), K^-1 and the gradient (EVAL_GRAD_ONLY) only when the optimiser or the capture
   // rule will read them (do_fit).  0: every trial is one fused evaluation.  Same kernels, same tiles, same bits either way.
   bool lazy_ = false;
-  std::function<std::shared_ptr<const DagPlan>(int, bool)> plan_for_;  // (workgroups, with the K^-1 tiles) -> the cached plan
+  std::function<std::shared_ptr<const DagPlan>(int, bool, int)> plan_for_;  // (workgroups, with the K^-1 tiles, ordered for) -> the cached plan
   // HBEGP_HOSTIO (default 1): an evaluation is driven through the slot's pinned blocks -- the first kernel reads the parameters
   // there and prepares the device-side blocks (EvalPrologue), the last one copies the results back and publishes the
   // evaluation's serial number, which the host thread spins on.  0: parameter copy + reset kernel + memset in front, a result
@@ -1026,7 +1030,7 @@ struct Problem : ProblemBase {
       dag_rl_ = env_int("HBEGP_DAG_RL", np / NB <= 80 ? 1 : 0) != 0;
       static std::mutex cache_mu;
       static std::map<DagPlanKey, std::shared_ptr<const DagPlan>> cache;
-      plan_for_ = [this](int nwg, bool lauum) {
+      plan_for_ = [this](int nwg, bool lauum, int order_wg) {
         const DagPlanKey key = {np / NB, dag_stage_depth(is_f32), env_int("HBEGP_DAG_SMALLH", dag_rl_ ? 4 : 8), nwg, lauum, dag_rl_,
                                 env_int("HBEGP_DAG_RL_GROUP", 32), env_int("HBEGP_DAG_RL_NEAR", 1),
                                 env_int("HBEGP_DAG_LAUUM_SPLIT", n_slots <= 1 ? 1 : 0),
@@ -1048,7 +1052,8 @@ struct Problem : ProblemBase {
                                 // 2: also the tiles with beta = 1 (the trailing updates; the old values are then fetched in the epilogue): M f64
                                 // 1.711 / 1.737 / 1.739 -> 1.753 / 1.754 / 1.756 (alternating), M f32 2.76 -> 2.80, C4 0.242 -> 0.249 fits/s.
                                 // One evaluation alone: n=6144 4.58 -> 4.73 ms (worse), n=8192 9.69 -> 9.31 ms: from 64 blocks on there too.
-                                env_int("HBEGP_DAG_BIG128", ((n_slots >= 2 && np / NB >= 32) || np / NB >= 64) ? 2 : 0)};  // one evaluation alone: 2.21 -> 2.17 ms at n=4096, 1.02 -> 0.97 at 2048; a fit: 1.67 -> 1.66
+                                env_int("HBEGP_DAG_BIG128", ((n_slots >= 2 && np / NB >= 32) || np / NB >= 64) ? 2 : 0),  // one evaluation alone: 2.21 -> 2.17 ms at n=4096, 1.02 -> 0.97 at 2048; a fit: 1.67 -> 1.66
+                                (order_wg == nwg || nwg <= 0) ? 0 : order_wg};
         std::shared_ptr<const DagPlan> cached;
         {
           std::lock_guard<std::mutex> lk(cache_mu);
@@ -1056,11 +1061,16 @@ struct Problem : ProblemBase {
           if (it != cache.end()) cached = it->second;
         }
         if (!cached) {
-          DagBuilder builder(key.bk, key.small_h, key.nwg);
+          DagBuilder builder(key.bk, key.small_h, key.nwg, true, key.order_wg);
           builder.set_rl(key.rl_group, key.rl_near, key.lauum_split != 0, key.chain32 != 0);
           builder.set_rl_progressive(key.prog != 0);
           builder.set_big128(key.big128 != 0, key.big128 >= 2);
           cached = std::make_shared<const DagPlan>(builder.build(0, np / NB, lauum, dag_rl_));
+          // a queue ordered for another count than it is launched with is checked before it runs anywhere, once per cached plan
+          if (key.order_wg != 0 && !cached->tasks.empty()) {
+            const std::string why = dag_plan_validate(*cached, np / NB);
+            if (!why.empty()) throw std::runtime_error("task queue ordered for another worker count is unsound: " + why);
+          }
           std::lock_guard<std::mutex> lk(cache_mu);
           if (cache.size() > 256) cache.clear();  // (a lazy fit keeps two plans per launch size)
           cache[key] = cached;
@@ -1069,7 +1079,19 @@ struct Problem : ProblemBase {
       };
       const int nvar = std::min(n_slots, DAG_MAX_VARIANTS);
       dag_nwg = share_of(n_slots);  // the default variant: every slot busy
-      auto plan_for = [this](int nwg) { return plan_for_(nwg, dag_lauum_); };
+      // What a queue is ordered for (dag_plan.hpp: DagBuilder's order_wg), per kind of queue -- 0 the fused one, 1 phase 1, 2 the K^-1
+      // tasks alone -- and per share of the launch (slot_share.hpp: even, which the busy-count and crowded-device variants are too,
+      // lead, lag).  HBEGP_DAG_ORDER_WG / _P1 / _KINV force it for the three queues of the even variants, _LEAD / _LAG for all three
+      // queues of the lead / the lag variant: N > 0 a list schedule for N workers, -1 the count-independent order; unset or 0: the
+      // default (dag_default_order_wg).  The answer 0 means the launch's own count -- the queues are then what they always were.
+      auto order_wg_for = [this](int queue, int share, int nwg) {
+        const char* name = share == SLOT_SHARE_LEAD ? "HBEGP_DAG_ORDER_WG_LEAD"
+                           : (share == SLOT_SHARE_LAG ? "HBEGP_DAG_ORDER_WG_LAG"
+                              : (queue == 1 ? "HBEGP_DAG_ORDER_WG_P1" : (queue == 2 ? "HBEGP_DAG_ORDER_WG_KINV" : "HBEGP_DAG_ORDER_WG")));
+        const int forced = env_int(name, 0);
+        return forced != 0 ? std::max(forced, DAG_ORDER_BY_LEVEL) : dag_default_order_wg(queue, share, nwg, dag_nwg, np / NB, n_slots);
+      };
+      auto plan_for = [this, order_wg_for](int nwg, int share = SLOT_SHARE_EVEN) { return plan_for_(nwg, dag_lauum_, order_wg_for(0, share, nwg)); };
       std::shared_ptr<const DagPlan> cached = plan_for(dag_nwg);
       if (cached->tasks.empty() && dag_rl_) {  // too many counters for 16-bit ids (n > ~12k): the recursion plan needs far fewer
         dag_rl_ = false;
@@ -1132,6 +1154,7 @@ struct Problem : ProblemBase {
           DagVariant& var = dag_var[v];
           std::shared_ptr<const DagPlan> pv = cached;
           var.nwg = dag_nwg;
+          const int share = v > nvar + dag_ncrowd_ ? (v == nvar + dag_ncrowd_ + 1 ? SLOT_SHARE_LEAD : SLOT_SHARE_LAG) : SLOT_SHARE_EVEN;
           if (v != nvar && adapt) {
             if (v > nvar + dag_ncrowd_) {
               var.nwg = std::min(share_wg[v - nvar - dag_ncrowd_ - 1], dag_ntasks);
@@ -1140,7 +1163,7 @@ struct Problem : ProblemBase {
               var.nwg = std::min(share_of(busy), dag_ntasks);
               if (v > nvar) var.nwg = std::min(var.nwg, dag_nwg);
             }
-            pv = plan_for(var.nwg);
+            pv = plan_for(var.nwg, share);
             if (pv->tasks.size() != plan.tasks.size()) { pv = cached; var.nwg = dag_nwg; }  // cannot happen: same task set
           }
           var.host_tasks = pv->tasks;
@@ -1155,8 +1178,11 @@ struct Problem : ProblemBase {
             // the K^-1 tiles (the planner's lauum = false form, as factor_only's arithmetic: the same tiles of the factorisation),
             // phase 2 the full queue's K^-1 tasks alone, in its order.  Workgroups per launch as the fused launch of the variant.
             const int wg_p1 = lazy_wg(var.nwg, 1), wg_kinv = lazy_wg(var.nwg, 2);
-            const std::shared_ptr<const DagPlan> p1 = plan_for_(wg_p1, false);
-            const DagPlan kv = dag_plan_kinv_only(*pv);
+            const std::shared_ptr<const DagPlan> p1 = plan_for_(wg_p1, false, order_wg_for(1, share, wg_p1));
+            // (the K^-1 tasks keep the order they have in a full queue: the variant's own, unless theirs is ordered for another count)
+            const int order_kinv = order_wg_for(2, share, wg_kinv);
+            const std::shared_ptr<const DagPlan> pk = order_kinv == 0 ? pv : plan_for_(var.nwg, true, order_kinv);
+            const DagPlan kv = dag_plan_kinv_only(*pk);
             if (p1->tasks.empty() || kv.tasks.empty() || p1->totals.size() > plan.totals.size() || kv.totals.size() > plan.totals.size()) {
               // the full plan exists and these are parts of it: anything else is a planner bug, not a reason to half-disable the path
               throw std::runtime_error("task queues of a two-phase evaluation could not be derived from the plan");
@@ -1230,7 +1256,50 @@ struct Problem : ProblemBase {
   }
   ~Problem() override { release(); }
 
+  // HBEGP_DAG_TRACE=<prefix> with HBEGP_DAG_TRACE_EVALS=a:b (fits only): the task trace of every task-queue launch a slot makes for
+  // its evaluations number a .. b-1, while the other slots run theirs beside it -- what tools/queue_workers.py reads to count the
+  // compute units a launch really holds.  Kept in memory (one copy per launch; the slot's stream is idle, the evaluation has been
+  // published) and written by release() to <prefix>.s<slot>.e<evaluation>.p<part>: a header line, then tools/dag_trace.py's
+  // columns with the task's flags behind them.
+  void keep_fit_trace(Slot<T>& s, int mode) {
+    static const char* range = getenv("HBEGP_DAG_TRACE_EVALS");
+    int a = 0, b = 0;
+    if (!range || !dag_ || !s.dag_trace || sscanf(range, "%d:%d", &a, &b) != 2 || s.seq < (unsigned long long)std::max(a, 0) || s.seq >= (unsigned long long)std::max(b, 0)) return;
+    const int part = !(lazy_ && dag_lauum_) ? 0 : (mode == EVAL_LML_ONLY ? 1 : (mode == EVAL_GRAD_ONLY ? 2 : 0));
+    const DagVariant& var = dag_var[s.dag_variant];
+    typename Slot<T>::KeptTrace k;
+    k.seq = s.seq; k.part = part; k.variant = s.dag_variant;
+    k.nwg = part == 1 ? var.nwg_p1 : (part == 2 ? var.nwg_kinv : var.nwg);
+    k.stamps.resize((size_t)5 * (part == 1 ? var.ntasks_p1 : (part == 2 ? var.ntasks_kinv : dag_ntasks)));
+    HIPCHECK(hipMemcpyAsync(k.stamps.data(), s.dag_trace, sizeof(unsigned long long) * k.stamps.size(), hipMemcpyDeviceToHost, s.stream));
+    HIPCHECK(hipStreamSynchronize(s.stream));
+    s.kept_traces.push_back(std::move(k));
+  }
+  void write_fit_traces() {
+    const char* prefix = getenv("HBEGP_DAG_TRACE");
+    for (size_t di = 0; prefix && di < slots.size(); ++di)
+      for (size_t si = 0; si < slots[di].size(); ++si)
+        for (const auto& k : slots[di][si].kept_traces) {
+          if (k.variant < 0 || k.variant >= (int)dag_var.size()) continue;
+          const DagVariant& var = dag_var[k.variant];
+          const std::vector<DagTask>& tasks = k.part == 1 ? var.host_tasks_p1 : (k.part == 2 ? var.host_tasks_kinv : var.host_tasks);
+          char name[512];
+          snprintf(name, sizeof name, "%s.s%zu.e%llu.p%d", prefix, si, k.seq, k.part);
+          FILE* f = fopen(name, "w");
+          if (!f) continue;
+          fprintf(f, "# slot %zu evaluation %llu part %d variant %d share %d nwg %d tasks %zu\n", si, k.seq, k.part, k.variant, share_of_variant(k.variant), k.nwg, tasks.size());
+          for (size_t i = 0; i < tasks.size() && 5 * i + 4 < k.stamps.size(); ++i) {
+            const DagTask& t = tasks[i];
+            const unsigned long long* tr = k.stamps.data() + 5 * i;
+            fprintf(f, "%zu %d %d %d %d %d %llu %llu %llu %llu %llu %llu %d\n", i, t.kind, t.row0, t.col0, t.kend - t.kbeg, t.nwait, tr[0], tr[1], tr[2], tr[3], tr[4] >> 32,
+                    tr[4] & 0xffffffffull, t.flags);
+          }
+          fclose(f);
+        }
+  }
+
   void release() {
+    write_fit_traces();
     for (size_t di = 0; di < slots.size(); ++di) {
       (void)hipSetDevice(ctx->devs[di]);
       for (auto& s : slots[di]) {
@@ -1695,6 +1764,7 @@ struct Problem : ProblemBase {
     }
     s.published = eval_published();  // what enqueue_eval records when it is not replayed from a graph (ONE rule for both: eval_published)
     wait_eval(s, t_launch, mode);
+    if (s.dag_trace) keep_fit_trace(s, mode);
     s.last_target = target;
     const int p = d + 2;
     if (s.hOut->info < 0) {
@@ -5644,6 +5714,49 @@ int hbegp_debug_dag_queues(int nblocks, int bk, int small_h, int nwg, int fine, 
   if (err && errlen > 0) snprintf(err, (size_t)errlen, "%s", why.c_str());
   return why.empty() ? HBEGP_OK : fail(HBEGP_EINVAL, "%s", why.c_str());
   GUARD_END
+}
+
+// A queue ordered for order_wg workers (0: nwg; -1: the count-independent order) and its in-order replay on `workers` workgroups
+// (dag_plan_replay), for the tests and tools/queue_order.py.  The other arguments as hbegp_debug_dag_queues.  tasks (may be NULL):
+// 18 ints per task -- kind, flags, row0, col0, kbeg, kend, nwait, wcnt[4], wval[4], sig[3] (65535: unused) -- for the first `cap`
+// tasks in queue order; out (may be NULL): makespan, waiting and busy time of the replay (us, CU x us, CU x us), the planner's
+// sim_us and crit_us, and the planner cost of the tasks carrying DAGF_ACC on a 128x128 tile (CU x us).  The queue is validated.
+int hbegp_debug_dag_replay(int nblocks, int bk, int small_h, int nwg, int order_wg, int fine, int big128, int which, int workers,
+                           int* ntasks, int* tasks, int cap, double* out, char* err, int errlen) {
+  if (nblocks < 1 || (bk != 16 && bk != 32) || small_h < 0 || nwg < 1 || which < 0 || which > 2 || !ntasks || workers < 0)
+    return fail(HBEGP_EINVAL, "bad argument");
+  GUARD_BEGIN
+  DagBuilder builder(bk, small_h, nwg, (fine & 1) != 0, order_wg);
+  builder.set_rl_progressive((fine & 16) != 0);
+  builder.set_big128(big128 != 0, big128 >= 2);
+  builder.set_rl(32, 1, (fine & 32) == 0, true);
+  DagPlan plan = builder.build(0, nblocks, which != 1, (fine & 8) != 0);
+  if (which == 2) plan = dag_plan_kinv_only(plan);
+  const std::string why = plan.tasks.empty() ? std::string("no tasks") : dag_plan_validate(plan, nblocks);
+  *ntasks = (int)plan.tasks.size();
+  if (tasks)
+    for (int i = 0; i < std::min(cap, (int)plan.tasks.size()); ++i) {
+      const DagTask& t = plan.tasks[i];
+      int* v = tasks + (size_t)18 * i;
+      v[0] = t.kind; v[1] = t.flags; v[2] = t.row0; v[3] = t.col0; v[4] = t.kbeg; v[5] = t.kend; v[6] = t.nwait;
+      for (int w = 0; w < DAG_MAXWAIT; ++w) { v[7 + w] = w < t.nwait ? t.wcnt[w] : 0; v[11 + w] = w < t.nwait ? t.wval[w] : 0; }
+      for (int q = 0; q < DAG_MAXSIG; ++q) v[15 + q] = t.sig[q];
+    }
+  if (out) {
+    const DagReplay r = workers > 0 ? dag_plan_replay(plan, workers) : DagReplay();
+    double acc128 = 0;
+    for (const DagTask& t : plan.tasks)
+      if (t.kind == DAG_GEMM_128x128 && (t.flags & DAGF_ACC)) acc128 += t.cost * 0.1;
+    out[0] = r.makespan_us; out[1] = r.wait_us; out[2] = r.busy_us; out[3] = plan.sim_us; out[4] = plan.crit_us; out[5] = acc128;
+  }
+  if (err && errlen > 0) snprintf(err, (size_t)errlen, "%s", why.c_str());
+  return why.empty() ? HBEGP_OK : fail(HBEGP_EINVAL, "%s", why.c_str());
+  GUARD_END
+}
+
+// What dag_default_order_wg answers (0: the launch's own count), for the tests: the defaults must be covered by the CPU checks.
+int hbegp_debug_dag_order_wg(int queue, int share, int nwg, int even_wg, int nblocks, int n_slots) {
+  return dag_default_order_wg(queue, share, nwg, even_wg, nblocks, n_slots);
 }
 
 int hbegp_debug_lbfgs_replay(int n, const double* x0, const double* lo, const double* hi, int maxeval, int memory, int fixed_work,

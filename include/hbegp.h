@@ -862,6 +862,19 @@ int hbegp_debug_lbfgs_decisions(int n, const double* x0, const double* lo, const
 int hbegp_debug_dag_queues(int nblocks, int bk, int small_h, int nwg, int fine, int big128, int which, int* ntasks, int* tasks, int cap,
                            char* err, int errlen);
 
+/* ---- test hook (host only, no GPU): a queue as hbegp_debug_dag_queues builds it, ordered for order_wg workers (0: nwg, the
+ * launch's own count; -1: for no count, strictly by bottom level among the tasks whose predecessors are in the queue), and its
+ * in-order replay on `workers` workgroups (0: none) under the planner's task times: each workgroup claims the next index when
+ * free, the task starts when its counters are complete.  tasks (may be NULL) receives 18 ints per task -- kind, flags, row0, col0,
+ * kbeg, kend, nwait, 4 counters waited for, their 4 values, 3 counters bumped (65535: unused).  out (may be NULL) receives 6
+ * doubles: the replay's makespan (us), its waiting and busy time (CU x us), the planner's sim_us and crit_us, and the planner cost
+ * of the 128x128 tasks with beta = 1.  hbegp_debug_dag_order_wg: the library's default order_wg (0: the launch's own count) for
+ * queue 0 / 1 / 2 (fused, phase 1, K^-1 alone) of an even (share 0), lead (1) or lag (2) launch of nwg workgroups, where the
+ * problem's even launch has even_wg. */
+int hbegp_debug_dag_replay(int nblocks, int bk, int small_h, int nwg, int order_wg, int fine, int big128, int which, int workers,
+                           int* ntasks, int* tasks, int cap, double* out, char* err, int errlen);
+int hbegp_debug_dag_order_wg(int queue, int share, int nwg, int even_wg, int nblocks, int n_slots);
+
 /* ---- test hooks (host only, no GPU): the share policy of a fit's slots (csrc/slot_share.hpp).  Per slot of one
  * problem on one device: running[i] != 0 while the slot is inside an optimiser run, done[i] the evaluations that run has completed,
  * maxeval[i] its cap.  share[i] receives 0 (even), 1 (lead) or 2 (lag).  hysteresis < 0: the library's default.  lead_wg / lag_wg
