@@ -53,10 +53,19 @@ static_assert(DAG_LDS_BYTES <= 163840, "the diagonal block and the control words
 // free (claiming it a whole task earlier parks the chain's tasks behind bulk tiles: measured 2.05 -> 3.06 ms per evaluation).
 // -DDAG_STAMP_INNER (diagnostic build, tools/trace_inner.py): two more time stamps per tile task -- first stage in the LDS (the
 // first MFMA can start) and last MFMA issued -- packed into the trace's CU-id word (low 32 bits of the 100 MHz clock each).
-template <typename T, int TA, int TB, typename PullFn, typename FetchFn>
+//
+// The 128x128 tile and structurally zero operand halves (engine.hpp: dag_zero_halves).  Its wave grid pairs
+// the two waves of a SIMD (waves w and w + 4) so that they differ in BOTH halves: wm = wave >> 1 as in the other tiles, but
+// wn = (wave ^ (wave >> 2)) & 1.  Whichever 64-wide half of A or of B is zero in a stage, exactly one wave of every SIMD owns it
+// and drops its fragment reads and MFMAs for that stage; the other wave has the SIMD's MFMA pipe to itself.  Which wave owns which
+// 32x64 block enters no element's accumulation chain, and a dropped MFMA would have added an exact zero: same bits.  The stages
+// at the two ends of the range where some half is zero are peeled out of the steady-state loop (whole pairs of stages); the
+// branch is wave-uniform, and every wave still loads, stores, meets the stage barrier, calls the hooks and flushes as before.
+// PAIRED = false (tools/tile_ubench.hip only): the plain grid wn = wave & 1.
+template <typename T, int TA, int TB, bool PAIRED = true, typename PullFn, typename FetchFn>
 __device__ __forceinline__ void dag_gemm_tile(int flags, int row0, int col0, int kbeg, int kend, T* __restrict__ W1,
                                               T* __restrict__ W2, T* __restrict__ W3, T* __restrict__ Kinv, int ld, char* smem_raw,
-                                              PullFn pull, FetchFn fetch, unsigned long long* inner = nullptr) {
+                                              PullFn pull, FetchFn fetch, unsigned long long* inner = nullptr, bool zero_skip = false) {
   using C = Cfg<T>;
   using G = DagGeom<T, TA, TB>;
   using vec_t = typename C::vec_t;
@@ -72,7 +81,21 @@ __device__ __forceinline__ void dag_gemm_tile(int flags, int row0, int col0, int
 
   T* lds = reinterpret_cast<T*>(smem_raw);  // [A buf0 | A buf1 | B buf0 | B buf1]
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
+  constexpr bool BIG = TA == 128 && TB == 128;
+  const int wm = wave >> 1, wn = (BIG && PAIRED) ? ((wave ^ (wave >> 2)) & 1) : (wave & 1);
+  // stages at the two ends of the range that this wave skips (its half of A or of B is zero there), and the most any wave skips
+  int lead_w = 0, trail_w = 0, lead_wg = 0, trail_wg = 0;
+  if constexpr (BIG) {
+    if (zero_skip) {
+      const DagZeroHalf z = dag_zero_halves(flags, row0, col0, kbeg, kend, BK);
+      const int wu = __builtin_amdgcn_readfirstlane(wave);
+      const int ha = wu >> 2, hb = PAIRED ? ((wu ^ (wu >> 2)) & 1) : (wu & 1);
+      lead_w = max(ha ? z.lead[0][1] : z.lead[0][0], hb ? z.lead[1][1] : z.lead[1][0]);
+      trail_w = max(ha ? z.trail[0][1] : z.trail[0][0], hb ? z.trail[1][1] : z.trail[1][0]);
+      lead_wg = max(max(z.lead[0][0], z.lead[0][1]), max(z.lead[1][0], z.lead[1][1]));
+      trail_wg = max(max(z.trail[0][0], z.trail[0][1]), max(z.trail[1][0], z.trail[1][1]));
+    }
+  }
 
   constexpr int CPK = BK / VEC;                   // chunks per slab row, operand stored [outer][k]
   constexpr int RPP_K = NT / CPK;                 // slab rows per pass
@@ -198,35 +221,39 @@ __device__ __forceinline__ void dag_gemm_tile(int flags, int row0, int col0, int
 #pragma unroll
       for (int b2 = 0; b2 < TMB; ++b2) acc[a][b2] = C::mfma(fa[k4][a], fb[k4][b2], acc[a][b2]);
   };
+  // skip (wave-uniform; the constant false outside the 128x128 tile's peeled stages): this wave's half of A or of B is zero in
+  // this stage -- no fragment reads of the stage, no MFMAs; everything else as ever, the next stage's first fragments included
   auto stage = [&](int cur, bool do_load, vec_t (&la)[NCHA], vec_t (&lb)[NCHB], bool do_store, vec_t (&sa)[NCHA],
-                   vec_t (&sb)[NCHB], bool has_next) {
+                   vec_t (&sb)[NCHB], bool has_next, bool skip) __attribute__((always_inline)) {
     if (do_load) load_stage(la, lb);
     // f32 128x128 (NK = 8: 48 fragment registers beside 64 fp64 chunk totals): the fragments of a stage are read in two
     // halves, the second under the first half's MFMAs -- with all of them up front the kernel spilled (round 4: 4 VGPRs)
     constexpr bool SPLIT_READS = NK >= 8 && TA * TB >= 128 * 128;
     constexpr int KH = SPLIT_READS ? NK / 2 : NK - 1;  // last k-step read up front
+    if (!skip) {
 #pragma unroll
-    for (int k4 = 1; k4 <= KH; ++k4) read_frags(cur, k4);
-    if constexpr (SPLIT_READS) {
+      for (int k4 = 1; k4 <= KH; ++k4) read_frags(cur, k4);
+      if constexpr (SPLIT_READS) {
 #pragma unroll
-      for (int k4 = 0; k4 + 1 < KH; ++k4) mfma_step(k4);
-      __builtin_amdgcn_sched_barrier(0);
+        for (int k4 = 0; k4 + 1 < KH; ++k4) mfma_step(k4);
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-      for (int k4 = KH + 1; k4 < NK; ++k4) read_frags(cur, k4);
+        for (int k4 = KH + 1; k4 < NK; ++k4) read_frags(cur, k4);
 #pragma unroll
-      for (int k4 = KH - 1; k4 + 2 < NK; ++k4) mfma_step(k4);
-    } else {
+        for (int k4 = KH - 1; k4 + 2 < NK; ++k4) mfma_step(k4);
+      } else {
 #pragma unroll
-      for (int k4 = 0; k4 + 2 < NK; ++k4) mfma_step(k4);
+        for (int k4 = 0; k4 + 2 < NK; ++k4) mfma_step(k4);
+      }
     }
     __builtin_amdgcn_sched_barrier(0);
     if (do_store) store_stage(cur ^ 1, sa, sb);
-    if (NK >= 2) mfma_step(NK - 2);
+    if (NK >= 2 && !skip) mfma_step(NK - 2);
     __builtin_amdgcn_sched_barrier(0);
     __syncthreads();
     __builtin_amdgcn_sched_barrier(0);
     if (has_next) read_frags(cur ^ 1, 0);
-    mfma_step(NK - 1);
+    if (!skip) mfma_step(NK - 1);
     __builtin_amdgcn_sched_group_barrier(0x100, TMA + TMB, 0);  // reads first: their latency hides under the MFMAs
     __builtin_amdgcn_sched_group_barrier(0x008, TMA * TMB, 0);
     __builtin_amdgcn_sched_barrier(0);
@@ -280,20 +307,34 @@ __device__ __forceinline__ void dag_gemm_tile(int flags, int row0, int col0, int
     if (inner && t == 0) st1 = __builtin_amdgcn_s_memrealtime();
 #endif
     int s = 0;
-    for (; s + 3 < nstages; s += 2) {
-      stage(0, true, ra0, rb0, true, ra1, rb1, true);
-      stage(1, true, ra1, rb1, true, ra0, rb0, true);
+    // stage index -> this wave skips it (never true outside the 128x128 tile, or without zero_skip)
+    auto skips = [&](int si) { return BIG && (si < lead_w || si >= nstages - trail_w); };
+    if constexpr (BIG) {  // leading stages in which some wave skips, in whole pairs
+      for (; s < lead_wg && s + 3 < nstages; s += 2) {
+        stage(0, true, ra0, rb0, true, ra1, rb1, true, skips(s));
+        stage(1, true, ra1, rb1, true, ra0, rb0, true, skips(s + 1));
+      }
+    }
+    for (; s + 3 < nstages - trail_wg; s += 2) {  // steady state: nobody skips
+      stage(0, true, ra0, rb0, true, ra1, rb1, true, false);
+      stage(1, true, ra1, rb1, true, ra0, rb0, true, false);
+    }
+    if constexpr (BIG) {  // trailing stages in which some wave skips, up to the last three
+      for (; s + 3 < nstages; s += 2) {
+        stage(0, true, ra0, rb0, true, ra1, rb1, true, skips(s));
+        stage(1, true, ra1, rb1, true, ra0, rb0, true, skips(s + 1));
+      }
     }
     const int left = nstages - s;  // 1..3
     if (left <= 2) pull();
     if (left == 1) fetch();
-    stage(0, left > 2, ra0, rb0, left > 1, ra1, rb1, left > 1);
+    stage(0, left > 2, ra0, rb0, left > 1, ra1, rb1, left > 1, skips(s));
     if (left > 2) pull();
     if (left == 2) fetch();
-    if (left > 1) stage(1, false, ra1, rb1, left > 2, ra0, rb0, left > 2);
+    if (left > 1) stage(1, false, ra1, rb1, left > 2, ra0, rb0, left > 2, skips(s + 1));
     if (left > 2) {
       fetch();
-      stage(0, false, ra0, rb0, false, ra1, rb1, false);
+      stage(0, false, ra0, rb0, false, ra1, rb1, false, skips(s + 2));
     }
 #ifdef DAG_STAMP_INNER
     if (inner && t == 0) *inner = ((st1 & 0xffffffffull) << 32) | (__builtin_amdgcn_s_memrealtime() & 0xffffffffull);
@@ -569,7 +610,7 @@ __global__ void __launch_bounds__(512, 2) dag_kernel(DagLaunch g) {
       } else if (kind == DAG_GEMM_64x64) {
         dag_gemm_tile<T, 64, 64>(flags, row0, col0, kbeg, kend, W1, W2, static_cast<T*>(g.W3), static_cast<T*>(g.Kinv), g.ld, smem_raw, pull, fetch, inner_stamp);
       } else if (kind == DAG_GEMM_128x128) {
-        dag_gemm_tile<T, 128, 128>(flags, row0, col0, kbeg, kend, W1, W2, static_cast<T*>(g.W3), static_cast<T*>(g.Kinv), g.ld, smem_raw, pull, fetch, inner_stamp);
+        dag_gemm_tile<T, 128, 128>(flags, row0, col0, kbeg, kend, W1, W2, static_cast<T*>(g.W3), static_cast<T*>(g.Kinv), g.ld, smem_raw, pull, fetch, inner_stamp, g.zero_skip != 0);
       } else if (kind == DAG_GEMM_32x64) {
         dag_gemm_tile_chain<T>(flags, row0, col0, kbeg, kend, W1, W2, static_cast<T*>(g.W3), g.ld, smem_raw, pull, fetch);
       }

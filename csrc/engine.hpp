@@ -131,6 +131,46 @@ struct DagTask {
 };
 static_assert(DAG_MAXSIG == 3, "DagTask::sig has three entries: dword 5 high half, dword 6 low half, dword 6 high half");
 static_assert(sizeof(DagTask) == 48, "DagTask layout");  // dag_kernel decodes it dword by dword: keep the field order
+
+// ---- structurally zero halves of a 128x128 task's operands (ONE rule for the host's accounting and the tile itself) ----------
+// An operand that lives in W2 is read out of X = L^-1, whose strict upper triangle is zero in memory.  A 128x128 task's contraction
+// range is the union of its two 64-wide halves' ranges, so at one end of the range one half of an operand can lie wholly above the
+// diagonal: its products are exact zeros and the waves that own that half may skip them.  Per side (0: A, 1: B) and 64-wide half
+// (rows / columns from origin + 64 h) the number of such stages of `bk` contraction elements:
+//   operand read [outer][k] (no DAGF_AKM / DAGF_BKM): rows R .. R+63 are zero where k0 >= R + 64        -> TRAILING stages
+//   operand read [k][outer] (DAGF_AKM / DAGF_BKM): columns R .. R+63 are zero where k0 + bk <= R          -> LEADING stages
+// Operands in W1, W3 or the K^-1 buffer are never triangular to this rule.  No descriptor field carries any of it.
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define HBEGP_HD __host__ __device__
+#else
+#define HBEGP_HD
+#endif
+struct DagZeroHalf {
+  int lead[2][2], trail[2][2];  // [side][half]: whole stages
+};
+HBEGP_HD inline DagZeroHalf dag_zero_halves(int flags, int row0, int col0, int kbeg, int kend, int bk) {
+  DagZeroHalf z = {{{0, 0}, {0, 0}}, {{0, 0}, {0, 0}}};
+  const int nst = (kend - kbeg) / bk;
+  if (nst <= 0) return z;
+  for (int side = 0; side < 2; ++side) {
+    const bool in_w2 = side == 0 ? ((flags & DAGF_ABUF) != 0 && (flags & DAGF_A3) == 0) : ((flags & DAGF_BBUF) != 0 && (flags & DAGF_B3) == 0);
+    if (!in_w2) continue;
+    const bool km = (flags & (side == 0 ? DAGF_AKM : DAGF_BKM)) != 0;
+    for (int h = 0; h < 2; ++h) {
+      const int r = (side == 0 ? row0 : col0) + 64 * h;
+      if (km) {
+        const int c = r > kbeg ? (r - kbeg) / bk : 0;  // stages that end at or above row r
+        z.lead[side][h] = c < nst ? c : nst;
+      } else {
+        const int d = r + 64 - kbeg;
+        const int first = d > 0 ? (d + bk - 1) / bk : 0;  // first stage that starts at or behind column r + 64
+        z.trail[side][h] = first < nst ? nst - first : 0;
+      }
+    }
+  }
+  return z;
+}
+
 constexpr int DAG_CTRL_WORDS = 4;     // ctrl[0] queue head, [1] first task that gave up waiting (+1), [2..3] spare; counters follow
 constexpr int DAG_INFO_TIMEOUT = -2;  // written to EvalOut::info when a wait exceeded its bound (a bug, never a data property)
 struct DagLaunch {
@@ -147,6 +187,7 @@ struct DagLaunch {
   unsigned long long* trace;  // optional (diagnostics): per task [pulled, inputs ready, computed, published] on the 100 MHz clock, then the CU id
   unsigned long long wait_ticks;  // bound of one dependency wait in ticks of the 100 MHz clock (host: from the plan's simulated makespan)
   int leaf_dbg;                   // debug bits of the diagonal-block tasks (tests: 16 = the helper wave starts late, HBEGP_LEAF_DBG)
+  int zero_skip;                  // 128x128 tiles: waves skip the MFMAs of structurally zero operand halves (dag_zero_halves; HBEGP_DAG_ZERO_SKIP)
 };
 template <typename T>
 void launch_dag(const DagLaunch& g, int nwg, hipStream_t s);

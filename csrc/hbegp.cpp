@@ -864,6 +864,10 @@ struct Problem : ProblemBase {
   // every evaluation would then sit out wait_eval's two-second fallback, or silently fall back to hipStreamSynchronize)
   bool eval_published() const { return hostio_ && !small_; }
   int leaf_dbg_ = 0;                        // HBEGP_LEAF_DBG: debug bits of the diagonal-block kernel (16: helper waves start late)
+  // HBEGP_DAG_ZERO_SKIP (default 1): the 128x128 task-queue tiles skip the MFMAs of structurally zero operand halves (engine.hpp:
+  // dag_zero_halves).  Only that tile reads it, so it is on from the size where those tiles are used; 0: every wave multiplies the
+  // zeros as before.  Same bits either way.
+  bool zero_skip_ = true;
 
   // Small device arrays of the problem (features, targets, task queues, schedule tables, control words) come from the block
   // pool too and go back to it in release(): hipMalloc / hipFree synchronise the whole device, which serialises host threads
@@ -901,6 +905,7 @@ struct Problem : ProblemBase {
     nu2 = std::isinf(nu) ? 0 : (int)std::lround(2 * nu);  // 0 = squared exponential (nu = infinity)
     is_f32 = sizeof(T) == 4;
     leaf_dbg_ = env_int("HBEGP_LEAF_DBG", 0) & 16;  // tests only; the bits that skip work stay with tools/leaf_bench
+    zero_skip_ = env_int("HBEGP_DAG_ZERO_SKIP", 1) != 0;
     // The reference's own regime (minimize.rs:118-120: n stays at 100-200): up to 128 rows the five launches of the general path
     // cost more in launch gaps and HBM round trips than in arithmetic; one workgroup does the whole evaluation in its LDS
     // instead (HBEGP_SMALL=0: the general path, which the tests compare it with).
@@ -1433,6 +1438,7 @@ struct Problem : ProblemBase {
     g.trace = s.dag_trace;
     g.wait_ticks = dag_wait_ticks_;
     g.leaf_dbg = leaf_dbg_;
+    g.zero_skip = zero_skip_ ? 1 : 0;
     if (tm) tm->begin(PhaseTimer::DAG, 0, part == 2 ? dag_gflop_lauum : (g.Kinv ? dag_gflop : dag_gflop - dag_gflop_lauum));
     launch_dag<T>(g, nwg, s.stream);
     if (tm) tm->end();
@@ -5752,6 +5758,16 @@ int hbegp_debug_dag_replay(int nblocks, int bk, int small_h, int nwg, int order_
   if (err && errlen > 0) snprintf(err, (size_t)errlen, "%s", why.c_str());
   return why.empty() ? HBEGP_OK : fail(HBEGP_EINVAL, "%s", why.c_str());
   GUARD_END
+}
+
+// dag_zero_halves (engine.hpp) for the tests: out receives 8 ints -- leading stages of A half 0, A half 1, B half 0, B half 1, then
+// the trailing stages in the same order.
+int hbegp_debug_dag_zero_halves(int flags, int row0, int col0, int kbeg, int kend, int bk, int* out) {
+  if (bk < 1 || !out) return fail(HBEGP_EINVAL, "bad argument");
+  const DagZeroHalf z = dag_zero_halves(flags, row0, col0, kbeg, kend, bk);
+  for (int side = 0; side < 2; ++side)
+    for (int h = 0; h < 2; ++h) { out[2 * side + h] = z.lead[side][h]; out[4 + 2 * side + h] = z.trail[side][h]; }
+  return HBEGP_OK;
 }
 
 // What dag_default_order_wg answers (0: the launch's own count), for the tests: the defaults must be covered by the CPU checks.

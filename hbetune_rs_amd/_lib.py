@@ -203,6 +203,7 @@ SIGNATURES = {
     "hbegp_debug_dag_replay": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip, _ip,
                                          C.c_int, _dp, C.c_char_p, C.c_int]),
     "hbegp_debug_dag_order_wg": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "hbegp_debug_dag_zero_halves": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip]),
     "hbegp_debug_slot_shares": (C.c_int, [C.c_int, _ip, _ip, _ip, C.c_int, _ip, C.c_int, C.c_int, _ip, _ip]),
     "hbegp_debug_fits_in_flight": (C.c_int, [C.c_int]),
     "hbegp_debug_dag_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip, _ip, _ip, _dp, _dp, _dp, C.c_char_p,

@@ -875,6 +875,13 @@ int hbegp_debug_dag_replay(int nblocks, int bk, int small_h, int nwg, int order_
                            int* ntasks, int* tasks, int cap, double* out, char* err, int errlen);
 int hbegp_debug_dag_order_wg(int queue, int share, int nwg, int even_wg, int nblocks, int n_slots);
 
+/* ---- test hook (host only, no GPU): the rule by which a 128x128 task-queue tile skips structurally zero operand halves
+ * (HBEGP_DAG_ZERO_SKIP; csrc/engine.hpp: dag_zero_halves), for a task's flags, row0, col0, kbeg, kend and the stage depth bk.
+ * out receives 8 ints: the leading stages in which A's rows row0.., A's rows row0 + 64.., B's columns col0.., B's columns
+ * col0 + 64.. lie wholly above the diagonal of the inverse factor, then the trailing stages in the same order.  An operand that
+ * does not live in the inverse factor's matrix gets zeros. */
+int hbegp_debug_dag_zero_halves(int flags, int row0, int col0, int kbeg, int kend, int bk, int* out);
+
 /* ---- test hooks (host only, no GPU): the share policy of a fit's slots (csrc/slot_share.hpp).  Per slot of one
  * problem on one device: running[i] != 0 while the slot is inside an optimiser run, done[i] the evaluations that run has completed,
  * maxeval[i] its cap.  share[i] receives 0 (even), 1 (lead) or 2 (lag).  hysteresis < 0: the library's default.  lead_wg / lag_wg
