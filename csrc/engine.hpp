@@ -406,7 +406,7 @@ void launch_qei_batch(const T* Xs, int B, int q, int d, const T* Q, const T* W, 
 //                v = rv [n] or null: the model's known row variances), zero padding; part: paths_project_chunks(F, n, S) * S * n doubles
 //   eval:        f [S][m], df [S][m][d] (want_grad) at Xs [m][d] (per_path = 0) or [S][m][d] (per_path = 1);
 //                part: paths_eval_chunks(n, F) * S * m * (d + 1) doubles
-int paths_project_chunks(int F, int n, int S, int* fch_out = nullptr);
+int paths_project_chunks(int F, int n, int S, int* fch_out = nullptr, int* cap_out = nullptr);  // cap_out: the most chunks the partial sums allow
 int paths_eval_chunks(int n, int F, int* nchd_out = nullptr);
 template <typename T>
 void launch_paths_scale_omega(const T* om0, int F, int d, const EvalParams* P, double* omT, hipStream_t s);

@@ -3571,6 +3571,11 @@ static int paths_create(hbegp_model* m, const T* omega0, const T* phase, const T
 // the points go through the kernels in blocks: at most PATHS_EVAL_ROWS (path, point) pairs and PATHS_EVAL_PART bytes of partial sums
 constexpr size_t PATHS_EVAL_ROWS = 262144;
 constexpr size_t PATHS_EVAL_PART = (size_t)256 << 20;
+// bytes of partial sums per point of a call, and the points per block of a call of cnt points (host only: hbegp_debug_paths_eval_blocks)
+static size_t paths_eval_per_point(int n, int d, int F, int S) { return sizeof(double) * (size_t)paths_eval_chunks(n, F) * S * (d + 1); }
+static int paths_eval_block(int n, int d, int F, int S, int cnt) {
+  return (int)std::max<size_t>(1, std::min<size_t>({(size_t)cnt, PATHS_EVAL_ROWS / (size_t)S, PATHS_EVAL_PART / paths_eval_per_point(n, d, F, S)}));
+}
 
 // the caller holds the model's mutex
 template <typename T>
@@ -3578,8 +3583,8 @@ static void paths_eval_locked(hbegp_paths* p, const T* Xs, int cnt, int per_path
   hbegp_model* m = p->model;
   hipStream_t s = m->stream;
   const int d = m->d, S = p->S;
-  const size_t per_point = sizeof(double) * (size_t)paths_eval_chunks(m->n, p->F) * S * (d + 1);
-  const int mb = (int)std::max<size_t>(1, std::min<size_t>({(size_t)cnt, PATHS_EVAL_ROWS / (size_t)S, PATHS_EVAL_PART / per_point}));
+  const size_t per_point = paths_eval_per_point(m->n, d, p->F, S);
+  const int mb = paths_eval_block(m->n, d, p->F, S, cnt);
   p->grow(&p->Xs, &p->cap_x, sizeof(T) * (size_t)(per_path ? S : 1) * mb * d);
   p->grow(&p->part, &p->cap_part, per_point * mb);
   p->grow(&p->f, &p->cap_f, sizeof(T) * (size_t)S * mb);
@@ -4978,6 +4983,31 @@ int hbegp_paths_info(const hbegp_paths* paths, int* n, int* d, int* n_features, 
 }
 void hbegp_paths_release(hbegp_paths* paths) { delete paths; }
 int hbegp_debug_paths_phases(int enable, double* phase_ms) { return debug_phases(PH_PATHS, 3, enable, phase_ms); }
+// The two size-dependent splits of the sample paths, as the engine itself computes them (host only, no device): the points per
+// block of an evaluation of m points (paths_eval_locked calls the same function) and the feature chunks of the projection.
+static int check_paths_sizes(int n, int F, int S) {
+  if (n < 1) return fail(HBEGP_EINVAL, "n must be >= 1 (got %d)", n);
+  if (F < 1 || F > HBEGP_PATHS_MAX_FEATURES) return fail(HBEGP_EINVAL, "F must be in [1, %d] (got %d)", HBEGP_PATHS_MAX_FEATURES, F);
+  if (S < 1 || S > HBEGP_PATHS_MAX_PATHS) return fail(HBEGP_EINVAL, "S must be in [1, %d] (got %d)", HBEGP_PATHS_MAX_PATHS, S);
+  return HBEGP_OK;
+}
+int hbegp_debug_paths_eval_blocks(int n, int d, int F, int S, int m, int* mb) {
+  if (int rc = check_paths_sizes(n, F, S)) return rc;
+  if (d < 1) return fail(HBEGP_EINVAL, "d must be >= 1 (got %d)", d);
+  if (m < 0) return fail(HBEGP_EINVAL, "m must be >= 0 (got %d)", m);
+  if (!mb) return fail(HBEGP_EINVAL, "mb is NULL");
+  *mb = paths_eval_block(n, d, F, S, m);
+  return HBEGP_OK;
+}
+int hbegp_debug_paths_project_chunks(int F, int n, int S, int* cap, int* nch, int* fch) {
+  if (int rc = check_paths_sizes(n, F, S)) return rc;
+  int c = 0, f = 0;
+  const int k = paths_project_chunks(F, n, S, &f, &c);
+  if (cap) *cap = c;
+  if (nch) *nch = k;
+  if (fch) *fch = f;
+  return HBEGP_OK;
+}
 // the check that needs no model comes first, so that each one has its own message whatever else is wrong
 static int check_model_loo(hbegp_model* model, bool want_f32, bool any_output) {
   if (!any_output) return fail(HBEGP_EINVAL, "every output is NULL");

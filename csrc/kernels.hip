@@ -4435,13 +4435,14 @@ __global__ void __launch_bounds__(256) paths_eval_finish_kernel(const double* __
 // Feature chunks of the projection.  A workgroup walks its chunk serially (one fp64 cosine per lane and feature), so the chunk
 // length is the launch's latency: chunks of 64 features while the partial sums (chunks x S x n doubles) stay within 128 MiB and
 // there are at most 64 of them, longer ones beyond.  The split depends only on (F, n, S): one handle, one summation order.
-int paths_project_chunks(int F, int n, int S, int* fch_out) {
+int paths_project_chunks(int F, int n, int S, int* fch_out, int* cap_out) {
   const size_t per_chunk = sizeof(double) * (size_t)S * (size_t)n;
   const int cap = (int)std::max<size_t>(1, std::min<size_t>(64, ((size_t)128 << 20) / per_chunk));
   int nch = std::max(1, std::min(cap, (F + 63) / 64));
   int fch = ((F + nch - 1) / nch + PP_FT - 1) / PP_FT * PP_FT;
   nch = (F + fch - 1) / fch;
   if (fch_out) *fch_out = fch;
+  if (cap_out) *cap_out = cap;
   return nch;
 }
 int paths_eval_chunks(int n, int F, int* nchd_out) {

@@ -177,6 +177,8 @@ SIGNATURES = {
     "hbegp_paths_info": (C.c_int, [_vp, _ip, _ip, _ip, _ip, _ip]),
     "hbegp_paths_release": (None, [_vp]),
     "hbegp_debug_paths_phases": (C.c_int, [C.c_int, _dp]),
+    "hbegp_debug_paths_eval_blocks": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip]),
+    "hbegp_debug_paths_project_chunks": (C.c_int, [C.c_int, C.c_int, C.c_int, _ip, _ip, _ip]),
     "hbegp_debug_posterior_phases": (C.c_int, [C.c_int, _dp]),
     "hbegp_debug_batch_select_phases": (C.c_int, [C.c_int, _dp]),
     "hbegp_debug_kg_phases": (C.c_int, [C.c_int, _dp]),

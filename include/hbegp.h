@@ -1010,6 +1010,16 @@ void hbegp_paths_release(hbegp_paths* paths);
  * thread's last timed hbegp_paths_create_* call -- uploads and the frequency scaling, the feature projection, the two triangular
  * products -- in milliseconds; then enable != 0 makes this thread's later create calls timed. */
 int hbegp_debug_paths_phases(int enable, double* phase_ms);
+/* ---- test hooks (host only, no GPU): the size-dependent splits of the sample paths, from the functions the engine itself calls.
+ * hbegp_debug_paths_eval_blocks: *mb = the points per block of hbegp_paths_eval_* with m points on a handle of S paths and F
+ * features over a model of n rows and d features -- min(m, 262144 / S, 256 MiB / (8 (ceil(n/512) + ceil(F/512)) S (d + 1))), at
+ * least 1; a call with m > mb runs ceil(m / mb) blocks, and a lockstep round of the minimiser is such a call with per-path points.
+ * hbegp_debug_paths_project_chunks: the projection of hbegp_paths_create_* walks F features in *nch chunks of *fch (a multiple of
+ * 32; the last chunk may be shorter), *cap = min(64, 128 MiB / (8 S n)), at least 1, being the most chunks its partial sums allow.
+ * Any output pointer of the second may be NULL.  HBEGP_EINVAL for sizes the entry points refuse (n, d < 1, m < 0, F or S outside
+ * their limits). */
+int hbegp_debug_paths_eval_blocks(int n, int d, int n_features, int n_paths, int m, int* mb);
+int hbegp_debug_paths_project_chunks(int n_features, int n, int n_paths, int* cap, int* nch, int* fch);
 
 #ifdef __cplusplus
 }

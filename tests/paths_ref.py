@@ -94,6 +94,21 @@ class Paths:
         df += self.amp * np.einsum("in,ns,ink->sik", psi, v, diff)
         return f, df
 
+    def evaluate_by_matmul(self, x):
+        """`evaluate` at shared points x [m, d] with every contraction a matrix product, one per gradient component: the same
+        sums, but O(S F m d) where the einsum above walks S F m d^2 at best (S = 1000, F = 16384: minutes against a second)."""
+        x = f8_(x)
+        th = x @ self.om.T + self.b[None, :]
+        cs, sn = np.cos(th), np.sin(th)
+        f = self.A * (self.w @ cs.T) + (self.kstar(x) @ self.v).T
+        r = scaled_dist(x, self.X, self.ell)
+        psi = np.where(r > 0, matern_psi(r, self.nu), 0.0)
+        df = np.empty(f.shape + (x.shape[1],))
+        for k in range(x.shape[1]):
+            slope = psi * ((x[:, None, k] - self.X[None, :, k]) / self.ell[k] ** 2)  # [m, n]
+            df[:, :, k] = -self.A * (self.w @ (sn * self.om[None, :, k]).T) + self.amp * (slope @ self.v).T
+        return f, df
+
     def mean(self, x):
         return self.kstar(x) @ np.linalg.solve(self.K, self.y)
 
@@ -111,3 +126,11 @@ class Paths:
 
 def f8_(a):
     return np.asarray(a, dtype=np.float64)
+
+
+def gather(f, df, idx):
+    """Per-path values from values at a shared pool of points: path s at its points pool[idx[s, i]] -> (f [S, m], df [S, m, d])
+    from f [S, P], df [S, P, d] at the pool.  A path's value at a point depends on nothing else, so this is `evaluate` at
+    pool[idx] without S times the pool's cosines."""
+    rows = np.arange(f.shape[0])[:, None]
+    return f[rows, idx], df[rows, idx]
