@@ -239,6 +239,33 @@ template <typename T>
 void launch_loo_trace(const T* X, int n, int d, int np, int nu2, const EvalParams* P, const T* Cm, const T* alpha, const T* u,
                       double* part, EvalOut* out, hipStream_t s);
 
+// Leave-group-out cross-validation (hbegp_model_lgo / hbegp_problem_eval_lgo; kernels.hip: lgo_*_kernel).  The
+// partition of the n rows into G groups of at most LGO_MAX_GROUP rows, as device arrays of ints (hbegp.cpp: LgoGroups):
+//   member [n]      the rows, group by group in ascending dense id, ascending inside a group
+//   gid    [n]      the dense id of the group that list position belongs to
+//   goff   [G + 1]  where a group's members start in `member`
+//   foff   [G + 1]  where its factor F_g (s x s, row-major, lower) starts in the packed array F: the sum of the earlier s^2
+//   boff   [nb + 1] bundles of consecutive groups with at most 64 rows together: the first group of each
+//   group: part: lgo_gram_chunks(n, smax) * f_elems doubles (f_elems = foff[G]: the chunks' shares of the Gram matrices M_II);
+//          mean / var [n] and lpd [G] (T), avec [np] (fp64: r_g on the group's rows; the caller zeroes the padding), F, share [G],
+//          out->lml = lgo, out->done |= 1; a pivot that is not > 0 sets out->info and makes the group's lpd NaN
+//   uy:    Y (np x np; the caller zeroes the padding columns) and u [np] (T) from the LOWER triangle of Kinv; pu: nb * np doubles;
+//          skipped when *info != 0
+constexpr int LGO_MAX_GROUP = 64;
+struct LgoLists {
+  const int *member, *gid, *goff, *foff, *boff;
+  int G, nb, smax;  // groups, bundles, the largest group
+};
+size_t lgo_group_lds_bytes(int smax);
+int lgo_gram_chunks(int n, int smax);
+size_t lgo_uy_lds_bytes(bool is_f32);
+template <typename T>
+void launch_lgo_group(const T* Xinv, int np, int n, const T* y, const T* alpha, const LgoLists& L, size_t f_elems, double* part, T* mean,
+                      T* var, T* lpd, double* avec, double* F, double* share, EvalOut* out, hipStream_t s);
+template <typename T>
+void launch_lgo_uy(const T* Kinv, int np, int n, const LgoLists& L, const double* avec, const double* F, T* Y, double* pu, T* u,
+                   const int* info, hipStream_t s);
+
 template <typename T>
 void launch_symmetrize(T* A, int np, hipStream_t s);  // mirror lower -> upper
 

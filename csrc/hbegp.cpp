@@ -29,6 +29,7 @@
 #include <string>
 #include <thread>
 #include <type_traits>
+#include <unordered_map>
 #include <vector>
 
 #include "dag_plan.hpp"
@@ -742,6 +743,31 @@ struct LooIn {
 template <typename T>
 static int loo_tail(const LooIn<T>& in, T* mean, T* var, T* lpd, double* loo, double* grad);
 
+// A partition of the training rows for leave-group-out cross-validation (lgo_tail): the caller's labels mapped to
+// dense ids 0 .. G - 1 in order of first appearance, and the int lists the kernels read (engine.hpp: LgoLists), back to back in
+// `lists` in the order member, gid, goff, foff, boff.
+struct LgoGroups {
+  int n = 0, G = 0, nb = 0, smax = 0;
+  size_t f_elems = 0;  // doubles of the packed factors: the sum of s^2
+  std::vector<int> lists;
+  size_t bytes() const { return sizeof(int) * lists.size(); }
+  LgoLists on_device(const int* base) const {
+    LgoLists L;
+    L.member = base;
+    L.gid = L.member + n;
+    L.goff = L.gid + n;
+    L.foff = L.goff + (G + 1);
+    L.boff = L.foff + (G + 1);
+    L.G = G; L.nb = nb; L.smax = smax;
+    return L;
+  }
+};
+// group == nullptr: every row is its own group.  HBEGP_EINVAL for a group of more than HBEGP_LGO_MAX_GROUP rows.
+static int build_lgo_groups(const int* group, int n, LgoGroups* out);
+// dlists (may be null: uploaded for the call): gr.lists on the device the tail runs on
+template <typename T>
+static int lgo_tail(const LooIn<T>& in, const LgoGroups& gr, const int* dlists, T* mean, T* var, T* lpd, double* lgo, double* grad);
+
 template <typename T>
 struct Slot {
   int dev = 0;
@@ -789,6 +815,8 @@ struct ProblemBase {
   virtual ~ProblemBase() {}
   virtual int eval(int dev, int slot, const double* theta, const double* lo, const double* hi, double* lml, double* grad) = 0;
   virtual int eval_loo(int dev, int slot, const double* theta, const double* lo, const double* hi, double* loo, double* grad) = 0;
+  virtual int eval_lgo(int dev, int slot, const double* theta, const double* lo, const double* hi, const LgoGroups& gr, double* lgo,
+                       double* grad) = 0;
   virtual int time_eval(int dev, int slot, const double* theta, int reps, double* phase_ms) = 0;
   virtual int time_concurrent(int dev, const double* theta, int reps, double* out) = 0;
 };
@@ -1841,6 +1869,28 @@ struct Problem : ProblemBase {
     return loo_on_slot((size_t)dev, slot, loo, grad);
   }
 
+  // The leave-group-out tail on the same results; dlists as in lgo_tail.
+  int lgo_on_slot(size_t di, int si, const LgoGroups& gr, const int* dlists, double* lgo, double* grad) {
+    Slot<T>& s = slots[di][si];
+    const LooIn<T> in{s.dev, s.stream, n, d, np, nu2, Xd[di], yd[di], s.alpha[s.last_target], s.W2, s.Kinv[s.last_target], s.hP};
+    return lgo_tail<T>(in, gr, dlists, nullptr, nullptr, nullptr, lgo, grad);
+  }
+
+  int eval_lgo(int dev, int slot, const double* theta, const double* lo, const double* hi, const LgoGroups& gr, double* lgo,
+               double* grad) override {
+    if (gr.n != n) return fail(HBEGP_EINVAL, "the groups cover %d rows, the problem has %d", gr.n, n);
+    double lml;
+    const int st = eval(dev, slot, theta, lo, hi, &lml, nullptr);
+    if (st != HBEGP_OK) {
+      if (st == HBEGP_NOT_PD) {
+        *lgo = -std::numeric_limits<double>::infinity();
+        if (grad) for (int j = 0; j < d + 2; ++j) grad[j] = 0.0;
+      }
+      return st;
+    }
+    return lgo_on_slot((size_t)dev, slot, gr, nullptr, lgo, grad);
+  }
+
   int time_eval(int dev, int slot, const double* theta, int reps, double* phase_ms) override {
     if (dev < 0 || dev >= (int)slots.size() || slot < 0 || slot >= n_slots) return fail(HBEGP_EINVAL, "bad device/slot index");
     Slot<T>& s = slots[dev][slot];
@@ -2317,7 +2367,7 @@ struct CallScratch {
 // ---- phase times of the posterior-side calls (hbegp_debug_*_phases) ----------------------------------------------------------
 // One record per kind and calling thread: whether the thread's calls of that kind are timed, and the phase times (ms) of its last
 // timed call of that kind that reached its end.
-enum PhaseKind { PH_POSTERIOR, PH_SELECT, PH_KG, PH_NEI, PH_SENS, PH_EHVI, PH_QEI, PH_LOO, PH_PATHS, PH_CEI, PH_LCEI, PH_MES, PH_EHVI_ND, PH_CB, PH_KINDS };
+enum PhaseKind { PH_POSTERIOR, PH_SELECT, PH_KG, PH_NEI, PH_SENS, PH_EHVI, PH_QEI, PH_LOO, PH_PATHS, PH_CEI, PH_LCEI, PH_MES, PH_EHVI_ND, PH_CB, PH_LGO, PH_KINDS };
 struct PhaseRecord {
   bool on = false;
   double ms[5] = {0, 0, 0, 0, 0};
@@ -2390,6 +2440,7 @@ class PhaseClock {
 //   mes        the predict (the uploads .. the last predict or gradient launch), the MES kernel with the arg-max
 //   ehvi_nd    as ehvi with n_obj predicts: each objective's predict on its model's stream, then the box kernel with the arg-max
 //   cb         as mes: the predict, the confidence-bound kernel with the arg-min
+//   lgo        group pass, u and Y, the SYRK, the weighted trace -- calls with a gradient only
 
 // Sigma = K** + noise I - Q Q^T at the candidates into W (lower tiles; m_p x m_p, kmat's identity padding): the candidates'
 // upload, the batched predict's launches (Kstar, the mean, Q = Kstar X^T; the variance too, unused), then kmat_kernel over
@@ -3462,6 +3513,161 @@ static int model_loo(hbegp_model* m, T* mean, T* var, T* lpd, double* loo, doubl
   return loo_tail<T>(in, mean, var, lpd, loo, grad);
 }
 
+// ---- leave-group-out cross-validation (hbegp_model_lgo / hbegp_problem_eval_lgo / hbegp_fit_lgo) ---------
+
+static int build_lgo_groups(const int* group, int n, LgoGroups* out) {
+  LgoGroups& gr = *out;
+  gr = LgoGroups{};
+  gr.n = n;
+  std::vector<int> id(n), size, label;
+  if (group) {
+    std::unordered_map<int, int> dense;
+    dense.reserve((size_t)n);
+    for (int i = 0; i < n; ++i) {
+      auto it = dense.find(group[i]);
+      if (it == dense.end()) {
+        it = dense.emplace(group[i], (int)size.size()).first;
+        size.push_back(0);
+        label.push_back(group[i]);
+      }
+      id[i] = it->second;
+      size[it->second]++;
+    }
+  } else {
+    size.assign(n, 1);
+    for (int i = 0; i < n; ++i) id[i] = i;
+  }
+  const int G = (int)size.size();
+  for (int g = 0; g < G; ++g)
+    if (size[g] > HBEGP_LGO_MAX_GROUP)
+      return fail(HBEGP_EINVAL, "group %d holds %d rows: leave-group-out takes at most %d rows per group", label[g], size[g], HBEGP_LGO_MAX_GROUP);
+  gr.G = G;
+  std::vector<int> boff{0};
+  for (int g = 0, held = 0; g < G; ++g) {  // bundles: consecutive groups, at most 64 rows together
+    if (held + size[g] > 64) { boff.push_back(g); held = 0; }
+    held += size[g];
+    gr.smax = std::max(gr.smax, size[g]);
+  }
+  boff.push_back(G);
+  gr.nb = (int)boff.size() - 1;
+  gr.lists.assign((size_t)2 * n + 2 * (G + 1) + boff.size(), 0);
+  int* member = gr.lists.data();
+  int* gid = member + n;
+  int* goff = gid + n;
+  int* foff = goff + (G + 1);
+  std::copy(boff.begin(), boff.end(), foff + (G + 1));
+  for (int g = 0; g < G; ++g) {
+    goff[g + 1] = goff[g] + size[g];
+    foff[g + 1] = foff[g] + size[g] * size[g];
+  }
+  gr.f_elems = (size_t)foff[G];
+  std::vector<int> fill(goff, goff + G);
+  for (int i = 0; i < n; ++i) {  // rows ascending inside a group
+    const int pos = fill[id[i]]++;
+    member[pos] = i;
+    gid[pos] = id[i];
+  }
+  return HBEGP_OK;
+}
+
+// The diagnostics of every group from L^-1 and alpha (one workgroup per group: the Gram matrix M_II, its factor, r_g, Sigma_g, lpd_g,
+// F_g), and with `grad` the gradient of their sum: u = K^-1 a and Y[:, I] = K^-1[:, I] F_g in one pass over K^-1, then loo_tail's
+// SYRK and weighted trace as they are.  Y and C are borrowed only with `grad`; everything borrowed goes back cleared.  lpd has G
+// entries.  A pivot that is not positive in a group, or a result that is not finite, is HBEGP_NOT_PD: lgo = -inf, grad = 0.
+template <typename T>
+static int lgo_tail(const LooIn<T>& in, const LgoGroups& gr, const int* dlists, T* mean, T* var, T* lpd, double* lgo, double* grad) {
+  HIPCHECK(hipSetDevice(in.dev));
+  const int n = in.n, np = in.np, p = in.d + 2, G = gr.G;
+  const size_t nn = (size_t)np * np;
+  if (grad && 2.0 * (double)sizeof(T) * (double)np * np > 1e15)
+    return fail(HBEGP_ENOMEM, "the leave-group-out gradient of %d rows needs %.3g bytes of device memory", n, 2.0 * sizeof(T) * (double)np * np);
+  hipStream_t s = in.s;
+  CallScratch ws{in.dev, s, {}};
+  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+  const size_t b_vec = up(sizeof(T) * np), b_dvec = up(sizeof(double) * np), b_out = up(sizeof(EvalOut));
+  const size_t b_lists = dlists ? 0 : up(gr.bytes()), b_F = up(sizeof(double) * gr.f_elems);
+  const size_t b_gram = up(sizeof(double) * gr.f_elems * (size_t)lgo_gram_chunks(n, gr.smax));
+  const size_t b_pu = grad ? up(sizeof(double) * (size_t)gr.nb * np) : 0;
+  const size_t b_pg = grad ? up(sizeof(double) * gradtrace_part_elems(np, in.d)) : 0;
+  char* q = static_cast<char*>(ws.get(b_out + 4 * b_vec + 2 * b_dvec + b_lists + b_F + b_gram + b_pu + b_pg));
+  EvalOut* dout = reinterpret_cast<EvalOut*>(q); q += b_out;
+  T* dmean = reinterpret_cast<T*>(q); q += b_vec;
+  T* dvar = reinterpret_cast<T*>(q); q += b_vec;
+  T* dlpd = reinterpret_cast<T*>(q); q += b_vec;  // G <= n entries
+  T* du = reinterpret_cast<T*>(q); q += b_vec;
+  double* avec = reinterpret_cast<double*>(q); q += b_dvec;
+  double* share = reinterpret_cast<double*>(q); q += b_dvec;
+  int* lists = reinterpret_cast<int*>(q); q += b_lists;
+  double* F = reinterpret_cast<double*>(q); q += b_F;
+  double* gram = reinterpret_cast<double*>(q); q += b_gram;
+  double* pu = reinterpret_cast<double*>(q); q += b_pu;
+  double* part_g = reinterpret_cast<double*>(q);
+  HIPCHECK(hipMemsetAsync(dout, 0, sizeof(EvalOut), s));  // info = 0, done = 0 (a recycled block holds its earlier owner's numbers)
+  HIPCHECK(hipMemsetAsync(avec, 0, sizeof(double) * np, s));  // the padding rows of a
+  if (!dlists) {
+    HIPCHECK(hipMemcpyAsync(lists, gr.lists.data(), gr.bytes(), hipMemcpyHostToDevice, s));
+    dlists = lists;
+  }
+  const LgoLists L = gr.on_device(dlists);
+  PhaseClock clk(t_phase[PH_LGO].on && grad, 5);
+  clk.mark(s);
+  launch_lgo_group<T>(in.Xinv, np, n, in.y, in.alpha, L, gr.f_elems, gram, dmean, dvar, dlpd, avec, F, share, dout, s);
+  clk.mark(s);
+  if (grad) {
+    T* Y = static_cast<T*>(ws.get(sizeof(T) * nn));
+    T* Cm = static_cast<T*>(ws.get(sizeof(T) * nn));
+    if (np > n) HIPCHECK(hipMemsetAsync(Y, 0, sizeof(T) * nn, s));  // the padding columns (the kernel writes every row of the others)
+    launch_lgo_uy<T>(in.Kinv, np, n, L, avec, F, Y, pu, du, &dout->info, s);
+    clk.mark(s);
+    {
+      // C = Y Y^T (lower tiles), contraction over all columns of Y
+      GemmLaunch g{};
+      g.nops = 1;
+      GemmOp& op = g.op[0];
+      op.A = Y; op.B = Y; op.C = Cm;
+      op.lda = op.ldb = op.ldc = np;
+      op.mi = np / NB; op.nj = np / NB; op.c_lower = 1;
+      op.k0 = 0; op.k1 = np / NB;
+      gemm_adhoc<T>(g, &dout->info, s);
+    }
+    clk.mark(s);
+    launch_loo_trace<T>(in.X, n, in.d, np, in.nu2, in.P, Cm, in.alpha, du, part_g, dout, s);
+    clk.mark(s);
+  }
+  CHECK_LAUNCHES();
+  EvalOut out;
+  HIPCHECK(hipMemcpyAsync(&out, dout, sizeof(EvalOut), hipMemcpyDeviceToHost, s));
+  if (mean) HIPCHECK(hipMemcpyAsync(mean, dmean, sizeof(T) * n, hipMemcpyDeviceToHost, s));
+  if (var) HIPCHECK(hipMemcpyAsync(var, dvar, sizeof(T) * n, hipMemcpyDeviceToHost, s));
+  if (lpd) HIPCHECK(hipMemcpyAsync(lpd, dlpd, sizeof(T) * G, hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
+  clk.store(PH_LGO, 4);
+  if (!(out.done & 1) || (grad && out.info == 0 && !(out.done & 2)))
+    throw HipError{hipErrorLaunchFailure, "leave-group-out: the kernels did not run", __LINE__};
+  bool finite = out.info == 0 && std::isfinite(out.lml);
+  if (grad && finite) for (int j = 0; j < p; ++j) finite = finite && std::isfinite(out.grad[j]);
+  if (!finite) {
+    if (lgo) *lgo = -std::numeric_limits<double>::infinity();
+    if (grad) for (int j = 0; j < p; ++j) grad[j] = 0.0;
+    if (out.info != 0) return fail(HBEGP_NOT_PD, "leave-group-out: the group of row %d is not positive definite", out.info - 1);
+    return fail(HBEGP_NOT_PD, "the leave-group-out predictive density is not finite");
+  }
+  if (lgo) *lgo = out.lml;
+  if (grad) for (int j = 0; j < p; ++j) grad[j] = out.grad[j];
+  return HBEGP_OK;
+}
+
+template <typename T>
+static int model_lgo(hbegp_model* m, const int* group, T* mean, T* var, T* lpd, int* n_groups, double* lgo, double* grad) {
+  LgoGroups gr;
+  if (int rc = build_lgo_groups(group, m->n, &gr)) return rc;
+  if (n_groups) *n_groups = gr.G;
+  std::lock_guard<std::mutex> lock(m->mu);
+  const LooIn<T> in{m->dev, m->stream, m->n, m->d, m->np, m->nu2, static_cast<const T*>(m->X), static_cast<const T*>(m->y),
+                    static_cast<const T*>(m->alpha), static_cast<const T*>(m->Xinv), static_cast<const T*>(m->Kinv), m->dP};
+  return lgo_tail<T>(in, gr, nullptr, mean, var, lpd, lgo, grad);
+}
+
 // ---- posterior sample paths (hbegp_paths_*) ------------------------------------------------------------
 // The handle keeps, on the model's device: om^T [d][F] = omega0^T / ell, the phases [F] and the weights [S][F] in fp64, and
 // V^T [S_p][n_p] (one path per row: the tile GEMMs' operand layout).  Its calls run on the model's stream under the model's
@@ -3753,11 +3959,39 @@ static int do_extend(hbegp_ctx* ctx, const T* X, const T* y, const double* rv, i
 
 // loo: the objective is the leave-one-out log pseudo-likelihood (hbegp_fit_loo_*) -- every evaluation is the slot's normal one
 // without the lml gradient plus the leave-one-out tail on its results, always under the host-driven optimiser, and the model
-// is `extend` at the captured theta.  Nothing else differs; loo = false is the fit as it always was.
+// is `extend` at the captured theta.  Nothing else differs; FIT_LML is the fit as it always was.  FIT_LGO (hbegp_fit_lgo_*) is the
+// same with the leave-group-out tail over `groups`, whose lists are uploaded once per device for the whole fit.
+enum FitObjective { FIT_LML = 0, FIT_LOO = 1, FIT_LGO = 2 };
+// gr.lists on every device of a fit, in pool blocks that go back cleared
+struct LgoDeviceLists {
+  size_t bytes = 0;
+  std::vector<std::pair<int, void*>> held;  // (device id, block), one per device of the context in its order
+  void upload(const std::vector<int>& devs, const LgoGroups& gr) {
+    bytes = std::max<size_t>(16, gr.bytes());
+    for (int dev : devs) {
+      HIPCHECK(hipSetDevice(dev));
+      bool fresh = false;
+      void* p = g_pool.get(dev, bytes, &fresh);
+      held.push_back({dev, p});
+      HIPCHECK(hipMemcpy(p, gr.lists.data(), gr.bytes(), hipMemcpyHostToDevice));
+    }
+  }
+  const int* on(size_t di) const { return static_cast<const int*>(held[di].second); }
+  ~LgoDeviceLists() {
+    for (auto& h : held) {
+      (void)hipSetDevice(h.first);
+      (void)hipMemset(h.second, 0, bytes);
+      (void)hipDeviceSynchronize();
+      g_pool.put(h.first, h.second, bytes);
+    }
+  }
+};
 template <typename T>
 static int do_fit(hbegp_ctx* ctx, const T* X, const T* y, const double* rv, int n, int d, double nu, const double* theta0,
                   const double* lo, const double* hi, const double* starts, int n_restarts, const hbegp_fit_options* opt_in,
-                  double* theta_best, double* lml_best, hbegp_model** model_out, bool loo = false) {
+                  double* theta_best, double* lml_best, hbegp_model** model_out, int objective = FIT_LML,
+                  const LgoGroups* groups = nullptr) {
+  const bool loo = objective != FIT_LML;  // a cross-validation objective: the slot's evaluation plus a tail
   hbegp_fit_options opt{};
   g_last_fit_stats = LastFitStats{};  // a fit that fails leaves zeros, not the previous fit's numbers
   if (int e = read_fit_options(opt_in, &opt)) return e;
@@ -3808,6 +4042,8 @@ static int do_fit(hbegp_ctx* ctx, const T* X, const T* y, const double* rv, int 
   if (host_serial) host_lk.lock();
   const auto th0 = std::chrono::steady_clock::now();  // (HBEGP_TIMING: how long the turns are)
   double held_ms = 0;
+  LgoDeviceLists lgo_lists;  // (declared before the problem: its slots are released first)
+  if (objective == FIT_LGO) lgo_lists.upload(ctx->devs, *groups);
   Problem<T> prob(ctx, X, y, n, d, nu, n_slots, false, true, !loo, rv);
   const auto tf1 = std::chrono::steady_clock::now();
   if (!(small_fit && prob.small_)) arrival.arrived();
@@ -4067,7 +4303,9 @@ static int do_fit(hbegp_ctx* ctx, const T* X, const T* y, const double* rv, int 
           if (share == SLOT_SHARE_LEAD) rs.lead++;
           if (share == SLOT_SHARE_LAG) rs.lag++;
           if (loo) {
-            if (st == HBEGP_OK) st = prob.loo_on_slot((size_t)di, si, &lml, grad);
+            if (st == HBEGP_OK)
+              st = objective == FIT_LGO ? prob.lgo_on_slot((size_t)di, si, *groups, lgo_lists.on((size_t)di), &lml, grad)
+                                        : prob.loo_on_slot((size_t)di, si, &lml, grad);
             else for (int j = 0; j < p; ++j) grad[j] = 0.0;
             if (st != HBEGP_OK && st != HBEGP_NOT_PD) throw std::runtime_error(g_last_error);
           }
@@ -4396,6 +4634,17 @@ int hbegp_problem_eval_loo(hbegp_problem* prob, int dev, int slot, const double*
   GUARD_END
 }
 
+int hbegp_problem_eval_lgo(hbegp_problem* prob, int dev, int slot, const double* theta, const double* lo, const double* hi,
+                           const int* group, double* lgo, double* grad) {
+  if (!prob) return fail(HBEGP_EINVAL, "NULL problem");
+  if (!theta || !lgo) return fail(HBEGP_EINVAL, "theta / lgo is NULL");
+  GUARD_BEGIN
+  LgoGroups gr;
+  if (int e = build_lgo_groups(group, prob->impl->n, &gr)) return e;
+  return prob->impl->eval_lgo(dev, slot, theta, lo, hi, gr, lgo, grad);
+  GUARD_END
+}
+
 int hbegp_problem_time_concurrent(hbegp_problem* prob, int dev, const double* theta, int reps, double* out) {
   if (!prob || !theta || !out || reps < 1) return fail(HBEGP_EINVAL, "bad argument");
   GUARD_BEGIN
@@ -4538,7 +4787,7 @@ int hbegp_fit_loo_f64(hbegp_ctx* ctx, const double* X, const double* y, int n, i
   if (int e = check_args(ctx, X, y, n, d, nu)) return e;
   if (!theta0 || !lo || !hi || (n_restarts > 0 && !starts)) return fail(HBEGP_EINVAL, "NULL theta0/lo/hi/starts");
   GUARD_BEGIN
-  return do_fit<double>(ctx, X, y, nullptr, n, d, nu, theta0, lo, hi, starts, n_restarts, opt, theta_best, loo_best, model, true);
+  return do_fit<double>(ctx, X, y, nullptr, n, d, nu, theta0, lo, hi, starts, n_restarts, opt, theta_best, loo_best, model, FIT_LOO);
   GUARD_END
 }
 int hbegp_fit_loo_f32(hbegp_ctx* ctx, const float* X, const float* y, int n, int d, double nu, const double* theta0,
@@ -4551,7 +4800,7 @@ int hbegp_fit_loo_f32(hbegp_ctx* ctx, const float* X, const float* y, int n, int
   if (int e = check_args(ctx, X, y, n, d, nu)) return e;
   if (!theta0 || !lo || !hi || (n_restarts > 0 && !starts)) return fail(HBEGP_EINVAL, "NULL theta0/lo/hi/starts");
   GUARD_BEGIN
-  return do_fit<float>(ctx, X, y, nullptr, n, d, nu, theta0, lo, hi, starts, n_restarts, opt, theta_best, loo_best, model, true);
+  return do_fit<float>(ctx, X, y, nullptr, n, d, nu, theta0, lo, hi, starts, n_restarts, opt, theta_best, loo_best, model, FIT_LOO);
   GUARD_END
 }
 
@@ -4637,7 +4886,7 @@ static int problem_create_rv(hbegp_ctx* ctx, const T* X, const T* y, const doubl
 template <typename T>
 static int fit_rv(hbegp_ctx* ctx, const T* X, const T* y, const double* rv, int n, int d, double nu, const double* theta0, const double* lo,
                   const double* hi, const double* starts, int n_restarts, const hbegp_fit_options* opt, double* theta_best, double* best,
-                  hbegp_model** model, bool loo) {
+                  hbegp_model** model, int objective, const int* group = nullptr) {
   {
     hbegp_fit_options probe;
     if (int e = read_fit_options(opt, &probe)) return e;  // the order of the plain entry points: options, arguments, then rv
@@ -4646,7 +4895,10 @@ static int fit_rv(hbegp_ctx* ctx, const T* X, const T* y, const double* rv, int 
   if (!theta0 || !lo || !hi || (n_restarts > 0 && !starts)) return fail(HBEGP_EINVAL, "theta0/lo/hi/starts is NULL");
   if (int e = check_rv<T>(rv, n)) return e;
   GUARD_BEGIN
-  return do_fit<T>(ctx, X, y, rv, n, d, nu, theta0, lo, hi, starts, n_restarts, opt, theta_best, best, model, loo);
+  LgoGroups gr;
+  if (objective == FIT_LGO)
+    if (int e = build_lgo_groups(group, n, &gr)) return e;
+  return do_fit<T>(ctx, X, y, rv, n, d, nu, theta0, lo, hi, starts, n_restarts, opt, theta_best, best, model, objective, &gr);
   GUARD_END
 }
 template <typename T>
@@ -4691,15 +4943,25 @@ int hbegp_fit_rv_f32(hbegp_ctx* ctx, const float* X, const float* y, const doubl
                      double* theta_best, double* lml_best, hbegp_model** model) {
   return fit_rv<float>(ctx, X, y, rv, n, d, nu, theta0, lo, hi, starts, n_restarts, opt, theta_best, lml_best, model, false);
 }
+int hbegp_fit_lgo_f64(hbegp_ctx* ctx, const double* X, const double* y, const double* rv, const int* group, int n, int d, double nu,
+                      const double* theta0, const double* lo, const double* hi, const double* starts, int n_restarts,
+                      const hbegp_fit_options* opt, double* theta_best, double* lgo_best, hbegp_model** model) {
+  return fit_rv<double>(ctx, X, y, rv, n, d, nu, theta0, lo, hi, starts, n_restarts, opt, theta_best, lgo_best, model, FIT_LGO, group);
+}
+int hbegp_fit_lgo_f32(hbegp_ctx* ctx, const float* X, const float* y, const double* rv, const int* group, int n, int d, double nu,
+                      const double* theta0, const double* lo, const double* hi, const double* starts, int n_restarts,
+                      const hbegp_fit_options* opt, double* theta_best, double* lgo_best, hbegp_model** model) {
+  return fit_rv<float>(ctx, X, y, rv, n, d, nu, theta0, lo, hi, starts, n_restarts, opt, theta_best, lgo_best, model, FIT_LGO, group);
+}
 int hbegp_fit_loo_rv_f64(hbegp_ctx* ctx, const double* X, const double* y, const double* rv, int n, int d, double nu, const double* theta0,
                          const double* lo, const double* hi, const double* starts, int n_restarts, const hbegp_fit_options* opt,
                          double* theta_best, double* loo_best, hbegp_model** model) {
-  return fit_rv<double>(ctx, X, y, rv, n, d, nu, theta0, lo, hi, starts, n_restarts, opt, theta_best, loo_best, model, true);
+  return fit_rv<double>(ctx, X, y, rv, n, d, nu, theta0, lo, hi, starts, n_restarts, opt, theta_best, loo_best, model, FIT_LOO);
 }
 int hbegp_fit_loo_rv_f32(hbegp_ctx* ctx, const float* X, const float* y, const double* rv, int n, int d, double nu, const double* theta0,
                          const double* lo, const double* hi, const double* starts, int n_restarts, const hbegp_fit_options* opt,
                          double* theta_best, double* loo_best, hbegp_model** model) {
-  return fit_rv<float>(ctx, X, y, rv, n, d, nu, theta0, lo, hi, starts, n_restarts, opt, theta_best, loo_best, model, true);
+  return fit_rv<float>(ctx, X, y, rv, n, d, nu, theta0, lo, hi, starts, n_restarts, opt, theta_best, loo_best, model, FIT_LOO);
 }
 int hbegp_extend_rv_f64(hbegp_ctx* ctx, const double* X, const double* y, const double* rv, int n, int d, double nu, const double* theta,
                         const double* lo, const double* hi, hbegp_model** model) {
@@ -5028,6 +5290,21 @@ int hbegp_model_loo_f32(hbegp_model* model, float* mean, float* var, float* lpd,
   GUARD_END
 }
 int hbegp_debug_loo_phases(int enable, double* phase_ms) { return debug_phases(PH_LOO, 4, enable, phase_ms); }
+int hbegp_model_lgo_f64(hbegp_model* model, const int* group, double* mean, double* var, double* lpd, int* n_groups, double* lgo,
+                        double* grad) {
+  if (int rc = check_model_loo(model, false, mean || var || lpd || n_groups || lgo || grad)) return rc;
+  GUARD_BEGIN
+  return model_lgo<double>(model, group, mean, var, lpd, n_groups, lgo, grad);
+  GUARD_END
+}
+int hbegp_model_lgo_f32(hbegp_model* model, const int* group, float* mean, float* var, float* lpd, int* n_groups, double* lgo,
+                        double* grad) {
+  if (int rc = check_model_loo(model, true, mean || var || lpd || n_groups || lgo || grad)) return rc;
+  GUARD_BEGIN
+  return model_lgo<float>(model, group, mean, var, lpd, n_groups, lgo, grad);
+  GUARD_END
+}
+int hbegp_debug_lgo_phases(int enable, double* phase_ms) { return debug_phases(PH_LGO, 4, enable, phase_ms); }
 int hbegp_debug_qei_phases(int enable, double* phase_ms) { return debug_phases(PH_QEI, 2, enable, phase_ms); }
 }  // extern "C"
 

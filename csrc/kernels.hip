@@ -1945,6 +1945,318 @@ LOO_INST(float)
 #undef LOO_INST
 
 // =================================================================================================================
+// Leave-group-out cross-validation in closed form.  For a group with the row set I, |I| = s <= LGO_MAX_GROUP:
+//   Sigma_g = (M_II)^-1,  r_g = Sigma_g alpha_I,  mu_g = y_I - r_g,  lpd_g = -1/2 alpha_I^T r_g + 1/2 ln|M_II| - s/2 ln 2 pi
+//   dlgo/dtheta_j = 1/2 sum_ab (u_a alpha_b + alpha_a u_b - 2 C_ab) dK_ab/dtheta_j,
+//   a_I = r_g,  u = M a,  B_g = 1/2 (r_g r_g^T + Sigma_g) = F_g F_g^T,  Y[:, I] = M[:, I] F_g,  C = Y Y^T
+// (the column of Y that belongs to the k-th member of a group is the column of that member's row index).  With s = 1 these are the
+// leave-one-out formulas above.  Every sum is fp64 in a fixed order for both element types; no atomics on results.
+// =================================================================================================================
+// In-place Cholesky factor (lower) of the s x s matrix A (leading dimension ld) in the LDS, right-looking, one column per step, by
+// the whole workgroup.  Returns false -- in every thread -- where a pivot is not > 0 (NaN included); the factor is then garbage.
+__device__ __forceinline__ bool lgo_chol(double* A, int s, int ld) {
+  const int t = threadIdx.x;
+  bool ok = true;
+  for (int k = 0; k < s; ++k) {
+    __syncthreads();
+    const double piv = A[k * ld + k];
+    ok = ok && (piv > 0.0);
+    const double dk = sqrt(piv);
+    __syncthreads();  // everyone has read the pivot
+    for (int i = k + t; i < s; i += 256) A[i * ld + k] = (i == k) ? dk : A[i * ld + k] / dk;
+    __syncthreads();
+    const int m = s - k - 1;
+    for (int e = t; e < m * m; e += 256) {
+      const int i = k + 1 + e / m, j = k + 1 + e % m;
+      if (j <= i) A[i * ld + j] = __builtin_fma(-A[i * ld + k], A[j * ld + k], A[i * ld + j]);
+    }
+  }
+  __syncthreads();
+  return ok;
+}
+
+constexpr int LGO_STAGE = 2048;  // doubles of the Gram pass's row stage
+size_t lgo_gram_lds_bytes(int smax) { return sizeof(double) * ((size_t)smax * (smax | 1) + LGO_STAGE); }
+size_t lgo_group_lds_bytes(int smax) { return sizeof(double) * ((size_t)2 * smax * (smax | 1)); }
+// Rows per chunk of a group's Gram sums: a function of the group's size alone, so that a group's sums never depend on the other
+// groups.  Small groups take all rows in one workgroup (a workgroup per group fills the chip by their number); a group of 64 rows
+// has 2080 sums over up to n rows each, 16 workgroups at n = 4096.
+__host__ __device__ inline int lgo_chunk_rows(int s) { return s <= 4 ? (1 << 30) : s <= 16 ? 1024 : 256; }
+int lgo_gram_chunks(int n, int smax) { return (n + lgo_chunk_rows(smax) - 1) / lgo_chunk_rows(smax); }
+
+// Workgroup (g, c): the share of chunk c -- the rows c CH .. (c + 1) CH - 1 below n, CH = lgo_chunk_rows(s) -- in M_II, the Gram
+// matrix of the group's columns of X = L^-1 (entries above the diagonal of X are never read; chunks that end above the group's
+// first row have no share and are never read): 4 x 4 register tiles of the lower triangle, the rows of a stage dealt round-robin to
+// `nsplit` thread sets whose sums are added in ascending order.  part[c][foff[g] + p s + q], q <= p.
+template <typename T>
+__global__ void __launch_bounds__(256) lgo_gram_kernel(const T* __restrict__ Xinv, int np, int n, LgoLists L, size_t f_elems,
+                                                       double* __restrict__ part) {
+  extern __shared__ __align__(16) char smem_raw[];
+  __shared__ int idx[LGO_MAX_GROUP];
+  const int g = blockIdx.x, t = threadIdx.x;
+  const int p0 = L.goff[g], s = L.goff[g + 1] - p0;
+  const int ld = L.smax | 1;
+  double* A = reinterpret_cast<double*>(smem_raw);
+  double* stage = A + (size_t)L.smax * ld;
+  if (t < s) idx[t] = L.member[p0 + t];
+  __syncthreads();
+  const int CH = lgo_chunk_rows(s);
+  const long long c_lo = (long long)blockIdx.y * CH;
+  if (c_lo >= n || c_lo + CH <= idx[0]) return;  // (uniform) no such chunk for this group's size, or all of it above the first row
+  const int row_begin = max((int)c_lo, idx[0]), row_end = (int)min((long long)n, c_lo + CH);
+  {
+    const int s4 = (s + 3) & ~3, t4 = s4 / 4, ntl = t4 * (t4 + 1) / 2;
+    const int nsplit = min(64, 256 / ntl);
+    const int R = min(256, LGO_STAGE / s4);
+    const int tile = t % ntl, rs = t / ntl;
+    const bool active = rs < nsplit;
+    const int tp = tri_row(tile), tq = tile - tp * (tp + 1) / 2;
+    double acc[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[i][j] = 0;
+    for (int a0 = row_begin; a0 < row_end; a0 += R) {
+      __syncthreads();
+      for (int e = t; e < R * s4; e += 256) {
+        const int r = e / s4, p = e - r * s4, a = a0 + r;
+        double v = 0;
+        if (p < s && a < row_end && a >= idx[p]) v = (double)Xinv[(size_t)a * np + idx[p]];
+        stage[e] = v;
+      }
+      __syncthreads();
+      if (active)
+        for (int r = rs; r < R; r += nsplit) {
+          double xp[4], xq[4];
+#pragma unroll
+          for (int i = 0; i < 4; ++i) { xp[i] = stage[r * s4 + 4 * tp + i]; xq[i] = stage[r * s4 + 4 * tq + i]; }
+#pragma unroll
+          for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_fma(xp[i], xq[j], acc[i][j]);
+        }
+    }
+    for (int q = 0; q < nsplit; ++q) {
+      __syncthreads();
+      if (active && rs == q)
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const int pi = 4 * tp + i, pj = 4 * tq + j;
+            if (pi < s && pj <= pi) A[pi * ld + pj] = (q == 0 ? 0.0 : A[pi * ld + pj]) + acc[i][j];
+          }
+    }
+  }
+  __syncthreads();
+  double* out = part + (size_t)blockIdx.y * f_elems + L.foff[g];
+  for (int e = t; e < s * s; e += 256) {
+    const int p = e / s, q = e - p * s;
+    if (q <= p) out[e] = A[p * ld + q];
+  }
+}
+
+// One workgroup per group.  M_II = its chunks' shares from the first one that has any, in ascending order; then in the LDS:
+// M_II = Lm Lm^T, W = Lm^-1, z = W alpha_I, r = W^T z (the two triangular solves, through the inverse factor), Sigma = W^T W, lpd from
+// z^T z and diag Lm, B = F F^T.  Nothing depends on the group's label or on the other groups: the rows' results are a function of
+// (X, alpha, I) alone.
+template <typename T>
+__global__ void __launch_bounds__(256) lgo_group_kernel(const double* __restrict__ part, size_t f_elems, int n, const T* __restrict__ y,
+                                                        const T* __restrict__ alpha, LgoLists L, T* __restrict__ mean,
+                                                        T* __restrict__ var, T* __restrict__ lpd, double* __restrict__ avec,
+                                                        double* __restrict__ F, double* __restrict__ share, int* info) {
+  extern __shared__ __align__(16) char smem_raw[];
+  __shared__ int idx[LGO_MAX_GROUP];
+  __shared__ double al[LGO_MAX_GROUP], z[LGO_MAX_GROUP], rr[LGO_MAX_GROUP];
+  const int g = blockIdx.x, t = threadIdx.x;
+  const int p0 = L.goff[g], s = L.goff[g + 1] - p0;
+  const int ld = L.smax | 1;
+  double* A = reinterpret_cast<double*>(smem_raw);
+  double* W = A + (size_t)L.smax * ld;
+  if (t < s) {
+    idx[t] = L.member[p0 + t];
+    al[t] = (double)alpha[idx[t]];
+  }
+  __syncthreads();
+  {
+    const int CH = lgo_chunk_rows(s);
+    const int c0 = idx[0] / CH, c1 = (n + CH - 1) / CH;
+    const double* in = part + L.foff[g];
+    for (int e = t; e < s * s; e += 256) {
+      const int p = e / s, q = e - p * s;
+      if (q > p) continue;
+      double v = 0;
+      for (int c = c0; c < c1; ++c) v += in[(size_t)c * f_elems + e];
+      A[p * ld + q] = v;
+    }
+  }
+  bool ok = lgo_chol(A, s, ld);  // A = Lm
+  if (t < s) {  // column t of W = Lm^-1
+    for (int i = t; i < s; ++i) {
+      double v = (i == t) ? 1.0 : 0.0;
+      for (int k = t; k < i; ++k) v = __builtin_fma(-A[i * ld + k], W[k * ld + t], v);
+      W[i * ld + t] = v / A[i * ld + i];
+    }
+  }
+  __syncthreads();
+  if (t < s) {
+    double v = 0;
+    for (int k = 0; k <= t; ++k) v = __builtin_fma(W[t * ld + k], al[k], v);
+    z[t] = v;
+  }
+  double l = 0;
+  if (t == 0) {  // before A is overwritten
+    double ldet = 0;
+    for (int k = 0; k < s; ++k) ldet += log(A[k * ld + k]);
+    l = ldet;
+  }
+  __syncthreads();
+  if (t < s) {
+    double v = 0;
+    for (int k = t; k < s; ++k) v = __builtin_fma(W[k * ld + t], z[k], v);
+    rr[t] = v;
+  }
+  __syncthreads();
+  for (int e = t; e < s * s; e += 256) {
+    const int p = e / s, q = e - p * s;
+    if (q > p) continue;
+    double v = 0;
+    for (int k = p; k < s; ++k) v = __builtin_fma(W[k * ld + p], W[k * ld + q], v);  // Sigma_pq
+    if (p == q) {
+      const int ip = idx[p];
+      var[ip] = (T)v;
+      mean[ip] = (T)((double)y[ip] - rr[p]);
+      avec[ip] = rr[p];
+    }
+    A[p * ld + q] = 0.5 * (rr[p] * rr[q] + v);
+  }
+  ok = lgo_chol(A, s, ld) && ok;  // A = F
+  double* Fg = F + L.foff[g];
+  for (int e = t; e < s * s; e += 256) {
+    const int q = e / s, k = e - q * s;
+    Fg[e] = (k <= q) ? A[q * ld + k] : 0.0;
+  }
+  if (t == 0) {
+    double zz = 0;
+    for (int k = 0; k < s; ++k) zz = __builtin_fma(z[k], z[k], zz);
+    l = l - 0.5 * zz - 0.5 * (double)s * log(2.0 * 3.14159265358979323846);
+    if (!ok) {
+      l = __builtin_nan("");
+      atomicCAS(info, 0, 1 + idx[0]);
+    }
+    lpd[g] = (T)l;
+    share[g] = l;
+  }
+}
+
+// lgo = the groups' shares: thread t adds its run of consecutive dense ids in ascending order, thread 0 the 256 runs in order
+__global__ void __launch_bounds__(256) lgo_sum_kernel(const double* __restrict__ share, int G, EvalOut* out) {
+  __shared__ double runs[256];
+  const int per = (G + 255) / 256, b = threadIdx.x * per;
+  double s = 0;
+  for (int g = b; g < min(b + per, G); ++g) s += share[g];
+  runs[threadIdx.x] = s;
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  s = 0;
+  for (int i = 0; i < 256; ++i) s += runs[i];
+  out->lml = s;
+  atomicOr(&out->done, 1);
+}
+
+// One workgroup per (bundle of consecutive groups with at most 64 rows together, 64-row block of K^-1): the 64 x 64 panel
+// M[block, rows of the bundle] -- an entry above the diagonal is read at its mirror position, so the slot's unmirrored buffer and
+// the model's full matrix give the same bits -- then Y[block, member] = sum_q M[., q] F_g[q, k] over the member's own group and the
+// bundle's share of u = M a: pu[bundle][row], the bundle's rows in ascending list order.
+template <typename T>
+__global__ void __launch_bounds__(256) lgo_uy_kernel(const T* __restrict__ Kinv, int np, int n, LgoLists L,
+                                                     const double* __restrict__ avec, const double* __restrict__ F,
+                                                     T* __restrict__ Y, double* __restrict__ pu, const int* info) {
+  extern __shared__ __align__(16) char smem_raw[];
+  __shared__ int col[64], gs[64], ge[64], fo[64];
+  __shared__ double av[64];
+  if (*info != 0) return;
+  double* Fl = reinterpret_cast<double*>(smem_raw);  // [64][64], block diagonal
+  T* tile = reinterpret_cast<T*>(Fl + 64 * 64);      // [64][65]
+  const int b = blockIdx.x, a0 = blockIdx.y * 64;
+  const int t = threadIdx.x, tx = t & 63, ty = t >> 6;
+  const int pb0 = L.goff[L.boff[b]], cnt = L.goff[L.boff[b + 1]] - pb0;
+  if (t < 64) {
+    int c = 0, s0 = 0, s1 = 0, f = 0;
+    double a = 0;
+    if (t < cnt) {
+      const int g = L.gid[pb0 + t];
+      c = L.member[pb0 + t];
+      s0 = L.goff[g] - pb0;
+      s1 = L.goff[g + 1] - pb0;
+      f = L.foff[g];
+      a = avec[c];
+    }
+    col[t] = c; gs[t] = s0; ge[t] = s1; fo[t] = f; av[t] = a;
+  }
+  __syncthreads();
+  for (int e = t; e < 64 * 64; e += 256) {
+    const int q = e >> 6, k = e & 63;
+    double v = 0;
+    if (q < cnt && k < cnt && gs[q] == gs[k]) v = F[(size_t)fo[k] + (size_t)(q - gs[k]) * (ge[k] - gs[k]) + (k - gs[k])];
+    Fl[e] = v;
+  }
+  // the panel: lanes along the bundle's rows where the entry lies on or below the diagonal, along the block's rows where above
+  for (int r = ty; r < 64; r += 4) {
+    const int ga = a0 + r;
+    if (tx < cnt && ga < n && ga >= col[tx]) tile[r * 65 + tx] = Kinv[(size_t)ga * np + col[tx]];
+  }
+  for (int q = ty; q < 64; q += 4) {
+    const int ga = a0 + tx;
+    T v = T(0);
+    const bool upper = q < cnt && ga < col[q];
+    if (upper) v = Kinv[(size_t)col[q] * np + ga];
+    if (upper || q >= cnt || ga >= n) tile[tx * 65 + q] = v;
+  }
+  __syncthreads();
+  if (tx < cnt) {
+    const int ke = ge[tx], c = col[tx];
+    for (int r = ty; r < 64; r += 4) {
+      double sum = 0;
+      for (int q = tx; q < ke; ++q) sum = __builtin_fma((double)tile[r * 65 + q], Fl[q * 64 + tx], sum);
+      Y[(size_t)(a0 + r) * np + c] = (T)sum;
+    }
+  }
+  if (t < 64) {
+    double sum = 0;
+    for (int q = 0; q < cnt; ++q) sum = __builtin_fma((double)tile[t * 65 + q], av[q], sum);
+    pu[(size_t)b * np + a0 + t] = sum;
+  }
+}
+
+size_t lgo_uy_lds_bytes(bool is_f32) { return sizeof(double) * 64 * 64 + (is_f32 ? sizeof(float) : sizeof(double)) * 64 * 65; }
+
+template <typename T>
+void launch_lgo_group(const T* Xinv, int np, int n, const T* y, const T* alpha, const LgoLists& L, size_t f_elems, double* part, T* mean,
+                      T* var, T* lpd, double* avec, double* F, double* share, EvalOut* out, hipStream_t s) {
+  hipLaunchKernelGGL((lgo_gram_kernel<T>), dim3(L.G, lgo_gram_chunks(n, L.smax)), dim3(256), lgo_gram_lds_bytes(L.smax), s, Xinv, np, n, L,
+                     f_elems, part);
+  hipLaunchKernelGGL((lgo_group_kernel<T>), dim3(L.G), dim3(256), lgo_group_lds_bytes(L.smax), s, part, f_elems, n, y, alpha, L, mean, var,
+                     lpd, avec, F, share, &out->info);
+  hipLaunchKernelGGL(lgo_sum_kernel, dim3(1), dim3(256), 0, s, share, L.G, out);
+}
+template <typename T>
+void launch_lgo_uy(const T* Kinv, int np, int n, const LgoLists& L, const double* avec, const double* F, T* Y, double* pu, T* u,
+                   const int* info, hipStream_t s) {
+  hipLaunchKernelGGL((lgo_uy_kernel<T>), dim3(L.nb, np / 64), dim3(256), lgo_uy_lds_bytes(sizeof(T) == 4), s, Kinv, np, n, L, avec, F, Y,
+                     pu, info);
+  hipLaunchKernelGGL((loo_u_finish_kernel<T>), dim3((np + 255) / 256), dim3(256), 0, s, pu, L.nb, np, u);
+}
+#define LGO_INST(T)                                                                                                                  \
+  template void launch_lgo_group<T>(const T*, int, int, const T*, const T*, const LgoLists&, size_t, double*, T*, T*, T*, double*, \
+                                    double*, double*, EvalOut*, hipStream_t);                                                        \
+  template void launch_lgo_uy<T>(const T*, int, int, const LgoLists&, const double*, const double*, T*, double*, T*, const int*,    \
+                                 hipStream_t);
+LGO_INST(double)
+LGO_INST(float)
+#undef LGO_INST
+
+// =================================================================================================================
 // symmetrize: mirror the lower triangle into the upper one (what invc() hands back, lml.rs:62)
 // =================================================================================================================
 template <typename T>
@@ -5261,6 +5573,12 @@ void init_kernels() {
   set_lds_attr(reinterpret_cast<const void*>(&leaf_keep_kernel<double, float>), (int)LeafGeom<double>::LDS_BYTES, "leaf_keep_kernel<f32>: dynamic LDS limit");
   set_lds_attr(reinterpret_cast<const void*>(&qei_batch_kernel<double>), (int)qei_lds_bytes(QEI_MAXQ, MAXD), "qei_batch_kernel<f64>: dynamic LDS limit");
   set_lds_attr(reinterpret_cast<const void*>(&qei_batch_kernel<float>), (int)qei_lds_bytes(QEI_MAXQ, MAXD), "qei_batch_kernel<f32>: dynamic LDS limit");
+  set_lds_attr(reinterpret_cast<const void*>(&lgo_group_kernel<double>), (int)lgo_group_lds_bytes(LGO_MAX_GROUP), "lgo_group_kernel<f64>: dynamic LDS limit");
+  set_lds_attr(reinterpret_cast<const void*>(&lgo_group_kernel<float>), (int)lgo_group_lds_bytes(LGO_MAX_GROUP), "lgo_group_kernel<f32>: dynamic LDS limit");
+  set_lds_attr(reinterpret_cast<const void*>(&lgo_gram_kernel<double>), (int)lgo_gram_lds_bytes(LGO_MAX_GROUP), "lgo_gram_kernel<f64>: dynamic LDS limit");
+  set_lds_attr(reinterpret_cast<const void*>(&lgo_gram_kernel<float>), (int)lgo_gram_lds_bytes(LGO_MAX_GROUP), "lgo_gram_kernel<f32>: dynamic LDS limit");
+  set_lds_attr(reinterpret_cast<const void*>(&lgo_uy_kernel<double>), (int)lgo_uy_lds_bytes(false), "lgo_uy_kernel<f64>: dynamic LDS limit");
+  set_lds_attr(reinterpret_cast<const void*>(&lgo_uy_kernel<float>), (int)lgo_uy_lds_bytes(true), "lgo_uy_kernel<f32>: dynamic LDS limit");
   set_lds_attr(reinterpret_cast<const void*>(&kg_kernel<double>), (int)kg_lds_bytes(KG_LDS_ROWS), "kg_kernel<f64>: dynamic LDS limit");
   set_lds_attr(reinterpret_cast<const void*>(&kg_kernel<float>), (int)kg_lds_bytes(KG_LDS_ROWS), "kg_kernel<f32>: dynamic LDS limit");
   {

@@ -168,6 +168,15 @@ SIGNATURES = {
     "hbegp_model_loo_f64": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp]),
     "hbegp_model_loo_f32": (C.c_int, [_vp, _fp, _fp, _fp, _dp, _dp]),
     "hbegp_debug_loo_phases": (C.c_int, [C.c_int, _dp]),
+    # leave-group-out cross-validation: `const int* group` (one label per row, NULL: singletons)
+    "hbegp_problem_eval_lgo": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, _dp, _ip, _dp, _dp]),
+    "hbegp_fit_lgo_f64": (C.c_int, [_vp, _dp, _dp, _dp, _ip, C.c_int, C.c_int, C.c_double, _dp, _dp, _dp, _dp, C.c_int,
+                                    C.POINTER(FitOptions), _dp, _dp, C.POINTER(_vp)]),
+    "hbegp_fit_lgo_f32": (C.c_int, [_vp, _fp, _fp, _dp, _ip, C.c_int, C.c_int, C.c_double, _dp, _dp, _dp, _dp, C.c_int,
+                                    C.POINTER(FitOptions), _dp, _dp, C.POINTER(_vp)]),
+    "hbegp_model_lgo_f64": (C.c_int, [_vp, _ip, _dp, _dp, _dp, _ip, _dp, _dp]),
+    "hbegp_model_lgo_f32": (C.c_int, [_vp, _ip, _fp, _fp, _fp, _ip, _dp, _dp]),
+    "hbegp_debug_lgo_phases": (C.c_int, [C.c_int, _dp]),
     "hbegp_paths_create_f64": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_int, C.c_int, C.POINTER(_vp)]),
     "hbegp_paths_create_f32": (C.c_int, [_vp, _fp, _fp, _fp, _fp, C.c_int, C.c_int, C.POINTER(_vp)]),
     "hbegp_paths_eval_f64": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp]),

@@ -122,6 +122,25 @@ def aggregate_replicates(x, y):
     return x[first[order]], mean.astype(y.dtype), var, counts
 
 
+def replicate_groups(x, max_size=64):
+    """Group labels for leave-group-out cross-validation (EstimatorGPR.estimate(..., groups=), SurrogateModelGPR.lgo_a): rows with
+    equal x share a label, int32 [n], dense 0 .. L - 1 in order of first appearance.  A set of more than max_size equal rows
+    (the engine holds out at most 64 rows together) is split, in row order, into consecutive labels of max_size rows each."""
+    x = np.asarray(x)
+    assert x.ndim == 2 and max_size >= 1
+    _, inverse = np.unique(x, axis=0, return_inverse=True)
+    inverse = np.asarray(inverse).reshape(-1)
+    labels = np.empty(x.shape[0], dtype=np.int32)
+    current, held, nxt = {}, {}, 0
+    for i, u in enumerate(inverse.tolist()):
+        if u not in current or held[u] == max_size:
+            current[u], held[u] = nxt, 0
+            nxt += 1
+        labels[i] = current[u]
+        held[u] += 1
+    return labels
+
+
 def _norm_cdf(z):
     return 0.5 * math.erfc(-z / math.sqrt(2.0))
 
@@ -524,6 +543,15 @@ class SurrogateModelGPR:
         m, v, _, _ = self.fitted.loo()
         alpha, _ = self.fitted.arrays(want_kinv=False)
         resid = alpha * np.sqrt(v)
+        return self.y_norm.project_mean_from_normalized(m, v), self.y_norm.project_std_from_normalized(m, v), resid
+
+    def lgo_a(self, groups):
+        """Leave-group-out cross-validation of the surrogate on its own observations (FittedKernel.lgo): per training row the
+        prediction from all rows outside its group (`groups`: one int label per row, see replicate_groups), projected back
+        like loo_a -- (mean[n], std[n]) in y units -- and the standardised residuals (y_i - mu_i) / sqrt(var_i) in the
+        normalised space.  Where rows have twins, loo_a's residuals shrink towards zero and these do not."""
+        m, v, _, _ = self.fitted.lgo(groups)
+        resid = (np.asarray(self.fitted.y_train, dtype=np.float64) - m) / np.sqrt(v)
         return self.y_norm.project_mean_from_normalized(m, v), self.y_norm.project_std_from_normalized(m, v), resid
 
     # Batched forms of the scalar trait methods (SURVEY.md 8f rank 1: the acquisition loops call these once per generation
@@ -1399,8 +1427,9 @@ class EstimatorGPR:
 
     def objective(self, name="lml"):
         """What `estimate` maximises over the hyper-parameters: "lml", the log marginal likelihood (the reference's and the
-        default), or "loo", the leave-one-out log pseudo-likelihood (FittedKernel.new_by_loo)."""
-        if name not in ("lml", "loo"):
+        default), "loo", the leave-one-out log pseudo-likelihood (FittedKernel.new_by_loo), or "lgo", the leave-group-out log
+        predictive density over the `groups` that `estimate` is given (FittedKernel.new_by_lgo)."""
+        if name not in ("lml", "loo", "lgo"):
             raise ValueError(name)
         self._objective = name
         return self
@@ -1418,8 +1447,10 @@ class EstimatorGPR:
         hi = np.array([self._noise_bounds[1], a_hi] + [b[1] for b in self._length_scale_bounds])
         return theta0, lo, hi
 
-    def estimate(self, x, y, prior, rng, y_variance=None):  # gpr.rs:238-291
-        """y_variance (opt-in, not in the reference): the known noise variance of every y in y's own units -- for means of
+    def estimate(self, x, y, prior, rng, y_variance=None, groups=None):  # gpr.rs:238-291
+        """groups (opt-in, read by objective("lgo") only): one int label per observation; rows that share a label are held out
+        together (replicate_groups labels equal rows).  None with that objective means singletons: leave-one-out.
+        y_variance (opt-in, not in the reference): the known noise variance of every y in y's own units -- for means of
         replicates the variance of the mean (aggregate_replicates).  It is projected into the normalised space and rides on the
         diagonal next to the learned noise (FittedKernel.new(..., row_variance=))."""
         x = np.asarray(x)
@@ -1438,6 +1469,9 @@ class EstimatorGPR:
         # the estimator's own nu only configures the default kernel
         nu = prior.fitted.nu if prior is not None else self._matern_nu
         fit = gpr.FittedKernel.new_by_loo if self._objective == "loo" else gpr.FittedKernel.new
+        if self._objective == "lgo":
+            def fit(*args, **kw):
+                return gpr.FittedKernel.new_by_lgo(*args, groups=groups, **kw)
         if row_variance is None:
             fitted = fit(x, y_train.astype(x.dtype), theta0, lo, hi, starts, nu=nu, ctx=self.ctx)
         else:

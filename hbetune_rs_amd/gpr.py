@@ -72,6 +72,22 @@ def _row_variance(row_variance, n):
     return rv
 
 
+def _group_labels(groups, n):
+    """The caller's group labels as the C ABI takes them: int32 [n], or None (every row its own group)."""
+    if groups is None:
+        return None
+    g = np.asarray(groups).reshape(-1)
+    if g.shape != (n,):
+        raise ValueError(f"groups must have one label per training row ({n}), got {g.shape}")
+    if not np.issubdtype(g.dtype, np.integer):
+        raise ValueError(f"group labels must be integers, got {g.dtype}")
+    return np.ascontiguousarray(g, dtype=np.int32)
+
+
+def _iptr(a):
+    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_int))
+
+
 class Problem:
     """X, y resident on the device; repeated lml/gradient evaluations (the optimiser's inner loop)."""
 
@@ -135,6 +151,23 @@ class Problem:
         if _lib.check(code, allow=(NOT_PD,)) == NOT_PD:
             return None
         return loo.value, grad
+
+    def lgo_with_gradient(self, theta, groups, lo=None, hi=None, want_grad=True, dev=0, slot=0):
+        """The leave-group-out log predictive density at log-space theta and its gradient (hbegp_problem_eval_lgo): the slot's
+        evaluation, then the closed-form leave-group-out tail over `groups` (one int label per row; None: singletons, which is
+        leave-one-out).  Returns (lgo, grad) or None when not PD."""
+        lib = _lib.load()
+        theta = _lib.as_c(theta, np.float64)
+        lo = None if lo is None else _lib.as_c(lo, np.float64)
+        hi = None if hi is None else _lib.as_c(hi, np.float64)
+        g = _group_labels(groups, self.n)
+        lgo = C.c_double()
+        grad = np.zeros(self.p) if want_grad else None
+        code = lib.hbegp_problem_eval_lgo(self._h, dev, slot, _lib.dptr(theta), _lib.dptr(lo), _lib.dptr(hi), _iptr(g), C.byref(lgo),
+                                          _lib.dptr(grad))
+        if _lib.check(code, allow=(NOT_PD,)) == NOT_PD:
+            return None
+        return lgo.value, grad
 
     def results(self, want_kinv=True, dev=0, slot=0):
         """(alpha, k_inv, diag(L)) of the most recent evaluation."""
@@ -262,7 +295,16 @@ class FittedKernel:
         return FittedKernel._fit("hbegp_fit_loo", x_train, y_train, theta0, lo, hi, starts, nu, ctx, maxeval, fixed_work, trace, row_variance)
 
     @staticmethod
-    def _fit(symbol, x_train, y_train, theta0, lo, hi, starts, nu, ctx, maxeval, fixed_work, trace, row_variance=None):
+    def new_by_lgo(x_train, y_train, theta0, lo, hi, starts=None, nu=2.5, ctx=None, maxeval=150, fixed_work=False, trace=False,
+                   groups=None, row_variance=None):
+        """`new_by_loo` with the leave-group-out log predictive density over `groups` (one int label per row, at most 64 rows
+        per group; None: singletons) as the objective (hbegp_fit_lgo_*): rows that are replicates or near-duplicates of each
+        other are held out together.  Capture of the best lgo in `.lgo_best`; the model is `extend` at the captured theta."""
+        return FittedKernel._fit("hbegp_fit_lgo", x_train, y_train, theta0, lo, hi, starts, nu, ctx, maxeval, fixed_work, trace, row_variance,
+                                 groups)
+
+    @staticmethod
+    def _fit(symbol, x_train, y_train, theta0, lo, hi, starts, nu, ctx, maxeval, fixed_work, trace, row_variance=None, groups=None):
         lib = _lib.load()
         ctx = ctx or default_context()
         dtype = np.dtype(x_train.dtype)
@@ -301,7 +343,10 @@ class FittedKernel:
         rv = _row_variance(row_variance, n)
         tail = (n, d, float(nu), _lib.dptr(theta0), _lib.dptr(lo), _lib.dptr(hi), _lib.dptr(starts_c), n_restarts, C.byref(opt),
                 _lib.dptr(theta_best), C.byref(lml_best), C.byref(handle))
-        if rv is None:
+        if symbol == "hbegp_fit_lgo":  # one entry point: rv and the labels are both nullable arguments
+            g = _group_labels(groups, n)
+            _lib.check(getattr(lib, f"{symbol}_{sfx}")(ctx._h, _lib.aptr(x), _lib.aptr(y), _lib.dptr(rv), _iptr(g), *tail))
+        elif rv is None:
             _lib.check(getattr(lib, f"{symbol}_{sfx}")(ctx._h, _lib.aptr(x), _lib.aptr(y), *tail))
         else:
             _lib.check(getattr(lib, f"{symbol}_rv_{sfx}")(ctx._h, _lib.aptr(x), _lib.aptr(y), _lib.dptr(rv), *tail))
@@ -319,6 +364,8 @@ class FittedKernel:
         fk.theta_best = theta_best
         if symbol == "hbegp_fit_loo":
             fk.loo_best = lml_best.value
+        if symbol == "hbegp_fit_lgo":
+            fk.lgo_best = lml_best.value
         if trace:
             k = tr["count"].value
             fk.trace = dict(theta=tr["theta"][:k], lml=tr["lml"][:k], run=tr["run"][:k])
@@ -389,6 +436,23 @@ class FittedKernel:
         fn = getattr(_lib.load(), f"hbegp_model_loo_{self._sfx}")
         _lib.check(fn(self._h, _lib.aptr(mean), _lib.aptr(var), _lib.aptr(lpd), C.byref(loo), _lib.dptr(grad)))
         return (mean, var, lpd, loo.value, grad) if want_grad else (mean, var, lpd, loo.value)
+
+    def lgo(self, groups, want_grad=False):
+        """Leave-group-out cross-validation of the model on its own training rows in closed form (hbegp_model_lgo_*), in the
+        normalised y space.  groups: one int label per row (any values; at most 64 rows share one; None: singletons).  Returns
+        (mean[n], var[n], lpd[G], lgo) and, with want_grad, d lgo / d theta [p]; lpd is indexed by the labels' dense ids in order
+        of first appearance.  var is the diagonal of the group's predictive covariance of the observations: it includes the noise."""
+        g = _group_labels(groups, self.n)
+        mean = np.zeros(self.n, dtype=self.dtype)
+        var = np.zeros(self.n, dtype=self.dtype)
+        lpd = np.zeros(self.n, dtype=self.dtype)
+        n_groups = C.c_int(0)
+        lgo = C.c_double()
+        grad = np.zeros(self.d + 2) if want_grad else None
+        fn = getattr(_lib.load(), f"hbegp_model_lgo_{self._sfx}")
+        _lib.check(fn(self._h, _iptr(g), _lib.aptr(mean), _lib.aptr(var), _lib.aptr(lpd), C.byref(n_groups), C.byref(lgo), _lib.dptr(grad)))
+        lpd = lpd[:n_groups.value].copy()
+        return (mean, var, lpd, lgo.value, grad) if want_grad else (mean, var, lpd, lgo.value)
 
     def predict(self, x, want_variance=True):
         """predict() (predict.rs:7-52): returns (mean, variance or None, n_warn)."""

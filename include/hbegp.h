@@ -118,6 +118,12 @@ int hbegp_problem_eval(hbegp_problem* prob, int dev, int slot, const double* the
 int hbegp_problem_eval_loo(hbegp_problem* prob, int dev, int slot, const double* theta, const double* lo, const double* hi,
                            double* loo, double* grad);
 
+/* The leave-group-out log predictive density (see hbegp_model_lgo_* below) at theta as an evaluation: hbegp_problem_eval_loo with
+ * the groups group[n] (NULL: singletons).  The slot's normal evaluation without the lml gradient, then the leave-group-out tail on
+ * the slot's stream; clamping, grad, HBEGP_NOT_PD, the slot's state afterwards and threading as hbegp_problem_eval_loo. */
+int hbegp_problem_eval_lgo(hbegp_problem* prob, int dev, int slot, const double* theta, const double* lo, const double* hi,
+                           const int* group, double* lgo, double* grad);
+
 /* Copy out device results of the most recent successful evaluation on (dev, slot); any pointer may be NULL.
  * alpha[n]; kinv[n*n] full symmetric row-major (what invc() returns, lml.rs:62); ldiag[n] = diag(L). */
 int hbegp_problem_get_f64(hbegp_problem* prob, int dev, int slot, double* alpha, double* kinv, double* ldiag);
@@ -285,6 +291,16 @@ int hbegp_fit_rv_f64(hbegp_ctx* ctx, const double* X, const double* y, const dou
 int hbegp_fit_rv_f32(hbegp_ctx* ctx, const float* X, const float* y, const double* rv, int n, int d, double nu,
                      const double* theta0, const double* lo, const double* hi, const double* starts, int n_restarts,
                      const hbegp_fit_options* opt, double* theta_best, double* lml_best, hbegp_model** model);
+/* Fit by maximising the leave-group-out log predictive density over group[n] (NULL: singletons): hbegp_fit_loo_* with
+ * hbegp_problem_eval_lgo's value and gradient -- host-driven for every n, capture by arg-max, *model what hbegp_extend_* (with rv:
+ * hbegp_extend_rv_*) returns at theta_best, bit for bit.  rv (may be NULL) as in hbegp_fit_rv_*.  The group lists are checked and
+ * built once and uploaded once per device. */
+int hbegp_fit_lgo_f64(hbegp_ctx* ctx, const double* X, const double* y, const double* rv, const int* group, int n, int d, double nu,
+                      const double* theta0, const double* lo, const double* hi, const double* starts, int n_restarts,
+                      const hbegp_fit_options* opt, double* theta_best, double* lgo_best, hbegp_model** model);
+int hbegp_fit_lgo_f32(hbegp_ctx* ctx, const float* X, const float* y, const double* rv, const int* group, int n, int d, double nu,
+                      const double* theta0, const double* lo, const double* hi, const double* starts, int n_restarts,
+                      const hbegp_fit_options* opt, double* theta_best, double* lgo_best, hbegp_model** model);
 int hbegp_fit_loo_rv_f64(hbegp_ctx* ctx, const double* X, const double* y, const double* rv, int n, int d, double nu,
                          const double* theta0, const double* lo, const double* hi, const double* starts, int n_restarts,
                          const hbegp_fit_options* opt, double* theta_best, double* loo_best, hbegp_model** model);
@@ -798,6 +814,28 @@ int hbegp_maximize_qei_f32(hbegp_model* model, const float* starts, int R, int q
 int hbegp_model_loo_f64(hbegp_model* model, double* mean, double* var, double* lpd, double* loo, double* grad);
 int hbegp_model_loo_f32(hbegp_model* model, float* mean, float* var, float* lpd, double* loo, double* grad);
 
+/* Leave-group-out cross-validation of the model on its own training data, in closed form, in the model's
+ * normalised y space: every group of rows is predicted from all rows outside it.  Where rows are replicates, near-duplicates or
+ * measured together, leave-one-out predicts a row from its twins and reports a confidence the model does not have.
+ * group[n] (NULL: every row is its own group, which is leave-one-out): one label per training row, any int values; the labels are
+ * mapped to dense ids 0 .. G - 1 in order of first appearance.  A group holds at most HBEGP_LGO_MAX_GROUP rows (HBEGP_EINVAL with a
+ * message that names the label and its size otherwise).  With K = c Matern + diag(s2 + v_i), M = K^-1 and a group's row set I (s rows):
+ *   Sigma_g = (M_II)^-1            the covariance of the OBSERVATIONS y_I given all other rows (it includes the noise, as
+ *                                  hbegp_model_loo's var does);  var[i] = its diagonal entry of row i
+ *   r_g     = Sigma_g alpha_I,     mean[i] = y_i - r_g[i]
+ *   lpd[g]  = -1/2 alpha_I^T r_g + 1/2 ln|M_II| - s/2 ln 2 pi     indexed by dense id;   *lgo = sum_g lpd[g];   *n_groups = G
+ * M_II is the Gram matrix of the group's columns of L^-1, summed in fp64 in a fixed order for both element types, never a block of
+ * the stored K^-1; a row's mean and var depend on its group's row set alone, not on labels or on the other groups.
+ * grad[p]: d lgo / d theta, order [ln s2, ln c, ln ell_k]: leave-one-out's one symmetric n^3 product with a block-diagonal weight.
+ * mean, var [n] and lpd [at most n] have the model's element type; lgo and grad are fp64.  Every output may be NULL, but not all
+ * of them.  Memory, HBEGP_EINVAL and threading as hbegp_model_loo_*.  A group whose M_II or B_g = 1/2 (r_g r_g^T + Sigma_g) has a
+ * pivot that is not positive, or a value that is not finite (NaN data), is HBEGP_NOT_PD with *lgo = -inf and grad = 0. */
+#define HBEGP_LGO_MAX_GROUP 64
+int hbegp_model_lgo_f64(hbegp_model* model, const int* group, double* mean, double* var, double* lpd, int* n_groups, double* lgo,
+                        double* grad);
+int hbegp_model_lgo_f32(hbegp_model* model, const int* group, float* mean, float* var, float* lpd, int* n_groups, double* lgo,
+                        double* grad);
+
 int hbegp_model_info(const hbegp_model* model, int* n, int* d, int* is_f32, double* nu, double* lml);
 /* theta[p] (log space, clamped), alpha[n], kinv[n*n] full symmetric; any pointer may be NULL. */
 int hbegp_model_get_f64(hbegp_model* model, double* theta, double* alpha, double* kinv);
@@ -962,6 +1000,10 @@ int hbegp_debug_qei_phases(int enable, double* phase_ms);
  * last timed leave-one-out call with a gradient (hbegp_model_loo_*, hbegp_problem_eval_loo) -- the diagonal pass, u and Y, the
  * SYRK C = Y Y^T, the weighted trace -- in milliseconds; then enable != 0 makes this thread's later calls timed. */
 int hbegp_debug_loo_phases(int enable, double* phase_ms);
+
+/* ---- timing hook (tools/lgo_bench.py): as hbegp_debug_loo_phases for the leave-group-out calls with a gradient (hbegp_model_lgo_*,
+ * hbegp_problem_eval_lgo): phase_ms[4] = the group pass, u and Y, the SYRK C = Y Y^T, the weighted trace. */
+int hbegp_debug_lgo_phases(int enable, double* phase_ms);
 
 /* ---- posterior sample paths: draws of the posterior that are FUNCTIONS (pathwise conditioning, Matheron's rule, on a
  * random-Fourier-feature prior draw).  In the model's normalised y space,

@@ -52,3 +52,5 @@ echo "[extra] max-value entropy search: phases beside the host (profiles/mes_ben
 python3 "$ROOT/tools/mes_bench.py" --reps 3 > "$OUT/mes_bench.txt" 2>&1
 echo "[extra] the confidence bound: phases beside the host, the minimiser beside 150 single-point bounds (profiles/cb_bench.txt: prepend its header by hand)"
 python3 "$ROOT/tools/cb_bench.py" --reps 5 > "$OUT/cb_bench.txt" 2>&1
+echo "[extra] leave-group-out beside leave-one-out: evaluations and phases (profiles/lgo_bench.txt: prepend its header by hand)"
+python3 "$ROOT/tools/lgo_bench.py" --reps 15 > "$OUT/lgo_bench.txt" 2>&1
