@@ -220,6 +220,20 @@ void launch_gradtrace(const T* X, int n, int d, int np, int nu2, const EvalParam
                       double* part, EvalOut* out, const int* info, hipStream_t s, int* ticket = nullptr, EvalOut* hout = nullptr);
 size_t gradtrace_part_elems(int np, int d);
 
+// Input warping (hbegp_problem_eval_xgrad / _eval_warped; kernels.hip: warp_kernel, xgrad_kernel, warp_chain_kernel)
+//   warp:   U[n][d] (T) = the Kumaraswamy warp (warp.hpp) of X[n][d] with ab = [a_1..a_d, b_1..b_d] on the device, fp64 arithmetic
+//           rounded once; dlna / dlnb [n][d] (fp64; each may be null) = dU/dln a, dU/dln b.  U may not alias X.
+//   xgrad:  G[n][d] (fp64) = d lml / d X from the results of an evaluation at P: alpha and the LOWER triangle of Kinv (np x np).
+//           part: xgrad_part_elems(n, d) doubles; ticket: a device int, zero between launches.  Fixed summation order.
+//   chain:  out[2 d] (fp64) = sum_i G[i][k] dlna[i][k], then the same with dlnb.
+size_t xgrad_part_elems(int n, int d);
+template <typename T>
+void launch_warp(const T* X, int n, int d, const double* ab, T* U, double* dlna, double* dlnb, hipStream_t s);
+template <typename T>
+void launch_xgrad(const T* X, int n, int d, int np, int nu2, const EvalParams* P, const T* Kinv, const T* alpha, double* part, double* G,
+                  int* ticket, hipStream_t s);
+void launch_warp_chain(const double* G, const double* dlna, const double* dlnb, int n, int d, double* out, hipStream_t s);
+
 // Leave-one-out cross-validation (hbegp_model_loo / hbegp_problem_eval_loo; kernels.hip: loo_*_kernel), all on one stream:
 //   diag:  m_j = column sums of squares of Xinv = L^-1 (rows < n), then mean / var / lpd [n] (T), avec = alpha / m and
 //          sbvec = sqrt((1 + alpha^2 / m) / (2 m)) [np] (fp64, zero on the padding), out->lml = loo, out->done |= 1;

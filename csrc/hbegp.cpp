@@ -38,6 +38,7 @@
 #include "lbfgs_step.hpp"
 #include "lockstep.hpp"
 #include "slot_share.hpp"
+#include "warp.hpp"
 
 
 using namespace hbegp;
@@ -743,6 +744,11 @@ struct LooIn {
 template <typename T>
 static int loo_tail(const LooIn<T>& in, T* mean, T* var, T* lpd, double* loo, double* grad);
 
+// The input-gradient tail (below the model) on the same results: G = d lml / d X [n][d] -> gx (host, may be null),
+// and with `chain` (host, 2 d entries) the dot products of G's columns with dlna / dlnb [n][d] (device, fp64).
+template <typename T>
+static int xgrad_tail(const LooIn<T>& in, double* gx, const double* dlna, const double* dlnb, double* chain);
+
 // A partition of the training rows for leave-group-out cross-validation (lgo_tail): the caller's labels mapped to
 // dense ids 0 .. G - 1 in order of first appearance, and the int lists the kernels read (engine.hpp: LgoLists), back to back in
 // `lists` in the order member, gid, goff, foff, boff.
@@ -817,6 +823,10 @@ struct ProblemBase {
   virtual int eval_loo(int dev, int slot, const double* theta, const double* lo, const double* hi, double* loo, double* grad) = 0;
   virtual int eval_lgo(int dev, int slot, const double* theta, const double* lo, const double* hi, const LgoGroups& gr, double* lgo,
                        double* grad) = 0;
+  virtual int eval_xgrad(int dev, int slot, const double* theta, const double* lo, const double* hi, double* lml, double* grad, double* gx) = 0;
+  virtual int eval_warped(int dev, int slot, const double* theta, const double* lo, const double* hi, const double* ab, double* lml,
+                          double* grad) = 0;
+  virtual int get_rows(int dev, void* out, bool want_f32) = 0;
   virtual int time_eval(int dev, int slot, const double* theta, int reps, double* phase_ms) = 0;
   virtual int time_concurrent(int dev, const double* theta, int reps, double* out) = 0;
 };
@@ -827,6 +837,9 @@ struct hbegp_problem {
 template <typename T>
 struct Problem : ProblemBase {
   std::vector<T*> Xd, yd;                 // per device
+  std::vector<T*> X0d;                    // per device: the caller's rows, kept from the first hbegp_problem_eval_warped on (null: never warped)
+  std::vector<double*> warp_ws_;          // per device, with X0d: the warp's parameters and parameter derivatives on the device
+  std::vector<double> warp_ab_;
   std::vector<T*> rvd;                    // per device: the rows' known noise variances, n entries (null: none) -- K = c Matern + diag(s2 + v)
   std::vector<std::vector<Slot<T>>> slots;  // [device][slot]
   std::vector<std::vector<Sched>> scheds;   // [device][gemm launch ordinal]
@@ -1891,6 +1904,94 @@ struct Problem : ProblemBase {
     return lgo_on_slot((size_t)dev, slot, gr, nullptr, lgo, grad);
   }
 
+  // The slot's normal evaluation, then the input-gradient tail on what it left behind (as loo_on_slot: every path leaves alpha and
+  // the lower triangle of K^-1 in the buffer it wrote, the clamped parameters in the pinned block).
+  int eval_xgrad(int dev, int slot, const double* theta, const double* lo, const double* hi, double* lml, double* grad, double* gx) override {
+    const int st = eval(dev, slot, theta, lo, hi, lml, grad);
+    if (st != HBEGP_OK) {
+      if (st == HBEGP_NOT_PD) std::fill(gx, gx + (size_t)n * d, 0.0);
+      return st;
+    }
+    Slot<T>& s = slots[dev][slot];
+    const LooIn<T> in{s.dev, s.stream, n, d, np, nu2, Xd[dev], yd[dev], s.alpha[s.last_target], s.W2, s.Kinv[s.last_target], s.hP};
+    return xgrad_tail<T>(in, gx, nullptr, nullptr, nullptr);
+  }
+
+  // lml(w(X; a, b), theta) and its p + 2 d gradient.  The device's feature buffer is shared by the problem's
+  // slots and this call rewrites it, hence one slot only.  Everything is ordered on the slot's stream: the warp writes U over Xd,
+  // the evaluation and the tail read it, the caller's rows (kept in X0d from the first call on) are copied back -- also when the
+  // evaluation fails or throws.  Nothing derived from X is cached between evaluations (kmat, gradtrace, the single-launch
+  // evaluation and the tails read Xd anew every time; the captured graphs hold the pointer, not the contents).
+  int eval_warped(int dev, int slot, const double* theta, const double* lo, const double* hi, const double* ab, double* lml,
+                  double* grad) override {
+    if (n_slots != 1)
+      return fail(HBEGP_EINVAL, "hbegp_problem_eval_warped rewrites the device's feature buffer, which the slots of a problem share: "
+                  "it needs a problem created with n_slots == 1 (this one has %d)", n_slots);
+    if (dev < 0 || dev >= (int)slots.size() || slot != 0) return fail(HBEGP_EINVAL, "bad device/slot index");
+    for (int k = 0; k < 2 * d; ++k)
+      if (!std::isfinite(ab[k]) || !(ab[k] > 0.0)) return fail(HBEGP_EINVAL, "warp parameter %d is not a positive finite number", k);
+    Slot<T>& s = slots[dev][slot];
+    HIPCHECK(hipSetDevice(s.dev));
+    const size_t nd = (size_t)n * d;
+    const int p = d + 2;
+    if (X0d.empty()) X0d.assign(slots.size(), nullptr);
+    if (!X0d[dev]) {
+      // first use: the warp is defined on [0, 1] -- look at the rows once
+      std::vector<T> rows(nd);
+      HIPCHECK(hipMemcpyAsync(rows.data(), Xd[dev], sizeof(T) * nd, hipMemcpyDeviceToHost, s.stream));
+      HIPCHECK(hipStreamSynchronize(s.stream));
+      for (size_t e = 0; e < nd; ++e)
+        if (!(rows[e] >= T(0) && rows[e] <= T(1)))
+          return fail(HBEGP_EINVAL, "input warping needs features in [0, 1]: row %zu, feature %zu is %g", e / d, e % d, (double)rows[e]);
+      T* keep = palloc<T>(s.dev, nd);
+      HIPCHECK(hipMemcpyAsync(keep, Xd[dev], sizeof(T) * nd, hipMemcpyDeviceToDevice, s.stream));
+      X0d[dev] = keep;
+      if (warp_ws_.empty()) warp_ws_.assign(slots.size(), nullptr);
+      warp_ws_[dev] = palloc<double>(s.dev, 2 * (size_t)d + 2 * nd);
+    }
+    double* dab = warp_ws_[dev];  // [2 d] the parameters, then dU/dln a and dU/dln b [n d] each
+    double* dlna = grad ? dab + 2 * d : nullptr;
+    double* dlnb = grad ? dlna + nd : nullptr;
+    warp_ab_.assign(ab, ab + 2 * d);  // the source of an asynchronous copy: the problem's, not the caller's
+    ab = warp_ab_.data();
+    struct Restore {  // the caller's rows go back behind whatever the stream still holds, whichever way the call ends
+      T* dst; const T* src; size_t bytes; hipStream_t st; bool keep;
+      ~Restore() {
+        if (!keep) (void)hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st);
+        (void)hipStreamSynchronize(st);
+      }
+      // HBEGP_WARP_DEBUG_KEEP=1 (tests; read per call): the warped rows stay in the feature buffer, where hbegp_problem_debug_rows_*
+      // reads what the evaluation read.  The next call warps from the kept rows again and, without the variable, restores them.
+    } restore{Xd[dev], X0d[dev], sizeof(T) * nd, s.stream, env_int("HBEGP_WARP_DEBUG_KEEP", 0) != 0};
+    HIPCHECK(hipMemcpyAsync(dab, ab, sizeof(double) * 2 * d, hipMemcpyHostToDevice, s.stream));
+    launch_warp<T>(X0d[dev], n, d, dab, Xd[dev], dlna, dlnb, s.stream);
+    CHECK_LAUNCHES();
+    const int st = eval(dev, slot, theta, lo, hi, lml, grad);
+    if (st != HBEGP_OK) {
+      if (st == HBEGP_NOT_PD && grad) std::fill(grad + p, grad + p + 2 * d, 0.0);
+      return st;
+    }
+    if (!grad) return HBEGP_OK;
+    const LooIn<T> in{s.dev, s.stream, n, d, np, nu2, Xd[dev], yd[dev], s.alpha[s.last_target], s.W2, s.Kinv[s.last_target], s.hP};
+    const int st2 = xgrad_tail<T>(in, nullptr, dlna, dlnb, grad + p);
+    if (st2 == HBEGP_NOT_PD) {
+      *lml = -std::numeric_limits<double>::infinity();
+      std::fill(grad, grad + p + 2 * d, 0.0);
+    }
+    return st2;
+  }
+
+  // the rows the device's feature buffer holds right now (tests: what warp_kernel wrote is what the evaluation read)
+  int get_rows(int dev, void* out, bool want_f32) override {
+    if (want_f32 != is_f32) return fail(HBEGP_EINVAL, "element type mismatch");
+    if (dev < 0 || dev >= (int)slots.size()) return fail(HBEGP_EINVAL, "bad device index");
+    Slot<T>& s = slots[dev][0];
+    HIPCHECK(hipSetDevice(s.dev));
+    HIPCHECK(hipMemcpyAsync(out, Xd[dev], sizeof(T) * (size_t)n * d, hipMemcpyDeviceToHost, s.stream));
+    HIPCHECK(hipStreamSynchronize(s.stream));
+    return HBEGP_OK;
+  }
+
   int time_eval(int dev, int slot, const double* theta, int reps, double* phase_ms) override {
     if (dev < 0 || dev >= (int)slots.size() || slot < 0 || slot >= n_slots) return fail(HBEGP_EINVAL, "bad device/slot index");
     Slot<T>& s = slots[dev][slot];
@@ -2068,6 +2169,7 @@ struct hbegp_model {
   bool is_f32 = false;
   double lml = 0;
   std::vector<double> theta;  // clamped, log space
+  std::vector<double> warp_ab;  // hbegp_fit_warped_*: [a_1..a_d, b_1..b_d] of the input warp the model's rows went through (empty: none)
   void *X = nullptr, *alpha = nullptr, *Kinv = nullptr;  // device
   void* y = nullptr;     // the (normalised) targets, n entries: the residual of a sample path (hbegp_paths_create) starts from them
   void* rv = nullptr;    // the rows' known noise variances, n entries in the element type (null: none)
@@ -3505,6 +3607,48 @@ static int loo_tail(const LooIn<T>& in, T* mean, T* var, T* lpd, double* loo, do
   return HBEGP_OK;
 }
 
+// ---- input warping (hbegp_problem_eval_xgrad / _eval_warped) ------------------------------------------------
+
+// G = d lml / d X from what an evaluation left behind; reads only, its work arrays are borrowed for the call.  A result that is
+// not finite is HBEGP_NOT_PD with zeros, as the evaluations handle it.
+template <typename T>
+static int xgrad_tail(const LooIn<T>& in, double* gx, const double* dlna, const double* dlnb, double* chain) {
+  HIPCHECK(hipSetDevice(in.dev));
+  const int n = in.n, d = in.d;
+  const size_t nd = (size_t)n * d;
+  hipStream_t s = in.s;
+  CallScratch ws{in.dev, s, {}};
+  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+  const size_t b_tk = 256, b_g = up(sizeof(double) * nd), b_part = up(sizeof(double) * xgrad_part_elems(n, d));
+  const size_t b_ch = up(sizeof(double) * 2 * d);
+  char* q = static_cast<char*>(ws.get(b_tk + b_g + b_part + b_ch));
+  int* ticket = reinterpret_cast<int*>(q); q += b_tk;
+  double* G = reinterpret_cast<double*>(q); q += b_g;
+  double* part = reinterpret_cast<double*>(q); q += b_part;
+  double* ch = reinterpret_cast<double*>(q);
+  HIPCHECK(hipMemsetAsync(ticket, 0, b_tk, s));  // a recycled block holds its earlier owner's numbers
+  launch_xgrad<T>(in.X, n, d, in.np, in.nu2, in.P, in.Kinv, in.alpha, part, G, ticket, s);
+  if (chain) launch_warp_chain(G, dlna, dlnb, n, d, ch, s);
+  CHECK_LAUNCHES();
+  std::vector<double> gh;
+  if (!gx) {  // looked at for NaN all the same
+    gh.resize(nd);
+    gx = gh.data();
+  }
+  HIPCHECK(hipMemcpyAsync(gx, G, sizeof(double) * nd, hipMemcpyDeviceToHost, s));
+  if (chain) HIPCHECK(hipMemcpyAsync(chain, ch, sizeof(double) * 2 * d, hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
+  bool finite = true;
+  for (size_t e = 0; e < nd; ++e) finite = finite && std::isfinite(gx[e]);
+  if (chain) for (int k = 0; k < 2 * d; ++k) finite = finite && std::isfinite(chain[k]);
+  if (!finite) {
+    std::fill(gx, gx + nd, 0.0);
+    if (chain) std::fill(chain, chain + 2 * d, 0.0);
+    return fail(HBEGP_NOT_PD, "the gradient with respect to the training inputs is not finite");
+  }
+  return HBEGP_OK;
+}
+
 template <typename T>
 static int model_loo(hbegp_model* m, T* mean, T* var, T* lpd, double* loo, double* grad) {
   std::lock_guard<std::mutex> lock(m->mu);
@@ -4645,6 +4789,69 @@ int hbegp_problem_eval_lgo(hbegp_problem* prob, int dev, int slot, const double*
   GUARD_END
 }
 
+int hbegp_problem_eval_xgrad(hbegp_problem* prob, int dev, int slot, const double* theta, const double* lo, const double* hi,
+                             double* lml, double* grad, double* gx) {
+  if (!prob) return fail(HBEGP_EINVAL, "NULL problem");
+  if (!theta || !lml || !gx) return fail(HBEGP_EINVAL, "theta / lml / gx is NULL");
+  GUARD_BEGIN
+  return prob->impl->eval_xgrad(dev, slot, theta, lo, hi, lml, grad, gx);
+  GUARD_END
+}
+
+int hbegp_problem_eval_warped(hbegp_problem* prob, int dev, int slot, const double* theta, const double* lo, const double* hi,
+                              const double* ab, double* lml, double* grad) {
+  if (!prob) return fail(HBEGP_EINVAL, "NULL problem");
+  if (!theta || !ab || !lml) return fail(HBEGP_EINVAL, "theta / ab / lml is NULL");
+  GUARD_BEGIN
+  return prob->impl->eval_warped(dev, slot, theta, lo, hi, ab, lml, grad);
+  GUARD_END
+}
+
+int hbegp_problem_debug_rows_f64(hbegp_problem* prob, int dev, double* out) {
+  if (!prob || !out) return fail(HBEGP_EINVAL, "NULL argument");
+  GUARD_BEGIN
+  return prob->impl->get_rows(dev, out, false);
+  GUARD_END
+}
+int hbegp_problem_debug_rows_f32(hbegp_problem* prob, int dev, float* out) {
+  if (!prob || !out) return fail(HBEGP_EINVAL, "NULL argument");
+  GUARD_BEGIN
+  return prob->impl->get_rows(dev, out, true);
+  GUARD_END
+}
+
+static int warp_check_ab(const double* ab, int d) {
+  if (!ab || d < 1) return fail(HBEGP_EINVAL, "warp: NULL parameters or d < 1");
+  for (int k = 0; k < 2 * d; ++k)
+    if (!std::isfinite(ab[k]) || !(ab[k] > 0.0)) return fail(HBEGP_EINVAL, "warp parameter %d is not a positive finite number", k);
+  return HBEGP_OK;
+}
+int hbegp_warp_apply(const double* ab, int d, const double* X, int m, double* U, double* dU_dlna, double* dU_dlnb, double* dU_dx) {
+  if (int e = warp_check_ab(ab, d)) return e;
+  if (m < 0 || (m > 0 && !X)) return fail(HBEGP_EINVAL, "warp: m < 0 or NULL X");
+  const size_t count = (size_t)m * d;
+  for (size_t e = 0; e < count; ++e)
+    if (!(X[e] >= 0.0 && X[e] <= 1.0)) return fail(HBEGP_EINVAL, "warp: row %zu, feature %zu is outside [0, 1]", e / d, e % d);
+  for (size_t e = 0; e < count; ++e) {
+    const int k = (int)(e % d);
+    hbegp::warp::apply(ab[k], ab[d + k], X[e], U ? U + e : nullptr, dU_dlna ? dU_dlna + e : nullptr, dU_dlnb ? dU_dlnb + e : nullptr,
+                       dU_dx ? dU_dx + e : nullptr);
+  }
+  return HBEGP_OK;
+}
+int hbegp_warp_invert(const double* ab, int d, const double* U, int m, double* X) {
+  if (int e = warp_check_ab(ab, d)) return e;
+  if (m < 0 || (m > 0 && (!U || !X))) return fail(HBEGP_EINVAL, "warp: m < 0 or NULL U / X");
+  const size_t count = (size_t)m * d;
+  for (size_t e = 0; e < count; ++e)
+    if (!(U[e] >= 0.0 && U[e] <= 1.0)) return fail(HBEGP_EINVAL, "warp: row %zu, feature %zu is outside [0, 1]", e / d, e % d);
+  for (size_t e = 0; e < count; ++e) {
+    const int k = (int)(e % d);
+    X[e] = hbegp::warp::invert(ab[k], ab[d + k], U[e]);
+  }
+  return HBEGP_OK;
+}
+
 int hbegp_problem_time_concurrent(hbegp_problem* prob, int dev, const double* theta, int reps, double* out) {
   if (!prob || !theta || !out || reps < 1) return fail(HBEGP_EINVAL, "bad argument");
   GUARD_BEGIN
@@ -4901,6 +5108,116 @@ static int fit_rv(hbegp_ctx* ctx, const T* X, const T* y, const double* rv, int 
   return do_fit<T>(ctx, X, y, rv, n, d, nu, theta0, lo, hi, starts, n_restarts, opt, theta_best, best, model, objective, &gr);
   GUARD_END
 }
+// The warped fit (hbegp_fit_warped_*): bounded L-BFGS (lbfgsb_minimize) over the p + 2 d log-space variables
+// [theta, ln a, ln b] with hbegp_problem_eval_warped's value and gradient, on ONE single-slot problem with the fit's path selection,
+// 1 + n_restarts runs one after another (the feature buffer is rewritten by every evaluation: runs side by side would need one per
+// slot).  The capture rule is do_fit's: the best lml wins, ties keep the earlier (run, evaluation); a failed evaluation counts as
+// +inf with a zero gradient.  The model is do_extend at theta_best on the rows warped by ab_best.
+template <typename T>
+static int fit_warped(hbegp_ctx* ctx, const T* X, const T* y, const double* rv, int n, int d, double nu, const double* theta0,
+                      const double* lo, const double* hi, const double* ab0, const double* ab_lo, const double* ab_hi,
+                      const double* starts, int n_restarts, const hbegp_fit_options* opt_in, double* theta_best, double* ab_best,
+                      double* lml_best, hbegp_model** model_out) {
+  hbegp_fit_options opt{};
+  if (int e = read_fit_options(opt_in, &opt)) return e;
+  if (int e = check_args(ctx, X, y, n, d, nu)) return e;
+  if (!theta0 || !lo || !hi || (n_restarts > 0 && !starts)) return fail(HBEGP_EINVAL, "theta0/lo/hi/starts is NULL");
+  if (int e = check_rv<T>(rv, n)) return e;
+  const int p = d + 2, q = p + 2 * d;
+  std::vector<double> lnlo(q), lnhi(q), wlo(2 * d), whi(2 * d);
+  for (int k = 0; k < 2 * d; ++k) {
+    wlo[k] = ab_lo ? ab_lo[k] : 0.2;
+    whi[k] = ab_hi ? ab_hi[k] : 5.0;
+    if (!std::isfinite(wlo[k]) || !std::isfinite(whi[k]) || !(wlo[k] > 0.0) || !(wlo[k] <= whi[k]))
+      return fail(HBEGP_EINVAL, "warp bounds %d: need 0 < lo <= hi, both finite (got %g, %g)", k, wlo[k], whi[k]);
+    if (ab0 && (!std::isfinite(ab0[k]) || !(ab0[k] > 0.0))) return fail(HBEGP_EINVAL, "ab0[%d] is not a positive finite number", k);
+  }
+  for (size_t e = 0; e < (size_t)n * d; ++e)
+    if (!(X[e] >= T(0) && X[e] <= T(1)))
+      return fail(HBEGP_EINVAL, "input warping needs features in [0, 1]: row %zu, feature %zu is %g", e / d, e % d, (double)X[e]);
+  GUARD_BEGIN
+  if (opt.maxeval <= 0) opt.maxeval = 150;
+  for (int i = 0; i < p; ++i) {
+    lnlo[i] = std::log(lo[i]);
+    lnhi[i] = std::log(hi[i]);
+  }
+  for (int k = 0; k < 2 * d; ++k) {
+    lnlo[p + k] = std::log(wlo[k]);
+    lnhi[p + k] = std::log(whi[k]);
+  }
+  hbegp_ctx one;
+  one.devs = {ctx->devs[0]};
+  const int nruns = 1 + std::max(0, n_restarts);
+  int n_evals = 0, n_not_pd = 0, trace_n = 0;
+  double best_lml = -std::numeric_limits<double>::infinity();
+  std::vector<double> best_v;
+  {
+    Problem<T> prob(&one, X, y, n, d, nu, 1, false, true, false, rv);
+    std::vector<double> ab(2 * d), x(q);
+    for (int r = 0; r < nruns; ++r) {
+      if (r == 0) {
+        for (int i = 0; i < p; ++i) x[i] = theta0[i];
+        for (int k = 0; k < 2 * d; ++k) x[p + k] = ab0 ? std::log(ab0[k]) : 0.0;
+      } else {
+        for (int i = 0; i < q; ++i) x[i] = starts[(size_t)(r - 1) * q + i];
+      }
+      Objective obj = [&](const double* v, double* grad) -> double {
+        for (int k = 0; k < 2 * d; ++k) ab[k] = std::min(std::max(std::exp(v[p + k]), wlo[k]), whi[k]);
+        double lml;
+        const int st = prob.eval_warped(0, 0, v, lo, hi, ab.data(), &lml, grad);
+        if (st != HBEGP_OK && st != HBEGP_NOT_PD) throw std::runtime_error(g_last_error);
+        ++n_evals;
+        if (st != HBEGP_OK) {
+          ++n_not_pd;
+          lml = -std::numeric_limits<double>::infinity();
+          for (int j = 0; j < q; ++j) grad[j] = 0.0;
+        }
+        if (opt.trace_cap > 0 && trace_n < opt.trace_cap) {
+          const int tI = trace_n++;
+          if (opt.trace_theta) memcpy(opt.trace_theta + (size_t)tI * q, v, sizeof(double) * q);
+          if (opt.trace_lml) opt.trace_lml[tI] = lml;
+          if (opt.trace_grad) memcpy(opt.trace_grad + (size_t)tI * q, grad, sizeof(double) * q);
+          if (opt.trace_run) opt.trace_run[tI] = r;
+        }
+        if (st != HBEGP_OK) return std::numeric_limits<double>::infinity();
+        if (best_v.empty() || lml > best_lml) {  // runs and evaluations come in order: a tie keeps the earlier one
+          best_lml = lml;
+          best_v.assign(v, v + q);
+        }
+        for (int j = 0; j < q; ++j) grad[j] = -grad[j];
+        return -lml;
+      };
+      LbfgsOptions lo_opt;
+      lo_opt.maxeval = opt.maxeval;
+      lo_opt.fixed_work = opt.fixed_work != 0;
+      if (opt.lbfgs_memory > 0) lo_opt.memory = opt.lbfgs_memory;
+      lbfgsb_minimize(obj, x.data(), lnlo.data(), lnhi.data(), q, lo_opt);
+    }
+  }  // the fit's slot is back in the pool before the model is built
+  if (opt.trace_count) *opt.trace_count = trace_n;
+  if (opt.n_evals) *opt.n_evals = n_evals;
+  if (opt.n_not_pd) *opt.n_not_pd = n_not_pd;
+  if (best_v.empty()) return fail(HBEGP_ALL_FAILED, "every evaluation of the fit failed (kernel matrix not positive definite)");
+  std::vector<double> th(p), abw(2 * d);
+  for (int i = 0; i < p; ++i) th[i] = std::log(std::min(std::max(std::exp(best_v[i]), lo[i]), hi[i]));
+  for (int k = 0; k < 2 * d; ++k) abw[k] = std::min(std::max(std::exp(best_v[p + k]), wlo[k]), whi[k]);
+  if (theta_best) memcpy(theta_best, th.data(), sizeof(double) * p);
+  if (ab_best) memcpy(ab_best, abw.data(), sizeof(double) * 2 * d);
+  if (lml_best) *lml_best = best_lml;
+  if (!model_out) return HBEGP_OK;
+  // the rows the captured evaluation read: hbegp_warp_apply's U rounded once to T (the device's warp is the same function)
+  std::vector<T> U((size_t)n * d);
+  for (size_t e = 0; e < U.size(); ++e) {
+    double u;
+    hbegp::warp::apply(abw[e % d], abw[d + e % d], (double)X[e], &u, nullptr, nullptr, nullptr);
+    U[e] = (T)u;
+  }
+  const int st = do_extend<T>(ctx, U.data(), y, rv, n, d, nu, th.data(), nullptr, nullptr, model_out);
+  if (st == HBEGP_OK) (*model_out)->warp_ab = abw;
+  return st;
+  GUARD_END
+}
+
 template <typename T>
 static int extend_rv(hbegp_ctx* ctx, const T* X, const T* y, const double* rv, int n, int d, double nu, const double* theta,
                      const double* lo, const double* hi, hbegp_model** model) {
@@ -4978,6 +5295,26 @@ int hbegp_extend_from_rv_f64(hbegp_ctx* ctx, hbegp_model* prior, const double* X
 int hbegp_extend_from_rv_f32(hbegp_ctx* ctx, hbegp_model* prior, const float* X, const float* y, const double* rv, int n,
                              hbegp_model** model, int* incremental) {
   return extend_from_rv<float>(ctx, prior, X, y, rv, n, model, incremental);
+}
+int hbegp_model_warp(const hbegp_model* model, double* ab) {
+  if (!model) return fail(HBEGP_EINVAL, "NULL model");
+  if (model->warp_ab.empty()) return 0;
+  if (ab) memcpy(ab, model->warp_ab.data(), sizeof(double) * model->warp_ab.size());
+  return 1;
+}
+int hbegp_fit_warped_f64(hbegp_ctx* ctx, const double* X, const double* y, const double* rv, int n, int d, double nu, const double* theta0,
+                         const double* lo, const double* hi, const double* ab0, const double* ab_lo, const double* ab_hi,
+                         const double* starts, int n_restarts, const hbegp_fit_options* opt, double* theta_best, double* ab_best,
+                         double* lml_best, hbegp_model** model) {
+  return fit_warped<double>(ctx, X, y, rv, n, d, nu, theta0, lo, hi, ab0, ab_lo, ab_hi, starts, n_restarts, opt, theta_best, ab_best,
+                            lml_best, model);
+}
+int hbegp_fit_warped_f32(hbegp_ctx* ctx, const float* X, const float* y, const double* rv, int n, int d, double nu, const double* theta0,
+                         const double* lo, const double* hi, const double* ab0, const double* ab_lo, const double* ab_hi,
+                         const double* starts, int n_restarts, const hbegp_fit_options* opt, double* theta_best, double* ab_best,
+                         double* lml_best, hbegp_model** model) {
+  return fit_warped<float>(ctx, X, y, rv, n, d, nu, theta0, lo, hi, ab0, ab_lo, ab_hi, starts, n_restarts, opt, theta_best, ab_best,
+                           lml_best, model);
 }
 int hbegp_model_row_variance(const hbegp_model* model, double* rv) {
   if (!model) return fail(HBEGP_EINVAL, "NULL model");

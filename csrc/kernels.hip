@@ -26,6 +26,7 @@
 #include "engine.hpp"
 #include "fastmath.hpp"
 #include "lbfgs_step.hpp"
+#include "warp.hpp"
 
 namespace hbegp {
 
@@ -1720,6 +1721,233 @@ template void launch_gradtrace<double>(const double*, int, int, int, int, const 
                                        double*, EvalOut*, const int*, hipStream_t, int*, EvalOut*);
 template void launch_gradtrace<float>(const float*, int, int, int, int, const EvalParams*, const float*, const float*,
                                       double*, EvalOut*, const int*, hipStream_t, int*, EvalOut*);
+
+// =================================================================================================================
+// Input warping (hbegp_problem_eval_xgrad / _eval_warped).
+//   warp_kernel        U = w(X; a, b) elementwise (warp.hpp, fp64, rounded once to T) and, on request, dU/dln a, dU/dln b (fp64)
+//   xgrad_kernel       G_ik = d lml / d x_ik = sum_j (alpha_i alpha_j - Kinv_ij) c psi(r_ij) (x_ik - x_jk) / ell_k^2, psi = phi'(r) / r
+//   warp_chain_kernel  out[k] = sum_i G_ik dU_ik/dln a_k, out[d + k] the same for b
+// xgrad_kernel is gradtrace's sibling: the same 64-row tiles of X in the LDS (xj_index layout), the same thread -> 4 x 4 entries
+// map, the same distance sum, the same gradient factor gr of the four orders (psi = -gr: dK/dln ell_k = c gr d_k with
+// d_k = -r dr/dln ell_k), GT_CHUNK features per register pass.  What differs is the sum: a row's entries are added over j ONLY,
+// with (x_ik - x_jk) / ell_k^2 in place of its square, so W is needed on both sides of the diagonal while the slot's K^-1 is valid
+// on and below it only: element (max(i, j), min(i, j)) is read.  Entries with r = 0 (the diagonal, duplicate rows) contribute 0:
+// their difference is 0 and gr is finite (0 for nu = 1/2).  Rows and columns >= n contribute nothing and receive nothing.
+// Grid: x = (row tile, feature chunk), y = XG_SPLIT-th shares of the j tiles (row tiles alone are 64 workgroups at n = 4096).
+// Workgroup (li, kc, s) adds its j tiles lj = s, s + S, ... in ascending order into fp64 registers (per entry row: the four
+// columns of a thread in T, as gradtrace adds them), then the 16 threads of a row by an xor butterfly, and stores
+// part[s][row][k] write-through; the launch's last workgroup (the ticket pattern) adds the S shares of every (row, k) in ascending
+// s.  S depends on n alone: the same inputs give the same bits whatever the timing.
+// =================================================================================================================
+constexpr int XG_SPLIT = 8;
+
+template <typename T, int NU2>
+__device__ __forceinline__ T matern_gr(T ds) {  // gradtrace_tile's gr
+#pragma clang fp contract(off)
+  if (NU2 == 5) {
+    const T tt = sqrt_nonneg(ds * T(5));
+    return T(5.0 / 3.0) * (tt + T(1)) * exp_nonpos(-tt);
+  } else if (NU2 == 3) {
+    const T tt = sqrt_nonneg(ds * T(3));
+    return T(3) * exp_nonpos(-tt);
+  } else if (NU2 == 0) {
+    return exp_nonpos(T(-0.5) * ds);
+  } else {
+    const T rr = sqrt_nonneg(ds);
+    return (rr > T(0)) ? exp_nonpos(-rr) / rr : T(0);
+  }
+}
+
+static int xgrad_splits(int n) { return std::min((n + 63) / 64, XG_SPLIT); }
+size_t xgrad_part_elems(int n, int d) { return (size_t)xgrad_splits(n) * ((n + 63) / 64 * 64) * d; }
+
+template <typename T, int NU2>
+__global__ void __launch_bounds__(256) xgrad_kernel(const T* __restrict__ X, int n, int d, int np, const EvalParams* __restrict__ P,
+                                                    const T* __restrict__ Kinv, const T* __restrict__ alpha,
+                                                    double* __restrict__ part, double* __restrict__ G, int* ticket) {
+  extern __shared__ __align__(16) char smem_raw[];
+  T* xi = reinterpret_cast<T*>(smem_raw);  // [d][64] raw features of the i tile
+  T* xj = xi + (size_t)d * 64;             // j tile, xj_index layout
+  __shared__ double inv_l2[MAXD];
+  const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
+  const int nt = (n + 63) / 64;            // tiles that hold a live row
+  const int li = (int)blockIdx.x % nt, kc = ((int)blockIdx.x / nt) * GT_CHUNK;
+  const int split = (int)blockIdx.y, nsplit = (int)gridDim.y;
+  const int i0 = li * 64;
+  if (t < d) {
+    const T ell = (T)P->ell[t];
+    inv_l2[t] = (double)(T(1) / (ell * ell));
+  }
+  const T amp = (T)P->amp;
+  for (int e = t; e < 64 * d; e += 256) {
+    const int row = e / d, k = e - row * d;
+    const int gi = i0 + row;
+    xi[k * 64 + row] = (gi < n) ? X[(size_t)gi * d + k] : T(0);
+  }
+  double acc[4][GT_CHUNK];
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+#pragma unroll
+    for (int u = 0; u < GT_CHUNK; ++u) acc[r][u] = 0;
+  typedef T vec4 __attribute__((ext_vector_type(4)));
+  for (int lj = split; lj < nt; lj += nsplit) {
+    const int j0 = lj * 64;
+    __syncthreads();  // the previous j tile has been read
+    for (int e = t; e < 64 * d; e += 256) {
+      const int row = e / d, k = e - row * d;
+      const int gj = j0 + row;
+      xj[xj_index<T>(k, row)] = (gj < n) ? X[(size_t)gj * d + k] : T(0);
+    }
+    __syncthreads();
+    T dsum[4][4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) dsum[r][c] = T(0);
+    for (int k = 0; k < d; ++k) {
+      const T il2 = (T)inv_l2[k];
+      T a[4], b[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) a[r] = xi[k * 64 + ty + 16 * r];
+      read_xj4<T>(xj, k, tx, b);
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const T df = a[r] - b[c];
+          dsum[r][c] += df * df * il2;
+        }
+    }
+    // coef = W_ij c psi(r_ij)
+    T coef[4][4];
+    if (li > lj && i0 + 64 <= n) {
+      // wholly inside the matrix and below the diagonal: K^-1 as stored, one 16-byte load per row
+      const vec4 aj = *reinterpret_cast<const vec4*>(alpha + j0 + tx * 4);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int gi = i0 + ty + 16 * r;
+        const T ai = alpha[gi];
+        const vec4 kv = *reinterpret_cast<const vec4*>(Kinv + (size_t)gi * np + j0 + tx * 4);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) coef[r][c] = -((ai * aj[c] - kv[c]) * amp * matern_gr<T, NU2>(dsum[r][c]));
+      }
+    } else {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int gi = i0 + ty + 16 * r;
+        const T ai = (gi < n) ? alpha[gi] : T(0);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const int gj = j0 + tx * 4 + c;
+          T cf = T(0);
+          if (gi < n && gj < n) {
+            const int hi = max(gi, gj), lo = min(gi, gj);  // the lower triangle is the valid one
+            const T w = ai * alpha[gj] - Kinv[(size_t)hi * np + lo];
+            cf = -(w * amp * matern_gr<T, NU2>(dsum[r][c]));
+          }
+          coef[r][c] = cf;
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < GT_CHUNK; ++u) {
+      const int k = kc + u;
+      if (k < d) {
+        const T il2 = (T)inv_l2[k];
+        T a[4], b[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) a[r] = xi[k * 64 + ty + 16 * r];
+        read_xj4<T>(xj, k, tx, b);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          T sacc = T(0);
+#pragma unroll
+          for (int c = 0; c < 4; ++c) sacc += coef[r][c] * ((a[r] - b[c]) * il2);
+          acc[r][u] += (double)sacc;
+        }
+      }
+    }
+  }
+  // the 16 threads of a row (tx = 0..15 are neighbouring lanes); every lane ends with the sum
+  const size_t n64 = (size_t)nt * 64;
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+#pragma unroll
+    for (int u = 0; u < GT_CHUNK; ++u) {
+      double v = acc[r][u];
+      v += __shfl_xor(v, 1, 64);
+      v += __shfl_xor(v, 2, 64);
+      v += __shfl_xor(v, 4, 64);
+      v += __shfl_xor(v, 8, 64);
+      const int k = kc + u;
+      if (tx == 0 && k < d) publish_f64(&part[((size_t)split * n64 + i0 + ty + 16 * r) * d + k], v);
+    }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (!last_workgroup(ticket)) return;
+  const size_t nd = (size_t)n * d, stride = n64 * d;
+  for (size_t e = t; e < nd; e += 256) {
+    double s = 0;
+    for (int q = 0; q < nsplit; ++q) s += part[(size_t)q * stride + e];
+    G[e] = s;
+  }
+}
+
+template <typename T>
+void launch_xgrad(const T* X, int n, int d, int np, int nu2, const EvalParams* P, const T* Kinv, const T* alpha, double* part, double* G,
+                  int* ticket, hipStream_t s) {
+  const int nt = (n + 63) / 64, nch = (d + GT_CHUNK - 1) / GT_CHUNK;
+  const size_t lds = (size_t)2 * d * 64 * sizeof(T);
+  const dim3 grid(nt * nch, xgrad_splits(n)), block(256);
+  switch (nu2) {
+    case 0: hipLaunchKernelGGL((xgrad_kernel<T, 0>), grid, block, lds, s, X, n, d, np, P, Kinv, alpha, part, G, ticket); break;
+    case 1: hipLaunchKernelGGL((xgrad_kernel<T, 1>), grid, block, lds, s, X, n, d, np, P, Kinv, alpha, part, G, ticket); break;
+    case 3: hipLaunchKernelGGL((xgrad_kernel<T, 3>), grid, block, lds, s, X, n, d, np, P, Kinv, alpha, part, G, ticket); break;
+    default: hipLaunchKernelGGL((xgrad_kernel<T, 5>), grid, block, lds, s, X, n, d, np, P, Kinv, alpha, part, G, ticket); break;
+  }
+}
+template void launch_xgrad<double>(const double*, int, int, int, int, const EvalParams*, const double*, const double*, double*, double*,
+                                   int*, hipStream_t);
+template void launch_xgrad<float>(const float*, int, int, int, int, const EvalParams*, const float*, const float*, double*, double*, int*,
+                                  hipStream_t);
+
+template <typename T>
+__global__ void __launch_bounds__(256) warp_kernel(const T* __restrict__ X, size_t count, int d, const double* __restrict__ ab,
+                                                   T* __restrict__ U, double* __restrict__ dlna, double* __restrict__ dlnb) {
+  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= count) return;
+  const int k = (int)(e % (size_t)d);
+  double u, da, db;
+  warp::apply(ab[k], ab[d + k], (double)X[e], &u, &da, &db, nullptr);  // (always all three: a conditional pointer keeps them on the stack)
+  U[e] = (T)u;
+  if (dlna) dlna[e] = da;
+  if (dlnb) dlnb[e] = db;
+}
+template <typename T>
+void launch_warp(const T* X, int n, int d, const double* ab, T* U, double* dlna, double* dlnb, hipStream_t s) {
+  const size_t count = (size_t)n * d;
+  hipLaunchKernelGGL((warp_kernel<T>), dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, X, count, d, ab, U, dlna, dlnb);
+}
+template void launch_warp<double>(const double*, int, int, const double*, double*, double*, double*, hipStream_t);
+template void launch_warp<float>(const float*, int, int, const double*, float*, double*, double*, hipStream_t);
+
+// One workgroup; wave w takes the 2 d dot products q = w, w + 4, ...: lane l adds rows l, l + 64, ... in ascending order, then the
+// wave sum.  Fixed order.
+__global__ void __launch_bounds__(256) warp_chain_kernel(const double* __restrict__ G, const double* __restrict__ dlna,
+                                                         const double* __restrict__ dlnb, int n, int d, double* __restrict__ out) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int q = wave; q < 2 * d; q += 4) {
+    const int k = q < d ? q : q - d;
+    const double* __restrict__ D = q < d ? dlna : dlnb;
+    double a = 0;
+    for (int i = lane; i < n; i += 64) a += G[(size_t)i * d + k] * D[(size_t)i * d + k];
+    a = wave_sum(a);
+    if (lane == 0) out[q] = a;
+  }
+}
+void launch_warp_chain(const double* G, const double* dlna, const double* dlnb, int n, int d, double* out, hipStream_t s) {
+  hipLaunchKernelGGL(warp_chain_kernel, dim3(1), dim3(256), 0, s, G, dlna, dlnb, n, d, out);
+}
 
 // =================================================================================================================
 // Leave-one-out cross-validation in closed form (Rasmussen & Williams 5.4.2).  With M = K^-1, m_i = M_ii:
@@ -5600,6 +5828,12 @@ void init_kernels() {
         (const void*)&gradtrace_kernel<double, 0>, (const void*)&gradtrace_kernel<double, 1>, (const void*)&gradtrace_kernel<double, 3>, (const void*)&gradtrace_kernel<double, 5>,
         (const void*)&gradtrace_kernel<float, 0>, (const void*)&gradtrace_kernel<float, 1>, (const void*)&gradtrace_kernel<float, 3>, (const void*)&gradtrace_kernel<float, 5>};
     for (const void* fn : fns) set_lds_attr(fn, 2 * MAXD * 64 * 8, "kmat / gradtrace kernel: dynamic LDS limit");
+  }
+  {
+    const void* fns[] = {
+        (const void*)&xgrad_kernel<double, 0>, (const void*)&xgrad_kernel<double, 1>, (const void*)&xgrad_kernel<double, 3>, (const void*)&xgrad_kernel<double, 5>,
+        (const void*)&xgrad_kernel<float, 0>, (const void*)&xgrad_kernel<float, 1>, (const void*)&xgrad_kernel<float, 3>, (const void*)&xgrad_kernel<float, 5>};
+    for (const void* fn : fns) set_lds_attr(fn, 2 * MAXD * 64 * 8, "xgrad kernel: dynamic LDS limit");
   }
   set_lds_attr(reinterpret_cast<const void*>(&small_eval_kernel<double, 0>), lb, "small_eval_kernel: dynamic LDS limit");
   set_lds_attr(reinterpret_cast<const void*>(&small_eval_kernel<double, 1>), lb, "small_eval_kernel: dynamic LDS limit");

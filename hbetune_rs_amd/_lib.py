@@ -236,6 +236,18 @@ SIGNATURES = {
     "hbegp_extend_from_rv_f64": (C.c_int, [_vp, _vp, _dp, _dp, _dp, C.c_int, C.POINTER(_vp), _ip]),
     "hbegp_extend_from_rv_f32": (C.c_int, [_vp, _vp, _fp, _fp, _dp, C.c_int, C.POINTER(_vp), _ip]),
     "hbegp_model_row_variance": (C.c_int, [_vp, _dp]),
+    # input warping: ab = [a_1..a_d, b_1..b_d]
+    "hbegp_warp_apply": (C.c_int, [_dp, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp]),
+    "hbegp_warp_invert": (C.c_int, [_dp, C.c_int, _dp, C.c_int, _dp]),
+    "hbegp_problem_eval_xgrad": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "hbegp_problem_eval_warped": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "hbegp_fit_warped_f64": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int, C.c_int, C.c_double, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.c_int,
+                                       C.POINTER(FitOptions), _dp, _dp, _dp, C.POINTER(_vp)]),
+    "hbegp_fit_warped_f32": (C.c_int, [_vp, _fp, _fp, _dp, C.c_int, C.c_int, C.c_double, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.c_int,
+                                       C.POINTER(FitOptions), _dp, _dp, _dp, C.POINTER(_vp)]),
+    "hbegp_model_warp": (C.c_int, [_vp, _dp]),
+    "hbegp_problem_debug_rows_f64": (C.c_int, [_vp, C.c_int, _dp]),
+    "hbegp_problem_debug_rows_f32": (C.c_int, [_vp, C.c_int, _fp]),
 }
 
 _lib = None

@@ -1389,6 +1389,7 @@ class EstimatorGPR:
         self._y_projection = "linear"
         self._known_optimum = None
         self._objective = "lml"
+        self._input_warping = False
         self.ctx = ctx
 
     @staticmethod
@@ -1434,6 +1435,15 @@ class EstimatorGPR:
         self._objective = name
         return self
 
+    def input_warping(self, on=True, bounds=(0.2, 5.0)):
+        """Opt-in (off by default, not in the reference): `estimate` learns one Kumaraswamy warp of [0, 1] per feature jointly with
+        the kernel parameters (FittedKernel.new_warped; features must lie in [0, 1]; objective "lml" only).  The model's `fitted`
+        is then a gpr.WarpedKernel: a plain fit first, the warped fit from its optimum, so the lml is no worse than without.
+        bounds: the box of every a_k and b_k."""
+        self._input_warping = bool(on)
+        self._warp_bounds = (float(bounds[0]), float(bounds[1]))
+        return self
+
     def _theta_and_bounds(self, prior, y_train):  # get_kernel_or_default gpr.rs:402-427
         if prior is not None:
             lo = np.array([prior.noise_bounds[0], prior.amplitude_bounds[0]] + [b[0] for b in prior.length_scale_bounds])
@@ -1469,6 +1479,12 @@ class EstimatorGPR:
         # the estimator's own nu only configures the default kernel
         nu = prior.fitted.nu if prior is not None else self._matern_nu
         fit = gpr.FittedKernel.new_by_loo if self._objective == "loo" else gpr.FittedKernel.new
+        if self._input_warping:
+            if self._objective != "lml":
+                raise NotImplementedError("input warping is built for the lml objective only")
+
+            def fit(*args, **kw):
+                return gpr.FittedKernel.new_warped(*args, warp_bounds=self._warp_bounds, **kw)
         if self._objective == "lgo":
             def fit(*args, **kw):
                 return gpr.FittedKernel.new_by_lgo(*args, groups=groups, **kw)
@@ -1487,7 +1503,11 @@ class EstimatorGPR:
         row_variance = None if y_variance is None else y_norm.project_variance_into_normalized(y, y_variance)
         lo = np.array([prior.noise_bounds[0], prior.amplitude_bounds[0]] + [b[0] for b in prior.length_scale_bounds])
         hi = np.array([prior.noise_bounds[1], prior.amplitude_bounds[1]] + [b[1] for b in prior.length_scale_bounds])
-        if row_variance is not None:
+        if isinstance(prior.fitted, gpr.WarpedKernel):
+            # the warp is the prior's, fixed: the new rows go through it (incrementally where the leading rows are the prior's)
+            ext = prior.fitted.extend_with if prior.fitted.dtype == x.dtype else prior.fitted.extend
+            fitted = ext(x, y_train.astype(x.dtype), ctx=self.ctx, row_variance=row_variance)
+        elif row_variance is not None:
             if prior.fitted.dtype == x.dtype:
                 fitted = prior.fitted.extend_with(x, y_train.astype(x.dtype), ctx=self.ctx, row_variance=row_variance)
             else:

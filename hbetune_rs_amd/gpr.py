@@ -88,6 +88,63 @@ def _iptr(a):
     return None if a is None else a.ctypes.data_as(C.POINTER(C.c_int))
 
 
+class Warp:
+    """The Kumaraswamy input warp u_k = 1 - (1 - x_k^a_k)^b_k of features in [0, 1] (hbegp_warp_apply / _invert: host fp64, no
+    GPU).  ab = [a_1..a_d, b_1..b_d], all > 0; a = b = 1 is the identity."""
+
+    def __init__(self, ab):
+        self.ab = _lib.as_c(np.asarray(ab, dtype=np.float64).reshape(-1), np.float64)
+        if self.ab.size < 2 or self.ab.size % 2:
+            raise ValueError(f"a warp takes 2 d parameters [a_1..a_d, b_1..b_d], got {self.ab.size}")
+        self.d = self.ab.size // 2
+        if not (np.all(np.isfinite(self.ab)) and np.all(self.ab > 0)):
+            raise ValueError("warp parameters must be finite and positive")
+
+    @staticmethod
+    def identity(d):
+        return Warp(np.ones(2 * d))
+
+    @property
+    def a(self):
+        return self.ab[:self.d]
+
+    @property
+    def b(self):
+        return self.ab[self.d:]
+
+    def _rows(self, x):
+        x = np.asarray(x)
+        rows = _lib.as_c(x.reshape(-1, self.d), np.float64)
+        return x, rows
+
+    def apply(self, x, want_param_gradients=False):
+        """u = w(x) in fp64, shaped like x ([..., d]); with want_param_gradients also du/dln a and du/dln b."""
+        x, rows = self._rows(x)
+        u = np.empty_like(rows)
+        da = np.empty_like(rows) if want_param_gradients else None
+        db = np.empty_like(rows) if want_param_gradients else None
+        _lib.check(_lib.load().hbegp_warp_apply(_lib.dptr(self.ab), self.d, _lib.dptr(rows), rows.shape[0], _lib.dptr(u), _lib.dptr(da),
+                                                _lib.dptr(db), None))
+        if want_param_gradients:
+            return u.reshape(x.shape), da.reshape(x.shape), db.reshape(x.shape)
+        return u.reshape(x.shape)
+
+    def invert(self, u):
+        """x with w(x) = u, shaped like u."""
+        u, rows = self._rows(u)
+        x = np.empty_like(rows)
+        _lib.check(_lib.load().hbegp_warp_invert(_lib.dptr(self.ab), self.d, _lib.dptr(rows), rows.shape[0], _lib.dptr(x)))
+        return x.reshape(u.shape)
+
+    def jacobian(self, x):
+        """du_k/dx_k, shaped like x (the map is per coordinate: the Jacobian is diagonal).  +inf at an end whose exponent is < 1."""
+        x, rows = self._rows(x)
+        dx = np.empty_like(rows)
+        _lib.check(_lib.load().hbegp_warp_apply(_lib.dptr(self.ab), self.d, _lib.dptr(rows), rows.shape[0], None, None, None,
+                                                _lib.dptr(dx)))
+        return dx.reshape(x.shape)
+
+
 class Problem:
     """X, y resident on the device; repeated lml/gradient evaluations (the optimiser's inner loop)."""
 
@@ -168,6 +225,47 @@ class Problem:
         if _lib.check(code, allow=(NOT_PD,)) == NOT_PD:
             return None
         return lgo.value, grad
+
+    def lml_with_x_gradient(self, theta, lo=None, hi=None, want_grad=True, dev=0, slot=0):
+        """lml_with_gradient plus gx [n, d] = d lml / d x_train in fp64 (hbegp_problem_eval_xgrad): the slot's evaluation, then
+        the input-gradient tail on its results.  Returns (lml, grad, gx) or None when not PD."""
+        lib = _lib.load()
+        theta = _lib.as_c(theta, np.float64)
+        lo = None if lo is None else _lib.as_c(lo, np.float64)
+        hi = None if hi is None else _lib.as_c(hi, np.float64)
+        lml = C.c_double()
+        grad = np.zeros(self.p) if want_grad else None
+        gx = np.zeros((self.n, self.d))
+        code = lib.hbegp_problem_eval_xgrad(self._h, dev, slot, _lib.dptr(theta), _lib.dptr(lo), _lib.dptr(hi), C.byref(lml),
+                                            _lib.dptr(grad), _lib.dptr(gx))
+        if _lib.check(code, allow=(NOT_PD,)) == NOT_PD:
+            return None
+        return lml.value, grad, gx
+
+    def warped_lml_with_gradient(self, theta, warp, lo=None, hi=None, want_grad=True, dev=0, slot=0):
+        """lml(w(x_train; a, b), theta) and its gradient [p + 2 d]: theta's entries, then d/dln a_k, then d/dln b_k
+        (hbegp_problem_eval_warped; single-slot problems with features in [0, 1] only).  `warp` is a Warp or its 2 d parameters.
+        Returns (lml, grad) or None when not PD."""
+        lib = _lib.load()
+        ab = warp.ab if isinstance(warp, Warp) else _lib.as_c(np.asarray(warp, dtype=np.float64).reshape(-1), np.float64)
+        if ab.shape != (2 * self.d,):
+            raise ValueError(f"the warp must have 2 d = {2 * self.d} parameters, got {ab.shape}")
+        theta = _lib.as_c(theta, np.float64)
+        lo = None if lo is None else _lib.as_c(lo, np.float64)
+        hi = None if hi is None else _lib.as_c(hi, np.float64)
+        lml = C.c_double()
+        grad = np.zeros(self.p + 2 * self.d) if want_grad else None
+        code = lib.hbegp_problem_eval_warped(self._h, dev, slot, _lib.dptr(theta), _lib.dptr(lo), _lib.dptr(hi), _lib.dptr(ab),
+                                             C.byref(lml), _lib.dptr(grad))
+        if _lib.check(code, allow=(NOT_PD,)) == NOT_PD:
+            return None
+        return lml.value, grad
+
+    def debug_rows(self, dev=0):
+        """The rows [n, d] the device's feature buffer holds at the moment (hbegp_problem_debug_rows_*)."""
+        out = np.zeros((self.n, self.d), dtype=self.dtype)
+        _lib.check(getattr(_lib.load(), f"hbegp_problem_debug_rows_{self._sfx}")(self._h, dev, _lib.aptr(out)))
+        return out
 
     def results(self, want_kinv=True, dev=0, slot=0):
         """(alpha, k_inv, diag(L)) of the most recent evaluation."""
@@ -372,6 +470,88 @@ class FittedKernel:
             if trace != "lml":
                 fk.trace["grad"] = tr["grad"][:k]
         return fk
+
+    @staticmethod
+    def new_warped(x_train, y_train, theta0, lo, hi, starts=None, nu=2.5, ctx=None, maxeval=150, fixed_work=False, trace=False,
+                   row_variance=None, warp_bounds=(0.2, 5.0), warp_starts=None, plain=None):
+        """`new` with one Kumaraswamy input warp per feature learned jointly with theta (hbegp_fit_warped_*; features in [0, 1]).
+
+        A plain `new` runs first (or `plain`, a FittedKernel from the same arguments, is taken); run 0 of the warped fit starts at
+        its optimum with the identity warp, so the result's lml is no worse than the plain fit's.  starts: [R, p] as for `new`; each
+        also starts a warped run, from warp_starts[r] ([R, 2 d], ln a then ln b; default: the identity).  The runs go one after
+        another on one slot.  Returns a WarpedKernel: `.inner` the u-space FittedKernel, `.warp` the learned Warp, `.plain_lml`
+        the plain fit's lml.  With trace: `.trace` rows hold the p + 2 d log-space variables."""
+        lib = _lib.load()
+        ctx = ctx or default_context()
+        dtype = np.dtype(x_train.dtype)
+        sfx = _suffix(dtype)
+        x = _lib.as_c(x_train, dtype)
+        y = _lib.as_c(y_train, dtype)
+        n, d = x.shape
+        p, q = d + 2, 3 * d + 2
+        lo = _lib.as_c(lo, np.float64)
+        hi = _lib.as_c(hi, np.float64)
+        own_plain = plain is None
+        if own_plain:
+            plain = FittedKernel.new(x, y, theta0, lo, hi, starts=starts, nu=nu, ctx=ctx, maxeval=maxeval, fixed_work=fixed_work,
+                                     row_variance=row_variance)
+        plain_lml, plain_theta = plain.lml, plain.theta.copy()
+        if own_plain:
+            plain.release()
+        n_restarts = 0 if starts is None else len(starts)
+        starts_c = None
+        if n_restarts:
+            ws = np.zeros((n_restarts, 2 * d)) if warp_starts is None else np.asarray(warp_starts, dtype=np.float64).reshape(n_restarts, 2 * d)
+            starts_c = _lib.as_c(np.concatenate([np.asarray(starts, dtype=np.float64).reshape(n_restarts, p), ws], axis=1), np.float64)
+        ab_lo = _lib.as_c(np.broadcast_to(np.asarray(warp_bounds[0], dtype=np.float64), (2 * d,)), np.float64)
+        ab_hi = _lib.as_c(np.broadcast_to(np.asarray(warp_bounds[1], dtype=np.float64), (2 * d,)), np.float64)
+        opt = _lib.FitOptions()
+        opt.maxeval = maxeval
+        opt.fixed_work = 1 if fixed_work else 0
+        n_evals, n_not_pd = C.c_int(0), C.c_int(0)
+        opt.n_evals = C.pointer(n_evals)
+        opt.n_not_pd = C.pointer(n_not_pd)
+        tr = None
+        if trace:
+            cap = (1 + n_restarts) * maxeval
+            tr = dict(theta=np.zeros((cap, q)), lml=np.zeros(cap), grad=np.zeros((cap, q)), run=np.zeros(cap, dtype=np.int32),
+                      count=C.c_int(0))
+            opt.trace_cap = cap
+            opt.trace_theta = _lib.dptr(tr["theta"])
+            opt.trace_lml = _lib.dptr(tr["lml"])
+            opt.trace_grad = _lib.dptr(tr["grad"])
+            opt.trace_run = tr["run"].ctypes.data_as(C.POINTER(C.c_int))
+            opt.trace_count = C.pointer(tr["count"])
+        handle = C.c_void_p()
+        theta_best, ab_best, lml_best = np.zeros(p), np.zeros(2 * d), C.c_double()
+        rv = _row_variance(row_variance, n)
+        theta_start = _lib.as_c(plain_theta, np.float64)
+        _lib.check(getattr(lib, f"hbegp_fit_warped_{sfx}")(
+            ctx._h, _lib.aptr(x), _lib.aptr(y), _lib.dptr(rv), n, d, float(nu), _lib.dptr(theta_start), _lib.dptr(lo), _lib.dptr(hi), None,
+            _lib.dptr(ab_lo), _lib.dptr(ab_hi), _lib.dptr(starts_c), n_restarts, C.byref(opt), _lib.dptr(theta_best), _lib.dptr(ab_best),
+            C.byref(lml_best), C.byref(handle)))
+        inner = FittedKernel(handle, dtype, n, d, nu)
+        warp = Warp(ab_best)
+        inner.x_train, inner.y_train = warp.apply(x.astype(np.float64)).astype(dtype), y
+        inner.n_evals, inner.n_not_pd = n_evals.value, n_not_pd.value
+        inner.theta_best = theta_best
+        wk = WarpedKernel(inner, warp)
+        wk.x_train, wk.lml_best, wk.plain_lml, wk.plain_theta = x, lml_best.value, plain_lml, plain_theta
+        if trace:
+            k = tr["count"].value
+            wk.trace = dict(theta=tr["theta"][:k], lml=tr["lml"][:k], grad=tr["grad"][:k], run=tr["run"][:k])
+        return wk
+
+    @property
+    def warp_parameters(self):
+        """[a_1..a_d, b_1..b_d] of the input warp a model from hbegp_fit_warped_* carries (hbegp_model_warp); None for every other
+        model."""
+        lib = _lib.load()
+        if lib.hbegp_model_warp(self._h, None) != 1:
+            return None
+        ab = np.zeros(2 * self.d)
+        lib.hbegp_model_warp(self._h, _lib.dptr(ab))
+        return ab
 
     @staticmethod
     def extend(x_train, y_train, theta, lo=None, hi=None, nu=2.5, ctx=None, row_variance=None):
@@ -814,6 +994,115 @@ class FittedKernel:
             self.release()
         except Exception:
             pass
+
+
+class WarpedKernel:
+    """A model behind a fixed input warp: `.inner` is a FittedKernel on the warped rows u = w(x) (u-space), `.warp` the Warp.  The
+    methods below take and return points in x-space; anything else the inner model offers is reached through `.inner` with
+    `.warp.apply(x)` rows (gradients it returns are with respect to u: multiply by `.warp.jacobian(x)`)."""
+
+    def __init__(self, inner, warp):
+        assert warp.d == inner.d
+        self.inner, self.warp = inner, warp
+        self.dtype, self.n, self.d, self.nu = inner.dtype, inner.n, inner.d, inner.nu
+        self.x_train = None
+
+    lml = property(lambda self: self.inner.lml)
+    theta = property(lambda self: self.inner.theta)
+    noise = property(lambda self: self.inner.noise)
+    amplitude = property(lambda self: self.inner.amplitude)
+    length_scale = property(lambda self: self.inner.length_scale)
+    y_train = property(lambda self: self.inner.y_train)
+    row_variance = property(lambda self: self.inner.row_variance)
+
+    def _u(self, x, dtype=None):
+        """The warped rows in the model's element type: hbegp_warp_apply in fp64, rounded once."""
+        return self.warp.apply(np.asarray(x, dtype=np.float64).reshape(-1, self.d)).astype(dtype or self.dtype)
+
+    def _x(self, u):
+        return self.warp.invert(np.asarray(u, dtype=np.float64)).astype(self.dtype)
+
+    def predict(self, x, want_variance=True):
+        return self.inner.predict(self._u(x), want_variance)
+
+    def predict_with_gradient(self, x, want_variance=True):
+        """inner.predict_with_gradient at w(x), the gradients multiplied by du/dx: with respect to x.  Where du/dx is infinite (an
+        end of [0, 1] whose exponent is below 1) so is the gradient, unless the u-gradient is 0 there (then NaN)."""
+        mean, var, dmean, dvar, n_warn = self.inner.predict_with_gradient(self._u(x), want_variance)
+        jac = self.warp.jacobian(np.asarray(x, dtype=np.float64).reshape(-1, self.d))
+        dmean = (dmean * jac).astype(self.dtype)
+        if dvar is not None:
+            dvar = (dvar * jac).astype(self.dtype)
+        return mean, var, dmean, dvar, n_warn
+
+    def predict_cov(self, x, jitter=0.0):
+        return self.inner.predict_cov(self._u(x), jitter)
+
+    def sample_posterior(self, x, z, jitter=0.0, want_samples=True):
+        return self.inner.sample_posterior(self._u(x), z, jitter, want_samples)
+
+    def select_batch(self, x, k, fmin_normalized, lie=None):
+        return self.inner.select_batch(self._u(x), k, fmin_normalized, lie)
+
+    def confidence_bound(self, x, kappa, want_grad=False, want_posterior=False):
+        out = self.inner.confidence_bound(self._u(x), kappa, want_grad, want_posterior)
+        if want_grad:
+            jac = self.warp.jacobian(np.asarray(x, dtype=np.float64).reshape(-1, self.d))
+            out = out[:2] + ((out[2] * jac).astype(self.dtype),) + out[3:]
+        return out
+
+    def _box(self, lo, hi):
+        """A monotone map per coordinate sends boxes to boxes: the corners' images."""
+        lo = np.asarray(lo, dtype=np.float64).reshape(1, self.d)
+        hi = np.asarray(hi, dtype=np.float64).reshape(1, self.d)
+        return self.warp.apply(lo)[0], self.warp.apply(hi)[0]
+
+    def _maximise(self, method, starts, lo, hi, *args, **kw):
+        ulo, uhi = self._box(lo, hi)
+        # (the starts in the element type, clipped into the image box: rounding may put a warped start a last place outside it)
+        ustarts = np.clip(self._u(np.atleast_2d(starts)), ulo.astype(self.dtype), uhi.astype(self.dtype))
+        ulo, uhi = np.minimum(ulo, ustarts.min(axis=0)), np.maximum(uhi, ustarts.max(axis=0))
+        u, val, nevals = method(ustarts, ulo, uhi, *args, **kw)
+        x = np.clip(self._x(u), np.asarray(lo, dtype=self.dtype), np.asarray(hi, dtype=self.dtype))
+        return x, val, nevals
+
+    def maximize_ei(self, starts, lo, hi, fmin_normalized, maxeval=150):
+        """inner.maximize_ei over the image of the box, from the warped starts; the points come back through the inverse warp
+        (inside [lo, hi]), the values are the u-space maximiser's."""
+        return self._maximise(self.inner.maximize_ei, starts, lo, hi, fmin_normalized, maxeval=maxeval)
+
+    def maximize_log_ei(self, starts, lo, hi, fmin_normalized, maxeval=150):
+        return self._maximise(self.inner.maximize_log_ei, starts, lo, hi, fmin_normalized, maxeval=maxeval)
+
+    def minimize_confidence_bound(self, starts, lo, hi, kappa, maxeval=150):
+        return self._maximise(self.inner.minimize_confidence_bound, starts, lo, hi, kappa, maxeval=maxeval)
+
+    def extend_with(self, x_train, y_train, ctx=None, row_variance=None):
+        """inner.extend_with on the rows warped by the fixed warp (the leading rows are this model's: the same function gives the
+        same bits, so the incremental path applies)."""
+        wk = WarpedKernel(self.inner.extend_with(self._u(x_train), y_train, ctx=ctx, row_variance=row_variance), self.warp)
+        wk.x_train = _lib.as_c(x_train, self.dtype)
+        return wk
+
+    def extend(self, x_train, y_train, ctx=None, row_variance=None):
+        """FittedKernel.extend at this model's theta on the rows warped by the fixed warp (the full path)."""
+        dtype = np.dtype(np.asarray(x_train).dtype)  # (the new rows' element type: a model may change it, as FittedKernel.extend allows)
+        inner = FittedKernel.extend(self._u(x_train, dtype), _lib.as_c(y_train, dtype), self.inner.theta, nu=self.nu, ctx=ctx,
+                                    row_variance=row_variance)
+        wk = WarpedKernel(inner, self.warp)
+        wk.x_train = _lib.as_c(x_train, dtype)
+        return wk
+
+    def release(self):
+        self.inner.release()
+
+    def __getattr__(self, name):
+        if name.startswith("_") or name in ("inner", "warp"):
+            raise AttributeError(name)
+        if hasattr(FittedKernel, name):
+            raise NotImplementedError(f"WarpedKernel.{name} is not wrapped: call .inner.{name} in u-space with .warp.apply(x) rows "
+                                      "(its gradients are with respect to u; .warp.jacobian(x) is du/dx)")
+        raise AttributeError(name)
 
 
 class PosteriorPaths:

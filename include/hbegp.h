@@ -124,6 +124,41 @@ int hbegp_problem_eval_loo(hbegp_problem* prob, int dev, int slot, const double*
 int hbegp_problem_eval_lgo(hbegp_problem* prob, int dev, int slot, const double* theta, const double* lo, const double* hi,
                            const int* group, double* lgo, double* grad);
 
+/* ---- input warping -----------------------------------------------------------------------------------
+ * The Kumaraswamy warp of feature k, u = 1 - (1 - x^a_k)^b_k, maps [0, 1] onto itself monotonically (a = b = 1: the identity).
+ * ab = [a_1..a_d, b_1..b_d] in linear space.  Pure host fp64, no context: U[m*d] = the warped rows, dU_dlna / dU_dlnb = du/dln a,
+ * du/dln b, dU_dx = du/dx, each [m*d] and each may be NULL.  At x = 0 and x = 1: u is exactly 0 / 1 and both parameter derivatives
+ * are exactly 0 (the limits); du/dx = a b x^(a-1) (1 - x^a)^(b-1) is +inf at an end whose exponent (a at 0, b at 1) is below 1.
+ * hbegp_warp_invert is the closed-form inverse x = (1 - (1 - u)^(1/b))^(1/a).  HBEGP_EINVAL for a parameter that is not finite and
+ * positive and for an input outside [0, 1] (NaN included); nothing is written then.  The device (hbegp_problem_eval_warped) warps
+ * with the same function: the rows it evaluates are bit for bit hbegp_warp_apply's U rounded once to the element type. */
+int hbegp_warp_apply(const double* ab, int d, const double* X, int m, double* U, double* dU_dlna, double* dU_dlnb, double* dU_dx);
+int hbegp_warp_invert(const double* ab, int d, const double* U, int m, double* X);
+
+/* hbegp_problem_eval plus the gradient of the lml with respect to the training inputs: gx[n*d], row-major,
+ *   gx[i][k] = d lml / d x_ik = sum_j (alpha alpha^T - K^-1)_ij c psi(r_ij) (x_ik - x_jk) / ell_k^2,  psi = phi'(r) / r,
+ * always fp64, at the clamped parameters the evaluation ran with.  Terms with r = 0 (the diagonal, duplicate rows) contribute 0, as
+ * in hbegp_predict_grad_*; neither the noise nor known row variances enter.  The slot's normal evaluation (lml, and grad[p] when
+ * it is not NULL: the bits hbegp_problem_eval returns), then the tail on the slot's stream.  Clamping, HBEGP_NOT_PD (lml = -inf,
+ * grad and gx zero), the state the slot is left in, the evaluation paths and element types covered and the threading contract are
+ * hbegp_problem_eval_loo's.  The same call gives the same bits. */
+int hbegp_problem_eval_xgrad(hbegp_problem* prob, int dev, int slot, const double* theta, const double* lo, const double* hi,
+                             double* lml, double* grad, double* gx);
+
+/* The warped objective lml(w(X; a, b), theta) and its gradient grad[p + 2d] (may be NULL: skips the gradient and the tail): the p
+ * entries of hbegp_problem_eval at the warped rows, then d lml / d ln a_k and d lml / d ln b_k.  Only for a problem created with
+ * n_slots == 1 whose features lie in [0, 1] (checked on first use): the call rewrites the device's feature buffer, which a
+ * problem's slots share -- HBEGP_EINVAL otherwise, with a message that says so.  On first use the problem keeps the caller's rows
+ * in a second buffer; every call warps them into the feature buffer, evaluates, runs the hbegp_problem_eval_xgrad tail and the chain
+ * rule, and copies the caller's rows back, all ordered on the slot's stream: a later hbegp_problem_eval returns the bits it returned
+ * before.  HBEGP_NOT_PD: lml = -inf, grad zero.  hbegp_problem_debug_rows_* copies out the rows [n*d] the device's feature buffer
+ * holds at the moment (tests; with HBEGP_WARP_DEBUG_KEEP=1 in the environment a call leaves the warped rows there instead of the
+ * caller's, and the next call without it puts the caller's back). */
+int hbegp_problem_eval_warped(hbegp_problem* prob, int dev, int slot, const double* theta, const double* lo, const double* hi,
+                              const double* ab, double* lml, double* grad);
+int hbegp_problem_debug_rows_f64(hbegp_problem* prob, int dev, double* out);
+int hbegp_problem_debug_rows_f32(hbegp_problem* prob, int dev, float* out);
+
 /* Copy out device results of the most recent successful evaluation on (dev, slot); any pointer may be NULL.
  * alpha[n]; kinv[n*n] full symmetric row-major (what invc() returns, lml.rs:62); ldiag[n] = diag(L). */
 int hbegp_problem_get_f64(hbegp_problem* prob, int dev, int slot, double* alpha, double* kinv, double* ldiag);
@@ -318,6 +353,31 @@ int hbegp_extend_from_rv_f32(hbegp_ctx* ctx, hbegp_model* prior, const float* X,
 /* 1 and, with rv != NULL, the n variances the model works with (for an f32 model the rounded values, widened); 0 for a model
  * without them (rv is not written). */
 int hbegp_model_row_variance(const hbegp_model* model, double* rv);
+
+/* The warped fit: theta and one warp per feature learned jointly.  A host-driven bounded L-BFGS over the p + 2d log-space
+ * variables [theta, ln a_1..ln a_d, ln b_1..ln b_d] with hbegp_problem_eval_warped's value and gradient, on ONE single-slot problem
+ * with a fit's path selection, 1 + n_restarts runs ONE AFTER ANOTHER.  Run 0 starts at (theta0, ab0), ab0 NULL = the identity: with
+ * a plain fit's optimum as theta0 the result is no worse than the plain fit.  starts[n_restarts * (p + 2d)] in log space; rv (may
+ * be NULL) as in hbegp_fit_rv_*; ab_lo / ab_hi [2d] (each may be NULL = 0.2 / 5 throughout) bound a and b as lo / hi bound theta.
+ * maxeval, fixed_work, lbfgs_memory and the trace come from opt (rows of trace_theta / trace_grad have p + 2d entries here; the
+ * other statistics of hbegp_last_fit_stats are not kept).  Capture as in hbegp_fit_*: the best lml wins, ties go to the lowest (run,
+ * evaluation); an HBEGP_NOT_PD evaluation counts as +inf with a zero gradient; HBEGP_ALL_FAILED when every evaluation failed.
+ * theta_best[p] (clamped, log space), ab_best[2d] (linear space, inside its bounds), *lml_best.  *model (may be NULL) is, bit for
+ * bit, hbegp_extend_* (hbegp_extend_rv_* with rv) at theta_best on the rows hbegp_warp_apply gives for ab_best, rounded once to the
+ * element type; it carries ab_best: hbegp_model_warp returns 1 and fills ab[2d] (may be NULL) for such a model, 0 for every other
+ * model.  All posterior entry points take a warped model as they take any model: they work in u-space, so their query points are
+ * warped rows and the gradients they return are with respect to u (multiply by hbegp_warp_apply's dU_dx for x).  HBEGP_EINVAL for
+ * features outside [0, 1] and for warp bounds or ab0 that are not finite and positive.  Not built here: runs side by side (they
+ * need a feature buffer per slot), the device-driven fit of at most 128 rows, leave-one-out / leave-group-out objectives. */
+int hbegp_fit_warped_f64(hbegp_ctx* ctx, const double* X, const double* y, const double* rv, int n, int d, double nu,
+                         const double* theta0, const double* lo, const double* hi, const double* ab0, const double* ab_lo,
+                         const double* ab_hi, const double* starts, int n_restarts, const hbegp_fit_options* opt,
+                         double* theta_best, double* ab_best, double* lml_best, hbegp_model** model);
+int hbegp_fit_warped_f32(hbegp_ctx* ctx, const float* X, const float* y, const double* rv, int n, int d, double nu,
+                         const double* theta0, const double* lo, const double* hi, const double* ab0, const double* ab_lo,
+                         const double* ab_hi, const double* starts, int n_restarts, const hbegp_fit_options* opt,
+                         double* theta_best, double* ab_best, double* lml_best, hbegp_model** model);
+int hbegp_model_warp(const hbegp_model* model, double* ab);
 
 /* ---- model: mirrors predict() (predict.rs:7-52) and the FittedKernel fields -------------------------- */
 /* mean[m]; var[m] or NULL.  var = c + 1e-5 - rowsum((K* K^-1) o K*), negatives clamped to 0 (predict.rs:25-48);

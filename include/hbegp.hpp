@@ -58,6 +58,12 @@ template <> struct Abi<double> {
   static int extend_rv(hbegp_ctx* c, const double* x, const double* y, const double* rv, int n, int d, double nu, const double* t, const double* lo,
                        const double* hi, hbegp_model** m) { return hbegp_extend_rv_f64(c, x, y, rv, n, d, nu, t, lo, hi, m); }
   static int extend_from_rv(hbegp_ctx* c, hbegp_model* p, const double* x, const double* y, const double* rv, int n, hbegp_model** m, int* inc) { return hbegp_extend_from_rv_f64(c, p, x, y, rv, n, m, inc); }
+  // the warped fit (hbegp.h: input warping); rv, ab0, ab_lo, ab_hi may be nullptr
+  static int fit_warped(hbegp_ctx* c, const double* x, const double* y, const double* rv, int n, int d, double nu, const double* t0,
+                        const double* lo, const double* hi, const double* ab0, const double* alo, const double* ahi, const double* st, int r,
+                        const hbegp_fit_options* o, double* tb, double* ab, double* lb, hbegp_model** m) {
+    return hbegp_fit_warped_f64(c, x, y, rv, n, d, nu, t0, lo, hi, ab0, alo, ahi, st, r, o, tb, ab, lb, m);
+  }
   static int predict(hbegp_model* m, const double* xs, int k, double* mean, double* var, int* w) { return hbegp_predict_f64(m, xs, k, mean, var, w); }
   static int predict_grad(hbegp_model* m, const double* xs, int k, double* mean, double* var, double* dm, double* dv, int* w) {
     return hbegp_predict_grad_f64(m, xs, k, mean, var, dm, dv, w);
@@ -156,6 +162,11 @@ template <> struct Abi<float> {
   static int extend_rv(hbegp_ctx* c, const float* x, const float* y, const double* rv, int n, int d, double nu, const double* t, const double* lo,
                        const double* hi, hbegp_model** m) { return hbegp_extend_rv_f32(c, x, y, rv, n, d, nu, t, lo, hi, m); }
   static int extend_from_rv(hbegp_ctx* c, hbegp_model* p, const float* x, const float* y, const double* rv, int n, hbegp_model** m, int* inc) { return hbegp_extend_from_rv_f32(c, p, x, y, rv, n, m, inc); }
+  static int fit_warped(hbegp_ctx* c, const float* x, const float* y, const double* rv, int n, int d, double nu, const double* t0,
+                        const double* lo, const double* hi, const double* ab0, const double* alo, const double* ahi, const double* st, int r,
+                        const hbegp_fit_options* o, double* tb, double* ab, double* lb, hbegp_model** m) {
+    return hbegp_fit_warped_f32(c, x, y, rv, n, d, nu, t0, lo, hi, ab0, alo, ahi, st, r, o, tb, ab, lb, m);
+  }
   static int predict(hbegp_model* m, const float* xs, int k, float* mean, float* var, int* w) { return hbegp_predict_f32(m, xs, k, mean, var, w); }
   static int predict_grad(hbegp_model* m, const float* xs, int k, float* mean, float* var, float* dm, float* dv, int* w) {
     return hbegp_predict_grad_f32(m, xs, k, mean, var, dm, dv, w);
@@ -241,6 +252,34 @@ template <> struct Abi<float> {
 }  // namespace detail
 
 // Kernel = ConstantKernel(amplitude) * Matern(nu, length_scale) + noise (gpr.rs:51); bounds in linear space.
+// The Kumaraswamy input warp u_k = 1 - (1 - x_k^a_k)^b_k of features in [0, 1] (hbegp_warp_apply / _invert: host fp64, no GPU).
+// ab = [a_1..a_d, b_1..b_d].  Rows are m x d, row-major.
+struct Warp {
+  std::vector<double> ab;
+  int d() const { return (int)(ab.size() / 2); }
+  static Warp identity(int d) { return Warp{std::vector<double>(2 * (size_t)d, 1.0)}; }
+  std::vector<double> apply(const double* x, int m) const {
+    std::vector<double> u((size_t)m * d());
+    check(hbegp_warp_apply(ab.data(), d(), x, m, u.data(), nullptr, nullptr, nullptr));
+    return u;
+  }
+  // du/dln a and du/dln b next to u (each may be nullptr)
+  void apply(const double* x, int m, double* u, double* du_dlna, double* du_dlnb) const {
+    check(hbegp_warp_apply(ab.data(), d(), x, m, u, du_dlna, du_dlnb, nullptr));
+  }
+  std::vector<double> invert(const double* u, int m) const {
+    std::vector<double> x((size_t)m * d());
+    check(hbegp_warp_invert(ab.data(), d(), u, m, x.data()));
+    return x;
+  }
+  // du_k/dx_k (the map is per coordinate); +inf at an end of [0, 1] whose exponent is below 1
+  std::vector<double> jacobian(const double* x, int m) const {
+    std::vector<double> j((size_t)m * d());
+    check(hbegp_warp_apply(ab.data(), d(), x, m, nullptr, nullptr, nullptr, j.data()));
+    return j;
+  }
+};
+
 struct KernelBounds {
   std::vector<double> lo, hi;  // order [noise, amplitude, ell_1..ell_d]
 };
@@ -276,6 +315,34 @@ class FittedKernel {
                        : detail::Abi<A>::fit(ctx.get(), x, y, n, d, nu, theta0.data(), b.lo.data(), b.hi.data(), st, nr, &opt, fk.theta_.data(),
                                              &fk.lml_, &fk.h_));
     return fk;
+  }
+  // `new_` with one input warp per feature learned jointly with theta (hbegp_fit_warped_*; features in [0, 1]).  Run 0 starts at
+  // (theta0, the identity): hand in a plain fit's theta() and the result's lml is no worse than that fit's.  starts: n_restarts *
+  // (p + 2 d) log-space start points [theta, ln a, ln b].  The model works in u-space: query it with warp().apply(x) rows; the
+  // gradients it returns are with respect to u (multiply by warp().jacobian(x)).
+  static FittedKernel new_warped(const Context& ctx, const A* x, const A* y, int n, int d, double nu, const std::vector<double>& theta0,
+                                 const KernelBounds& b, const std::vector<double>& starts, int maxeval = 150,
+                                 const double* row_variance = nullptr, double warp_lo = 0.2, double warp_hi = 5.0) {
+    const int p = d + 2, q = p + 2 * d;
+    if ((int)theta0.size() != p || (int)b.lo.size() != p || (int)b.hi.size() != p || starts.size() % q != 0)
+      throw Error(HBEGP_EINVAL, "theta0 / bounds / starts have the wrong length");
+    hbegp_fit_options opt = HBEGP_FIT_OPTIONS_INIT;
+    opt.maxeval = maxeval;
+    FittedKernel fk;
+    fk.n_ = n; fk.d_ = d; fk.theta_.resize(p);
+    std::vector<double> ab(2 * (size_t)d), alo(2 * (size_t)d, warp_lo), ahi(2 * (size_t)d, warp_hi);
+    check(detail::Abi<A>::fit_warped(ctx.get(), x, y, row_variance, n, d, nu, theta0.data(), b.lo.data(), b.hi.data(), nullptr, alo.data(),
+                                     ahi.data(), starts.empty() ? nullptr : starts.data(), (int)(starts.size() / q), &opt, fk.theta_.data(),
+                                     ab.data(), &fk.lml_, &fk.h_));
+    return fk;
+  }
+  // the input warp a model from new_warped carries (hbegp_model_warp); an empty ab for every other model
+  Warp warp() const {
+    Warp w;
+    if (hbegp_model_warp(h_, nullptr) != 1) return w;
+    w.ab.resize(2 * (size_t)d_);
+    hbegp_model_warp(h_, w.ab.data());
+    return w;
   }
   // fit.rs:33-68
   static FittedKernel extend(const Context& ctx, const A* x, const A* y, int n, int d, double nu, const std::vector<double>& theta,

@@ -43,6 +43,10 @@ pub struct HbegpCtx {
 pub struct HbegpModel {
     _private: [u8; 0],
 }
+#[repr(C)]
+pub struct HbegpProblem {
+    _private: [u8; 0],
+}
 
 /// `hbegp_fit_options` (include/hbegp.h)
 #[repr(C)]
@@ -286,6 +290,34 @@ extern "C" {
     fn hbegp_model_get_f32(model: *mut HbegpModel, theta: *mut c_double, alpha: *mut c_float, kinv: *mut c_float) -> c_int;
     fn hbegp_model_retain(model: *mut HbegpModel);
     fn hbegp_model_release(model: *mut HbegpModel);
+    // input warping (include/hbegp.h; declared to keep the block in step with the header, the binding does not wrap them yet):
+    // ab = [a_1..a_d, b_1..b_d]; every output of hbegp_warp_apply may be null
+    pub fn hbegp_warp_apply(
+        ab: *const c_double, d: c_int, x: *const c_double, m: c_int, u: *mut c_double, du_dlna: *mut c_double, du_dlnb: *mut c_double,
+        du_dx: *mut c_double,
+    ) -> c_int;
+    pub fn hbegp_warp_invert(ab: *const c_double, d: c_int, u: *const c_double, m: c_int, x: *mut c_double) -> c_int;
+    pub fn hbegp_problem_eval_xgrad(
+        prob: *mut HbegpProblem, dev: c_int, slot: c_int, theta: *const c_double, lo: *const c_double, hi: *const c_double,
+        lml: *mut c_double, grad: *mut c_double, gx: *mut c_double,
+    ) -> c_int;
+    pub fn hbegp_problem_eval_warped(
+        prob: *mut HbegpProblem, dev: c_int, slot: c_int, theta: *const c_double, lo: *const c_double, hi: *const c_double,
+        ab: *const c_double, lml: *mut c_double, grad: *mut c_double,
+    ) -> c_int;
+    pub fn hbegp_fit_warped_f64(
+        ctx: *mut HbegpCtx, x: *const c_double, y: *const c_double, rv: *const c_double, n: c_int, d: c_int, nu: c_double,
+        theta0: *const c_double, lo: *const c_double, hi: *const c_double, ab0: *const c_double, ab_lo: *const c_double,
+        ab_hi: *const c_double, starts: *const c_double, n_restarts: c_int, opt: *const HbegpFitOptions, theta_best: *mut c_double,
+        ab_best: *mut c_double, lml_best: *mut c_double, model: *mut *mut HbegpModel,
+    ) -> c_int;
+    pub fn hbegp_fit_warped_f32(
+        ctx: *mut HbegpCtx, x: *const c_float, y: *const c_float, rv: *const c_double, n: c_int, d: c_int, nu: c_double,
+        theta0: *const c_double, lo: *const c_double, hi: *const c_double, ab0: *const c_double, ab_lo: *const c_double,
+        ab_hi: *const c_double, starts: *const c_double, n_restarts: c_int, opt: *const HbegpFitOptions, theta_best: *mut c_double,
+        ab_best: *mut c_double, lml_best: *mut c_double, model: *mut *mut HbegpModel,
+    ) -> c_int;
+    pub fn hbegp_model_warp(model: *const HbegpModel, ab: *mut c_double) -> c_int;
 }
 
 fn last_error() -> String {
